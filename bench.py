@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the hot path (BASELINE.json): ns/day of a ~100k-atom flexible TIP3P box
 under RESPA (near/far split + multiple-timescale inner loop) on N MI355X, plus the near-nonbonded
-kernel's roofline figure and a CPU baseline timed in the same run.
+kernel's roofline figure from the same timed steps.  `--full` adds what the headline does not need: the PME
+outer-force leg, a CPU baseline and BASELINE configs C2 / C5 as legs of their own.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+--dump-outputs DIR: after the timed steps, what a caller of the timed path receives from its last step -- the positions and
+velocities of every atom (dump_outputs) -- as DIR/<name>.npy in fp64.  The inputs are seeded and the kernels deterministic, so
+two builds run with the same arguments can be compared output for output.
 
 Workload: 32 768 flexible TIP3P waters (98 304 atoms, L = 9.94 nm) built by
 atomsmm_amd.testing.tip3p_box (seeded, synthetic); RESPASystem(rcutIn = 0.7 nm, rswitchIn = 0.5 nm,
@@ -141,6 +146,8 @@ def bench_c2(args, torch):
     elapsed = time.perf_counter() - t0
     launches, ms = eng.ctx.profile_read(fid)
     eng.ctx.profile_enable(False)
+    if args.dump_outputs:
+        dump_outputs(simulation, args.dump_outputs)
     st1 = eng.ctx.pair_stats(fid)
     pairs = eng.ctx.pair_count_within(fid, eng.x, rc) / 2
     t_k = ms * 1e-3 / max(launches, 1)
@@ -171,7 +178,7 @@ def bench_c2(args, torch):
                    'pairs_within_cutoff_counted': int(pairs), 'lanes_per_atom': st1['lanes_per_atom'], 'rlist_nm': st1['rlist'],
                    'list_kind': st1['list_kind'], 'kernel_revision': backend.kernel_revision()},
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # CPU leg: the oracle's OpenMP cell-list traversal of the same force at the final configuration (one evaluation = one step's
         # force work; kicks and moves are negligible next to it), all host threads OpenMP gives it
         try:
@@ -208,12 +215,30 @@ def stored_traffic(backend):
         return {}
 
 
+DUMP_MAX_ATOMS = 1 << 20       # --dump-outputs: 2 arrays x 3 x 8 B per atom -> at most 48 MB in all
+
+
+def dump_outputs(simulation, directory):
+    """--dump-outputs: the state a caller of the timed path receives after its last step, from Context.getState -- positions (nm)
+    and velocities (nm/ps) in the System's atom order, fp64, as positions.npy and velocities.npy (C3: 98 304 x 3 each, 4.7 MB).
+    A box of more than DUMP_MAX_ATOMS atoms is sampled: the same seeded set of atoms (rows in increasing order) in both files."""
+    state = simulation.context.getState(getPositions=True, getVelocities=True)
+    x = np.asarray(state.getPositions(asNumpy=True)._value, dtype=np.float64)
+    v = np.asarray(state.getVelocities(asNumpy=True)._value, dtype=np.float64)
+    if len(x) > DUMP_MAX_ATOMS:
+        rows = np.sort(np.random.default_rng(0).choice(len(x), DUMP_MAX_ATOMS, replace=False))
+        x, v = x[rows], v[rows]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, 'positions.npy'), x)
+    np.save(os.path.join(directory, 'velocities.npy'), v)
+
+
 def run_leg(config, steps, warmup, timeout_s=280):
     """Another BASELINE config (c2 / c5) as a short timed region of its own, in a child process (`bench.py --config ...`: a fresh
-    interpreter and context; the parent's GPU work is over and it only waits), condensed for the default line's `detail`: ns/day,
+    interpreter and context; the parent's GPU work is over and it only waits), condensed for the --full line's `detail`: ns/day,
     ms/step, the dominant kernel's roofline entry, the CPU leg where the config has one.  A failure costs the leg, not the line."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), '--config', config, '--steps', str(steps), '--warmup', str(warmup), '--no-legs']
+    cmd = [sys.executable, os.path.abspath(__file__), '--config', config, '--steps', str(steps), '--warmup', str(warmup), '--full', '--no-legs']
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s)
     except subprocess.TimeoutExpired:
@@ -411,14 +436,20 @@ def main():
     ap.add_argument('--outer-skin', type=float, default=None, help='dual Verlet list: buffer of the cell-built outer list in nm (default: single list)')
     ap.add_argument('--skin', type=float, default=None, help='Verlet buffer in nm (default: the library default, 0.1)')
     ap.add_argument('--option', action='append', default=[], help='name=value: a context option of the library (tuning; not for the headline)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline figure does not need: the PME outer-force leg (--pme-steps), the CPU baseline '
+                         '(--no-cpu-baseline) and, on the C3 line, BASELINE configs 2 and 5 as legs (--no-legs)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the positions and velocities after the last timed step to DIR/positions.npy, DIR/velocities.npy (fp64)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--no-relax', action='store_true')
     ap.add_argument('--verbose', action='store_true')
     ap.add_argument('--pme-steps', type=int, default=100,
-                    help='also time this many steps with the PME NonbondedForce as the outer force (what RESPASystem leaves in group 2 for a '
-                         'PME source, systems.py:74-75) and report them under detail.pme_outer; 0 skips it')
+                    help='with --full: also time this many steps with the PME NonbondedForce as the outer force (what RESPASystem leaves in '
+                         'group 2 for a PME source, systems.py:74-75) and report them under detail.pme_outer; 0 skips it')
     ap.add_argument('--no-legs', action='store_true',
-                    help='the default line also times BASELINE configs 2 and 5 (short regions, child processes) under detail.c2 / detail.c5; this skips them')
+                    help='with --full the C3 line also times BASELINE configs 2 and 5 (short regions, child processes) under detail.c2 / '
+                         'detail.c5; this skips them')
     ap.add_argument('--leg-steps', type=int, nargs=2, default=[2000, 60], metavar=('C2', 'C5'), help='timed steps of the two legs')
     ap.add_argument('--cpu-baseline-child', default=None, help=argparse.SUPPRESS)      # internal: cpu_baseline_in_child
     args = ap.parse_args()
@@ -509,6 +540,8 @@ def main():
     n_near, ms_near = eng.ctx.profile_read(near_id)
     n_dual, ms_dual = eng.ctx.profile_read(far_id)
     eng.ctx.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(simulation, args.dump_outputs)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device='cuda')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -532,7 +565,7 @@ def main():
     # the same box with the PME NonbondedForce as the outer force (what RESPASystem leaves in group 2 for a PME source,
     # systems.py:74-75; SURVEY 8d C3 ii): continued from the state the headline run ended in, its own short timed region
     pme_outer = None
-    if args.pme_steps > 0 and args.outer == 'damped' and args.config == 'c3' and world == 1:      # (a second context + communicator only on the 1-GPU line)
+    if args.full and args.pme_steps > 0 and args.outer == 'damped' and args.config == 'c3' and world == 1:      # (a second context + communicator only on the 1-GPU line)
         from atomsmm_amd import unit
         sim2, _ = build_simulation(args.nside, loops, dt_fs, 'pme', args.skin, args.outer_skin)
         sim2.context.setPositions(eng.x.cpu().numpy() * unit.nanometers)
@@ -692,9 +725,9 @@ def main():
                        'row_padding': padding or None, 'pme_outer': pme_outer,
                        'run_stats': {k: rs.get(k, 0) - rs0.get(k, 0) for k in rs} or None},
         }
-        if world == 1 and not args.no_cpu_baseline and args.outer == 'damped':
+        if args.full and world == 1 and not args.no_cpu_baseline and args.outer == 'damped':
             result['cpu_baseline'] = cpu_baseline_in_child(args.nside, eng.x.cpu().numpy(), eng.v.cpu().numpy())
-        if world == 1 and args.config == 'c3' and args.outer == 'damped' and args.nside == 32 and not args.no_legs:
+        if args.full and world == 1 and args.config == 'c3' and args.outer == 'damped' and args.nside == 32 and not args.no_legs:
             # BASELINE configs 2 and 5 on the same line: short timed regions after the headline's, each in a child
             # process; configs[1] = the 32k-atom Lennard-Jones fluid, configs[4] = the ~250k-atom solvated chain under AFED
             result['detail']['c2'] = run_leg('c2', args.leg_steps[0], 200)

@@ -30,5 +30,5 @@ for cfg in c2 c5; do
 done
 cp "$out/${tag}_traffic.json" profiles/${tag}_traffic.json      # bench.py quotes the traffic measured on this box
 cp "$(find "$out/${tag}_stats" -name '*kernel_stats.csv' | head -1)" "$out/${tag}_bench_kernel_stats.csv"
-python3 bench.py > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"
+python3 bench.py --full > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"
 cat "$out/${tag}_bench.json"
