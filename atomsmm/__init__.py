@@ -7,7 +7,7 @@ import atomsmm_amd as _impl
 from atomsmm_amd import *  # noqa: F401,F403
 from atomsmm_amd import __all__, __version__  # noqa: F401
 
-for _name in ('forces', 'integrators', 'propagators', 'systems', 'utils', 'computers'):
+for _name in ('forces', 'integrators', 'propagators', 'systems', 'utils', 'computers', 'reporters'):
     _module = getattr(_impl, _name, None) or __import__('atomsmm_amd.' + _name, fromlist=[_name])
     sys.modules[__name__ + '.' + _name] = _module
     globals()[_name] = _module

@@ -39,13 +39,17 @@ from .propagators import (MassiveNoseHooverPropagator, NoseHooverPropagator, Orn
                           NoseHooverLangevinPropagator)
 from .systems import AlchemicalRespaSystem, AlchemicalSystem, ComputingSystem, RESPASystem, SolvationSystem  # noqa: F401
 from .computers import PressureComputer  # noqa: F401
+from .reporters import CenterOfMassReporter  # noqa: F401
+from .reporters import CustomIntegratorReporter  # noqa: F401
+from .reporters import ExtendedStateDataReporter  # noqa: F401
+from .reporters import XYZReporter  # noqa: F401
 from .utils import InputError  # noqa: F401
 from .utils import countDegreesOfFreedom  # noqa: F401
 from .utils import evaluateForce  # noqa: F401
 from .utils import findNonbondedForce  # noqa: F401
 from .utils import hijackForce  # noqa: F401
 from .utils import splitPotentialEnergy  # noqa: F401
-from . import forces, integrators, propagators, systems, utils  # noqa: F401
+from . import forces, integrators, propagators, reporters, systems, utils  # noqa: F401
 
 __forces__ = ['DampedSmoothedForce', 'NonbondedExceptionsForce', 'NearExceptionForce', 'NearNonbondedForce',
               'FarNonbondedForce', 'SoftcoreLennardJonesForce', 'SoftcoreForce']
@@ -60,5 +64,6 @@ __propagators__ = ['ChainedPropagator', 'MultipleTimeScalePropagator', 'RespaPro
                    'NoseHooverChainPropagator', 'NoseHooverLangevinPropagator']
 __systems__ = ['RESPASystem', 'SolvationSystem', 'ComputingSystem', 'PressureComputer',
                'AlchemicalRespaSystem', 'AlchemicalSystem']
+__reporters__ = ['ExtendedStateDataReporter', 'XYZReporter', 'CenterOfMassReporter', 'CustomIntegratorReporter']
 __utils__ = ['countDegreesOfFreedom', 'evaluateForce', 'findNonbondedForce', 'hijackForce', 'splitPotentialEnergy']
-__all__ = __forces__ + __integrators__ + __propagators__ + __systems__ + __utils__
+__all__ = __forces__ + __integrators__ + __propagators__ + __reporters__ + __systems__ + __utils__

@@ -21,6 +21,7 @@ OP_ALLREDUCE = 11
 EXCHANGE_REDUCE, EXCHANGE_GATHER = 0, 1
 COMM_ID_BYTES = 128
 MAX_SLOTS, SLOT_X, SLOT_V = 64, 62, 63
+MAX_STATES = 64  # amm_pair_energy_states
 GROUP_ALL = 32   # pseudo-group of the force symbol `f` (all groups)
 KC = 138.935456   # forces.py:407
 ARITY = {BOND_HARMONIC: 2, ANGLE_HARMONIC: 3, BOND_LJC: 2, BOND_NEAR: 2, TORSION_PERIODIC: 4, BOND_EWALD_EXCL: 2,
@@ -38,6 +39,7 @@ EXPORTS = [
     'amm_pme_create', 'amm_pme_set_charges', 'amm_pme_set_sliced', 'amm_pair_set_lambda', 'amm_pair_set_lambda_dev', 'amm_expr_eval', 'amm_expr_eval_scalar', 'amm_expr_define', 'amm_expr_seed', 'amm_bath_define', 'amm_bath_define_nhl', 'amm_bath_define_sin', 'amm_iso_define', 'amm_pair_energy_derivative', 'amm_constraints_create', 'amm_pair_set_scale',
     'amm_comm_unique_id', 'amm_comm_init', 'amm_comm_destroy', 'amm_comm_allreduce', 'amm_comm_stats', 'amm_group_set_exchange', 'amm_bind_exchange', 'amm_exchange_finish',
     'amm_set_option', 'amm_positions_changed', 'amm_exchange_per', 'amm_run_stats', 'amm_run_ops_from', 'amm_exchange_pending',
+    'amm_pair_energy_states',
 ]
 
 
@@ -183,6 +185,7 @@ def lib():
         L.amm_expr_seed.argtypes = [vp, C.c_uint64]
         L.amm_constraints_create.argtypes = [vp, ip, dp, C.c_int32, C.c_double]
         L.amm_pair_energy_derivative.argtypes = [vp, C.c_int32, vp, vp]
+        L.amm_pair_energy_states.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp]
         L.amm_bath_define.argtypes = [vp, C.c_double, C.c_double, ip]
         L.amm_bath_define_nhl.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, ip]
         L.amm_bath_define_sin.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, ip]
@@ -305,6 +308,12 @@ class HipContext:
 
     def pair_energy_derivative(self, fid, pos, out):
         _chk(lib().amm_pair_energy_derivative(self.h, fid, _ptr(pos), _ptr(out)))
+
+    def pair_energy_states(self, fid, pos, lambdas, out):
+        """out[k] += energy of softcore force `fid` at lambda = lambdas[k] (device fp64 tensors of equal length, 1..MAX_STATES), energy
+        only; the force's own lambda stays as it is."""
+        assert lambdas.numel() == out.numel(), 'one output per lambda'
+        _chk(lib().amm_pair_energy_states(self.h, fid, _ptr(pos), _ptr(lambdas), int(lambdas.numel()), _ptr(out)))
 
     def pair_set_scale(self, fid, value):
         _chk(lib().amm_pair_set_scale(self.h, fid, float(value)))

@@ -385,6 +385,40 @@ int amm_pair_energy_derivative(amm_ctx *ctx, int32_t force_id, const double *d_p
     return rc;
 }
 
+int amm_pair_energy_states(amm_ctx *ctx, int32_t force_id, const double *d_pos, const double *d_lambdas, int32_t n_states, double *d_out) {
+    PairForce *pf = get_pair(ctx, force_id);
+    if (!pf) return 1;
+    if (n_states < 1 || n_states > AMM_MAX_STATES) {
+        amm_set_error("amm_pair_energy_states: need 1 <= n_states <= AMM_MAX_STATES (" + std::to_string(AMM_MAX_STATES) + ")");
+        return 1;
+    }
+    if (!d_pos || !d_lambdas || !d_out) {
+        amm_set_error("amm_pair_energy_states: null argument");
+        return 1;
+    }
+    if (pf->desc.family != AMM_SOFTCORE) {
+        amm_set_error("amm_pair_energy_states: only the softcore family depends on a global parameter");
+        return 1;
+    }
+    if (!(ctx->opt_positions_private && d_pos == ctx->d_x)) ctx->pos_epoch++;     // (as amm_pair_energy_derivative)
+    if (pf->small && ctx->opt_small_group && !pf->built && amm_small_group_supported(pf))
+        return amm_small_group_energy_states(ctx, pf, d_pos, d_lambdas, n_states, d_out);
+    // a force on the list path (both sets large): one energy evaluation per lambda, with lambda swapped into the launch constants and
+    // restored as amm_pair_energy_derivative does with its flag (the list path never reads a device lambda)
+    std::vector<double> lam(n_states);
+    AMM_HIP(hipMemcpyAsync(lam.data(), d_lambdas, sizeof(double) * n_states, hipMemcpyDeviceToHost, ctx->stream));
+    AMM_HIP(hipStreamSynchronize(ctx->stream));
+    if (!ctx->d_fscratch) AMM_HIP(hipMalloc(&ctx->d_fscratch, sizeof(double) * 3 * (size_t)ctx->n));
+    const double alpha = pf->pc.alpha;
+    int rc = 0;
+    for (int k = 0; k < n_states && rc == 0; ++k) {
+        pf->pc.alpha = lam[k];
+        rc = amm_pair_eval_impl(ctx, pf, d_pos, ctx->d_fscratch, 0, d_out + k);
+    }
+    pf->pc.alpha = alpha;
+    return rc;
+}
+
 static int share_list_pf(amm_ctx *ctx, PairForce *g, PairForce *h) {
     if (g == h || h->host || g->host || g->rnear_build > 0) {
         amm_set_error("amm_pair_share_list: invalid host/guest combination");
@@ -552,6 +586,13 @@ int amm_pair_set_params(amm_ctx *ctx, int32_t force_id, const double *h_q, const
         pf->sites_match = -1;
         for (auto &fo : ctx->forces)
             if (fo.type == 1 && fo.pair->host == pf) fo.pair->sites_match = -1;
+    }
+    // the sorted copies of the parameters that a launch wrote ahead of time (epilogues: pair.hip, cluster.hip) were made with the old
+    // ones: no later evaluation may take them for current, whichever force of the list (this one or a guest) they belong to
+    {
+        PairForce *L = pf->host ? pf->host : pf;
+        L->a_sorted_for = nullptr;
+        if (L->cl) L->cl->sorted_for = nullptr;
     }
     // dual evaluation needs bitwise equal parameters on guest and host: re-check after any change
     pf->dual_ok = pf->fuse_ok = -1;

@@ -371,6 +371,111 @@ __global__ void __launch_bounds__(256) k_small_group(SmallArgs A, PairConsts c_l
     }
 }
 
+// ---- energies at many values of lambda (amm_pair_energy_states): softcore family, energy only ----
+// The same walk as k_small_group (the small set in LDS, four lanes per atom of the large set, the candidates when the companion list
+// vouches for them) with nothing but energies: no force rows, no reactions, no candidate list kept.  A block takes one chunk of up to
+// AMM_STATES_CHUNK lambdas (the chunks are blocks of the grid: block b walks with b % nwalk and takes chunk b / nwalk), so a pair's
+// (r/sigma)^6 and switch are computed once for the chunk and its energies at the chunk's lambdas are added to registers: 64 states
+// hold eight accumulators, not sixty-four.  Each block leaves its chunk's partial sums in `spart`; the last block (ticket) adds them
+// in block order, as k_small_group's tail does -- the same sums on every launch.
+#define AMM_STATES_CHUNK 8
+__global__ void __launch_bounds__(256) k_small_group_states(SmallArgs A, PairConsts c, const double *lambdas, int K, int nwalk,
+                                                            double *spart, int *ticket, double *out) {
+    __shared__ double4 s_pos[AMM_SMALL_MAX];          // x, y, z, Kc q
+    __shared__ double2 s_lj[AMM_SMALL_MAX];
+    __shared__ double red[4][AMM_STATES_CHUNK];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, sub = lane & 3;
+    const int chunk = (int)blockIdx.x / nwalk, pb = (int)blockIdx.x - chunk * nwalk;
+    const int nchunks = (K + AMM_STATES_CHUNK - 1) / AMM_STATES_CHUNK;
+    // every atom, or the candidates of the companion list (read only: this launch keeps no list)
+    bool full = true;
+    int ncand = 0;
+    if (A.cand_on && A.cand_trust && A.lflags[AMM_FLAG_FAR] == 0 && (int)A.lcounters[0] == A.cstate[1]) {
+        full = false;
+        ncand = A.cstate[0];
+    }
+    const int walkers = full ? nwalk : max(1, min(nwalk, (ncand + 63) >> 6));
+    if (pb >= walkers) return;                        // (not counted by the ticket; its partials are not read)
+    double lam[AMM_STATES_CHUNK], acc[AMM_STATES_CHUNK];
+#pragma unroll
+    for (int s = 0; s < AMM_STATES_CHUNK; ++s) {
+        const int k = chunk * AMM_STATES_CHUNK + s;
+        lam[s] = k < K ? lambdas[k] : 0.0;            // (a padding lambda of 0: finite energies, never read)
+        acc[s] = 0.0;
+    }
+    for (int k = threadIdx.x; k < A.ns; k += 256) {
+        const int i = A.small[k];
+        s_pos[k] = make_double4(A.pos[3 * i], A.pos[3 * i + 1], A.pos[3 * i + 2], A.q[i]);
+        s_lj[k] = make_double2(A.hsig[i], A.seps2[i]);
+    }
+    __syncthreads();
+    const int walk_n = full ? A.j1 - A.j0 : ncand;
+    for (int itb = pb * 64; itb < walk_n; itb += walkers * 64) {
+        const int it = itb + (int)(threadIdx.x >> 2);
+        const bool in = it < walk_n;
+        const int t = min(it, walk_n - 1);
+        const int j = full ? A.j0 + t : A.cand[t];
+        const float code = in ? A.member[j] : 0.f;
+        const bool partner = in && code != 0.f && code != A.small_code;
+        if (__builtin_amdgcn_ballot_w64(partner) == 0ull) continue;       // wave-uniform
+        const double px = A.pos[3 * j], py = A.pos[3 * j + 1], pz = A.pos[3 * j + 2];
+        const double qj = c.Kc * A.q[j];
+        const double2 lj = make_double2(A.hsig[j], A.seps2[j]);
+        for (int kk = sub; kk < A.ns; kk += 4) {
+            const double4 pk = s_pos[kk];
+            const double dx = amm_min_image(px - pk.x, A.box.L[0], A.box.invL[0]);
+            const double dy = amm_min_image(py - pk.y, A.box.L[1], A.box.invL[1]);
+            const double dz = amm_min_image(pz - pk.z, A.box.L[2], A.box.invL[2]);
+            const double r2 = dx * dx + dy * dy + dz * dz;
+            if (!(partner && r2 < c.rc2)) continue;
+            const double2 lk = s_lj[kk];
+            bool member;
+            const double t6 = amm_softcore_t6(r2, qj * pk.w, lj.x + lk.x, member);
+            if (!member) continue;
+            const double r = r2 * amm_rsqrt(r2);
+            double S, dSdr;
+            amm_softcore_switch(c, r, S, dSdr);
+            const double eps4 = lj.y * lk.y;
+#pragma unroll
+            for (int s = 0; s < AMM_STATES_CHUNK; ++s) {
+                double x, ix;
+                const double V = amm_softcore_V(lam[s], eps4, t6, x, ix);
+                acc[s] += (S * V) * c.sign;           // (amm_pair_math: e = S V, times the sign)
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < AMM_STATES_CHUNK; ++s) {
+        double e = acc[s];
+        for (int off = 32; off > 0; off >>= 1) e += __shfl_xor(e, off);
+        if (lane == 0) red[w][s] = e;
+    }
+    __syncthreads();
+    if (threadIdx.x < AMM_STATES_CHUNK) {
+        const int s = threadIdx.x;
+        const double e = ((red[0][s] + red[1][s]) + red[2][s]) + red[3][s];
+        amm_st_l2((unsigned long long *)&spart[(size_t)blockIdx.x * AMM_STATES_CHUNK + s], (unsigned long long)__double_as_longlong(e));
+    }
+    if (!(full ? amm_last_block(ticket) : amm_last_of(ticket, walkers * nchunks))) return;
+    if (!full && threadIdx.x == 0) A.cstate[3] += 1;          // (counted with the force's candidate walks: amm_pair_get_stats)
+    // last block: state k's partials are those of the walking blocks of its chunk, added in block order
+    __shared__ double sh[256];
+    for (int k = 0; k < K; ++k) {
+        const int ck = k / AMM_STATES_CHUNK, sk = k - ck * AMM_STATES_CHUNK;
+        double sum = 0.0;
+        for (int b = threadIdx.x; b < walkers; b += 256)
+            sum += __longlong_as_double((long long)amm_ld_l2((const unsigned long long *)&spart[((size_t)ck * nwalk + b) * AMM_STATES_CHUNK + sk]));
+        sh[threadIdx.x] = sum;
+        __syncthreads();
+        for (int off = 128; off > 0; off >>= 1) {
+            if (threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) out[k] += sh[0];
+        __syncthreads();
+    }
+}
+
 struct SmallGroup {
     int ns = 0;
     float code = 0.f;
@@ -383,11 +488,16 @@ struct SmallGroup {
     double *d_fpair = nullptr;
     int *d_cand = nullptr, *d_cstate = nullptr;
     const void *companion = nullptr;       // the list the candidates were made against (another one: the list starts over)
+    // energies at many lambdas (k_small_group_states): [blocks][AMM_STATES_CHUNK] partial sums, their capacity, the launch's ticket
+    double *d_spart = nullptr;
+    size_t spart_cap = 0;
+    int *d_sticket = nullptr;
 };
 
 int amm_small_group_free(SmallGroup *sg) {
     if (!sg) return 0;
-    void *ptrs[] = {sg->d_small, sg->d_acc, sg->d_ticket, sg->d_epart, sg->d_overflow, sg->d_fpair, sg->d_cand, sg->d_cstate};
+    void *ptrs[] = {sg->d_small, sg->d_acc, sg->d_ticket, sg->d_epart, sg->d_overflow, sg->d_fpair, sg->d_cand, sg->d_cstate, sg->d_spart,
+                    sg->d_sticket};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     delete sg;
@@ -599,4 +709,67 @@ int amm_small_group_failed(SmallGroup *sg) {
     int flag = 0;
     if (hipMemcpy(&flag, sg->d_overflow, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return flag;
+}
+
+// amm_pair_energy_states on the list-free path: d_out[k] += E(d_lambdas[k]) at d_pos for this rank's block of atoms (the caller has
+// checked the family and 1 <= K <= AMM_MAX_STATES).  Reads the force's candidates when they serve these positions; changes nothing of
+// the force's state (lambda, its device binding, the candidate list) but the count of candidate walks (a statistic).
+int amm_small_group_energy_states(amm_ctx *ctx, PairForce *pf, const double *d_pos, const double *d_lambdas, int K, double *d_out) {
+    SmallGroup *sg = pf->small;
+    hipStream_t st = ctx->stream;
+    const int n = pf->n;
+    const int per = (n + ctx->world - 1) / ctx->world;
+    SmallArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.n = n;
+    A.j0 = std::min(n, ctx->rank * per);
+    A.j1 = std::min(n, A.j0 + per);
+    A.ns = sg->ns;
+    A.small = sg->d_small;
+    A.small_code = sg->code;
+    A.pos = d_pos;
+    A.q = pf->d_q;
+    A.hsig = pf->d_hsig;
+    A.seps2 = pf->d_seps2;
+    A.member = pf->d_member;
+    A.box = ctx->box;
+    if (ctx->opt_group_candidates && ctx->world == 1 && sg->d_cand) {
+        // (the companion an evaluation would take: its candidates serve only if they were made against it)
+        const ClusterList *cl = nullptr;
+        for (auto &fo : ctx->forces)
+            if (fo.type == 1 && fo.pair->cl && fo.pair->cl->built && fo.pair->last_kind >= 1 && !fo.pair->host) {
+                cl = fo.pair->cl;
+                break;
+            }
+        if (cl && sg->companion == (const void *)cl) {
+            A.cand_on = 1;
+            A.cand_trust = ((cl->pre_epoch == ctx->pos_epoch && cl->pre_pos == d_pos) || (cl->checked_epoch == ctx->pos_epoch && cl->checked_pos == d_pos)) ? 1 : 0;
+            A.lflags = cl->d_flags;
+            A.lcounters = cl->d_counters;
+            A.cand = sg->d_cand;
+            A.cstate = sg->d_cstate;
+        }
+    }
+    static int ncu_dev[64] = {0};
+    int &ncu = ncu_dev[ctx->device & 63];
+    if (!ncu) AMM_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    const int nwalk = std::max(1, std::min((A.j1 - A.j0 + 63) / 64, AMM_SG_BPC * std::max(ncu, 1)));
+    const int nchunks = (K + AMM_STATES_CHUNK - 1) / AMM_STATES_CHUNK;
+    const size_t need = (size_t)nwalk * nchunks * AMM_STATES_CHUNK;
+    if (need > sg->spart_cap) {
+        if (sg->d_spart) {
+            AMM_HIP(hipStreamSynchronize(st));          // (a launch in flight may still read the old buffer)
+            AMM_HIP(hipFree(sg->d_spart));
+        }
+        AMM_HIP(hipMalloc(&sg->d_spart, sizeof(double) * need));
+        sg->spart_cap = need;
+    }
+    if (!sg->d_sticket) {
+        AMM_HIP(hipMalloc(&sg->d_sticket, sizeof(int) * AMM_TICKET_INTS));
+        AMM_HIP(hipMemset(sg->d_sticket, 0, sizeof(int) * AMM_TICKET_INTS));
+    }
+    hipLaunchKernelGGL(k_small_group_states, dim3(nwalk * nchunks), dim3(256), 0, st, A, pf->pc, d_lambdas, K, nwalk, sg->d_spart,
+                       sg->d_sticket, d_out);
+    AMM_HIP(hipGetLastError());
+    return 0;
 }

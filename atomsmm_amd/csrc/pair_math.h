@@ -75,6 +75,35 @@ __device__ __forceinline__ void amm_erfc_exp(double x, const double *tab, double
     ec = ex * p;
 }
 
+// The softcore pair of SolvationSystem (systems.py:266-272) in three pieces, so that the multi-state energy kernel (group.hip:
+// k_small_group_states) evaluates ONE pair at many lambdas with the arithmetic of amm_pair_math:
+//   amm_softcore_t6     (r/sigma)^6; member: qq = code_i*code_j (Kc = 1) is 2 for a (set 1, set 2) pair of the interaction group
+//   amm_softcore_switch S(r) and dS/dr of the built-in switch (AMM_SWITCH)
+//   amm_softcore_V      V = 4 lambda eps (1-x)/x^2 with x = t6 + (1-lambda)/2; also returns x and 1/x
+__device__ __forceinline__ double amm_softcore_t6(double r2, double qq, double sig, bool &member) {
+    member = (qq == 2.0) && (sig > 0.0);
+    const double sg = member ? sig : 1.0;
+    const double isg2 = 1.0 / (sg * sg);
+    const double t2 = r2 * isg2;
+    return t2 * t2 * t2;
+}
+__device__ __forceinline__ void amm_softcore_switch(const PairConsts &c, double r, double &S, double &dSdr) {
+    S = 1.0;
+    dSdr = 0.0;
+    if ((c.flags & AMM_SWITCH) && r > c.rswitch) {
+        const double t = (r - c.rswitch) * c.inv_sw_dr;
+        S = amm_sw_S(t);
+        dSdr = amm_sw_dS(t) * c.inv_sw_dr;
+    }
+}
+__device__ __forceinline__ double amm_softcore_V(double lambda, double eps4, double t6, double &x, double &ix) {
+    x = t6 + 0.5 * (1.0 - lambda);
+    ix = 1.0 / x;
+    const double ix2 = ix * ix;
+    const double le = lambda * eps4;
+    return le * (1.0 - x) * ix2;
+}
+
 // GROUPED: interaction-group forces (AMM_GROUP_LJ / AMM_GROUP_Q) are separate instantiations, so that the common path
 // carries no per-pair flag tests or selects
 template <int FAM, int CMODE, bool GUARD, bool EN, bool GROUPED = false>
@@ -158,22 +187,16 @@ __device__ __forceinline__ void amm_pair_math(const PairConsts &c, double r2, do
         fr = S * mdV_r - dSdr * V * rinv;
         if (EN) e = S * V;
     } else if (FAM == AMM_SOFTCORE) {
-        // qq = code_i*code_j (Kc = 1): 2 for a (set 1, set 2) pair of the interaction group; lambda travels in alpha
-        const bool member = (qq == 2.0) && (sig > 0.0);
-        const double sg = member ? sig : 1.0;
-        const double isg2 = 1.0 / (sg * sg);
-        const double t2 = r2 * isg2, t6 = t2 * t2 * t2;                 // (r/sigma)^6
-        const double x = t6 + 0.5 * (1.0 - c.alpha);
-        const double ix = 1.0 / x, ix2 = ix * ix;
+        // lambda travels in alpha
+        bool member;
+        const double t6 = amm_softcore_t6(r2, qq, sig, member);
+        double x, ix;
+        const double V = amm_softcore_V(c.alpha, eps4, t6, x, ix);
+        const double ix2 = ix * ix;
         const double le = c.alpha * eps4;                               // 4 lambda eps
-        const double V = le * (1.0 - x) * ix2;
         const double mdV_r = 6.0 * le * (2.0 - x) * ix2 * ix * t6 * rinv2;      // (-dV/dr)/r
-        double S = 1.0, dSdr = 0.0;
-        if ((c.flags & AMM_SWITCH) && r > c.rswitch) {
-            const double t = (r - c.rswitch) * c.inv_sw_dr;
-            S = amm_sw_S(t);
-            dSdr = amm_sw_dS(t) * c.inv_sw_dr;
-        }
+        double S, dSdr;
+        amm_softcore_switch(c, r, S, dSdr);
         fr = member ? S * mdV_r - dSdr * V * rinv : 0.0;
         if (EN) {
             // AMM_DERIV_LAMBDA: the "energy" output is dE/dlambda of the pair (deriv(energy, lambda), integrators.py:735):

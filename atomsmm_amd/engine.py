@@ -338,6 +338,8 @@ class Engine:
         self._scalar_code, self._scalar_consts = [], []      # assignments to device scalars not yet launched (one launch per batch)
         self._lrc_on_device = {}    # (pair force, lambda's scalar) -> the correction's lambda-derivative there
         self.n_scalar_evals = self.n_scalar_launches = self.n_settles = 0     # (tests / bench: global expressions evaluated on the device, blocking reads of the scalars)
+        self.n_state_fallbacks = 0  # energies_at_states calls that took the reference loop for some force
+        self.state_paths = dict(once=0, states=0, quadratic=0, loop=0)      # ... and the forces each of its paths served
         self.device_globals = True  # nonlinear uses of deferred globals are evaluated on the device (amm_expr_eval_scalar) instead of waited for
         self._valid = {}
         self._interpreted = None    # None: undecided; True: general (host-walked) step programs
@@ -654,6 +656,9 @@ class Engine:
                 return True
             entry.update = update
             entry.depends = set(lam)
+            # offsets that touch the charges only: the energy is a quadratic in them (energies_at_states interpolates; energy_derivative
+            # keeps its small central step for this force)
+            entry.charge_offsets_in = {nm for k, nm in enumerate(names) if not np.any(scales[k][:, 1:])}
 
     def _translate_alchemical_pair(self, force, entry, d, outer=None, outer_depends=()):
         """Pair forces of AlchemicalRespaSystem (systems.py:628-772): force-switched potentials without the constant
@@ -965,6 +970,8 @@ class Engine:
                 return True
             entry.update = update
             entry.depends = set(lam)
+            # offsets on the charge product only: the energy is linear in them (energies_at_states, as for the pair forces above)
+            entry.charge_offsets_in = {nm for k, nm in enumerate(names) if not np.any(scales[k][:, 1:])}
 
     # ------------------------------------------------------------------------------- state
     def _invalidate_forces(self):
@@ -2007,6 +2014,111 @@ class Engine:
             self._invalidate_forces()
             total += (values[0] - values[1]) / (here + h - lo)
         return total
+
+    def energies_at_states(self, names, rows):
+        """Potential energy at K states of global parameters for the current positions: rows[k][i] is the value of names[i] in state k
+        (ExtendedStateDataReporter's globalParameterStates, ExpandedEnsembleReporter).  The same numbers as setting each state in
+        turn, getState(getEnergy=True) and restoring -- without the set / evaluate / restore round trips where the forces allow:
+
+        * a force that depends on none of the varied parameters is evaluated once;
+        * a softcore pair force whose only varied parameter is its lambda: ONE launch at all K lambdas (amm_pair_energy_states), plus
+          its long-range correction at each of them;
+        * forces that depend on one varied parameter in which their energy is a quadratic (charge offsets: `lambda_coul`) are
+          evaluated at three of its values and interpolated -- exact up to rounding;
+        * anything else takes the reference loop (counted in `n_state_fallbacks`).
+
+        Leaves no trace for the first two kinds: parameters, lambda bindings, valid force buffers and compiled programs stay as they
+        are.  The other two change parameters and restore them as energy_derivative does."""
+        names = list(names)
+        rows = np.asarray(rows, dtype=np.float64).reshape(-1, len(names))
+        K = len(rows)
+        for name in names:
+            if name not in self.parameters:
+                raise mm.OpenMMException('energies_at_states: no such Context parameter: ' + name)
+        if any(isinstance(self.parameters[name], X.Deferred) for name in names):
+            integ = self.integrator
+            self._settle([integ._gvalues] if isinstance(integ, mm.CustomIntegrator) else [])     # (a lambda still on the device)
+        here = {name: self.parameters[name] for name in names}
+        varied = {name for i, name in enumerate(names) if np.any(rows[:, i] != here[name])}
+        column = {name: rows[:, i] for i, name in enumerate(names)}
+
+        def state(k, base=None):
+            trial = dict(self.parameters if base is None else base)
+            trial.update({name: float(column[name][k]) for name in varied})
+            return trial
+
+        fixed, soft, quadratic, loop = [], [], {}, []
+        for entry in self.entries:
+            hit = getattr(entry, 'depends', set()) & varied
+            sc = entry.softcore
+            if not hit:
+                fixed.append(entry)
+            elif sc is not None and hit == {sc['lambda_name']} and hasattr(self.ctx, 'pair_energy_states'):
+                soft.append(entry)
+            elif len(hit) == 1 and next(iter(hit)) in (getattr(entry, 'quadratic_in', None) or set()) | getattr(entry, 'charge_offsets_in', set()):
+                quadratic.setdefault(next(iter(hit)), []).append(entry)
+            else:
+                loop.append(entry)
+        for path, entries in (('once', fixed), ('states', soft), ('quadratic', [e for g in quadratic.values() for e in g]), ('loop', loop)):
+            self.state_paths[path] += len(entries)
+        for entry in [e for group in quadratic.values() for e in group] + loop:
+            if entry.update is None:
+                raise NotImplementedError('energies_at_states: a force that depends on a varied parameter cannot be re-parameterised')
+        out = np.zeros(K)
+        if soft:                        # (first: the evaluations below may leave the candidate list of the force behind them)
+            torch = self.torch
+            dev = self.x.device
+            pair = torch.zeros(K, dtype=torch.float64, device=dev)
+            for entry in soft:
+                sc = entry.softcore
+                lam = column[sc['lambda_name']]
+                for k0 in range(0, K, B.MAX_STATES):
+                    k1 = min(K, k0 + B.MAX_STATES)
+                    self.ctx.pair_energy_states(sc['pid'], self.x, torch.as_tensor(lam[k0:k1], dtype=torch.float64, device=dev),
+                                                pair[k0:k1])
+                out += np.array([sc['constant'](state(k)) for k in range(K)])
+            self._check()
+            if self._coll:
+                self._allreduce(pair)
+            out += pair.cpu().numpy()
+        if fixed:
+            out += self._energy_of(fixed)
+        if quadratic or loop:
+            rebuilt = []
+
+            def apply(trial, entries, names_):
+                for entry in entries:
+                    result = entry.update(trial, names_)
+                    rebuilt.append(bool(result) and result != 'values')
+            for name, entries in quadratic.items():
+                values = column[name]
+                distinct = np.unique(values)
+                if len(distinct) <= 3:
+                    points = [float(p) for p in distinct]
+                else:                           # (the ends and the middle of the range: a well-conditioned interpolation)
+                    points = [float(distinct[0]), 0.5 * float(distinct[0] + distinct[-1]), float(distinct[-1])]
+                energies = []
+                for p in points:
+                    apply(dict(self.parameters, **{name: p}), entries, {name})
+                    energies.append(self._energy_of(entries))
+                for k, v in enumerate(values):
+                    basis = [np.prod([(v - q) / (p - q) for q in points if q != p]) for p in points]
+                    out[k] += sum(b * e for b, e in zip(basis, energies))
+                apply(self.parameters, entries, {name})
+            if loop:
+                self.n_state_fallbacks += 1
+                names_ = varied & set().union(*(e.depends for e in loop))
+                for k in range(K):
+                    apply(state(k), loop, names_)
+                    out[k] += self._energy_of(loop)
+                apply(self.parameters, loop, names_)
+            if any(rebuilt):
+                self._forget_groups()
+                self._programs.clear()
+                self._emit_memo.clear()
+                self._segment_memo.clear()
+            self._invalidate_forces()
+        return out
 
     def _deriv_deferred(self, what, name, settle):
         """deriv(energy, name) of a host-walked program without waiting for the GPU: the softcore pair kernel in derivative

@@ -527,7 +527,9 @@ class Simulation:
 class StateDataReporter:
     """app.StateDataReporter(file, reportInterval, step=..., time=..., potentialEnergy=..., kineticEnergy=..., totalEnergy=...,
     temperature=..., volume=..., density=..., speed=..., separator=','): the columns of OpenMM's reporter that a script of
-    the reference typically asks for, written as separated text (units: ps, kJ/mol, K, nm^3, g/mL, ns/day)."""
+    the reference typically asks for, written as separated text (units: ps, kJ/mol, K, nm^3, g/mL, ns/day).  As in OpenMM, a
+    subclass adds columns through _constructHeaders() / _constructReportValues(simulation, state) and asks for more of the State
+    through _needsPositions / _needsVelocities / _needsForces (atomsmm_amd.reporters.ExtendedStateDataReporter)."""
 
     def __init__(self, file, reportInterval, step=False, time=False, potentialEnergy=False, kineticEnergy=False,
                  totalEnergy=False, temperature=False, volume=False, density=False, speed=False, separator=',', **ignored):
@@ -539,22 +541,29 @@ class StateDataReporter:
                                                ('Density (g/mL)', density), ('Speed (ns/day)', speed)) if on]
         self._separator = separator
         self._started = None
+        self._speed, self._elapsedTime, self._remainingTime = bool(speed), False, False     # (OpenMM's trailing columns: speed only here)
+        self._needsPositions = self._needsVelocities = self._needsForces = False
+        self._needEnergy = True
 
     def describeNextReport(self, simulation):
         steps = self._interval - simulation.currentStep % self._interval
-        return (steps, False, False, False, True)
+        return (steps, self._needsPositions, self._needsVelocities, self._needsForces, self._needEnergy)
 
-    def report(self, simulation, state):
+    def _constructHeaders(self):
+        return list(self._columns)
+
+    def _initializeConstants(self, simulation, state):
         import time as _time
         system = simulation.system
-        if self._started is None:
-            print('#"' + ('"' + self._separator + '"').join(self._columns) + '"', file=self._out)
-            self._started = (_time.time(), state.getTime().value_in_unit(_unit.picoseconds))
-            masses = [system.getParticleMass(i).value_in_unit(_unit.dalton) for i in range(system.getNumParticles())]
-            self._mass = sum(masses)
-            self._dof = 3 * sum(1 for m in masses if m > 0) - system.getNumConstraints()
-            if any(type(force).__name__ == 'CMMotionRemover' for force in system.getForces()):
-                self._dof -= 3
+        self._started = (_time.time(), state.getTime().value_in_unit(_unit.picoseconds))
+        masses = [system.getParticleMass(i).value_in_unit(_unit.dalton) for i in range(system.getNumParticles())]
+        self._mass = sum(masses)
+        self._dof = 3 * sum(1 for m in masses if m > 0) - system.getNumConstraints()
+        if any(type(force).__name__ == 'CMMotionRemover' for force in system.getForces()):
+            self._dof -= 3
+
+    def _constructReportValues(self, simulation, state):
+        import time as _time
         pe = state.getPotentialEnergy().value_in_unit(_unit.kilojoules_per_mole)
         ke = state.getKineticEnergy().value_in_unit(_unit.kilojoules_per_mole)
         box = state.getPeriodicBoxVectors()
@@ -566,6 +575,14 @@ class StateDataReporter:
                   'Temperature (K)': 2.0 * ke / (self._dof * 8.3144626e-3),
                   'Box Volume (nm^3)': volume, 'Density (g/mL)': self._mass / volume / 602.214076,
                   'Speed (ns/day)': (t_ps - self._started[1]) * 86.4 / elapsed if elapsed > 0 else 0.0}
-        print(self._separator.join(str(values[name]) for name in self._columns), file=self._out)
+        return [values[name] for name in self._columns]
+
+    def report(self, simulation, state):
+        if self._started is None:
+            headers = self._constructHeaders()
+            print('#"' + ('"' + self._separator + '"').join(headers) + '"', file=self._out)
+            self._initializeConstants(simulation, state)
+        values = self._constructReportValues(simulation, state)
+        print(self._separator.join(str(v) for v in values), file=self._out)
         if hasattr(self._out, 'flush'):
             self._out.flush()

@@ -196,6 +196,12 @@ int amm_pair_set_scale(amm_ctx *ctx, int32_t force_id, double scale);
 /* deriv(energy, lambda) of a softcore pair force (addEnergyParameterDerivative, systems.py:712-718; used by the AFED
  * kicks, integrators.py:735-737): *d_out (device) += sum over pairs of dE/dlambda at d_pos. */
 int amm_pair_energy_derivative(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *d_out);
+/* Energies of a softcore pair force at n_states values of its lambda in one pass over its pairs: d_out[k] += E(d_lambdas[k]) at d_pos.
+ * Energy only (no forces are written).  The force's own lambda -- host value or amm_pair_set_lambda_dev binding -- is neither read
+ * nor changed.  1 <= n_states <= AMM_MAX_STATES (64).  A force with a small set takes one launch (csrc/group.hip); one on the list
+ * path takes one energy evaluation per lambda.  Multi-rank: each rank adds its block's share (sum d_out over the ranks). */
+#define AMM_MAX_STATES 64
+int amm_pair_energy_states(amm_ctx *ctx, int32_t force_id, const double *d_pos, const double *d_lambdas, int32_t n_states, double *d_out);
 
 int amm_bonded_create(amm_ctx *ctx, int32_t *force_id);
 int amm_bonded_add_terms(amm_ctx *ctx, int32_t force_id, int32_t kind, const int32_t *h_idx,
