@@ -37,6 +37,10 @@ from .propagators import (MassiveNoseHooverPropagator, NoseHooverPropagator, Orn
                           GenericBoostPropagator, GenericScalingPropagator, MassiveIsokineticPropagator,
                           SIN_R_Propagator, MassiveGeneralizedGaussianMomentPropagator, NoseHooverChainPropagator,
                           NoseHooverLangevinPropagator)
+from .propagators import (RegulatedTranslationPropagator, RegulatedBoostPropagator,  # noqa: F401
+                          RegulatedMassiveNoseHooverLangevinPropagator, TwiceRegulatedMassiveNoseHooverLangevinPropagator,
+                          RegulatedAtomicNoseHooverLangevinPropagator, TwiceRegulatedAtomicNoseHooverLangevinPropagator,
+                          TwiceRegulatedGlobalNoseHooverLangevinPropagator)
 from .systems import AlchemicalRespaSystem, AlchemicalSystem, ComputingSystem, RESPASystem, SolvationSystem  # noqa: F401
 from .computers import PressureComputer  # noqa: F401
 from .reporters import CenterOfMassReporter  # noqa: F401
@@ -61,7 +65,10 @@ __propagators__ = ['ChainedPropagator', 'MultipleTimeScalePropagator', 'RespaPro
                    'VelocityRescalingPropagator', 'NoseHooverPropagator', 'MassiveNoseHooverPropagator',
                    'OrnsteinUhlenbeckPropagator', 'GenericBoostPropagator', 'GenericScalingPropagator',
                    'MassiveIsokineticPropagator', 'SIN_R_Propagator', 'MassiveGeneralizedGaussianMomentPropagator',
-                   'NoseHooverChainPropagator', 'NoseHooverLangevinPropagator']
+                   'NoseHooverChainPropagator', 'NoseHooverLangevinPropagator',
+                   'RegulatedTranslationPropagator', 'RegulatedBoostPropagator', 'RegulatedMassiveNoseHooverLangevinPropagator',
+                   'TwiceRegulatedMassiveNoseHooverLangevinPropagator', 'RegulatedAtomicNoseHooverLangevinPropagator',
+                   'TwiceRegulatedAtomicNoseHooverLangevinPropagator', 'TwiceRegulatedGlobalNoseHooverLangevinPropagator']
 __systems__ = ['RESPASystem', 'SolvationSystem', 'ComputingSystem', 'PressureComputer',
                'AlchemicalRespaSystem', 'AlchemicalSystem']
 __reporters__ = ['ExtendedStateDataReporter', 'XYZReporter', 'CenterOfMassReporter', 'CustomIntegratorReporter']

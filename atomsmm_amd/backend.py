@@ -36,7 +36,7 @@ EXPORTS = [
     'amm_move', 'amm_copy', 'amm_mvv', 'amm_bind_state', 'amm_bind_buffer', 'amm_group_define', 'amm_run_ops',
     'amm_set_fuse_inner', 'amm_set_outer_skin',
     'amm_pair_get_stats', 'amm_profile_enable', 'amm_profile_read', 'amm_pair_count_within', 'amm_pair_row_padding', 'amm_kernel_revision',
-    'amm_pme_create', 'amm_pme_set_charges', 'amm_pme_set_sliced', 'amm_pair_set_lambda', 'amm_pair_set_lambda_dev', 'amm_expr_eval', 'amm_expr_eval_scalar', 'amm_expr_define', 'amm_expr_seed', 'amm_bath_define', 'amm_bath_define_nhl', 'amm_bath_define_sin', 'amm_iso_define', 'amm_pair_energy_derivative', 'amm_constraints_create', 'amm_pair_set_scale',
+    'amm_pme_create', 'amm_pme_set_charges', 'amm_pme_set_sliced', 'amm_pair_set_lambda', 'amm_pair_set_lambda_dev', 'amm_expr_eval', 'amm_expr_eval_scalar', 'amm_expr_define', 'amm_expr_seed', 'amm_bath_define', 'amm_bath_define_nhl', 'amm_bath_define_sin', 'amm_iso_define', 'amm_regulated_define', 'amm_bath_define_regulated', 'amm_pair_energy_derivative', 'amm_constraints_create', 'amm_pair_set_scale',
     'amm_comm_unique_id', 'amm_comm_init', 'amm_comm_destroy', 'amm_comm_allreduce', 'amm_comm_stats', 'amm_group_set_exchange', 'amm_bind_exchange', 'amm_exchange_finish',
     'amm_set_option', 'amm_positions_changed', 'amm_exchange_per', 'amm_run_stats', 'amm_run_ops_from', 'amm_exchange_pending',
     'amm_pair_energy_states',
@@ -190,6 +190,8 @@ def lib():
         L.amm_bath_define_nhl.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, ip]
         L.amm_bath_define_sin.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, ip]
         L.amm_iso_define.argtypes = [vp, C.c_int32, C.c_double, C.c_double, C.c_int32]
+        L.amm_regulated_define.argtypes = [vp, C.c_int32, C.c_double, C.c_double]
+        L.amm_bath_define_regulated.argtypes = [vp, C.c_int32, C.c_int32] + [C.c_double] * 8 + [C.c_int32, ip]
         L.amm_set_option.argtypes = [vp, C.c_char_p, C.c_double]
         L.amm_positions_changed.argtypes = [vp]
         L.amm_exchange_per.argtypes = [vp, ip]
@@ -439,6 +441,17 @@ class HipContext:
 
     def iso_define(self, on, LkT=0.0, Q1=0.0, slot_v1=-1):
         _chk(lib().amm_iso_define(self.h, int(bool(on)), float(LkT), float(Q1), int(slot_v1)))
+
+    def regulated_define(self, on, alpha=1.0, an_kT=0.0):
+        """Regulated mode: every MOVE op is x <- x + c tanh(alpha v/c) coef with c = sqrt(an_kT/m)."""
+        _chk(lib().amm_regulated_define(self.h, int(bool(on)), float(alpha), float(an_kT)))
+
+    def bath_define_regulated(self, kind, split, h, z, kT, Q, omega, friction, alpha, an, slot_v_eta):
+        """A regulated Nose-Hoover-Langevin bath block (kind 3..6, include/atomsmm_hip.h) as one BATH op."""
+        bid = C.c_int32(-1)
+        _chk(lib().amm_bath_define_regulated(self.h, int(kind), int(bool(split)), float(h), float(z), float(kT), float(Q), float(omega),
+                                             float(friction), float(alpha), float(an), int(slot_v_eta), C.byref(bid)))
+        return bid.value
 
     def expr_seed(self, seed):
         _chk(lib().amm_expr_seed(self.h, int(seed) & (2 ** 64 - 1)))

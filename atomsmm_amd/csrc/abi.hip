@@ -875,6 +875,44 @@ int amm_bath_define_sin(amm_ctx *ctx, double h, double z, double kT, double Q2, 
     return 0;
 }
 
+int amm_bath_define_regulated(amm_ctx *ctx, int32_t kind, int32_t split, double h, double z, double kT, double Q, double omega,
+                              double friction, double alpha, double an, int32_t slot_v_eta, int32_t *bath_id) {
+    if (!ctx || !bath_id || kind < 3 || kind > 6 || !(z >= 0.0 && z <= 1.0) || !(kT > 0.0) || !(Q > 0.0) || !(omega >= 0.0) ||
+        !(friction > 0.0) || !(alpha > 0.0) || !(an > 0.0) || slot_v_eta < 0 || slot_v_eta >= AMM_SLOT_X) {
+        amm_set_error("amm_bath_define_regulated: need kind 3..6, 0 <= z <= 1, kT > 0, Q > 0, omega >= 0, friction > 0, alpha > 0, "
+                      "an > 0 and a per-DOF buffer slot");
+        return 1;
+    }
+    BathDef b;
+    b.kind = kind;
+    b.split = split != 0;
+    b.h = h;
+    b.z = z;
+    b.kT = kT;
+    b.Q = Q;
+    b.omega = omega;
+    b.friction = friction;
+    b.alpha = alpha;
+    b.an = an;
+    const double n = an / alpha;
+    b.kfac = (n + 1.0) / (alpha * n);
+    b.slot = slot_v_eta;
+    ctx->baths.push_back(b);
+    *bath_id = (int32_t)ctx->baths.size() - 1;
+    return 0;
+}
+
+int amm_regulated_define(amm_ctx *ctx, int32_t on, double alpha, double an_kT) {
+    if (!ctx || (on && !(alpha > 0.0 && an_kT > 0.0))) {
+        amm_set_error("amm_regulated_define: need alpha > 0 and an_kT > 0");
+        return 1;
+    }
+    ctx->reg.on = on != 0;
+    ctx->reg.alpha = alpha;
+    ctx->reg.an_kT = an_kT;
+    return 0;
+}
+
 int amm_iso_define(amm_ctx *ctx, int32_t on, double LkT, double Q1, int32_t slot_v1) {
     if (!ctx || (on && (!(LkT > 0.0) || !(Q1 > 0.0) || slot_v1 < 0 || slot_v1 >= AMM_SLOT_X))) {
         amm_set_error("amm_iso_define: need LkT > 0, Q1 > 0 and a per-DOF buffer slot");
@@ -1116,7 +1154,8 @@ int amm_run_ops_from(amm_ctx *ctx, const amm_op *ops, int32_t n_ops, int32_t rep
         return 1;
     };
     auto plan_epilogue = [&](int after, int rep, EpiPlan &P, int &q_resume, bool &wraps) -> bool {
-        if (!ctx->fuse_inner || !ctx->opt_fuse_epilogue || ctx->iso.on || swapped || f0_slot >= 0) return false;
+        // (regulated mode: the epilogue's moves are plain ones -- not planned, the ops run on the paths that know the mode)
+        if (!ctx->fuse_inner || !ctx->opt_fuse_epilogue || ctx->iso.on || ctx->reg.on || swapped || f0_slot >= 0) return false;
         std::vector<amm_op> kicks;
         int j = after;
         wraps = false;
@@ -1194,7 +1233,7 @@ int amm_run_ops_from(amm_ctx *ctx, const amm_op *ops, int32_t n_ops, int32_t rep
     // ... and for per-atom rows (pair.hip: AtomEpiArgs): `[KICK ...] [; MOVE]` behind the EVAL of a group that is one pair force -- a
     // velocity-Verlet step's closing half kick and, across the end of the repetition, the opening half kick + move of the next
     auto plan_atoms = [&](int after, int rep, EpiPlan &P, int &q_resume, bool &wraps) -> bool {
-        if (!ctx->fuse_inner || !ctx->opt_fuse_epilogue || ctx->iso.on || ctx->world != 1 || swapped || f0_slot >= 0) return false;
+        if (!ctx->fuse_inner || !ctx->opt_fuse_epilogue || ctx->iso.on || ctx->reg.on || ctx->world != 1 || swapped || f0_slot >= 0) return false;
         std::vector<amm_op> kicks;
         int j = after;
         wraps = false;
@@ -1361,9 +1400,10 @@ int amm_run_ops_from(amm_ctx *ctx, const amm_op *ops, int32_t n_ops, int32_t rep
             // fused inner RESPA iteration: KICK(c1, fg) ; MOVE(d) ; EVAL(g) ; KICK(c2, fg) with g = one bond-list set
             // (kicks deferred from the previous repetition must not be overtaken by this block's move: deferral requires
             // f0_slot < 0, i.e. that this block never matched -- flushed here all the same, so that the order does not rest on that)
-            if (!deferred.empty() && ctx->fuse_inner && !ctx->iso.on && op.op == AMM_OP_KICK && op.b < 0 && k + 3 < n_ops &&
+            // (regulated mode: k_fused_inner predicts the partners' positions with plain moves -- not taken)
+            if (!deferred.empty() && ctx->fuse_inner && !ctx->iso.on && !ctx->reg.on && op.op == AMM_OP_KICK && op.b < 0 && k + 3 < n_ops &&
                 ops[k + 1].op == AMM_OP_MOVE && ops[k + 2].op == AMM_OP_EVAL && flush_deferred()) return 1;
-            if (ctx->fuse_inner && !ctx->iso.on && op.op == AMM_OP_KICK && op.b < 0 && k + 3 < n_ops && ops[k + 1].op == AMM_OP_MOVE &&
+            if (ctx->fuse_inner && !ctx->iso.on && !ctx->reg.on && op.op == AMM_OP_KICK && op.b < 0 && k + 3 < n_ops && ops[k + 1].op == AMM_OP_MOVE &&
                 ops[k + 2].op == AMM_OP_EVAL && ops[k + 3].op == AMM_OP_KICK && ops[k + 3].b < 0 && ops[k + 3].a == op.a &&
                 ops[k + 2].a >= 0 && ops[k + 2].a < AMM_MAX_GROUPS) {
                 GroupDef &g = ctx->groups[ops[k + 2].a];
@@ -1469,7 +1509,8 @@ int amm_run_ops_from(amm_ctx *ctx, const amm_op *ops, int32_t n_ops, int32_t rep
             // which group.hip evaluates without a list and which writes EVERY row]: the pair force goes first, the terms are
             // evaluated, and the launch that gathers their forces also applies the kicks and the move that follow -- an inner RESPA
             // iteration of a system that is not pure water (config C5: chain + solute + waters) is then 3 launches, not 8.
-            if (ctx->fuse_inner && !ctx->iso.on && op.op == AMM_OP_EVAL && op.a >= 0 && op.a < AMM_MAX_GROUPS && ctx->groups[op.a].slot >= 0 &&
+            // (regulated mode: the gather launch's move is a plain one -- not taken)
+            if (ctx->fuse_inner && !ctx->iso.on && !ctx->reg.on && op.op == AMM_OP_EVAL && op.a >= 0 && op.a < AMM_MAX_GROUPS && ctx->groups[op.a].slot >= 0 &&
                 !ctx->groups[op.a].exchange && k + 1 < n_ops && ops[k + 1].op == AMM_OP_KICK) {
                 GroupDef &g = ctx->groups[op.a];
                 BondedSet *bs = nullptr;

@@ -242,11 +242,26 @@ struct ExprDef {
 // kind 2 (stochastic-isokinetic, SIN_R_Integrator with L = 1: propagators.py:276-355, 1045-1105): v1 <- v1 exp(-h v2) ;
 // isokinetic rescale of (v, v1) ; v2 <- z v2 + sqrt(kT (1 - z^2)/Q2) gaussian + (Q1 v1^2 - kT)(1 - z)/(Q2 friction) ;
 // v1 <- v1 exp(-h v2) ; rescale -- thermostat velocities v1 in the context's isokinetic slot, v2 in `slot`.
+// kinds 3..6 (regulated Nose-Hoover-Langevin, propagators.py:1598-2007): 3 massive, 4 twice-regulated massive, 5 atomic, 6
+// twice-regulated atomic -- [boost of w ;] scaling of v ; Ornstein-Uhlenbeck step of w ; scaling of v [; boost of w] (`split`: the
+// boosts are there and the OU step has no drift), w in `slot`; the atomic kinds keep one w per atom in all three components.
+// amm_reg_bath_step (expr_vm.h) has the arithmetic.
 struct BathDef {
     double z, kT;
-    int kind = 0;                  // 0 Ornstein-Uhlenbeck, 1 Nose-Hoover-Langevin, 2 stochastic-isokinetic
+    int kind = 0;                  // 0 Ornstein-Uhlenbeck, 1 Nose-Hoover-Langevin, 2 stochastic-isokinetic, 3..6 regulated
     double h = 0, Q = 0, friction = 0;
     int slot = -1;
+    int split = 0;                 // regulated kinds: boosts of w around the block, OU step without drift
+    double omega = 0, alpha = 1, an = 1;   // regulated kinds: noise amplitude, alpha_n, alpha_n n
+    double kfac = 1;               // twice-regulated kinds: (n + 1)/(alpha_n n), the factor of m v^2 in the drive
+};
+
+// Regulated mode of a context (RegulatedTranslationPropagator, propagators.py:1537-1575): every AMM_OP_MOVE is
+//   x <- x + c tanh(alpha v / c) coef,  c = sqrt(an_kT / m)
+// (amm_reg_dx, expr_vm.h), so that no degree of freedom moves faster than c.
+struct RegDef {
+    bool on = false;
+    double alpha = 1, an_kT = 0;
 };
 
 // Isokinetic mode of a context (SIN(R), L = 1): every AMM_OP_KICK is the isokinetic kick
@@ -370,6 +385,7 @@ struct amm_ctx {
     std::vector<ExprDef> exprs;    // registered per-DOF expressions (AMM_OP_EXPR)
     std::vector<BathDef> baths;    // registered baths (AMM_OP_BATH)
     IsoDef iso;                    // isokinetic mode: what AMM_OP_KICK means (amm_iso_define)
+    RegDef reg;                    // regulated mode: what AMM_OP_MOVE means (amm_regulated_define)
     unsigned long long expr_seed = 0, expr_counter = 0;
     // ping-pong partners of x, v and the group-0 force buffer for the fused inner RESPA iteration
     double *alt_x = nullptr, *alt_v = nullptr, *alt_f = nullptr;

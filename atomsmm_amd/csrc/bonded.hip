@@ -386,6 +386,9 @@ struct CompArgs {
     int bath_kind;                  // 0 Ornstein-Uhlenbeck, 1 Nose-Hoover-Langevin, 2 stochastic-isokinetic (thermostat velocities in bath_w)
     double bath_h, bath_Q, bath_friction;
     double *bath_w;
+    int reg;                        // regulated mode: the moves are x <- x + amm_reg_dx(...) (RegDef)
+    RegDef reg_def;
+    BathDef bath;                   // the bath itself (regulated kinds 3..6: amm_reg_bath_dof / amm_reg_bath_atom)
     unsigned long long seed, counter0;
     PreKick pre[AMM_MAX_PRE];
     // displacement watchers: neighbour lists whose rebuild trigger this kernel evaluates for the positions it
@@ -410,7 +413,8 @@ struct CompArgs {
 // iteration instead of 2 + 2).
 // HONLY: the set holds harmonic bonds and angles only (a flexible water model): the other kinds' code is compiled out.
 // ISO: the isokinetic mode of SIN(R) exists in the kernel (its extra registers and tests are compiled out otherwise).
-template <int G, bool BATH, bool TERMS, bool HONLY, bool ISO>
+// REG: the regulated mode and the regulated baths exist in the kernel (likewise).
+template <int G, bool BATH, bool TERMS, bool HONLY, bool ISO, bool REG = false>
 __global__ void __launch_bounds__(256) k_inner_lanes(BondedArgs A, CompArgs C) {
     __shared__ double s_x[3][256];
     const int tid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -505,17 +509,22 @@ __global__ void __launch_bounds__(256) k_inner_lanes(BondedArgs A, CompArgs C) {
                     const double dv = amm_div_mass(num, m, rm, rok);
                     v[j] = v[j] + dv;
                 }
-                const double dx = C.d * v[j];
+                const double dx = (REG && C.reg) ? amm_reg_dx(v[j], m, C.d, C.reg_def.alpha, C.reg_def.an_kT) : C.d * v[j];
                 x[j] = x[j] + dx;
             }
         }
         if (BATH) {
             // the same amm_ou_step / random stream as a separate AMM_OP_BATH launch of this iteration would use
             const unsigned long long counter = (1ull << 63) | (C.counter0 + (unsigned long long)it + 1ull);
+            if (REG && C.bath_kind >= 5) {
+                amm_reg_bath_atom(C.bath, v, w[0], m, amm_gaussian(C.seed, counter, (unsigned)(3 * a)));
+                w[1] = w[2] = w[0];
+            } else
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 const double g = amm_gaussian(C.seed, counter, (unsigned)(3 * a + j));
-                if (ISO && C.bath_kind == 2) amm_sin_bath_step(v[j], u1[j], w[j], m, C.bath_h, C.bath_z, C.bath_kT, C.bath_Q, C.bath_friction, C.iso_Q1, C.iso_LkT, g);
+                if (REG && C.bath_kind >= 3) amm_reg_bath_dof(C.bath, v[j], w[j], m, g);
+                else if (ISO && C.bath_kind == 2) amm_sin_bath_step(v[j], u1[j], w[j], m, C.bath_h, C.bath_z, C.bath_kT, C.bath_Q, C.bath_friction, C.iso_Q1, C.iso_LkT, g);
                 else if (C.bath_kind == 1) amm_nhl_step(v[j], w[j], m, C.bath_h, C.bath_z, C.bath_kT, C.bath_Q, C.bath_friction, g);
                 else v[j] = amm_ou_step(v[j], m, C.bath_z, C.bath_kT, g);
             }
@@ -523,7 +532,7 @@ __global__ void __launch_bounds__(256) k_inner_lanes(BondedArgs A, CompArgs C) {
 #pragma clang fp contract(off)
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
-                    const double dx = C.d2 * v[j];
+                    const double dx = (REG && C.reg) ? amm_reg_dx(v[j], m, C.d2, C.reg_def.alpha, C.reg_def.an_kT) : C.d2 * v[j];
                     x[j] = x[j] + dx;
                 }
             }
@@ -1131,6 +1140,14 @@ int amm_inner_components_impl(amm_ctx *ctx, BondedSet *bs, double *x, double *v,
         amm_set_error("isokinetic mode: the thermostat-velocity buffer is not bound (or a stochastic-isokinetic bath without the mode)");
         return 1;
     }
+    C.reg = ctx->reg.on ? 1 : 0;
+    C.reg_def = ctx->reg;
+    C.bath = bath ? *bath : BathDef();
+    const bool reg = ctx->reg.on || (bath && bath->kind >= 3);
+    if (reg && ctx->iso.on) {
+        amm_set_error("regulated and isokinetic modes in one inner loop");
+        return 1;
+    }
     C.seed = ctx->expr_seed;
     C.counter0 = ctx->expr_counter;
     const bool no_terms = ctx->opt_no_term_lanes != 0;     // tuning option (A/B)
@@ -1143,7 +1160,10 @@ int amm_inner_components_impl(amm_ctx *ctx, BondedSet *bs, double *x, double *v,
     for (int kd = 2; kd < 8; ++kd) honly = honly && bs->n_terms[kd] == 0;
 #define AMM_LAUNCH_INNER(GG, BB, TT)                                                                          \
     do {                                                                                                        \
-        if (C.iso) {                                                                                            \
+        if (reg) {                                                                                              \
+            if (honly) hipLaunchKernelGGL((k_inner_lanes<GG, BB, TT, true, false, true>), grid, block, 0, ctx->stream, A, C);   \
+            else hipLaunchKernelGGL((k_inner_lanes<GG, BB, TT, false, false, true>), grid, block, 0, ctx->stream, A, C);       \
+        } else if (C.iso) {                                                                                     \
             if (honly) hipLaunchKernelGGL((k_inner_lanes<GG, BB, TT, true, true>), grid, block, 0, ctx->stream, A, C);    \
             else hipLaunchKernelGGL((k_inner_lanes<GG, BB, TT, false, true>), grid, block, 0, ctx->stream, A, C);        \
         } else {                                                                                                \

@@ -46,6 +46,16 @@ struct PosAdvanced {
     }
 };
 
+// displacement of the regulated move (RegulatedTranslationPropagator, propagators.py:1537-1575): c tanh(alpha v / c) coef with
+// c = sqrt(an_kT / m), in the operation order of `c*tanh(alpha*v/c)*...; c=sqrt(an*kT/m)` -- every move site of a context in
+// regulated mode calls this, so |dx| <= c |coef| whatever v is (tanh saturates at +-1)
+__device__ __forceinline__ double amm_reg_dx(double v, double m, double coef, double alpha, double an_kT) {
+#pragma clang fp contract(off)
+    const double c = sqrt(an_kT / m);
+    const double t = tanh((alpha * v) / c);
+    return (c * t) * coef;
+}
+
 // displacement triggers of the watched lists for ONE atom at its new position (movers call this for every atom they move)
 __device__ __forceinline__ void amm_watch_atom(const WatchArgs &W, int a, const double *xn) {
     for (int q = 0; q < W.n; ++q) {

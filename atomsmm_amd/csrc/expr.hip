@@ -281,6 +281,29 @@ __global__ void k_bath_sin(int n3, double *v, double *v1, double *v2, const doub
     v2[dof] = c;
 }
 
+// regulated Nose-Hoover-Langevin baths (kinds 3..6): massive kinds one lane per DOF, atomic kinds one lane per atom (the atom's
+// thermostat velocity is the x component of w, written back to all three; its noise is the gaussian of its x component)
+__global__ void k_bath_reg(int n3, double *v, double *w, const double *__restrict__ mass, BathDef b, unsigned long long seed,
+                           unsigned long long counter) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b.kind == 5 || b.kind == 6) {
+        if (3 * t >= n3) return;
+        double vv[3] = {v[3 * t], v[3 * t + 1], v[3 * t + 2]}, ww = w[3 * t];
+        amm_reg_bath_atom(b, vv, ww, mass[t], amm_gaussian(seed, counter, (unsigned)(3 * t)));
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            v[3 * t + j] = vv[j];
+            w[3 * t + j] = ww;
+        }
+        return;
+    }
+    if (t >= n3) return;
+    double vv = v[t], ww = w[t];
+    amm_reg_bath_dof(b, vv, ww, mass[t / 3], amm_gaussian(seed, counter, (unsigned)t));
+    v[t] = vv;
+    w[t] = ww;
+}
+
 // isokinetic kick outside the inner-loop kernel (amm_kick_impl dispatches here when the context is in isokinetic mode)
 __global__ void k_isokick(int n3, double *v, double *v1, const double *__restrict__ f, const double *__restrict__ f2, int plus,
                           const double *__restrict__ mass, double coef, double LkT, double Q1) {
@@ -318,6 +341,18 @@ int amm_bath_impl(amm_ctx *ctx, const BathDef &bath, double *d_v, unsigned long 
         }
         hipLaunchKernelGGL(k_bath_sin, dim3((n3 + 255) / 256), dim3(256), 0, ctx->stream, n3, d_v, v1, v2, ctx->d_mass, bath, ctx->iso.Q1,
                            ctx->iso.LkT, ctx->expr_seed, counter);
+        AMM_HIP(hipGetLastError());
+        return 0;
+    }
+    if (bath.kind >= 3) {
+        double *w = (bath.slot >= 0 && bath.slot < AMM_MAX_SLOTS) ? ctx->slots[bath.slot] : nullptr;
+        if (!w) {
+            amm_set_error("regulated Nose-Hoover-Langevin bath: the thermostat-velocity buffer is not bound");
+            return 1;
+        }
+        const int lanes = bath.kind >= 5 ? ctx->n : n3;
+        hipLaunchKernelGGL(k_bath_reg, dim3((lanes + 255) / 256), dim3(256), 0, ctx->stream, n3, d_v, w, ctx->d_mass, bath, ctx->expr_seed,
+                           counter);
         AMM_HIP(hipGetLastError());
         return 0;
     }

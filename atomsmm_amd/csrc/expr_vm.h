@@ -111,6 +111,88 @@ __device__ __forceinline__ void amm_sin_bath_step(double &v, double &v1, double 
     amm_iso_rescale(v, v1, m, LkT, Q1);
 }
 
+// Regulated Nose-Hoover-Langevin baths (BathDef kinds 3..6; propagators.py:1598-2007), in the operation order of the reference's
+// expressions with h = (fraction/2) dt: the drive G of the thermostat velocity w, the scaling of v, and the Ornstein-Uhlenbeck step
+//   w <- w z [+ G (1 - z)/friction] + omega sqrt(1 - z^2) g      (the drift term only without `split`)
+// c = sqrt(an kT / m) is the speed limit of the DOF.  The twice-regulated scaling takes asinh as the reference writes it,
+// (2 step(z) - 1) log(select(step(za - 1E8), 2 za, za + sqrt(1 + z z))), not the device asinh.
+__device__ __forceinline__ double amm_reg_speed(const BathDef &b, double m) {
+#pragma clang fp contract(off)
+    return sqrt((b.an * b.kT) / m);
+}
+// drive of one DOF (massive kinds 3, 4): (m v c tanh(alpha v/c) - kT)/Q  or  (kfac m (c tanh(alpha v/c))^2 - kT)/Q
+__device__ __forceinline__ double amm_reg_drive(const BathDef &b, double v, double m) {
+#pragma clang fp contract(off)
+    const double c = amm_reg_speed(b, m);
+    double s;
+    if (b.kind == 3) {
+        const double t = tanh((b.alpha * v) / c);
+        s = ((m * v) * c) * t;
+    } else {
+        const double y = c * tanh((b.alpha * v) / c);
+        s = (b.kfac * m) * (y * y);
+    }
+    return (s - b.kT) / b.Q;
+}
+// drive of one atom (atomic kinds 5, 6): (dot(m v, c tanh(alpha v/c)) - 3 kT)/Q  or  (kfac dot(m c y, c y) - 3 kT)/Q
+__device__ __forceinline__ double amm_reg_drive3(const BathDef &b, const double *v, double m) {
+#pragma clang fp contract(off)
+    const double c = amm_reg_speed(b, m);
+    double p[3], q[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double t = tanh((b.alpha * v[j]) / c);
+        if (b.kind == 5) {
+            p[j] = m * v[j];
+            q[j] = c * t;
+        } else {
+            p[j] = (m * c) * t;
+            q[j] = c * t;
+        }
+    }
+    const double d = ((p[0] * q[0]) + (p[1] * q[1])) + (p[2] * q[2]);
+    const double s = b.kind == 5 ? d : b.kfac * d;
+    return (s - 3.0 * b.kT) / b.Q;
+}
+// scaling of one velocity component by the thermostat velocity w over h
+__device__ __forceinline__ double amm_reg_scale(const BathDef &b, double v, double w, double m) {
+#pragma clang fp contract(off)
+    const double e = exp(-w * b.h);
+    if (b.kind == 3 || b.kind == 5) return v * e;
+    const double c = amm_reg_speed(b, m);
+    const double z = sinh((b.alpha * v) / c) * e;
+    const double za = fabs(z);
+    const double arg = za - 1e8 >= 0.0 ? 2.0 * za : za + sqrt(1.0 + z * z);
+    const double asinhz = (z >= 0.0 ? 1.0 : -1.0) * log(arg);
+    return ((1.0 / b.alpha) * c) * asinhz;
+}
+__device__ __forceinline__ double amm_reg_ou(const BathDef &b, double w, double G, double g) {
+#pragma clang fp contract(off)
+    const double noise = (b.omega * sqrt(1.0 - b.z * b.z)) * g;
+    if (b.split) return (w * b.z) + noise;
+    return ((w * b.z) + ((G * (1.0 - b.z)) / b.friction)) + noise;
+}
+// the whole block for one DOF of a massive kind (w: its thermostat velocity, g: its gaussian)
+__device__ __forceinline__ void amm_reg_bath_dof(const BathDef &b, double &v, double &w, double m, double g) {
+#pragma clang fp contract(off)
+    if (b.split) w = w + amm_reg_drive(b, v, m) * b.h;
+    v = amm_reg_scale(b, v, w, m);
+    w = amm_reg_ou(b, w, b.split ? 0.0 : amm_reg_drive(b, v, m), g);
+    v = amm_reg_scale(b, v, w, m);
+    if (b.split) w = w + amm_reg_drive(b, v, m) * b.h;
+}
+// ... and for one atom of an atomic kind (one w per atom, g: the gaussian of its x component)
+__device__ __forceinline__ void amm_reg_bath_atom(const BathDef &b, double *v, double &w, double m, double g) {
+#pragma clang fp contract(off)
+    if (b.split) w = w + amm_reg_drive3(b, v, m) * b.h;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) v[j] = amm_reg_scale(b, v[j], w, m);
+    w = amm_reg_ou(b, w, b.split ? 0.0 : amm_reg_drive3(b, v, m), g);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) v[j] = amm_reg_scale(b, v[j], w, m);
+    if (b.split) w = w + amm_reg_drive3(b, v, m) * b.h;
+}
+
 // Scalar programs (amm_expr_eval_scalar): a sequence of assignments  scalars[dst] <- expression  over constants and other scalars
 // (X_DEVG), each closed by X_OUT dst.  One thread runs it; code, constants, stack and locals sit in LDS (a lone thread waits for
 // every access: from the launch argument and private memory the same interpreter took ~0.6 us per word).

@@ -25,10 +25,13 @@ __global__ void k_kick(int n3, double *__restrict__ v, const double *__restrict_
 }
 
 // x <- x + (coef)*v                propagators.py:249
-__global__ void k_move(int n3, double *__restrict__ x, const double *__restrict__ v, double coef) {
+// REG: the regulated move x <- x + c tanh(alpha v/c) coef of a context in regulated mode (amm_reg_dx, RegDef)
+template <bool REG>
+__global__ void k_move(int n3, double *__restrict__ x, const double *__restrict__ v, double coef, const double *__restrict__ mass,
+                       RegDef R) {
     int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n3) return;
-    const double dx = coef * v[t];
+    const double dx = REG ? amm_reg_dx(v[t], mass[t / 3], coef, R.alpha, R.an_kT) : coef * v[t];
     x[t] = x[t] + dx;
 }
 
@@ -59,8 +62,9 @@ __global__ void k_kicks_move(int n3, double *__restrict__ x, double *__restrict_
 }
 // the same with a move, one thread per ATOM: the three new coordinates are at hand, so the launch also evaluates the displacement
 // triggers of the neighbour lists (WatchArgs) -- the check launch in front of the next pair evaluation is not needed then
+template <bool REG>
 __global__ void k_kicks_move_atoms(int n, double *__restrict__ x, double *__restrict__ v, KickList K, const double *__restrict__ mass,
-                                   double dcoef, WatchArgs W) {
+                                   double dcoef, WatchArgs W, RegDef R) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const double m = mass[i];
@@ -80,7 +84,7 @@ __global__ void k_kicks_move_atoms(int n, double *__restrict__ x, double *__rest
             }
         }
         v[t] = vt;
-        const double dx = dcoef * vt;
+        const double dx = REG ? amm_reg_dx(vt, m, dcoef, R.alpha, R.an_kT) : dcoef * vt;
         xn[c] = x[t] + dx;
         x[t] = xn[c];
     }
@@ -101,11 +105,16 @@ int amm_kicks_move_impl(amm_ctx *ctx, const double *const *fa, const double *con
     if (with_move) {
         WatchArgs W;
         amm_collect_watches(ctx, W);           // (the caller bumps pos_epoch and calls amm_watch_moved)
-        hipLaunchKernelGGL(k_kicks_move_atoms, dim3((ctx->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_x, ctx->d_v, K,
-                           ctx->d_mass, dcoef, W);
+        if (ctx->reg.on)
+            hipLaunchKernelGGL(k_kicks_move_atoms<true>, dim3((ctx->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_x,
+                               ctx->d_v, K, ctx->d_mass, dcoef, W, ctx->reg);
+        else
+            hipLaunchKernelGGL(k_kicks_move_atoms<false>, dim3((ctx->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_x,
+                               ctx->d_v, K, ctx->d_mass, dcoef, W, ctx->reg);
         AMM_HIP(hipGetLastError());
         return 0;
     }
+    // (kicks only: a run that moves goes to the per-atom launch above, which knows the regulated mode)
     hipLaunchKernelGGL(k_kicks_move, dim3((n3 + 255) / 256), dim3(256), 0, ctx->stream, n3, ctx->d_x, ctx->d_v, K, ctx->d_mass,
                        with_move, dcoef);
     AMM_HIP(hipGetLastError());
@@ -140,7 +149,10 @@ int amm_kick_impl(amm_ctx *ctx, double *d_v, const double *d_f, const double *d_
 }
 int amm_move_impl(amm_ctx *ctx, double *d_x, const double *d_v, double coef) {
     const int n3 = 3 * ctx->n;
-    hipLaunchKernelGGL(k_move, dim3((n3 + 255) / 256), dim3(256), 0, ctx->stream, n3, d_x, d_v, coef);
+    if (ctx->reg.on)
+        hipLaunchKernelGGL(k_move<true>, dim3((n3 + 255) / 256), dim3(256), 0, ctx->stream, n3, d_x, d_v, coef, ctx->d_mass, ctx->reg);
+    else
+        hipLaunchKernelGGL(k_move<false>, dim3((n3 + 255) / 256), dim3(256), 0, ctx->stream, n3, d_x, d_v, coef, ctx->d_mass, ctx->reg);
     AMM_HIP(hipGetLastError());
     return 0;
 }

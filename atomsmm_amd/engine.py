@@ -251,7 +251,19 @@ def slice_bounds(n_items, rank, world):
     return begin, min(n_items, begin + per)
 
 
+class VectorExpressionError(NotImplementedError):
+    """A per-DOF expression with the vector functions dot() / _x() (the atomic regulated baths) that no native op took."""
+
+
+def _refuse_vector_functions(expr):
+    if re.search(r'(?<![A-Za-z_0-9])(dot|_x|_y|_z|cross|vector)\(', expr):
+        raise VectorExpressionError('per-DOF expressions with vector functions (dot, _x, ...) run only as the native bath op of the '
+                                    'atomic regulated propagators (a global kT and Q, the reference\'s step text); not: ' + expr)
+
+
 class Engine:
+    native_regulated = True       # regulated moves and baths as native ops (False: per-DOF expressions -- a measurement knob)
+
     def __init__(self, system, integrator, properties):
         import torch
         self.torch = torch
@@ -285,6 +297,10 @@ class Engine:
         # measure its host-side cost on a single GPU
         self._coll = self.world > 1 or (os.environ.get('AMM_FORCE_COLLECTIVES') == '1' and dist.is_available()
                                         and dist.is_initialized())
+        if self.world > 1 and any(k == mm.CustomIntegrator.ComputePerDof and t == 'x' and 'tanh(' in e
+                                  for k, t, e in getattr(integrator, '_steps', [])):
+            # (the ranks' fused paths -- state exchange, sliced epilogues -- carry plain moves only)
+            raise NotImplementedError('regulated dynamics (RegulatedTranslationPropagator) runs on one rank only')
         device = int(properties.get('DeviceIndex', torch.cuda.current_device() if torch.cuda.is_available() else 0))
         self.ctx = _context_factory(n, self.box, device=device, rank=self.rank, world=self.world)
         self.n = n
@@ -1176,12 +1192,40 @@ class Engine:
         kinetic = None
         if want_energy:
             out = torch.zeros(1, dtype=torch.float64, device=self.x.device)
-            self.ctx.mvv(self.v, self.mass, out)
-            kinetic = 0.5 * out.item()
+            expression = getattr(self.integrator, '_kinetic', None)
+            if expression is None:
+                self.ctx.mvv(self.v, self.mass, out)
+                kinetic = 0.5 * out.item()
+            else:
+                kinetic = self._kinetic_energy(expression, out)
         pos = self.x.cpu().numpy() if want_pos else None
         vel = self.v.cpu().numpy() if want_vel else None
         box = [(self.box[0], 0, 0), (0, self.box[1], 0), (0, 0, self.box[2])]
         return mm.State(energy, kinetic, forces, pos, vel, box, self.time)
+
+    def _kinetic_energy(self, expression, out):
+        """The integrator's kinetic-energy expression (setKineticEnergyExpression: the regulated propagators' sum of
+        m (c tanh(alpha v/c))^2 / 2) summed over the degrees of freedom on the device."""
+        integ = self.integrator
+        env = dict(self.parameters)
+        env.update(zip(integ._gnames, integ._gvalues))
+
+        def resolve(name):
+            if name == 'm':
+                return ('mass',)
+            if name == 'v':
+                return ('buf', B.SLOT_V)
+            if name == 'x':
+                return ('buf', B.SLOT_X)
+            if name in integ._pnames:
+                return ('buf', self._slot(name))
+            if name in env:
+                return ('global',)
+            return None
+        prog = X.compile_per_dof(expression, resolve)
+        # (counter 0: the expression draws no random numbers, and the program's random stream is left where it is)
+        self.ctx.expr_eval(prog.code, prog.consts, [float(env[name]) for name in prog.globals_], 0, 0, total=out)
+        return out.item()
 
     # ------------------------------------------------------------------------------- step programs
     def _slot(self, name):
@@ -1292,6 +1336,7 @@ class Engine:
         self._mirror_work = dict(self._mirror)
         self._static_exprs = True
         self._iso_found, self._plain_kick = None, False      # isokinetic (SIN(R)) kicks recognised / ordinary kicks emitted
+        self._reg_found, self._plain_move = None, False      # regulated moves recognised (alpha, an kT) / ordinary moves emitted
         ops = [B.Op(B.OP_SAVE_REF, 0, 0, 0, 0.0)] if self._has_constraints else []
         pc = 0
         guard = 0
@@ -1307,10 +1352,12 @@ class Engine:
                         raise NotImplementedError('step programs that change Context parameters (%s) are not supported' % target)
                 env[target] = value
             elif kind == C.ComputePerDof:
-                skip = self._emit_native_bath_block(steps, pc, env, ops) or self._emit_native_iso_block(steps, pc, env, ops, valid)
+                skip = self._emit_native_bath_block(steps, pc, env, ops) or self._emit_native_iso_block(steps, pc, env, ops, valid) or \
+                    self._emit_regulated_bath_block(steps, pc, env, ops)
                 if skip:
                     pc += skip
                     continue
+                _refuse_vector_functions(expr)
                 self._emit_per_dof(target, expr, env, ops, valid)
             elif kind == C.ComputeSum:
                 raise NotImplementedError('ComputeSum steps (thermostat propagators) are outside this round\'s scope')
@@ -1331,6 +1378,16 @@ class Engine:
             # isokinetic ones as general expressions
             self._no_native_iso = True
             return self._compile()
+        if self._reg_found and (self._plain_move or self._iso_found):
+            # regulated AND ordinary moves (or the isokinetic mode as well): the context-wide regulated mode cannot serve both --
+            # run the regulated moves as general expressions
+            self._no_native_reg = True
+            return self._compile()
+        if hasattr(self.ctx, 'regulated_define'):
+            if self._reg_found:
+                self.ctx.regulated_define(True, *self._reg_found)
+            else:
+                self.ctx.regulated_define(False)
         if hasattr(self.ctx, 'iso_define'):
             if self._iso_found:
                 LkT, Q1, v1 = self._iso_found
@@ -1369,6 +1426,76 @@ class Engine:
         ops.append(B.Op(B.OP_BATH, self._expr_ids[key], B.SLOT_V, 0, 0.0))
         self._mirror_work.pop(w, None)
         return 3
+
+    _NUM = r'([0-9.eE+-]+)'
+    _REG_SCALE = re.compile(r'v\*exp\(-v_eta\*(.+)\*dt\)')
+    _REG_SCALE2 = re.compile(_NUM + r'\*c\*asinhz;asinhz=\(2\*step\(z\)-1\)\*log\(select\(step\(za-1E8\),2\*za,za\+sqrt\(1\+z\*z\)\)\);za=abs\(z\);'
+                             r'z=sinh\(' + _NUM + r'\*v/c\)\*exp\(-v_eta\*(.+)\*dt\);c=sqrt\(' + _NUM + r'\*kT/m\)')
+    # the drive G of each kind: (kfac,) alpha, an
+    _REG_DRIVE = {3: r'\(m\*v\*c\*tanh\(' + _NUM + r'\*v/c\)-kT\)/Q;c=sqrt\(' + _NUM + r'\*kT/m\)',
+                  4: r'\(' + _NUM + r'\*m\*\(c\*tanh\(' + _NUM + r'\*v/c\)\)\^2-kT\)/Q;c=sqrt\(' + _NUM + r'\*kT/m\)',
+                  5: r'\(dot\(m\*v,c\*tanh\(' + _NUM + r'\*v/c\)\)-3\*kT\)/Q;c=sqrt\(' + _NUM + r'\*kT/m\)',
+                  6: r'\(' + _NUM + r'\*dot\(m\*c\*y,c\*y\)-3\*kT\)/Q;y=tanh\(' + _NUM + r'\*v/c\);c=sqrt\(' + _NUM + r'\*kT/m\)'}
+
+    def _emit_regulated_bath_block(self, steps, pc, env, ops):
+        """The bath block of a regulated Nose-Hoover-Langevin propagator (propagators.py:1598-2007) -- [boost of v_eta ;] scaling of
+        v ; Ornstein-Uhlenbeck step of v_eta ; scaling of v [; boost] -- becomes ONE native bath op (amm_bath_define_regulated,
+        kinds 3..6), which the inner-loop kernel carries between its two half moves.  Needs the reference's text with global kT,
+        Q, omega and friction (not `adiabatic`).  Returns the number of program steps consumed (0: not such a block)."""
+        C = mm.CustomIntegrator
+        if not (self.native_regulated and hasattr(self.ctx, 'bath_define_regulated')) or steps[pc][1] not in ('v', 'v_eta'):
+            return 0
+        split = steps[pc][1] == 'v_eta'
+        count = 5 if split else 3
+        if pc + count > len(steps) or any(steps[pc + k][0] != C.ComputePerDof for k in range(count)):
+            return 0
+        block = [(t, e.replace(' ', '')) for _, t, e in steps[pc:pc + count]]
+        integ = self.integrator
+        if [t for t, _ in block] != (['v_eta', 'v', 'v_eta', 'v', 'v_eta'] if split else ['v', 'v_eta', 'v']) or \
+                'v_eta' not in integ._pnames or any(g not in env or g in integ._pnames for g in ('kT', 'Q', 'omega', 'friction')):
+            return 0
+        scale, ou = block[1 if split else 0][1], block[2 if split else 1][1]
+        if block[3 if split else 2][1] != scale or (split and block[4][1] != block[0][1]):
+            return 0
+        s1, s2 = self._REG_SCALE.fullmatch(scale), self._REG_SCALE2.fullmatch(scale)
+        twice = s2 is not None
+        if not (s1 or s2):
+            return 0
+        atomic = '_x(gaussian)' in ou
+        kind = (5 if atomic else 3) + (1 if twice else 0)
+        noise = '_x\\(gaussian\\)' if atomic else 'gaussian'
+        drive = self._REG_DRIVE[kind]
+        tail = r';z=exp\(-friction\*(.+)\*dt\)'
+        if split:
+            o = re.fullmatch(r'v_eta\*z\+omega\*sqrt\(1-z\^2\)\*' + noise + tail, ou)
+            b = re.fullmatch(r'v_eta\+G\*(.+)\*dt;G=' + drive, block[0][1])
+            if not (o and b):
+                return 0
+            d = b.groups()[1:]
+            if self._eval(b.group(1), env) != self._eval((s2 or s1).group(3 if twice else 1), env):
+                return 0
+        else:
+            o = re.fullmatch(r'v_eta\*z\+G\*\(1-z\)/friction\+omega\*sqrt\(1-z\^2\)\*' + noise + ';G=' + drive + tail, ou)
+            if not o:
+                return 0
+            d = o.groups()[:-1]
+        numbers = [float(t) for t in d]
+        kfac = numbers.pop(0) if twice else None
+        alpha, an = numbers
+        n = an / alpha
+        if twice:
+            if float(s2.group(1)) != 1 / alpha or float(s2.group(2)) != alpha or float(s2.group(4)) != an or \
+                    abs(kfac - (n + 1) / (alpha * n)) > 1e-12 * kfac:
+                return 0
+        h = self._eval((s2 or s1).group(3 if twice else 1), env) * env['dt']
+        z = math.exp((-env['friction'] * self._eval(o.groups()[-1], env)) * env['dt'])
+        args = (kind, split, h, z, float(env['kT']), float(env['Q']), float(env['omega']), float(env['friction']), alpha, an)
+        key = ('regulated',) + args
+        if key not in self._expr_ids:
+            self._expr_ids[key] = self.ctx.bath_define_regulated(*args, self._slot('v_eta'))
+        ops.append(B.Op(B.OP_BATH, self._expr_ids[key], B.SLOT_V, 0, 0.0))
+        self._mirror_work.pop('v_eta', None)
+        return count
 
     _ISO_KICK = re.compile(r'v\*cosh\(z\)\+sqrt\(LkT/m\)\*sinh\(z\);z=(.+)/sqrt\(m\*LkT\)')
     _ISO_H = re.compile(r'sqrt\(LkT/\(m\*v\^2\+0\.5\*Q1\*\((\w+)\^2\)\)\)')
@@ -1679,10 +1806,49 @@ class Engine:
         if kicked:
             self._plain_kick = True
 
+    _REG_MOVE = re.compile(r'x\+c\*tanh\(([0-9.eE+-]+)\*v/c\)\*(.+)\*dt;c=sqrt\(([0-9.eE+-]+)\*kT/m\)')
+
+    def _emit_regulated_move(self, target, expr, env, ops, valid):
+        """`x <- x + c*tanh(alpha*v/c)*h*dt; c=sqrt(an*kT/m)` with a global kT (RegulatedTranslationPropagator,
+        propagators.py:1537-1575): a MOVE op of a context in regulated mode (amm_regulated_define).  Only in unrolled programs, whose
+        compilation ends by setting the mode; False: not such a move."""
+        m = self._REG_MOVE.fullmatch(expr.replace(' ', '')) if target == 'x' else None
+        if not (m and self.native_regulated and getattr(self, '_static_exprs', False) and not getattr(self, '_no_native_reg', False) and
+                hasattr(self.ctx, 'regulated_define') and 'kT' in env and 'kT' not in self.integrator._pnames):
+            return False
+        found = (float(m.group(1)), float(m.group(3)) * float(env['kT']))
+        if self._reg_found not in (None, found):
+            self._plain_move = True              # two different regulated moves: one mode cannot serve both
+            return False
+        self._reg_found = found
+        ops.append(B.Op(B.OP_MOVE, 0, 0, 0, self._eval('(%s)*dt' % m.group(2), env)))
+        for g in valid:
+            valid[g] = False
+        self._deriv_cache.clear()
+        return True
+
     def _emit_per_dof(self, target, expr, env, ops, valid):
+        if self._emit_regulated_move(target, expr, env, ops, valid):
+            return
         text = expr.replace(' ', '')
         if ';' in text:
             text = ''         # auxiliary definitions: never a plain kick / move / copy -> general expression below
+        # the kick written force first, `v + (f0)*0.0625*dt/m` (RegulatedBoostPropagator, propagators.py:1578-1595): OpenMM's
+        # parser computes ((F*a)*b)/m, AMM_OP_KICK (a*b*F)/m -- the same to rounding
+        if target == 'v' and text.startswith('v+') and text.endswith('/m'):
+            factors = self._split_product(text[2:-2])
+            if factors and len(factors) >= 2 and self._is_global_product(factors[1:], env):
+                terms = self._signed_terms(factors[0])
+                if terms and len(terms) <= 2 and terms[0][0] == 1 and all(self._is_force_symbol(t[1]) for t in terms):
+                    coef = self._eval('*'.join(factors[1:]), env)
+                    a = self._force_ref(terms[0][1], ops, valid)
+                    b, plus = -1, 0
+                    if len(terms) == 2:
+                        b = self._force_ref(terms[1][1], ops, valid)
+                        plus = 1 if terms[1][0] == 1 else 0
+                    ops.append(B.Op(B.OP_KICK, a, b, plus, coef))
+                    self._plain_kick = True
+                    return
         # kick: v <- v + (coef)*FORCE/m
         if target == 'v' and text.startswith('v+') and text.endswith('/m'):
             parts = self._split_leading_group(text[2:-2])
@@ -1724,6 +1890,7 @@ class Engine:
                 coef_text = '*'.join(factors[:-1])          # `x + 1.0*dt*v`: ((1.0*dt)*v), the move's arithmetic
             if coef_text is not None:
                 ops.append(B.Op(B.OP_MOVE, 0, 0, 0, self._eval(coef_text, env)))
+                self._plain_move = True
                 for g in valid:
                     valid[g] = False
                 self._deriv_cache.clear()
@@ -2444,6 +2611,7 @@ class Engine:
                             eager[0] -= 1
                             flush()
                     if not done:
+                        _refuse_vector_functions(expr)
                         prog = X.compile_per_dof(expr, resolve)
                         flush()                                   # EVALs emitted by resolve() run first
                         gvals = [float(env[name]) for name in prog.globals_]
@@ -2509,9 +2677,14 @@ class Engine:
             try:
                 self._compile()
                 self._interpreted = False
+            except VectorExpressionError:
+                self._static_exprs = False
+                raise
             except (NotImplementedError, NameError, SyntaxError, TypeError, KeyError, X.ExpressionError):
                 self._static_exprs = False
                 self._interpreted = True
+                if hasattr(self.ctx, 'regulated_define'):
+                    self.ctx.regulated_define(False)       # (the general path writes regulated moves as expressions)
         if self._interpreted:
             return self._step_interpreted(n)
         remaining = int(n)

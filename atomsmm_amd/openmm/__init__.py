@@ -691,6 +691,7 @@ class CustomIntegrator(Integrator):
         self._gnames, self._gvalues = [], []
         self._pnames, self._pvalues = [], []
         self._steps = []
+        self._kinetic = None
 
     # variables
     def addGlobalVariable(self, name, initialValue):
@@ -774,6 +775,15 @@ class CustomIntegrator(Integrator):
 
     def endBlock(self):
         return self._add(self.EndBlock)
+
+    def setKineticEnergyExpression(self, expression):
+        """The per-DOF expression whose sum State.getKineticEnergy() reports (default: m*v*v/2)."""
+        self._kinetic = expression
+        if self._context is not None:
+            self._context._engine.invalidate_program()
+
+    def getKineticEnergyExpression(self):
+        return self._kinetic if self._kinetic is not None else 'm*v*v/2'
 
     def getNumComputations(self):
         return len(self._steps)

@@ -11,8 +11,9 @@ later unrolls that program into kick / move / copy / force-group-evaluation ops 
 The basic thermostat propagators are here too -- unconstrained velocity Verlet, stochastic
 velocity rescaling, global and massive Nose-Hoover, Ornstein-Uhlenbeck / Langevin, generic boost and scaling; their
 programs contain ComputeSum steps, random numbers and general per-DOF expressions, which the engine runs through
-`amm_expr_eval` (atomsmm_amd/expr.py).  The 'regulated', 'limited-speed' and isokinetic families (reference :276-682,
-:1452-2172) are not restated.
+`amm_expr_eval` (atomsmm_amd/expr.py).  The regulated family (reference :1537-2117) is at the end; the engine runs its
+move, boost and massive / atomic baths as native ops (regulated dynamics).  The 'limited-speed' family and the
+other propagators of reference :1452-2172 are not restated.
 """
 import math
 
@@ -655,3 +656,165 @@ class GenericScalingPropagator(Propagator):
     def addSteps(self, integrator, fraction=1.0, force='f'):
         expression = '{}*exp(-({}*dt)*{})'.format(self.velocity, fraction, self.damping)
         (integrator.addComputePerDof if self.perDof else integrator.addComputeGlobal)(self.velocity, expression)
+
+
+class RegulatedTranslationPropagator(Propagator):
+    """The regulated move x <- x + c tanh(alpha_n v/c) (fraction dt) with the speed limit c = sqrt(alpha_n n kT/m) of each degree
+    of freedom (interface of propagators.py:1537-1575); also sets the integrator's kinetic energy, sum of m (c tanh(alpha_n v/c))^2/2.
+    kT is a global of the bath propagator it is composed with."""
+
+    MOVE = 'dof x <- x + c*tanh({alpha}*v/c)*{h}*dt; c=sqrt({an}*kT/m)'
+
+    def __init__(self, temperature, n, alpha_n=1):
+        super().__init__()
+        self._alpha = alpha_n
+        self._an = alpha_n * n
+
+    def addSteps(self, integrator, fraction=1.0, force='f'):
+        integrator.setKineticEnergyExpression('0.5*m*(c*tanh({}*v/c))^2; c=sqrt({}*kT/m)'.format(self._alpha, self._an))
+        play(integrator, self.MOVE, alpha=self._alpha, an=self._an, h=fraction)
+
+
+class RegulatedBoostPropagator(Propagator):
+    """The kick v <- v + force*(fraction*dt)/m written force first, as the regulated propagators do (propagators.py:1578-1595)."""
+
+    def addSteps(self, integrator, fraction=1.0, force='f'):
+        play(integrator, 'dof v <- v + {F}*{h}*dt/m', F=force, h=fraction)
+
+
+class _RegulatedNoseHooverLangevin(Propagator):
+    """Shared by the regulated Nose-Hoover-Langevin baths (propagators.py:1598-2117): one thermostat velocity v_eta per degree of
+    freedom (massive), per atom (atomic) or for the system (global), driven by G; the block is
+
+        [boost v_eta by G (fraction/2)]  scaling of v  Ornstein-Uhlenbeck step of v_eta  scaling of v  [boost again]
+
+    with the boosts when `split`, and the drift G (1 - z)/friction inside the OU step otherwise.  A subclass names its drive G,
+    its scaling and the noise it draws; `_global` makes v_eta a global updated by ComputeSum + ComputeGlobal steps."""
+
+    OU = 'v_eta*z + omega*sqrt(1-z^2)*{noise}'
+    OU_DRIFT = 'v_eta*z + G*(1-z)/friction + omega*sqrt(1-z^2)*{noise}{G}'
+    NOISE = 'gaussian'
+
+    def __init__(self, alpha_n, n, split):
+        super().__init__()
+        self._alpha, self._n, self._an, self._split = alpha_n, n, alpha_n * n, split
+
+    def _drive(self):
+        raise NotImplementedError
+
+    def _scaling(self, fraction):
+        return 'v*exp(-v_eta*{}*dt)'.format(0.5 * fraction)
+
+    def _twice_scaling(self, fraction):
+        return ('{}*c*asinhz; asinhz=(2*step(z)-1)*log(select(step(za-1E8),2*za,za+sqrt(1+z*z))); za=abs(z); '
+                'z=sinh({}*v/c)*exp(-v_eta*{}*dt); c=sqrt({}*kT/m)').format(1 / self._alpha, self._alpha, 0.5 * fraction, self._an)
+
+    def addSteps(self, integrator, fraction=1.0, force='f'):
+        G = self._drive()
+        boost = 'dof v_eta <- v_eta + G*{}*dt{}'.format(0.5 * fraction, G)
+        OU = (self.OU if self._split else self.OU_DRIFT).format(noise=self.NOISE, G=G)
+        OU = 'dof v_eta <- {}; z=exp(-friction*{}*dt)'.format(OU, fraction)
+        scaling = 'dof v <- ' + self._scaling(fraction)
+        play(integrator, '\n'.join(([boost] if self._split else []) + [scaling, OU, scaling] + ([boost] if self._split else [])))
+
+
+class RegulatedMassiveNoseHooverLangevinPropagator(_RegulatedNoseHooverLangevin):
+    """Regulated massive Nose-Hoover-Langevin (interface of propagators.py:1598-1699): one v_eta per degree of freedom, Q = kT tau^2,
+    G = (m v c tanh(alpha_n v/c) - kT)/Q.  `adiabatic`: kT is a per-DOF variable and Q = kT omega^-2 is defined in the expression."""
+
+    def __init__(self, temperature, n, timeScale, frictionConstant, alpha_n=1, split=False, adiabatic=False):
+        super().__init__(alpha_n, n, split)
+        kT = kB * temperature
+        self._adiabatic = adiabatic
+        if adiabatic:
+            self.perDofVariables['kT'] = kT
+        else:
+            self.globalVariables['kT'] = kT
+            self.globalVariables['Q'] = kT * timeScale ** 2
+        self.globalVariables['omega'] = 1 / timeScale
+        self.globalVariables['friction'] = frictionConstant
+        self.perDofVariables['v_eta'] = 0
+
+    def _drive(self):
+        return '; G=(m*v*c*tanh({}*v/c) - kT)/Q; c=sqrt({}*kT/m){}'.format(self._alpha, self._an, '; Q=kT/omega^2' if self._adiabatic else '')
+
+
+class TwiceRegulatedMassiveNoseHooverLangevinPropagator(RegulatedMassiveNoseHooverLangevinPropagator):
+    """Twice-regulated massive Nose-Hoover-Langevin (interface of propagators.py:1702-1807): G = ((n+1)/(alpha_n n) m (c tanh(alpha_n
+    v/c))^2 - kT)/Q and the scaling (m c/alpha_n) asinh[sinh(alpha_n p/(m c)) exp(-alpha_n v_eta t)], with asinh written out."""
+
+    def __init__(self, temperature, n, timeScale, frictionConstant, alpha_n=1, split=False, adiabatic=False):
+        super().__init__(temperature, n, timeScale, frictionConstant, alpha_n, split, adiabatic)
+        if not adiabatic:            # the reference's table order: Q before kT
+            kT = self.globalVariables.pop('kT')
+            self.globalVariables = dict(Q=self.globalVariables.pop('Q'), kT=kT, **self.globalVariables)
+
+    def _drive(self):
+        return '; G=({}*m*(c*tanh({}*v/c))^2 - kT)/Q; c=sqrt({}*kT/m){}'.format(
+            (self._n + 1) / (self._alpha * self._n), self._alpha, self._an, '; Q=kT/omega^2' if self._adiabatic else '')
+
+    _scaling = _RegulatedNoseHooverLangevin._twice_scaling
+
+
+class RegulatedAtomicNoseHooverLangevinPropagator(_RegulatedNoseHooverLangevin):
+    """Regulated atomic Nose-Hoover-Langevin (interface of propagators.py:1810-1905): one v_eta per atom (held in all three components of
+    the per-DOF variable), Q = 3 kT tau^2, G = (dot(m v, c tanh(alpha_n v/c)) - 3 kT)/Q, noise from the x component of the atom's
+    gaussian."""
+
+    NOISE = '_x(gaussian)'
+
+    def __init__(self, temperature, n, timeScale, frictionConstant, alpha_n=1, split=False):
+        super().__init__(alpha_n, n, split)
+        kT = kB * temperature
+        Q = 3 * kT * timeScale ** 2
+        self.globalVariables['kT'] = kT
+        self.globalVariables['Q'] = Q
+        self.globalVariables['omega'] = unit.sqrt(kT / Q)
+        self.globalVariables['friction'] = frictionConstant
+        self.perDofVariables['v_eta'] = 0
+
+    def _drive(self):
+        return '; G=(dot(m*v,c*tanh({}*v/c)) - 3*kT)/Q; c=sqrt({}*kT/m)'.format(self._alpha, self._an)
+
+
+class TwiceRegulatedAtomicNoseHooverLangevinPropagator(RegulatedAtomicNoseHooverLangevinPropagator):
+    """Twice-regulated atomic Nose-Hoover-Langevin (interface of propagators.py:1908-2007): G = ((n+1)/(alpha_n n) dot(m c y, c y) -
+    3 kT)/Q with y = tanh(alpha_n v/c), and the twice-regulated scaling."""
+
+    def _drive(self):
+        return '; G=({}*dot(m*c*y,c*y) - 3*kT)/Q; y=tanh({}*v/c); c=sqrt({}*kT/m)'.format(
+            (self._n + 1) / (self._alpha * self._n), self._alpha, self._an)
+
+    _scaling = _RegulatedNoseHooverLangevin._twice_scaling
+
+
+class TwiceRegulatedGlobalNoseHooverLangevinPropagator(_RegulatedNoseHooverLangevin):
+    """Twice-regulated global Nose-Hoover-Langevin (interface of propagators.py:2010-2117): one global v_eta driven by
+    G = ((n+1)/(alpha_n n) sum_mvv - N_f kT)/Q, sum_mvv = sum of m (c tanh(alpha_n v/c))^2 over the degrees of freedom (a ComputeSum
+    ahead of every use), Q = 3 kT tau^2."""
+
+    def __init__(self, degreesOfFreedom, temperature, n, timeScale, frictionConstant, alpha_n=1, split=False):
+        super().__init__(alpha_n, n, split)
+        self._Nf = degreesOfFreedom
+        kT = kB * temperature
+        Q = 3 * kT * timeScale ** 2
+        self.globalVariables['kT'] = kT
+        self.globalVariables['Q'] = Q
+        self.globalVariables['omega'] = unit.sqrt(kT / Q)
+        self.globalVariables['friction'] = frictionConstant
+        self.globalVariables['sum_mvv'] = 0
+        self.globalVariables['v_eta'] = 0
+
+    _scaling = _RegulatedNoseHooverLangevin._twice_scaling
+
+    def addSteps(self, integrator, fraction=1.0, force='f'):
+        G = '; G=({}*sum_mvv - {}*kT)/Q'.format((self._n + 1) / (self._alpha * self._n), self._Nf)
+        total = 'sum sum_mvv <- m*(c*tanh({}*v/c))^2; c=sqrt({}*kT/m)'.format(self._alpha, self._an)
+        boost = 'global v_eta <- v_eta + G*{}*dt{}'.format(0.5 * fraction, G)
+        OU = (self.OU if self._split else self.OU_DRIFT).format(noise=self.NOISE, G=G)
+        OU = 'global v_eta <- {}; z=exp(-friction*{}*dt)'.format(OU, fraction)
+        scaling = 'dof v <- ' + self._scaling(fraction)
+        if self._split:
+            play(integrator, '\n'.join([total, boost, scaling, OU, scaling, total, boost]))
+        else:
+            play(integrator, '\n'.join([scaling, total, OU, scaling]))

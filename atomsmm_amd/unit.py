@@ -197,6 +197,11 @@ class Quantity:
             yield Quantity(v, self.unit)
 
 
+def sqrt(x):
+    """simtk.unit.sqrt: the square root of a quantity (its unit too) or of a number."""
+    return x.sqrt() if isinstance(x, Quantity) else math.sqrt(x)
+
+
 def is_quantity(x):
     return isinstance(x, Quantity)
 

@@ -99,7 +99,8 @@ enum {
     AMM_OP_EVAL = 1,   /* a = group: buffer[group_slot(a)] <- sum of the group's forces at current x */
     AMM_OP_KICK = 2,   /* v <- v + coef*(buf[a] -/+ buf[b])/m  (b = -1: single buffer; c = 1: plus)  propagators.py:271,
                           force expressions (f0), (f2-f1), (f0+fm1) ... of propagators.py:917-928 */
-    AMM_OP_MOVE = 3,   /* x <- x + coef*v                                                propagators.py:249 */
+    AMM_OP_MOVE = 3,   /* x <- x + coef*v                                                propagators.py:249
+                          (regulated mode, amm_regulated_define: x <- x + c tanh(alpha v/c) coef)         */
     AMM_OP_COPY = 4,   /* buf[a] <- buf[b]                          integrators.py:139-144 (`_f2_ <- f2`)    */
     AMM_OP_COMBINE = 5,/* buf[a] <- buf[b] + coef*buf[c]            propagators.py:951 (`fm2 <- f2-f1`)       */
     AMM_OP_EXPR = 6,   /* buf[b] <- per-DOF expression a (amm_expr_define): bath steps inside a RESPA loop, e.g. a
@@ -282,6 +283,19 @@ int amm_bath_define_nhl(amm_ctx *ctx, double h, double z, double kT, double Q, d
  * (Q2 friction) ; v1 <- v1 exp(-h v2) ; rescale -- as ONE AMM_OP_BATH (v2 in slot_v2; needs the isokinetic mode). */
 int amm_iso_define(amm_ctx *ctx, int32_t on, double LkT, double Q1, int32_t slot_v1);
 int amm_bath_define_sin(amm_ctx *ctx, double h, double z, double kT, double Q2, double friction, int32_t slot_v2, int32_t *bath_id);
+/* Regulated dynamics (RegulatedTranslationPropagator and the regulated Nose-Hoover-Langevin baths, propagators.py:1537-2007).
+ * amm_regulated_define(on = 1) puts the context in regulated mode: every AMM_OP_MOVE becomes
+ *   x <- x + c tanh(alpha v / c) coef,  c = sqrt(an_kT / m)      (an_kT = alpha_n n kT)
+ * so that no degree of freedom moves faster than c; the fused epilogues of the pair-force launches are not planned then.
+ * amm_bath_define_regulated registers the bath block of one regulated propagator as ONE AMM_OP_BATH: kind 3 regulated massive,
+ * 4 twice-regulated massive, 5 regulated atomic, 6 twice-regulated atomic Nose-Hoover-Langevin.  The block is
+ *   [w <- w + G h ;] v <- S(v, w) ; w <- w z [+ G (1 - z)/friction] + omega sqrt(1 - z^2) gaussian ; v <- S(v, w) [; w <- w + G h]
+ * (bracketed boosts with split = 1, the drift term without), h = (fraction/2) dt, z = exp(-friction fraction dt); G and the
+ * scaling S as the reference writes them (an = alpha_n n; Q = kT tau^2, or 3 kT tau^2 for the atomic kinds).  w is the per-DOF
+ * buffer slot_v_eta; the atomic kinds keep one w per atom in all three components and draw the gaussian of its x component. */
+int amm_regulated_define(amm_ctx *ctx, int32_t on, double alpha, double an_kT);
+int amm_bath_define_regulated(amm_ctx *ctx, int32_t kind, int32_t split, double h, double z, double kT, double Q, double omega,
+                              double friction, double alpha, double an, int32_t slot_v_eta, int32_t *bath_id);
 
 int amm_bind_state(amm_ctx *ctx, double *d_x, double *d_v, const double *d_mass);
 #define AMM_MAX_SLOTS 64

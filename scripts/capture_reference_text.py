@@ -97,6 +97,7 @@ class CustomIntegrator:
         self._dt = float(stepSize)
         self.globals_, self.perdof, self.steps = [], [], []
         self.seed = None
+        self.kinetic = None
 
     def getStepSize(self): return Q(self._dt)
     def setStepSize(self, v): self._dt = float(v)
@@ -132,7 +133,7 @@ class CustomIntegrator:
     def getRandomNumberSeed(self): return self.seed or 0
     def setConstraintTolerance(self, tol): pass
     def getConstraintTolerance(self): return 1e-5
-    def setKineticEnergyExpression(self, e): pass
+    def setKineticEnergyExpression(self, e): self.kinetic = e
     def step(self, n): pass
 
 
@@ -359,6 +360,38 @@ PROGRAMS = {
     'afed_periodic_langevin': 'atomsmm.AdiabaticDynamicsIntegrator(atomsmm.RespaPropagator([2, 1]).integrator(1*unit.femtoseconds), 1, [atomsmm.ExtendedSystemVariable("phi", 100, 2.5, 40*unit.femtoseconds, -3.14, 3.14, periodic=True, thermostat="langevin")])',
 }
 
+# the regulated propagators (propagators.py:1537-2117) as the one-GPU-pass RESPA composition uses them: each bath class in the
+# innermost loop of MultipleTimeScaleIntegrator([4, 2, 1]), split off and on, plus n / alpha_n != 1, scheme='xo-respa' and the
+# adiabatic / global variants -> tests/golden/regulated_programs.json (with the kinetic-energy expression)
+N_REG, REG = '2', 'atomsmm.propagators.'
+_REG_MTS = 'atomsmm.integrators.MultipleTimeScaleIntegrator(4*unit.femtoseconds, [4, 2, 1], move=%sRegulatedTranslationPropagator(%s, %s%s), boost=%sRegulatedBoostPropagator(), bath=%s%s%s)'
+_REG_BATHS = {
+    'massive': 'RegulatedMassiveNoseHooverLangevinPropagator(%s, {n}, %s, %s{kw})' % (T, TAU, GAMMA),
+    'twice_massive': 'TwiceRegulatedMassiveNoseHooverLangevinPropagator(%s, {n}, %s, %s{kw})' % (T, TAU, GAMMA),
+    'atomic': 'RegulatedAtomicNoseHooverLangevinPropagator(%s, {n}, %s, %s{kw})' % (T, TAU, GAMMA),
+    'twice_atomic': 'TwiceRegulatedAtomicNoseHooverLangevinPropagator(%s, {n}, %s, %s{kw})' % (T, TAU, GAMMA),
+    'twice_global': 'TwiceRegulatedGlobalNoseHooverLangevinPropagator(3000, %s, {n}, %s, %s{kw})' % (T, TAU, GAMMA),
+}
+
+
+def _reg(bath, n=N_REG, alpha='', split=False, extra='', tail=''):
+    kw = (', alpha_n=%s' % alpha if alpha else '') + (', split=True' if split else '') + extra
+    return _REG_MTS % (REG, T, n, ', alpha_n=%s' % alpha if alpha else '', REG, REG, _REG_BATHS[bath].format(n=n, kw=kw), tail)
+
+
+REGULATED = {
+    **{'reg_%s%s' % (bath, '_split' if split else ''): _reg(bath, split=split) for bath in _REG_BATHS for split in (False, True)},
+    'reg_massive_n3_alpha2': _reg('massive', n='3', alpha='2'),
+    'reg_twice_massive_n3_alpha2_split': _reg('twice_massive', n='3', alpha='2', split=True),
+    'reg_twice_atomic_n3_alpha2': _reg('twice_atomic', n='3', alpha='2'),
+    'reg_massive_xo_respa': _reg('massive', tail=', scheme="xo-respa"'),
+    'reg_twice_atomic_split_xo_respa': _reg('twice_atomic', split=True, tail=', scheme="xo-respa"'),
+    'reg_massive_adiabatic': _reg('massive', extra=', adiabatic=True'),
+    'reg_twice_massive_adiabatic_split': _reg('twice_massive', split=True, extra=', adiabatic=True'),
+    'reg_translation': REG + 'RegulatedTranslationPropagator(%s, 4, alpha_n=1.5).integrator(1*unit.femtoseconds)' % T,
+    'reg_boost': REG + 'RegulatedBoostPropagator().integrator(1*unit.femtoseconds)',
+}
+
 # a-2 ... a-6: energy strings after importFrom(nonbonded) of a two-particle CutoffPeriodic force
 FORCES = {
     'near_none': 'atomsmm.NearNonbondedForce(0.7*unit.nanometers, 0.5*unit.nanometers, None)',
@@ -398,15 +431,9 @@ def patch_sympy():
     sympy_parser.parse_expr = parse_expr
 
 
-def capture(reference):
-    mm, unit = install_stand_in()
-    patch_sympy()
-    sys.path.insert(0, reference)
-    import atomsmm                       # the REFERENCE (sys.path[0]); this script never imports atomsmm_amd
-    assert os.path.realpath(os.path.dirname(atomsmm.__file__)).startswith(os.path.realpath(reference))
-    ns = {'atomsmm': atomsmm, 'unit': unit, 'openmm': mm}
-    programs, failed = {}, {}
-    for name, ctor in PROGRAMS.items():
+def _programs(table, ns, failed, kinetic=False):
+    programs = {}
+    for name, ctor in table.items():
         try:
             integ = eval(ctor, ns)
         except Exception as exc:          # e.g. a scheme the reference itself cannot build: recorded, not hidden
@@ -414,6 +441,21 @@ def capture(reference):
             continue
         programs[name] = {'ctor': ctor, 'per_dof': list(integ.perdof), 'globals': [g[0] for g in integ.globals_],
                           'global_values': {g[0]: g[1] for g in integ.globals_}, 'steps': pretty_steps(integ)}
+        if kinetic:
+            programs[name]['kinetic'] = integ.kinetic
+    return programs
+
+
+def capture(reference):
+    mm, unit = install_stand_in()
+    patch_sympy()
+    sys.path.insert(0, reference)
+    import atomsmm                       # the REFERENCE (sys.path[0]); this script never imports atomsmm_amd
+    assert os.path.realpath(os.path.dirname(atomsmm.__file__)).startswith(os.path.realpath(reference))
+    ns = {'atomsmm': atomsmm, 'unit': unit, 'openmm': mm}
+    failed, regulated_failed = {}, {}
+    programs = _programs(PROGRAMS, ns, failed)
+    regulated = _programs(REGULATED, ns, regulated_failed, kinetic=True)
     forces = {}
     for name, ctor in FORCES.items():
         nb = mm.NonbondedForce()
@@ -430,15 +472,17 @@ def capture(reference):
             continue
         forces[name] = {'ctor': ctor, 'energy': force.getEnergyFunction(),
                         'globals': {n: v for n, v in force.globals_} if hasattr(force, 'globals_') else {}}
-    return programs, forces, failed
+    return programs, forces, failed, regulated, regulated_failed
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reference', default='/root/reference/src')
     ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests', 'golden', 'programs.json'))
+    ap.add_argument('--regulated-out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests', 'golden',
+                                                            'regulated_programs.json'))
     args = ap.parse_args()
-    programs, forces, failed = capture(args.reference)
+    programs, forces, failed, regulated, regulated_failed = capture(args.reference)
     doc = {'_comment': 'Captured by scripts/capture_reference_text.py from the reference\'s Python layer (AtomsMM v0.1.0, /root/reference/src/atomsmm: '
                        'propagators.py, integrators.py, forces.py) under a recording stand-in for simtk; data only -- constructor expressions and the '
                        'text they emit.  "failed": constructor expressions the reference itself raises on (its defects, SURVEY Appendix A).',
@@ -447,6 +491,15 @@ def main():
         json.dump(doc, fh, indent=1, sort_keys=True)
     print('%d programs, %d force strings, %d failed -> %s' % (len(programs), len(forces), len(failed), args.out))
     for name, info in failed.items():
+        print('  failed %s: %s' % (name, info['error']))
+    doc = {'_comment': 'Captured by scripts/capture_reference_text.py from the reference\'s Python layer (AtomsMM v0.1.0, propagators.py:1537-2117, '
+                       'integrators.py) under a recording stand-in for simtk; data only -- constructor expressions, the text they emit and the '
+                       'kinetic-energy expression they set.',
+           'programs': regulated, 'failed': regulated_failed}
+    with open(args.regulated_out, 'w') as fh:
+        json.dump(doc, fh, indent=1, sort_keys=True)
+    print('%d regulated programs, %d failed -> %s' % (len(regulated), len(regulated_failed), args.regulated_out))
+    for name, info in regulated_failed.items():
         print('  failed %s: %s' % (name, info['error']))
 
 
