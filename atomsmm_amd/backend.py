@@ -40,6 +40,8 @@ EXPORTS = [
     'amm_comm_unique_id', 'amm_comm_init', 'amm_comm_destroy', 'amm_comm_allreduce', 'amm_comm_stats', 'amm_group_set_exchange', 'amm_bind_exchange', 'amm_exchange_finish',
     'amm_set_option', 'amm_positions_changed', 'amm_exchange_per', 'amm_run_stats', 'amm_run_ops_from', 'amm_exchange_pending',
     'amm_pair_energy_states',
+    'amm_min_create', 'amm_min_release', 'amm_min_begin', 'amm_min_advance', 'amm_min_trial', 'amm_min_scalars', 'amm_min_stats',
+    'amm_min_read',
 ]
 
 
@@ -196,6 +198,14 @@ def lib():
         L.amm_positions_changed.argtypes = [vp]
         L.amm_exchange_per.argtypes = [vp, ip]
         L.amm_expr_eval.argtypes = [vp, ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, C.c_uint64, C.c_uint64, vp, vp]
+        L.amm_min_create.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, vp, vp, ip]
+        L.amm_min_release.argtypes = [vp, C.c_int32]
+        L.amm_min_begin.argtypes = [vp, C.c_int32, vp, vp]
+        L.amm_min_advance.argtypes = [vp, C.c_int32, vp, vp]
+        L.amm_min_trial.argtypes = [vp, C.c_int32, C.c_double, vp]
+        L.amm_min_scalars.argtypes = [vp, C.c_int32, dp]
+        L.amm_min_stats.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
+        L.amm_min_read.argtypes = [vp, C.c_int32, C.c_int32, dp]
         for name in EXPORTS:
             if name not in ('amm_last_error', 'amm_kernel_revision'):
                 getattr(L, name).restype = C.c_int
@@ -466,6 +476,49 @@ class HipContext:
 
     def force_eval(self, fid, pos, force, accumulate=False, energy=None):
         _chk(lib().amm_force_eval(self.h, fid, _ptr(pos), _ptr(force), int(bool(accumulate)), _ptr(energy)))
+
+    # ---- energy minimisation (csrc/minimize.hip): the L-BFGS vectors of LocalEnergyMinimizer.minimize on the device
+    def min_create(self, scalars, mass=None, memory=8, max_step=0.1, force_input=True):
+        """A minimiser object.  scalars: 8 doubles on the device (include/atomsmm_hip.h: amm_min_create) -- evaluations add the
+        energy to scalars[0]; mass: [n] or None; force_input: begin / advance are handed forces, not gradients.  The caller keeps
+        both tensors alive until min_release."""
+        assert scalars.numel() >= 8
+        mid = C.c_int32(-1)
+        _chk(lib().amm_min_create(self.h, int(memory), float(max_step), int(bool(force_input)), _ptr(mass), _ptr(scalars), C.byref(mid)))
+        return mid.value
+
+    def min_release(self, mid):
+        _chk(lib().amm_min_release(self.h, mid))
+
+    def min_begin(self, mid, x=None, g=None):
+        """Start at (x, g); without arguments: clear the history and go back to steepest descent at the stored point."""
+        _chk(lib().amm_min_begin(self.h, mid, _ptr(x), _ptr(g)))
+
+    def min_advance(self, mid, x, g):
+        _chk(lib().amm_min_advance(self.h, mid, _ptr(x), _ptr(g)))
+
+    def min_trial(self, mid, alpha, x_out):
+        _chk(lib().amm_min_trial(self.h, mid, float(alpha), _ptr(x_out)))
+
+    def min_scalars(self, mid):
+        """(E, g.d, g.g, max|g|, newest pair dropped, pairs in use, step factor of the last trial, largest |d_atom|^2); waits for the stream."""
+        out = (C.c_double * 8)()
+        _chk(lib().amm_min_scalars(self.h, mid, out))
+        return list(out)
+
+    def min_stats(self, mid):
+        out = (C.c_int64 * 8)()
+        _chk(lib().amm_min_stats(self.h, mid, out))
+        return dict(pairs=out[0], trials=out[1], dropped=out[2], restarts=out[3], resets=out[4], in_use=out[5], memory=out[6])
+
+    def min_read(self, mid, what, memory=None):
+        """Inspection (tests): 'gram' -> (2m+1, 2m+1), 'delta' -> (2m+1,), 'direction' -> (n, 3) numpy arrays."""
+        m = memory if memory is not None else self.min_stats(mid)['memory']
+        nb = 2 * m + 1
+        shape = {'gram': (nb, nb), 'delta': (nb,), 'direction': (self.n, 3)}[what]
+        out = np.zeros(shape, dtype=np.float64)
+        _chk(lib().amm_min_read(self.h, mid, ['gram', 'delta', 'direction'].index(what), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
 
     # ---- step primitives
     def kick(self, v, f, mass, coef, fsub=None, fadd=None):

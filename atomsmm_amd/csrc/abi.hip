@@ -95,6 +95,7 @@ int amm_destroy(amm_ctx *ctx) {
     if (ctx->d_expr_part) (void)hipFree(ctx->d_expr_part);
     if (ctx->d_fscratch) (void)hipFree(ctx->d_fscratch);
     if (ctx->constraints) amm_constraints_free(ctx->constraints);
+    for (MinObj *mo : ctx->minimizers) amm_min_free(mo);
     if (ctx->alt_x) (void)hipFree(ctx->alt_x);
     if (ctx->alt_v) (void)hipFree(ctx->alt_v);
     if (ctx->alt_f) (void)hipFree(ctx->alt_f);
@@ -765,6 +766,30 @@ int amm_positions_changed(amm_ctx *ctx) {
     ctx->pos_epoch++;
     return 0;
 }
+
+int amm_min_create(amm_ctx *ctx, int32_t memory, double max_step, int32_t force_input, const double *d_mass, double *d_scalars,
+                   int32_t *min_id) {
+    if (!ctx || !d_scalars || !min_id) {
+        amm_set_error("amm_min_create: bad arguments");
+        return 1;
+    }
+    int id = -1;
+    if (amm_min_create_impl(ctx, memory, max_step, force_input, d_mass, d_scalars, &id)) return 1;
+    *min_id = id;
+    return 0;
+}
+int amm_min_release(amm_ctx *ctx, int32_t min_id) { return amm_min_release_impl(ctx, min_id); }
+int amm_min_begin(amm_ctx *ctx, int32_t min_id, const double *d_x, const double *d_g) { return amm_min_begin_impl(ctx, min_id, d_x, d_g); }
+int amm_min_advance(amm_ctx *ctx, int32_t min_id, const double *d_x, const double *d_g) {
+    return amm_min_advance_impl(ctx, min_id, d_x, d_g);
+}
+int amm_min_trial(amm_ctx *ctx, int32_t min_id, double alpha, double *d_x_out) {
+    if (ctx) ctx->pos_epoch++;            // (the output may be the bound position buffer: as amm_move)
+    return amm_min_trial_impl(ctx, min_id, alpha, d_x_out);
+}
+int amm_min_scalars(amm_ctx *ctx, int32_t min_id, double out[8]) { return amm_min_scalars_impl(ctx, min_id, out); }
+int amm_min_stats(amm_ctx *ctx, int32_t min_id, int64_t out[8]) { return amm_min_stats_impl(ctx, min_id, out); }
+int amm_min_read(amm_ctx *ctx, int32_t min_id, int32_t what, double *h_out) { return amm_min_read_impl(ctx, min_id, what, h_out); }
 
 int amm_kick(amm_ctx *ctx, double *d_v, const double *d_f, const double *d_f2, int32_t plus, const double *d_mass, double coef) {
     return amm_kick_impl(ctx, d_v, d_f, d_f2, plus, d_mass, coef);

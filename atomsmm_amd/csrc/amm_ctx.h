@@ -222,6 +222,7 @@ struct BondedSet {
 
 struct PmeForce;      // pme.hip
 struct ConstraintSet; // constraints.hip
+struct MinObj;        // minimize.hip: one L-BFGS minimisation (history ring, Gram matrix, direction)
 
 struct ForceObj {
     int type = 0;   // 1 pair, 2 bonded, 3 PME reciprocal space
@@ -382,6 +383,7 @@ struct amm_ctx {
     double *d_expr_part = nullptr; // block partial sums of amm_expr_eval
     double *d_fscratch = nullptr;  // [n][3] force sink of amm_pair_energy_derivative
     ConstraintSet *constraints = nullptr;   // distance constraints of the System (AMM_OP_CONSTRAIN_*)
+    std::vector<MinObj *> minimizers;       // amm_min_create (ids are positions, never reused)
     std::vector<ExprDef> exprs;    // registered per-DOF expressions (AMM_OP_EXPR)
     std::vector<BathDef> baths;    // registered baths (AMM_OP_BATH)
     IsoDef iso;                    // isokinetic mode: what AMM_OP_KICK means (amm_iso_define)
@@ -506,3 +508,12 @@ int amm_move_impl(amm_ctx *ctx, double *d_x, const double *d_v, double coef);
 int amm_copy_impl(amm_ctx *ctx, double *d_dst, const double *d_src);
 int amm_mvv_impl(amm_ctx *ctx, const double *d_v, const double *d_m, double *d_out);
 int amm_reduce_add(amm_ctx *ctx, const double *d_part, int n, double scale, double *d_out);
+int amm_min_create_impl(amm_ctx *ctx, int memory, double max_step, int force_input, const double *d_mass, double *d_scalars, int *id);
+int amm_min_release_impl(amm_ctx *ctx, int id);
+int amm_min_free(MinObj *mo);
+int amm_min_begin_impl(amm_ctx *ctx, int id, const double *d_x, const double *d_g);
+int amm_min_advance_impl(amm_ctx *ctx, int id, const double *d_x, const double *d_g);
+int amm_min_trial_impl(amm_ctx *ctx, int id, double alpha, double *d_x_out);
+int amm_min_scalars_impl(amm_ctx *ctx, int id, double out[8]);
+int amm_min_stats_impl(amm_ctx *ctx, int id, int64_t out[8]);
+int amm_min_read_impl(amm_ctx *ctx, int id, int what, double *h_out);

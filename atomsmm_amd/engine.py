@@ -1309,6 +1309,161 @@ class Engine:
             self.ctx.run_ops([B.Op(B.OP_CONSTRAIN_V, 0, 0, 0, 0.0)], 1)
             self._check()
 
+    # ------------------------------------------------------------------------------- energy minimisation
+    def _constraint_errors(self, pairs, dist):
+        """Largest relative error |r - d| / d over the constrained pairs at the current positions (minimum image; on the device)."""
+        torch = self.torch
+        box = torch.as_tensor(self.box, device=self.x.device)
+        d = self.x[pairs[:, 0]] - self.x[pairs[:, 1]]
+        d = d - box * torch.round(d / box)
+        return float((torch.abs(torch.linalg.norm(d, dim=1) - dist) / dist).max().item())
+
+    def minimize(self, tolerance=10.0, max_iterations=0, reporter=None, memory=8, max_step=0.1):
+        """LocalEnergyMinimizer.minimize: L-BFGS on the sum of all force groups until the RMS of the free force components is
+        <= tolerance (kJ/mol/nm) or max_iterations (0: no limit) iterations are done.  Positions only: velocities, time, per-DOF
+        variables, parameters and the random stream stay as they are.  With constraints (as OpenMM): start on the constraint surface,
+        minimise with harmonic restraints k (r - d)^2 / 2 over the constrained pairs, stiffen k tenfold while the largest relative
+        constraint error exceeds the integrator's tolerance, finish with applyConstraints().  reporter(iteration, x, grad, args) ->
+        stop?, x and grad fetched only when one is given.  Returns dict(iterations, evaluations, energy, reason, ...)."""
+        if self.world > 1:
+            raise InputError('minimisation runs on a single rank')
+        tolerance, max_iterations = float(tolerance), int(max_iterations)
+        if not tolerance > 0:
+            raise ValueError('minimize: the tolerance must be positive')
+        torch = self.torch
+        dev = self.x.device
+        result = dict(iterations=0, evaluations=0, passes=0, restraint_strength=0.0)
+        if self._has_constraints:
+            cons = self.system._constraints
+            pairs = np.array([[c[0], c[1]] for c in cons], dtype=np.int32)
+            dist = np.array([c[2] for c in cons], dtype=np.float64)
+            d_pairs, d_dist = torch.as_tensor(pairs.astype(np.int64), device=dev), torch.as_tensor(dist, device=dev)
+            ctol = self.integrator.getConstraintTolerance() if hasattr(self.integrator, 'getConstraintTolerance') else 1e-5
+            self.apply_constraints()
+            k = 100.0 / max(1e-4, ctol)          # (OpenMM's first strength)
+            for _ in range(9):                   # k grows by 10^8 at most: beyond that the restraints swamp fp64 sums of the energy
+                rid = self._make_bonded([(B.BOND_HARMONIC, pairs, np.stack([dist, np.full(len(dist), k)], axis=1), True, None)], sliced=False)
+                try:
+                    done = self._minimize_pass(tolerance, max_iterations, reporter, memory, max_step, rid, k,
+                                               lambda: self._constraint_errors(d_pairs, d_dist), result)
+                finally:
+                    self.ctx.bonded_release(rid)
+                error = self._constraint_errors(d_pairs, d_dist)
+                result.update(restraint_strength=k, max_constraint_error=error)
+                if error <= ctol or done == 'reporter':
+                    break
+                k *= 10.0
+            self.apply_constraints()
+        else:
+            self._minimize_pass(tolerance, max_iterations, reporter, memory, max_step, None, 0.0, lambda: 0.0, result)
+        self._invalidate_forces()
+        return result
+
+    def _minimize_pass(self, tolerance, max_iterations, reporter, memory, max_step, restraint, strength, constraint_error, result):
+        """One L-BFGS minimisation from the current positions (csrc/minimize.hip holds the vectors; this is the line search).  The host
+        reads one block of eight scalars per energy evaluation -- the energy the line search needs, with g.d, g.g and the step factor
+        riding along -- and nothing else."""
+        torch, ctx = self.torch, self.ctx
+        dev, f64 = self.x.device, torch.float64
+        scal = torch.zeros(8, dtype=f64, device=dev)
+        force = torch.zeros((self.n, 3), dtype=f64, device=dev)
+        nfree = 3 * int(np.count_nonzero(np.asarray(self.system._masses, dtype=np.float64) > 0))
+        if nfree == 0:
+            result.update(reason='converged', energy=float('nan'))
+            return 'converged'
+        const = sum(entry.constant for entry in self.entries)
+
+        def evaluate(read=True):
+            # (every group, as get_state does; the energies add up in scal[0], which amm_min_trial / the zeroing above cleared)
+            force.zero_()
+            for entry in self.entries:
+                for pid in entry.pair_ids:
+                    ctx.force_eval(pid, self.x, force, accumulate=True, energy=scal)
+                if entry.bonded_id is not None:
+                    ctx.force_eval(entry.bonded_id, self.x, force, accumulate=True, energy=scal)
+                if entry.recip is not None:
+                    ctx.force_eval(entry.recip, self.x, force, accumulate=True, energy=scal)
+            if restraint is not None:
+                ctx.force_eval(restraint, self.x, force, accumulate=True, energy=scal)
+            result['evaluations'] += 1
+            if not read:
+                return None
+            s = ctx.min_scalars(mid)          # the evaluation's one wait
+            self._check()                     # a neighbour-row overflow raises instead of corrupting the search
+            return s
+
+        def report(iteration, energy):
+            e_restraint = 0.0
+            if restraint is not None:
+                tmp, sink = torch.zeros(1, dtype=f64, device=dev), torch.zeros_like(force)
+                ctx.force_eval(restraint, self.x, sink, accumulate=False, energy=tmp)
+                e_restraint = tmp.item()
+            args = {'system energy': energy - e_restraint, 'restraint energy': e_restraint, 'restraint strength': strength,
+                    'max constraint error': constraint_error()}
+            return bool(reporter.report(iteration, self.x.cpu().numpy().ravel().tolist(), (-force).cpu().numpy().ravel().tolist(), args))
+
+        def moved():
+            # the Verlet lists' displacement checks must see the move (amm_min_trial says so itself; this is the engine's own rule
+            # for every write of self.x)
+            ctx.positions_changed()
+            self._invalidate_forces()
+
+        mid = ctx.min_create(scal, mass=self.mass, memory=memory, max_step=max_step, force_input=True)
+        try:
+            result['passes'] += 1
+            evaluate(read=False)
+            ctx.min_begin(mid, self.x, force)
+            s = ctx.min_scalars(mid)
+            self._check()
+            energy = s[0] + const
+            iteration, reason = 0, None
+            if math.sqrt(s[2] / nfree) <= tolerance:
+                reason = 'converged'
+            alpha = min(1.0, 1.0 / math.sqrt(s[2])) if s[2] > 0 else 1.0
+            steepest, pending = True, False
+            while reason is None:
+                accepted = False
+                for _ in range(21):           # alpha, then at most 20 halvings
+                    ctx.min_trial(mid, alpha, self.x)
+                    moved()
+                    s = evaluate()
+                    if pending:               # the first read after an advance: g.g of the point the line search starts from
+                        pending = False
+                        steepest = s[5] == 0
+                        if math.sqrt(s[2] / nfree) <= tolerance:
+                            reason = 'converged'
+                            break
+                    trial_energy = s[0] + const
+                    if math.isfinite(trial_energy) and trial_energy <= energy + 1e-4 * s[6] * s[1]:
+                        accepted = True
+                        break
+                    alpha = 0.5 * s[6]
+                if reason is not None or not accepted:
+                    if reason is None and not steepest:
+                        ctx.min_begin(mid)    # clear the history, steepest descent from the same point
+                        steepest, alpha = True, 1.0
+                        continue
+                    reason = reason or 'no progress'
+                    ctx.min_trial(mid, 0.0, self.x)       # back to the point the line search started from
+                    moved()
+                    break
+                energy = trial_energy
+                stop = report(iteration, energy) if reporter is not None else False
+                iteration += 1
+                if stop:
+                    reason = 'reporter'
+                elif max_iterations and iteration >= max_iterations:
+                    reason = 'max iterations'
+                else:
+                    ctx.min_advance(mid, self.x, force)
+                    pending, alpha = True, 1.0
+            stats = ctx.min_stats(mid)
+        finally:
+            ctx.min_release(mid)
+        result['iterations'] += iteration
+        result.update(reason=reason, energy=energy, dropped_pairs=stats['dropped'], restarts=stats['restarts'])
+        return reason
+
     def _eval(self, expr, env):
         code = _CODE_CACHE.get(expr)
         if code is None:

@@ -996,4 +996,34 @@ class Context:
         self._engine.reinitialize(preserveState)
 
 
+class MinimizationReporter:
+    """openmm.MinimizationReporter (OpenMM 8.1): subclass it and override report(); an instance handed to
+    LocalEnergyMinimizer.minimize / Simulation.minimizeEnergy is called once per L-BFGS iteration."""
+
+    def report(self, iteration, x, grad, args):
+        """iteration: 0, 1, ...; x, grad: flat sequences of 3N numbers (nm, kJ/mol/nm); args: 'system energy', 'restraint energy'
+        (kJ/mol), 'restraint strength' (kJ/mol/nm^2), 'max constraint error' (relative).  Return True to stop the minimisation."""
+        return False
+
+
+class LocalEnergyMinimizer:
+    """openmm.LocalEnergyMinimizer: L-BFGS on the Context's potential energy, positions left in the Context.  The vectors and the
+    energy evaluations stay on the GPU (csrc/minimize.hip, Engine.minimize)."""
+
+    @staticmethod
+    def minimize(context, tolerance=10.0, maxIterations=0, reporter=None):
+        """tolerance: RMS force at which to stop, a Quantity of energy / length or a number of kJ/mol/nm; maxIterations = 0: until
+        converged."""
+        if isinstance(tolerance, Quantity):
+            tolerance = md_value(tolerance, kjmol / nm)
+        tolerance, maxIterations = float(tolerance), int(maxIterations)
+        if not tolerance > 0:
+            raise OpenMMException('LocalEnergyMinimizer: the tolerance must be positive')
+        if maxIterations < 0:
+            raise OpenMMException('LocalEnergyMinimizer: maxIterations must not be negative')
+        if reporter is not None and not callable(getattr(reporter, 'report', None)):
+            raise TypeError('LocalEnergyMinimizer: reporter must be a MinimizationReporter')
+        context._engine.minimize(tolerance, maxIterations, reporter)
+
+
 from . import app  # noqa: E402,F401

@@ -504,6 +504,12 @@ class Simulation:
         self.currentStep = 0
         self.reporters = []
 
+    def minimizeEnergy(self, tolerance=10.0, maxIterations=0, reporter=None):
+        """Local energy minimisation from the Context's positions (LocalEnergyMinimizer.minimize); tolerance in kJ/mol/nm or a
+        Quantity, maxIterations = 0: until converged."""
+        from . import LocalEnergyMinimizer
+        LocalEnergyMinimizer.minimize(self.context, tolerance, maxIterations, reporter)
+
     def step(self, steps):
         """Advance by `steps`, serving `self.reporters` with OpenMM's reporter protocol: `describeNextReport(simulation)` ->
         (steps until the next report, positions?, velocities?, forces?, energies?[, wrap?]) and `report(simulation, state)`."""

@@ -344,6 +344,47 @@ int amm_exchange_per(amm_ctx *ctx, int32_t *per);
 /* amm_run_ops fuses KICK;MOVE;EVAL(bond-list group);KICK into one launch (bit-identical results); 0 disables. */
 int amm_set_fuse_inner(amm_ctx *ctx, int32_t on);
 
+/* ---- energy minimisation --------------------------------------------------------------------- */
+/* LocalEnergyMinimizer::minimize(context, tolerance, maxIterations) of OpenMM, which the reference reaches through
+ * app.Simulation.minimizeEnergy (the line every AtomsMM script runs before simulation.step): OpenMM runs L-BFGS on the host over
+ * positions it copies to and from the platform at every evaluation.  Here the L-BFGS vectors live on the device (csrc/minimize.hip,
+ * Gram-matrix form of the two-loop recursion): the caller evaluates energies and forces with amm_force_eval, the object below keeps
+ * the history of steps and gradient differences, makes search directions and trial positions, and hands the line search one block
+ * of eight scalars per evaluation.  The line search itself (a few comparisons per evaluation) is the caller's.
+ *
+ * amm_min_create: memory = pairs (s, y) kept, 1 .. 8; max_step (nm; <= 0: 0.1) = the farthest any atom moves in one trial;
+ * force_input = 1: the d_g arguments below hold FORCES (minus the gradient), as amm_force_eval leaves them; d_mass ([n], caller-owned,
+ * may be NULL): atoms of mass 0 never move and their gradient counts as zero (OpenMM's massless particles); d_scalars: 8 doubles of
+ * device memory, caller-owned, zeroed here --
+ *   [0] E         the caller's evaluations ADD the energy here (amm_force_eval's d_energy); amm_min_trial sets it to 0
+ *   [1] g.d       slope along the current direction (< 0)          [2] g.g over the free components
+ *   [3] max|g_i|  over the free components                         [4] 1 if the newest pair failed the curvature test
+ *   [5] pairs in use (0: d = -g)                                   [6] the step factor the last amm_min_trial used
+ *   [7] largest |d_atom|^2 over the atoms
+ * Sums are fixed-order: two runs give the same bits.  Everything is enqueued on the context's stream; only amm_min_scalars,
+ * amm_min_stats, amm_min_read and amm_min_release wait for it. */
+int amm_min_create(amm_ctx *ctx, int32_t memory, double max_step, int32_t force_input, const double *d_mass, double *d_scalars,
+                   int32_t *min_id);
+int amm_min_release(amm_ctx *ctx, int32_t min_id);
+/* Start at (d_x, d_g): x_prev <- x, g_prev <- g, history cleared, direction d = -g.  With d_x = d_g = NULL: keep the stored point,
+ * clear the history and return to d = -g (the restart of a line search that found no step).  lbfgs() start / restart. */
+int amm_min_begin(amm_ctx *ctx, int32_t min_id, const double *d_x, const double *d_g);
+/* The accepted point (d_x, d_g): the pair s = x - x_prev, y = g - g_prev enters the ring (it is dropped again if s.y <= 1e-10 |s||y|),
+ * x_prev <- x, g_prev <- g, and the object's direction buffer receives d = -H g of the two-loop recursion with H0 = (s.y / y.y) I of
+ * the newest pair; d = -g if that is no descent direction.  Three launches: Gram update, coefficients, combination. */
+int amm_min_advance(amm_ctx *ctx, int32_t min_id, const double *d_x, const double *d_g);
+/* d_x_out <- x_prev + a d with a = min(alpha, max_step / largest |d_atom|); atoms of mass 0 (and alpha = 0) copy x_prev bit for bit.
+ * One launch. */
+int amm_min_trial(amm_ctx *ctx, int32_t min_id, double alpha, double *d_x_out);
+/* The scalar block, after waiting for the stream: the one synchronisation of an energy evaluation. */
+int amm_min_scalars(amm_ctx *ctx, int32_t min_id, double out[8]);
+/* out[0] = pairs formed (amm_min_advance calls), [1] = trials, [2] = pairs dropped by the curvature test, [3] = restarts
+ * (amm_min_begin without arguments), [4] = directions replaced by -g because g.d >= 0, [5] = pairs in use, [6] = memory.  Synchronises. */
+int amm_min_stats(amm_ctx *ctx, int32_t min_id, int64_t out[8]);
+/* Test and inspection access (host memory out; synchronises): what = 0 the matrix of dot products, (2m+1)^2 doubles over
+ * [s_0 .. s_{m-1}, y_0 .. y_{m-1}, g] by ring slot; 1 the coefficients delta, 2m+1; 2 the direction d, 3n. */
+int amm_min_read(amm_ctx *ctx, int32_t min_id, int32_t what, double *h_out);
+
 /* ---- measurement ----------------------------------------------------------------------------- */
 typedef struct {
     int64_t n_builds;       /* neighbour-list (re)builds so far                       */
