@@ -144,6 +144,16 @@ struct PairForce {
     double *d_epart = nullptr;
     int n_epart = 0;
     double *d_tab = nullptr;       // radial Coulomb table: pc.tab.nint x 6 doubles (pair_tab.h)
+    unsigned long long tab_serial = 0;     // of this upload of d_tab / d_tab_ss (amm_pair_build_table): no two uploads share one
+    // what the molecule-row kernels stage when this force's Coulomb table comes first in LDS (cluster.hip: cpair_tab_image): the
+    // launch's tables in one array, by what it holds (bit 0: a guest's tables too, bit 1: site-site tables); made of the uploads
+    // with these serial numbers by copies on `stream`
+    struct TabImage {
+        char *d = nullptr;
+        size_t bytes = 0;
+        unsigned long long host_serial = 0, guest_serial = 0;
+        hipStream_t stream = nullptr;
+    } tab_image[4];
     double tab_error = 0;          // largest relative interpolation error found when the table was built
     int *d_cls = nullptr;          // per atom (original order): 1 = no Lennard-Jones site (eps = 0) -- sorted behind the others in its cell
     int *d_cell_count_lj = nullptr, *d_cell_start_lj = nullptr;   // per cell: atoms WITH a Lennard-Jones site (count, exclusive scan)

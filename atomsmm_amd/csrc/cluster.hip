@@ -997,7 +997,7 @@ struct CPairArgs {
     int rpx, nphase;
     int ph_off[AMM_CPHASES], ph_shift[AMM_CPHASES], ph_ntask[AMM_CPHASES];
 #ifdef AMM_CPAIR_TIMING           // measurement builds (scripts/build_variant.sh): wall clock of every wavefront
-    unsigned long long *wave_times;      // [wavefront][4]: kernel entry, tables staged, tasks done, flags (interior tasks << 8 | tasks)
+    unsigned long long *wave_times;      // [wavefront][4]: kernel entry, tables staged, tasks done, flags (first trip done, ticks after entry << 24 | interior tasks << 8 | tasks)
 #endif
     // site-site tables (pair_tab.h: SiteTable; kernels with SS): LDS byte offset FROM THE FORCE'S COULOMB TABLE to the place
     // interval 0 of its site-site table would have, the bytes it really holds, and the site class for the analytic fallback
@@ -1007,6 +1007,12 @@ struct CPairArgs {
     // the guest force of a fused pass: its tables, its output and its factors relative to the host's
     const double *guest_tab, *guest_tab_ss;
     int guest_bytes, guest_ss_bytes, guest_ss_off, g_accumulate;
+    // what k_cpair stages: the launch's tables in ONE array laid out as LDS is (cpair_tab_image puts it together from the arrays
+    // above, which are known by the serial numbers of their uploads -- PairForce::tab_serial -- and keeps it in tab_owner, the
+    // force host_tab belongs to; host side only)
+    const double *tab_image;
+    unsigned long long host_serial, guest_serial;
+    PairForce *tab_owner;
     double *gforce;
     double gfac, gsr;                  // (Kc sign)_guest / (Kc sign)_host ; sign_guest / sign_host
 };
@@ -1034,11 +1040,18 @@ struct CPairArgs {
 // second set of nine accumulators.  The scheduling barriers keep the two forces' look-up registers from being live together
 // (the forms with the guest inside the host's nine-pair body all spilled: 72 to 436 bytes of scratch per lane).  Product and sum
 // of the guest are rounded as its stand-alone launch rounds them: the same bits either way.
+#ifdef AMM_CPAIR_TIMING          // measurement builds: the clock when a wavefront's first trip is done
+#define CWALK_T_PARAM , unsigned long long &t_first
+#define CWALK_T_ARG , t_first
+#else
+#define CWALK_T_PARAM
+#define CWALK_T_ARG
+#endif
 template <int FAM, int CMODE, int GFAM, int IMG, int SMASK>
 __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts &c, const PairConsts &g, const char *tabh, const char *tabg,
                                            const double *erfcx, const double4 (&pi)[3], const double2 *li, int i_sites, const int (&so)[3],
                                            const int (&sog)[3], double sign_lj, const int *row, int nfront, int nn, int sub, int lpa,
-                                           int self, double (&f)[9], double (&fg)[9]) {
+                                           int self, double (&f)[9], double (&fg)[9] CWALK_T_PARAM) {
     constexpr bool DUAL = GFAM >= 0;
     constexpr bool SS = SMASK != 0;          // SMASK: the row atoms that can be sites (1: only the first -- water; 7: any)
     const int back = A.cap - 1 + nfront;
@@ -1190,6 +1203,9 @@ __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts 
         e = en;
         en = e2;
         k += lpa;
+#ifdef AMM_CPAIR_TIMING
+        if (!t_first) t_first = wall_clock64();
+#endif
     }
 }
 
@@ -1563,26 +1579,73 @@ k_cpair(CPairArgs A, PairConsts c, PairConsts g, CEpiArgs E) {
     }
 #ifdef AMM_CPAIR_TIMING
     const unsigned long long t_entry = wall_clock64();
-    unsigned long long t_staged = 0;
+    unsigned long long t_staged = 0, t_first = 0;
     int n_tasks_done = 0, n_interior = 0;
     unsigned long long t_epi[3] = {0, 0, 0};      // epilogue: forces visible / preceding kicks done / loop done (last task)
 #endif
-    auto stage = [&](int at, const double *src, int bytes) {
-        for (int o = threadIdx.x * 16; o < bytes; o += BS * 16)
-            *reinterpret_cast<double2 *>(s_lds + at + o) = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(src) + o);
-    };
-    const int gbytes = DUAL ? A.guest_bytes : 0;
-    stage(0, A.host_tab, A.host_bytes);
-    if (DUAL) stage(A.host_bytes, A.guest_tab, gbytes);
-    int used = A.host_bytes + gbytes;
-    if (SS) {
-        stage(used, A.host_tab_ss, A.host_ss_bytes);
-        used += A.host_ss_bytes;
-        if (DUAL) {
-            stage(used, A.guest_tab_ss, A.guest_ss_bytes);
-            used += A.guest_ss_bytes;
+    constexpr int WPB = BS / 64;
+    const int lane = threadIdx.x & 63;
+    const double sign = c.sign;
+    // one contiguous eighth of the rows per XCD (blockIdx & 7): consecutive cell-sorted rows = one slab of the box per L2
+    const int xcd = blockIdx.x & 7, nwx = (gridDim.x >> 3) * WPB;
+    const int row_end = min((xcd + 1) * A.rpx, A.nrows);
+#ifdef AMM_CPAIR_SWAP          // measurement: which tasks the last four wavefronts of a block take (is their lag theirs or their rows'?)
+    const int wave = (int)(threadIdx.x >> 6) ^ 4;
+#else
+    const int wave = (int)(threadIdx.x >> 6);
+#endif
+    // (the same in all lanes, and said so: phase, task and the phase's lanes per row stay in scalar registers)
+    const int task0 = (int)(blockIdx.x >> 3) * WPB + __builtin_amdgcn_readfirstlane(wave);
+    // The wavefront's tasks: task0, task0 + nwx ... of phase 0, then the same of phase 1 ...  `seek` stops at the next one there is.
+    int phase = 0, task = task0;
+    auto seek = [&]() {
+        while (phase < A.nphase && task >= A.ph_ntask[phase]) {
+            ++phase;
+            task = task0;
         }
-    }
+        return phase < A.nphase;
+    };
+    // A task's row prologue: the row atoms' records, the rows' lengths and places in the list -- the first of the three dependent
+    // round trips to memory a walk begins with (the lanes' first entries and the first partner's records follow inside
+    // cwalk_rows).  None of it depends on the tables, so the first task's is issued ahead of the tables' loads and arrives with them;
+    // a later task's is issued behind the walk of the one before and arrives while that one's sums are reduced and stored.  A
+    // wavefront without a task loads nothing; a task's invalid lanes load row 0.
+    // (Handing the walk its first entries or partner records as well costs the fused pass its registers: 100 to 136 bytes of scratch
+    // per lane where the parent form has 20 to 40, and a reload of the row pointer on every trip; profiles/prologue_wave_times.txt
+    // has what it would have bought.)  The kernels without site-site tables -- the fallback path, with the rows' parameter strip in
+    // LDS -- fetch a task's rows where they always did, at the head of the task: ahead of the walk the records cost them registers
+    // and scratch they do not have.
+    constexpr bool AHEAD = SS;
+    int shift = 0, lpa = 1, sub = 0, a = 0, cs = 0, nfront = 0, nn = 0;
+    bool valid = false;
+    const int *row = nullptr;
+    double4 pi[3];
+    double2 pl[3];
+    auto pre_rows = [&]() {
+        shift = A.ph_shift[phase];
+        lpa = 1 << shift;
+        sub = lane & (lpa - 1);
+        a = xcd * A.rpx + A.ph_off[phase] + task * (64 >> shift) + (lane >> shift);
+        valid = a < row_end;
+        cs = A.c_begin + (valid ? a : 0);
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            pi[t] = A.posq[3 * cs + t];
+            pl[t] = A.lj[3 * cs + t];
+        }
+        nfront = valid ? A.nnb[a] : 0;
+        nn = valid ? (A.nnb_total ? A.nnb_total[a] : nfront) : 0;
+        row = A.nl + (size_t)(valid ? a : 0) * A.cap;
+    };
+    bool has = seek();
+    if (AHEAD && has) pre_rows();
+
+    // the tables: one image in global memory, laid out as LDS is (cpair_tab_image); 20 pieces of BS x 16 bytes are the 160 KB of a CU
+    const int used = A.host_bytes + (DUAL ? A.guest_bytes : 0) + (SS ? A.host_ss_bytes + (DUAL ? A.guest_ss_bytes : 0) : 0);
+    double2 tabs[(160 * 1024) / (BS * 16)];
+    amm_stage_issue<BS>(tabs, A.tab_image, used);
+    amm_stage_commit<BS>(tabs, s_lds, used);
+    amm_stage_rest<BS>(tabs, A.tab_image, s_lds, used);
 #if defined(AMM_EXP_TAB_GLOBAL)           // measurement only: the table is read through the vector-memory path instead of LDS
     const char *tabh = reinterpret_cast<const char *>(A.host_tab);
 #else
@@ -1603,37 +1666,21 @@ k_cpair(CPairArgs A, PairConsts c, PairConsts g, CEpiArgs E) {
     t_staged = wall_clock64();
 #endif
 
-    constexpr int WPB = BS / 64;
-    const int lane = threadIdx.x & 63;
-    const double sign = c.sign;
     PairConsts c1 = c, g1 = g;
     c1.sign = 1.0;          // the sign travels with the row atoms' charges and epsilons (every family is linear in both)
     g1.sign = 1.0;
-    // one contiguous eighth of the rows per XCD (blockIdx & 7): consecutive cell-sorted rows = one slab of the box per L2
-    const int xcd = blockIdx.x & 7, nwx = (gridDim.x >> 3) * WPB;
-    const int row_end = min((xcd + 1) * A.rpx, A.nrows);
-    for (int phase = 0; phase < A.nphase; ++phase) {
-    const int shift = A.ph_shift[phase], row0 = xcd * A.rpx + A.ph_off[phase], ntask = A.ph_ntask[phase];
-    const int lpa = 1 << shift;
-    const int sub = lane & (lpa - 1);
-    const int rpw = 64 >> shift;
-#ifdef AMM_CPAIR_SWAP          // measurement: which tasks the last four wavefronts of a block take (is their lag theirs or their rows'?)
-    for (int task = (int)(blockIdx.x >> 3) * WPB + ((int)(threadIdx.x >> 6) ^ 4); task < ntask; task += nwx) {
-#else
-    for (int task = (int)(blockIdx.x >> 3) * WPB + (int)(threadIdx.x >> 6); task < ntask; task += nwx) {
-#endif
-        const int a = row0 + task * rpw + (lane >> shift);
-        const bool valid = a < row_end;
-        const int cs = A.c_begin + (valid ? a : 0);
-        double4 pi[3];
+    while (has) {
+        if (!AHEAD) pre_rows();
+        // (the task's own: the prologue of the next one overwrites them behind the walk)
+        const int t_a = a, t_cs = cs, t_sub = sub, t_lpa = lpa;
+        const bool t_valid = valid;
         int i_sites = 0;
         int so[3] = {0, 0, 0}, sog[3] = {0, 0, 0};
         if (!SS) __builtin_amdgcn_wave_barrier();        // the previous task's reads of the strip are done
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
-            pi[t] = A.posq[3 * cs + t];
             pi[t].w *= c.Kc * sign;
-            double2 l = A.lj[3 * cs + t];
+            double2 l = pl[t];
             l.y *= sign;
             if (!SS) s_li[64 * t + lane] = l;
             const bool site = valid && l.y != 0.0;
@@ -1649,9 +1696,6 @@ k_cpair(CPairArgs A, PairConsts c, PairConsts g, CEpiArgs E) {
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
         const double2 *li = SS ? nullptr : s_li + lane;  // li[64 a]
-        const int nfront = valid ? A.nnb[a] : 0;
-        const int nn = valid ? (A.nnb_total ? A.nnb_total[a] : nfront) : 0;
-        const int *row = A.nl + (size_t)(valid ? a : 0) * A.cap;
         const bool edge = valid && !(pi[0].x >= A.margin && pi[0].x <= A.box.L[0] - A.margin && pi[0].y >= A.margin &&
                                      pi[0].y <= A.box.L[1] - A.margin && pi[0].z >= A.margin && pi[0].z <= A.box.L[2] - A.margin);
         const bool interior = __builtin_amdgcn_ballot_w64(edge) == 0ull;
@@ -1662,20 +1706,23 @@ k_cpair(CPairArgs A, PairConsts c, PairConsts g, CEpiArgs E) {
         double f[9], fg[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) f[k] = fg[k] = 0.0;
-        if (A.per_pair_image) cwalk_rows<FAM, CMODE, GFAM, 2, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, sign, row, nfront, nn, sub, lpa, cs, f, fg);
-        else if (interior) cwalk_rows<FAM, CMODE, GFAM, 0, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, sign, row, nfront, nn, sub, lpa, cs, f, fg);
-        else cwalk_rows<FAM, CMODE, GFAM, 1, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, sign, row, nfront, nn, sub, lpa, cs, f, fg);
-        for (int off = lpa >> 1; off > 0; off >>= 1) {
+        if (A.per_pair_image) cwalk_rows<FAM, CMODE, GFAM, 2, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, sign, row, nfront, nn, sub, lpa, cs, f, fg CWALK_T_ARG);
+        else if (interior) cwalk_rows<FAM, CMODE, GFAM, 0, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, sign, row, nfront, nn, sub, lpa, cs, f, fg CWALK_T_ARG);
+        else cwalk_rows<FAM, CMODE, GFAM, 1, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, sign, row, nfront, nn, sub, lpa, cs, f, fg CWALK_T_ARG);
+        task += nwx;
+        has = seek();
+        if (AHEAD && has) pre_rows();
+        for (int off = t_lpa >> 1; off > 0; off >>= 1) {
 #pragma unroll
             for (int k = 0; k < 9; ++k) {
                 f[k] += __shfl_xor(f[k], off);
                 if (DUAL) fg[k] += __shfl_xor(fg[k], off);
             }
         }
-        if (valid && sub == 0) {
+        if (t_valid && t_sub == 0) {
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
-                const int i = A.sorted_out ? 3 * a + t : A.aperm[3 * cs + t];
+                const int i = A.sorted_out ? 3 * t_a + t : A.aperm[3 * t_cs + t];
 #pragma unroll
                 for (int d = 0; d < 3; ++d) {
                     // (host first: when both forces go to the same buffer the guest adds to what the host just wrote)
@@ -1689,7 +1736,6 @@ k_cpair(CPairArgs A, PairConsts c, PairConsts g, CEpiArgs E) {
             }
         }
         // the inner RESPA loop of the rows' molecules (cepi_rows): the row's sums are in f / fg on all of its lanes
-    }
     }
 #ifdef AMM_CPAIR_TIMING
     if (EPI) t_staged = wall_clock64();        // (measurement builds, kernels with the epilogue: the second clock = rows walked)
@@ -1729,7 +1775,7 @@ k_cpair(CPairArgs A, PairConsts c, PairConsts g, CEpiArgs E) {
         o[2] = wall_clock64();
         // (kernels with the epilogue: the fourth word holds three 20-bit offsets from "rows walked", in clock ticks of 10 ns)
         o[3] = EPI ? (((t_epi[0] - t_staged) & 0xfffffull) | (((t_epi[1] - t_staged) & 0xfffffull) << 20) | (((t_epi[2] - t_staged) & 0xfffffull) << 40))
-                   : (((unsigned long long)n_interior << 8) | (unsigned long long)n_tasks_done);
+                   : ((((t_first ? t_first - t_entry : 0ull) & 0xfffffull) << 24) | ((unsigned long long)(n_interior & 0xffff) << 8) | (unsigned long long)(n_tasks_done & 0xff));
     }
 #endif
 }
@@ -1787,6 +1833,41 @@ static void cpair_plan(CPairArgs &P, int waves, int enabled) {
     }
 }
 
+// The tables of a launch as k_cpair stages them: [host Coulomb][guest Coulomb][host site-site][guest site-site], one array, kept in
+// the force whose Coulomb table comes first (PairForce::tab_image, freed with it).  It is put together by copies on the launch's
+// stream, ahead of the launch, and is known by what it was made from: the serial numbers of the two forces' table uploads
+// (amm_pair_build_table -- the one place that writes d_tab / d_tab_ss -- draws a new number every time, whatever made it run: new
+// parameters, a new scale, a new site class) and its length.  So an image cannot outlive its tables unnoticed.  The stream is part of
+// the key: an image made on another stream is made again (after that stream's launches, which may still read it, are done).
+static int cpair_tab_image(amm_ctx *ctx, CPairArgs &P, bool dual, bool ss) {
+    const void *src[4] = {P.host_tab, dual ? P.guest_tab : nullptr, ss ? P.host_tab_ss : nullptr, (ss && dual) ? P.guest_tab_ss : nullptr};
+    const int len[4] = {P.host_bytes, dual ? P.guest_bytes : 0, ss ? P.host_ss_bytes : 0, (ss && dual) ? P.guest_ss_bytes : 0};
+    const unsigned long long gs = dual ? P.guest_serial : 0;
+    const size_t bytes = (size_t)len[0] + len[1] + len[2] + len[3];
+    PairForce::TabImage &im = P.tab_owner->tab_image[(dual ? 1 : 0) | (ss ? 2 : 0)];
+    if (!(im.d && im.host_serial == P.host_serial && im.guest_serial == gs && im.bytes == bytes && im.stream == ctx->stream)) {
+        im.host_serial = 0;               // (no upload has this number: whatever fails below, the image is not taken for a good one)
+        if (im.d && im.stream != ctx->stream) AMM_HIP(hipDeviceSynchronize());
+        if (im.bytes != bytes) {
+            if (im.d) (void)hipFree(im.d);
+            im.d = nullptr;
+            im.bytes = 0;
+            AMM_HIP(hipMalloc(&im.d, bytes));
+            im.bytes = bytes;
+        }
+        size_t at = 0;
+        for (int k = 0; k < 4; ++k) {
+            if (len[k] > 0) AMM_HIP(hipMemcpyAsync(im.d + at, src[k], (size_t)len[k], hipMemcpyDeviceToDevice, ctx->stream));
+            at += (size_t)len[k];
+        }
+        im.stream = ctx->stream;
+        im.guest_serial = gs;
+        im.host_serial = P.host_serial;
+    }
+    P.tab_image = reinterpret_cast<const double *>(im.d);
+    return 0;
+}
+
 // per (device, kernel) launch configuration: dynamic LDS attribute + blocks per CU from the occupancy query
 struct CLaunchCfg {
     int lds_set = 0, bpc = -1;
@@ -1827,6 +1908,7 @@ static int launch_cpair_t(amm_ctx *ctx, const CPairArgs &A, const PairConsts &c,
     nblk = std::max(8L, (nblk + 7) / 8 * 8);
     CPairArgs P = A;
     cpair_plan(P, (int)(nblk >> 3) * WPB, ctx->opt_row_phases);
+    if (cpair_tab_image(ctx, P, DUAL, SS)) return 1;
 #ifdef AMM_CPAIR_TIMING
     // the AMM_WAVE_TIMES-th launch of this kernel writes its wavefronts' clocks to $AMM_WAVE_TIMES_OUT.<fused|single> (measurement builds)
     static int launches = 0;
@@ -2322,6 +2404,10 @@ int amm_cluster_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, doub
         A.box = ctx->box;
         A.host_tab = pf->d_tab;
         A.host_bytes = pf->pc.tab.nint * AMM_TAB_STRIDE;
+        A.host_serial = pf->tab_serial;
+        A.tab_owner = pf;
+        A.guest_serial = 0;
+        A.tab_image = nullptr;
         // site-site table right behind the Coulomb table in LDS (fused pass: behind both Coulomb tables, the host's first)
         auto ss_bytes = [](const PairForce *p) { return (p->d_tab_ss && p->pc.tab.ss_first >= 0) ? (p->pc.tab.nint - p->pc.tab.ss_first) * AMM_TAB_STRIDE : 0; };
         A.host_tab_ss = pf->d_tab_ss;
@@ -2431,6 +2517,7 @@ int amm_cluster_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, doub
             // host and guest in ONE walk of the rows when a fused kernel exists for the two families
             CPairArgs D = A;
             D.guest_tab = guest->d_tab;
+            D.guest_serial = guest->tab_serial;
             D.guest_bytes = guest->pc.tab.nint * AMM_TAB_STRIDE;
             D.guest_tab_ss = guest->d_tab_ss;
             D.guest_ss_bytes = ss_bytes(guest);
@@ -2460,6 +2547,8 @@ int amm_cluster_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, doub
             G.force = gout;
             G.accumulate = (g_force == d_force && !exchange) ? 1 : g_accumulate;
             G.host_tab = guest->d_tab;
+            G.host_serial = guest->tab_serial;
+            G.tab_owner = guest;
             G.host_bytes = guest->pc.tab.nint * AMM_TAB_STRIDE;
             G.host_tab_ss = guest->d_tab_ss;
             G.host_ss_bytes = ss_bytes(guest);

@@ -12,6 +12,7 @@
 //   perm[s]   original atom index of sorted slot s; forces are written to f[perm[s]].
 // Work decomposition: `lpa` lanes of a 64-wide wavefront share one i-atom and stride through its
 // neighbour row (coalesced 4*lpa-byte reads); partial forces are combined with wavefront shuffles.
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1185,13 +1186,17 @@ template <int FAM, int CMODE, int GFAM, int BS, bool PH = false, bool NOQ = fals
 __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(AMM_TAB_WAVES_PER_EU)))
 k_pair_tab(PairArgs A, PairConsts c, PairConsts gc, TabArgs T, AtomEpiArgs E) {
     extern __shared__ __align__(16) char s_lds[];
-    // stage the table(s): 16-byte pieces, coalesced
-    for (int o = threadIdx.x * 16; o < T.host_bytes; o += BS * 16)
-        *reinterpret_cast<double2 *>(s_lds + o) = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(T.host_tab) + o);
+    // stage the table(s): 16-byte pieces, coalesced, the loads of both tables in flight together (pair_tab.h: amm_stage_issue / amm_stage_commit)
     const char *tabh = s_lds, *tabg = s_lds + T.host_bytes;
-    if (GFAM >= 0)
-        for (int o = threadIdx.x * 16; o < T.guest_bytes; o += BS * 16)
-            *reinterpret_cast<double2 *>(s_lds + T.host_bytes + o) = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(T.guest_tab) + o);
+    {
+        double2 sh[6], sg[GFAM >= 0 ? 6 : 1];
+        amm_stage_issue<BS>(sh, T.host_tab, T.host_bytes);
+        if (GFAM >= 0) amm_stage_issue<BS>(sg, T.guest_tab, T.guest_bytes);
+        amm_stage_commit<BS>(sh, s_lds, T.host_bytes);
+        if (GFAM >= 0) amm_stage_commit<BS>(sg, s_lds + T.host_bytes, T.guest_bytes);
+        amm_stage_rest<BS>(sh, T.host_tab, s_lds, T.host_bytes);
+        if (GFAM >= 0) amm_stage_rest<BS>(sg, T.guest_tab, s_lds + T.host_bytes, T.guest_bytes);
+    }
     double *s_erfcx = reinterpret_cast<double *>(s_lds + T.host_bytes + (GFAM >= 0 ? T.guest_bytes : 0));
     if (T.need_erfcx)
         for (int k = threadIdx.x; k < AMM_ERFCX_NI * AMM_ERFCX_NC; k += BS) s_erfcx[k] = amm_erfcx_table_dev[k];
@@ -2223,9 +2228,9 @@ int amm_pair_count_within_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos,
 extern "C" __attribute__((weak)) const char *amm_variant_tag(void);
 const char *amm_kernel_revision_impl() {
 #ifdef AMM_CLUSTER_TUNE
-    return "r05-epi5-tune";
+    return "r06-prologue-tune";
 #else
-    return amm_variant_tag ? "r05-epi5-tune" : "r05-epi5";
+    return amm_variant_tag ? "r06-prologue-tune" : "r06-prologue";
 #endif
 }
 
@@ -2251,6 +2256,9 @@ int amm_pair_build_table(PairForce *pf) {
         pf->d_tab_ss = nullptr;
     }
     pf->ss_error = ss.error;
+    // (what was put together from the old arrays -- PairForce::tab_image -- is known by this number)
+    static std::atomic<unsigned long long> uploads{0};
+    pf->tab_serial = ++uploads;
     // The bound is enforced, not assumed: the refinement stops at the LDS budget (or at its finest level), and a narrow
     // switching window or a high DAMPED degree can leave the table short of the arithmetic's accuracy.  Such a force keeps
     // the analytic kernels (no table: `tab_ok` is false for it, and a guest without a table disables the one-pass forms).
@@ -2309,6 +2317,10 @@ int amm_pair_free(PairForce *pf) {
                     pf->d_row_order, pf->d_member, pf->d_active, pf->d_cell_sets, pf->d_nnb_lj, pf->d_mol_first, pf->d_rest_idx};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    for (PairForce::TabImage &im : pf->tab_image) {
+        if (im.d) (void)hipFree(im.d);
+        im = PairForce::TabImage();
+    }
     for (hipEvent_t e : pf->ev) (void)hipEventDestroy(e);
     if (pf->cl) amm_cluster_free(pf->cl);
     pf->cl = nullptr;

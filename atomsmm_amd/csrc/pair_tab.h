@@ -294,6 +294,40 @@ static inline double amm_build_coulomb_table(PairConsts &pc, std::vector<double>
 // ------------------------------------------------------------------------------------------------ device
 #if defined(__HIPCC__)
 #include "pair_math.h"
+// Staging of a block's tables in LDS: `bytes` (a multiple of 16) of global memory go to LDS in 16-byte pieces, coalesced.  A copy
+// loop (load a piece, store it, next piece) is a chain of round trips to memory, one per BS x 16 bytes -- 19 for the 155 KB of a
+// fused molecule-row pass: 6.7 us where the bandwidth of a CU needs about one.  Here a thread issues the loads of U pieces into
+// registers (amm_stage_issue) before it stores the first of them (amm_stage_commit): one round trip per U pieces, and whatever the caller puts between
+// issue and commit travels with it.  The bytes land where the copy loop put them.
+// (Written so that the compiler keeps it that way: pieces past the end are skipped by a branch on the kernel's arguments, the last
+// piece's threads past the end load offset 0 instead, and only the LDS store is per thread.  With the load under the thread's own
+// condition as well, the compiler moves it next to its store -- the copy loop again -- or keeps r in scratch.)
+template <int BS, int U>
+__device__ __forceinline__ void amm_stage_issue(double2 (&r)[U], const void *src, int bytes, int from = 0) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int o = from + u * BS * 16 + (int)threadIdx.x * 16;
+        r[u] = make_double2(0.0, 0.0);
+        if (from + u * BS * 16 < bytes) r[u] = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(src) + (o < bytes ? o : 0));
+    }
+}
+template <int BS, int U>
+__device__ __forceinline__ void amm_stage_commit(const double2 (&r)[U], char *lds, int bytes, int from = 0) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int o = from + u * BS * 16 + (int)threadIdx.x * 16;
+        if (o < bytes) *reinterpret_cast<double2 *>(lds + o) = r[u];
+    }
+}
+// what lies past the first U pieces (nothing when U x BS x 16 bytes cover the tables)
+template <int BS, int U>
+__device__ __forceinline__ void amm_stage_rest(double2 (&r)[U], const void *src, char *lds, int bytes) {
+    for (int from = U * BS * 16; from < bytes; from += U * BS * 16) {
+        amm_stage_issue<BS>(r, src, bytes, from);
+        amm_stage_commit<BS>(r, lds, bytes, from);
+    }
+}
+
 __device__ __forceinline__ double amm_tab_eval(const char *lds_tab, const PairTab &T, double r2) {
     const double w = r2 * T.scale;
     const unsigned hi = (unsigned)__double2hiint(w);

@@ -8,7 +8,7 @@ O=atomsmm_amd/csrc/_obj
 file=$1; shift
 mkdir -p atomsmm_amd/exp
 objs=""
-for s in abi pair cluster group bonded integrate pme expr constraints comm; do
+for s in abi pair cluster group bonded integrate pme expr constraints comm minimize; do
     [ "$s" = "$file" ] || objs="$objs $O/$s.o"
 done
 # the revision tag of a variant library ends in "-tune" (amm_kernel_revision): bench.py and the tests refuse it
