@@ -42,6 +42,7 @@ EXPORTS = [
     'amm_pair_energy_states',
     'amm_min_create', 'amm_min_release', 'amm_min_begin', 'amm_min_advance', 'amm_min_trial', 'amm_min_scalars', 'amm_min_stats',
     'amm_min_read',
+    'amm_set_box', 'amm_box_stats', 'amm_mol_define', 'amm_mol_scale',
 ]
 
 
@@ -206,6 +207,10 @@ def lib():
         L.amm_min_scalars.argtypes = [vp, C.c_int32, dp]
         L.amm_min_stats.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
         L.amm_min_read.argtypes = [vp, C.c_int32, C.c_int32, dp]
+        L.amm_set_box.argtypes = [vp, dp]
+        L.amm_box_stats.argtypes = [vp, C.POINTER(C.c_int64)]
+        L.amm_mol_define.argtypes = [vp, ip, ip, C.c_int32]
+        L.amm_mol_scale.argtypes = [vp, vp, vp, dp]
         for name in EXPORTS:
             if name not in ('amm_last_error', 'amm_kernel_revision'):
                 getattr(L, name).restype = C.c_int
@@ -587,6 +592,31 @@ class HipContext:
     def positions_changed(self):
         """The bound position buffer was written outside the library (option 'positions_private')."""
         _chk(lib().amm_positions_changed(self.h))
+
+    # ---- a box that changes (constant-pressure runs)
+    def set_box(self, edges):
+        """New box edges (nm) for every later launch; raises, and keeps the old box, when a pair cutoff exceeds half an edge."""
+        b, bp = _hd(np.asarray(edges, dtype=np.float64).reshape(3))
+        _chk(lib().amm_set_box(self.h, bp))
+
+    def box_stats(self):
+        out = (C.c_int64 * 4)()
+        _chk(lib().amm_box_stats(self.h, out))
+        return dict(changes=out[0], regrids=out[1], waits=out[2])
+
+    def mol_define(self, molecules):
+        """The molecules (a sequence of atom-index sequences, every atom exactly once) that mol_scale moves."""
+        ptr = np.zeros(len(molecules) + 1, dtype=np.int32)
+        ptr[1:] = np.cumsum([len(m) for m in molecules])
+        atoms = np.concatenate([np.asarray(m, dtype=np.int32).reshape(-1) for m in molecules]) if len(molecules) else np.zeros(0, np.int32)
+        p_, pp = _hi(ptr)
+        a_, ap = _hi(atoms if len(atoms) else np.zeros(1, np.int32))
+        _chk(lib().amm_mol_define(self.h, pp, ap, len(molecules)))
+
+    def mol_scale(self, x, scale, saved=None):
+        """x <- x + (scale - 1) * centre of the atom's molecule, per axis; saved (or None) <- the old x, bit for bit."""
+        s_, sp = _hd(np.asarray(scale, dtype=np.float64).reshape(3))
+        _chk(lib().amm_mol_scale(self.h, _ptr(x), _ptr(saved), sp))
 
     def exchange_per(self):
         """Slots of the cell-sorted order per rank (whole molecules of three): chunk geometry of the exchange buffer."""

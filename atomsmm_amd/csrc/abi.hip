@@ -99,6 +99,7 @@ int amm_destroy(amm_ctx *ctx) {
     if (ctx->alt_x) (void)hipFree(ctx->alt_x);
     if (ctx->alt_v) (void)hipFree(ctx->alt_v);
     if (ctx->alt_f) (void)hipFree(ctx->alt_f);
+    amm_mol_free(ctx);
     delete ctx;
     return 0;
 }
@@ -181,6 +182,39 @@ int amm_check(amm_ctx *ctx) {
     return 0;
 }
 
+// Verlet buffers and list radii of a pair force from the buffer it asked for and the context's box (amm_pair_create; amm_set_box)
+static void pair_derive_buffers(amm_ctx *ctx, PairForce *pf) {
+    const amm_pair_desc *desc = &pf->desc;
+    double Lmin = std::min(ctx->box.L[0], std::min(ctx->box.L[1], ctx->box.L[2]));
+    double skin = std::min(pf->skin_req, std::max(0.0, 0.5 * Lmin - desc->rc) * 0.999);
+    pf->skin = skin;
+    // a force guarded by step(rc0 - r) (the discount of FarNonbondedForce, forces.py:714; group 31 of RESPASystem) vanishes
+    // beyond rc0 whatever its nominal cutoff: its list needs to reach rc0 only
+    const double reach = ((desc->flags & AMM_GUARD_RC0) && desc->rc0 > 0.0) ? std::min(desc->rc, desc->rc0) : desc->rc;
+    pf->rlist = reach + skin;
+    pf->rlist_build = pf->rlist + 2e-4;   // fp32 build: positions carry ~1e-6 nm rounding, superset is harmless
+    // outer buffer: large enough that the cell-based build is rare (hydrogens consume 0.05 nm in ~2 outer steps)
+    // default: single list (skin_out = skin).  Measured at C3: the prune pass costs about as much as a cell build
+    // (both are bound by L1 line-access rate / instruction issue), so the dual list only pays for slow-moving systems.
+    double skin_out = pf->skin_out_req > 0 ? pf->skin_out_req : skin;
+    skin_out = std::max(skin, std::min(skin_out, std::max(0.0, 0.5 * Lmin - desc->rc) * 0.999));
+    pf->skin_out = skin_out;
+    pf->rlist_out_build = reach + skin_out + 2e-4;
+}
+
+// what sharing a list does to the buffers of guest and host (amm_pair_share_list; amm_set_box after it has derived both again)
+static void share_buffers(PairForce *g, PairForce *h) {
+    // the guest's skin must be consumed no later than the host's: same displacement trigger
+    g->skin = std::min(g->skin, h->skin);
+    h->skin = g->skin;
+    g->skin_out = h->skin_out;
+    h->rlist = h->desc.rc + h->skin;
+    h->rlist_build = h->rlist + 2e-4;
+    if (h->skin_out < h->skin) h->skin_out = h->skin;
+    h->rlist_out_build = h->desc.rc + h->skin_out + 2e-4;
+    h->rnear_build = g->rlist_build;
+}
+
 int amm_pair_create(amm_ctx *ctx, const amm_pair_desc *desc, const double *h_q, const double *h_sigma,
                     const double *h_eps, const int32_t *h_excl, int32_t n_excl, double skin, int32_t *force_id) {
     if (!ctx || !desc || !h_q || !h_sigma || !h_eps || !force_id) {
@@ -198,6 +232,7 @@ int amm_pair_create(amm_ctx *ctx, const amm_pair_desc *desc, const double *h_q, 
     PairForce *pf = new PairForce();
     pf->desc = *desc;
     pf->n = ctx->n;
+    pf->skin_out_req = ctx->skin_out;
     if (ctx->n >= (1 << 26)) {      // the traversal addresses the sorted copies with 32-bit byte offsets (32 B per slot)
         amm_set_error("amm_pair_create: more than 2^26 atoms are not supported");
         delete pf;
@@ -208,25 +243,12 @@ int amm_pair_create(amm_ctx *ctx, const amm_pair_desc *desc, const double *h_q, 
         return 1;
     }
     const int n = ctx->n;
-    double Lmin = std::min(ctx->box.L[0], std::min(ctx->box.L[1], ctx->box.L[2]));
     // default Verlet buffer: 0.1 nm on one GPU (C3: list build 0.58 x 320 us per step against +30 % pair work at 0.2 nm);
     // a rank's slice makes the pair kernels 2 - 5 x cheaper but the rebuild only 1.6 - 2 x (scripts/probe_pair.py --world N),
     // so the optimum moves to a larger buffer: 0.15 nm for 2 ranks, 0.2 nm beyond
     if (skin < 0) skin = ctx->world >= 4 ? 0.2 : (ctx->world >= 2 ? 0.15 : 0.1);
-    skin = std::min(skin, std::max(0.0, 0.5 * Lmin - desc->rc) * 0.999);
-    pf->skin = skin;
-    // a force guarded by step(rc0 - r) (the discount of FarNonbondedForce, forces.py:714; group 31 of RESPASystem) vanishes
-    // beyond rc0 whatever its nominal cutoff: its list needs to reach rc0 only
-    const double reach = ((desc->flags & AMM_GUARD_RC0) && desc->rc0 > 0.0) ? std::min(desc->rc, desc->rc0) : desc->rc;
-    pf->rlist = reach + skin;
-    pf->rlist_build = pf->rlist + 2e-4;   // fp32 build: positions carry ~1e-6 nm rounding, superset is harmless
-    // outer buffer: large enough that the cell-based build is rare (hydrogens consume 0.05 nm in ~2 outer steps)
-    // default: single list (skin_out = skin).  Measured at C3: the prune pass costs about as much as a cell build
-    // (both are bound by L1 line-access rate / instruction issue), so the dual list only pays for slow-moving systems.
-    double skin_out = ctx->skin_out > 0 ? ctx->skin_out : skin;
-    skin_out = std::max(skin, std::min(skin_out, std::max(0.0, 0.5 * Lmin - desc->rc) * 0.999));
-    pf->skin_out = skin_out;
-    pf->rlist_out_build = reach + skin_out + 2e-4;
+    pf->skin_req = skin;
+    pair_derive_buffers(ctx, pf);
     if (amm_pair_setup_grid(ctx, pf)) {
         delete pf;
         return 1;
@@ -279,6 +301,7 @@ int amm_pair_create(amm_ctx *ctx, const amm_pair_desc *desc, const double *h_q, 
     AMM_HIP(hipMalloc(&pf->d_hsig, sizeof(double) * n));
     AMM_HIP(hipMalloc(&pf->d_seps2, sizeof(double) * n));
     const int nc = pf->grid.ncell;
+    pf->ncell_alloc = nc;
     AMM_HIP(hipMalloc(&pf->d_cell_of, sizeof(int) * n));
     AMM_HIP(hipMalloc(&pf->d_cell_count, sizeof(int) * (nc + 1)));
     AMM_HIP(hipMemset(pf->d_cell_count, 0, sizeof(int) * (nc + 1)));
@@ -461,15 +484,7 @@ static int share_list_pf(amm_ctx *ctx, PairForce *g, PairForce *h) {
         amm_set_error("amm_pair_share_list: exclusion lists differ");
         return 1;
     }
-    // the guest's skin must be consumed no later than the host's: same displacement trigger
-    g->skin = std::min(g->skin, h->skin);
-    h->skin = g->skin;
-    g->skin_out = h->skin_out;
-    h->rlist = h->desc.rc + h->skin;
-    h->rlist_build = h->rlist + 2e-4;
-    if (h->skin_out < h->skin) h->skin_out = h->skin;
-    h->rlist_out_build = h->desc.rc + h->skin_out + 2e-4;
-    h->rnear_build = g->rlist_build;
+    share_buffers(g, h);
     g->host = h;
     // both hybrid (same exclusions: the same molecules): the per-atom parts share a list the same way
     if (g->rest && h->rest) return share_list_pf(ctx, g->rest, h->rest);
@@ -1997,6 +2012,204 @@ int amm_set_option(amm_ctx *ctx, const char *name, double value) {
         return 1;
     }
     return 0;
+}
+
+// ---- a box that changes (constant-pressure runs) --------------------------------------------------------------------------
+// How far amm_set_box lets a kept grid squeeze a Verlet buffer before it chooses the cell counts again: half of the buffer the force
+// would have in this box with cells to match.
+static const double AMM_BOX_SKIN_KEEP = 0.5;
+// ... and how far the density of list entries (rlist^3 / V) may grow beyond the first build's before the row capacities (1.5 x the
+// longest row then + 32) are sized again: a quarter leaves a fifth for fluctuations.
+static const double AMM_BOX_ROWS_GROW = 1.25;
+
+// the largest list radius the cells of a kept grid admit in the context's box: neighbours within +-2 cells need cw >= radius / 2
+static double grid_room(const amm_ctx *ctx, const CellGrid &g) {
+    double room = 1.0e30;
+    for (int k = 0; k < 3; ++k) room = std::min(room, 2.0 * ctx->box.L[k] / g.nc[k]);
+    return room;
+}
+// the cell counts setup_grid / cluster_setup_grid would choose today for list radius `reach`
+static bool grid_differs(const amm_ctx *ctx, const CellGrid &g, double reach) {
+    for (int k = 0; k < 3; ++k) {
+        int nc = (int)floor(ctx->box.L[k] / (0.5 * reach));
+        nc = std::max(1, std::min(512, nc));
+        if (nc != g.nc[k]) return true;
+    }
+    return false;
+}
+static bool box_within(const amm_ctx *ctx, const double L0[3], double tol) {
+    for (int k = 0; k < 3; ++k)
+        if (std::fabs(ctx->box.L[k] - L0[k]) > tol * L0[k]) return false;
+    return true;
+}
+
+// the lists of the context follow ctx->box (amm_set_box, and its way back when a step of this fails)
+static int box_apply(amm_ctx *ctx, bool &regrid, bool &waited) {
+    const double V = ctx->box.L[0] * ctx->box.L[1] * ctx->box.L[2];
+    // 1. every force's buffers as amm_pair_create would derive them in this box (a hybrid list's per-atom part asks for a multiple of
+    // its parent's: the parent comes first in ctx->forces)
+    for (auto &fo : ctx->forces) {
+        if (fo.type != 1) continue;
+        PairForce *pf = fo.pair;
+        pair_derive_buffers(ctx, pf);
+        if (pf->rest) pf->rest->skin_req = pf->skin * ctx->opt_rest_skin_factor;
+    }
+    // 2. list owners: keep the cell counts while the cells admit the list radius (the buffer gives way first, down to
+    // AMM_BOX_SKIN_KEEP of it) and the capacities still fit the density; else choose them again -- a regrid: the list is dropped and
+    // the next evaluation sizes and builds it as the first one did
+    auto wait_once = [&]() -> int {
+        if (!waited) AMM_HIP(hipStreamSynchronize(ctx->stream));
+        waited = true;
+        return 0;
+    };
+    for (auto &fo : ctx->forces) {
+        if (fo.type != 1 || fo.pair->host) continue;
+        PairForce *L = fo.pair;
+        const bool dual = L->skin_out > L->skin * (1 + 1e-9);
+        const double full_skin = L->skin;
+        // per-atom rows
+        {
+            const double rgrid = dual ? L->rlist_out_build : L->rlist_build;
+            const double room = grid_room(ctx, L->grid);
+            const double skin_room = room - L->desc.rc - 2e-4 - 1e-9;
+            bool again = false;
+            if (!L->built) {
+                // nothing is sized yet: the grid of a fresh context in this box; the per-cell arrays grow if they must
+                if (grid_differs(ctx, L->grid, rgrid)) {
+                    regrid = true;
+                    if (amm_pair_setup_grid(ctx, L)) return 1;
+                    again = L->grid.ncell > L->ncell_alloc;
+                }
+            } else if (dual != L->dual) again = true;     // the clamp took the outer buffer away, or gave it back: another kind of list
+            else if (!box_within(ctx, L->built_L, 0.02) && grid_differs(ctx, L->grid, rgrid)) again = true;
+            else if (rgrid > room && (dual || skin_room < 0.0 || skin_room < AMM_BOX_SKIN_KEEP * full_skin)) again = true;
+            else if (L->rlist_build * L->rlist_build * L->rlist_build / V > AMM_BOX_ROWS_GROW * L->built_rows) again = true;
+            if (again) {
+                if (wait_once() || amm_pair_regrid(ctx, L)) return 1;
+                regrid = true;
+            } else {
+                if (L->built && rgrid > room) L->skin = L->skin_out = skin_room;
+                for (int k = 0; k < 3; ++k) {
+                    L->grid.cw[k] = ctx->box.L[k] / L->grid.nc[k];
+                    L->grid.inv_cw[k] = L->grid.nc[k] / ctx->box.L[k];
+                }
+            }
+        }
+        // molecule rows (their cells are wider by the molecules' extent)
+        if (L->cl) {
+            ClusterList *cl = L->cl;
+            const double room = grid_room(ctx, cl->grid) - 2.0 * cl->rext;
+            const double skin_room = room - L->desc.rc - 2e-4 - 1e-9;
+            bool again = !cl->built;        // (a first build that failed: start over)
+            if (!again && !box_within(ctx, cl->built_L, 0.02) && grid_differs(ctx, cl->grid, L->rlist_build + 2.0 * cl->rext)) again = true;
+            if (!again && L->rlist_build > room && (skin_room < 0.0 || skin_room < AMM_BOX_SKIN_KEEP * full_skin)) again = true;
+            if (!again && L->rlist_build * L->rlist_build * L->rlist_build / V > AMM_BOX_ROWS_GROW * cl->built_rows) again = true;
+            if (again) {
+                if (wait_once()) return 1;
+                amm_cluster_free(cl);
+                L->cl = nullptr;
+                L->force_rebuild_c = false;
+                regrid = true;
+            } else if (L->rlist_build > room) {
+                L->skin = L->skin_out = std::min(L->skin, skin_room);
+            }
+        }
+        if (L->skin != full_skin) {
+            const double reach = ((L->desc.flags & AMM_GUARD_RC0) && L->desc.rc0 > 0.0) ? std::min(L->desc.rc, L->desc.rc0) : L->desc.rc;
+            L->rlist = reach + L->skin;
+            L->rlist_build = L->rlist + 2e-4;
+            L->rlist_out_build = reach + L->skin_out + 2e-4;
+        }
+    }
+    // 3. shared lists, as amm_pair_share_list left them
+    for (auto &fo : ctx->forces)
+        if (fo.type == 1 && fo.pair->host) {
+            PairForce *g = fo.pair, *h = g->host;
+            g->rlist_build = std::min(g->rlist_build, h->desc.rc + std::min(g->skin, h->skin) + 2e-4);
+            share_buffers(g, h);
+        }
+    // 4. nothing made for the old box survives: lists are rebuilt by their next evaluation, sorted copies gathered again, the
+    // displacement triggers start from the positions of that rebuild, candidate sets start over
+    for (auto &fo : ctx->forces) {
+        if (fo.type != 1) continue;
+        PairForce *pf = fo.pair;
+        pf->a_sorted_for = nullptr;
+        pf->a_sorted_epoch = pf->checked_epoch = pf->pre_epoch = -1;
+        if (pf->built) pf->force_rebuild = true;
+        if (pf->cl) amm_cluster_rebox(ctx, pf);
+        amm_small_group_forget(pf->small);
+    }
+    ctx->n_watched = 0;
+    ctx->pos_epoch++;
+    return 0;
+}
+
+int amm_set_box(amm_ctx *ctx, const double h_box[3]) {
+    if (!ctx || !h_box) {
+        amm_set_error("amm_set_box: null argument");
+        return 1;
+    }
+    for (int k = 0; k < 3; ++k)
+        if (!(h_box[k] > 0.0)) {
+            amm_set_error("amm_set_box: box edges must be positive (orthorhombic periodic box)");
+            return 1;
+        }
+    if (ctx->world > 1 || ctx->pending.active) {
+        amm_set_error("amm_set_box: a context that is one rank of several keeps the box it was created with");
+        return 1;
+    }
+    for (auto &fo : ctx->forces)
+        if (fo.type == 1)
+            for (int k = 0; k < 3; ++k)
+                if (fo.pair->desc.rc > 0.5 * h_box[k] * (1 + 1e-12)) {
+                    amm_set_error("pair cutoff exceeds half the box edge (minimum image needs rc <= L/2)");
+                    return 1;           // (nothing was touched: the old box stays in force)
+                }
+    const Box old = ctx->box;
+    for (int k = 0; k < 3; ++k) {
+        ctx->box.L[k] = h_box[k];
+        ctx->box.invL[k] = 1.0 / h_box[k];
+    }
+    bool regrid = false, waited = false;
+    if (box_apply(ctx, regrid, waited)) {
+        // a wait or an allocation failed on the way: back to the old box (lists already dropped are built again by their next
+        // evaluation), with the error of the first failure
+        const std::string why = amm_last_error();
+        bool r2 = false, w2 = false;
+        ctx->box = old;
+        (void)box_apply(ctx, r2, w2);
+        amm_set_error(why);
+        return 1;
+    }
+    ctx->box_changes++;
+    if (regrid) ctx->box_regrids++;
+    if (waited) ctx->box_waits++;
+    return 0;
+}
+
+int amm_box_stats(amm_ctx *ctx, int64_t out[4]) {
+    if (!ctx || !out) return 1;
+    out[0] = ctx->box_changes;
+    out[1] = ctx->box_regrids;
+    out[2] = ctx->box_waits;
+    out[3] = 0;
+    return 0;
+}
+
+int amm_mol_define(amm_ctx *ctx, const int32_t *h_ptr, const int32_t *h_atoms, int32_t n_mol) {
+    if (!ctx || !h_ptr || !h_atoms) {
+        amm_set_error("amm_mol_define: null argument");
+        return 1;
+    }
+    return amm_mol_define_impl(ctx, h_ptr, h_atoms, n_mol);
+}
+
+int amm_mol_scale(amm_ctx *ctx, double *d_x, double *d_x_saved, const double scale[3]) {
+    if (!ctx || !d_x || !scale) {
+        amm_set_error("amm_mol_scale: null argument");
+        return 1;
+    }
+    return amm_mol_scale_impl(ctx, d_x, d_x_saved, scale);
 }
 
 int amm_run_stats(amm_ctx *ctx, int64_t out[4]) {

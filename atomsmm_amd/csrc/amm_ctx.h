@@ -100,6 +100,11 @@ struct PairForce {
     int n = 0;
     int id = -1;                   // force id within the context
     double skin = 0, rlist = 0;
+    double skin_out_req = -1;      // the context's outer buffer when the force was created (<= 0: none asked for)
+    double skin_req = 0;           // the buffer asked for at creation, before the box clamps it: amm_set_box derives `skin` from it again
+    double built_L[3] = {0, 0, 0}; // box edges at the first build of the per-atom rows, and rlist_build^3 / V then: the row capacity was
+    double built_rows = 0;         // sized for that density (amm_set_box trusts it while this quantity has grown by less than a quarter)
+    int ncell_alloc = 0;           // cells the per-cell arrays below were allocated for
     double rlist_build = 0;        // rlist + fp32 safety margin used by the prune pass (inner list)
     double skin_out = 0;           // outer Verlet buffer (cell-built list, radius rc + skin_out)
     double rlist_out_build = 0;
@@ -406,6 +411,11 @@ struct amm_ctx {
     // summation then depends on the rows that share its wavefront: results agree to rounding, not bit for bit, between two
     // decompositions.  AMM_SITE_TRIPS=0 (read when the context is created) switches it off -- what the bit-identity tests do.
     bool site_trips = true;
+    // amm_set_box: changes so far, those that chose new cell counts for some list, those that freed / allocated device memory or waited
+    long long box_changes = 0, box_regrids = 0, box_waits = 0;
+    // molecules of amm_mol_define (barostat.hip): CSR on the device, and the molecules of at most AMM_CLUSTER_ATOMS atoms / the longer ones
+    int n_mol = 0, n_mol_small = 0, n_mol_long = 0;
+    int *d_mol_ptr = nullptr, *d_mol_atoms = nullptr, *d_mol_small = nullptr, *d_mol_long = nullptr;
     long pos_epoch = 0;            // bumped whenever the positions may have changed (see amm_pair_eval_impl)
     double skin_out = -1.0;        // outer Verlet buffer for pair forces created afterwards (<= 0: default)
     void *comm = nullptr;          // ncclComm_t of the library's own communicator (comm.hip), or none
@@ -453,7 +463,14 @@ int amm_comm_allreduce_impl(amm_ctx *ctx, double *d_buf, size_t count);
 int amm_comm_allgather_impl(amm_ctx *ctx, double *d_buf, size_t count_per_rank);
 int amm_exchange_finish_impl(amm_ctx *ctx);
 
+// barostat.hip
+#define AMM_CLUSTER_ATOMS 8      // molecules of at most this many atoms are scaled one lane each (amm_mol_scale)
+int amm_mol_define_impl(amm_ctx *ctx, const int32_t *h_ptr, const int32_t *h_atoms, int n_mol);
+int amm_mol_scale_impl(amm_ctx *ctx, double *d_x, double *d_x_saved, const double scale[3]);
+int amm_mol_free(amm_ctx *ctx);
+
 // group.hip
+void amm_small_group_forget(SmallGroup *sg);      // the companion list is about to change under it (amm_set_box): candidates start over
 int amm_small_group_setup(amm_ctx *ctx, PairForce *pf, const std::vector<float> &member);
 // carry_terms: the launch also evaluates the terms of this (finalized, term-parallel) bond-list set into its parked-force buffer
 // own_rows: the caller can take the force's rows from a buffer of the force's own (returned here; nullptr: they are in d_force
@@ -475,6 +492,9 @@ int amm_pair_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double 
 bool amm_pair_can_eval_dual(amm_ctx *ctx, PairForce *guest, PairForce *host);
 bool amm_pair_can_fuse_discount(amm_ctx *ctx, PairForce *guest, PairForce *host);
 int amm_pair_free(PairForce *pf);
+// amm_set_box: drop the per-atom rows and their capacities and choose the cell counts again for the context's box (the next evaluation
+// builds and sizes them as the first one did); frees device memory -- the caller has waited for the stream
+int amm_pair_regrid(amm_ctx *ctx, PairForce *pf);
 int amm_pair_build_table(PairForce *pf);
 int amm_pair_count_within_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double r_within, long long *count);
 const char *amm_kernel_revision_impl();

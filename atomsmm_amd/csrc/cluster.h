@@ -59,6 +59,8 @@ struct ClusterList {
     int spec_parity = 0;
     long assigned_epoch = -1;
     const double *assigned_pos = nullptr;
+    double built_L[3] = {0, 0, 0}; // box edges at the first build, and rlist_build^3 / V then (amm_set_box: are the capacities still good?)
+    double built_rows = 0;
     bool per_pair_image = false;   // small box: the periodic image is chosen per atom pair, not per molecule pair
 };
 
@@ -72,3 +74,6 @@ int amm_cluster_count_within_impl(amm_ctx *ctx, PairForce *pf, const double *d_p
 int amm_cluster_row_padding_impl(amm_ctx *ctx, PairForce *pf, long long out[2]);
 int amm_cluster_state_finish_impl(amm_ctx *ctx);       // second half of a state exchange: k_state_scatter
 int amm_cluster_free(ClusterList *cl);
+// amm_set_box with the cell counts kept: radii, cell widths and the per-pair-image condition for the context's box; every record of
+// work done ahead for the old box is dropped and the next evaluation rebuilds the rows
+void amm_cluster_rebox(amm_ctx *ctx, PairForce *L);

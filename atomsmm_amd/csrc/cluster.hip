@@ -2275,7 +2275,27 @@ static int cluster_first_build(amm_ctx *ctx, PairForce *L, const double *d_pos) 
     AMM_HIP(hipMalloc(&cl->d_nl, sizeof(int) * ns * cl->cap));
     if (cluster_chain(ctx, L, cl, d_pos, 1, false, nullptr)) return 1;
     cl->built = true;
+    for (int k = 0; k < 3; ++k) cl->built_L[k] = ctx->box.L[k];
+    cl->built_rows = cl->rlist_build * cl->rlist_build * cl->rlist_build / (ctx->box.L[0] * ctx->box.L[1] * ctx->box.L[2]);
     return 0;
+}
+
+void amm_cluster_rebox(amm_ctx *ctx, PairForce *L) {
+    ClusterList *cl = L->cl;
+    cl->skin = L->skin;
+    cl->rlist_build = L->rlist_build;
+    cl->rnear_build = L->rnear_build;
+    cl->per_pair_image = false;
+    for (int k = 0; k < 3; ++k) {
+        const double Lk = ctx->box.L[k];
+        cl->grid.cw[k] = Lk / cl->grid.nc[k];
+        cl->grid.inv_cw[k] = cl->grid.nc[k] / Lk;
+        if (!(L->desc.rc + cl->skin + 2.0 * cl->rext < 0.5 * Lk * (1 - 1e-9))) cl->per_pair_image = true;      // (as cluster_setup_grid)
+    }
+    // rows, sorted copies and cells filed ahead by the launch that moved the atoms were made for the old box
+    cl->sorted_for = nullptr;
+    cl->sorted_epoch = cl->assigned_epoch = cl->checked_epoch = cl->pre_epoch = -1;
+    L->force_rebuild_c = true;
 }
 
 int amm_cluster_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double *d_force, int accumulate, PairForce *guest,

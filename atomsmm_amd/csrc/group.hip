@@ -494,6 +494,10 @@ struct SmallGroup {
     int *d_sticket = nullptr;
 };
 
+void amm_small_group_forget(SmallGroup *sg) {
+    if (sg) sg->companion = nullptr;       // (the next launch with candidates resets their state on the stream)
+}
+
 int amm_small_group_free(SmallGroup *sg) {
     if (!sg) return 0;
     void *ptrs[] = {sg->d_small, sg->d_acc, sg->d_ticket, sg->d_epart, sg->d_overflow, sg->d_fpair, sg->d_cand, sg->d_cstate, sg->d_spart,

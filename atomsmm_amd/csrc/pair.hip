@@ -1731,6 +1731,8 @@ static int first_build(amm_ctx *ctx, PairForce *pf, const double *d_pos) {
         if (pf->hybrid_rest && ctx->world == 1) pf->active_cap = (int)std::min<size_t>(ns, (size_t)4 * f16[8] + 1024);
     }
     pf->built = true;
+    for (int k = 0; k < 3; ++k) pf->built_L[k] = ctx->box.L[k];
+    pf->built_rows = pf->rlist_build * pf->rlist_build * pf->rlist_build / (ctx->box.L[0] * ctx->box.L[1] * ctx->box.L[2]);
     return 0;
 }
 
@@ -2331,3 +2333,34 @@ int amm_pair_free(PairForce *pf) {
 
 // exported for abi.hip
 int amm_pair_setup_grid(amm_ctx *ctx, PairForce *pf) { return setup_grid(ctx, pf); }
+
+int amm_pair_regrid(amm_ctx *ctx, PairForce *pf) {
+    // what first_build allocated and sized: the next evaluation goes through it again
+    void **owned[] = {(void **)&pf->d_nnb, (void **)&pf->d_nnb_near, (void **)&pf->d_nnb_out, (void **)&pf->d_nnb_scratch, (void **)&pf->d_row_order,
+                      (void **)&pf->d_nnb_lj, (void **)&pf->d_active, (void **)&pf->d_cell_members, (void **)&pf->d_cell_sets, (void **)&pf->d_blockstats,
+                      (void **)&pf->d_nl_out, (void **)&pf->d_nl};
+    for (void **p : owned) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    pf->built = false;
+    pf->capc = pf->cap = pf->cap_out = 0;
+    pf->active_cap = pf->active_size = 0;
+    pf->built_rows = 0;
+    if (setup_grid(ctx, pf)) return 1;
+    const int nc = pf->grid.ncell;
+    if (nc > pf->ncell_alloc) {
+        for (int **p : {&pf->d_cell_count, &pf->d_cell_start, &pf->d_cell_count_lj, &pf->d_cell_start_lj}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+            AMM_HIP(hipMalloc(p, sizeof(int) * (nc + 1)));
+        }
+        pf->ncell_alloc = nc;
+    }
+    // (the counts are zero between launches; cleared all the same, with the flags and tickets of the list that is gone)
+    AMM_HIP(hipMemset(pf->d_cell_count, 0, sizeof(int) * (nc + 1)));
+    AMM_HIP(hipMemset(pf->d_cell_count_lj, 0, sizeof(int) * (nc + 1)));
+    AMM_HIP(hipMemset(pf->d_flags, 0, sizeof(int) * 16));
+    AMM_HIP(hipMemset(pf->d_ticket, 0, sizeof(int) * 4 * AMM_TICKET_INTS));
+    return 0;
+}

@@ -27,6 +27,7 @@ import numpy as np
 from . import backend as B
 from . import expr as X
 from . import openmm as mm
+from . import unit
 from .forces import describe_energy
 from .utils import InputError
 
@@ -283,6 +284,11 @@ class Engine:
                 if i != j and abs(vecs[i][j]) > 1e-12:
                     raise InputError('only orthorhombic periodic boxes are supported by the HIP path')
         self.box = np.array([vecs[0][0], vecs[1][1], vecs[2][2]], dtype=np.float64)
+        # every long-range-correction constant is proportional to 1 / V: the quadratures are made for the box of creation and their
+        # results multiplied by V(creation) / V(now) where they are handed out (set_box)
+        self._box_ref = self.box.copy()
+        self._vscale = 1.0
+        self.barostat = None
         self.rank, self.world = 0, 1
         dist = torch.distributed
         # (ranks as threads of this process: LocalWorld above)
@@ -377,6 +383,135 @@ class Engine:
                                         integrator.getConstraintTolerance() if hasattr(integrator, 'getConstraintTolerance') else 1e-5)
         if isinstance(integrator, mm.CustomIntegrator):
             integrator._n_hint = n
+        if self.barostat is not None:
+            self._init_barostat()
+
+    # ------------------------------------------------------------------------------- constant pressure
+    def _init_barostat(self):
+        """A MonteCarloBarostat in the System: what it cannot run with is refused here, when the Context is created."""
+        integ = self.integrator
+        if self.world > 1:
+            raise InputError('a MonteCarloBarostat runs on a single rank')
+        steps = getattr(integ, '_steps', [])
+        if any(k == mm.CustomIntegrator.ComputePerDof and t == 'x' and 'tanh(' in e for k, t, e in steps):
+            raise NotImplementedError('a MonteCarloBarostat with regulated dynamics (RegulatedTranslationPropagator) is not supported')
+        # OpenMM makes the attempt at the program's UpdateContextState step (at its start when it has none); here it is made before
+        # the step: the same thing unless a step ahead of UpdateContextState moves x or reads a force or an energy
+        ahead = []
+        for kind, target, expr in steps:
+            if kind == mm.CustomIntegrator.UpdateContextState:
+                break
+            ahead.append((kind, target, expr))
+        else:
+            ahead = []
+        for kind, target, expr in ahead:
+            moves = kind == mm.CustomIntegrator.ConstrainPositions or (kind == mm.CustomIntegrator.ComputePerDof and target == 'x')
+            reads = bool(re.search(r'(?<![A-Za-z_0-9])(f|energy)[0-9]*(?![A-Za-z_0-9])', expr or ''))
+            if moves or reads:
+                raise NotImplementedError('MonteCarloBarostat: the step program moves x or reads a force or an energy ahead of its '
+                                          'UpdateContextState step; only programs whose attempt can be made before the step are supported')
+        molecules = mm.molecules_of(self.system)
+        self.ctx.mol_define(molecules)
+        self._n_molecules = len(molecules)
+        # (device-resident extended variables would carry 1 / V in the coefficients of their correction polynomials across an
+        # attempt: with a barostat such globals are waited for instead)
+        self.device_globals = False
+        seed = self.barostat.getRandomNumberSeed()
+        self._baro_rng = np.random.default_rng(seed if seed != 0 else None)
+        self._baro_due = None           # steps that run before the next attempt (None: frequency - 1, decided at the first step)
+        self._baro_scale = None         # volumeScale (nm^3; 1 % of the volume at the first attempt)
+        self._baro_window = [0, 0]      # attempts / acceptances since the step size last changed
+        self.barostat_stats = dict(attempts=0, accepted=0)
+        self.barostat_log = []          # per attempt: (accepted, w, u2 or None, box edges afterwards) -- the last 1024
+        self._x_saved = self.torch.zeros_like(self.x)
+
+    def set_box(self, edges):
+        """New box edges (nm) for the live context: Context.setPeriodicBoxVectors.  Positions are not touched.  Every 1 / V constant
+        follows and forces and derivative caches become stale.  Compiled step programs stay: they hold no such constant (a program
+        that reads an energy is walked by the host, which asks the entries for their constants as it goes).  The PME mesh and alpha
+        stay as chosen at creation, as in OpenMM."""
+        if self.world > 1:
+            raise InputError('changing the box of a live Context runs on a single rank')
+        edges = np.array(edges, dtype=np.float64).reshape(3)
+        if not np.all(edges > 0):
+            raise InputError('box edges must be positive')
+        if np.array_equal(edges, self.box):
+            return
+        if self._pending is not None and self._pending[1]:
+            # (nothing is pending between two steps today; should that change, the integrator's globals hold such scalars too)
+            self._settle([getattr(self.integrator, '_gvalues', []), self.parameters])
+        self.ctx.set_box(edges)         # (raises, and keeps the old box, when a cutoff exceeds half an edge)
+        self.box = edges
+        self._vscale = float(np.prod(self._box_ref) / np.prod(edges))
+        for entry in self.entries:
+            rescale = getattr(entry, 'rescale', None)
+            if rescale is not None:
+                rescale()
+        self._lrc_on_device = {}
+        self._invalidate_forces()
+
+    def _potential_energy(self):
+        """The potential energy of all force groups with ONE wait for the device: every term adds to one scalar there.  Behind that
+        wait amm_check reads the flag block of every built list (64 bytes each, the stream is idle by then) and the scalar is
+        read: one pipeline drain, 1 + (lists built) small copies."""
+        e = self._energy.zero_()
+        fp = self._fwork.zero_()
+        const = 0.0
+        for entry in self.entries:
+            for pid in entry.pair_ids:
+                self.ctx.force_eval(pid, self.x, fp, accumulate=True, energy=e)
+            if entry.bonded_id is not None:
+                self.ctx.force_eval(entry.bonded_id, self.x, fp, accumulate=True, energy=e)
+            if entry.recip is not None:
+                self.ctx.force_eval(entry.recip, self.x, fp, accumulate=True, energy=e)
+            const += entry.constant
+        self._check()
+        return e.item() + const
+
+    def _barostat_attempt(self):
+        """One Monte Carlo volume move [OpenMM: MonteCarloBarostatImpl::updateContextState]: two energy evaluations, each read with
+        one wait for the device (_potential_energy): two pipeline drains per attempt."""
+        baro = self.barostat
+        pressure = self.parameters[baro.Pressure()] * unit.bar.scale         # bar -> kJ/mol/nm^3 (N_A 1e-25)
+        kT = unit.MOLAR_GAS_CONSTANT_R._value * self.parameters[baro.Temperature()]
+        e0 = self._potential_energy()
+        box0 = self.box.copy()
+        volume = float(np.prod(box0))
+        if self._baro_scale is None:
+            self._baro_scale = 0.01 * volume
+        delta = self._baro_scale * 2.0 * (self._baro_rng.random() - 0.5)
+        new_volume = volume + delta
+        s = (new_volume / volume) ** (1.0 / 3.0)
+        valid = dict(self._valid)
+        self.set_box(box0 * s)
+        self.ctx.mol_scale(self.x, [s, s, s], self._x_saved)
+        e1 = self._potential_energy()
+        w = e1 - e0 + pressure * delta - self._n_molecules * kT * math.log(new_volume / volume)
+        u2 = None
+        accepted = True
+        if w > 0:
+            u2 = self._baro_rng.random()
+            accepted = not u2 > math.exp(-w / kT)
+        if not accepted:
+            # the saved bits and the old box: the force buffers that were valid before the attempt are valid again
+            self.ctx.copy(self.x, self._x_saved)
+            self.ctx.positions_changed()
+            self.set_box(box0)
+            self._valid.update(valid)
+        self.barostat_stats['attempts'] += 1
+        self.barostat_stats['accepted'] += int(accepted)
+        self.barostat_log.append((accepted, w, u2, self.box.copy()))
+        del self.barostat_log[:-1024]
+        self._baro_window[0] += 1
+        self._baro_window[1] += int(accepted)
+        if self._baro_window[0] >= 10:
+            attempts, hits = self._baro_window
+            if hits < 0.25 * attempts:
+                self._baro_scale /= 1.1
+                self._baro_window = [0, 0]
+            elif hits > 0.75 * attempts:
+                self._baro_scale = min(self._baro_scale * 1.1, 0.3 * float(np.prod(self.box)))
+                self._baro_window = [0, 0]
 
     # ------------------------------------------------------------------------------- translation
     def _register_globals(self, force):
@@ -387,6 +522,13 @@ class Engine:
     def _translate(self, force):
         self._register_globals(force)
         if isinstance(force, mm.CMMotionRemover):
+            return
+        if isinstance(force, mm.MonteCarloBarostat):
+            if self.barostat is not None:
+                raise InputError('a System holds one MonteCarloBarostat at most')
+            self.barostat = force       # no energy of its own: it drives Engine.step (_barostat_attempt)
+            self.parameters[force.Pressure()] = force.getDefaultPressure()._value
+            self.parameters[force.Temperature()] = force.getDefaultTemperature()._value
             return
         entry = _Entry(force, force.getForceGroup())
         if isinstance(force, mm.NonbondedForce):
@@ -562,10 +704,11 @@ class Engine:
             if not nb._dispersion:
                 return 0.0
             p = self._effective(base, scales, names, defaults)
-            return dispersion_correction(p[:, 1], p[:, 2], self.box, rc, nb._switch if nb._use_switch else None)
+            return self._vscale * dispersion_correction(p[:, 1], p[:, 2], self._box_ref, rc, nb._switch if nb._use_switch else None)
 
         entry.terms = bonded_terms(self.parameters)
         entry.constant = constant(self.parameters)
+        entry.rescale = lambda: setattr(entry, 'constant', constant(self.parameters))
         lam = set(names) | set(enames)
 
         def update(parameters, changed, force=False):
@@ -762,15 +905,17 @@ class Engine:
             if d['family'] != 'lj':
                 raise NotImplementedError('long-range correction of this CustomNonbondedForce')
             lrc = custom_long_range_correction(lambda r, s_, e_: 4.0 * e_ * ((s_ / r) ** 12 - (s_ / r) ** 6), p[:, 1], p[:, 2],
-                                               self.box, rc, rswitch, codes)
+                                               self._box_ref, rc, rswitch, codes)
         entry.constant = lrc * scale(self.parameters)
+        if lrc:
+            entry.rescale = lambda: setattr(entry, 'constant', self._vscale * lrc * scale(self.parameters))
         depends = set(outer_depends) | ({scale_name} if scale_name else set()) | scale_symbols
         if depends:
             def update(parameters, changed):
                 if not (depends & changed):
                     return False
                 self.ctx.pair_set_scale(pid, scale(parameters))
-                entry.constant = lrc * scale(parameters)
+                entry.constant = self._vscale * lrc * scale(parameters)
                 return 'values'
             entry.update = update
             entry.depends = set(depends)
@@ -811,8 +956,10 @@ class Engine:
         desc = B.pair_desc(B.LJ_VIRIAL, rc, rswitch=rswitch or 0.0, flags=B.SWITCH if rswitch is not None else 0)
         entry.pair_ids.append(self._pair_create(desc, p[:, 0], p[:, 1], p[:, 2], excl))
         if force.getUseLongRangeCorrection():
-            entry.constant = custom_long_range_correction(
-                lambda r, s, e: 24.0 * e * (2.0 * (s / r) ** 12 - (s / r) ** 6), p[:, 1], p[:, 2], self.box, rc, rswitch)
+            virial = custom_long_range_correction(
+                lambda r, s, e: 24.0 * e * (2.0 * (s / r) ** 12 - (s / r) ** 6), p[:, 1], p[:, 2], self._box_ref, rc, rswitch)
+            entry.constant = virial
+            entry.rescale = lambda: setattr(entry, 'constant', self._vscale * virial)
 
     def _translate_softcore(self, force, entry, d):
         """SolvationSystem's softcore CustomNonbondedForce (systems.py:266-272): one interaction group solute x
@@ -861,7 +1008,7 @@ class Engine:
 
         def quadrature(parameters, lam_value):
             record = classes_of(parameters)
-            return record, softcore_long_range_correction(record[1], record[2], codes, self.box, rc, rswitch, lam_value, record[0])
+            return record, softcore_long_range_correction(record[1], record[2], codes, self._box_ref, rc, rswitch, lam_value, record[0])
 
         def on_unit_interval(parameters):
             """The correction as a function of lambda on [0, 1] (it is analytic there): a Chebyshev interpolant through 24 of
@@ -882,7 +1029,7 @@ class Engine:
                 value = float(on_unit_interval(parameters)[0](lam_value))
             else:
                 value = quadrature(parameters, lam_value)[1]
-            return value * (parameters[scale_name] if scale_name else 1.0)
+            return self._vscale * value * (parameters[scale_name] if scale_name else 1.0)
 
         def constant_derivative(parameters):
             """d(correction)/d(lambda)"""
@@ -894,7 +1041,7 @@ class Engine:
             else:
                 h = 1e-6
                 value = (quadrature(parameters, lam_value + h)[1] - quadrature(parameters, lam_value - h)[1]) / (2 * h)
-            return value * (parameters[scale_name] if scale_name else 1.0)
+            return self._vscale * value * (parameters[scale_name] if scale_name else 1.0)
 
         def derivative_polynomial(parameters):
             """d(correction)/d(lambda) on [0, 1] as monomial coefficients in u = 2 lambda - 1 (lowest first), for the evaluation on
@@ -909,10 +1056,11 @@ class Engine:
                 while keep > 1 and np.abs(cheb[keep - 1:]).sum() < 1e-15 * np.abs(cheb).max():
                     keep -= 1
                 record.append([float(c) for c in np.polynomial.chebyshev.cheb2poly(cheb[:keep])])
-            scale = parameters[scale_name] if scale_name else 1.0
+            scale = self._vscale * (parameters[scale_name] if scale_name else 1.0)
             return record[4] if scale == 1.0 else [c * scale for c in record[4]]
 
         entry.constant = constant(self.parameters)
+        entry.rescale = lambda: setattr(entry, 'constant', constant(self.parameters))
         lam = set(names) | {lam_name} | ({scale_name} if scale_name else set())
         entry.softcore = dict(pid=pid, lambda_name=lam_name, constant=constant, constant_derivative=constant_derivative, depends=lam,
                               use_lrc=bool(use_lrc), derivative_polynomial=derivative_polynomial)
@@ -2820,6 +2968,26 @@ class Engine:
             self.time += integ._dt
 
     def step(self, n):
+        """n steps of the integrator's program.  With a MonteCarloBarostat the attempt of every `frequency`-th step is made right
+        before that step, and the steps between two attempts run as one chunk (the compiled `repeat` path)."""
+        remaining = int(n)
+        if self.barostat is None or remaining <= 0:
+            return self._step_program(n)
+        while remaining > 0:
+            frequency = self.barostat.getFrequency()
+            if frequency <= 0:
+                return self._step_program(remaining)
+            if self._baro_due is None:
+                self._baro_due = frequency - 1
+            if self._baro_due <= 0:
+                self._barostat_attempt()
+                self._baro_due = frequency
+            count = min(remaining, self._baro_due)
+            self._step_program(count)
+            self._baro_due -= count
+            remaining -= count
+
+    def _step_program(self, n):
         integ = self.integrator
         if not isinstance(integ, mm.CustomIntegrator):
             raise NotImplementedError('only CustomIntegrator step programs run on the HIP path')

@@ -20,6 +20,7 @@ import numpy as np
 
 from .. import unit as _unit
 from ..unit import Quantity, md_value
+from ..utils import InputError
 
 nm = _unit.nanometer
 kjmol = _unit.kilojoule_per_mole
@@ -581,6 +582,63 @@ class CMMotionRemover(Force):
         self._frequency = frequency
 
 
+class MonteCarloBarostat(Force):
+    """openmm.MonteCarloBarostat: isotropic Monte Carlo volume moves at constant pressure [OpenMM: MonteCarloBarostatImpl.cpp].
+    Every `frequency` steps the Context scales the centres of its molecules (Context.getMolecules()) and the box by
+    s = ((V + dV) / V)^(1/3), dV uniform in +-volumeScale, and keeps the move with probability min(1, exp(-w / kT)),
+    w = dE + P dV - N_molecules kT ln((V + dV) / V); a rejected move restores positions and box bit for bit.  volumeScale starts at
+    1 % of the volume and follows the acceptance rate (below 25 % of ten attempts: / 1.1, above 75 %: x 1.1, at most 0.3 V).
+    The attempt is made where the step program has its UpdateContextState step -- here: before the step (Engine.step), which is the
+    same thing for every program that neither moves x nor reads a force or an energy ahead of that step; other programs are refused
+    when the Context is created.  The random numbers are numpy's (default_rng(seed); seed 0: entropy), not OpenMM's stream: one draw
+    for dV per attempt, one for the Metropolis test only when w > 0.  No energy of its own; the engine skips it like CMMotionRemover."""
+
+    def __init__(self, defaultPressure, defaultTemperature, frequency=25):
+        Force.__init__(self)
+        self.setDefaultPressure(defaultPressure)
+        self.setDefaultTemperature(defaultTemperature)
+        self.setFrequency(frequency)
+        self._seed = 0
+
+    @staticmethod
+    def Pressure():
+        return 'MonteCarloPressure'
+
+    @staticmethod
+    def Temperature():
+        return 'MonteCarloTemperature'
+
+    def getDefaultPressure(self):
+        return Quantity(self._pressure, _unit.bar)
+
+    def setDefaultPressure(self, pressure):
+        self._pressure = float(pressure.value_in_unit(_unit.bar) if isinstance(pressure, Quantity) else pressure)
+
+    def getDefaultTemperature(self):
+        return Quantity(self._temperature, _unit.kelvin)
+
+    def setDefaultTemperature(self, temperature):
+        self._temperature = float(md_value(temperature, _unit.kelvin))
+
+    def getFrequency(self):
+        return self._frequency
+
+    def setFrequency(self, frequency):
+        """Steps between two attempts; 0 disables the barostat."""
+        if int(frequency) < 0:
+            raise OpenMMException('MonteCarloBarostat: the frequency must not be negative')
+        self._frequency = int(frequency)
+
+    def getRandomNumberSeed(self):
+        return self._seed
+
+    def setRandomNumberSeed(self, seed):
+        self._seed = int(seed)
+
+    def usesPeriodicBoundaryConditions(self):
+        return False
+
+
 # ------------------------------------------------------------------------------------------------ system
 class System:
     def __init__(self):
@@ -875,6 +933,35 @@ def _as_array(values, n, what):
     return arr
 
 
+def molecules_of(system):
+    """The molecules of a System: connected components of its bond graph (Context.getMolecules)."""
+    n = system.getNumParticles()
+    parent = list(range(n))
+
+    def find(a):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+    pairs = [(c[0], c[1]) for c in system._constraints]
+    for force in system.getForces():
+        if isinstance(force, (HarmonicBondForce, CustomBondForce)):
+            pairs += [(b[0], b[1]) for b in force._bonds]
+        elif isinstance(force, (HarmonicAngleForce, CustomAngleForce)):
+            pairs += [(r[0], r[1]) for r in force._angles] + [(r[1], r[2]) for r in force._angles]
+        elif isinstance(force, PeriodicTorsionForce):
+            pairs += [(r[0], r[1]) for r in force._torsions] + [(r[1], r[2]) for r in force._torsions] + \
+                     [(r[2], r[3]) for r in force._torsions]
+    for i, j in pairs:
+        a, b = find(int(i)), find(int(j))
+        if a != b:
+            parent[max(a, b)] = min(a, b)
+    groups = {}
+    for i in range(n):
+        groups.setdefault(find(i), []).append(i)
+    return [groups[r] for r in sorted(groups)]
+
+
 class Context:
     def __init__(self, system, integrator, platform=None, properties=None):
         from ..engine import Engine
@@ -924,6 +1011,8 @@ class Context:
         self._engine.apply_velocity_constraints()
 
     def setParameter(self, name, value):
+        if name == MonteCarloBarostat.Pressure() and isinstance(value, Quantity):
+            value = value.value_in_unit(_unit.bar)        # (the parameter is a number of bar, as in OpenMM)
         self._engine.set_parameter(name, float(md_value(value)))
 
     def getParameter(self, name):
@@ -933,12 +1022,18 @@ class Context:
         return dict(self._engine.parameters)
 
     def setPeriodicBoxVectors(self, a, b, c):
-        new = [float(md_value(a[0])), float(md_value(b[1])), float(md_value(c[2]))]
-        if not np.allclose(new, self._engine.box, rtol=0, atol=1e-12):
-            raise OpenMMException('changing the box of a live Context is not supported by the HIP path')
+        """A new (orthorhombic) box for the live Context; the positions stay as they are, as in OpenMM."""
+        vecs = [[float(md_value(x)) for x in md_value(v)] for v in (a, b, c)]
+        for i in range(3):
+            for j in range(3):
+                if i != j and abs(vecs[i][j]) > 1e-12:
+                    raise InputError('only orthorhombic periodic boxes are supported by the HIP path')
+        self._engine.set_box([vecs[0][0], vecs[1][1], vecs[2][2]])
 
     def setState(self, state):
-        """Positions and velocities (those the State carries) of another Context's State."""
+        """Box, then positions and velocities (those the State carries) of another Context's State."""
+        if state._box is not None:
+            self.setPeriodicBoxVectors(*state._box)
         if state._x is not None:
             self._engine.set_positions(state._x)
         if state._v is not None:
@@ -947,31 +1042,7 @@ class Context:
     def getMolecules(self):
         """Connected components of the bond graph (bonds of the bonded forces + constraints), as OpenMM's
         Context.getMolecules(): a list of lists of atom indices, each in increasing order."""
-        n = self._system.getNumParticles()
-        parent = list(range(n))
-
-        def find(a):
-            while parent[a] != a:
-                parent[a] = parent[parent[a]]
-                a = parent[a]
-            return a
-        pairs = [(c[0], c[1]) for c in self._system._constraints]
-        for force in self._system.getForces():
-            if isinstance(force, (HarmonicBondForce, CustomBondForce)):
-                pairs += [(b[0], b[1]) for b in force._bonds]
-            elif isinstance(force, (HarmonicAngleForce, CustomAngleForce)):
-                pairs += [(r[0], r[1]) for r in force._angles] + [(r[1], r[2]) for r in force._angles]
-            elif isinstance(force, PeriodicTorsionForce):
-                pairs += [(r[0], r[1]) for r in force._torsions] + [(r[1], r[2]) for r in force._torsions] + \
-                         [(r[2], r[3]) for r in force._torsions]
-        for i, j in pairs:
-            a, b = find(int(i)), find(int(j))
-            if a != b:
-                parent[max(a, b)] = min(a, b)
-        groups = {}
-        for i in range(n):
-            groups.setdefault(find(i), []).append(i)
-        return [groups[r] for r in sorted(groups)]
+        return molecules_of(self._system)
 
     def getState(self, getPositions=False, getVelocities=False, getForces=False, getEnergy=False,
                  getParameters=False, enforcePeriodicBox=False, groups=-1, getParameterDerivatives=False):

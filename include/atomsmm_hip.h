@@ -344,6 +344,35 @@ int amm_exchange_per(amm_ctx *ctx, int32_t *per);
 /* amm_run_ops fuses KICK;MOVE;EVAL(bond-list group);KICK into one launch (bit-identical results); 0 disables. */
 int amm_set_fuse_inner(amm_ctx *ctx, int32_t on);
 
+/* ---- a box that changes: constant-pressure runs ------------------------------------------------- */
+/* Context::setPeriodicBoxVectors of OpenMM on a live context (orthorhombic: the three edges), which MonteCarloBarostat calls at
+ * every attempt and PressureComputer.import_configuration (computers.py:243) at every frame.  Legal between any two amm_run_ops /
+ * amm_force_eval calls; stream-ordered -- every kernel takes the box by value at launch, so work already queued keeps the old one.
+ * Every pair force derives its Verlet buffer and list radii again under the clamp skin <= 0.999 (L/2 - rc), every neighbour list,
+ * sorted copy, candidate set and displacement reference made for the old box is dropped, and the next evaluation is exact for the
+ * new one.  The cell counts of a list are kept, and nothing is sized, allocated or waited for, while (a) the cells still admit the
+ * list radius -- a kept grid may take up to half of the Verlet buffer before it gives way, (b) the density of list entries
+ * rlist^3 / V has grown by less than a quarter since the list was sized, and (c) the edges are within 2 % of those at that time or
+ * the cell counts a fresh context would choose are the same.  Otherwise the list is dropped with its capacities and the next
+ * evaluation sizes and builds it as a first evaluation does (a "regrid").  Non-zero with the message of amm_pair_create when a pair
+ * force has rc > L/2 on some axis, or when a wait or an allocation fails: the old box then stays in force (lists that were already
+ * dropped are built again by their next evaluation).  A list made with an outer buffer (amm_set_outer_skin) is sized again when the
+ * clamp takes that buffer away or gives it back.  Not for a context that is one rank of several (nor is amm_mol_scale). */
+int amm_set_box(amm_ctx *ctx, const double h_box[3]);
+/* out[0] = amm_set_box calls that succeeded, out[1] = those that chose new cell counts for some list, out[2] = those that
+ * freed or allocated device memory or waited for the stream, out[3] = 0. */
+int amm_box_stats(amm_ctx *ctx, int64_t out[4]);
+/* Context::getMolecules of OpenMM, handed over once: molecule m holds atoms h_atoms[h_ptr[m] .. h_ptr[m + 1]) (CSR, n_mol + 1
+ * offsets).  Every atom of the context belongs to exactly one molecule -- anything else is an error; the atoms of a molecule need
+ * not be contiguous.  Replaces an earlier definition (waits for the stream). */
+int amm_mol_define(amm_ctx *ctx, const int32_t *h_ptr, const int32_t *h_atoms, int32_t n_mol);
+/* The coordinate scaling of MonteCarloBarostat (ReferenceMonteCarloBarostat::applyBarostat of OpenMM): for every molecule, the centre
+ * c = the unweighted mean of its atoms' positions, summed in list order with a fixed association (two runs give the same bits); every
+ * atom of the molecule moves by (scale[k] - 1) c[k] along axis k.  d_x_saved (may be NULL) first receives the old positions bit for
+ * bit: amm_copy from it undoes a rejected move.  Nothing is wrapped into the box.  One launch (csrc/barostat.hip: one lane per
+ * molecule of up to 8 atoms, one wavefront per longer one); counts as amm_positions_changed. */
+int amm_mol_scale(amm_ctx *ctx, double *d_x, double *d_x_saved, const double scale[3]);
+
 /* ---- energy minimisation --------------------------------------------------------------------- */
 /* LocalEnergyMinimizer::minimize(context, tolerance, maxIterations) of OpenMM, which the reference reaches through
  * app.Simulation.minimizeEnergy (the line every AtomsMM script runs before simulation.step): OpenMM runs L-BFGS on the host over
