@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get('AMM_LIB') or os.path.join(HERE, 'libatomsmm_hip.so') 
 
 NEAR_NONE, NEAR_SHIFT, NEAR_FSWITCH, DAMPED, NONBONDED, SOFTCORE, LJ_VIRIAL = range(7)
 GUARD_RC0, COULOMB_EWALD, COULOMB_RF, SWITCH, NO_SHIFT, GROUP_LJ, GROUP_Q = 1, 2, 4, 8, 16, 32, 64
+FREE_SPACE = 128   # NoCutoff / CutoffNonPeriodic: all pairs, no box, no list (csrc/free.hip)
 BOND_HARMONIC, ANGLE_HARMONIC, BOND_LJC, BOND_NEAR, TORSION_PERIODIC, BOND_EWALD_EXCL = range(6)
 BOND_VIRIAL_HARMONIC, BOND_VIRIAL_LJ = 6, 7
 OP_EVAL, OP_KICK, OP_MOVE, OP_COPY, OP_COMBINE, OP_EXPR, OP_BATH = 1, 2, 3, 4, 5, 6, 7
@@ -280,7 +281,8 @@ class HipContext:
         torch.cuda.set_device(self.device)
         if stream is None:
             stream = torch.cuda.current_stream(self.torch_device).cuda_stream
-        b, bp = _hd(np.asarray(box, dtype=np.float64).reshape(3))
+        # box = None: a context without a periodic box (free-space pair forces and non-periodic terms only)
+        b, bp = (None, None) if box is None else _hd(np.asarray(box, dtype=np.float64).reshape(3))
         h = C.c_void_p()
         _chk(L.amm_create(self.n, bp, self.device, C.c_void_p(stream), C.byref(h)))
         self.h = h

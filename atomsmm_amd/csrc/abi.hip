@@ -40,17 +40,42 @@ static int upload(T **dst, const T *src, size_t n) {
     return 0;
 }
 
+// exclusion pairs -> symmetric CSR in original atom indices (amm_pair_create)
+static int amm_excl_csr(int n, const int32_t *h_excl, int n_excl, std::vector<int> &ptr, std::vector<int> &idx) {
+    ptr.assign(n + 1, 0);
+    for (int e = 0; e < n_excl; ++e) {
+        int i = h_excl[2 * e], j = h_excl[2 * e + 1];
+        if (i < 0 || j < 0 || i >= n || j >= n) {
+            amm_set_error("amm_pair_create: exclusion index out of range");
+            return 1;
+        }
+        if (i == j) continue;
+        ptr[i + 1]++;
+        ptr[j + 1]++;
+    }
+    for (int i = 0; i < n; ++i) ptr[i + 1] += ptr[i];
+    idx.assign(ptr[n], 0);
+    std::vector<int> fill(ptr.begin(), ptr.end() - 1);
+    for (int e = 0; e < n_excl; ++e) {
+        int i = h_excl[2 * e], j = h_excl[2 * e + 1];
+        if (i == j) continue;
+        idx[fill[i]++] = j;
+        idx[fill[j]++] = i;
+    }
+    return 0;
+}
+
 extern "C" {
 
 int amm_abi_version(void) { return AMM_ABI_VERSION; }
 const char *amm_last_error(void) { return g_error.c_str(); }
 
 int amm_create(int32_t n_atoms, const double h_box[3], int32_t device, void *stream, amm_ctx **out) {
-    if (!out || n_atoms <= 0 || !h_box) {
+    if (!out || n_atoms <= 0) {
         amm_set_error("amm_create: bad arguments");
         return 1;
     }
-    for (int k = 0; k < 3; ++k)
+    for (int k = 0; h_box && k < 3; ++k)
         if (!(h_box[k] > 0.0)) {
             amm_set_error("amm_create: box edges must be positive (orthorhombic periodic box)");
             return 1;
@@ -66,9 +91,10 @@ int amm_create(int32_t n_atoms, const double h_box[3], int32_t device, void *str
     ctx->n = n_atoms;
     ctx->device = device;
     ctx->stream = (hipStream_t)stream;
+    ctx->has_box = h_box != nullptr;       // (no box: free-space forces and non-periodic terms only; nothing reads ctx->box)
     for (int k = 0; k < 3; ++k) {
-        ctx->box.L[k] = h_box[k];
-        ctx->box.invL[k] = 1.0 / h_box[k];
+        ctx->box.L[k] = h_box ? h_box[k] : 0.0;
+        ctx->box.invL[k] = h_box ? 1.0 / h_box[k] : 0.0;
     }
     AMM_HIP(hipMalloc(&ctx->d_scratch, sizeof(double) * ((n_atoms + 255) / 256 + 8)));
     *out = ctx;
@@ -114,11 +140,16 @@ int amm_set_slice(amm_ctx *ctx, int32_t rank, int32_t world) {
         amm_set_error("amm_set_slice: need 0 <= rank < world");
         return 1;
     }
-    for (auto &f : ctx->forces)
+    for (auto &f : ctx->forces) {
+        if (f.pair && f.pair->free_space && world > 1) {
+            amm_set_error("amm_set_slice: a free-space pair force runs on a single rank");
+            return 1;
+        }
         if (f.pair && f.pair->built) {
             amm_set_error("amm_set_slice must be called before the first force evaluation");
             return 1;
         }
+    }
     ctx->rank = rank;
     ctx->world = world;
     return 0;
@@ -225,24 +256,73 @@ int amm_pair_create(amm_ctx *ctx, const amm_pair_desc *desc, const double *h_q, 
         amm_set_error("amm_pair_create: unknown family");
         return 1;
     }
-    if (!(desc->rc > 0.0)) {
+    const bool free_space = (desc->flags & AMM_FREE_SPACE) != 0;
+    if (!free_space && !ctx->has_box) {
+        amm_set_error("amm_pair_create: the context has no periodic box (only AMM_FREE_SPACE pair forces run without one)");
+        return 1;
+    }
+    if (!free_space && !(desc->rc > 0.0)) {
         amm_set_error("amm_pair_create: cutoff must be positive");
         return 1;
+    }
+    if (free_space) {
+        std::string why;
+        if (!amm_free_supported(*desc, why)) {
+            amm_set_error("amm_pair_create (AMM_FREE_SPACE): " + why);
+            return 1;
+        }
+        if (ctx->n > AMM_FREE_MAX_ATOMS) {
+            amm_set_error("amm_pair_create: a free-space pair force walks all n^2 pairs and takes at most " + std::to_string(AMM_FREE_MAX_ATOMS) +
+                          " atoms (this context has " + std::to_string(ctx->n) + ")");
+            return 1;
+        }
+        if (ctx->world > 1) {
+            amm_set_error("amm_pair_create: a free-space pair force runs on a single rank");
+            return 1;
+        }
     }
     PairForce *pf = new PairForce();
     pf->desc = *desc;
     pf->n = ctx->n;
     pf->skin_out_req = ctx->skin_out;
+    pf->free_space = free_space;
     if (ctx->n >= (1 << 26)) {      // the traversal addresses the sorted copies with 32-bit byte offsets (32 B per slot)
         amm_set_error("amm_pair_create: more than 2^26 atoms are not supported");
         delete pf;
         return 1;
     }
-    if (amm_pair_build_consts(*desc, pf->pc) || amm_pair_build_table(pf)) {
+    if (amm_pair_build_consts(*desc, pf->pc) || (!free_space && amm_pair_build_table(pf))) {
         delete pf;
         return 1;
     }
     const int n = ctx->n;
+    if (free_space) {
+        // no radial table, no grid, no list: the exclusion CSR and the parameters in atom order are all such a force keeps
+        std::memset(&pf->pc.tab, 0, sizeof(pf->pc.tab));
+        pf->pc.tab.ss_first = -1;
+        pf->last_kind = 4;
+        std::memset(&pf->grid, 0, sizeof(pf->grid));
+        std::vector<int> ptr, idx;
+        if (amm_excl_csr(n, h_excl, n_excl, ptr, idx)) {
+            delete pf;
+            return 1;
+        }
+        // (the kernel reads the charges and one (sigma/2, 2 sqrt(eps)) record per atom: no separate sigma / epsilon arrays)
+        if (upload(&pf->d_excl_ptr, ptr.data(), ptr.size()) || upload(&pf->d_excl_idx, idx.data(), idx.size()) ||
+            hipMalloc(&pf->d_q, sizeof(double) * n) != hipSuccess || hipMalloc(&pf->d_lj_s, sizeof(double2) * n) != hipSuccess) {
+            amm_set_error("amm_pair_create: device allocation failed");
+            amm_pair_free(pf);
+            delete pf;
+            return 1;
+        }
+        ForceObj fo;
+        fo.type = 1;
+        fo.pair = pf;
+        ctx->forces.push_back(fo);
+        *force_id = (int)ctx->forces.size() - 1;
+        pf->id = *force_id;
+        return amm_pair_set_params(ctx, *force_id, h_q, h_sigma, h_eps);
+    }
     // default Verlet buffer: 0.1 nm on one GPU (C3: list build 0.58 x 320 us per step against +30 % pair work at 0.2 nm);
     // a rank's slice makes the pair kernels 2 - 5 x cheaper but the rebuild only 1.6 - 2 x (scripts/probe_pair.py --world N),
     // so the optimum moves to a larger buffer: 0.15 nm for 2 ranks, 0.2 nm beyond
@@ -254,27 +334,16 @@ int amm_pair_create(amm_ctx *ctx, const amm_pair_desc *desc, const double *h_q, 
         return 1;
     }
     // exclusions -> symmetric CSR in original atom indices
-    std::vector<int> ptr(n + 1, 0);
-    for (int e = 0; e < n_excl; ++e) {
-        int i = h_excl[2 * e], j = h_excl[2 * e + 1];
-        if (i < 0 || j < 0 || i >= n || j >= n) {
-            amm_set_error("amm_pair_create: exclusion index out of range");
-            delete pf;
-            return 1;
-        }
-        if (i == j) continue;
-        ptr[i + 1]++;
-        ptr[j + 1]++;
+    std::vector<int> ptr, idx;
+    if (amm_excl_csr(n, h_excl, n_excl, ptr, idx)) {
+        delete pf;
+        return 1;
     }
-    for (int i = 0; i < n; ++i) ptr[i + 1] += ptr[i];
-    std::vector<int> idx(ptr[n]), fill(ptr.begin(), ptr.end() - 1);
-    for (int e = 0; e < n_excl; ++e) {
-        int i = h_excl[2 * e], j = h_excl[2 * e + 1];
-        if (i == j) continue;
-        idx[fill[i]++] = j;
-        idx[fill[j]++] = i;
+    if (upload(&pf->d_excl_ptr, ptr.data(), ptr.size()) || upload(&pf->d_excl_idx, idx.data(), idx.size())) {
+        amm_pair_free(pf);
+        delete pf;
+        return 1;
     }
-    if (upload(&pf->d_excl_ptr, ptr.data(), ptr.size()) || upload(&pf->d_excl_idx, idx.data(), idx.size())) return 1;
     if (desc->family == AMM_SOFTCORE || (desc->flags & (AMM_GROUP_LJ | AMM_GROUP_Q))) {
         pf->h_excl_ptr = ptr;
         pf->h_excl_idx = idx;
@@ -353,6 +422,10 @@ int amm_pair_create(amm_ctx *ctx, const amm_pair_desc *desc, const double *h_q, 
 int amm_pair_set_lambda(amm_ctx *ctx, int32_t force_id, double value) {
     PairForce *pf = get_pair(ctx, force_id);
     if (!pf) return 1;
+    if (pf->free_space) {
+        amm_set_error("amm_pair_set_lambda: not for a free-space pair force (AMM_FREE_SPACE)");
+        return 1;
+    }
     if (pf->desc.family != AMM_SOFTCORE) {
         amm_set_error("amm_pair_set_lambda: not a softcore pair force");
         return 1;
@@ -365,6 +438,10 @@ int amm_pair_set_lambda(amm_ctx *ctx, int32_t force_id, double value) {
 int amm_pair_set_lambda_dev(amm_ctx *ctx, int32_t force_id, const double *d_lambda) {
     PairForce *pf = get_pair(ctx, force_id);
     if (!pf) return 1;
+    if (pf->free_space) {
+        amm_set_error("amm_pair_set_lambda_dev: not for a free-space pair force (AMM_FREE_SPACE)");
+        return 1;
+    }
     if (pf->desc.family != AMM_SOFTCORE) {
         amm_set_error("amm_pair_set_lambda_dev: not a softcore pair force");
         return 1;
@@ -394,6 +471,10 @@ int amm_pair_set_scale(amm_ctx *ctx, int32_t force_id, double scale) {
 int amm_pair_energy_derivative(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *d_out) {
     PairForce *pf = get_pair(ctx, force_id);
     if (!pf || !d_pos || !d_out) return 1;
+    if (pf->free_space) {
+        amm_set_error("amm_pair_energy_derivative: not for a free-space pair force (AMM_FREE_SPACE)");
+        return 1;
+    }
     if (pf->desc.family != AMM_SOFTCORE) {
         amm_set_error("amm_pair_energy_derivative: only the softcore family depends on a global parameter");
         return 1;
@@ -412,6 +493,10 @@ int amm_pair_energy_derivative(amm_ctx *ctx, int32_t force_id, const double *d_p
 int amm_pair_energy_states(amm_ctx *ctx, int32_t force_id, const double *d_pos, const double *d_lambdas, int32_t n_states, double *d_out) {
     PairForce *pf = get_pair(ctx, force_id);
     if (!pf) return 1;
+    if (pf->free_space) {
+        amm_set_error("amm_pair_energy_states: not for a free-space pair force (AMM_FREE_SPACE)");
+        return 1;
+    }
     if (n_states < 1 || n_states > AMM_MAX_STATES) {
         amm_set_error("amm_pair_energy_states: need 1 <= n_states <= AMM_MAX_STATES (" + std::to_string(AMM_MAX_STATES) + ")");
         return 1;
@@ -498,6 +583,10 @@ int amm_pair_share_list(amm_ctx *ctx, int32_t force_id, int32_t host_id) {
         amm_set_error("amm_pair_share_list: not a force of the caller's");
         return 1;
     }
+    if (g->free_space || h->free_space) {
+        amm_set_error("amm_pair_share_list: a free-space pair force (AMM_FREE_SPACE) has no neighbour list to share");
+        return 1;
+    }
     return share_list_pf(ctx, g, h);
 }
 
@@ -519,6 +608,16 @@ int amm_pair_set_params(amm_ctx *ctx, int32_t force_id, const double *h_q, const
     // ordered after any kernels already queued on the stream
     AMM_HIP(hipStreamSynchronize(ctx->stream));
     AMM_HIP(hipMemcpy(pf->d_q, h_q, sizeof(double) * n, hipMemcpyHostToDevice));
+    if (pf->free_space) {
+        // the tiles of free.hip read (sigma/2, 2 sqrt(eps)) as one 16-byte record per atom, in atom order; nothing else is kept
+        std::vector<double> lj(2 * (size_t)n);
+        for (int i = 0; i < n; ++i) {
+            lj[2 * i] = hs[i];
+            lj[2 * i + 1] = se[i];
+        }
+        AMM_HIP(hipMemcpy(pf->d_lj_s, lj.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+        return 0;
+    }
     AMM_HIP(hipMemcpy(pf->d_hsig, hs.data(), sizeof(double) * n, hipMemcpyHostToDevice));
     AMM_HIP(hipMemcpy(pf->d_seps2, se.data(), sizeof(double) * n, hipMemcpyHostToDevice));
     // interaction-group forces carry the set code of every atom (0 none, 1, 2) in place of a parameter: q for SOFTCORE and
@@ -641,6 +740,10 @@ int amm_bonded_add_terms(amm_ctx *ctx, int32_t force_id, int32_t kind, const int
         amm_set_error("amm_bonded_add_terms: unknown kind");
         return 1;
     }
+    if ((periodic || kind == AMM_BOND_EWALD_EXCL) && !ctx->has_box) {
+        amm_set_error("amm_bonded_add_terms: periodic terms, but the context has no periodic box");
+        return 1;
+    }
     if (!bs->h_idx[kind].empty() && bs->periodic[kind] != periodic) {
         amm_set_error("amm_bonded_add_terms: mixed periodic flags within one kind");
         return 1;
@@ -732,6 +835,10 @@ int amm_pme_create(amm_ctx *ctx, double alpha, int32_t nx, int32_t ny, int32_t n
                    int32_t *force_id) {
     if (!ctx || !h_q || !force_id) {
         amm_set_error("amm_pme_create: bad arguments");
+        return 1;
+    }
+    if (!ctx->has_box) {
+        amm_set_error("amm_pme_create: the context has no periodic box");
         return 1;
     }
     AMM_HIP(hipSetDevice(ctx->device));
@@ -1258,6 +1365,7 @@ int amm_run_ops_from(amm_ctx *ctx, const amm_op *ops, int32_t n_ops, int32_t rep
             const int ga = ops[t].a;
             if (ga < 0 || ga >= AMM_MAX_GROUPS || ctx->groups[ga].forces.empty() || ctx->forces[ctx->groups[ga].forces[0]].type != 1) break;
             PairForce *pa = ctx->forces[ctx->groups[ga].forces[0]].pair;
+            if (pa->free_space) break;          // (a free-space force reads no sorted copies)
             P.next = pa;
             if (t + 1 < n_ops && ops[t + 1].op == AMM_OP_EVAL && ops[t + 1].a >= 0 && ops[t + 1].a < AMM_MAX_GROUPS &&
                 !ctx->groups[ops[t + 1].a].forces.empty() && ctx->forces[ctx->groups[ops[t + 1].a].forces[0]].type == 1) {
@@ -1311,7 +1419,8 @@ int amm_run_ops_from(amm_ctx *ctx, const amm_op *ops, int32_t n_ops, int32_t rep
             }
             if (ops[t].op != AMM_OP_EVAL) continue;
             const int ga = ops[t].a;
-            if (ga >= 0 && ga < AMM_MAX_GROUPS && ctx->groups[ga].forces.size() == 1 && ctx->forces[ctx->groups[ga].forces[0]].type == 1)
+            if (ga >= 0 && ga < AMM_MAX_GROUPS && ctx->groups[ga].forces.size() == 1 && ctx->forces[ctx->groups[ga].forces[0]].type == 1 &&
+                !ctx->forces[ctx->groups[ga].forces[0]].pair->free_space)
                 P.next = ctx->forces[ctx->groups[ga].forces[0]].pair;
             break;
         }
@@ -1675,7 +1784,7 @@ int amm_run_ops_from(amm_ctx *ctx, const amm_op *ops, int32_t n_ops, int32_t rep
                 }
                 if (g.forces.empty()) AMM_HIP(hipMemsetAsync(buf, 0, sizeof(double) * 3 * (size_t)ctx->n, ctx->stream));
                 if ((ctx->world == 1 ? !g.exchange : g.exchange == AMM_EXCHANGE_GATHER) && g.forces.size() == 1 &&
-                    ctx->forces[g.forces[0]].type == 1) {
+                    ctx->forces[g.forces[0]].type == 1 && !ctx->forces[g.forces[0]].pair->free_space) {
                     // one pair force: the kicks and the inner loop that follow can ride on its launch (molecule rows: cepi_rows; several
                     // ranks: followed by an exchange of positions and velocities instead of forces)
                     EpiPlan plan;
@@ -1711,8 +1820,8 @@ int amm_run_ops_from(amm_ctx *ctx, const amm_op *ops, int32_t n_ops, int32_t rep
                 }
                 forget_own_only(buf);           // (every path below writes the group's buffer in full)
                 if (g.exchange) {
-                    if (g.forces.size() != 1 || ctx->forces[g.forces[0]].type != 1) {
-                        amm_set_error("amm_run_ops: an exchanged group must hold exactly one pair force");
+                    if (g.forces.size() != 1 || ctx->forces[g.forces[0]].type != 1 || ctx->forces[g.forces[0]].pair->free_space) {
+                        amm_set_error("amm_run_ops: an exchanged group must hold exactly one pair force (with a neighbour list)");
                         return 1;
                     }
                     if (amm_pair_eval_impl(ctx, ctx->forces[g.forces[0]].pair, ctx->d_x, buf, 0, nullptr, nullptr, nullptr, 0, 1)) return 1;
@@ -1872,6 +1981,12 @@ int amm_pair_get_stats(amm_ctx *ctx, int32_t force_id, amm_pair_stats *out) {
     std::memset(out, 0, sizeof(*out));
     AMM_HIP(hipStreamSynchronize(ctx->stream));
     out->n_evals = pf->n_evals;
+    if (pf->free_space) {          // no grid, no list, no builds: its evaluations and its lanes per row
+        out->lanes_per_atom = amm_free_lanes_per_row(pf->n);
+        out->n_slice_atoms = pf->n;
+        out->list_kind = 4;
+        return 0;
+    }
     PairForce *L = pf->host ? pf->host : pf;
     out->capacity = L->cap;
     out->lanes_per_atom = L->lpa;
@@ -1937,6 +2052,7 @@ int amm_pair_row_padding(amm_ctx *ctx, int32_t force_id, int64_t out[2]) {
     }
     PairForce *L = pf->host ? pf->host : pf;
     out[0] = out[1] = 0;
+    if (pf->free_space) return 0;
     if (!(L->last_kind >= 1 && L->cl && L->cl->built)) return 0;       // per-atom rows: not reported
     long long v[2];
     if (amm_cluster_row_padding_impl(ctx, pf, v)) return 1;
@@ -1949,6 +2065,10 @@ int amm_pair_count_within(amm_ctx *ctx, int32_t force_id, const double *d_pos, d
     PairForce *pf = get_pair(ctx, force_id);
     if (!pf || !d_pos || !count) {
         amm_set_error("amm_pair_count_within: null argument or not a pair force");
+        return 1;
+    }
+    if (pf->free_space) {
+        amm_set_error("amm_pair_count_within: a free-space pair force (AMM_FREE_SPACE) has no neighbour rows to count");
         return 1;
     }
     long long c = 0;
@@ -2049,7 +2169,7 @@ static int box_apply(amm_ctx *ctx, bool &regrid, bool &waited) {
     // 1. every force's buffers as amm_pair_create would derive them in this box (a hybrid list's per-atom part asks for a multiple of
     // its parent's: the parent comes first in ctx->forces)
     for (auto &fo : ctx->forces) {
-        if (fo.type != 1) continue;
+        if (fo.type != 1 || fo.pair->free_space) continue;
         PairForce *pf = fo.pair;
         pair_derive_buffers(ctx, pf);
         if (pf->rest) pf->rest->skin_req = pf->skin * ctx->opt_rest_skin_factor;
@@ -2063,7 +2183,7 @@ static int box_apply(amm_ctx *ctx, bool &regrid, bool &waited) {
         return 0;
     };
     for (auto &fo : ctx->forces) {
-        if (fo.type != 1 || fo.pair->host) continue;
+        if (fo.type != 1 || fo.pair->host || fo.pair->free_space) continue;
         PairForce *L = fo.pair;
         const bool dual = L->skin_out > L->skin * (1 + 1e-9);
         const double full_skin = L->skin;
@@ -2131,7 +2251,7 @@ static int box_apply(amm_ctx *ctx, bool &regrid, bool &waited) {
     // 4. nothing made for the old box survives: lists are rebuilt by their next evaluation, sorted copies gathered again, the
     // displacement triggers start from the positions of that rebuild, candidate sets start over
     for (auto &fo : ctx->forces) {
-        if (fo.type != 1) continue;
+        if (fo.type != 1 || fo.pair->free_space) continue;
         PairForce *pf = fo.pair;
         pf->a_sorted_for = nullptr;
         pf->a_sorted_epoch = pf->checked_epoch = pf->pre_epoch = -1;
@@ -2154,12 +2274,16 @@ int amm_set_box(amm_ctx *ctx, const double h_box[3]) {
             amm_set_error("amm_set_box: box edges must be positive (orthorhombic periodic box)");
             return 1;
         }
+    if (!ctx->has_box) {
+        amm_set_error("amm_set_box: the context has no periodic box");
+        return 1;
+    }
     if (ctx->world > 1 || ctx->pending.active) {
         amm_set_error("amm_set_box: a context that is one rank of several keeps the box it was created with");
         return 1;
     }
     for (auto &fo : ctx->forces)
-        if (fo.type == 1)
+        if (fo.type == 1 && !fo.pair->free_space)
             for (int k = 0; k < 3; ++k)
                 if (fo.pair->desc.rc > 0.5 * h_box[k] * (1 + 1e-12)) {
                     amm_set_error("pair cutoff exceeds half the box edge (minimum image needs rc <= L/2)");
@@ -2207,6 +2331,10 @@ int amm_mol_define(amm_ctx *ctx, const int32_t *h_ptr, const int32_t *h_atoms, i
 int amm_mol_scale(amm_ctx *ctx, double *d_x, double *d_x_saved, const double scale[3]) {
     if (!ctx || !d_x || !scale) {
         amm_set_error("amm_mol_scale: null argument");
+        return 1;
+    }
+    if (!ctx->has_box) {
+        amm_set_error("amm_mol_scale: the context has no periodic box");
         return 1;
     }
     return amm_mol_scale_impl(ctx, d_x, d_x_saved, scale);

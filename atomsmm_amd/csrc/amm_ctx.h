@@ -69,6 +69,7 @@ struct SmallGroup;    // group.hip: interaction-group force with one small set, 
 
 struct PairForce {
     amm_pair_desc desc;
+    bool free_space = false;       // AMM_FREE_SPACE: all pairs at the distance the positions give (free.hip) -- no grid, no list, no rebuild
     ClusterList *cl = nullptr;     // molecule rows (built on the first force-only evaluation of a qualifying force; list owners only)
     bool cluster_ok = false;       // the force has three-site molecules (their three pairs their only exclusions) and walks molecule rows
     // Hybrid list: molecule rows for the pairs of two such molecules + per-atom rows, kept by a hidden child force (`rest`, filtered to
@@ -386,6 +387,7 @@ struct amm_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     Box box;
+    bool has_box = true;           // false: amm_create without box edges -- only free-space pair forces and non-periodic terms
     int rank = 0, world = 1;
     std::vector<ForceObj> forces;
     double *d_x = nullptr, *d_v = nullptr;
@@ -484,6 +486,11 @@ int amm_small_group_energy_states(amm_ctx *ctx, PairForce *pf, const double *d_p
 int amm_small_group_free(SmallGroup *sg);
 int amm_small_group_failed(SmallGroup *sg);
 int amm_small_group_stats(SmallGroup *sg, int out[2]);
+// free.hip: all-pairs evaluation of a free-space pair force (AMM_FREE_SPACE)
+int amm_free_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double *d_force, int accumulate, double *d_energy);
+int amm_free_supported(const amm_pair_desc &d, std::string &why);     // 0 + reason: k_pair_free has no instantiation for it
+int amm_free_lanes_per_row(int n);
+#define AMM_FREE_MAX_ATOMS 32768   // an evaluation is O(n^2): about 10^9 distance tests at the limit
 // implemented in pair.hip / cells.hip / bonded.hip / integrate.hip
 int amm_pair_build_consts(const amm_pair_desc &d, PairConsts &pc);
 int amm_pair_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double *d_force, int accumulate,

@@ -60,12 +60,19 @@ int amm_pair_build_consts(const amm_pair_desc &d, PairConsts &pc) {
         pc.f6c = pow(1 + b, 3) / pow(b, 3);
         pc.f1c = (30 * (1 + b)) * (b * b * (1 + b) * (1 + b) * log(1 / b + 1) - b * b * b - 1.5 * b * b - b / 3 + 1.0 / 12);
     }
+    if ((d.flags & AMM_FREE_SPACE) && !(d.rc > 0.0)) {
+        // NoCutoff: every pair counts, and neither the switch nor a reaction-field term is applied
+        pc.rc2 = INFINITY;
+        pc.flags &= ~AMM_SWITCH;
+        pc.cmode = 0;
+        pc.krf = pc.crf = 0.0;
+    }
     pc.sw_den = 1.0;
     pc.inv_sw_dr = 0.0;
     if (d.family == AMM_DAMPED) pc.sw_den = pow(d.rc, pc.degree) - pow(d.rswitch, pc.degree);
     pc.inv_sw_den = 1.0 / pc.sw_den;
     pc.rswitch_d = pow(d.rswitch, pc.degree);
-    if ((d.family == AMM_NONBONDED || d.family == AMM_SOFTCORE || d.family == AMM_LJ_VIRIAL) && (d.flags & AMM_SWITCH)) pc.inv_sw_dr = 1.0 / (d.rc - d.rswitch);
+    if ((d.family == AMM_NONBONDED || d.family == AMM_SOFTCORE || d.family == AMM_LJ_VIRIAL) && (pc.flags & AMM_SWITCH)) pc.inv_sw_dr = 1.0 / (d.rc - d.rswitch);
     return 0;
 }
 
@@ -1773,6 +1780,15 @@ int amm_exchange_finish_impl(amm_ctx *ctx) {
 
 int amm_pair_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double *d_force, int accumulate,
                        double *d_energy, PairForce *guest, double *g_force, int g_accumulate, int exchange) {
+    if (pf->free_space) {          // all pairs, no list (free.hip); the one-pass forms and the exchange never pair with such a force
+        if (guest || exchange) {
+            amm_set_error("a free-space pair force is evaluated alone (no shared list, no exchange)");
+            return 1;
+        }
+        ctx->epi_request = nullptr;
+        ctx->epi_done = false;
+        return amm_free_eval_impl(ctx, pf, d_pos, d_force, accumulate, d_energy);
+    }
     hipStream_t st = ctx->stream;
     const int n = pf->n;
     const int nb = (n + 255) / 256;

@@ -277,16 +277,23 @@ class Engine:
             vecs = system._box
         except AttributeError:
             vecs = None
-        if vecs is None:
-            raise InputError('the HIP path needs a periodic orthorhombic box: call System.setDefaultPeriodicBoxVectors')
-        for i in range(3):
-            for j in range(3):
-                if i != j and abs(vecs[i][j]) > 1e-12:
-                    raise InputError('only orthorhombic periodic boxes are supported by the HIP path')
-        self.box = np.array([vecs[0][0], vecs[1][1], vecs[2][2]], dtype=np.float64)
-        # every long-range-correction constant is proportional to 1 / V: the quadratures are made for the box of creation and their
-        # results multiplied by V(creation) / V(now) where they are handed out (set_box)
-        self._box_ref = self.box.copy()
+        # the forces decide the mode: free space (NoCutoff / CutoffNonPeriodic everywhere, no periodic bonded force) or a periodic box
+        self.free_space = self._free_space_mode(system, vecs is not None)
+        if self.free_space:
+            # box vectors, if the System has any, are ignored by the forces: nothing below reads a placeholder
+            self.box = self._box_ref = None
+        else:
+            if vecs is None:
+                raise InputError('the HIP path needs a periodic orthorhombic box: call System.setDefaultPeriodicBoxVectors (CutoffPeriodic, '
+                                 'Ewald and PME sums need one; only NoCutoff and CutoffNonPeriodic run in free space)')
+            for i in range(3):
+                for j in range(3):
+                    if i != j and abs(vecs[i][j]) > 1e-12:
+                        raise InputError('only orthorhombic periodic boxes are supported by the HIP path')
+            self.box = np.array([vecs[0][0], vecs[1][1], vecs[2][2]], dtype=np.float64)
+            # every long-range-correction constant is proportional to 1 / V: the quadratures are made for the box of creation and their
+            # results multiplied by V(creation) / V(now) where they are handed out (set_box)
+            self._box_ref = self.box.copy()
         self._vscale = 1.0
         self.barostat = None
         self.rank, self.world = 0, 1
@@ -303,6 +310,9 @@ class Engine:
         # measure its host-side cost on a single GPU
         self._coll = self.world > 1 or (os.environ.get('AMM_FORCE_COLLECTIVES') == '1' and dist.is_available()
                                         and dist.is_initialized())
+        if self.free_space and self.world > 1:
+            raise InputError('a System in free space (NoCutoff / CutoffNonPeriodic) runs on a single rank: its pair forces walk all pairs '
+                             'and are not sliced')
         if self.world > 1 and any(k == mm.CustomIntegrator.ComputePerDof and t == 'x' and 'tanh(' in e
                                   for k, t, e in getattr(integrator, '_steps', [])):
             # (the ranks' fused paths -- state exchange, sliced epilogues -- carry plain moves only)
@@ -386,6 +396,31 @@ class Engine:
         if self.barostat is not None:
             self._init_barostat()
 
+    @staticmethod
+    def _free_space_mode(system, has_box):
+        """True: a free-space Context -- every NonbondedForce / CustomNonbondedForce is NoCutoff or CutoffNonPeriodic, no bonded
+        force uses periodic boundary conditions and the System holds a force (box vectors may be absent; present ones are ignored).
+        False: all nonbonded forces periodic, as ever.  A mixture is an InputError."""
+        def pair_forces(force):
+            if isinstance(force, (mm.NonbondedForce, mm.CustomNonbondedForce)):
+                return [force]
+            if isinstance(force, mm.CustomCVForce):
+                return [f for k in range(force.getNumCollectiveVariables()) for f in pair_forces(force.getCollectiveVariable(k))]
+            return []
+        forces = list(system.getForces())
+        pairs = [f for force in forces for f in pair_forces(force)]
+        free = [f for f in pairs if not f.usesPeriodicBoundaryConditions()]
+        if free and len(free) != len(pairs):
+            raise InputError('the System mixes periodic and non-periodic nonbonded methods: every NonbondedForce / CustomNonbondedForce '
+                             'must be NoCutoff or CutoffNonPeriodic (free space), or every one periodic')
+        if (pairs and not free) or (not pairs and (has_box or not forces)):
+            return False              # periodic, or nothing to decide by (no box and no forces: the error of old)
+        periodic = [f for f in forces if not pair_forces(f) and not isinstance(f, mm.MonteCarloBarostat) and f.usesPeriodicBoundaryConditions()]
+        if periodic:
+            raise InputError('the System mixes non-periodic nonbonded methods (or no box) with a %s that uses periodic boundary '
+                             'conditions' % periodic[0].__class__.__name__)
+        return True
+
     # ------------------------------------------------------------------------------- constant pressure
     def _init_barostat(self):
         """A MonteCarloBarostat in the System: what it cannot run with is refused here, when the Context is created."""
@@ -425,11 +460,18 @@ class Engine:
         self.barostat_log = []          # per attempt: (accepted, w, u2 or None, box edges afterwards) -- the last 1024
         self._x_saved = self.torch.zeros_like(self.x)
 
+    def _refuse_in_free_space(self, what):
+        if self.free_space:
+            raise NotImplementedError(what + ' is not available for a System in free space (NoCutoff / CutoffNonPeriodic): its pair '
+                                      'forces have no parameter-derivative or multi-state evaluation')
+
     def set_box(self, edges):
         """New box edges (nm) for the live context: Context.setPeriodicBoxVectors.  Positions are not touched.  Every 1 / V constant
         follows and forces and derivative caches become stale.  Compiled step programs stay: they hold no such constant (a program
         that reads an energy is walked by the host, which asks the entries for their constants as it goes).  The PME mesh and alpha
         stay as chosen at creation, as in OpenMM."""
+        if self.free_space:
+            raise InputError('a Context in free space (NoCutoff / CutoffNonPeriodic) has no periodic box to change')
         if self.world > 1:
             raise InputError('changing the box of a live Context runs on a single rank')
         edges = np.array(edges, dtype=np.float64).reshape(3)
@@ -524,6 +566,9 @@ class Engine:
         if isinstance(force, mm.CMMotionRemover):
             return
         if isinstance(force, mm.MonteCarloBarostat):
+            if self.free_space:
+                raise InputError('a MonteCarloBarostat needs a periodic box: a System in free space (NoCutoff / CutoffNonPeriodic) has '
+                                 'no volume to change')
             if self.barostat is not None:
                 raise InputError('a System holds one MonteCarloBarostat at most')
             self.barostat = force       # no energy of its own: it drives Engine.step (_barostat_attempt)
@@ -566,6 +611,10 @@ class Engine:
         self.entries.append(entry)
 
     def _pair_create(self, desc, q, sigma, eps, excl):
+        if self.free_space:
+            # all pairs at the distance the positions give (csrc/free.hip): no list to build, to share or to count
+            desc.flags |= B.FREE_SPACE
+            return self.ctx.pair_create(desc, q, sigma, eps, excl, skin=self.skin)
         pid = self.ctx.pair_create(desc, q, sigma, eps, excl, skin=self.skin)
         key = np.sort(np.sort(np.asarray(excl, dtype=np.int64).reshape(-1, 2), axis=1), axis=0).tobytes()
         # interaction-group forces keep a list of their own: it holds the (set 1, set 2) pairs only
@@ -632,9 +681,12 @@ class Engine:
 
     def _translate_nonbonded(self, nb, entry):
         method = nb.getNonbondedMethod()
-        if method not in (nb.CutoffPeriodic, nb.Ewald, nb.PME):
-            raise InputError('the HIP path evaluates periodic NonbondedForces only (CutoffPeriodic, Ewald, PME)')
-        rc = nb._cutoff
+        if method not in (nb.NoCutoff, nb.CutoffNonPeriodic, nb.CutoffPeriodic, nb.Ewald, nb.PME):
+            raise InputError('the HIP path evaluates NonbondedForces with NoCutoff, CutoffNonPeriodic, CutoffPeriodic, Ewald or PME')
+        periodic = not self.free_space
+        # NoCutoff: all non-excepted pairs, 4 eps ((sigma/r)^12 - (sigma/r)^6) + Kc qq / r -- no switch, no reaction field (rc = 0)
+        no_cutoff = method == nb.NoCutoff
+        rc = 0.0 if no_cutoff else nb._cutoff
         n = self.n
         base = np.array(nb._particles, dtype=np.float64).reshape(n, 3)
         names = []
@@ -653,10 +705,13 @@ class Engine:
         escales = np.zeros((len(enames), len(exc), 3))
         for name, idx, qs, ss, es in nb._exception_offsets:
             escales[enames.index(name), idx] = [qs, ss, es]
-        flags = B.SWITCH if nb._use_switch else 0
+        use_switch = nb._use_switch and not no_cutoff
+        flags = B.SWITCH if use_switch else 0
         alpha = krf = crf = 0.0
         ewald = method in (nb.Ewald, nb.PME)
-        if ewald:
+        if no_cutoff:
+            pass
+        elif ewald:
             alpha = nb._pme[0] if nb._pme[0] > 0 else math.sqrt(-math.log(2 * nb._ewald_tol)) / rc
             flags |= B.COULOMB_EWALD
         else:
@@ -664,7 +719,7 @@ class Engine:
             krf = (eps_rf - 1) / ((2 * eps_rf + 1) * rc ** 3)
             crf = 3 * eps_rf / ((2 * eps_rf + 1) * rc)
             flags |= B.COULOMB_RF
-        desc = B.pair_desc(B.NONBONDED, rc, rswitch=nb._switch if nb._use_switch else 0.0, alpha=alpha, flags=flags,
+        desc = B.pair_desc(B.NONBONDED, rc, rswitch=nb._switch if use_switch else 0.0, alpha=alpha, flags=flags,
                            krf=krf, crf=crf)
         eff = self._effective(base, scales, names, self.parameters)
         pid = self._pair_create(desc, eff[:, 0], eff[:, 1], eff[:, 2], exc)
@@ -688,9 +743,9 @@ class Engine:
             ep = self._effective(exc_base, escales, enames, parameters) if len(exc) else exc_base
             keep = (ep[:, 0] != 0.0) | (ep[:, 2] != 0.0) if len(exc) else np.zeros(0, bool)
             if keep.any():
-                terms.append((B.BOND_LJC, exc[keep], ep[keep], True, B.pair_desc(B.NONBONDED, rc)))
+                terms.append((B.BOND_LJC, exc[keep], ep[keep], periodic, B.pair_desc(B.NONBONDED, rc)))
             if ewald and len(exc):
-                terms.append((B.BOND_EWALD_EXCL, exc, (q[exc[:, 0]] * q[exc[:, 1]]).reshape(-1, 1), True,
+                terms.append((B.BOND_EWALD_EXCL, exc, (q[exc[:, 0]] * q[exc[:, 1]]).reshape(-1, 1), periodic,
                               B.pair_desc(B.NONBONDED, rc, alpha=alpha)))
             return terms
 
@@ -701,7 +756,7 @@ class Engine:
             # OpenMM evaluates the dispersion coefficient with the global parameters at their DEFAULT values and keeps
             # it when Context.setParameter changes them -- pinned by tests/test_systems.py:54 and :121 (sigma/epsilon
             # offsets at lambda_vdw = 0.5: the literals are met to 2e-7 kJ/mol only this way)
-            if not nb._dispersion:
+            if not nb._dispersion or self.free_space:       # (no volume: no dispersion correction in free space)
                 return 0.0
             p = self._effective(base, scales, names, defaults)
             return self._vscale * dispersion_correction(p[:, 1], p[:, 2], self._box_ref, rc, nb._switch if nb._use_switch else None)
@@ -773,7 +828,15 @@ class Engine:
         d = dict(self._descriptor_of(force))
         if d['family'] == 'ljc':
             raise InputError('the LJC exception expression belongs in a CustomBondForce')
-        if force.getNonbondedMethod() != force.CutoffPeriodic:
+        if self.free_space:
+            if force.getNonbondedMethod() == force.NoCutoff:
+                raise InputError('only a NonbondedForce runs without a cutoff (NoCutoff): the near and damped-smoothed energy texts of '
+                                 'a CustomNonbondedForce are not defined beyond their cutoff -- use CutoffNonPeriodic')
+            if d['family'] in ('softcore', 'lj-virial') or force.getNumInteractionGroups() > 0 or d['family'] == 'lj' \
+                    or d.get('noshift') or d.get('scale_name') or d.get('scale_text'):
+                raise NotImplementedError('softcore forces, interaction groups, lj-virial and the alchemical pair forces are not '
+                                          'evaluated under a non-periodic nonbonded method (free space)')
+        elif force.getNonbondedMethod() != force.CutoffPeriodic:
             raise InputError('the HIP path evaluates CutoffPeriodic CustomNonbondedForces only')
         if d['family'] == 'softcore':
             return self._translate_softcore(force, entry, d)
@@ -827,6 +890,9 @@ class Engine:
         n = self.n
         if getattr(force, '_offset_parameters', []):
             raise NotImplementedError('alchemical pair force with parameter offsets')
+        if self.free_space:
+            raise NotImplementedError('alchemical pair forces (interaction groups, coupling factors) are not evaluated under a '
+                                      'non-periodic nonbonded method (free space)')
         if force.getNonbondedMethod() != force.CutoffPeriodic:
             raise InputError('the HIP path evaluates CutoffPeriodic CustomNonbondedForces only')
         p = np.array(force._particles, dtype=np.float64).reshape(n, -1)
@@ -1348,7 +1414,7 @@ class Engine:
                 kinetic = self._kinetic_energy(expression, out)
         pos = self.x.cpu().numpy() if want_pos else None
         vel = self.v.cpu().numpy() if want_vel else None
-        box = [(self.box[0], 0, 0), (0, self.box[1], 0), (0, 0, self.box[2])]
+        box = None if self.box is None else [(self.box[0], 0, 0), (0, self.box[1], 0), (0, 0, self.box[2])]
         return mm.State(energy, kinetic, forces, pos, vel, box, self.time)
 
     def _kinetic_energy(self, expression, out):
@@ -1459,11 +1525,13 @@ class Engine:
 
     # ------------------------------------------------------------------------------- energy minimisation
     def _constraint_errors(self, pairs, dist):
-        """Largest relative error |r - d| / d over the constrained pairs at the current positions (minimum image; on the device)."""
+        """Largest relative error |r - d| / d over the constrained pairs at the current positions (minimum image in a periodic box,
+        plain distances in free space; on the device)."""
         torch = self.torch
-        box = torch.as_tensor(self.box, device=self.x.device)
         d = self.x[pairs[:, 0]] - self.x[pairs[:, 1]]
-        d = d - box * torch.round(d / box)
+        if self.box is not None:
+            box = torch.as_tensor(self.box, device=self.x.device)
+            d = d - box * torch.round(d / box)
         return float((torch.abs(torch.linalg.norm(d, dim=1) - dist) / dist).max().item())
 
     def minimize(self, tolerance=10.0, max_iterations=0, reporter=None, memory=8, max_step=0.1):
@@ -2443,6 +2511,7 @@ class Engine:
         * parameter offsets of a NonbondedForce (SolvationSystem's `lambda_coul`, systems.py:289-308): the energy is a
           quadratic form of the charges, so the central difference over a whole unit of lambda is exact; offsets that act
           on sigma / epsilon (`use_softcore=False`, systems.py:309-312) take a small central step instead (O(h^2))."""
+        self._refuse_in_free_space('deriv(energy, %s)' % name)
         if name not in self.parameters:
             raise mm.OpenMMException('deriv(energy, %s): no such Context parameter' % name)
         torch = self.torch
@@ -2499,6 +2568,7 @@ class Engine:
 
         Leaves no trace for the first two kinds: parameters, lambda bindings, valid force buffers and compiled programs stay as they
         are.  The other two change parameters and restore them as energy_derivative does."""
+        self._refuse_in_free_space('energies_at_states')
         names = list(names)
         rows = np.asarray(rows, dtype=np.float64).reshape(-1, len(names))
         K = len(rows)

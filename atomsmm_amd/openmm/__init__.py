@@ -912,6 +912,8 @@ class State:
         return self._vecs(self._v, nm / _unit.picosecond, asNumpy)
 
     def getPeriodicBoxVectors(self):
+        if self._box is None:          # a Context in free space (NoCutoff / CutoffNonPeriodic)
+            return None
         return [Quantity(Vec3(*v), nm) for v in self._box]
 
     def getTime(self):

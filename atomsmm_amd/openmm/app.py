@@ -25,6 +25,7 @@ from . import (CMMotionRemover, Context, HarmonicAngleForce, HarmonicBondForce, 
                PeriodicTorsionForce, Platform, System, Vec3)
 from .. import unit as _unit
 from ..unit import Quantity, md_value
+from ..utils import InputError
 
 # nonbonded methods and constraint choices, as exposed by openmm.app
 NoCutoff = NonbondedForce.NoCutoff
@@ -573,7 +574,12 @@ class StateDataReporter:
         pe = state.getPotentialEnergy().value_in_unit(_unit.kilojoules_per_mole)
         ke = state.getKineticEnergy().value_in_unit(_unit.kilojoules_per_mole)
         box = state.getPeriodicBoxVectors()
-        volume = (box[0][0] * box[1][1] * box[2][2]).value_in_unit(_unit.nanometers ** 3)
+        if box is None:
+            if any(name in self._columns for name in ('Box Volume (nm^3)', 'Density (g/mL)')):
+                raise InputError('StateDataReporter: volume and density need a periodic box; this Context runs in free space')
+            volume = float('nan')
+        else:
+            volume = (box[0][0] * box[1][1] * box[2][2]).value_in_unit(_unit.nanometers ** 3)
         now, t_ps = _time.time(), state.getTime().value_in_unit(_unit.picoseconds)
         elapsed = now - self._started[0]
         values = {'Step': simulation.currentStep, 'Time (ps)': t_ps, 'Potential Energy (kJ/mole)': pe,

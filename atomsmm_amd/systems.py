@@ -276,6 +276,10 @@ class ComputingSystem(_AtomsMM_System):
 
     def __init__(self, system):
         super().__init__(system, copyForces=False)
+        if any(isinstance(force, (openmm.NonbondedForce, openmm.CustomNonbondedForce)) and not force.usesPeriodicBoundaryConditions()
+               for force in system.getForces()):
+            raise utils.InputError('ComputingSystem / PressureComputer need a periodic box: a System in free space (NoCutoff / '
+                             'CutoffNonPeriodic) has no volume, hence no pressure')
         # force groups: 0 dispersion virial, 1 bond-stretching virial, 2 Coulomb (whose virial is its energy)
         group = dict(dispersion=0, bonded=1, coulomb=2)
         self._dispersion, self._bonded, self._coulomb = (1 << group[k] for k in ('dispersion', 'bonded', 'coulomb'))

@@ -77,8 +77,11 @@ def system_from_arrays(c, nonbondedMethod='CutoffPeriodic', cutoff=1.0, switch=N
     system = openmm.System()
     for m in c['mass']:
         system.addParticle(float(m))
-    L = c['box']
-    system.setDefaultPeriodicBoxVectors((float(L[0]), 0, 0), (0, float(L[1]), 0), (0, 0, float(L[2])))
+    L = c.get('box')
+    if L is not None:         # (a free-space case -- nonbondedMethod 'NoCutoff' / 'CutoffNonPeriodic' -- may have none)
+        system.setDefaultPeriodicBoxVectors((float(L[0]), 0, 0), (0, float(L[1]), 0), (0, 0, float(L[2])))
+    elif nonbondedMethod not in ('NoCutoff', 'CutoffNonPeriodic'):
+        raise ValueError("a case without 'box' needs nonbondedMethod 'NoCutoff' or 'CutoffNonPeriodic'")
     mass = np.asarray(c['mass'])
     is_h = mass < 1.5
     constrained_bonds, dropped_angles = set(), set()

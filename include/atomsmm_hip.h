@@ -61,10 +61,20 @@ enum {
     AMM_GROUP_LJ = 32,      /* interaction group for Lennard-Jones-only forces: the charge array carries the set
                                of each atom (1, 2, 0; Kc = 1), a pair counts iff the codes multiply to 2, no
                                Coulomb term (systems.py:739-772)                                         */
-    AMM_GROUP_Q = 64        /* interaction group for Coulomb-only forces (the force-switched solute-solvent
+    AMM_GROUP_Q = 64,       /* interaction group for Coulomb-only forces (the force-switched solute-solvent
                                electrostatics of Coulomb scaling, systems.py:696-708, 848-856): the sigma array
                                carries TWICE the set code of each atom (2, 4, 0): the mixed sigma (sigma_i +
                                sigma_j)/2 = 3 selects a (set 1, set 2) pair; epsilon is ignored         */
+    AMM_FREE_SPACE = 128    /* nonbondedMethod NoCutoff / CutoffNonPeriodic (forces.py:278-283; systems.py:371-372,
+                               850-851): every pair that is not excluded, at the distance the positions give -- no box,
+                               no minimum image, no neighbour list (csrc/free.hip walks all n^2 pairs; at most 32768
+                               atoms).  rc > 0: pairs with r >= rc skipped (CutoffNonPeriodic); rc <= 0: no cutoff
+                               (NONBONDED only: no switch and no reaction-field term are applied).  Families NEAR_*,
+                               DAMPED and NONBONDED with plain or reaction-field Coulomb; no interaction groups.
+                               amm_pair_set_params and amm_pair_set_scale work on such a force; amm_pair_share_list,
+                               amm_pair_set_lambda[_dev], amm_pair_energy_derivative, amm_pair_energy_states and
+                               amm_pair_count_within return non-zero; amm_pair_get_stats reports its evaluations, zero
+                               builds and list_kind 4.  Single rank only.                                */
 };
 
 typedef struct {
@@ -127,7 +137,11 @@ int amm_abi_version(void);
 const char *amm_last_error(void);
 
 /* Context.__init__ / Context.setPeriodicBoxVectors  (utils.py:153-155 builds the Simulation/Context).
- * stream: hipStream_t as void* (NULL = default stream). */
+ * stream: hipStream_t as void* (NULL = default stream).
+ * h_box = NULL: a context without a periodic box (a System without box vectors: a solute in vacuum, a droplet).  It holds
+ * free-space pair forces (AMM_FREE_SPACE) and bond-list terms with periodic = 0; amm_pair_create without that flag, bond-list
+ * terms with periodic != 0, amm_pme_create, amm_set_box and amm_mol_scale return non-zero with "the context has no periodic
+ * box" on it.  A context created with a box accepts free-space forces too. */
 int amm_create(int32_t n_atoms, const double h_box[3], int32_t device, void *stream, amm_ctx **out);
 int amm_destroy(amm_ctx *ctx);
 int amm_set_stream(amm_ctx *ctx, void *stream);
@@ -431,7 +445,8 @@ typedef struct {
                                max_neighbors are molecule partners per row, lanes_per_atom is lanes per row), 2 hybrid: one per
                                three-site molecule for the pairs of two molecules + one per atom, filtered to the pairs with an
                                atom outside the molecules, for the rest (an ion, a solute, a chain next to the waters), 3 none:
-                               an interaction-group force whose smaller set has <= 128 atoms is evaluated without a list */
+                               an interaction-group force whose smaller set has <= 128 atoms is evaluated without a list,
+                               4 none: a free-space force (AMM_FREE_SPACE) walks all pairs; lanes_per_atom is its lanes per row */
     int64_t n_outer_builds; /* cell-based builds of the outer list (n_builds counts prunes of the inner list) */
     int64_t n_outer_pairs;
     double rlist_outer;
