@@ -19,18 +19,29 @@ static thread_local std::string g_error;
 void amm_set_error(const std::string &msg) { g_error = msg; }
 
 static PairForce *get_pair(amm_ctx *ctx, int id) {
-    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != 1) {
+    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_PAIR) {
         amm_set_error("invalid pair force id");
         return nullptr;
     }
     return ctx->forces[id].pair;
 }
 static BondedSet *get_bonded(amm_ctx *ctx, int id) {
-    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != 2) {
+    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_BONDED) {
         amm_set_error("invalid bonded force id");
         return nullptr;
     }
     return ctx->forces[id].bonded;
+}
+// one force of any type (also the members of a group: run_ops.hip)
+int amm_force_eval_dispatch(amm_ctx *ctx, int force_id, const double *d_pos, double *d_force, int accumulate, double *d_energy) {
+    ForceObj &f = ctx->forces[force_id];
+    if (f.type == AMM_FORCE_RELEASED) {
+        amm_set_error("evaluation of a released force id");
+        return 1;
+    }
+    if (f.type == AMM_FORCE_PAIR) return amm_pair_eval_impl(ctx, f.pair, d_pos, d_force, accumulate, d_energy);
+    if (f.type == AMM_FORCE_PME) return amm_pme_eval_impl(ctx, f.pme, d_pos, d_force, accumulate, d_energy);
+    return amm_bonded_eval_impl(ctx, f.bonded, d_pos, d_force, accumulate, d_energy);
 }
 
 template <typename T>
@@ -316,7 +327,7 @@ int amm_pair_create(amm_ctx *ctx, const amm_pair_desc *desc, const double *h_q, 
             return 1;
         }
         ForceObj fo;
-        fo.type = 1;
+        fo.type = AMM_FORCE_PAIR;
         fo.pair = pf;
         ctx->forces.push_back(fo);
         *force_id = (int)ctx->forces.size() - 1;
@@ -393,7 +404,7 @@ int amm_pair_create(amm_ctx *ctx, const amm_pair_desc *desc, const double *h_q, 
     AMM_HIP(hipMalloc(&pf->d_counters, sizeof(unsigned long long) * 8));
     AMM_HIP(hipMemset(pf->d_counters, 0, sizeof(unsigned long long) * 8));
     ForceObj fo;
-    fo.type = 1;
+    fo.type = AMM_FORCE_PAIR;
     fo.pair = pf;
     ctx->forces.push_back(fo);
     *force_id = (int)ctx->forces.size() - 1;
@@ -462,7 +473,7 @@ int amm_pair_set_scale(amm_ctx *ctx, int32_t force_id, double scale) {
     // the pairings cached for the one-pass evaluations depend on the sign (host sign == 1): decide them again
     pf->dual_ok = pf->fuse_ok = -1;
     for (auto &fo : ctx->forces)
-        if (fo.type == 1 && fo.pair->host == pf) fo.pair->dual_ok = fo.pair->fuse_ok = -1;
+        if (fo.type == AMM_FORCE_PAIR && fo.pair->host == pf) fo.pair->dual_ok = fo.pair->fuse_ok = -1;
     // (a hybrid list's per-atom part is a force of its own with its own constants: same scale)
     if (pf->rest) return amm_pair_set_scale(ctx, pf->rest->id, scale);
     return 0;
@@ -700,7 +711,7 @@ int amm_pair_set_params(amm_ctx *ctx, int32_t force_id, const double *h_q, const
         pf->h_cls = cls;
         pf->sites_match = -1;
         for (auto &fo : ctx->forces)
-            if (fo.type == 1 && fo.pair->host == pf) fo.pair->sites_match = -1;
+            if (fo.type == AMM_FORCE_PAIR && fo.pair->host == pf) fo.pair->sites_match = -1;
     }
     // the sorted copies of the parameters that a launch wrote ahead of time (epilogues: pair.hip, cluster.hip) were made with the old
     // ones: no later evaluation may take them for current, whichever force of the list (this one or a guest) they belong to
@@ -712,7 +723,7 @@ int amm_pair_set_params(amm_ctx *ctx, int32_t force_id, const double *h_q, const
     // dual evaluation needs bitwise equal parameters on guest and host: re-check after any change
     pf->dual_ok = pf->fuse_ok = -1;
     for (auto &fo : ctx->forces)
-        if (fo.type == 1 && fo.pair->host == pf) fo.pair->dual_ok = fo.pair->fuse_ok = -1;
+        if (fo.type == AMM_FORCE_PAIR && fo.pair->host == pf) fo.pair->dual_ok = fo.pair->fuse_ok = -1;
     if (pf->rest) return amm_pair_set_params(ctx, pf->rest->id, h_q, h_sigma, h_eps);
     return 0;
 }
@@ -721,7 +732,7 @@ int amm_bonded_create(amm_ctx *ctx, int32_t *force_id) {
     BondedSet *bs = new BondedSet();
     std::memset(&bs->near_pc, 0, sizeof(bs->near_pc));
     ForceObj fo;
-    fo.type = 2;
+    fo.type = AMM_FORCE_BONDED;
     fo.bonded = bs;
     ctx->forces.push_back(fo);
     *force_id = (int)ctx->forces.size() - 1;
@@ -815,20 +826,8 @@ int amm_bonded_release(amm_ctx *ctx, int32_t force_id) {
     amm_bonded_free(bs);
     delete bs;
     ctx->forces[force_id].bonded = nullptr;
-    ctx->forces[force_id].type = 0;
+    ctx->forces[force_id].type = AMM_FORCE_RELEASED;
     return 0;
-}
-
-static int force_eval_dispatch(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *d_force, int32_t accumulate,
-                               double *d_energy) {
-    ForceObj &f = ctx->forces[force_id];
-    if (f.type == 0) {
-        amm_set_error("evaluation of a released force id");
-        return 1;
-    }
-    if (f.type == 1) return amm_pair_eval_impl(ctx, f.pair, d_pos, d_force, accumulate, d_energy);
-    if (f.type == 3) return amm_pme_eval_impl(ctx, f.pme, d_pos, d_force, accumulate, d_energy);
-    return amm_bonded_eval_impl(ctx, f.bonded, d_pos, d_force, accumulate, d_energy);
 }
 
 int amm_pme_create(amm_ctx *ctx, double alpha, int32_t nx, int32_t ny, int32_t nz, double Kc, const double *h_q,
@@ -846,7 +845,7 @@ int amm_pme_create(amm_ctx *ctx, double alpha, int32_t nx, int32_t ny, int32_t n
     PmeForce *pm = nullptr;
     if (amm_pme_create_impl(ctx, alpha, K, Kc, h_q, &pm)) return 1;
     ForceObj fo;
-    fo.type = 3;
+    fo.type = AMM_FORCE_PME;
     fo.pme = pm;
     ctx->forces.push_back(fo);
     *force_id = (int32_t)ctx->forces.size() - 1;
@@ -854,7 +853,7 @@ int amm_pme_create(amm_ctx *ctx, double alpha, int32_t nx, int32_t ny, int32_t n
 }
 
 static PmeForce *get_pme(amm_ctx *ctx, int id) {
-    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != 3) {
+    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_PME) {
         amm_set_error("not a PME force id");
         return nullptr;
     }
@@ -880,7 +879,7 @@ int amm_force_eval(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *
         return 1;
     }
     if (!(ctx->opt_positions_private && d_pos == ctx->d_x)) ctx->pos_epoch++;     // a caller's positions may have changed in any way since the last call
-    return force_eval_dispatch(ctx, force_id, d_pos, d_force, accumulate, d_energy);
+    return amm_force_eval_dispatch(ctx, force_id, d_pos, d_force, accumulate, d_energy);
 }
 
 int amm_positions_changed(amm_ctx *ctx) {
@@ -1153,14 +1152,6 @@ int amm_group_define(amm_ctx *ctx, int32_t group, int32_t slot, const int32_t *f
     return 0;
 }
 
-// without a communicator of its own the library cannot complete an exchanged EVAL inside a program: such an EVAL must
-// be the LAST op of its amm_run_ops call; the host then gathers the chunks and calls amm_exchange_finish
-static int exchange_left_to_host(amm_ctx *ctx, bool last_op) {
-    if (!ctx->pending.active || last_op) return 0;
-    amm_set_error("amm_run_ops: without a communicator (amm_comm_init) an exchanged EVAL must be the last op of the call");
-    return 1;
-}
-
 int amm_group_set_exchange(amm_ctx *ctx, int32_t group, int32_t mode) {
     if (!ctx || group < 0 || group >= AMM_MAX_GROUPS || (mode != AMM_EXCHANGE_REDUCE && mode != AMM_EXCHANGE_GATHER)) {
         amm_set_error("amm_group_set_exchange: bad group or mode");
@@ -1193,786 +1184,21 @@ int amm_run_ops(amm_ctx *ctx, const amm_op *ops, int32_t n_ops, int32_t repeat) 
 // cursor != nullptr: resumable.  Starts at op *cursor of the unrolled program (repetition * n_ops + index) and runs to its end --
 // or to the first exchanged evaluation whose exchange is the HOST's to make (no communicator of the library's own): then it returns 0
 // with *cursor at the op to go on from and the exchange pending (the host all-gathers the chunks, calls amm_exchange_finish and
-// calls again).  *cursor == repeat * n_ops on return: the program is through.
+// calls again).  *cursor == repeat * n_ops on return: the program is through.  (The scheduler itself: run_ops.hip.)
 int amm_run_ops_from(amm_ctx *ctx, const amm_op *ops, int32_t n_ops, int32_t repeat, int64_t *cursor) {
-    if (!ctx->d_x || !ctx->d_v || !ctx->d_mass) {
-        amm_set_error("amm_run_ops: state not bound (amm_bind_state)");
+    if (!ctx) {
+        amm_set_error("amm_run_ops: null context");
         return 1;
     }
-    const long total_ops = (long)repeat * n_ops;
-    if (cursor && (*cursor < 0 || *cursor > total_ops)) {
-        amm_set_error("amm_run_ops_from: cursor out of range");
-        return 1;
-    }
-    // (*cursor == total_ops: nothing left to run -- the call winds the program up: force buffers that hold this rank's rows only)
-    if (ctx->pending.active) {
-        amm_set_error("amm_run_ops: an exchanged evaluation still waits for amm_exchange_finish");
-        return 1;
-    }
-    // user-visible buffers; the fused inner iteration ping-pongs between them and library-owned partners
-    double *const user_x = ctx->d_x, *const user_v = ctx->d_v;
-    if (!ctx->opt_positions_private) ctx->pos_epoch++;                 // the caller may have written the bound position buffer
-    int f0_slot = -1;
-    double *user_f0 = nullptr;
-    bool swapped = false;
-    // Every exit -- also the early `return 1` of a failed launch, an unbound buffer or a failed collective -- must leave the
-    // context bound to the CALLER's buffers: the fused inner iteration ping-pongs d_x / d_v / the group-0 slot onto the
-    // library's alt_* buffers.  On the error path the state held in the alt buffers is copied back on a best-effort basis.
-    struct RestoreBindings {
-        amm_ctx *ctx;
-        double *ux, *uv;
-        double *&uf0;
-        int &slot;
-        bool &swapped;
-        bool done = false;
-        void restore(bool copy_back) {
-            if (done) return;
-            done = true;
-            if (slot < 0) return;
-            if (swapped && copy_back) {
-                const size_t bytes = sizeof(double) * 3 * (size_t)ctx->n;
-                (void)hipMemcpyAsync(ux, ctx->d_x, bytes, hipMemcpyDeviceToDevice, ctx->stream);
-                (void)hipMemcpyAsync(uv, ctx->d_v, bytes, hipMemcpyDeviceToDevice, ctx->stream);
-                (void)hipMemcpyAsync(uf0, ctx->slots[slot], bytes, hipMemcpyDeviceToDevice, ctx->stream);
-            }
-            ctx->d_x = ux;
-            ctx->d_v = uv;
-            ctx->slots[slot] = uf0;
-            ctx->slots[AMM_SLOT_X] = ux;
-            ctx->slots[AMM_SLOT_V] = uv;
-        }
-        ~RestoreBindings() { restore(true); }
-    } bindings{ctx, user_x, user_v, user_f0, f0_slot, swapped};
-    // kicks that close one repetition of the program ride on the first inner-loop launch of the next (as further
-    // "preceding kicks"): same order, same arithmetic, two launches less per outer step
-    std::vector<amm_op> deferred;
-    auto flush_deferred = [&]() -> int {
-        for (const amm_op &ko : deferred) {
-            double *fa = (ko.a >= 0 && ko.a < AMM_MAX_SLOTS) ? ctx->slots[ko.a] : nullptr;
-            double *fb = (ko.b >= 0 && ko.b < AMM_MAX_SLOTS) ? ctx->slots[ko.b] : nullptr;
-            if (!fa || (ko.b >= 0 && !fb)) {
-                amm_set_error("amm_run_ops: KICK buffer not bound");
-                return 1;
-            }
-            if (!ctx->own_only.empty()) {
-                const auto has = [&](const double *b) { return b && std::find(ctx->own_only.begin(), ctx->own_only.end(), b) != ctx->own_only.end(); };
-                if (has(fa) || has(fb)) {
-                    amm_set_error("amm_run_ops: a deferred kick reads a force buffer that holds this rank's rows only (state exchange)");
-                    return 1;
-                }
-            }
-            if (amm_kick_impl(ctx, ctx->d_v, fa, fb, ko.c, ctx->d_mass, ko.coef)) return 1;
-        }
-        deferred.clear();
+    if (n_ops <= 0 || repeat <= 0) {        // an empty program: through before it starts
+        if (cursor) *cursor = 0;
         return 0;
-    };
-    const bool no_defer = ctx->opt_no_defer != 0;      // tuning option (A/B)
-    // ---- epilogue plans (cluster.hip: cepi_rows) ----
-    // The ops that follow a force-only pair evaluation at op index `after` -- [KICK ...] ; n x { KICK(f0) ; MOVE ; EVAL(g0) ; KICK(f0) }
-    // with g0 = one bond-list set of three-site molecules -- as a plan the evaluation's launch can carry.  When the program ENDS
-    // with the kicks (the closing half kicks of an outer step) and another repetition follows, the plan goes on with the kicks and
-    // the inner loop that open that repetition (`wraps`; what the deferred kicks do for the stand-alone inner-loop launch).
-    // q_resume: the first op not covered (in the next repetition when wraps).
-    auto slot_of = [&](int a) -> double * { return (a >= 0 && a < AMM_MAX_SLOTS) ? ctx->slots[a] : nullptr; };
-    // Buffers that hold this rank's rows only (state exchange, cluster.hip).  complete(buf): before an op reads `buf` for ALL atoms --
-    // a bond-list group's buffer is evaluated again (every rank can: positions are whole after every exchange; the same numbers the
-    // owners hold), anything else is an error: a pair group must be evaluated again before its forces are read.
-    auto forget_own_only = [&](const double *buf) {
-        auto it = std::find(ctx->own_only.begin(), ctx->own_only.end(), buf);
-        if (it != ctx->own_only.end()) ctx->own_only.erase(it);
-    };
-    auto complete = [&](const double *buf) -> int {
-        if (!buf || ctx->own_only.empty() || std::find(ctx->own_only.begin(), ctx->own_only.end(), buf) == ctx->own_only.end()) return 0;
-        for (int gi = 0; gi < AMM_MAX_GROUPS; ++gi) {
-            GroupDef &g = ctx->groups[gi];
-            if (g.slot < 0 || ctx->slots[g.slot] != buf || g.forces.empty()) continue;
-            bool bonded_only = true;
-            for (int fid : g.forces) bonded_only = bonded_only && ctx->forces[fid].type == 2 && !ctx->forces[fid].bonded->sliced;
-            if (!bonded_only) break;
-            bool first = true;
-            for (int fid : g.forces) {
-                if (amm_bonded_eval_impl(ctx, ctx->forces[fid].bonded, ctx->d_x, ctx->slots[g.slot], first ? 0 : 1, nullptr)) return 1;
-                first = false;
-            }
-            forget_own_only(buf);
-            return 0;
-        }
-        amm_set_error("amm_run_ops: an op reads a force buffer that holds this rank's rows only (state exchange) before its group was evaluated again");
+    }
+    if (!ops) {
+        amm_set_error("amm_run_ops: null ops");
         return 1;
-    };
-    auto plan_epilogue = [&](int after, int rep, EpiPlan &P, int &q_resume, bool &wraps) -> bool {
-        // (regulated mode: the epilogue's moves are plain ones -- not planned, the ops run on the paths that know the mode)
-        if (!ctx->fuse_inner || !ctx->opt_fuse_epilogue || ctx->iso.on || ctx->reg.on || swapped || f0_slot >= 0) return false;
-        std::vector<amm_op> kicks;
-        int j = after;
-        wraps = false;
-        while (true) {
-            while (j < n_ops && ops[j].op == AMM_OP_KICK && (int)kicks.size() <= AMM_MAX_PRE) kicks.push_back(ops[j++]);
-            if (j == n_ops && !wraps && rep + 1 < repeat && !no_defer && !kicks.empty() && ops[0].op == AMM_OP_KICK) {
-                wraps = true;
-                j = 0;
-                continue;
-            }
-            break;
-        }
-        // the last kick of the run opens the first inner iteration
-        if (kicks.empty() || j < 1 || j + 2 >= n_ops) return false;
-        const int start = j - 1;
-        const amm_op &k1 = ops[start];
-        if (!(k1.op == AMM_OP_KICK && k1.b < 0 && ops[start + 1].op == AMM_OP_MOVE && ops[start + 2].op == AMM_OP_EVAL &&
-              ops[start + 3 < n_ops ? start + 3 : start].op == AMM_OP_KICK && start + 3 < n_ops)) return false;
-        const int g0 = ops[start + 2].a;
-        if (g0 < 0 || g0 >= AMM_MAX_GROUPS) return false;
-        GroupDef &g = ctx->groups[g0];
-        if (!(g.slot == k1.a && g.forces.size() == 1 && ctx->forces[g.forces[0]].type == 2 && !g.exchange)) return false;
-        BondedSet *bs = ctx->forces[g.forces[0]].bonded;
-        if (!bs->mol3_ok || bs->sliced) return false;
-        auto is_iter = [&](int q) {
-            return q + 3 < n_ops && ops[q].op == AMM_OP_KICK && ops[q].b < 0 && ops[q].a == k1.a && ops[q].coef == k1.coef &&
-                   ops[q + 1].op == AMM_OP_MOVE && ops[q + 1].coef == ops[start + 1].coef && ops[q + 2].op == AMM_OP_EVAL &&
-                   ops[q + 2].a == g0 && ops[q + 3].op == AMM_OP_KICK && ops[q + 3].b < 0 && ops[q + 3].a == k1.a &&
-                   ops[q + 3].coef == ops[start + 3].coef;
-        };
-        int niter = 0, q = start;
-        while (is_iter(q)) { ++niter; q += 4; }
-        const int npre = (int)kicks.size() - 1;
-        if (niter < 1 || npre > AMM_MAX_PRE) return false;
-        P = EpiPlan();
-        P.bs = bs;
-        P.f0 = ctx->slots[g.slot];
-        P.npre = npre;
-        P.niter = niter;
-        for (int p = 0; p < npre; ++p) {
-            P.pre_a[p] = slot_of(kicks[p].a);
-            P.pre_b[p] = kicks[p].b >= 0 ? slot_of(kicks[p].b) : nullptr;
-            if (!P.pre_a[p] || (kicks[p].b >= 0 && !P.pre_b[p])) return false;
-            P.pre_coef[p] = kicks[p].coef;
-            P.pre_plus[p] = kicks[p].c;
-        }
-        P.c1 = k1.coef;
-        P.d = ops[start + 1].coef;
-        P.c2 = ops[start + 3].coef;
-        if (!P.f0) return false;
-        // the force whose sorted copies the next pair evaluation reads: the next EVAL in program order (the list owner when it is
-        // one of a pair that is evaluated in one pass)
-        P.next = nullptr;
-        for (int t = q, seen = 0; seen < n_ops; ++seen, ++t) {
-            if (t >= n_ops) {
-                if (rep + (wraps ? 2 : 1) >= repeat) break;
-                t = 0;
-            }
-            if (ops[t].op != AMM_OP_EVAL) continue;
-            const int ga = ops[t].a;
-            if (ga < 0 || ga >= AMM_MAX_GROUPS || ctx->groups[ga].forces.empty() || ctx->forces[ctx->groups[ga].forces[0]].type != 1) break;
-            PairForce *pa = ctx->forces[ctx->groups[ga].forces[0]].pair;
-            if (pa->free_space) break;          // (a free-space force reads no sorted copies)
-            P.next = pa;
-            if (t + 1 < n_ops && ops[t + 1].op == AMM_OP_EVAL && ops[t + 1].a >= 0 && ops[t + 1].a < AMM_MAX_GROUPS &&
-                !ctx->groups[ops[t + 1].a].forces.empty() && ctx->forces[ctx->groups[ops[t + 1].a].forces[0]].type == 1) {
-                PairForce *pb = ctx->forces[ctx->groups[ops[t + 1].a].forces[0]].pair;
-                if (pa->host == pb) P.next = pb;
-                else if (pb->host == pa) P.next = pa;
-            }
-            break;
-        }
-        q_resume = q;
-        return true;
-    };
-    // ... and for per-atom rows (pair.hip: AtomEpiArgs): `[KICK ...] [; MOVE]` behind the EVAL of a group that is one pair force -- a
-    // velocity-Verlet step's closing half kick and, across the end of the repetition, the opening half kick + move of the next
-    auto plan_atoms = [&](int after, int rep, EpiPlan &P, int &q_resume, bool &wraps) -> bool {
-        if (!ctx->fuse_inner || !ctx->opt_fuse_epilogue || ctx->iso.on || ctx->reg.on || ctx->world != 1 || swapped || f0_slot >= 0) return false;
-        std::vector<amm_op> kicks;
-        int j = after;
-        wraps = false;
-        while (true) {
-            while (j < n_ops && ops[j].op == AMM_OP_KICK && (int)kicks.size() < 4) kicks.push_back(ops[j++]);
-            if (j == n_ops && !wraps && rep + 1 < repeat && !no_defer && !kicks.empty() && ops[0].op == AMM_OP_KICK) {
-                wraps = true;
-                j = 0;
-                continue;
-            }
-            break;
-        }
-        if (kicks.empty() || (j < n_ops && ops[j].op == AMM_OP_KICK)) return false;        // (a fifth kick: left to the plain path)
-        const bool moves = j < n_ops && ops[j].op == AMM_OP_MOVE;
-        if (!moves && !wraps && j == n_ops) return false;                                  // (closing kicks of the call's last step: as before)
-        P = EpiPlan();
-        P.kind = 1;
-        P.npre = (int)kicks.size();
-        for (int p = 0; p < P.npre; ++p) {
-            P.pre_a[p] = slot_of(kicks[p].a);
-            P.pre_b[p] = kicks[p].b >= 0 ? slot_of(kicks[p].b) : nullptr;
-            if (!P.pre_a[p] || (kicks[p].b >= 0 && !P.pre_b[p])) return false;
-            P.pre_coef[p] = kicks[p].coef;
-            P.pre_plus[p] = kicks[p].c;
-        }
-        P.with_move = moves ? 1 : 0;
-        P.dcoef = moves ? ops[j].coef : 0.0;
-        q_resume = moves ? j + 1 : j;
-        // the next pair evaluation's force: the next EVAL in program order
-        P.next = nullptr;
-        for (int t = q_resume, seen = 0; seen < n_ops; ++seen, ++t) {
-            if (t >= n_ops) {
-                if (rep + (wraps ? 2 : 1) >= repeat) break;
-                t = 0;
-            }
-            if (ops[t].op != AMM_OP_EVAL) continue;
-            const int ga = ops[t].a;
-            if (ga >= 0 && ga < AMM_MAX_GROUPS && ctx->groups[ga].forces.size() == 1 && ctx->forces[ctx->groups[ga].forces[0]].type == 1 &&
-                !ctx->forces[ctx->groups[ga].forces[0]].pair->free_space)
-                P.next = ctx->forces[ctx->groups[ga].forces[0]].pair;
-            break;
-        }
-        return q_resume < n_ops || !wraps;        // (a wrapped plan that swallowed the whole next repetition: not a step program)
-    };
-    // leave to the host what only it can do: an exchange pending without a communicator of the library's own.  0: go on, 1: error,
-    // 2: *cursor is set -- wind up and return
-    auto leave_to_host = [&](long next_pos) -> int {
-        if (!ctx->pending.active) return 0;
-        if (cursor) {
-            *cursor = next_pos;
-            return 2;
-        }
-        if (next_pos == total_ops) return 0;       // (the plain entry point: the caller finishes the exchange of the program's last op)
-        amm_set_error("amm_run_ops: without a communicator (amm_comm_init) an exchanged EVAL must be the last op of the call (or use amm_run_ops_from)");
-        return 1;
-    };
-    bool yielded = false;
-    int k_start = cursor ? (int)(*cursor % n_ops) : 0;
-    for (int rep = cursor ? (int)(*cursor / n_ops) : 0; rep < repeat && !yielded; ++rep) {
-        const int k_first = k_start;
-        k_start = 0;
-        for (int k = k_first; k < n_ops && !yielded; ++k) {
-            const amm_op &op = ops[k];
-            if (!deferred.empty() && !(k == 0 && op.op == AMM_OP_KICK) && flush_deferred()) return 1;
-            // trailing block of the program = only KICKs and COPYs, and the program opens with KICKs: defer the kicks
-            if (ctx->fuse_inner && !no_defer && !swapped && f0_slot < 0 && rep + 1 < repeat && k > 0 && op.op == AMM_OP_KICK &&
-                deferred.empty() && ops[0].op == AMM_OP_KICK) {
-                bool safe = true;
-                int nk = 0;
-                for (int j = k; j < n_ops && safe; ++j) {
-                    if (ops[j].op == AMM_OP_KICK) ++nk;
-                    else if (ops[j].op == AMM_OP_COPY) {
-                        // the copy runs now, the kicks before it later: it must not feed or clobber what they read
-                        if (ops[j].a >= AMM_SLOT_X || ops[j].b >= AMM_SLOT_X) safe = false;
-                        for (int i = k; i < j; ++i)
-                            if (ops[i].op == AMM_OP_KICK && (ops[i].a == ops[j].a || ops[i].b == ops[j].a)) safe = false;
-                    } else safe = false;
-                }
-                if (safe && nk <= 3) {
-                    for (int j = k; j < n_ops; ++j) {
-                        if (ops[j].op == AMM_OP_KICK) deferred.push_back(ops[j]);
-                        else {
-                            double *dst = (ops[j].a >= 0 && ops[j].a < AMM_MAX_SLOTS) ? ctx->slots[ops[j].a] : nullptr;
-                            double *src = (ops[j].b >= 0 && ops[j].b < AMM_MAX_SLOTS) ? ctx->slots[ops[j].b] : nullptr;
-                            if (!dst || !src) {
-                                amm_set_error("amm_run_ops: COPY buffer not bound");
-                                return 1;
-                            }
-                            if (amm_copy_impl(ctx, dst, src)) return 1;
-                        }
-                    }
-                    break;          // next repetition
-                }
-            }
-            // component-parallel inner loop: [preceding KICKs] + n x {KICK(c1, fg) ; MOVE(d) ; EVAL(g) ; KICK(c2, fg)} in one launch
-            if (ctx->fuse_inner && !swapped && op.op == AMM_OP_KICK) {
-                int p = k, npre = 0;
-                while (p < n_ops && ops[p].op == AMM_OP_KICK && npre < 4) { ++p; ++npre; }
-                // the last KICK of the run is the first op of the inner pattern
-                int start = p - 1;
-                npre -= 1;
-                // iteration = KICK(c1, fg) ; MOVE(d) ; [BATH(b) ; MOVE(d2) ;] EVAL(g) ; KICK(c2, fg)
-                const bool bathed = start + 5 < n_ops && ops[start + 2].op == AMM_OP_BATH && ops[start + 3].op == AMM_OP_MOVE;
-                const int stride = bathed ? 6 : 4, eo = bathed ? 4 : 2;       // ops per iteration / offset of the EVAL
-                auto is_iter = [&](int q, const amm_op &first) {
-                    if (!(q + stride - 1 < n_ops && ops[q].op == AMM_OP_KICK && ops[q].b < 0 && ops[q + 1].op == AMM_OP_MOVE &&
-                          ops[q + eo].op == AMM_OP_EVAL && ops[q + eo + 1].op == AMM_OP_KICK && ops[q + eo + 1].b < 0 &&
-                          ops[q + eo + 1].a == ops[q].a && ops[q].a == first.a && ops[q].coef == first.coef &&
-                          ops[q + 1].coef == ops[start + 1].coef && ops[q + eo + 1].coef == ops[start + eo + 1].coef &&
-                          ops[q + eo].a == ops[start + eo].a))
-                        return false;
-                    if (bathed)
-                        return ops[q + 2].op == AMM_OP_BATH && ops[q + 2].a == ops[start + 2].a && ops[q + 2].a >= 0 &&
-                               ops[q + 2].a < (int)ctx->baths.size() && ops[q + 3].op == AMM_OP_MOVE &&
-                               ops[q + 3].coef == ops[start + 3].coef;
-                    return true;
-                };
-                const int ndef = (int)deferred.size();
-                if (npre <= 3 && start >= k && is_iter(start, ops[start]) && ops[start + eo].a >= 0 && ops[start + eo].a < AMM_MAX_GROUPS) {
-                    GroupDef &g = ctx->groups[ops[start + eo].a];
-                    BondedSet *bs = (g.slot == ops[start].a && g.forces.size() == 1 && ctx->forces[g.forces[0]].type == 2)
-                                        ? ctx->forces[g.forces[0]].bonded : nullptr;
-                    if (bs && bs->max_comp <= 8 && !(bs->sliced && ctx->world > 1)) {
-                        int niter = 0, q = start;
-                        while (is_iter(q, ops[start])) { ++niter; q += stride; }
-                        const double *pa[AMM_MAX_PRE] = {nullptr}, *pb[AMM_MAX_PRE] = {nullptr};
-                        double pc[AMM_MAX_PRE] = {0};
-                        int pp[AMM_MAX_PRE] = {0};
-                        bool ok = true;
-                        for (int j = 0; j < ndef + npre; ++j) {
-                            const amm_op &ko = j < ndef ? deferred[j] : ops[k + j - ndef];
-                            pa[j] = (ko.a >= 0 && ko.a < AMM_MAX_SLOTS) ? ctx->slots[ko.a] : nullptr;
-                            pb[j] = (ko.b >= 0 && ko.b < AMM_MAX_SLOTS) ? ctx->slots[ko.b] : nullptr;
-                            pc[j] = ko.coef;
-                            pp[j] = ko.c;
-                            if (!pa[j] || (ko.b >= 0 && !pb[j])) ok = false;
-                        }
-                        double *f0 = ctx->slots[g.slot];
-                        if (ok && f0) {
-                            if (complete(f0)) return 1;
-                            for (int j = 0; j < ndef + npre; ++j)
-                                if (complete(pa[j]) || complete(pb[j])) return 1;
-                            deferred.clear();
-                            if (amm_inner_components_impl(ctx, bs, ctx->d_x, ctx->d_v, f0, ndef + npre, pa, pb, pc, pp, ops[start].coef,
-                                                          ops[start + 1].coef, ops[start + eo + 1].coef, niter,
-                                                          bathed ? &ctx->baths[ops[start + 2].a] : nullptr,
-                                                          bathed ? ops[start + 3].coef : 0.0)) return 1;
-                            ctx->pos_epoch++;
-                            amm_watch_moved(ctx);
-                            k = q - 1;
-                            continue;
-                        }
-                    }
-                }
-                if (!deferred.empty()) {
-                    // no component launch to ride on: the deferred kicks can still lead the launch of the run of plain kicks (+ move)
-                    // that opens this repetition (the block further down) -- a velocity-Verlet step is then KICK + KICK + MOVE in one
-                    int run = 0;
-                    for (int j = k; j < n_ops && ops[j].op == AMM_OP_KICK; ++j) ++run;
-                    if (ctx->iso.on || (int)deferred.size() + run > 4) {
-                        if (flush_deferred()) return 1;
-                    }
-                }
-            }
-            // fused inner RESPA iteration: KICK(c1, fg) ; MOVE(d) ; EVAL(g) ; KICK(c2, fg) with g = one bond-list set
-            // (kicks deferred from the previous repetition must not be overtaken by this block's move: deferral requires
-            // f0_slot < 0, i.e. that this block never matched -- flushed here all the same, so that the order does not rest on that)
-            // (regulated mode: k_fused_inner predicts the partners' positions with plain moves -- not taken)
-            if (!deferred.empty() && ctx->fuse_inner && !ctx->iso.on && !ctx->reg.on && op.op == AMM_OP_KICK && op.b < 0 && k + 3 < n_ops &&
-                ops[k + 1].op == AMM_OP_MOVE && ops[k + 2].op == AMM_OP_EVAL && flush_deferred()) return 1;
-            if (ctx->fuse_inner && !ctx->iso.on && !ctx->reg.on && op.op == AMM_OP_KICK && op.b < 0 && k + 3 < n_ops && ops[k + 1].op == AMM_OP_MOVE &&
-                ops[k + 2].op == AMM_OP_EVAL && ops[k + 3].op == AMM_OP_KICK && ops[k + 3].b < 0 && ops[k + 3].a == op.a &&
-                ops[k + 2].a >= 0 && ops[k + 2].a < AMM_MAX_GROUPS) {
-                GroupDef &g = ctx->groups[ops[k + 2].a];
-                if (g.slot == op.a && g.forces.size() == 1 && ctx->forces[g.forces[0]].type == 2 &&
-                    !(ctx->forces[g.forces[0]].bonded->sliced && ctx->world > 1) && (f0_slot < 0 || f0_slot == g.slot)) {
-                    BondedSet *bs = ctx->forces[g.forces[0]].bonded;
-                    if (!ctx->alt_x) {
-                        const size_t bytes = sizeof(double) * 3 * (size_t)ctx->n;
-                        AMM_HIP(hipMalloc(&ctx->alt_x, bytes));
-                        AMM_HIP(hipMalloc(&ctx->alt_v, bytes));
-                        AMM_HIP(hipMalloc(&ctx->alt_f, bytes));
-                    }
-                    if (f0_slot < 0) {
-                        f0_slot = g.slot;
-                        user_f0 = ctx->slots[f0_slot];
-                    }
-                    double *xi = ctx->d_x, *vi = ctx->d_v, *fi = ctx->slots[f0_slot];
-                    double *xo = swapped ? user_x : ctx->alt_x, *vo = swapped ? user_v : ctx->alt_v,
-                           *fo = swapped ? user_f0 : ctx->alt_f;
-                    if (amm_fused_inner_impl(ctx, bs, xi, vi, fi, xo, vo, fo, op.coef, ops[k + 1].coef, ops[k + 3].coef)) return 1;
-                    ctx->pos_epoch++;
-                    ctx->d_x = xo;
-                    ctx->d_v = vo;
-                    ctx->slots[f0_slot] = fo;
-                    ctx->slots[AMM_SLOT_X] = xo;
-                    ctx->slots[AMM_SLOT_V] = vo;
-                    swapped = !swapped;
-                    k += 3;
-                    continue;
-                }
-            }
-            // EVAL(ga) ; EVAL(gb) of a guest pair force and the owner of its list, same positions: one pass for both
-            const bool no_dual = ctx->opt_no_dual != 0;     // tuning option
-            if (ctx->fuse_inner && !no_dual && op.op == AMM_OP_EVAL && k + 1 < n_ops && ops[k + 1].op == AMM_OP_EVAL && op.a >= 0 &&
-                op.a < AMM_MAX_GROUPS && ops[k + 1].a >= 0 && ops[k + 1].a < AMM_MAX_GROUPS && op.a != ops[k + 1].a) {
-                GroupDef &g1 = ctx->groups[op.a], &g2 = ctx->groups[ops[k + 1].a];
-                // further members of the two groups (bond-list terms, reciprocal space of a PME outer force) are added after
-                // the shared pass; they must not be pair forces themselves
-                auto tail_ok = [&](const GroupDef &g) {
-                    for (size_t j = 1; j < g.forces.size(); ++j)
-                        if (ctx->forces[g.forces[j]].type == 1) return false;
-                    return true;
-                };
-                if (!g1.forces.empty() && !g2.forces.empty() && tail_ok(g1) && tail_ok(g2) && g1.slot >= 0 && g2.slot >= 0 &&
-                    ctx->slots[g1.slot] && ctx->slots[g2.slot] && ctx->forces[g1.forces[0]].type == 1 &&
-                    ctx->forces[g2.forces[0]].type == 1) {
-                    PairForce *pa = ctx->forces[g1.forces[0]].pair, *pb = ctx->forces[g2.forces[0]].pair;
-                    PairForce *guest = pa->host == pb ? pa : (pb->host == pa ? pb : nullptr);
-                    if (guest) {
-                        PairForce *host = guest->host;
-                        double *fg = ctx->slots[guest == pa ? g1.slot : g2.slot], *fh = ctx->slots[guest == pa ? g2.slot : g1.slot];
-                        if (g1.exchange == g2.exchange && amm_pair_can_eval_dual(ctx, guest, host)) {
-                            // the kicks and the inner loop that follow as the launch's epilogue, when both groups are the pair forces alone
-                            EpiPlan plan;
-                            int q_resume = 0;
-                            bool wraps = false;
-                            // (several ranks: only groups whose exchange is the all-gather of slices -- the launch then integrates
-                            // this rank's molecules and the ranks exchange positions and velocities: cluster.hip, state exchange)
-                            const bool planned = (ctx->world == 1 ? !g1.exchange : g1.exchange == AMM_EXCHANGE_GATHER) &&
-                                                 g1.forces.size() == 1 && g2.forces.size() == 1 && plan_epilogue(k + 2, rep, plan, q_resume, wraps);
-                            ctx->epi_request = planned ? &plan : nullptr;
-                            ctx->epi_done = false;
-                            const int rc_dual = amm_pair_eval_impl(ctx, host, ctx->d_x, fh, 0, nullptr, guest, fg, 0, g1.exchange);
-                            ctx->epi_request = nullptr;
-                            if (rc_dual) return 1;
-                            if (ctx->epi_done) {
-                                ctx->epi_done = false;
-                                const int lv = leave_to_host(wraps ? (long)(rep + 1) * n_ops + q_resume : (long)rep * n_ops + q_resume);
-                                if (lv == 1) return 1;
-                                if (lv == 2) {
-                                    yielded = true;
-                                    break;
-                                }
-                                if (wraps) {
-                                    k_start = q_resume;
-                                    break;
-                                }
-                                k = q_resume - 1;
-                                continue;
-                            }
-                            forget_own_only(fh);           // (both buffers are written in full: by the kernel, or by the exchange's unsort)
-                            forget_own_only(fg);
-                            {
-                                const int lv = leave_to_host((long)rep * n_ops + k + 2);
-                                if (lv == 1) return 1;
-                                if (lv == 2) {
-                                    // (further members of the two groups are added after the exchange: only pair-only groups get here --
-                                    // an exchanged group holds exactly one pair force)
-                                    yielded = true;
-                                    break;
-                                }
-                            }
-                            for (const GroupDef *g : {&g1, &g2})
-                                for (size_t j = 1; j < g->forces.size(); ++j)
-                                    if (force_eval_dispatch(ctx, g->forces[j], ctx->d_x, ctx->slots[g->slot], 1, nullptr)) return 1;
-                            k += 1;
-                            continue;
-                        }
-                    }
-                }
-            }
-            // EVAL(g) ; KICK ... [; MOVE] with g = a term-parallel bond-list set [+ an interaction-group pair force with a small set,
-            // which group.hip evaluates without a list and which writes EVERY row]: the pair force goes first, the terms are
-            // evaluated, and the launch that gathers their forces also applies the kicks and the move that follow -- an inner RESPA
-            // iteration of a system that is not pure water (config C5: chain + solute + waters) is then 3 launches, not 8.
-            // (regulated mode: the gather launch's move is a plain one -- not taken)
-            if (ctx->fuse_inner && !ctx->iso.on && !ctx->reg.on && op.op == AMM_OP_EVAL && op.a >= 0 && op.a < AMM_MAX_GROUPS && ctx->groups[op.a].slot >= 0 &&
-                !ctx->groups[op.a].exchange && k + 1 < n_ops && ops[k + 1].op == AMM_OP_KICK) {
-                GroupDef &g = ctx->groups[op.a];
-                BondedSet *bs = nullptr;
-                PairForce *ps = nullptr;
-                bool plain = g.forces.size() >= 1 && g.forces.size() <= 2;
-                for (int fid : g.forces) {
-                    ForceObj &fo = ctx->forces[fid];
-                    if (fo.type == 2 && !bs) bs = fo.bonded;
-                    else if (fo.type == 1 && !ps && fo.pair->small && ctx->opt_small_group && !fo.pair->built && amm_small_group_supported(fo.pair)) ps = fo.pair;
-                    else plain = false;
-                }
-                double *buf = ctx->slots[g.slot];
-                if (plain && bs && buf && bs->n_gterms > 0 && !(bs->sliced && ctx->world > 1) && ctx->world == 1) {
-                    KickList K;
-                    K.n = 0;
-                    int j = k + 1;
-                    bool bound = true;
-                    while (j < n_ops && K.n < 4 && ops[j].op == AMM_OP_KICK) {
-                        const amm_op &kick = ops[j];
-                        const double *a_ = (kick.a >= 0 && kick.a < AMM_MAX_SLOTS) ? ctx->slots[kick.a] : nullptr;
-                        const double *b_ = (kick.b >= 0 && kick.b < AMM_MAX_SLOTS) ? ctx->slots[kick.b] : nullptr;
-                        if (!a_ || (kick.b >= 0 && !b_)) {
-                            bound = false;
-                            break;
-                        }
-                        K.f[K.n] = a_;
-                        K.f2[K.n] = b_;
-                        K.plus[K.n] = kick.c;
-                        K.coef[K.n] = kick.coef;
-                        ++K.n;
-                        ++j;
-                    }
-                    for (int q = K.n; q < 4; ++q) {
-                        K.f[q] = K.f2[q] = nullptr;
-                        K.plus[q] = 0;
-                        K.coef[q] = 0.0;
-                    }
-                    const bool more_kicks = j < n_ops && ops[j].op == AMM_OP_KICK;      // a fifth kick: left to the next launch
-                    const bool moves = !more_kicks && j < n_ops && ops[j].op == AMM_OP_MOVE;
-                    if (bound && K.n >= 1) {
-                        // (the pair force's launch evaluates the bond-list terms too: group.hip, TermsWork)
-                        const double *pair_rows = nullptr;         // (the pair force's rows: in `buf`, or in a buffer of its own)
-                        const bool own = bs->mixed_ok && ctx->opt_mixed_terms;       // (k_mixed_eval_kicks takes them from anywhere)
-                        if (ps && amm_small_group_eval_impl(ctx, ps, ctx->d_x, buf, 0, nullptr, bs, own ? &pair_rows : nullptr) != 0) return 1;
-                        if (amm_bonded_eval_kicks_impl(ctx, bs, ctx->d_x, buf, ps ? 1 : 0, K, moves ? 1 : 0, moves ? ops[j].coef : 0.0, ps ? 1 : 0, pair_rows)) return 1;
-                        if (moves) {
-                            ctx->pos_epoch++;
-                            amm_watch_moved(ctx);
-                        }
-                        k = j - (moves ? 0 : 1);
-                        continue;
-                    }
-                }
-            }
-            // a run of plain kicks, then (maybe) a move: one launch (same arithmetic per degree of freedom, same order)
-            if (ctx->fuse_inner && !ctx->iso.on && op.op == AMM_OP_KICK) {
-                const double *fa[4], *fb[4];
-                int plus[4], nk = 0;
-                double coef[4];
-                // (kicks deferred from the end of the previous repetition come first: the order they were written in)
-                const int ndef = (int)deferred.size();
-                bool def_ok = ndef <= 4;
-                for (int q = 0; q < ndef && def_ok; ++q) {
-                    const amm_op &kick = deferred[q];
-                    const double *a_ = (kick.a >= 0 && kick.a < AMM_MAX_SLOTS) ? ctx->slots[kick.a] : nullptr;
-                    const double *b_ = (kick.b >= 0 && kick.b < AMM_MAX_SLOTS) ? ctx->slots[kick.b] : nullptr;
-                    if (!a_ || (kick.b >= 0 && !b_)) {
-                        def_ok = false;
-                        break;
-                    }
-                    fa[nk] = a_;
-                    fb[nk] = b_;
-                    plus[nk] = kick.c;
-                    coef[nk] = kick.coef;
-                    ++nk;
-                }
-                if (ndef > 0 && !def_ok) {
-                    if (flush_deferred()) return 1;         // (reports the unbound buffer)
-                    nk = 0;
-                }
-                const int nlead = nk;
-                int j = k;
-                while (j < n_ops && nk < 4 && ops[j].op == AMM_OP_KICK) {
-                    const amm_op &kick = ops[j];
-                    const double *a_ = (kick.a >= 0 && kick.a < AMM_MAX_SLOTS) ? ctx->slots[kick.a] : nullptr;
-                    const double *b_ = (kick.b >= 0 && kick.b < AMM_MAX_SLOTS) ? ctx->slots[kick.b] : nullptr;
-                    if (!a_ || (kick.b >= 0 && !b_)) break;                 // left to the plain path, which reports it
-                    fa[nk] = a_;
-                    fb[nk] = b_;
-                    plus[nk] = kick.c;
-                    coef[nk] = kick.coef;
-                    ++nk;
-                    ++j;
-                }
-                const bool moves = j < n_ops && ops[j].op == AMM_OP_MOVE;
-                const bool whole_run = !(j < n_ops && ops[j].op == AMM_OP_KICK);       // (a fifth kick: the run goes on)
-                if (nk - nlead == j - k && (nlead == 0 || whole_run) && (nk >= 2 || (nk == 1 && moves))) {
-                    for (int q = 0; q < nk; ++q)
-                        if (complete(fa[q]) || complete(fb[q])) return 1;
-                    if (amm_kicks_move_impl(ctx, fa, fb, plus, coef, nk, moves ? 1 : 0, moves ? ops[j].coef : 0.0)) return 1;
-                    deferred.clear();
-                    if (moves) {
-                        ctx->pos_epoch++;
-                        amm_watch_moved(ctx);
-                    }
-                    k = j - (moves ? 0 : 1);
-                    continue;
-                }
-                if (!deferred.empty() && flush_deferred()) return 1;       // (not taken along: before anything else, in their order)
-            }
-            switch (op.op) {
-            case AMM_OP_EVAL: {
-                if (op.a < 0 || op.a >= AMM_MAX_GROUPS || ctx->groups[op.a].slot < 0) {
-                    amm_set_error("amm_run_ops: EVAL of an undefined group");
-                    return 1;
-                }
-                GroupDef &g = ctx->groups[op.a];
-                double *buf = ctx->slots[g.slot];
-                if (!buf) {
-                    amm_set_error("amm_run_ops: group buffer not bound");
-                    return 1;
-                }
-                if (g.forces.empty()) AMM_HIP(hipMemsetAsync(buf, 0, sizeof(double) * 3 * (size_t)ctx->n, ctx->stream));
-                if ((ctx->world == 1 ? !g.exchange : g.exchange == AMM_EXCHANGE_GATHER) && g.forces.size() == 1 &&
-                    ctx->forces[g.forces[0]].type == 1 && !ctx->forces[g.forces[0]].pair->free_space) {
-                    // one pair force: the kicks and the inner loop that follow can ride on its launch (molecule rows: cepi_rows; several
-                    // ranks: followed by an exchange of positions and velocities instead of forces)
-                    EpiPlan plan;
-                    int q_resume = 0;
-                    bool wraps = false;
-                    if (plan_epilogue(k + 1, rep, plan, q_resume, wraps) ||
-                        (ctx->forces[g.forces[0]].pair->all_q_zero && !ctx->forces[g.forces[0]].pair->cluster_ok &&
-                         plan_atoms(k + 1, rep, plan, q_resume, wraps))) {
-                        ctx->epi_request = &plan;
-                        ctx->epi_done = false;
-                        const int rc_one = amm_pair_eval_impl(ctx, ctx->forces[g.forces[0]].pair, ctx->d_x, buf, 0, nullptr, nullptr, nullptr, 0, g.exchange);
-                        ctx->epi_request = nullptr;
-                        if (rc_one) return 1;
-                        if (ctx->epi_done) {
-                            ctx->epi_done = false;
-                            const int lv = leave_to_host(wraps ? (long)(rep + 1) * n_ops + q_resume : (long)rep * n_ops + q_resume);
-                            if (lv == 1) return 1;
-                            if (lv == 2) yielded = true;
-                            else if (wraps) {
-                                k_start = q_resume;
-                                k = n_ops;          // (leaves the loop over this repetition's ops)
-                            } else {
-                                k = q_resume - 1;
-                            }
-                        } else {
-                            forget_own_only(buf);
-                            const int lv = leave_to_host((long)rep * n_ops + k + 1);
-                            if (lv == 1) return 1;
-                            if (lv == 2) yielded = true;
-                        }
-                        break;
-                    }
-                }
-                forget_own_only(buf);           // (every path below writes the group's buffer in full)
-                if (g.exchange) {
-                    if (g.forces.size() != 1 || ctx->forces[g.forces[0]].type != 1 || ctx->forces[g.forces[0]].pair->free_space) {
-                        amm_set_error("amm_run_ops: an exchanged group must hold exactly one pair force (with a neighbour list)");
-                        return 1;
-                    }
-                    if (amm_pair_eval_impl(ctx, ctx->forces[g.forces[0]].pair, ctx->d_x, buf, 0, nullptr, nullptr, nullptr, 0, 1)) return 1;
-                    const int lv = leave_to_host((long)rep * n_ops + k + 1);
-                    if (lv == 1) return 1;
-                    if (lv == 2) yielded = true;
-                    break;
-                }
-                // FarNonbondedForce (forces.py:710-724) = total + discount, two forces of one group: when the discount
-                // (guarded near force, sign -1) shares the total's neighbour list, both are evaluated in ONE traversal that
-                // accumulates into the same buffer (the reference, and OpenMM, run two passes)
-                std::vector<char> done(g.forces.size(), 0);
-                bool first = true;
-                for (size_t j = 0; j < g.forces.size(); ++j) {
-                    if (done[j]) continue;
-                    ForceObj &fj = ctx->forces[g.forces[j]];
-                    if (fj.type == 1) {
-                        size_t partner = g.forces.size();
-                        for (size_t i = 0; i < g.forces.size() && partner == g.forces.size(); ++i)
-                            if (i != j && !done[i] && ctx->forces[g.forces[i]].type == 1 &&
-                                amm_pair_can_fuse_discount(ctx, ctx->forces[g.forces[i]].pair, fj.pair)) partner = i;
-                        if (partner < g.forces.size()) {
-                            if (amm_pair_eval_impl(ctx, fj.pair, ctx->d_x, buf, first ? 0 : 1, nullptr, ctx->forces[g.forces[partner]].pair, buf, 1, 0)) return 1;
-                            done[j] = done[partner] = 1;
-                            first = false;
-                            continue;
-                        }
-                        // the discount itself comes later in the list: let its host pick it up
-                        bool is_discount = false;
-                        for (size_t i = 0; i < g.forces.size(); ++i)
-                            if (i != j && !done[i] && ctx->forces[g.forces[i]].type == 1 && amm_pair_can_fuse_discount(ctx, fj.pair, ctx->forces[g.forces[i]].pair)) is_discount = true;
-                        if (is_discount) continue;
-                    }
-                    if (force_eval_dispatch(ctx, g.forces[j], ctx->d_x, buf, first ? 0 : 1, nullptr)) return 1;
-                    done[j] = 1;
-                    first = false;
-                }
-                for (size_t j = 0; j < g.forces.size(); ++j)      // (a discount whose host was consumed by another pairing)
-                    if (!done[j]) {
-                        if (force_eval_dispatch(ctx, g.forces[j], ctx->d_x, buf, first ? 0 : 1, nullptr)) return 1;
-                        first = false;
-                    }
-            } break;
-            case AMM_OP_KICK: {
-                double *fa = (op.a >= 0 && op.a < AMM_MAX_SLOTS) ? ctx->slots[op.a] : nullptr;
-                double *fb = (op.b >= 0 && op.b < AMM_MAX_SLOTS) ? ctx->slots[op.b] : nullptr;
-                if (!fa || (op.b >= 0 && !fb)) {
-                    amm_set_error("amm_run_ops: KICK buffer not bound");
-                    return 1;
-                }
-                if (complete(fa) || complete(fb)) return 1;
-                if (amm_kick_impl(ctx, ctx->d_v, fa, fb, op.c, ctx->d_mass, op.coef)) return 1;
-            } break;
-            case AMM_OP_MOVE:
-                if (amm_move_impl(ctx, ctx->d_x, ctx->d_v, op.coef)) return 1;
-                ctx->pos_epoch++;
-                break;
-            case AMM_OP_COPY: {
-                double *dst = (op.a >= 0 && op.a < AMM_MAX_SLOTS) ? ctx->slots[op.a] : nullptr;
-                double *src = (op.b >= 0 && op.b < AMM_MAX_SLOTS) ? ctx->slots[op.b] : nullptr;
-                if (!dst || !src) {
-                    amm_set_error("amm_run_ops: COPY buffer not bound");
-                    return 1;
-                }
-                if (complete(src)) return 1;
-                if (amm_copy_impl(ctx, dst, src)) return 1;
-                if (dst == ctx->d_x) ctx->pos_epoch++;
-            } break;
-            case AMM_OP_COMBINE: {
-                double *dst = (op.a >= 0 && op.a < AMM_MAX_SLOTS) ? ctx->slots[op.a] : nullptr;
-                double *sa = (op.b >= 0 && op.b < AMM_MAX_SLOTS) ? ctx->slots[op.b] : nullptr;
-                double *sb = (op.c >= 0 && op.c < AMM_MAX_SLOTS) ? ctx->slots[op.c] : nullptr;
-                if (!dst || !sa || !sb) {
-                    amm_set_error("amm_run_ops: COMBINE buffer not bound");
-                    return 1;
-                }
-                if (complete(sa) || complete(sb)) return 1;
-                if (amm_combine_impl(ctx, dst, sa, sb, op.coef)) return 1;
-                if (dst == ctx->d_x) ctx->pos_epoch++;
-            } break;
-            case AMM_OP_EXPR: {
-                double *dst = (op.b >= 0 && op.b < AMM_MAX_SLOTS) ? ctx->slots[op.b] : nullptr;
-                if (op.a < 0 || op.a >= (int)ctx->exprs.size() || !dst) {
-                    amm_set_error("amm_run_ops: EXPR with an unknown expression or an unbound destination");
-                    return 1;
-                }
-                const ExprDef &e = ctx->exprs[op.a];
-                // the high bit of the counter keeps these streams apart from those of direct amm_expr_eval calls
-                const unsigned long long counter = (1ull << 63) | ++ctx->expr_counter;
-                if (amm_expr_eval_impl(ctx, e.code.data(), (int)e.code.size(), e.consts.data(), (int)e.consts.size(),
-                                       e.globals.data(), (int)e.globals.size(), ctx->expr_seed, counter, dst, nullptr)) return 1;
-            } break;
-            case AMM_OP_SAVE_REF:
-            case AMM_OP_CONSTRAIN_X:
-            case AMM_OP_CONSTRAIN_V: {
-                if (!ctx->constraints) break;       // no constraints in the System: identity (OpenMM does the same)
-                if (op.op == AMM_OP_SAVE_REF) {
-                    if (amm_constraints_save_reference(ctx, ctx->constraints, ctx->d_x)) return 1;
-                } else if (op.op == AMM_OP_CONSTRAIN_X) {
-                    if (amm_constrain_positions(ctx, ctx->constraints, ctx->d_x)) return 1;
-                    ctx->pos_epoch++;
-                } else if (amm_constrain_velocities(ctx, ctx->constraints, ctx->d_x, ctx->d_v)) return 1;
-            } break;
-            case AMM_OP_BATH: {
-                if (op.a < 0 || op.a >= (int)ctx->baths.size()) {
-                    amm_set_error("amm_run_ops: BATH with an unknown bath id");
-                    return 1;
-                }
-                if (amm_bath_impl(ctx, ctx->baths[op.a], ctx->d_v, (1ull << 63) | ++ctx->expr_counter)) return 1;
-            } break;
-            case AMM_OP_ALLREDUCE: {
-                auto bound = [&](const amm_op &o) { return o.a >= 0 && o.a < AMM_MAX_SLOTS && ctx->slots[o.a]; };
-                if (!bound(op)) {
-                    amm_set_error("amm_run_ops: ALLREDUCE of an unbound buffer");
-                    return 1;
-                }
-                // consecutive all-reduces of buffers that are neighbours in memory (the near and the outer force after a
-                // dual evaluation) travel as ONE message: the exchange is latency bound at 2.4 MB
-                const size_t n3 = 3 * (size_t)ctx->n;
-                double *lo = ctx->slots[op.a];
-                size_t count = n3;
-                while (k + 1 < n_ops && ops[k + 1].op == AMM_OP_ALLREDUCE && bound(ops[k + 1])) {
-                    double *nb = ctx->slots[ops[k + 1].a];
-                    if (nb == lo + count) count += n3;
-                    else if (nb + n3 == lo) { lo = nb; count += n3; }
-                    else break;
-                    ++k;
-                }
-                if (amm_comm_allreduce_impl(ctx, lo, count)) return 1;
-            } break;
-            default: amm_set_error("amm_run_ops: unknown op"); return 1;
-            }
-        }
     }
-    if (flush_deferred()) return 1;
-    if (cursor && !yielded) *cursor = total_ops;
-    if (!yielded && !ctx->own_only.empty()) {
-        // the program is through: the caller may read any force buffer now (the engine serves cached forces): bond-list groups are
-        // evaluated again in full, a pair group left with this rank's rows only is an error (a RESPA program ends on a whole evaluation)
-        const std::vector<const double *> left = ctx->own_only;
-        for (const double *b : left)
-            if (complete(b)) return 1;
-    }
-    if (swapped) {   // odd number of fused iterations: bring the state back into the caller's buffers
-        const size_t bytes = sizeof(double) * 3 * (size_t)ctx->n;
-        AMM_HIP(hipMemcpyAsync(user_x, ctx->d_x, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        AMM_HIP(hipMemcpyAsync(user_v, ctx->d_v, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        AMM_HIP(hipMemcpyAsync(user_f0, ctx->slots[f0_slot], bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    bindings.restore(false);        // the copies above were checked; only the pointers are left to rebind
-    return 0;
+    return amm_run_ops_impl(ctx, ops, n_ops, repeat, cursor);
 }
 
 int amm_pair_get_stats(amm_ctx *ctx, int32_t force_id, amm_pair_stats *out) {
@@ -2113,13 +1339,11 @@ int amm_set_option(amm_ctx *ctx, const char *name, double value) {
     else if (k == "dual_unroll") ctx->opt_dual_unroll = v;
     else if (k == "tab_block") ctx->opt_tab_bs = v;
     else if (k == "tab_dual_block") ctx->opt_tab_dual_bs = v;
-    else if (k == "no_dual") ctx->opt_no_dual = v;
     else if (k == "fuse_rows") ctx->opt_fuse_rows = v;
     else if (k == "row_phases") ctx->opt_row_phases = v;
     else if (k == "group_candidates") ctx->opt_group_candidates = v;
     else if (k == "positions_private") ctx->opt_positions_private = v;
     else if (k == "site_tab") ctx->opt_site_tab = v;
-    else if (k == "no_defer") ctx->opt_no_defer = v;
     else if (k == "terms_from") ctx->opt_terms_from = v;
     else if (k == "no_term_lanes") ctx->opt_no_term_lanes = v;
     else if (k == "fuse_epilogue") ctx->opt_fuse_epilogue = v;
@@ -2169,7 +1393,7 @@ static int box_apply(amm_ctx *ctx, bool &regrid, bool &waited) {
     // 1. every force's buffers as amm_pair_create would derive them in this box (a hybrid list's per-atom part asks for a multiple of
     // its parent's: the parent comes first in ctx->forces)
     for (auto &fo : ctx->forces) {
-        if (fo.type != 1 || fo.pair->free_space) continue;
+        if (fo.type != AMM_FORCE_PAIR || fo.pair->free_space) continue;
         PairForce *pf = fo.pair;
         pair_derive_buffers(ctx, pf);
         if (pf->rest) pf->rest->skin_req = pf->skin * ctx->opt_rest_skin_factor;
@@ -2183,7 +1407,7 @@ static int box_apply(amm_ctx *ctx, bool &regrid, bool &waited) {
         return 0;
     };
     for (auto &fo : ctx->forces) {
-        if (fo.type != 1 || fo.pair->host || fo.pair->free_space) continue;
+        if (fo.type != AMM_FORCE_PAIR || fo.pair->host || fo.pair->free_space) continue;
         PairForce *L = fo.pair;
         const bool dual = L->skin_out > L->skin * (1 + 1e-9);
         const double full_skin = L->skin;
@@ -2243,7 +1467,7 @@ static int box_apply(amm_ctx *ctx, bool &regrid, bool &waited) {
     }
     // 3. shared lists, as amm_pair_share_list left them
     for (auto &fo : ctx->forces)
-        if (fo.type == 1 && fo.pair->host) {
+        if (fo.type == AMM_FORCE_PAIR && fo.pair->host) {
             PairForce *g = fo.pair, *h = g->host;
             g->rlist_build = std::min(g->rlist_build, h->desc.rc + std::min(g->skin, h->skin) + 2e-4);
             share_buffers(g, h);
@@ -2251,7 +1475,7 @@ static int box_apply(amm_ctx *ctx, bool &regrid, bool &waited) {
     // 4. nothing made for the old box survives: lists are rebuilt by their next evaluation, sorted copies gathered again, the
     // displacement triggers start from the positions of that rebuild, candidate sets start over
     for (auto &fo : ctx->forces) {
-        if (fo.type != 1 || fo.pair->free_space) continue;
+        if (fo.type != AMM_FORCE_PAIR || fo.pair->free_space) continue;
         PairForce *pf = fo.pair;
         pf->a_sorted_for = nullptr;
         pf->a_sorted_epoch = pf->checked_epoch = pf->pre_epoch = -1;
@@ -2283,7 +1507,7 @@ int amm_set_box(amm_ctx *ctx, const double h_box[3]) {
         return 1;
     }
     for (auto &fo : ctx->forces)
-        if (fo.type == 1 && !fo.pair->free_space)
+        if (fo.type == AMM_FORCE_PAIR && !fo.pair->free_space)
             for (int k = 0; k < 3; ++k)
                 if (fo.pair->desc.rc > 0.5 * h_box[k] * (1 + 1e-12)) {
                     amm_set_error("pair cutoff exceeds half the box edge (minimum image needs rc <= L/2)");

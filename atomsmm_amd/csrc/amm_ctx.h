@@ -240,8 +240,9 @@ struct PmeForce;      // pme.hip
 struct ConstraintSet; // constraints.hip
 struct MinObj;        // minimize.hip: one L-BFGS minimisation (history ring, Gram matrix, direction)
 
+enum : int { AMM_FORCE_RELEASED = 0, AMM_FORCE_PAIR = 1, AMM_FORCE_BONDED = 2, AMM_FORCE_PME = 3 };   // ForceObj::type
 struct ForceObj {
-    int type = 0;   // 1 pair, 2 bonded, 3 PME reciprocal space
+    int type = AMM_FORCE_RELEASED;
     PairForce *pair = nullptr;
     BondedSet *bonded = nullptr;
     PmeForce *pme = nullptr;
@@ -381,7 +382,7 @@ struct amm_ctx {
     int opt_group_candidates = 1;       // list-free group forces on the fused inner loop: walk the atoms near the small set only while a companion list vouches for them
     int opt_row_phases = 1;             // molecule rows: the remainder of the rows after whole rounds of tasks goes out in smaller tasks (cpair_plan)
     int opt_fuse_rows = 1;              // molecule rows: host + guest force of a shared list in ONE launch when a fused kernel exists
-    int opt_no_dual = 0, opt_no_defer = 0, opt_terms_from = 8192, opt_no_term_lanes = 0;
+    int opt_terms_from = 8192, opt_no_term_lanes = 0;
     ListWatch watched[AMM_MAX_WATCH];
     int n_watched = 0;
     int device = 0;
@@ -455,6 +456,9 @@ struct WatchArgs {
 void amm_collect_watches(amm_ctx *ctx, WatchArgs &W);
 void amm_watch_moved(amm_ctx *ctx);
 
+// run_ops.hip: the op scheduler (validated arguments, n_ops > 0, repeat > 0); abi.hip: one force of any type
+int amm_run_ops_impl(amm_ctx *ctx, const amm_op *ops, int n_ops, int repeat, int64_t *cursor);
+int amm_force_eval_dispatch(amm_ctx *ctx, int force_id, const double *d_pos, double *d_force, int accumulate, double *d_energy);
 // comm.hip
 int amm_comm_unique_id_impl(const char *rccl_path, unsigned char *out);
 int amm_comm_init_impl(amm_ctx *ctx, const char *rccl_path, const unsigned char *id_bytes, int rank, int world);

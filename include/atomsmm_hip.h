@@ -329,7 +329,7 @@ int amm_set_outer_skin(amm_ctx *ctx, double skin_out);
  * force-only kernels), "site_trips", "lanes_per_row", "build_parts", "build_split" (molecule rows: the split-stream
  * list build -- a block per (cell, part), both passes shared out over its four wavefronts; 0 = off (default: not faster than the
  * one-wavefront build on the slices measured), -1 = for a rank's slice of the rows, k = k blocks per cell; the rows are the same), "unroll", "dual_unroll", "tab_block", "tab_dual_block",
- * "no_dual", "no_defer", "terms_from", "no_term_lanes", "row_phases" (1: the rows a molecule-row traversal cannot deal out in whole
+ * "terms_from", "no_term_lanes", "row_phases" (1: the rows a molecule-row traversal cannot deal out in whole
  * rounds of wavefront tasks go out in smaller tasks), "group_candidates" (1: a list-free group force on a fused inner loop walks only
  * the atoms near its small set while a neighbour list of the context vouches for them), "positions_private" (1: the caller promises
  * to call amm_positions_changed after writing the bound position buffer itself; amm_run_ops then trusts the displacement checks its

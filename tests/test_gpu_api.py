@@ -711,3 +711,33 @@ def test_pme_respa_trajectory_fused_equals_unfused(spcfw):
                         eng.ctx.pair_stats(eng.pair_force_ids(2)[0])['n_builds']))
     assert np.array_equal(results[0][0], results[1][0]) and np.array_equal(results[0][1], results[1][1])
     assert results[0][2] == results[1][2] and results[0][2] >= 2          # the list was rebuilt on the way
+
+
+def test_run_ops_from_empty_program_and_null_ops():
+    """The resumable entry point on the library itself: an empty program is through before it starts (returns 0, cursor at
+    0 == repeat * n_ops, nothing divided by n_ops), and a program without ops is an error with a message."""
+    import ctypes as C
+    from atomsmm_amd import backend as B
+    L = B.lib()
+    ctx = B.HipContext(8, [3.0, 3.0, 3.0])
+    try:
+        x = torch.rand(8, 3, dtype=torch.float64, device='cuda')
+        v = torch.zeros_like(x)
+        mass = torch.ones(8, dtype=torch.float64, device='cuda')
+        ctx.bind_state(x, v, mass)
+        x0 = x.clone()
+        ops = (B.Op * 1)(B.Op(2, 0, -1, 0, 0.5))
+        for n_ops, repeat in ((0, 1), (0, 0), (1, 0)):
+            cursor = C.c_int64(0)
+            assert L.amm_run_ops_from(ctx.h, ops, n_ops, repeat, C.byref(cursor)) == 0
+            assert cursor.value == 0
+        assert L.amm_run_ops_from(ctx.h, None, 0, 1, None) == 0
+        cursor = C.c_int64(0)
+        assert L.amm_run_ops_from(ctx.h, None, 1, 1, C.byref(cursor)) != 0
+        assert b'null ops' in L.amm_last_error()
+        assert L.amm_run_ops_from(None, ops, 1, 1, None) != 0
+        assert b'null context' in L.amm_last_error()
+        ctx.synchronize()
+        assert torch.equal(x, x0)
+    finally:
+        ctx.close()
