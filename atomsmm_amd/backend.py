@@ -19,6 +19,8 @@ BOND_VIRIAL_HARMONIC, BOND_VIRIAL_LJ = 6, 7
 OP_EVAL, OP_KICK, OP_MOVE, OP_COPY, OP_COMBINE, OP_EXPR, OP_BATH = 1, 2, 3, 4, 5, 6, 7
 OP_SAVE_REF, OP_CONSTRAIN_X, OP_CONSTRAIN_V = 8, 9, 10
 OP_ALLREDUCE = 11
+OP_STOCK = 12
+STOCK_VERLET, STOCK_LANGEVIN_MIDDLE, STOCK_LANGEVIN, STOCK_BROWNIAN = range(4)   # amm_stock_define kinds
 EXCHANGE_REDUCE, EXCHANGE_GATHER = 0, 1
 COMM_ID_BYTES = 128
 MAX_SLOTS, SLOT_X, SLOT_V = 64, 62, 63
@@ -37,7 +39,7 @@ EXPORTS = [
     'amm_move', 'amm_copy', 'amm_mvv', 'amm_bind_state', 'amm_bind_buffer', 'amm_group_define', 'amm_run_ops',
     'amm_set_fuse_inner', 'amm_set_outer_skin',
     'amm_pair_get_stats', 'amm_profile_enable', 'amm_profile_read', 'amm_pair_count_within', 'amm_pair_row_padding', 'amm_kernel_revision',
-    'amm_pme_create', 'amm_pme_set_charges', 'amm_pme_set_sliced', 'amm_pair_set_lambda', 'amm_pair_set_lambda_dev', 'amm_expr_eval', 'amm_expr_eval_scalar', 'amm_expr_define', 'amm_expr_seed', 'amm_bath_define', 'amm_bath_define_nhl', 'amm_bath_define_sin', 'amm_iso_define', 'amm_regulated_define', 'amm_bath_define_regulated', 'amm_pair_energy_derivative', 'amm_constraints_create', 'amm_pair_set_scale',
+    'amm_pme_create', 'amm_pme_set_charges', 'amm_pme_set_sliced', 'amm_pair_set_lambda', 'amm_pair_set_lambda_dev', 'amm_expr_eval', 'amm_expr_eval_scalar', 'amm_expr_define', 'amm_expr_seed', 'amm_bath_define', 'amm_stock_define', 'amm_bath_define_nhl', 'amm_bath_define_sin', 'amm_iso_define', 'amm_regulated_define', 'amm_bath_define_regulated', 'amm_pair_energy_derivative', 'amm_constraints_create', 'amm_constraints_set_tolerance', 'amm_pair_set_scale',
     'amm_comm_unique_id', 'amm_comm_init', 'amm_comm_destroy', 'amm_comm_allreduce', 'amm_comm_stats', 'amm_group_set_exchange', 'amm_bind_exchange', 'amm_exchange_finish',
     'amm_set_option', 'amm_positions_changed', 'amm_exchange_per', 'amm_run_stats', 'amm_run_ops_from', 'amm_exchange_pending',
     'amm_pair_energy_states',
@@ -188,9 +190,11 @@ def lib():
         L.amm_expr_define.argtypes = [vp, ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip]
         L.amm_expr_seed.argtypes = [vp, C.c_uint64]
         L.amm_constraints_create.argtypes = [vp, ip, dp, C.c_int32, C.c_double]
+        L.amm_constraints_set_tolerance.argtypes = [vp, C.c_double]
         L.amm_pair_energy_derivative.argtypes = [vp, C.c_int32, vp, vp]
         L.amm_pair_energy_states.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp]
         L.amm_bath_define.argtypes = [vp, C.c_double, C.c_double, ip]
+        L.amm_stock_define.argtypes = [vp, C.c_int32, C.c_double, C.c_double, C.c_double, ip]
         L.amm_bath_define_nhl.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, ip]
         L.amm_bath_define_sin.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, ip]
         L.amm_iso_define.argtypes = [vp, C.c_int32, C.c_double, C.c_double, C.c_int32]
@@ -388,6 +392,9 @@ class HipContext:
     def pme_set_sliced(self, fid, on=True):
         _chk(lib().amm_pme_set_sliced(self.h, fid, int(bool(on))))
 
+    def constraints_set_tolerance(self, tolerance):
+        _chk(lib().amm_constraints_set_tolerance(self.h, float(tolerance)))
+
     def expr_define(self, code, consts, globals_):
         c_, cp = _hi(code)
         k_, kp = _hd(consts if len(consts) else [0.0])
@@ -439,12 +446,18 @@ class HipContext:
         """What amm_run_ops fused so far: launches that carried the inner RESPA loop as an epilogue, evaluations without a gather launch."""
         out = (C.c_int64 * 4)()
         _chk(lib().amm_run_stats(self.h, out))
-        return dict(epilogues=out[0], copies_current=out[1], state_exchanges=out[2])
+        return dict(epilogues=out[0], copies_current=out[1], state_exchanges=out[2], scheduled=out[3])
 
     def bath_define(self, z, kT):
         bid = C.c_int32(-1)
         _chk(lib().amm_bath_define(self.h, float(z), float(kT), C.byref(bid)))
         return bid.value
+
+    def stock_define(self, kind, dt, friction, kT):
+        """One of OpenMM's stock integrators (STOCK_*) for OP_STOCK: dt in ps, friction in 1/ps, kT in kJ/mol."""
+        sid = C.c_int32(-1)
+        _chk(lib().amm_stock_define(self.h, int(kind), float(dt), float(friction), float(kT), C.byref(sid)))
+        return sid.value
 
     def bath_define_nhl(self, h, z, kT, Q, friction, slot):
         bid = C.c_int32(-1)

@@ -957,6 +957,14 @@ int amm_constraints_create(amm_ctx *ctx, const int32_t *h_pairs, const double *h
     return amm_constraints_create_impl(ctx, h_pairs, h_dist, n_constraints, tolerance, &ctx->constraints);
 }
 
+int amm_constraints_set_tolerance(amm_ctx *ctx, double tolerance) {
+    if (!ctx || !ctx->constraints) {
+        amm_set_error("amm_constraints_set_tolerance: the context has no constraint set (amm_constraints_create)");
+        return 1;
+    }
+    return amm_constraints_set_tolerance_impl(ctx->constraints, tolerance);
+}
+
 int amm_expr_define(amm_ctx *ctx, const int32_t *code, int32_t n_code, const double *consts, int32_t n_consts,
                     const double *globals, int32_t n_globals, int32_t *expr_id) {
     if (!ctx || !code || n_code < 1 || !expr_id || (n_consts > 0 && !consts) || (n_globals > 0 && !globals)) {
@@ -982,6 +990,39 @@ int amm_bath_define(amm_ctx *ctx, double z, double kT, int32_t *bath_id) {
     b.kT = kT;
     ctx->baths.push_back(b);
     *bath_id = (int32_t)ctx->baths.size() - 1;
+    return 0;
+}
+
+int amm_stock_define(amm_ctx *ctx, int32_t kind, double dt, double friction, double kT, int32_t *stock_id) {
+    if (!ctx || !stock_id) {
+        amm_set_error("amm_stock_define: null argument");
+        return 1;
+    }
+    if (kind < AMM_STOCK_VERLET || kind > AMM_STOCK_BROWNIAN) {
+        amm_set_error("amm_stock_define: unknown kind " + std::to_string(kind) + " (0 Verlet, 1 LangevinMiddle, 2 Langevin, 3 Brownian)");
+        return 1;
+    }
+    if (!(friction >= 0.0) || !(kT >= 0.0)) {
+        amm_set_error("amm_stock_define: the friction and kT must not be negative");
+        return 1;
+    }
+    if (kind == AMM_STOCK_BROWNIAN && !(friction > 0.0)) {
+        amm_set_error("amm_stock_define: a Brownian integrator needs a friction > 0");
+        return 1;
+    }
+    if (!(dt == dt) || dt == 0.0) {
+        amm_set_error("amm_stock_define: the step size must not be 0 (the velocities are differences of positions over it)");
+        return 1;
+    }
+    StockDef sd;
+    sd.kind = kind;
+    sd.dt = dt;
+    sd.friction = friction;
+    sd.kT = kT;
+    sd.a = exp(-friction * dt);
+    sd.b = friction > 0.0 ? (1.0 - sd.a) / friction : dt;
+    ctx->stocks.push_back(sd);
+    *stock_id = (int32_t)ctx->stocks.size() - 1;
     return 0;
 }
 
@@ -1569,7 +1610,7 @@ int amm_run_stats(amm_ctx *ctx, int64_t out[4]) {
     out[0] = ctx->n_epilogues;
     out[1] = ctx->n_copies_current;
     out[2] = ctx->n_state_exchanges;
-    out[3] = 0;
+    out[3] = ctx->n_sched;
     return 0;
 }
 

@@ -274,6 +274,12 @@ struct BathDef {
     double kfac = 1;               // twice-regulated kinds: (n + 1)/(alpha_n n), the factor of m v^2 in the drive
 };
 
+// One of OpenMM's stock integrators (amm_stock_define; stock.hip): a = exp(-friction dt), b = (1 - a)/friction (dt when friction = 0)
+struct StockDef {
+    int kind = 0;                  // AMM_STOCK_*
+    double dt = 0, friction = 0, kT = 0, a = 1, b = 0;
+};
+
 // Regulated mode of a context (RegulatedTranslationPropagator, propagators.py:1537-1575): every AMM_OP_MOVE is
 //   x <- x + c tanh(alpha v / c) coef,  c = sqrt(an_kT / m)
 // (amm_reg_dx, expr_vm.h), so that no degree of freedom moves faster than c.
@@ -364,6 +370,7 @@ struct amm_ctx {
     // nobody else needs them) until their group is evaluated again in full: amm_run_ops refuses -- or, for bond-list groups,
     // re-evaluates -- before an op reads one for all atoms
     std::vector<const double *> own_only;
+    long long n_sched = 0;             // scheduling decisions of amm_run_ops so far: launches of the step program, an evaluation counted as one
     long long n_copies_current = 0;    // evaluations that found their sorted copies in place (no gather launch)
     // tuning / test options (amm_set_option): never read from the environment, so that a stray variable cannot change the
     // order of summation of a production run
@@ -404,6 +411,7 @@ struct amm_ctx {
     std::vector<MinObj *> minimizers;       // amm_min_create (ids are positions, never reused)
     std::vector<ExprDef> exprs;    // registered per-DOF expressions (AMM_OP_EXPR)
     std::vector<BathDef> baths;    // registered baths (AMM_OP_BATH)
+    std::vector<StockDef> stocks;  // registered stock integrators (AMM_OP_STOCK)
     IsoDef iso;                    // isokinetic mode: what AMM_OP_KICK means (amm_iso_define)
     RegDef reg;                    // regulated mode: what AMM_OP_MOVE means (amm_regulated_define)
     unsigned long long expr_seed = 0, expr_counter = 0;
@@ -524,12 +532,14 @@ int amm_inner_components_impl(amm_ctx *ctx, BondedSet *bs, double *x, double *v,
                               const double *const *pre_b, const double *pre_coef, const int *pre_plus, double c1, double d,
                               double c2, int niter, const BathDef *bath = nullptr, double d2 = 0.0);
 int amm_bath_impl(amm_ctx *ctx, const BathDef &bath, double *d_v, unsigned long long counter);
+int amm_stock_step_impl(amm_ctx *ctx, const StockDef &sd, const double *d_f, unsigned long long counter);       // stock.hip
 int amm_isokick_impl(amm_ctx *ctx, double *d_v, const double *d_f, const double *d_f2, int plus, const double *d_mass, double coef);
 int amm_constraints_create_impl(amm_ctx *ctx, const int32_t *h_pairs, const double *h_dist, int n_cons, double tol,
                                 ConstraintSet **out);
 int amm_constraints_save_reference(amm_ctx *ctx, ConstraintSet *cs, const double *d_x);
 int amm_constrain_positions(amm_ctx *ctx, ConstraintSet *cs, double *d_x);
 int amm_constrain_velocities(amm_ctx *ctx, ConstraintSet *cs, const double *d_x, double *d_v);
+int amm_constraints_set_tolerance_impl(ConstraintSet *cs, double tol);
 int amm_constraints_failed(amm_ctx *ctx, ConstraintSet *cs);
 int amm_constraints_free(ConstraintSet *cs);
 int amm_fused_inner_impl(amm_ctx *ctx, BondedSet *bs, const double *x_in, const double *v_in, const double *f_in,

@@ -11,33 +11,9 @@
 // MI355X mapping: constraints only couple atoms of one small cluster (a rigid water: 3 atoms / 3 constraints; X-H
 // groups: up to 4 atoms): ONE THREAD solves one cluster entirely in private memory -- no inter-thread traffic, no
 // atomics, deterministic.  Positions are not wrapped (a molecule never straddles the box in the engine's arrays).
-#include "amm_ctx.h"
+#include "cons_sweeps.h"
 
-#define AMM_CLUSTER_ATOMS 8
-#define AMM_CLUSTER_CONS 16
-
-struct ConstraintSet {
-    int ncluster = 0;
-    double tol = 1e-5;
-    int *d_cptr = nullptr;       // [ncluster+1] constraints of each cluster
-    int *d_aptr = nullptr;       // [ncluster+1] atoms of each cluster
-    int *d_atoms = nullptr;      // atom indices, cluster by cluster
-    int2 *d_pair = nullptr;      // constraint -> (local i, local j) within its cluster
-    double *d_dist = nullptr;    // constraint -> distance
-    double *d_xref = nullptr;    // [n][3] reference positions (see above)
-    int *d_fail = nullptr;       // set when a cluster does not converge
-};
-
-struct ConsArgs {
-    int ncluster;
-    const int *cptr, *aptr, *atoms;
-    const int2 *pair;
-    const double *dist;
-    const double *mass;
-    double tol;
-    int *fail;
-};
-
+// the sweeps themselves are in cons_sweeps.h (amm_shake_sweeps / amm_rattle_sweeps, generic shape here)
 __global__ void __launch_bounds__(128) k_shake(ConsArgs A, double *x, double *xref) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= A.ncluster) return;
@@ -51,31 +27,8 @@ __global__ void __launch_bounds__(128) k_shake(ConsArgs A, double *x, double *xr
             r[k][j] = xref[3 * i + j];
         }
     }
-    const double lower = 1.0 - 2.0 * A.tol + A.tol * A.tol, upper = 1.0 + 2.0 * A.tol + A.tol * A.tol;
-    bool done = false;
-    for (int it = 0; it < 500 && !done; ++it) {
-        done = true;
-        for (int q = 0; q < nc; ++q) {
-            const int2 ij = A.pair[c0 + q];
-            const double d2 = A.dist[c0 + q] * A.dist[c0 + q];
-            double dp[3], dr[3], pp = 0.0, rp = 0.0;
-            for (int j = 0; j < 3; ++j) {
-                dp[j] = p[ij.x][j] - p[ij.y][j];
-                dr[j] = r[ij.x][j] - r[ij.y][j];
-                pp += dp[j] * dp[j];
-                rp += dr[j] * dp[j];
-            }
-            if (pp < lower * d2 || pp > upper * d2) {
-                done = false;
-                const double g = (d2 - pp) / (2.0 * (im[ij.x] + im[ij.y]) * rp);
-                for (int j = 0; j < 3; ++j) {
-                    p[ij.x][j] += g * im[ij.x] * dr[j];
-                    p[ij.y][j] -= g * im[ij.y] * dr[j];
-                }
-            }
-        }
-    }
-    if (!done) *A.fail = 1;
+    const ConsShapeGeneric S = {nc, A.pair + c0, A.dist + c0};
+    if (!amm_shake_sweeps(S, p, r, im, A.tol)) *A.fail = 1;
     for (int k = 0; k < na; ++k) {
         const int i = A.atoms[a0 + k];
         for (int j = 0; j < 3; ++j) {
@@ -98,29 +51,8 @@ __global__ void __launch_bounds__(128) k_rattle(ConsArgs A, const double *x, dou
             w[k][j] = v[3 * i + j];
         }
     }
-    bool done = false;
-    for (int it = 0; it < 500 && !done; ++it) {
-        done = true;
-        for (int q = 0; q < nc; ++q) {
-            const int2 ij = A.pair[c0 + q];
-            double dp[3], dot = 0.0, pp = 0.0;
-            for (int j = 0; j < 3; ++j) {
-                dp[j] = p[ij.x][j] - p[ij.y][j];
-                dot += dp[j] * (w[ij.x][j] - w[ij.y][j]);
-                pp += dp[j] * dp[j];
-            }
-            // relative rate of change of the bond length, d ln|r| / dt, against the tolerance (1/ps)
-            if (fabs(dot) > A.tol * pp) {
-                done = false;
-                const double g = -dot / ((im[ij.x] + im[ij.y]) * pp);
-                for (int j = 0; j < 3; ++j) {
-                    w[ij.x][j] += g * im[ij.x] * dp[j];
-                    w[ij.y][j] -= g * im[ij.y] * dp[j];
-                }
-            }
-        }
-    }
-    if (!done) *A.fail = 1;
+    const ConsShapeGeneric S = {nc, A.pair + c0, A.dist + c0};
+    if (!amm_rattle_sweeps(S, p, w, im, A.tol)) *A.fail = 1;
     for (int k = 0; k < na; ++k) {
         const int i = A.atoms[a0 + k];
         for (int j = 0; j < 3; ++j) v[3 * i + j] = w[k][j];
@@ -194,9 +126,46 @@ int amm_constraints_create_impl(amm_ctx *ctx, const int32_t *h_pairs, const doub
         aptr[c + 1] = (int)flat_atoms.size();
         cptr[c + 1] = (int)pair.size();
     }
+    // work units of the stock-integrator step (stock.hip): clusters by class, then the atoms of no cluster.  A triangle's atoms are
+    // numbered so that its constraints, in their order, are (0,1), (0,2), (1,2): 0 is the atom the first two share (the sweep order
+    // is kept; the orientation of a constraint does not enter the result)
+    std::vector<int> units[3], free_atoms, fixed_tri, fixed_two;
+    for (int c = 0; c < ncl; ++c) {
+        const int na = aptr[c + 1] - aptr[c], nc = cptr[c + 1] - cptr[c];
+        const int2 *pq = pair.data() + cptr[c];
+        const int *at = flat_atoms.data() + aptr[c];
+        int cls = AMM_CONS_GENERIC;
+        if (na == 3 && nc == 3) {
+            const int shared = pq[0].x == pq[1].x || pq[0].x == pq[1].y ? pq[0].x : pq[0].y == pq[1].x || pq[0].y == pq[1].y ? pq[0].y : -1;
+            if (shared >= 0) {
+                const int one = pq[0].x == shared ? pq[0].y : pq[0].x, two = pq[1].x == shared ? pq[1].y : pq[1].x;
+                const bool closes = (pq[2].x == one && pq[2].y == two) || (pq[2].x == two && pq[2].y == one);
+                if (one != two && one != shared && two != shared && closes) {
+                    cls = AMM_CONS_TRIANGLE;
+                    for (int k : {shared, one, two}) fixed_tri.push_back(at[k]);
+                }
+            }
+        } else if (na == 2 && nc == 1) {
+            cls = AMM_CONS_PAIR;
+            fixed_two.push_back(at[pq[0].x]);
+            fixed_two.push_back(at[pq[0].y]);
+        }
+        units[cls].push_back(c);
+    }
+    for (int i = 0; i < n; ++i)
+        if (cluster_of[i] < 0) free_atoms.push_back(i);
+    std::vector<int> flat_units;
+    for (int cls : {AMM_CONS_TRIANGLE, AMM_CONS_PAIR, AMM_CONS_GENERIC}) flat_units.insert(flat_units.end(), units[cls].begin(), units[cls].end());
+    flat_units.insert(flat_units.end(), free_atoms.begin(), free_atoms.end());
     ConstraintSet *cs = new ConstraintSet();
     cs->ncluster = ncl;
     cs->tol = tol > 0 ? tol : 1e-5;
+    cs->n_tri = (int)units[AMM_CONS_TRIANGLE].size();
+    cs->n_two = (int)units[AMM_CONS_PAIR].size();
+    cs->n_gen = (int)units[AMM_CONS_GENERIC].size();
+    cs->n_free = (int)free_atoms.size();
+    fixed_tri.insert(fixed_tri.end(), fixed_two.begin(), fixed_two.end());
+    if (cons_upload(&cs->d_units, flat_units) || cons_upload(&cs->d_fixed, fixed_tri)) return 1;
     if (cons_upload(&cs->d_cptr, cptr) || cons_upload(&cs->d_aptr, aptr) || cons_upload(&cs->d_atoms, flat_atoms) ||
         cons_upload(&cs->d_pair, pair) || cons_upload(&cs->d_dist, dist))
         return 1;
@@ -240,6 +209,11 @@ int amm_constrain_velocities(amm_ctx *ctx, ConstraintSet *cs, const double *d_x,
     return 0;
 }
 
+int amm_constraints_set_tolerance_impl(ConstraintSet *cs, double tol) {
+    cs->tol = tol > 0 ? tol : 1e-5;          // (passed to the kernels by value at every launch)
+    return 0;
+}
+
 int amm_constraints_failed(amm_ctx *ctx, ConstraintSet *cs) {
     int fail = 0;
     if (hipMemcpy(&fail, cs->d_fail, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return 1;
@@ -249,7 +223,7 @@ int amm_constraints_failed(amm_ctx *ctx, ConstraintSet *cs) {
 }
 
 int amm_constraints_free(ConstraintSet *cs) {
-    void *ptrs[] = {cs->d_cptr, cs->d_aptr, cs->d_atoms, cs->d_pair, cs->d_dist, cs->d_xref, cs->d_fail};
+    void *ptrs[] = {cs->d_cptr, cs->d_aptr, cs->d_atoms, cs->d_pair, cs->d_dist, cs->d_xref, cs->d_fail, cs->d_units, cs->d_fixed};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     delete cs;

@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "amm_ctx.h"
+#include "expr_vm.h"
 
 namespace {
 
@@ -629,8 +630,12 @@ struct OpRun {
                 return FAILED;
             }
             const ExprDef &e = ctx->exprs[op.a];
-            // the high bit of the counter keeps these streams apart from those of direct amm_expr_eval calls
-            const unsigned long long counter = (1ull << 63) | ++ctx->expr_counter;
+            // the high bit of the counter keeps these streams apart from those of direct amm_expr_eval calls.  An expression whose
+            // code draws no random number takes no counter: a step's random ops then see the same counters whatever deterministic
+            // expressions stand between them (a stock integrator's op-by-op step draws what its AMM_OP_STOCK draws)
+            bool draws = false;
+            for (const int32_t word : e.code) draws = draws || (word & 0xFF) == X_GAUSS || (word & 0xFF) == X_UNIFORM;
+            const unsigned long long counter = (1ull << 63) | (draws ? ++ctx->expr_counter : ctx->expr_counter);
             if (amm_expr_eval_impl(ctx, e.code.data(), (int)e.code.size(), e.consts.data(), (int)e.consts.size(),
                                    e.globals.data(), (int)e.globals.size(), ctx->expr_seed, counter, dst, nullptr)) return FAILED;
         } break;
@@ -651,6 +656,25 @@ struct OpRun {
                 return FAILED;
             }
             if (amm_bath_impl(ctx, ctx->baths[op.a], ctx->d_v, (1ull << 63) | ++ctx->expr_counter)) return FAILED;
+        } break;
+        case AMM_OP_STOCK: {
+            const double *f = slot(op.b);
+            if (op.a < 0 || op.a >= (int)ctx->stocks.size()) {
+                amm_set_error("amm_run_ops: STOCK with an unknown stock id");
+                return FAILED;
+            }
+            if (!f) {
+                amm_set_error("amm_run_ops: STOCK force buffer not bound");
+                return FAILED;
+            }
+            if (ctx->iso.on || ctx->reg.on) {
+                amm_set_error("amm_run_ops: STOCK does not run in the isokinetic or the regulated mode");
+                return FAILED;
+            }
+            if (complete(f)) return FAILED;
+            if (amm_stock_step_impl(ctx, ctx->stocks[op.a], f, (1ull << 63) | ++ctx->expr_counter)) return FAILED;
+            ctx->pos_epoch++;
+            amm_watch_moved(ctx);
         } break;
         case AMM_OP_ALLREDUCE: {
             if (!slot(op.a)) {
@@ -707,6 +731,7 @@ struct OpRun {
             while (k < n_ops && !yielded) {
                 const int r = step(k);
                 if (r == FAILED) return 1;
+                ctx->n_sched++;
                 yielded = r == YIELDED;
             }
         }

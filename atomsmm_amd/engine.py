@@ -265,10 +265,17 @@ def _refuse_vector_functions(expr):
 class Engine:
     native_regulated = True       # regulated moves and baths as native ops (False: per-DOF expressions -- a measurement knob)
 
+    stock_native = True           # a stock integrator's post-force update as ONE native op (False: op by op -- set_stock_native)
+
     def __init__(self, system, integrator, properties):
         import torch
         self.torch = torch
         self.system = system
+        # OpenMM's stock integrators (Verlet, Langevin, LangevinMiddle, Brownian): `self.integrator` is their step written as a
+        # CustomIntegrator program, made again whenever one of their setters invalidates it (invalidate_program)
+        self._stock = integrator if getattr(integrator, '_stock_kind', None) is not None else None
+        if self._stock is not None:
+            integrator = self._stock._program()
         self.integrator = integrator
         n = system.getNumParticles()
         if n == 0:
@@ -313,6 +320,10 @@ class Engine:
         if self.free_space and self.world > 1:
             raise InputError('a System in free space (NoCutoff / CutoffNonPeriodic) runs on a single rank: its pair forces walk all pairs '
                              'and are not sliced')
+        # (a VerletIntegrator has always been accepted on any number of ranks, where it serves static energies and minimisations:
+        # it is refused at its first step instead)
+        if self._stock is not None and self.world > 1 and self._stock._stock_kind != 0:
+            raise NotImplementedError('stock integrators run on one rank')
         if self.world > 1 and any(k == mm.CustomIntegrator.ComputePerDof and t == 'x' and 'tanh(' in e
                                   for k, t, e in getattr(integrator, '_steps', [])):
             # (the ranks' fused paths -- state exchange, sliced epilogues -- carry plain moves only)
@@ -1279,6 +1290,25 @@ class Engine:
         self._emit_memo.clear()
         self._segment_memo.clear()
         self._interpreted = None
+        if self._stock is not None:
+            self.integrator = self._stock._program()
+
+    def set_stock_native(self, on=True):
+        """Stock integrators: True (the default) runs the post-force update of a step as one AMM_OP_STOCK launch, False emits the
+        same step from the existing ops (KICK, CONSTRAIN_V, MOVE, BATH / EXPR, COPY, CONSTRAIN_X, EXPR) -- the fallback for a
+        backend without the op, and what the fused step is compared against."""
+        self.stock_native = bool(on)
+        self.invalidate_program()
+
+    def set_constraint_tolerance(self, tol):
+        """setConstraintTolerance of a bound stock integrator: the solver's tolerance lives in the library's constraint set."""
+        if self._has_constraints:
+            if hasattr(self.ctx, 'constraints_set_tolerance'):
+                self.ctx.constraints_set_tolerance(float(tol))
+            else:
+                cons = self.system._constraints
+                self.ctx.constraints_create(np.array([[c[0], c[1]] for c in cons], dtype=np.int32), np.array([c[2] for c in cons]), float(tol))
+        self.invalidate_program()
 
     def reinitialize(self, preserveState=False):
         raise NotImplementedError('Context.reinitialize: create a new Context instead')
@@ -1688,6 +1718,8 @@ class Engine:
 
     def _compile(self):
         """Unroll one outer step of the CustomIntegrator program into backend ops (host-side control flow)."""
+        if self._stock is not None and self.stock_native and hasattr(self.ctx, 'stock_define'):
+            return self._compile_stock()
         integ = self.integrator
         steps = integ._steps
         C = mm.CustomIntegrator
@@ -1767,6 +1799,27 @@ class Engine:
                 self.ctx.iso_define(False)
         finals = {name: env[name] for name in integ._gnames}
         return self._drop_dead_copies(self._pair_up_evals(ops)), valid, finals, dict(self._mirror_work)
+
+    def _compile_stock(self):
+        """The step of a stock integrator as ONE op behind the evaluation of all forces (no SAVE_REF: the launch takes the bond
+        vectors from the positions it loads).  Nothing of the op-by-op program is compiled or registered with the library."""
+        stock, integ = self._stock, self.integrator
+        valid = dict(self._valid)
+        self._mirror_work = dict(self._mirror)
+        ops = []
+        slot = self._force_ref('f', ops, valid)
+        key = ('stock', stock._stock_kind, stock._dt, stock._friction, stock._kT())
+        if key not in self._expr_ids:
+            self._expr_ids[key] = self.ctx.stock_define(stock._stock_kind, stock._dt, stock._friction, stock._kT())
+        ops.append(B.Op(B.OP_STOCK, self._expr_ids[key], slot, 0, 0.0))
+        for g in valid:
+            valid[g] = False
+        self._deriv_cache.clear()
+        if hasattr(self.ctx, 'regulated_define'):
+            self.ctx.regulated_define(False)
+        if hasattr(self.ctx, 'iso_define'):
+            self.ctx.iso_define(False)
+        return ops, valid, dict(zip(integ._gnames, integ._gvalues)), dict(self._mirror_work)
 
     _NHL_SCALE = re.compile(r'v\*exp\(-\((.+)\*dt\)\*(\w+)\)')
     _NHL_UPDATE = re.compile(r'z\*(\w+)\+sqrt\(kT\*\(1-z\*z\)/mass\)\*gaussian\+force\*\(1-z\)/\(mass\*friction\);force=m\*v\^2-kT;'
@@ -3060,7 +3113,10 @@ class Engine:
     def _step_program(self, n):
         integ = self.integrator
         if not isinstance(integ, mm.CustomIntegrator):
-            raise NotImplementedError('only CustomIntegrator step programs run on the HIP path')
+            raise NotImplementedError('the HIP path runs CustomIntegrator step programs and the stock Verlet, Langevin, LangevinMiddle '
+                                      'and Brownian integrators; %s is neither' % type(integ).__name__)
+        if self._stock is not None and self.world > 1:
+            raise NotImplementedError('stock integrators run on one rank')
         if self._seed_set != integ.getRandomNumberSeed():
             self._seed_set = integ.getRandomNumberSeed()
             self.ctx.expr_seed(self._seed_set)

@@ -736,8 +736,145 @@ class Integrator:
         self._context._engine.step(int(steps))
 
 
-class VerletIntegrator(Integrator):
-    """Leapfrog Verlet in OpenMM; here it only serves the reference's static energy checks (step size 0)."""
+class _StockIntegrator(Integrator):
+    """OpenMM's stock integrators: the engine runs their step as `EVAL ; STOCK` -- one launch for the whole post-force update
+    (csrc/stock.hip) -- or, with its `stock_native` switch off, as the CustomIntegrator program `_program` returns."""
+    _stock_kind = None              # backend.STOCK_*
+
+    def __init__(self, stepSize, temperature=0.0, frictionCoeff=0.0):
+        Integrator.__init__(self, stepSize)
+        self._temperature = float(md_value(temperature))
+        self._friction = float(md_value(frictionCoeff))
+
+    def _changed(self):
+        if self._context is not None:
+            self._context._engine.invalidate_program()
+
+    def setConstraintTolerance(self, tol):
+        Integrator.setConstraintTolerance(self, tol)
+        if self._context is not None:
+            self._context._engine.set_constraint_tolerance(self._ctol)
+
+    def setRandomNumberSeed(self, seed):
+        Integrator.setRandomNumberSeed(self, seed)
+        self._changed()
+
+    def _kT(self):
+        return _unit.BOLTZMANN_CONSTANT_kB._value * self._temperature
+
+    def _new_program(self):
+        prog = CustomIntegrator(self._dt)
+        prog._seed = self._seed
+        prog._ctol = self.getConstraintTolerance()
+        prog.addUpdateContextState()
+        return prog
+
+    @staticmethod
+    def _leapfrog_tail(prog):
+        """x0 <- x ; x <- x + dt v ; constrain ; v <- (x - x0)/dt: how the leapfrog kinds end."""
+        prog.addComputePerDof('x0', 'x')
+        prog.addComputePerDof('x', 'x+dt*v')
+        prog.addConstrainPositions()
+        prog.addComputePerDof('v', '(x-x0)/dt')
+
+
+class _ThermostatedIntegrator(_StockIntegrator):
+    def __init__(self, temperature, frictionCoeff, stepSize):
+        _StockIntegrator.__init__(self, stepSize, temperature, frictionCoeff)
+        if self._temperature < 0 or self._friction < 0:
+            raise OpenMMException('%s: the temperature and the friction coefficient must not be negative' % type(self).__name__)
+
+    def getTemperature(self):
+        return Quantity(self._temperature, _unit.kelvin)
+
+    def setTemperature(self, temperature):
+        self._temperature = float(md_value(temperature))
+        self._changed()
+
+    def getFriction(self):
+        return Quantity(self._friction, _unit.dimensionless / _unit.picosecond)
+
+    def setFriction(self, frictionCoeff):
+        self._friction = float(md_value(frictionCoeff))
+        self._changed()
+
+
+class VerletIntegrator(_StockIntegrator):
+    """openmm.VerletIntegrator(stepSize): leapfrog Verlet.  (With step size 0 it serves the reference's static energy checks.)"""
+    _stock_kind = 0
+
+    def __init__(self, stepSize):
+        _StockIntegrator.__init__(self, stepSize)
+
+    def _program(self):
+        prog = self._new_program()
+        prog.addPerDofVariable('x0', 0)
+        prog.addComputePerDof('v', 'v+dt*f/m')
+        self._leapfrog_tail(prog)
+        return prog
+
+
+class LangevinMiddleIntegrator(_ThermostatedIntegrator):
+    """openmm.LangevinMiddleIntegrator(temperature, frictionCoeff, stepSize): the LFMiddle discretisation (Zhang et al. 2019)."""
+    _stock_kind = 1
+
+    def _program(self):
+        prog = self._new_program()
+        prog.addGlobalVariable('kT', self._kT())
+        prog.addGlobalVariable('friction', self._friction)
+        prog.addPerDofVariable('x1', 0)
+        prog.addComputePerDof('v', 'v+dt*f/m')
+        prog.addConstrainVelocities()
+        prog.addComputePerDof('x', 'x+0.5*dt*v')
+        prog.addComputePerDof('v', 'z*v + sqrt(kT*(1 - z*z)/mass)*gaussian; mass=m; z=exp(-(1.0*dt)*friction)')
+        prog.addComputePerDof('x', 'x+0.5*dt*v')
+        prog.addComputePerDof('x1', 'x')
+        prog.addConstrainPositions()
+        prog.addComputePerDof('v', 'v+(x-x1)/dt')
+        return prog
+
+
+class LangevinIntegrator(_ThermostatedIntegrator):
+    """openmm.LangevinIntegrator(temperature, frictionCoeff, stepSize): the leapfrog Langevin scheme of OpenMM before 7.5's default."""
+    _stock_kind = 2
+
+    def _program(self):
+        prog = self._new_program()
+        vscale = math.exp(-self._friction * self._dt)
+        prog.addGlobalVariable('kT', self._kT())
+        prog.addGlobalVariable('vscale', vscale)
+        prog.addGlobalVariable('fscale', (1.0 - vscale) / self._friction if self._friction > 0 else self._dt)
+        prog.addPerDofVariable('x0', 0)
+        prog.addComputePerDof('v', 'vscale*v+fscale*f/m+sqrt(kT*(1-vscale*vscale)/m)*gaussian')
+        self._leapfrog_tail(prog)
+        return prog
+
+
+class BrownianIntegrator(_ThermostatedIntegrator):
+    """openmm.BrownianIntegrator(temperature, frictionCoeff, stepSize): overdamped dynamics; the velocities are (x' - x)/dt."""
+    _stock_kind = 3
+
+    def __init__(self, temperature, frictionCoeff, stepSize):
+        _ThermostatedIntegrator.__init__(self, temperature, frictionCoeff, stepSize)
+        if not self._friction > 0:
+            raise OpenMMException('BrownianIntegrator: the friction coefficient must be positive')
+
+    def setFriction(self, frictionCoeff):
+        if not float(md_value(frictionCoeff)) > 0:
+            raise OpenMMException('BrownianIntegrator: the friction coefficient must be positive')
+        _ThermostatedIntegrator.setFriction(self, frictionCoeff)
+
+    def _program(self):
+        prog = self._new_program()
+        prog.addGlobalVariable('fscale', self._dt / self._friction)
+        prog.addGlobalVariable('noisevar', 2.0 * self._kT() * self._dt / self._friction)
+        prog.addPerDofVariable('x0', 0)
+        prog.addComputePerDof('x0', 'x')
+        prog.addComputePerDof('x', 'x+fscale*f/m+sqrt(noisevar/m)*gaussian')
+        prog.addConstrainPositions()
+        prog.addComputePerDof('v', '(x-x0)/dt')
+        return prog
+
 
 
 class CustomIntegrator(Integrator):

@@ -123,8 +123,11 @@ enum {
     AMM_OP_CONSTRAIN_X = 9, /* addConstrainPositions (propagators.py:250, 1129): SHAKE along the reference bond vectors,
                                then reference <- x                                                                    */
     AMM_OP_CONSTRAIN_V = 10,/* addConstrainVelocities (propagators.py:272, 1131): RATTLE                              */
-    AMM_OP_ALLREDUCE = 11   /* buf[a] <- sum over ranks of buf[a] (RCCL, the context's own communicator: amm_comm_init):
+    AMM_OP_ALLREDUCE = 11,  /* buf[a] <- sum over ranks of buf[a] (RCCL, the context's own communicator: amm_comm_init):
                                the exchange of atom decomposition after the EVAL of a sliced group      */
+    AMM_OP_STOCK = 12       /* the whole post-force update of one step of stock integrator a (amm_stock_define) with the forces
+                               in buf[b], in ONE launch: kick, RATTLE, moves, bath, SHAKE and velocity correction per constraint
+                               cluster (or per atom of no cluster); takes one random-stream counter                     */
 };
 typedef struct {
     int32_t op, a, b, c;
@@ -276,6 +279,8 @@ int amm_expr_eval_scalar(amm_ctx *ctx, const int32_t *code, int32_t n_code, cons
  * reference's tests, tests/test_propagators.py:11-18).  Clusters of coupled constraints (<= 8 atoms, <= 16 constraints)
  * are solved by one thread each; tolerance as CustomIntegrator.getConstraintTolerance() (<= 0: 1e-5). */
 int amm_constraints_create(amm_ctx *ctx, const int32_t *h_pairs, const double *h_dist, int32_t n_constraints, double tolerance);
+/* A new tolerance for the solvers of the existing constraint set (setConstraintTolerance of a bound integrator); <= 0: 1e-5. */
+int amm_constraints_set_tolerance(amm_ctx *ctx, double tolerance);
 
 /* Register a per-DOF expression with fixed globals for AMM_OP_EXPR; amm_expr_seed sets the random stream used by the
  * ops (integrator.setRandomNumberSeed, integrators.py:149-151) and restarts its counter. */
@@ -284,6 +289,11 @@ int amm_expr_define(amm_ctx *ctx, const int32_t *code, int32_t n_code, const dou
 int amm_expr_seed(amm_ctx *ctx, uint64_t seed);
 /* z = exp(-gamma * fraction * dt), kT in kJ/mol: the constants of one Ornstein-Uhlenbeck bath step for AMM_OP_BATH. */
 int amm_bath_define(amm_ctx *ctx, double z, double kT, int32_t *bath_id);
+/* One of OpenMM's stock integrators for AMM_OP_STOCK: kind 0 Verlet (leapfrog), 1 LangevinMiddle, 2 Langevin, 3 Brownian; dt in ps,
+ * friction in 1/ps, kT in kJ/mol (csrc/stock.hip has the formulas).  Refused: an unknown kind, friction <= 0 for Brownian, a
+ * negative friction or kT, a step size of 0 (three kinds divide by it).  The op itself is refused while the isokinetic or the regulated mode is on. */
+enum { AMM_STOCK_VERLET = 0, AMM_STOCK_LANGEVIN_MIDDLE = 1, AMM_STOCK_LANGEVIN = 2, AMM_STOCK_BROWNIAN = 3 };
+int amm_stock_define(amm_ctx *ctx, int32_t kind, double dt, double friction, double kT, int32_t *stock_id);
 /* The Nose-Hoover-Langevin bath block of NHL_R_Integrator (integrators.py:272-330; MassiveNoseHooverLangevinPropagator,
  * propagators.py:1362-1449) as ONE AMM_OP_BATH: v <- v exp(-h w) ; w <- z w + sqrt(kT (1 - z^2)/Q) gaussian +
  * (m v^2 - kT)(1 - z)/(Q friction) ; v <- v exp(-h w), with the per-DOF thermostat velocities w in buffer slot `slot`
@@ -342,7 +352,8 @@ int amm_set_option(amm_ctx *ctx, const char *name, double value);
 /* What amm_run_ops fused so far (statistics for tests and bench.py): out[0] = pair-kernel launches that carried the inner RESPA loop
  * of their molecules as an epilogue (the reference runs it as CustomIntegrator steps, propagators.py:933-973), out[1] = pair
  * evaluations that found their sorted copies written by the launch that moved the atoms (no gather launch), out[2] = of out[0], the
- * launches on a rank's slice that were followed by an exchange of positions and velocities instead of forces, out[3] = 0. */
+ * launches on a rank's slice that were followed by an exchange of positions and velocities instead of forces, out[3] = scheduling
+ * decisions made so far: one per op or fused run of ops (an evaluation counts as one whatever it launches) -- not kernel launches. */
 int amm_run_stats(amm_ctx *ctx, int64_t out[4]);
 /* amm_run_ops, resumable (several ranks whose collectives the HOST makes -- torch.distributed over gloo, or RCCL outside the library):
  * starts at op *cursor of the unrolled program (repetition * n_ops + index; 0 at first) and runs to the end (*cursor = repeat * n_ops)
