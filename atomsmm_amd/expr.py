@@ -346,12 +346,16 @@ def eval_global(text, env, rng=None):
     """Value of a global expression (addComputeGlobal) for the variable values in `env`; `rng` (numpy Generator)
     supplies `gaussian` / `uniform` (one draw of each per evaluation)."""
     main, defs = split_definitions(text)
-    cache, draws = {}, {}
+    cache, draws, in_progress = {}, {}, set()
 
     def value_of(name):
         if name in defs:
             if name not in cache:
+                if name in in_progress:
+                    raise ExpressionError('circular auxiliary definition: ' + name)
+                in_progress.add(name)
                 cache[name] = ev(_parse(defs[name]))
+                in_progress.discard(name)
             return cache[name]
         if name in ('gaussian', 'uniform', 'random'):
             key = 'gaussian' if name == 'gaussian' else 'uniform'
@@ -392,6 +396,8 @@ def eval_global(text, env, rng=None):
             value = env['__deriv__'](node.args[0].id, node.args[1].id)
             return value if isinstance(value, Deferred) else float(value)
         if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id in _HOST_FUNCS and not node.keywords:
+            if len(node.args) != _ARITY.get(node.func.id, 1):
+                raise ExpressionError('unsupported function call: %s/%d' % (node.func.id, len(node.args)))
             return float(_HOST_FUNCS[node.func.id](*[ev(a) for a in node.args]))
         raise ExpressionError('unsupported syntax in expression: ' + ast.dump(node))
 
