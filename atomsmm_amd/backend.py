@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('AMM_LIB') or os.path.join(HERE, 'libatomsmm_hip.so')      # AMM_LIB: an experimental build (kernel tuning)
 
 NEAR_NONE, NEAR_SHIFT, NEAR_FSWITCH, DAMPED, NONBONDED, SOFTCORE, LJ_VIRIAL = range(7)
+PAIR_EXPR = 7      # any other CustomNonbondedForce text: compiled (expr.compile_pair) and interpreted per pair (csrc/pair_expr.hip)
 GUARD_RC0, COULOMB_EWALD, COULOMB_RF, SWITCH, NO_SHIFT, GROUP_LJ, GROUP_Q = 1, 2, 4, 8, 16, 32, 64
 FREE_SPACE = 128   # NoCutoff / CutoffNonPeriodic: all pairs, no box, no list (csrc/free.hip)
 BOND_HARMONIC, ANGLE_HARMONIC, BOND_LJC, BOND_NEAR, TORSION_PERIODIC, BOND_EWALD_EXCL = range(6)
@@ -46,6 +47,7 @@ EXPORTS = [
     'amm_min_create', 'amm_min_release', 'amm_min_begin', 'amm_min_advance', 'amm_min_trial', 'amm_min_scalars', 'amm_min_stats',
     'amm_min_read',
     'amm_set_box', 'amm_box_stats', 'amm_mol_define', 'amm_mol_scale',
+    'amm_pair_expr_create', 'amm_pair_expr_set_globals',
 ]
 
 
@@ -155,6 +157,8 @@ def lib():
         L.amm_check.argtypes = [vp]
         L.amm_pair_create.argtypes = [vp, C.POINTER(PairDesc), dp, dp, dp, ip, C.c_int32, C.c_double, ip]
         L.amm_pair_set_params.argtypes = [vp, C.c_int32, dp, dp, dp]
+        L.amm_pair_expr_create.argtypes = [vp, C.POINTER(PairDesc), ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, dp, dp, dp, ip, C.c_int32, C.c_double, ip]
+        L.amm_pair_expr_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
         L.amm_pair_share_list.argtypes = [vp, C.c_int32, C.c_int32]
         L.amm_bonded_create.argtypes = [vp, ip]
         L.amm_bonded_add_terms.argtypes = [vp, C.c_int32, C.c_int32, ip, dp, C.c_int32, C.c_int32, C.POINTER(PairDesc)]
@@ -321,6 +325,25 @@ class HipContext:
         fid = C.c_int32(-1)
         _chk(lib().amm_pair_create(self.h, C.byref(desc), qp, sp, ep, exp_, len(ex_), float(skin), C.byref(fid)))
         return fid.value
+
+    def pair_expr_create(self, desc, code, consts, globals_, p0, p1, p2, excl_pairs=None, skin=-1.0):
+        """A generic pair force (family PAIR_EXPR): the program of expr.compile_pair, the values of its globals in the program's order
+        and the three per-particle parameter slots, stored raw (None: all zero)."""
+        c_, cp = _hi(code)
+        k_, kp = _hd(consts if len(consts) else [0.0])
+        g_, gp = _hd(globals_ if len(globals_) else [0.0])
+        slots = [None if p is None else _hd(p) for p in (p0, p1, p2)]
+        assert all(s is None or len(s[0]) == self.n for s in slots)
+        ex = np.zeros((0, 2), np.int32) if excl_pairs is None else np.asarray(excl_pairs, dtype=np.int32).reshape(-1, 2)
+        ex_, exp_ = _hi(ex)
+        fid = C.c_int32(-1)
+        _chk(lib().amm_pair_expr_create(self.h, C.byref(desc), cp, len(c_), kp, len(consts), gp, len(globals_),
+                                        *[None if s is None else s[1] for s in slots], exp_, len(ex_), float(skin), C.byref(fid)))
+        return fid.value
+
+    def pair_expr_set_globals(self, fid, globals_):
+        g_, gp = _hd(globals_ if len(globals_) else [0.0])
+        _chk(lib().amm_pair_expr_set_globals(self.h, fid, gp, len(globals_)))
 
     def pair_share_list(self, fid, host_fid):
         _chk(lib().amm_pair_share_list(self.h, fid, host_fid))

@@ -6,6 +6,7 @@
 
 #include "amm_ctx.h"
 #include "cluster.h"
+#include "pair_expr_vm.h"
 
 int amm_pair_setup_grid(amm_ctx *ctx, PairForce *pf);
 static bool amm_family_allows_cluster(int family, int flags) {
@@ -257,16 +258,9 @@ static void share_buffers(PairForce *g, PairForce *h) {
     h->rnear_build = g->rlist_build;
 }
 
-int amm_pair_create(amm_ctx *ctx, const amm_pair_desc *desc, const double *h_q, const double *h_sigma,
-                    const double *h_eps, const int32_t *h_excl, int32_t n_excl, double skin, int32_t *force_id) {
-    if (!ctx || !desc || !h_q || !h_sigma || !h_eps || !force_id) {
-        amm_set_error("amm_pair_create: null argument");
-        return 1;
-    }
-    if (desc->family < AMM_NEAR_NONE || desc->family > AMM_LJ_VIRIAL) {
-        amm_set_error("amm_pair_create: unknown family");
-        return 1;
-    }
+// amm_pair_create, and amm_pair_expr_create with the program of its force (`expr`, owned by the force from here on)
+static int pair_create_common(amm_ctx *ctx, const amm_pair_desc *desc, const double *h_q, const double *h_sigma,
+                              const double *h_eps, const int32_t *h_excl, int32_t n_excl, double skin, int32_t *force_id, PairExpr *expr) {
     const bool free_space = (desc->flags & AMM_FREE_SPACE) != 0;
     if (!free_space && !ctx->has_box) {
         amm_set_error("amm_pair_create: the context has no periodic box (only AMM_FREE_SPACE pair forces run without one)");
@@ -403,6 +397,7 @@ int amm_pair_create(amm_ctx *ctx, const amm_pair_desc *desc, const double *h_q, 
     AMM_HIP(hipMemset(pf->d_ticket, 0, sizeof(int) * 4 * AMM_TICKET_INTS));
     AMM_HIP(hipMalloc(&pf->d_counters, sizeof(unsigned long long) * 8));
     AMM_HIP(hipMemset(pf->d_counters, 0, sizeof(unsigned long long) * 8));
+    pf->expr = expr;          // (the force owns the program once it is registered: amm_pair_free)
     ForceObj fo;
     fo.type = AMM_FORCE_PAIR;
     fo.pair = pf;
@@ -430,9 +425,95 @@ int amm_pair_create(amm_ctx *ctx, const amm_pair_desc *desc, const double *h_q, 
     return 0;
 }
 
+int amm_pair_create(amm_ctx *ctx, const amm_pair_desc *desc, const double *h_q, const double *h_sigma,
+                    const double *h_eps, const int32_t *h_excl, int32_t n_excl, double skin, int32_t *force_id) {
+    if (!ctx || !desc || !h_q || !h_sigma || !h_eps || !force_id) {
+        amm_set_error("amm_pair_create: null argument");
+        return 1;
+    }
+    if (desc->family == AMM_PAIR_EXPR) {
+        amm_set_error("amm_pair_create: a pair-expression force (AMM_PAIR_EXPR) comes with its program: amm_pair_expr_create");
+        return 1;
+    }
+    if (desc->family < AMM_NEAR_NONE || desc->family > AMM_LJ_VIRIAL) {
+        amm_set_error("amm_pair_create: unknown family");
+        return 1;
+    }
+    return pair_create_common(ctx, desc, h_q, h_sigma, h_eps, h_excl, n_excl, skin, force_id, nullptr);
+}
+
+// CustomNonbondedForce(any energy text): the compiled text (atomsmm_amd/expr.py: compile_pair) and the raw per-particle parameters
+int amm_pair_expr_create(amm_ctx *ctx, const amm_pair_desc *desc, const int32_t *code, int32_t ncode, const double *consts, int32_t nconst,
+                         const double *globals, int32_t nglobal, const double *h_p0, const double *h_p1, const double *h_p2,
+                         const int32_t *h_excl, int32_t n_excl, double skin, int32_t *force_id) {
+    if (!ctx || !desc || !code || !force_id || (nconst > 0 && !consts) || (nglobal > 0 && !globals)) {
+        amm_set_error("amm_pair_expr_create: null argument");
+        return 1;
+    }
+    if (desc->family != AMM_PAIR_EXPR) {
+        amm_set_error("amm_pair_expr_create: the descriptor's family must be AMM_PAIR_EXPR");
+        return 1;
+    }
+    if (desc->flags & AMM_FREE_SPACE) {
+        amm_set_error("amm_pair_expr_create: a pair-expression force (AMM_PAIR_EXPR) walks neighbour rows in a periodic box: no AMM_FREE_SPACE");
+        return 1;
+    }
+    if ((desc->flags & AMM_SWITCH) && !(desc->rswitch >= 0.0 && desc->rswitch < desc->rc)) {
+        amm_set_error("amm_pair_expr_create: the switch needs 0 <= rswitch < rc");
+        return 1;
+    }
+    if (amm_pair_expr_validate(code, ncode, nconst, nglobal)) return 1;
+    // only rc, rswitch, the switch flag and the sign are read: the other fields do not reach the constants
+    amm_pair_desc d;
+    std::memset(&d, 0, sizeof(d));
+    d.family = AMM_PAIR_EXPR;
+    d.flags = desc->flags & AMM_SWITCH;
+    d.degree = 1;
+    d.sign = desc->sign;
+    d.rc = desc->rc;
+    d.rswitch = (desc->flags & AMM_SWITCH) ? desc->rswitch : 0.0;
+    PairExpr *px = new PairExpr();
+    std::memset(&px->h, 0, sizeof(px->h));
+    px->h.ncode = ncode;
+    px->h.nconst = nconst;
+    px->h.nglobal = nglobal;
+    std::copy(code, code + ncode, px->h.code);
+    std::copy(consts, consts + nconst, px->h.consts);
+    std::copy(globals, globals + nglobal, px->h.globals);
+    if (amm_pair_expr_upload(ctx, px, false)) {
+        amm_pair_expr_free(px);
+        return 1;
+    }
+    const std::vector<double> zero(ctx->n, 0.0);          // (a NULL parameter array: all zero)
+    const size_t before = ctx->forces.size();
+    const int rc = pair_create_common(ctx, &d, h_p0 ? h_p0 : zero.data(), h_p1 ? h_p1 : zero.data(), h_p2 ? h_p2 : zero.data(), h_excl, n_excl,
+                                      skin, force_id, px);
+    if (rc && ctx->forces.size() == before) amm_pair_expr_free(px);     // (not registered: nobody else frees the program)
+    return rc;
+}
+
+int amm_pair_expr_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal) {
+    PairForce *pf = get_pair(ctx, force_id);
+    if (!pf) return 1;
+    if (!pf->expr) {
+        amm_set_error("amm_pair_expr_set_globals: not a pair-expression force (AMM_PAIR_EXPR)");
+        return 1;
+    }
+    if (nglobal != pf->expr->h.nglobal || (nglobal > 0 && !globals)) {
+        amm_set_error("amm_pair_expr_set_globals: the program reads " + std::to_string(pf->expr->h.nglobal) + " globals, " + std::to_string(nglobal) + " given");
+        return 1;
+    }
+    std::copy(globals, globals + nglobal, pf->expr->h.globals);
+    return amm_pair_expr_upload(ctx, pf->expr, true);
+}
+
 int amm_pair_set_lambda(amm_ctx *ctx, int32_t force_id, double value) {
     PairForce *pf = get_pair(ctx, force_id);
     if (!pf) return 1;
+    if (pf->expr) {
+        amm_set_error("amm_pair_set_lambda: not for a pair-expression force (AMM_PAIR_EXPR): its globals go through amm_pair_expr_set_globals");
+        return 1;
+    }
     if (pf->free_space) {
         amm_set_error("amm_pair_set_lambda: not for a free-space pair force (AMM_FREE_SPACE)");
         return 1;
@@ -449,6 +530,10 @@ int amm_pair_set_lambda(amm_ctx *ctx, int32_t force_id, double value) {
 int amm_pair_set_lambda_dev(amm_ctx *ctx, int32_t force_id, const double *d_lambda) {
     PairForce *pf = get_pair(ctx, force_id);
     if (!pf) return 1;
+    if (pf->expr) {
+        amm_set_error("amm_pair_set_lambda_dev: not for a pair-expression force (AMM_PAIR_EXPR)");
+        return 1;
+    }
     if (pf->free_space) {
         amm_set_error("amm_pair_set_lambda_dev: not for a free-space pair force (AMM_FREE_SPACE)");
         return 1;
@@ -482,6 +567,10 @@ int amm_pair_set_scale(amm_ctx *ctx, int32_t force_id, double scale) {
 int amm_pair_energy_derivative(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *d_out) {
     PairForce *pf = get_pair(ctx, force_id);
     if (!pf || !d_pos || !d_out) return 1;
+    if (pf->expr) {
+        amm_set_error("amm_pair_energy_derivative: not for a pair-expression force (AMM_PAIR_EXPR): the interpreter differentiates in r only");
+        return 1;
+    }
     if (pf->free_space) {
         amm_set_error("amm_pair_energy_derivative: not for a free-space pair force (AMM_FREE_SPACE)");
         return 1;
@@ -504,6 +593,10 @@ int amm_pair_energy_derivative(amm_ctx *ctx, int32_t force_id, const double *d_p
 int amm_pair_energy_states(amm_ctx *ctx, int32_t force_id, const double *d_pos, const double *d_lambdas, int32_t n_states, double *d_out) {
     PairForce *pf = get_pair(ctx, force_id);
     if (!pf) return 1;
+    if (pf->expr) {
+        amm_set_error("amm_pair_energy_states: not for a pair-expression force (AMM_PAIR_EXPR)");
+        return 1;
+    }
     if (pf->free_space) {
         amm_set_error("amm_pair_energy_states: not for a free-space pair force (AMM_FREE_SPACE)");
         return 1;
@@ -594,6 +687,10 @@ int amm_pair_share_list(amm_ctx *ctx, int32_t force_id, int32_t host_id) {
         amm_set_error("amm_pair_share_list: not a force of the caller's");
         return 1;
     }
+    if (g->expr || h->expr) {
+        amm_set_error("amm_pair_share_list: a pair-expression force (AMM_PAIR_EXPR) keeps a neighbour list of its own");
+        return 1;
+    }
     if (g->free_space || h->free_space) {
         amm_set_error("amm_pair_share_list: a free-space pair force (AMM_FREE_SPACE) has no neighbour list to share");
         return 1;
@@ -605,6 +702,21 @@ int amm_pair_set_params(amm_ctx *ctx, int32_t force_id, const double *h_q, const
     PairForce *pf = get_pair(ctx, force_id);
     if (!pf) return 1;
     const int n = pf->n;
+    if (pf->expr) {
+        // a pair-expression force: the program reads the three slots as the text's own per-particle parameters -- RAW values (any
+        // sign), a NULL array = all zero.  Every atom counts as a site (no row is cut short), no charge-less or one-class shortcut.
+        const std::vector<double> zero(n, 0.0);
+        AMM_HIP(hipStreamSynchronize(ctx->stream));
+        AMM_HIP(hipMemcpy(pf->d_q, h_q ? h_q : zero.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+        AMM_HIP(hipMemcpy(pf->d_hsig, h_sigma ? h_sigma : zero.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+        AMM_HIP(hipMemcpy(pf->d_seps2, h_eps ? h_eps : zero.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+        if (pf->h_cls.empty()) {
+            pf->h_cls.assign(n, 0);
+            AMM_HIP(hipMemcpy(pf->d_cls, pf->h_cls.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+        }
+        pf->a_sorted_for = nullptr;
+        return 0;
+    }
     std::vector<double> hs(n), se(n);
     for (int i = 0; i < n; ++i) {
         if (h_eps[i] < 0.0) {

@@ -66,6 +66,8 @@ struct CellGrid {
 
 struct ClusterList;   // cluster.h: molecule-row list of the force-only traversal
 struct SmallGroup;    // group.hip: interaction-group force with one small set, evaluated without a neighbour list
+struct PairExpr;      // pair_expr_vm.h: compiled energy text of a generic pair force (AMM_PAIR_EXPR)
+struct PairArgs;      // pair_args.h: launch arguments of the per-atom-row traversals
 
 struct PairForce {
     amm_pair_desc desc;
@@ -75,6 +77,7 @@ struct PairForce {
     // Hybrid list: molecule rows for the pairs of two such molecules + per-atom rows, kept by a hidden child force (`rest`, filtered to
     // the pairs that involve an atom outside the molecules), for everything else -- an ion, a solute, a chain next to the waters.
     bool hybrid = false;
+    PairExpr *expr = nullptr;      // AMM_PAIR_EXPR: the program k_pair_expr interprets (pair_expr.hip); the three parameter arrays hold RAW values
     SmallGroup *small = nullptr;   // interaction-group force whose smaller set has <= 128 atoms (group.hip): no list at all
     std::vector<int> h_excl_ptr, h_excl_idx;    // host copy of the exclusion CSR (interaction-group forces)
     PairForce *rest = nullptr;     // the child (registered in ctx->forces behind its parent, in no group)
@@ -503,6 +506,10 @@ int amm_free_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double 
 int amm_free_supported(const amm_pair_desc &d, std::string &why);     // 0 + reason: k_pair_free has no instantiation for it
 int amm_free_lanes_per_row(int n);
 #define AMM_FREE_MAX_ATOMS 32768   // an evaluation is O(n^2): about 10^9 distance tests at the limit
+// pair_expr.hip: a force of family AMM_PAIR_EXPR on the per-atom rows of pair.hip
+int amm_pair_expr_launch(amm_ctx *ctx, PairForce *pf, const PairArgs &A, dim3 grid, bool en);
+int amm_pair_expr_upload(amm_ctx *ctx, PairExpr *px, bool globals_only);
+void amm_pair_expr_free(PairExpr *px);
 // implemented in pair.hip / cells.hip / bonded.hip / integrate.hip
 int amm_pair_build_consts(const amm_pair_desc &d, PairConsts &pc);
 int amm_pair_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double *d_force, int accumulate,

@@ -22,6 +22,7 @@
 #include "bonded_terms.h"
 #include "cluster.h"
 #include "device_utils.h"
+#include "pair_args.h"
 #include "pair_math.h"
 #include "pair_tab.h"
 
@@ -773,28 +774,6 @@ __global__ void __launch_bounds__(256) k_prune(int s_begin, int s_end, int lpp_s
 // per trip with all loads issued up front (index -> position/charge -> sigma/eps gathers are the latency
 // chain; independent chains per lane + 4-6 waves per SIMD hide it), branch-free arithmetic, wavefront-shuffle
 // reduction.
-struct PairArgs {
-    int s_begin, s_end, lpa_shift, cap;
-    const int *perm;
-    const int *nl;
-    const int *nnb;        // entries at the front of the row
-    const int *nnb_total;  // if non-null: total entries; those beyond nnb[a] are stored from the back of the row
-    const double4 *posq_s;
-    const double2 *lj_s;
-    double *force;     // original order [n][3]
-    double *epart;     // per-block energy partials
-    int accumulate;
-    Box box;
-    double *gforce;    // dual evaluation: force buffer of the guest force that shares this list (same particles)
-    int gaccumulate;
-    int sorted_out;    // exchange by all-gather: rows go to force[3 (s - s_begin)] (this rank's chunk of the exchange buffer)
-    int gsame;         // the guest accumulates into the SAME rows as the host (fused FarNonbondedForce): one store of the sum
-    const int *active;     // filtered lists: the rows that hold entries (slice-relative) ...
-    const int *n_active;   // ... and their number (device); null: every row of the slice is walked
-    const int *n_long;     // ... of which this many, filed from the front of `active`, are long rows; the others sit at the back
-    int active_size;       //     of its active_size slots (amm_active_row)
-    int long_shift;        // > 0: the long rows are walked with 1 << long_shift lanes each, before the others (k_pair_tab)
-};
 
 
 // row a (0 <= a < *n_active) of a filtered list's walk: the long rows from the front of `active`, the short ones from the back
@@ -2125,6 +2104,9 @@ int amm_pair_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double 
             launch_pair<AMM_SOFTCORE, 0>(grid, block, st, false, en, A, pf->pc);
             break;
         case AMM_LJ_VIRIAL: launch_pair<AMM_LJ_VIRIAL, 0>(grid, block, st, false, en, A, pf->pc); break;
+        case AMM_PAIR_EXPR:
+            if (amm_pair_expr_launch(ctx, pf, A, grid, en)) return 1;
+            break;
         case AMM_NONBONDED:
             if (pf->pc.cmode == 1) launch_pair<AMM_NONBONDED, 1>(grid, block, st, false, en, A, pf->pc);
             else if (pf->pc.cmode == 2) launch_pair<AMM_NONBONDED, 2>(grid, block, st, false, en, A, pf->pc);
@@ -2344,6 +2326,8 @@ int amm_pair_free(PairForce *pf) {
     pf->cl = nullptr;
     if (pf->small) amm_small_group_free(pf->small);
     pf->small = nullptr;
+    amm_pair_expr_free(pf->expr);
+    pf->expr = nullptr;
     return 0;
 }
 

@@ -1,0 +1,174 @@
+// atomsmm_amd/csrc/pair_expr.hip -- generic pair force: a CustomNonbondedForce whose energy text is none of the hand-written families
+// (AMM_PAIR_EXPR), evaluated by interpreting the compiled text per pair (pair_expr_vm.h).
+//
+// Takes over what OpenMM does for any CustomNonbondedForce(energy) with CutoffPeriodic: per pair within the cutoff and not excluded,
+// the energy expression and its derivative in r (Lepton differentiates the text; here the interpreter carries d/dr along).
+//
+// k_pair_expr walks the per-atom neighbour rows of pair.hip exactly as k_pair_nlist does -- same PairArgs, lanes per atom, front / back
+// row entries, minimum image, r2 < rc2, fixed butterfly reduction, owner-computes without atomics, per-block energy partials with the
+// factor 1/2 -- one row entry per lane and trip.  The row atom's three per-particle doubles are <name>1, the neighbour's <name>2; they
+// are the RAW values of the force's per-particle parameters.  Every pair is evaluated from both rows, so the text must be symmetric
+// under 1 <-> 2 (the host checks it: engine.py).
+//
+// Layout: code, constants and globals are staged once per block in LDS (2.8 KiB) and read back wave-uniformly.  The top of each
+// lane's stack is a register pair; the 15 slots below it are the lane's column of an LDS strip (15 x 256 lanes x 16 B = 60 KiB per
+// block: two blocks per CU, two wavefronts per SIMD -- the transcendental ops of the interpreter need more than 128 VGPRs anyway); the
+// 16 locals are a private array.  DESIGN.md 3.PE has the resource figures and the measured cost.
+#include <cstring>
+
+#include "amm_ctx.h"
+#include "pair_args.h"
+#include "pair_math.h"
+#include "pair_expr_vm.h"
+
+template <bool EN>
+__global__ void __launch_bounds__(256) k_pair_expr(PairArgs A, const PairExprProg *__restrict__ prog, double rc2, double rswitch,
+                                                   double inv_sw_dr, int use_switch, double sign) {
+#pragma clang fp contract(off)
+    __shared__ int s_code[AMM_PEXPR_MAXCODE];
+    __shared__ double s_consts[AMM_PEXPR_MAXCONST];
+    __shared__ double s_globals[AMM_PEXPR_MAXGLOBAL];
+    __shared__ double2 s_stack[(AMM_PEXPR_STACK - 1) * AMM_PEXPR_STRIDE];      // all but the top of every lane's stack
+    const int ncode = prog->ncode;
+    for (int k = threadIdx.x; k < ncode; k += blockDim.x) s_code[k] = prog->code[k];
+    for (int k = threadIdx.x; k < prog->nconst; k += blockDim.x) s_consts[k] = prog->consts[k];
+    for (int k = threadIdx.x; k < prog->nglobal; k += blockDim.x) s_globals[k] = prog->globals[k];
+    __syncthreads();
+    const int lpa = 1 << A.lpa_shift;
+    const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+    const int a = tid >> A.lpa_shift;
+    const int sub = tid & (lpa - 1);
+    const int s = A.s_begin + a;
+    const bool valid = s < A.s_end;
+    double fx = 0.0, fy = 0.0, fz = 0.0, esum = 0.0;
+    if (valid) {
+        const double4 pi = A.posq_s[s];
+        const double2 li = A.lj_s[s];
+        const double pa[AMM_PEXPR_PARAMS] = {pi.w, li.x, li.y};
+        const int nfront = A.nnb[a];
+        const int nn = A.nnb_total ? A.nnb_total[a] : nfront;
+        const int *row = A.nl + (size_t)a * A.cap;
+        const int back = A.cap - 1 + nfront;
+        for (int k = sub; k < nn; k += lpa) {
+            const int j = row[k < nfront ? k : back - k];
+            const double4 pj = A.posq_s[j];
+            const double2 lj = A.lj_s[j];
+            const double dx = amm_min_image(pi.x - pj.x, A.box.L[0], A.box.invL[0]);
+            const double dy = amm_min_image(pi.y - pj.y, A.box.L[1], A.box.invL[1]);
+            const double dz = amm_min_image(pi.z - pj.z, A.box.L[2], A.box.invL[2]);
+            const double r2 = dx * dx + dy * dy + dz * dz;
+            if (r2 < rc2) {
+                const double r = sqrt(r2);
+                const double pb[AMM_PEXPR_PARAMS] = {pj.w, lj.x, lj.y};
+                double e, de;
+                pair_expr_run(s_code, ncode, s_consts, s_globals, r, pa, pb, s_stack + threadIdx.x, e, de);
+                if (use_switch && r > rswitch) {
+                    // OpenMM's built-in switch, S = 1 - 10 t^3 + 15 t^4 - 6 t^5, applied after the program
+                    const double t = (r - rswitch) * inv_sw_dr;
+                    const double S = 1.0 + (t * t * t) * (-10.0 + t * (15.0 - 6.0 * t));
+                    const double omt = 1.0 - t;
+                    const double dS = (-30.0 * (t * t) * (omt * omt)) * inv_sw_dr;
+                    de = S * de + dS * e;
+                    e = S * e;
+                }
+                const double fr = -(sign * de) / r;
+                fx += fr * dx;
+                fy += fr * dy;
+                fz += fr * dz;
+                if (EN) esum += sign * e;
+            }
+        }
+    }
+    // combine the lpa partial sums of each atom (fixed butterfly order -> deterministic)
+    for (int off = lpa >> 1; off > 0; off >>= 1) {
+        fx += __shfl_xor(fx, off);
+        fy += __shfl_xor(fy, off);
+        fz += __shfl_xor(fz, off);
+    }
+    if (valid && sub == 0) {
+        const int i = A.sorted_out ? s - A.s_begin : A.perm[s];
+        if (A.accumulate) {
+            A.force[3 * i] += fx;
+            A.force[3 * i + 1] += fy;
+            A.force[3 * i + 2] += fz;
+        } else {
+            A.force[3 * i] = fx;
+            A.force[3 * i + 1] = fy;
+            A.force[3 * i + 2] = fz;
+        }
+    }
+    if (EN) {
+        __shared__ double red[4];
+        for (int off = 32; off > 0; off >>= 1) esum += __shfl_xor(esum, off);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = esum;
+        __syncthreads();
+        if (threadIdx.x == 0) A.epart[blockIdx.x] = 0.5 * (((red[0] + red[1]) + red[2]) + red[3]);
+    }
+}
+
+// the launch of amm_pair_eval_impl for a force of family AMM_PAIR_EXPR (grid: one lane group per row of the slice, as k_pair_nlist)
+int amm_pair_expr_launch(amm_ctx *ctx, PairForce *pf, const PairArgs &A, dim3 grid, bool en) {
+    if (!pf->expr || !pf->expr->d) {
+        amm_set_error("pair-expression force (AMM_PAIR_EXPR) without a program");
+        return 1;
+    }
+    if (A.active || A.gsame) {
+        amm_set_error("pair-expression force (AMM_PAIR_EXPR): filtered rows and dual evaluation are not for this family");
+        return 1;
+    }
+    const PairConsts &c = pf->pc;
+    const int use_switch = (c.flags & AMM_SWITCH) ? 1 : 0;
+    const double inv_sw_dr = use_switch ? 1.0 / (c.rc - c.rswitch) : 0.0;
+    if (en) hipLaunchKernelGGL(k_pair_expr<true>, grid, dim3(256), 0, ctx->stream, A, pf->expr->d, c.rc2, c.rswitch, inv_sw_dr, use_switch, c.sign);
+    else hipLaunchKernelGGL(k_pair_expr<false>, grid, dim3(256), 0, ctx->stream, A, pf->expr->d, c.rc2, c.rswitch, inv_sw_dr, use_switch, c.sign);
+    return 0;
+}
+
+// ---- host: program checks, upload ----
+int amm_pair_expr_validate(const int32_t *code, int ncode, int nconst, int nglobal) {
+    auto fail = [](const std::string &what) {
+        amm_set_error("amm_pair_expr_create: " + what);
+        return 1;
+    };
+    if (ncode < 1 || ncode > AMM_PEXPR_MAXCODE) return fail("the program has " + std::to_string(ncode) + " code words (limit " + std::to_string(AMM_PEXPR_MAXCODE) + ")");
+    if (nconst < 0 || nconst > AMM_PEXPR_MAXCONST) return fail("the program has " + std::to_string(nconst) + " constants (limit " + std::to_string(AMM_PEXPR_MAXCONST) + ")");
+    if (nglobal < 0 || nglobal > AMM_PEXPR_MAXGLOBAL) return fail("the program has " + std::to_string(nglobal) + " globals (limit " + std::to_string(AMM_PEXPR_MAXGLOBAL) + ")");
+    int sp = 0;
+    for (int pc = 0; pc < ncode; ++pc) {
+        const int op = code[pc] & 0xff, arg = code[pc] >> 8;
+        int pops = 1, pushes = 1;          // (the unary functions)
+        switch (op) {
+        case X_CONST: pops = 0; if (arg < 0 || arg >= nconst) return fail("constant index out of range"); break;
+        case X_GLOBAL: pops = 0; if (arg < 0 || arg >= nglobal) return fail("global index out of range"); break;
+        case X_PAIR_R: pops = 0; break;
+        case X_PAIR_P1: case X_PAIR_P2: pops = 0; if (arg < 0 || arg >= AMM_PEXPR_PARAMS) return fail("per-particle parameter index out of range (limit " + std::to_string(AMM_PEXPR_PARAMS) + ")"); break;
+        case X_LOAD: pops = 0; if (arg < 0 || arg >= AMM_PEXPR_LOCALS) return fail("local index out of range (limit " + std::to_string(AMM_PEXPR_LOCALS) + ")"); break;
+        case X_STORE: pushes = 0; if (arg < 0 || arg >= AMM_PEXPR_LOCALS) return fail("local index out of range (limit " + std::to_string(AMM_PEXPR_LOCALS) + ")"); break;
+        case X_ADD: case X_SUB: case X_MUL: case X_DIV: case X_POW: case X_MIN: case X_MAX: case X_ATAN2: pops = 2; break;
+        case X_SELECT: pops = 3; break;
+        case X_NEG: case X_POWI: case X_SQRT: case X_EXP: case X_LOG: case X_SIN: case X_COS: case X_TAN: case X_ASIN: case X_ACOS: case X_ATAN:
+        case X_SINH: case X_COSH: case X_TANH: case X_ERF: case X_ERFC: case X_ABS: case X_FLOOR: case X_CEIL: case X_STEP: case X_DELTA: break;
+        default: return fail("opcode " + std::to_string(op) + " is not a pair-expression op");
+        }
+        if (sp < pops) return fail("stack underflow at word " + std::to_string(pc));
+        sp += pushes - pops;
+        if (sp > AMM_PEXPR_STACK) return fail("stack depth exceeds " + std::to_string(AMM_PEXPR_STACK));
+    }
+    if (sp != 1) return fail("the program leaves " + std::to_string(sp) + " values on the stack (one expected)");
+    return 0;
+}
+
+int amm_pair_expr_upload(amm_ctx *ctx, PairExpr *px, bool globals_only) {
+    // ordered after any kernel already queued on the stream that reads the old program
+    AMM_HIP(hipStreamSynchronize(ctx->stream));
+    if (!px->d) AMM_HIP(hipMalloc(&px->d, sizeof(PairExprProg)));
+    if (globals_only) AMM_HIP(hipMemcpy(px->d->globals, px->h.globals, sizeof(px->h.globals), hipMemcpyHostToDevice));
+    else AMM_HIP(hipMemcpy(px->d, &px->h, sizeof(PairExprProg), hipMemcpyHostToDevice));
+    return 0;
+}
+
+void amm_pair_expr_free(PairExpr *px) {
+    if (!px) return;
+    if (px->d) (void)hipFree(px->d);
+    delete px;
+}

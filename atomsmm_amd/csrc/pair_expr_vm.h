@@ -1,0 +1,202 @@
+// atomsmm_amd/csrc/pair_expr_vm.h -- the pair-expression interpreter (device side) of k_pair_expr (pair_expr.hip): the energy text of
+// a CustomNonbondedForce that is none of the hand-written families, compiled by atomsmm_amd/expr.py (compile_pair) into the postfix
+// code of expr_vm.h, evaluated per pair together with its derivative in r.
+//
+// Forward mode: every stack slot and every local is a pair (value, d/dr).  X_PAIR_R pushes (r, 1); constants, globals and the
+// per-particle parameters push (x, 0), so that a mixing rule -- a definition without r -- carries a zero derivative through every
+// op on its own.  The chain rule goes through pexpr_chain: a factor whose operand has derivative exactly zero contributes an exact
+// zero whatever f'(x) is (sqrt(eps1*eps2) at eps = 0 has f' = inf; the pair's energy does not depend on r through it).
+// Discontinuous ops follow Lepton: step, delta, floor, ceil have derivative 0, abs takes the sign of its operand, min / max / select
+// carry the derivative of the operand they return.
+#pragma once
+#include "expr_vm.h"
+
+#define AMM_PEXPR_MAXCODE 256
+#define AMM_PEXPR_MAXCONST 48
+#define AMM_PEXPR_MAXGLOBAL 48
+#define AMM_PEXPR_STACK 16
+#define AMM_PEXPR_LOCALS 16
+#define AMM_PEXPR_PARAMS 3          // per-particle doubles a neighbour row carries per atom (charge slot, two Lennard-Jones slots)
+
+// opcodes beside those of expr_vm.h (X_BUF, X_MASS, X_GAUSS, X_UNIFORM, X_DEVG, X_OUT and X_HORNER are not pair ops)
+enum { X_PAIR_R = 50, X_PAIR_P1 = 51, X_PAIR_P2 = 52 };
+
+// the compiled text as the device holds it: staged into LDS once per block
+struct PairExprProg {
+    int ncode, nconst, nglobal, pad_;
+    int code[AMM_PEXPR_MAXCODE];            // opcode | arg << 8
+    double consts[AMM_PEXPR_MAXCONST];
+    double globals[AMM_PEXPR_MAXGLOBAL];
+};
+
+// host side of a generic pair force (PairForce::expr)
+struct PairExpr {
+    PairExprProg h;
+    PairExprProg *d = nullptr;
+};
+
+// non-zero + message naming the limit that a program exceeds, or a word that is no pair op / leaves the stack or the locals
+int amm_pair_expr_validate(const int32_t *code, int ncode, int nconst, int nglobal);
+
+#ifdef __HIPCC__
+__device__ __forceinline__ double pexpr_chain(double fprime, double xd) { return xd == 0.0 ? 0.0 : fprime * xd; }
+
+__device__ __forceinline__ double pexpr_powi(double b, int n) {
+#pragma clang fp contract(off)
+    int e = n < 0 ? -n : n;
+    double r = 1.0, q = b;
+    while (e) {
+        if (e & 1) r *= q;
+        q *= q;
+        e >>= 1;
+    }
+    return n < 0 ? 1.0 / r : r;
+}
+
+// The transcendental ops are CALLED, one copy per kernel (as expr_run is): inlined into the dispatch loop, the constants of their
+// polynomials are hoisted out of it and stay live across every op (388 registers, one wavefront per SIMD).  (f(x), f'(x)):
+static __device__ __noinline__ double2 pexpr_fn(int op, double x) {
+#pragma clang fp contract(off)
+    double v = 0.0, fp = 0.0;
+    switch (op) {
+    case X_EXP: v = exp(x); fp = v; break;
+    case X_LOG: v = log(x); fp = 1.0 / x; break;
+    case X_SIN: v = sin(x); fp = cos(x); break;
+    case X_COS: v = cos(x); fp = -sin(x); break;
+    case X_TAN: v = tan(x); fp = 1.0 + v * v; break;
+    case X_ASIN: v = asin(x); fp = 1.0 / sqrt(1.0 - x * x); break;
+    case X_ACOS: v = acos(x); fp = -1.0 / sqrt(1.0 - x * x); break;
+    case X_ATAN: v = atan(x); fp = 1.0 / (1.0 + x * x); break;
+    case X_SINH: v = sinh(x); fp = cosh(x); break;
+    case X_COSH: v = cosh(x); fp = sinh(x); break;
+    case X_TANH: v = tanh(x); fp = 1.0 - v * v; break;
+    case X_ERF: v = erf(x); fp = 1.1283791670955125739 * exp(-(x * x)); break;
+    case X_ERFC: v = erfc(x); fp = -(1.1283791670955125739 * exp(-(x * x))); break;
+    default: break;
+    }
+    return make_double2(v, fp);
+}
+// (a^b, d/da, d/db) of the general power: b a^(b-1) and a^b log a
+static __device__ __noinline__ double3 pexpr_pow(double a, double b, bool with_log) {
+#pragma clang fp contract(off)
+    const double v = pow(a, b);
+    return make_double3(v, b * pow(a, b - 1.0), with_log ? v * log(a) : 0.0);
+}
+static __device__ __noinline__ double pexpr_atan2(double y, double x) { return atan2(y, x); }
+
+// E(r) and dE/dr of one pair.  code / consts / globals: the block's LDS copies; pa / pb: the parameters of the row atom (<name>1) and
+// of the neighbour (<name>2).  The program is the same for every lane, so the word is made scalar (readfirstlane) and the dispatch is
+// a scalar branch.  The top of the stack lives in registers (tv, td): a unary op touches no memory, a binary op reads one slot.  The
+// elements below it are the lane's column of an LDS strip -- st[k * AMM_PEXPR_STRIDE], one (value, d/dr) record of 16 bytes per
+// slot, neighbouring lanes in neighbouring records (conflict-free) -- and the locals are a private array.
+#define AMM_PEXPR_STRIDE 256        // lanes per block of k_pair_expr: slot k of lane t is s_stack[k * 256 + t]
+__device__ __forceinline__ void pair_expr_run(const int *code, int ncode, const double *consts, const double *globals, double r,
+                                              const double *pa, const double *pb, double2 *st, double &E, double &dE) {
+#pragma clang fp contract(off)
+    double lv[AMM_PEXPR_LOCALS], ld[AMM_PEXPR_LOCALS];
+    double tv = 0.0, td = 0.0;
+    int sp = 0;                     // elements on the stack: 0 .. sp - 2 in the strip, sp - 1 in (tv, td)
+#define PEXPR_PUSH(V, D)                                                  \
+    do {                                                                  \
+        const double v_ = (V), d_ = (D);                                  \
+        if (sp) st[(sp - 1) * AMM_PEXPR_STRIDE] = make_double2(tv, td);   \
+        tv = v_;                                                          \
+        td = d_;                                                          \
+        ++sp;                                                             \
+    } while (0)
+#define PEXPR_UNARY(VALUE, FPRIME)                 \
+    do {                                           \
+        const double x = tv;                       \
+        const double v = (VALUE);                  \
+        (void)x;                                   \
+        td = pexpr_chain((FPRIME), td);            \
+        tv = v;                                    \
+    } while (0)
+    for (int pc = 0; pc < ncode; ++pc) {
+        const int word = __builtin_amdgcn_readfirstlane(code[pc]), op = word & 0xff, arg = word >> 8;
+        switch (op) {
+        case X_CONST: PEXPR_PUSH(consts[arg], 0.0); break;
+        case X_GLOBAL: PEXPR_PUSH(globals[arg], 0.0); break;
+        case X_PAIR_R: PEXPR_PUSH(r, 1.0); break;
+        case X_PAIR_P1: PEXPR_PUSH(arg == 0 ? pa[0] : (arg == 1 ? pa[1] : pa[2]), 0.0); break;
+        case X_PAIR_P2: PEXPR_PUSH(arg == 0 ? pb[0] : (arg == 1 ? pb[1] : pb[2]), 0.0); break;
+        case X_LOAD: PEXPR_PUSH(lv[arg], ld[arg]); break;
+        case X_STORE: {
+            lv[arg] = tv;
+            ld[arg] = td;
+            --sp;
+            if (sp) {
+                const double2 t = st[(sp - 1) * AMM_PEXPR_STRIDE];
+                tv = t.x;
+                td = t.y;
+            }
+        } break;
+        case X_ADD: case X_SUB: case X_MUL: case X_DIV: case X_POW: case X_MIN: case X_MAX: case X_ATAN2: {
+            const double2 lhs = st[(sp - 2) * AMM_PEXPR_STRIDE];
+            const double a = lhs.x, ad = lhs.y, b = tv, bd = td;
+            --sp;
+            if (op == X_ADD) {
+                tv = a + b;
+                td = ad + bd;
+            } else if (op == X_SUB) {
+                tv = a - b;
+                td = ad - bd;
+            } else if (op == X_MUL) {
+                tv = a * b;
+                td = pexpr_chain(b, ad) + pexpr_chain(a, bd);
+            } else if (op == X_DIV) {
+                const double q = a / b;
+                tv = q;
+                td = (ad == 0.0 && bd == 0.0) ? 0.0 : (ad - pexpr_chain(q, bd)) / b;
+            } else if (op == X_POW) {
+                // b' = 0: b a^(b-1) a'; else the full form, the term in log a taken only then (a <= 0: the value is what pow gives)
+                const double3 p = pexpr_pow(a, b, bd != 0.0);
+                double d = pexpr_chain(p.y, ad);
+                if (bd != 0.0) d = d + p.z * bd;
+                tv = p.x;
+                td = d;
+            } else if (op == X_MIN) {
+                td = a <= b ? ad : bd;
+                tv = fmin(a, b);
+            } else if (op == X_MAX) {
+                td = a >= b ? ad : bd;
+                tv = fmax(a, b);
+            } else {        // atan2(a, b)
+                tv = pexpr_atan2(a, b);
+                td = (ad == 0.0 && bd == 0.0) ? 0.0 : (b * ad - a * bd) / (b * b + a * a);
+            }
+        } break;
+        case X_SELECT: {
+            const double2 c = st[(sp - 3) * AMM_PEXPR_STRIDE], a = st[(sp - 2) * AMM_PEXPR_STRIDE];
+            sp -= 2;
+            const bool first = c.x != 0.0;
+            tv = first ? a.x : tv;
+            td = first ? a.y : td;
+        } break;
+        case X_NEG: tv = -tv; td = -td; break;
+        case X_POWI: {
+            const double x = tv;
+            tv = pexpr_powi(x, arg);
+            td = arg == 0 ? 0.0 : pexpr_chain((double)arg * pexpr_powi(x, arg - 1), td);
+        } break;
+        case X_SQRT: PEXPR_UNARY(sqrt(x), 0.5 / v); break;
+        case X_EXP: case X_LOG: case X_SIN: case X_COS: case X_TAN: case X_ASIN: case X_ACOS: case X_ATAN: case X_SINH: case X_COSH:
+        case X_TANH: case X_ERF: case X_ERFC: {
+            const double2 f = pexpr_fn(op, tv);
+            tv = f.x;
+            td = pexpr_chain(f.y, td);
+        } break;
+        case X_ABS: td = tv >= 0.0 ? td : -td; tv = fabs(tv); break;
+        case X_FLOOR: tv = floor(tv); td = 0.0; break;
+        case X_CEIL: tv = ceil(tv); td = 0.0; break;
+        case X_STEP: tv = tv >= 0.0 ? 1.0 : 0.0; td = 0.0; break;
+        case X_DELTA: tv = tv == 0.0 ? 1.0 : 0.0; td = 0.0; break;
+        default: break;
+        }
+    }
+#undef PEXPR_PUSH
+#undef PEXPR_UNARY
+    E = tv;
+    dE = td;
+}
+#endif

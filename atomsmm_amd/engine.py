@@ -239,6 +239,8 @@ class _Entry:
         self.update = None          # callable(parameters) refreshing lambda-dependent parameters
         self.softcore = None        # softcore pair force: dict(pid, lambda_name, constant, depends)
         self.depends = set()        # global parameters this entry's backend data depend on
+        self.pair_expr = False      # a CustomNonbondedForce on the pair-expression kernel (generic energy text) ...
+        self.program = None         # ... and its compiled program (expr.compile_pair)
 
 
 def slice_bounds(n_items, rank, world):
@@ -835,7 +837,99 @@ class Engine:
             flags |= B.NO_SHIFT
         return B.pair_desc(_FAMILY[family], rc, rc0=rc0, rs0=rs0, flags=flags, sign=d.get('sign', 1.0), Kc=d.get('Kc', B.KC))
 
+    @staticmethod
+    def check_pair_symmetry(text, per_particle_names, global_values, samples=6, seed=20240607):
+        """A pair is evaluated from both atoms' rows and counted once (csrc/pair_expr.hip), so the text must not change when the
+        particles swap: evaluate it on the host at a handful of seeded random (r, parameters of 1, parameters of 2) and at the
+        swapped parameters.  OpenMM leaves an asymmetric text undefined (which atom is 1 depends on its neighbour list)."""
+        rng = np.random.default_rng(seed)
+        for _ in range(samples):
+            r = float(rng.uniform(0.3, 1.2))
+            one = {nm: float(rng.uniform(0.2, 1.5)) for nm in per_particle_names}
+            two = {nm: float(rng.uniform(0.2, 1.5)) for nm in per_particle_names}
+            env = dict(global_values, r=r)
+            fwd = dict(env, **{nm + '1': one[nm] for nm in per_particle_names}, **{nm + '2': two[nm] for nm in per_particle_names})
+            swp = dict(env, **{nm + '1': two[nm] for nm in per_particle_names}, **{nm + '2': one[nm] for nm in per_particle_names})
+            try:
+                a, b = X.eval_global(text, fwd), X.eval_global(text, swp)
+            except (ArithmeticError, ValueError) as exc:
+                if isinstance(exc, X.ExpressionError):
+                    raise
+                continue               # (outside the text's domain at this draw: says nothing about symmetry)
+            if not abs(a - b) <= 1e-12 * max(abs(a), abs(b), 1e-300):      # (a few roundings of operations taken in another order)
+                raise InputError('energy expression is not symmetric in particles 1 and 2')
+
+    def _translate_pair_expression(self, force, entry):
+        """A CustomNonbondedForce whose energy text is none of the AtomsMM families: compiled here (expr.compile_pair) and interpreted
+        per pair, with its derivative in r, by the pair-expression kernel (csrc/pair_expr.hip) on per-atom neighbour rows."""
+        text = force.getEnergyFunction()
+        # (what the generic kernel leaves out is said together with why the force came here)
+        generic = 'energy expression not recognised as one of the AtomsMM families (%s); the generic pair-expression kernel ' % text.split(';')[0]
+        if getattr(force, '_derivs', None):
+            raise NotImplementedError(generic + 'differentiates in r only: no addEnergyParameterDerivative')
+        if self.free_space or force.getNonbondedMethod() != force.CutoffPeriodic:
+            raise NotImplementedError(generic + 'evaluates with CutoffPeriodic only (not NoCutoff / CutoffNonPeriodic)')
+        if self.world > 1:
+            raise NotImplementedError(generic + 'runs on a single rank')
+        if force.getNumInteractionGroups() > 0:
+            raise NotImplementedError(generic + 'takes no interaction groups')
+        if force.getUseLongRangeCorrection():
+            raise NotImplementedError(generic + 'computes no long-range correction')
+        names = [force.getPerParticleParameterName(k) for k in range(force.getNumPerParticleParameters())]
+        if len(names) > X.PAIR_MAX_PARAMS:
+            raise InputError(generic + 'takes at most %d per-particle parameters (%d given): a neighbour row carries three doubles '
+                             'per atom' % (X.PAIR_MAX_PARAMS, len(names)))
+        gnames = [force.getGlobalParameterName(k) for k in range(force.getNumGlobalParameters())]
+        try:
+            prog = X.compile_pair(text, names, gnames)
+        except X.ExpressionError as exc:
+            raise InputError('energy expression not recognised by the HIP path as one of the AtomsMM families, and not a pair '
+                             'expression the generic kernel can run: %s' % exc)
+        self.check_pair_symmetry(text, names, {g: self.parameters[g] for g in prog.globals_})
+        n = self.n
+        if force.getNumParticles() != n:
+            raise mm.OpenMMException('CustomNonbondedForce must have exactly as many particles as the System')
+
+        def slots():
+            allp = np.array(force._particles, dtype=np.float64).reshape(n, -1)
+            if allp.shape[1] != len(names):
+                raise mm.OpenMMException('CustomNonbondedForce: every particle needs %d parameters' % len(names))
+            return [np.ascontiguousarray(allp[:, k]) if k < len(names) else np.zeros(n) for k in range(3)]
+
+        rc = force._cutoff
+        use_switch = force.getUseSwitchingFunction()
+        if use_switch and not (0.0 <= force._switch < rc):
+            raise mm.OpenMMException('CustomNonbondedForce: the switching distance must lie between 0 and the cutoff')
+        desc = B.pair_desc(B.PAIR_EXPR, rc, rswitch=force._switch if use_switch else 0.0, flags=B.SWITCH if use_switch else 0)
+        excl = np.array(force._exclusions, dtype=np.int32).reshape(-1, 2)
+        pid = self.ctx.pair_expr_create(desc, prog.code, prog.consts, [self.parameters[g] for g in prog.globals_], *slots(), excl,
+                                        skin=self.skin)
+        self._pair_info[pid] = (float(rc), ('expr', pid))       # (a list of its own: never host or guest of a shared one)
+        entry.pair_ids.append(pid)
+        entry.pair_expr = True
+        entry.program = prog
+
+        def reload():          # updateParametersInContext: the per-particle parameters are read again
+            self.ctx.pair_set_params(pid, *slots())
+            return 'values'
+        entry.reload = reload
+        if prog.globals_:
+            depends = set(prog.globals_)
+
+            def update(parameters, changed):
+                if not (depends & changed):
+                    return False
+                self.ctx.pair_expr_set_globals(pid, [parameters[g] for g in prog.globals_])
+                return 'values'
+            entry.update = update
+            entry.depends = depends
+
     def _translate_custom_nonbonded(self, force, entry):
+        if getattr(force, '_amm', None) is None:
+            globs = {force.getGlobalParameterName(i): force.getGlobalParameterDefaultValue(i)
+                     for i in range(force.getNumGlobalParameters())}
+            if describe_energy(force.getEnergyFunction(), globs) is None:
+                return self._translate_pair_expression(force, entry)
         d = dict(self._descriptor_of(force))
         if d['family'] == 'ljc':
             raise InputError('the LJC exception expression belongs in a CustomBondForce')
@@ -2579,6 +2673,9 @@ class Engine:
                     self._allreduce(out)
                 total += out.item() + sc['constant_derivative'](self.parameters)
             elif name in getattr(entry, 'depends', ()):
+                if getattr(entry, 'pair_expr', False):
+                    raise NotImplementedError('deriv(energy, %s) of a CustomNonbondedForce with a generic energy expression (the '
+                                              'pair-expression kernel differentiates in r only)' % name)
                 if entry.update is None:
                     raise NotImplementedError('deriv(energy, %s): the force that depends on it cannot be re-parameterised' % name)
                 by_difference.append(entry)

@@ -18,8 +18,13 @@ OPCODES = dict(
     ADD=10, SUB=11, MUL=12, DIV=13, NEG=14, POW=15, POWI=16,
     sqrt=20, exp=21, log=22, sin=23, cos=24, tan=25, asin=26, acos=27, atan=28, sinh=29, cosh=30, tanh=31, erf=32,
     erfc=33, abs=34, floor=35, ceil=36, step=37, delta=38, min=39, max=40, select=41, atan2=42, HORNER=43)
+# the words only a pair expression has (compile_pair; csrc/pair_expr_vm.h), beside those of OPCODES that it shares
+PAIR_OPCODES = dict(PAIR_R=50, PAIR_P1=51, PAIR_P2=52)
+ALL_OPCODES = dict(OPCODES, **PAIR_OPCODES)
 _ARITY = {'min': 2, 'max': 2, 'select': 3, 'atan2': 2}
 MAX_LOCALS = 16
+# limits of a pair-expression program (csrc/pair_expr_vm.h)
+PAIR_MAX_CODE, PAIR_MAX_CONSTS, PAIR_MAX_GLOBALS, PAIR_MAX_STACK, PAIR_MAX_LOCALS, PAIR_MAX_PARAMS = 256, 48, 48, 16, 16, 3
 
 
 class ExpressionError(ValueError):
@@ -136,7 +141,7 @@ class Program:
         self.code, self.consts, self.globals_ = [], [], []
 
     def emit(self, op, arg=0):
-        self.code.append(OPCODES[op] | (int(arg) << 8))
+        self.code.append(ALL_OPCODES[op] | (int(arg) << 8))
 
     def const(self, value):
         value = float(value)
@@ -152,29 +157,99 @@ class Program:
         return self.globals_.index(name)
 
 
-def compile_per_dof(text, resolve):
-    """Compile a per-DOF (or sum) expression.  `resolve(name)` returns ('buf', slot), ('mass',), ('global',) or None."""
+def _folded_trees(main, defs):
+    """Syntax trees of the main expression and of the definitions with every subexpression of literals -- and of definitions that
+    come down to a literal, `b = 2.5` -- replaced by its value in double arithmetic (what Lepton's optimiser does to a
+    CustomNonbondedForce text): the coefficients of a force-switched potential are polynomials in such a `b`.  New nodes: the cached
+    trees of _parse are not touched."""
+    memo, busy = {}, set()
+
+    def definition(name):
+        if name not in memo:
+            if name in busy:
+                raise ExpressionError('circular auxiliary definition: ' + name)
+            busy.add(name)
+            memo[name] = fold(_parse(defs[name]))
+            busy.discard(name)
+        return memo[name]
+
+    def number(node):
+        return isinstance(node, ast.Constant) and isinstance(node.value, (int, float))
+
+    def fold(node):
+        if isinstance(node, ast.Name):
+            if node.id in defs:
+                tree = definition(node.id)
+                return tree if number(tree) else node
+            return node
+        if isinstance(node, ast.UnaryOp) and isinstance(node.op, (ast.USub, ast.UAdd)):
+            operand = fold(node.operand)
+            if number(operand):
+                return ast.Constant(value=-float(operand.value) if isinstance(node.op, ast.USub) else float(operand.value))
+            return ast.UnaryOp(op=node.op, operand=operand)
+        if isinstance(node, ast.BinOp):
+            left, right = fold(node.left), fold(node.right)
+            if number(left) and number(right):
+                a, b = float(left.value), float(right.value)
+                try:
+                    if isinstance(node.op, ast.Pow) and b == int(b) and abs(b) < 1 << 20:
+                        q, value, e = a, 1.0, abs(int(b))          # as the interpreters take an integer power
+                        while e:
+                            if e & 1:
+                                value *= q
+                            q *= q
+                            e >>= 1
+                        value = 1.0 / value if b < 0 else value
+                    else:
+                        value = {ast.Add: lambda: a + b, ast.Sub: lambda: a - b, ast.Mult: lambda: a * b, ast.Div: lambda: a / b,
+                                 ast.Pow: lambda: math.pow(a, b)}[type(node.op)]()
+                    return ast.Constant(value=float(value))
+                except (KeyError, ArithmeticError, ValueError):
+                    pass               # (left to the device, which has an answer for 1/0)
+            return ast.BinOp(left=left, op=node.op, right=right)
+        if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and not node.keywords:
+            args = [fold(a) for a in node.args]
+            if node.func.id in _HOST_FUNCS and len(args) == _ARITY.get(node.func.id, 1) and all(number(a) for a in args):
+                try:
+                    return ast.Constant(value=float(_HOST_FUNCS[node.func.id](*[float(a.value) for a in args])))
+                except (ArithmeticError, ValueError):
+                    pass
+            return ast.Call(func=node.func, args=args, keywords=[])
+        return node
+
+    return fold(_parse(main)), definition
+
+
+def compile_per_dof(text, resolve, what='per-DOF', random_ok=True, fold=False):
+    """Compile a per-DOF (or sum) expression.  `resolve(name)` returns ('buf', slot), ('mass',), ('global',), ('op', opcode name, arg)
+    or None.  `what` names the kind of expression in error messages; random_ok=False: `gaussian` / `uniform` are errors; fold=True:
+    subexpressions of literals are evaluated here (_folded_trees)."""
     main, defs = split_definitions(text)
     prog = Program()
     local_of, in_progress = {}, set()
+    main_tree, tree_of = (_folded_trees(main, defs) if fold else (_parse(main), lambda name: _parse(defs[name])))
 
     def gen(node):
         if isinstance(node, ast.Constant) and isinstance(node.value, (int, float)):
             prog.emit('CONST', prog.const(node.value))
         elif isinstance(node, ast.Name):
             name = node.id
-            if name in defs:
+            if name in defs and fold and isinstance(tree_of(name), ast.Constant):
+                prog.emit('CONST', prog.const(tree_of(name).value))
+            elif name in defs:
                 if name not in local_of:
                     if name in in_progress:
                         raise ExpressionError('circular auxiliary definition: ' + name)
                     if len(local_of) + len(in_progress) >= MAX_LOCALS:
                         raise ExpressionError('too many auxiliary definitions')
                     in_progress.add(name)
-                    gen(_parse(defs[name]))
+                    gen(tree_of(name))
                     in_progress.discard(name)
                     local_of[name] = len(local_of)
                     prog.emit('STORE', local_of[name])
                 prog.emit('LOAD', local_of[name])
+            elif name in ('gaussian', 'uniform', 'random') and not random_ok:
+                raise ExpressionError('random numbers (%s) are not defined in a %s expression' % (name, what))
             elif name == 'gaussian':
                 prog.emit('GAUSS')
             elif name in ('uniform', 'random'):
@@ -182,8 +257,10 @@ def compile_per_dof(text, resolve):
             else:
                 kind = resolve(name)
                 if kind is None:
-                    raise ExpressionError('unknown symbol in per-DOF expression: ' + name)
-                if kind[0] == 'buf':
+                    raise ExpressionError('unknown symbol in %s expression: %s' % (what, name))
+                if kind[0] == 'op':
+                    prog.emit(kind[1], kind[2])
+                elif kind[0] == 'buf':
                     prog.emit('BUF', kind[1])
                 elif kind[0] == 'mass':
                     prog.emit('MASS')
@@ -215,7 +292,53 @@ def compile_per_dof(text, resolve):
         else:
             raise ExpressionError('unsupported syntax in expression: ' + ast.dump(node))
 
-    gen(_parse(main))
+    gen(main_tree)
+    return prog
+
+
+_STACK_EFFECT = {'CONST': 1, 'GLOBAL': 1, 'PAIR_R': 1, 'PAIR_P1': 1, 'PAIR_P2': 1, 'LOAD': 1, 'STORE': -1, 'ADD': -1, 'SUB': -1, 'MUL': -1,
+                 'DIV': -1, 'POW': -1, 'min': -1, 'max': -1, 'atan2': -1, 'select': -2}
+
+
+def compile_pair(text, per_particle_names, global_names):
+    """Compile the energy text of a CustomNonbondedForce for the pair-expression kernel (csrc/pair_expr.hip): `r` is PAIR_R, the row
+    atom's parameter `<name>1` is PAIR_P1 k and the neighbour's `<name>2` PAIR_P2 k (k: position in per_particle_names), a global
+    parameter GLOBAL k (k: position in the program's globals_); auxiliary definitions, in any order, become locals.  The limits of
+    csrc/pair_expr_vm.h are enforced here, each with an ExpressionError that names it."""
+    per_particle_names, global_names = list(per_particle_names), set(global_names)
+    if len(per_particle_names) > PAIR_MAX_PARAMS:
+        raise ExpressionError('a pair expression takes at most %d per-particle parameters (%d given)' % (PAIR_MAX_PARAMS, len(per_particle_names)))
+    slots = {}
+    for k, name in enumerate(per_particle_names):
+        slots[name + '1'] = ('op', 'PAIR_P1', k)
+        slots[name + '2'] = ('op', 'PAIR_P2', k)
+
+    def resolve(name):
+        if name == 'r':
+            return ('op', 'PAIR_R', 0)
+        if name in slots:
+            return slots[name]
+        return ('global',) if name in global_names else None
+
+    try:
+        prog = compile_per_dof(text, resolve, what='pair', random_ok=False, fold=True)
+    except ExpressionError as exc:
+        if 'too many auxiliary definitions' in str(exc):
+            raise ExpressionError('pair expression: more than %d auxiliary definitions (locals)' % PAIR_MAX_LOCALS)
+        raise
+    if len(prog.code) > PAIR_MAX_CODE:
+        raise ExpressionError('pair expression: %d code words (limit %d)' % (len(prog.code), PAIR_MAX_CODE))
+    if len(prog.consts) > PAIR_MAX_CONSTS:
+        raise ExpressionError('pair expression: %d constants (limit %d)' % (len(prog.consts), PAIR_MAX_CONSTS))
+    if len(prog.globals_) > PAIR_MAX_GLOBALS:
+        raise ExpressionError('pair expression: %d global parameters (limit %d)' % (len(prog.globals_), PAIR_MAX_GLOBALS))
+    names = {v: k for k, v in ALL_OPCODES.items()}
+    depth = deepest = 0
+    for word in prog.code:
+        depth += _STACK_EFFECT.get(names[word & 0xff], 0)
+        deepest = max(deepest, depth)
+    if deepest > PAIR_MAX_STACK:
+        raise ExpressionError('pair expression: stack depth %d (limit %d)' % (deepest, PAIR_MAX_STACK))
     return prog
 
 

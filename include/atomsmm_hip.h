@@ -48,8 +48,11 @@ enum {
                                (systems.py:266-272).  lambda = desc.alpha; the charge array carries the set of
                                each atom (1, 2, 0 = neither; use Kc = 1): a pair counts iff the codes multiply
                                to 2; AMM_SWITCH = OpenMM's built-in switch imported with the cutoff            */
-    AMM_LJ_VIRIAL = 6       /* ComputingSystem's dispersion virial as an energy, 24 eps (2 (sigma/r)^12 - (sigma/r)^6)
+    AMM_LJ_VIRIAL = 6,      /* ComputingSystem's dispersion virial as an energy, 24 eps (2 (sigma/r)^12 - (sigma/r)^6)
                                (systems.py:894), AMM_SWITCH as imported                                        */
+    AMM_PAIR_EXPR = 7       /* any other energy text of a CustomNonbondedForce, compiled by the host and interpreted per
+                               pair together with its derivative in r (csrc/pair_expr.hip); created by
+                               amm_pair_expr_create only.  AMM_SWITCH = OpenMM's built-in switch rswitch -> rc      */
 };
 enum {
     AMM_GUARD_RC0 = 1,      /* energy *= step(rc0 - r)         forces.py:661, 714 ; systems.py:73      */
@@ -196,6 +199,22 @@ int amm_pair_create(amm_ctx *ctx, const amm_pair_desc *desc, const double *h_q, 
  * (forces.py:247-258, 292-309: charge+lambda*chargeScale ...). Effective values are passed. */
 int amm_pair_set_params(amm_ctx *ctx, int32_t force_id, const double *h_q, const double *h_sigma,
                         const double *h_eps);
+/* CustomNonbondedForce(energy) with ANY energy text + addPerParticleParameter / addGlobalParameter + addParticle + addExclusion,
+ * CutoffPeriodic (what OpenMM compiles with Lepton; the reference's forces are the texts amm_pair_create knows by family).
+ * desc->family = AMM_PAIR_EXPR; only rc, rswitch, flags & AMM_SWITCH and sign are read (AMM_FREE_SPACE: non-zero).  code / consts /
+ * globals: the program of atomsmm_amd.expr.compile_pair -- postfix words opcode | arg << 8 over r (opcode 50), the row atom's
+ * parameters <name>1 (51, arg = slot), the neighbour's <name>2 (52), constants (0), globals (1), locals (6 / 7) and the arithmetic
+ * and function opcodes of csrc/expr_vm.h; at most 256 words, 48 constants, 48 globals, stack depth 16, 16 locals (csrc/pair_expr_vm.h),
+ * checked here.  h_p0..h_p2: the three per-particle parameter slots, stored RAW (NULL = all zero).  Each pair is evaluated from both
+ * rows and counted once, so the text must be symmetric under 1 <-> 2.  The force is an ordinary member of a group and walks per-atom
+ * rows (list_kind 0) of its own: amm_pair_share_list, amm_pair_set_lambda[_dev], amm_pair_energy_derivative, amm_pair_energy_states
+ * and amm_pair_create with this family return non-zero with a message naming the family; amm_pair_set_params stores raw values;
+ * amm_pair_get_stats, amm_pair_count_within, amm_set_box and the profile hooks work as for any per-atom-row force. */
+int amm_pair_expr_create(amm_ctx *ctx, const amm_pair_desc *desc, const int32_t *code, int32_t ncode, const double *consts,
+                         int32_t nconst, const double *globals, int32_t nglobal, const double *h_p0, const double *h_p1,
+                         const double *h_p2, const int32_t *h_excl, int32_t n_excl, double skin, int32_t *force_id);
+/* Context.setParameter(name, value) for a global parameter of such a force: all of the program's globals, in its order. */
+int amm_pair_expr_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal);
 /* RESPASystem puts a short-ranged copy (group 1, rcutIn) and the full force (group 2) over the SAME particles and
  * exclusions (systems.py:71-77): let `force_id` traverse the front part of `host_id`'s neighbour rows instead of
  * building its own list.  Call before the first evaluation; exclusions must be identical. */
