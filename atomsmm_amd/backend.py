@@ -15,6 +15,7 @@ NEAR_NONE, NEAR_SHIFT, NEAR_FSWITCH, DAMPED, NONBONDED, SOFTCORE, LJ_VIRIAL = ra
 PAIR_EXPR = 7      # any other CustomNonbondedForce text: compiled (expr.compile_pair) and interpreted per pair (csrc/pair_expr.hip)
 GUARD_RC0, COULOMB_EWALD, COULOMB_RF, SWITCH, NO_SHIFT, GROUP_LJ, GROUP_Q = 1, 2, 4, 8, 16, 32, 64
 FREE_SPACE = 128   # NoCutoff / CutoffNonPeriodic: all pairs, no box, no list (csrc/free.hip)
+TERM_BOND, TERM_ANGLE, TERM_TORSION, TERM_EXTERNAL = range(4)     # amm_term_kind: the variable of a term-expression force
 BOND_HARMONIC, ANGLE_HARMONIC, BOND_LJC, BOND_NEAR, TORSION_PERIODIC, BOND_EWALD_EXCL = range(6)
 BOND_VIRIAL_HARMONIC, BOND_VIRIAL_LJ = 6, 7
 OP_EVAL, OP_KICK, OP_MOVE, OP_COPY, OP_COMBINE, OP_EXPR, OP_BATH = 1, 2, 3, 4, 5, 6, 7
@@ -48,6 +49,7 @@ EXPORTS = [
     'amm_min_read',
     'amm_set_box', 'amm_box_stats', 'amm_mol_define', 'amm_mol_scale',
     'amm_pair_expr_create', 'amm_pair_expr_set_globals',
+    'amm_term_expr_create', 'amm_term_expr_set_globals', 'amm_term_expr_set_params', 'amm_term_expr_release',
 ]
 
 
@@ -159,6 +161,10 @@ def lib():
         L.amm_pair_set_params.argtypes = [vp, C.c_int32, dp, dp, dp]
         L.amm_pair_expr_create.argtypes = [vp, C.POINTER(PairDesc), ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, dp, dp, dp, ip, C.c_int32, C.c_double, ip]
         L.amm_pair_expr_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
+        L.amm_term_expr_create.argtypes = [vp, C.c_int32, ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip, dp, C.c_int32, C.c_int32, C.c_int32, ip]
+        L.amm_term_expr_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
+        L.amm_term_expr_set_params.argtypes = [vp, C.c_int32, dp, C.c_int32, C.c_int32]
+        L.amm_term_expr_release.argtypes = [vp, C.c_int32]
         L.amm_pair_share_list.argtypes = [vp, C.c_int32, C.c_int32]
         L.amm_bonded_create.argtypes = [vp, ip]
         L.amm_bonded_add_terms.argtypes = [vp, C.c_int32, C.c_int32, ip, dp, C.c_int32, C.c_int32, C.POINTER(PairDesc)]
@@ -400,6 +406,36 @@ class HipContext:
     def bonded_release(self, fid):
         """Free a bond-list set that has been replaced (its id is retired)."""
         _chk(lib().amm_bonded_release(self.h, fid))
+
+    def term_expr_create(self, kind, code, consts, globals_, idx, params, periodic=False):
+        """A generic term force (csrc/term_expr.hip): the program of expr.compile_term, the values of its globals in the program's
+        order, `idx` (n_terms x 4, padded with -1) and `params` (n_params x n_terms: parameter-major)."""
+        c_, cp = _hi(code)
+        k_, kp = _hd(consts if len(consts) else [0.0])
+        g_, gp = _hd(globals_ if len(globals_) else [0.0])
+        idx_, ixp = _hi(np.asarray(idx, dtype=np.int32).reshape(-1, 4))
+        par = np.asarray(params, dtype=np.float64)
+        par = par.reshape(-1, len(idx_)) if len(idx_) else np.zeros((par.shape[0] if par.ndim == 2 else 0, 0))
+        par_, pp = _hd(par if par.size else [0.0])
+        fid = C.c_int32(-1)
+        _chk(lib().amm_term_expr_create(self.h, int(kind), cp, len(c_), kp, len(consts), gp, len(globals_), ixp, pp, len(idx_), len(par),
+                                        int(bool(periodic)), C.byref(fid)))
+        return fid.value
+
+    def term_expr_set_globals(self, fid, globals_):
+        g_, gp = _hd(globals_ if len(globals_) else [0.0])
+        _chk(lib().amm_term_expr_set_globals(self.h, fid, gp, len(globals_)))
+
+    def term_expr_set_params(self, fid, params, n_terms):
+        """All per-term values again (n_params x n_terms, parameter-major)."""
+        par = np.asarray(params, dtype=np.float64)
+        par = par.reshape(-1, n_terms) if n_terms else np.zeros((par.shape[0] if par.ndim == 2 else 0, 0))
+        par_, pp = _hd(par if par.size else [0.0])
+        _chk(lib().amm_term_expr_set_params(self.h, fid, pp, int(n_terms), len(par)))
+
+    def term_expr_release(self, fid):
+        """Free a term-expression force (its id is retired)."""
+        _chk(lib().amm_term_expr_release(self.h, fid))
 
     def pme_create(self, alpha, grid, q, Kc=KC):
         """Reciprocal space of a PME / Ewald NonbondedForce (smooth PME, order 5) on a grid[0] x grid[1] x grid[2] mesh."""

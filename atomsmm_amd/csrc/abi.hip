@@ -7,6 +7,7 @@
 #include "amm_ctx.h"
 #include "cluster.h"
 #include "pair_expr_vm.h"
+#include "term_expr_vm.h"
 
 int amm_pair_setup_grid(amm_ctx *ctx, PairForce *pf);
 static bool amm_family_allows_cluster(int family, int flags) {
@@ -27,6 +28,10 @@ static PairForce *get_pair(amm_ctx *ctx, int id) {
     return ctx->forces[id].pair;
 }
 static BondedSet *get_bonded(amm_ctx *ctx, int id) {
+    if (ctx && id >= 0 && id < (int)ctx->forces.size() && ctx->forces[id].type == AMM_FORCE_TERM_EXPR) {
+        amm_set_error("not a bond-list set: force " + std::to_string(id) + " is a term-expression force (amm_term_expr_*)");
+        return nullptr;
+    }
     if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_BONDED) {
         amm_set_error("invalid bonded force id");
         return nullptr;
@@ -42,6 +47,7 @@ int amm_force_eval_dispatch(amm_ctx *ctx, int force_id, const double *d_pos, dou
     }
     if (f.type == AMM_FORCE_PAIR) return amm_pair_eval_impl(ctx, f.pair, d_pos, d_force, accumulate, d_energy);
     if (f.type == AMM_FORCE_PME) return amm_pme_eval_impl(ctx, f.pme, d_pos, d_force, accumulate, d_energy);
+    if (f.type == AMM_FORCE_TERM_EXPR) return amm_term_expr_eval_impl(ctx, f.term, d_pos, d_force, accumulate, d_energy);
     return amm_bonded_eval_impl(ctx, f.bonded, d_pos, d_force, accumulate, d_energy);
 }
 
@@ -128,6 +134,7 @@ int amm_destroy(amm_ctx *ctx) {
             delete f.bonded;
         }
         if (f.pme) amm_pme_free(f.pme);
+        if (f.term) amm_term_expr_free(f.term);
     }
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
     if (ctx->d_expr_part) (void)hipFree(ctx->d_expr_part);
@@ -938,6 +945,96 @@ int amm_bonded_release(amm_ctx *ctx, int32_t force_id) {
     amm_bonded_free(bs);
     delete bs;
     ctx->forces[force_id].bonded = nullptr;
+    ctx->forces[force_id].type = AMM_FORCE_RELEASED;
+    return 0;
+}
+
+static TermExprForce *get_term_expr(amm_ctx *ctx, int id, const char *who) {
+    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_TERM_EXPR) {
+        amm_set_error(std::string(who) + ": not a term-expression force id");
+        return nullptr;
+    }
+    return ctx->forces[id].term;
+}
+
+// Custom{Bond,Angle,Torsion,External}Force(any energy text): the compiled text (atomsmm_amd/expr.py: compile_term), the terms' atoms
+// and their parameters, parameter-major
+int amm_term_expr_create(amm_ctx *ctx, int32_t kind, const int32_t *code, int32_t ncode, const double *consts, int32_t nconst,
+                         const double *globals, int32_t nglobal, const int32_t *h_idx, const double *h_params, int32_t n_terms,
+                         int32_t n_params, int32_t periodic, int32_t *force_id) {
+    auto fail = [](const std::string &what) {
+        amm_set_error("amm_term_expr_create: " + what);
+        return 1;
+    };
+    if (!ctx || !code || !force_id || (nconst > 0 && !consts) || (nglobal > 0 && !globals) || n_terms < 0 || (n_terms > 0 && !h_idx)) return fail("null argument");
+    if (kind < AMM_TERM_BOND || kind > AMM_TERM_EXTERNAL) return fail("unknown kind " + std::to_string(kind));
+    if (n_params < 0 || n_params > AMM_TERM_MAX_PARAMS) return fail(std::to_string(n_params) + " per-term parameters (limit " + std::to_string(AMM_TERM_MAX_PARAMS) + ")");
+    if (n_params > 0 && n_terms > 0 && !h_params) return fail("null parameter array");
+    if (periodic && kind == AMM_TERM_EXTERNAL) return fail("an external term reads raw coordinates: it is never periodic");
+    if (periodic && !ctx->has_box) return fail("periodic terms, but the context has no periodic box");
+    if (amm_expr_program_validate("amm_term_expr_create", code, ncode, nconst, nglobal, kind == AMM_TERM_EXTERNAL ? 3 : 1, n_params)) return 1;
+    for (int t = 0; t < n_terms; ++t)
+        for (int r = 0; r < amm_term_arity(kind); ++r) {
+            const int a = h_idx[(size_t)t * 4 + r];
+            if (a < 0 || a >= ctx->n) return fail("atom index " + std::to_string(a) + " of term " + std::to_string(t) + " is out of range");
+        }
+    AMM_HIP(hipSetDevice(ctx->device));
+    TermExprForce *tf = new TermExprForce();
+    tf->kind = kind;
+    tf->periodic = periodic ? 1 : 0;
+    tf->n_terms = n_terms;
+    tf->n_params = n_params;
+    std::memset(&tf->h, 0, sizeof(tf->h));
+    tf->h.ncode = ncode;
+    tf->h.nconst = nconst;
+    tf->h.nglobal = nglobal;
+    std::copy(code, code + ncode, tf->h.code);
+    std::copy(consts, consts + nconst, tf->h.consts);
+    std::copy(globals, globals + nglobal, tf->h.globals);
+    if (amm_term_expr_build(ctx, tf, h_idx, h_params)) {
+        amm_term_expr_free(tf);
+        return 1;
+    }
+    ForceObj fo;
+    fo.type = AMM_FORCE_TERM_EXPR;
+    fo.term = tf;
+    ctx->forces.push_back(fo);
+    *force_id = (int32_t)ctx->forces.size() - 1;
+    return 0;
+}
+
+int amm_term_expr_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal) {
+    TermExprForce *tf = get_term_expr(ctx, force_id, "amm_term_expr_set_globals");
+    if (!tf) return 1;
+    if (nglobal != tf->h.nglobal || (nglobal > 0 && !globals)) {
+        amm_set_error("amm_term_expr_set_globals: the program reads " + std::to_string(tf->h.nglobal) + " globals, " + std::to_string(nglobal) + " given");
+        return 1;
+    }
+    std::copy(globals, globals + nglobal, tf->h.globals);
+    return amm_term_expr_upload(ctx, tf, true);
+}
+
+int amm_term_expr_set_params(amm_ctx *ctx, int32_t force_id, const double *h_params, int32_t n_terms, int32_t n_params) {
+    TermExprForce *tf = get_term_expr(ctx, force_id, "amm_term_expr_set_params");
+    if (!tf) return 1;
+    if (n_terms != tf->n_terms || n_params != tf->n_params || ((size_t)n_terms * n_params > 0 && !h_params)) {
+        amm_set_error("amm_term_expr_set_params: the force has " + std::to_string(tf->n_terms) + " terms of " + std::to_string(tf->n_params) +
+                      " parameters, " + std::to_string(n_terms) + " x " + std::to_string(n_params) + " given");
+        return 1;
+    }
+    return amm_term_expr_upload_params(ctx, tf, h_params);
+}
+
+int amm_term_expr_release(amm_ctx *ctx, int32_t force_id) {
+    TermExprForce *tf = get_term_expr(ctx, force_id, "amm_term_expr_release");
+    if (!tf) return 1;
+    AMM_HIP(hipStreamSynchronize(ctx->stream));            // nothing in flight may still read it
+    for (int g = 0; g < AMM_MAX_GROUPS; ++g) {
+        std::vector<int> &m = ctx->groups[g].forces;
+        m.erase(std::remove(m.begin(), m.end(), (int)force_id), m.end());
+    }
+    amm_term_expr_free(tf);
+    ctx->forces[force_id].term = nullptr;
     ctx->forces[force_id].type = AMM_FORCE_RELEASED;
     return 0;
 }

@@ -242,13 +242,15 @@ struct BondedSet {
 struct PmeForce;      // pme.hip
 struct ConstraintSet; // constraints.hip
 struct MinObj;        // minimize.hip: one L-BFGS minimisation (history ring, Gram matrix, direction)
+struct TermExprForce; // term_expr_vm.h: bond / angle / torsion / external terms with a compiled energy text (term_expr.hip)
 
-enum : int { AMM_FORCE_RELEASED = 0, AMM_FORCE_PAIR = 1, AMM_FORCE_BONDED = 2, AMM_FORCE_PME = 3 };   // ForceObj::type
+enum : int { AMM_FORCE_RELEASED = 0, AMM_FORCE_PAIR = 1, AMM_FORCE_BONDED = 2, AMM_FORCE_PME = 3, AMM_FORCE_TERM_EXPR = 4 };   // ForceObj::type
 struct ForceObj {
     int type = AMM_FORCE_RELEASED;
     PairForce *pair = nullptr;
     BondedSet *bonded = nullptr;
     PmeForce *pme = nullptr;
+    TermExprForce *term = nullptr;
 };
 
 struct ExprDef {
@@ -510,6 +512,12 @@ int amm_free_lanes_per_row(int n);
 int amm_pair_expr_launch(amm_ctx *ctx, PairForce *pf, const PairArgs &A, dim3 grid, bool en);
 int amm_pair_expr_upload(amm_ctx *ctx, PairExpr *px, bool globals_only);
 void amm_pair_expr_free(PairExpr *px);
+// term_expr.hip: a force of type AMM_FORCE_TERM_EXPR
+int amm_term_expr_build(amm_ctx *ctx, TermExprForce *tf, const int32_t *h_idx, const double *h_params);   // device arrays + CSR of a new force
+int amm_term_expr_upload(amm_ctx *ctx, TermExprForce *tf, bool globals_only);
+int amm_term_expr_upload_params(amm_ctx *ctx, TermExprForce *tf, const double *h_params);
+int amm_term_expr_eval_impl(amm_ctx *ctx, TermExprForce *tf, const double *d_pos, double *d_force, int accumulate, double *d_energy);
+void amm_term_expr_free(TermExprForce *tf);
 // implemented in pair.hip / cells.hip / bonded.hip / integrate.hip
 int amm_pair_build_consts(const amm_pair_desc &d, PairConsts &pc);
 int amm_pair_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double *d_force, int accumulate,

@@ -20,6 +20,7 @@
 #include "pair_args.h"
 #include "pair_math.h"
 #include "pair_expr_vm.h"
+#include "term_expr_vm.h"
 
 template <bool EN>
 __global__ void __launch_bounds__(256) k_pair_expr(PairArgs A, const PairExprProg *__restrict__ prog, double rc2, double rswitch,
@@ -126,10 +127,15 @@ int amm_pair_expr_launch(amm_ctx *ctx, PairForce *pf, const PairArgs &A, dim3 gr
 
 // ---- host: program checks, upload ----
 int amm_pair_expr_validate(const int32_t *code, int ncode, int nconst, int nglobal) {
-    auto fail = [](const std::string &what) {
-        amm_set_error("amm_pair_expr_create: " + what);
+    return amm_expr_program_validate("amm_pair_expr_create", code, ncode, nconst, nglobal, -1, 0);
+}
+
+int amm_expr_program_validate(const char *who, const int32_t *code, int ncode, int nconst, int nglobal, int term_vars, int term_params) {
+    auto fail = [who](const std::string &what) {
+        amm_set_error(std::string(who) + ": " + what);
         return 1;
     };
+    const bool pair = term_vars < 0;
     if (ncode < 1 || ncode > AMM_PEXPR_MAXCODE) return fail("the program has " + std::to_string(ncode) + " code words (limit " + std::to_string(AMM_PEXPR_MAXCODE) + ")");
     if (nconst < 0 || nconst > AMM_PEXPR_MAXCONST) return fail("the program has " + std::to_string(nconst) + " constants (limit " + std::to_string(AMM_PEXPR_MAXCONST) + ")");
     if (nglobal < 0 || nglobal > AMM_PEXPR_MAXGLOBAL) return fail("the program has " + std::to_string(nglobal) + " globals (limit " + std::to_string(AMM_PEXPR_MAXGLOBAL) + ")");
@@ -140,15 +146,17 @@ int amm_pair_expr_validate(const int32_t *code, int ncode, int nconst, int nglob
         switch (op) {
         case X_CONST: pops = 0; if (arg < 0 || arg >= nconst) return fail("constant index out of range"); break;
         case X_GLOBAL: pops = 0; if (arg < 0 || arg >= nglobal) return fail("global index out of range"); break;
-        case X_PAIR_R: pops = 0; break;
-        case X_PAIR_P1: case X_PAIR_P2: pops = 0; if (arg < 0 || arg >= AMM_PEXPR_PARAMS) return fail("per-particle parameter index out of range (limit " + std::to_string(AMM_PEXPR_PARAMS) + ")"); break;
+        case X_PAIR_R: pops = 0; if (!pair) return fail("opcode " + std::to_string(op) + " is not a term-expression op"); break;
+        case X_TERM_VAR: pops = 0; if (pair) return fail("opcode " + std::to_string(op) + " is not a pair-expression op"); if (arg < 0 || arg >= term_vars) return fail("variable index out of range (the kind has " + std::to_string(term_vars) + ")"); break;
+        case X_TERM_P: pops = 0; if (pair) return fail("opcode " + std::to_string(op) + " is not a pair-expression op"); if (arg < 0 || arg >= term_params) return fail("per-term parameter index out of range (the force has " + std::to_string(term_params) + ")"); break;
+        case X_PAIR_P1: case X_PAIR_P2: pops = 0; if (!pair) return fail("opcode " + std::to_string(op) + " is not a term-expression op"); if (arg < 0 || arg >= AMM_PEXPR_PARAMS) return fail("per-particle parameter index out of range (limit " + std::to_string(AMM_PEXPR_PARAMS) + ")"); break;
         case X_LOAD: pops = 0; if (arg < 0 || arg >= AMM_PEXPR_LOCALS) return fail("local index out of range (limit " + std::to_string(AMM_PEXPR_LOCALS) + ")"); break;
         case X_STORE: pushes = 0; if (arg < 0 || arg >= AMM_PEXPR_LOCALS) return fail("local index out of range (limit " + std::to_string(AMM_PEXPR_LOCALS) + ")"); break;
         case X_ADD: case X_SUB: case X_MUL: case X_DIV: case X_POW: case X_MIN: case X_MAX: case X_ATAN2: pops = 2; break;
         case X_SELECT: pops = 3; break;
         case X_NEG: case X_POWI: case X_SQRT: case X_EXP: case X_LOG: case X_SIN: case X_COS: case X_TAN: case X_ASIN: case X_ACOS: case X_ATAN:
         case X_SINH: case X_COSH: case X_TANH: case X_ERF: case X_ERFC: case X_ABS: case X_FLOOR: case X_CEIL: case X_STEP: case X_DELTA: break;
-        default: return fail("opcode " + std::to_string(op) + " is not a pair-expression op");
+        default: return fail("opcode " + std::to_string(op) + (pair ? " is not a pair-expression op" : " is not a term-expression op"));
         }
         if (sp < pops) return fail("stack underflow at word " + std::to_string(pc));
         sp += pushes - pops;

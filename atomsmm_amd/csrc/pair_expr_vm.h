@@ -20,6 +20,8 @@
 
 // opcodes beside those of expr_vm.h (X_BUF, X_MASS, X_GAUSS, X_UNIFORM, X_DEVG, X_OUT and X_HORNER are not pair ops)
 enum { X_PAIR_R = 50, X_PAIR_P1 = 51, X_PAIR_P2 = 52 };
+// ... and the leaves of a term expression (term_expr_vm.h): the term's geometric variable k, its parameter k
+enum { X_TERM_VAR = 53, X_TERM_P = 54 };
 
 // the compiled text as the device holds it: staged into LDS once per block
 struct PairExprProg {
@@ -84,14 +86,23 @@ static __device__ __noinline__ double3 pexpr_pow(double a, double b, bool with_l
 }
 static __device__ __noinline__ double pexpr_atan2(double y, double x) { return atan2(y, x); }
 
-// E(r) and dE/dr of one pair.  code / consts / globals: the block's LDS copies; pa / pb: the parameters of the row atom (<name>1) and
-// of the neighbour (<name>2).  The program is the same for every lane, so the word is made scalar (readfirstlane) and the dispatch is
-// a scalar branch.  The top of the stack lives in registers (tv, td): a unary op touches no memory, a binary op reads one slot.  The
-// elements below it are the lane's column of an LDS strip -- st[k * AMM_PEXPR_STRIDE], one (value, d/dr) record of 16 bytes per
-// slot, neighbouring lanes in neighbouring records (conflict-free) -- and the locals are a private array.
-#define AMM_PEXPR_STRIDE 256        // lanes per block of k_pair_expr: slot k of lane t is s_stack[k * 256 + t]
-__device__ __forceinline__ void pair_expr_run(const int *code, int ncode, const double *consts, const double *globals, double r,
-                                              const double *pa, const double *pb, double2 *st, double &E, double &dE) {
+// The leaves of a pair expression: r with derivative 1, pa / pb the parameters of the row atom (<name>1) and of the neighbour (<name>2).
+struct PairLeaves {
+    static constexpr bool kPair = true;
+    double r;
+    const double *pa, *pb;
+};
+
+// E and its derivative along the leaves' seed.  code / consts / globals: the block's LDS copies.  The program is the same for every
+// lane, so the word is made scalar (readfirstlane) and the dispatch is a scalar branch.  The top of the stack lives in registers
+// (tv, td): a unary op touches no memory, a binary op reads one slot.  The elements below it are the lane's column of an LDS strip --
+// st[k * AMM_PEXPR_STRIDE], one (value, derivative) record of 16 bytes per slot, neighbouring lanes in neighbouring records
+// (conflict-free) -- and the locals are a private array.  `Leaves`: PairLeaves, or the TermLeaves of term_expr_vm.h -- the words of
+// the other kind compile to nothing.
+#define AMM_PEXPR_STRIDE 256        // lanes per block of k_pair_expr / k_term_expr: slot k of lane t is s_stack[k * 256 + t]
+template <class Leaves>
+__device__ __forceinline__ void pexpr_run(const int *code, int ncode, const double *consts, const double *globals, const Leaves &leaves,
+                                          double2 *st, double &E, double &dE) {
 #pragma clang fp contract(off)
     double lv[AMM_PEXPR_LOCALS], ld[AMM_PEXPR_LOCALS];
     double tv = 0.0, td = 0.0;
@@ -117,9 +128,11 @@ __device__ __forceinline__ void pair_expr_run(const int *code, int ncode, const 
         switch (op) {
         case X_CONST: PEXPR_PUSH(consts[arg], 0.0); break;
         case X_GLOBAL: PEXPR_PUSH(globals[arg], 0.0); break;
-        case X_PAIR_R: PEXPR_PUSH(r, 1.0); break;
-        case X_PAIR_P1: PEXPR_PUSH(arg == 0 ? pa[0] : (arg == 1 ? pa[1] : pa[2]), 0.0); break;
-        case X_PAIR_P2: PEXPR_PUSH(arg == 0 ? pb[0] : (arg == 1 ? pb[1] : pb[2]), 0.0); break;
+        case X_PAIR_R: if constexpr (Leaves::kPair) PEXPR_PUSH(leaves.r, 1.0); break;
+        case X_PAIR_P1: if constexpr (Leaves::kPair) PEXPR_PUSH(arg == 0 ? leaves.pa[0] : (arg == 1 ? leaves.pa[1] : leaves.pa[2]), 0.0); break;
+        case X_PAIR_P2: if constexpr (Leaves::kPair) PEXPR_PUSH(arg == 0 ? leaves.pb[0] : (arg == 1 ? leaves.pb[1] : leaves.pb[2]), 0.0); break;
+        case X_TERM_VAR: if constexpr (!Leaves::kPair) PEXPR_PUSH(leaves.var(arg), leaves.seed(arg)); break;
+        case X_TERM_P: if constexpr (!Leaves::kPair) PEXPR_PUSH(leaves.param(arg), 0.0); break;
         case X_LOAD: PEXPR_PUSH(lv[arg], ld[arg]); break;
         case X_STORE: {
             lv[arg] = tv;
@@ -198,5 +211,11 @@ __device__ __forceinline__ void pair_expr_run(const int *code, int ncode, const 
 #undef PEXPR_UNARY
     E = tv;
     dE = td;
+}
+
+// E(r) and dE/dr of one pair
+__device__ __forceinline__ void pair_expr_run(const int *code, int ncode, const double *consts, const double *globals, double r,
+                                              const double *pa, const double *pb, double2 *st, double &E, double &dE) {
+    pexpr_run(code, ncode, consts, globals, PairLeaves{r, pa, pb}, st, E, dE);
 }
 #endif

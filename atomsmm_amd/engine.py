@@ -241,6 +241,8 @@ class _Entry:
         self.depends = set()        # global parameters this entry's backend data depend on
         self.pair_expr = False      # a CustomNonbondedForce on the pair-expression kernel (generic energy text) ...
         self.program = None         # ... and its compiled program (expr.compile_pair)
+        self.term_ids = []          # backend term-expression forces (csrc/term_expr.hip): a bond / angle / torsion / external force with
+        self.term_expr = False      # a generic energy text; `program` is then that of expr.compile_term
 
 
 def slice_bounds(n_items, rank, world):
@@ -517,6 +519,8 @@ class Engine:
                 self.ctx.force_eval(pid, self.x, fp, accumulate=True, energy=e)
             if entry.bonded_id is not None:
                 self.ctx.force_eval(entry.bonded_id, self.x, fp, accumulate=True, energy=e)
+            for tid in entry.term_ids:
+                self.ctx.force_eval(tid, self.x, fp, accumulate=True, energy=e)
             if entry.recip is not None:
                 self.ctx.force_eval(entry.recip, self.x, fp, accumulate=True, energy=e)
             const += entry.constant
@@ -607,13 +611,16 @@ class Engine:
             entry.terms.append((B.ANGLE_HARMONIC, a, p, force.usesPeriodicBoundaryConditions(), None))
         elif isinstance(force, mm.CustomAngleForce):
             if force.getEnergyFunction().replace(' ', '') != '0.5*(K0*(theta-t0)^2-Kn*(theta-tn)^2)':
-                raise InputError('CustomAngleForce: only the redefine_angle difference potential is supported')
-            # difference of two harmonic angles (RESPASystem.redefine_angle, systems.py:226)
-            a = np.array([r[:3] for r in force._angles], dtype=np.int32).reshape(-1, 3)
-            p = np.array([r[3] for r in force._angles], dtype=np.float64).reshape(-1, 4)
-            periodic = force.usesPeriodicBoundaryConditions()
-            entry.terms.append((B.ANGLE_HARMONIC, a, p[:, [0, 1]], periodic, None))
-            entry.terms.append((B.ANGLE_HARMONIC, a, np.stack([p[:, 2], -p[:, 3]], axis=1), periodic, None))
+                self._translate_term_expression(force, entry)
+            else:
+                # difference of two harmonic angles (RESPASystem.redefine_angle, systems.py:226)
+                a = np.array([r[:3] for r in force._angles], dtype=np.int32).reshape(-1, 3)
+                p = np.array([r[3] for r in force._angles], dtype=np.float64).reshape(-1, 4)
+                periodic = force.usesPeriodicBoundaryConditions()
+                entry.terms.append((B.ANGLE_HARMONIC, a, p[:, [0, 1]], periodic, None))
+                entry.terms.append((B.ANGLE_HARMONIC, a, np.stack([p[:, 2], -p[:, 3]], axis=1), periodic, None))
+        elif isinstance(force, (mm.CustomTorsionForce, mm.CustomExternalForce)):
+            self._translate_term_expression(force, entry)
         elif isinstance(force, mm.PeriodicTorsionForce):
             t = np.array([r[:4] for r in force._torsions], dtype=np.int32).reshape(-1, 4)
             p = np.array([[r[4], r[5], r[6]] for r in force._torsions], dtype=np.float64).reshape(-1, 3)
@@ -1250,6 +1257,75 @@ class Engine:
         entry.update = update
         entry.depends = set(lam)
 
+    # (class, kind, variables, per-term names: count / name getters, rows attribute, atoms per term, what OpenMM calls a term)
+    _TERM_CLASSES = (('CustomBondForce', B.TERM_BOND, ('r',), 'PerBond', '_bonds', 2, 'bonds'),
+                     ('CustomAngleForce', B.TERM_ANGLE, ('theta',), 'PerAngle', '_angles', 3, 'angles'),
+                     ('CustomTorsionForce', B.TERM_TORSION, ('theta',), 'PerTorsion', '_torsions', 4, 'torsions'),
+                     ('CustomExternalForce', B.TERM_EXTERNAL, ('x', 'y', 'z'), 'PerParticle', '_particles', 1, 'particles'))
+
+    def _translate_term_expression(self, force, entry):
+        """A CustomBondForce / CustomAngleForce / CustomTorsionForce / CustomExternalForce whose energy text is none of the hand-written
+        kinds: compiled here (expr.compile_term) and interpreted per term, with its derivative in the term's variable, by the
+        term-expression kernels (csrc/term_expr.hip).  A force object of its own: no bond-list terms to merge into the group's set."""
+        cls, kind, variables, per, attr, arity, what = [c for c in self._TERM_CLASSES if isinstance(force, getattr(mm, c[0]))][0]
+        text = force.getEnergyFunction()
+        generic = '%s: energy expression not recognised as one of the hand-written kinds (%s); the generic term-expression kernel ' % (
+            cls, text.split(';')[0])
+        if getattr(force, '_derivs', None):
+            raise NotImplementedError(generic + 'differentiates in %s only: no addEnergyParameterDerivative' % ', '.join(variables))
+        if self.world > 1:
+            raise NotImplementedError(generic + 'runs on a single rank')
+        periodic = bool(kind != B.TERM_EXTERNAL and force.usesPeriodicBoundaryConditions())
+        if periodic and self.free_space:
+            raise InputError('%s uses periodic boundary conditions in a System in free space' % cls)
+        names = [getattr(force, 'get%sParameterName' % per)(k) for k in range(getattr(force, 'getNum%sParameters' % per)())]
+        gnames = [force.getGlobalParameterName(k) for k in range(force.getNumGlobalParameters())]
+        try:
+            prog = X.compile_term(text, variables, names, gnames)
+        except X.ExpressionError as exc:
+            raise InputError('%s: energy expression not recognised by the HIP path as one of the hand-written kinds, and not a term '
+                             'expression the generic kernel can run: %s' % (cls, exc))
+
+        def tables():
+            rows = getattr(force, attr)
+            idx = np.full((len(rows), 4), -1, dtype=np.int32)
+            par = np.zeros((len(names), len(rows)), dtype=np.float64)
+            for t, row in enumerate(rows):
+                if len(row[arity]) != len(names):
+                    raise mm.OpenMMException('%s: every one of the %s needs %d parameters' % (cls, what, len(names)))
+                idx[t, :arity] = row[:arity]
+                par[:, t] = row[arity]
+            if len(rows) and (idx[:, :arity].min() < 0 or idx[:, :arity].max() >= self.n):
+                raise mm.OpenMMException('%s: a particle index is out of range' % cls)
+            return idx, par
+
+        idx, par = tables()
+        tid = self.ctx.term_expr_create(kind, prog.code, prog.consts, [self.parameters[g] for g in prog.globals_], idx, par,
+                                        periodic=periodic)
+        entry.term_ids.append(tid)
+        entry.term_expr = True
+        entry.program = prog
+
+        def reload():          # updateParametersInContext: the per-term parameters are read again
+            fresh_idx, fresh = tables()
+            if len(fresh_idx) != len(idx):
+                raise mm.OpenMMException('updateParametersInContext: the number of %s has changed' % what)
+            if not np.array_equal(fresh_idx, idx):
+                raise mm.OpenMMException('updateParametersInContext: the particles of the %s have changed' % what)
+            self.ctx.term_expr_set_params(tid, fresh, len(idx))
+            return 'values'
+        entry.reload = reload
+        if prog.globals_:
+            depends = set(prog.globals_)
+
+            def update(parameters, changed):
+                if not (depends & changed):
+                    return False
+                self.ctx.term_expr_set_globals(tid, [parameters[g] for g in prog.globals_])
+                return 'values'
+            entry.update = update
+            entry.depends = depends
+
     def _translate_custom_bond(self, force, entry):
         if force.getEnergyFunction().replace(' ', '') == '0.5*(K0*(r-r0)^2-Kn*(r-rn)^2)':
             # difference of two harmonic bonds (RESPASystem.redefine_bond, systems.py:162): +K0 at r0, -Kn at rn
@@ -1265,6 +1341,11 @@ class Engine:
             par = np.array([b[2] for b in force._bonds], dtype=np.float64).reshape(-1, 2)
             entry.terms.append((B.BOND_VIRIAL_HARMONIC, idx, par, force.usesPeriodicBoundaryConditions(), None))
             return
+        if getattr(force, '_amm', None) is None:
+            globs = {force.getGlobalParameterName(i): force.getGlobalParameterDefaultValue(i)
+                     for i in range(force.getNumGlobalParameters())}
+            if describe_energy(force.getEnergyFunction(), globs) is None:
+                return self._translate_term_expression(force, entry)
         d = dict(self._descriptor_of(force))
         nb_ = force.getNumBonds()
         idx = np.array([[b[0], b[1]] for b in force._bonds], dtype=np.int32).reshape(-1, 2)
@@ -1512,6 +1593,8 @@ class Engine:
                         self.ctx.force_eval(pid, self.x, fp, accumulate=True, energy=e_pair)
                     if entry.bonded_id is not None:
                         self.ctx.force_eval(entry.bonded_id, self.x, fb, accumulate=True, energy=e_bond)
+                    for tid in entry.term_ids:
+                        self.ctx.force_eval(tid, self.x, fb, accumulate=True, energy=e_bond)
                     const += entry.constant
                 if entry.recip is not None and mask & (1 << entry.recip_group):
                     # reciprocal space: every rank evaluates all of it (spread + FFTs are not sharded)
@@ -1612,6 +1695,9 @@ class Engine:
                 e.recip_sliced = reduced
                 self.ctx.pme_set_sliced(e.recip, reduced)
                 ids.append(e.recip)
+        # term-expression forces last: each is a member of its own (the scheduler's fusion rules decline a group that holds one and
+        # evaluate it member by member), and the first member still writes the buffer
+        ids += [tid for e in members for tid in e.term_ids]
         index = B.GROUP_ALL if g == 'all' else int(g)
         if reduced and g != 'all':
             self._buffer('f{}'.format(g), together=['f{}'.format(e.group) for e in self.entries if e.pair_ids])
@@ -1721,6 +1807,8 @@ class Engine:
                     ctx.force_eval(pid, self.x, force, accumulate=True, energy=scal)
                 if entry.bonded_id is not None:
                     ctx.force_eval(entry.bonded_id, self.x, force, accumulate=True, energy=scal)
+                for tid in entry.term_ids:
+                    ctx.force_eval(tid, self.x, force, accumulate=True, energy=scal)
                 if entry.recip is not None:
                     ctx.force_eval(entry.recip, self.x, force, accumulate=True, energy=scal)
             if restraint is not None:
@@ -2638,6 +2726,8 @@ class Engine:
                 self.ctx.force_eval(pid, self.x, fp, accumulate=True, energy=e_pair)
             if entry.bonded_id is not None:
                 self.ctx.force_eval(entry.bonded_id, self.x, fb, accumulate=True, energy=e_bond)
+            for tid in entry.term_ids:
+                self.ctx.force_eval(tid, self.x, fb, accumulate=True, energy=e_bond)
             if entry.recip is not None:
                 self.ctx.pme_set_sliced(entry.recip, False)
                 self.ctx.force_eval(entry.recip, self.x, fb, accumulate=True, energy=e_bond)
@@ -2676,6 +2766,9 @@ class Engine:
                 if getattr(entry, 'pair_expr', False):
                     raise NotImplementedError('deriv(energy, %s) of a CustomNonbondedForce with a generic energy expression (the '
                                               'pair-expression kernel differentiates in r only)' % name)
+                if getattr(entry, 'term_expr', False):
+                    raise NotImplementedError('deriv(energy, %s) of a %s with a generic energy expression (the term-expression '
+                                              'kernel differentiates in the term\'s variable only)' % (name, type(entry.force).__name__))
                 if entry.update is None:
                     raise NotImplementedError('deriv(energy, %s): the force that depends on it cannot be re-parameterised' % name)
                 by_difference.append(entry)

@@ -13,6 +13,8 @@ import functools
 import math
 import re
 
+from .utils import InputError
+
 OPCODES = dict(
     CONST=0, GLOBAL=1, BUF=2, MASS=3, GAUSS=4, UNIFORM=5, LOAD=6, STORE=7, DEVG=8, OUT=9,
     ADD=10, SUB=11, MUL=12, DIV=13, NEG=14, POW=15, POWI=16,
@@ -20,11 +22,15 @@ OPCODES = dict(
     erfc=33, abs=34, floor=35, ceil=36, step=37, delta=38, min=39, max=40, select=41, atan2=42, HORNER=43)
 # the words only a pair expression has (compile_pair; csrc/pair_expr_vm.h), beside those of OPCODES that it shares
 PAIR_OPCODES = dict(PAIR_R=50, PAIR_P1=51, PAIR_P2=52)
-ALL_OPCODES = dict(OPCODES, **PAIR_OPCODES)
+# the words only a term expression has (compile_term; csrc/term_expr_vm.h): the term's geometric variable k and its parameter k
+TERM_OPCODES = dict(TERM_VAR=53, TERM_P=54)
+ALL_OPCODES = dict(OPCODES, **PAIR_OPCODES, **TERM_OPCODES)
 _ARITY = {'min': 2, 'max': 2, 'select': 3, 'atan2': 2}
 MAX_LOCALS = 16
 # limits of a pair-expression program (csrc/pair_expr_vm.h)
 PAIR_MAX_CODE, PAIR_MAX_CONSTS, PAIR_MAX_GLOBALS, PAIR_MAX_STACK, PAIR_MAX_LOCALS, PAIR_MAX_PARAMS = 256, 48, 48, 16, 16, 3
+# a term expression shares them, but for its parameters: one row of doubles per term, not a neighbour row's three (csrc/term_expr_vm.h)
+TERM_MAX_PARAMS = 8
 
 
 class ExpressionError(ValueError):
@@ -296,7 +302,7 @@ def compile_per_dof(text, resolve, what='per-DOF', random_ok=True, fold=False):
     return prog
 
 
-_STACK_EFFECT = {'CONST': 1, 'GLOBAL': 1, 'PAIR_R': 1, 'PAIR_P1': 1, 'PAIR_P2': 1, 'LOAD': 1, 'STORE': -1, 'ADD': -1, 'SUB': -1, 'MUL': -1,
+_STACK_EFFECT = {'CONST': 1, 'GLOBAL': 1, 'PAIR_R': 1, 'PAIR_P1': 1, 'PAIR_P2': 1, 'TERM_VAR': 1, 'TERM_P': 1, 'LOAD': 1, 'STORE': -1, 'ADD': -1, 'SUB': -1, 'MUL': -1,
                  'DIV': -1, 'POW': -1, 'min': -1, 'max': -1, 'atan2': -1, 'select': -2}
 
 
@@ -320,26 +326,52 @@ def compile_pair(text, per_particle_names, global_names):
             return slots[name]
         return ('global',) if name in global_names else None
 
+    return _checked_program(text, resolve, 'pair')
+
+
+def _checked_program(text, resolve, what):
+    """The folded program of a pair or term energy text, held against the limits of csrc/pair_expr_vm.h."""
     try:
-        prog = compile_per_dof(text, resolve, what='pair', random_ok=False, fold=True)
+        prog = compile_per_dof(text, resolve, what=what, random_ok=False, fold=True)
     except ExpressionError as exc:
         if 'too many auxiliary definitions' in str(exc):
-            raise ExpressionError('pair expression: more than %d auxiliary definitions (locals)' % PAIR_MAX_LOCALS)
+            raise ExpressionError('%s expression: more than %d auxiliary definitions (locals)' % (what, PAIR_MAX_LOCALS))
         raise
     if len(prog.code) > PAIR_MAX_CODE:
-        raise ExpressionError('pair expression: %d code words (limit %d)' % (len(prog.code), PAIR_MAX_CODE))
+        raise ExpressionError('%s expression: %d code words (limit %d)' % (what, len(prog.code), PAIR_MAX_CODE))
     if len(prog.consts) > PAIR_MAX_CONSTS:
-        raise ExpressionError('pair expression: %d constants (limit %d)' % (len(prog.consts), PAIR_MAX_CONSTS))
+        raise ExpressionError('%s expression: %d constants (limit %d)' % (what, len(prog.consts), PAIR_MAX_CONSTS))
     if len(prog.globals_) > PAIR_MAX_GLOBALS:
-        raise ExpressionError('pair expression: %d global parameters (limit %d)' % (len(prog.globals_), PAIR_MAX_GLOBALS))
+        raise ExpressionError('%s expression: %d global parameters (limit %d)' % (what, len(prog.globals_), PAIR_MAX_GLOBALS))
     names = {v: k for k, v in ALL_OPCODES.items()}
     depth = deepest = 0
     for word in prog.code:
         depth += _STACK_EFFECT.get(names[word & 0xff], 0)
         deepest = max(deepest, depth)
     if deepest > PAIR_MAX_STACK:
-        raise ExpressionError('pair expression: stack depth %d (limit %d)' % (deepest, PAIR_MAX_STACK))
+        raise ExpressionError('%s expression: stack depth %d (limit %d)' % (what, deepest, PAIR_MAX_STACK))
     return prog
+
+
+def compile_term(text, variables, per_term_names, global_names):
+    """Compile the energy text of a CustomBondForce / CustomAngleForce / CustomTorsionForce / CustomExternalForce for the
+    term-expression kernels (csrc/term_expr.hip): variable k of `variables` -- ('r',), ('theta',) or ('x', 'y', 'z') -- is TERM_VAR k,
+    per-term parameter k TERM_P k, a global parameter GLOBAL k (k: position in the program's globals_); auxiliary definitions, in any
+    order, become locals.  The limits are those of compile_pair, but for the parameters: up to TERM_MAX_PARAMS per term."""
+    variables, per_term_names, global_names = list(variables), list(per_term_names), set(global_names)
+    if len(per_term_names) > TERM_MAX_PARAMS:
+        raise InputError('a term expression takes at most %d per-term parameters (%d given)' % (TERM_MAX_PARAMS, len(per_term_names)))
+    if re.search(r'\bperiodicdistance\s*\(', text):
+        raise ExpressionError('periodicdistance(...) is not supported in a term expression')
+
+    def resolve(name):
+        if name in per_term_names:
+            return ('op', 'TERM_P', per_term_names.index(name))
+        if name in variables:
+            return ('op', 'TERM_VAR', variables.index(name))
+        return ('global',) if name in global_names else None
+
+    return _checked_program(text, resolve, 'term')
 
 
 def compile_polynomial(coefficients, scale, shift, operand):

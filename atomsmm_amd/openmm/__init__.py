@@ -416,6 +416,7 @@ class CustomBondForce(Force, _GlobalParams):
         self._energy = energy
         self._bnames = []
         self._bonds = []
+        self._derivs = []
         self._periodic = False
 
     def getEnergyFunction(self):
@@ -434,6 +435,9 @@ class CustomBondForce(Force, _GlobalParams):
     def getPerBondParameterName(self, index):
         return self._bnames[index]
 
+    def addEnergyParameterDerivative(self, name):
+        self._derivs.append(name)
+
     def addBond(self, particle1, particle2, parameters=()):
         self._bonds.append([int(particle1), int(particle2), [float(md_value(p)) for p in parameters]])
         return len(self._bonds) - 1
@@ -447,6 +451,10 @@ class CustomBondForce(Force, _GlobalParams):
 
     def setBondParameters(self, index, particle1, particle2, parameters=()):
         self._bonds[index] = [int(particle1), int(particle2), [float(md_value(p)) for p in parameters]]
+
+    def updateParametersInContext(self, context):
+        """Upload the per-bond parameters again (the atoms and the number of bonds must not have changed)."""
+        context._engine.update_force_parameters(self)
 
     def setUsesPeriodicBoundaryConditions(self, periodic):
         self._periodic = bool(periodic)
@@ -489,6 +497,7 @@ class CustomAngleForce(Force, _GlobalParams):
         self._energy = energy
         self._anames = []
         self._angles = []
+        self._derivs = []
         self._periodic = False
 
     def getEnergyFunction(self):
@@ -504,6 +513,9 @@ class CustomAngleForce(Force, _GlobalParams):
     def getPerAngleParameterName(self, index):
         return self._anames[index]
 
+    def addEnergyParameterDerivative(self, name):
+        self._derivs.append(name)
+
     def addAngle(self, particle1, particle2, particle3, parameters=()):
         self._angles.append([int(particle1), int(particle2), int(particle3), [float(md_value(p)) for p in parameters]])
         return len(self._angles) - 1
@@ -514,6 +526,16 @@ class CustomAngleForce(Force, _GlobalParams):
     def getAngleParameters(self, index):
         i, j, k, p = self._angles[index]
         return [i, j, k, tuple(p)]
+
+    def setAngleParameters(self, index, particle1, particle2, particle3, parameters=()):
+        self._angles[index] = [int(particle1), int(particle2), int(particle3), [float(md_value(p)) for p in parameters]]
+
+    def setEnergyFunction(self, energy):
+        self._energy = energy
+
+    def updateParametersInContext(self, context):
+        """Upload the per-angle parameters again (the atoms and the number of angles must not have changed)."""
+        context._engine.update_force_parameters(self)
 
     def setUsesPeriodicBoundaryConditions(self, periodic):
         self._periodic = bool(periodic)
@@ -572,6 +594,111 @@ class PeriodicTorsionForce(Force):
 
     def usesPeriodicBoundaryConditions(self):
         return self._periodic
+
+
+class CustomTorsionForce(Force, _GlobalParams):
+    """Torsions with any energy text in `theta`, the dihedral angle in (-pi, pi] (PeriodicTorsionForce's convention)."""
+
+    def __init__(self, energy):
+        Force.__init__(self)
+        self._init_globals()
+        self._energy = energy
+        self._tnames = []
+        self._derivs = []
+        self._torsions = []
+        self._periodic = False
+
+    def getEnergyFunction(self):
+        return self._energy
+
+    def setEnergyFunction(self, energy):
+        self._energy = energy
+
+    def addPerTorsionParameter(self, name):
+        self._tnames.append(name)
+        return len(self._tnames) - 1
+
+    def getNumPerTorsionParameters(self):
+        return len(self._tnames)
+
+    def getPerTorsionParameterName(self, index):
+        return self._tnames[index]
+
+    def addEnergyParameterDerivative(self, name):
+        self._derivs.append(name)
+
+    def addTorsion(self, particle1, particle2, particle3, particle4, parameters=()):
+        self._torsions.append([int(particle1), int(particle2), int(particle3), int(particle4), [float(md_value(p)) for p in parameters]])
+        return len(self._torsions) - 1
+
+    def getNumTorsions(self):
+        return len(self._torsions)
+
+    def getTorsionParameters(self, index):
+        a, b, c, d, p = self._torsions[index]
+        return [a, b, c, d, tuple(p)]
+
+    def setTorsionParameters(self, index, particle1, particle2, particle3, particle4, parameters=()):
+        self._torsions[index] = [int(particle1), int(particle2), int(particle3), int(particle4), [float(md_value(p)) for p in parameters]]
+
+    def setUsesPeriodicBoundaryConditions(self, periodic):
+        self._periodic = bool(periodic)
+
+    def usesPeriodicBoundaryConditions(self):
+        return self._periodic
+
+    def updateParametersInContext(self, context):
+        """Upload the per-torsion parameters again (the atoms and the number of torsions must not have changed)."""
+        context._engine.update_force_parameters(self)
+
+
+class CustomExternalForce(Force, _GlobalParams):
+    """A force on single particles with any energy text in their coordinates x, y, z (as the positions give them: never periodic)."""
+
+    def __init__(self, energy):
+        Force.__init__(self)
+        self._init_globals()
+        self._energy = energy
+        self._pnames = []
+        self._particles = []
+        self._derivs = []
+
+    def getEnergyFunction(self):
+        return self._energy
+
+    def setEnergyFunction(self, energy):
+        self._energy = energy
+
+    def addPerParticleParameter(self, name):
+        self._pnames.append(name)
+        return len(self._pnames) - 1
+
+    def getNumPerParticleParameters(self):
+        return len(self._pnames)
+
+    def getPerParticleParameterName(self, index):
+        return self._pnames[index]
+
+    def addEnergyParameterDerivative(self, name):
+        self._derivs.append(name)
+
+    def addParticle(self, particle, parameters=()):
+        self._particles.append([int(particle), [float(md_value(p)) for p in parameters]])
+        return len(self._particles) - 1
+
+    def getNumParticles(self):
+        return len(self._particles)
+
+    def getParticleParameters(self, index):
+        i, p = self._particles[index]
+        return [i, tuple(p)]
+
+    def setParticleParameters(self, index, particle, parameters=()):
+        self._particles[index] = [int(particle), [float(md_value(p)) for p in parameters]]
+
+    def updateParametersInContext(self, context):
+        """Upload the per-particle parameters again (the atoms and the number of particles must not have changed)."""
+        context._engine.update_force_parameters(self)
 
 
 class CMMotionRemover(Force):
@@ -1088,7 +1215,7 @@ def molecules_of(system):
             pairs += [(b[0], b[1]) for b in force._bonds]
         elif isinstance(force, (HarmonicAngleForce, CustomAngleForce)):
             pairs += [(r[0], r[1]) for r in force._angles] + [(r[1], r[2]) for r in force._angles]
-        elif isinstance(force, PeriodicTorsionForce):
+        elif isinstance(force, (PeriodicTorsionForce, CustomTorsionForce)):
             pairs += [(r[0], r[1]) for r in force._torsions] + [(r[1], r[2]) for r in force._torsions] + \
                      [(r[2], r[3]) for r in force._torsions]
     for i, j in pairs:

@@ -252,6 +252,36 @@ int amm_bonded_set_sliced(amm_ctx *ctx, int32_t force_id, int32_t on);
  * leaves every group definition. */
 int amm_bonded_release(amm_ctx *ctx, int32_t force_id);
 
+/* CustomBondForce / CustomAngleForce / CustomTorsionForce / CustomExternalForce with ANY energy text (what OpenMM compiles with
+ * Lepton; the texts the reference ships are the kinds of amm_bonded_add_terms).  A force object of its own, an ordinary member of a
+ * group, evaluated through amm_force_eval; the amm_bonded_* calls refuse its id.  kind: what the text's variable is -- */
+typedef enum {
+    AMM_TERM_BOND = 0,       /* idx[2]: r = |x0 - x1|                                               */
+    AMM_TERM_ANGLE = 1,      /* idx[3]: theta in [0, pi] at atom 1 (the angle of AMM_ANGLE_HARMONIC)    */
+    AMM_TERM_TORSION = 2,    /* idx[4]: theta in (-pi, pi], the dihedral of AMM_TORSION_PERIODIC         */
+    AMM_TERM_EXTERNAL = 3    /* idx[1]: x, y, z of the atom as the positions give them (never wrapped)   */
+} amm_term_kind;
+#define AMM_TERM_MAX_PARAMS 8
+/* code / consts / globals: the program of atomsmm_amd.expr.compile_term -- the words of amm_pair_expr_create, but for its leaves:
+ * the term's variable k (opcode 53: r or theta is k = 0; x, y, z are k = 0, 1, 2) and the term's parameter k (54) instead of 50..52;
+ * the same limits (csrc/pair_expr_vm.h), checked here with a walk of the stack.  h_idx: n_terms x 4 atom indices, padded with -1
+ * behind the kind's arity; an index outside [0, n) is refused.  h_params: n_params x n_terms doubles, PARAMETER-major (all terms'
+ * parameter 0, then parameter 1 ...), n_params <= AMM_TERM_MAX_PARAMS; NULL when n_params = 0.  periodic: differences of positions
+ * take the minimum image (needs a context with a box; not for AMM_TERM_EXTERNAL).  Evaluation is deterministic: every term once
+ * (dE/dvariable comes with E from one forward-mode pass; an external term takes three), its forces parked per role, every atom then
+ * adds its records in term order; with accumulate = 0 every row of the buffer is written.  The forces of an evaluation with and
+ * without energy are the same numbers. */
+int amm_term_expr_create(amm_ctx *ctx, int32_t kind, const int32_t *code, int32_t ncode, const double *consts, int32_t nconst,
+                         const double *globals, int32_t nglobal, const int32_t *h_idx, const double *h_params, int32_t n_terms,
+                         int32_t n_params, int32_t periodic, int32_t *force_id);
+/* Context.setParameter(name, value) for a global parameter of such a force: all of the program's globals, in its order. */
+int amm_term_expr_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal);
+/* set*Parameters + updateParametersInContext: all per-term values again, laid out as at creation (same n_terms, n_params; the
+ * atoms of a term do not change). */
+int amm_term_expr_set_params(amm_ctx *ctx, int32_t force_id, const double *h_params, int32_t n_terms, int32_t n_params);
+/* Free such a force; as amm_bonded_release, the id is retired and leaves every group definition. */
+int amm_term_expr_release(amm_ctx *ctx, int32_t force_id);
+
 /* Reciprocal space of a NonbondedForce with nonbondedMethod PME / Ewald, as RESPASystem and FarNonbondedForce
  * keep it in group 2 with the source force's Ewald tolerance / PME parameters (systems.py:74-75,
  * forces.py:185-188; setReciprocalSpaceForceGroup: utils.py:147-152).  Smooth PME, B-spline order 5, grid
