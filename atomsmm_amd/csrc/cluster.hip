@@ -1017,6 +1017,53 @@ struct CPairArgs {
     double gfac, gsr;                  // (Kc sign)_guest / (Kc sign)_host ; sign_guest / sign_host
 };
 
+// The argument block of k_cpair, and how the kernel reads it.  The block is 1.7 KB; a trip of the walk reads a few dozen scalars of
+// it (table scale, shifts, bases and clamp of either force, the cutoffs, gfac, the sorted copies, cap, the box for the image
+// variants), the rest belongs to code that runs once per task, once per launch or never: the row prologue, the stores, the analytic
+// path below the tables, the epilogue.  Taken from by-value kernel arguments all of it is loaded at kernel entry and stays live across
+// the trip loops -- 166 scalars of the fused pass were parked in lanes of three VGPRs and 27 to 29 of them read back on every
+// trip (profiles/trip_loop_isa.txt).  So every piece of code reads what it needs from the block IN PLACE, in the
+// kernarg segment (scalar loads through the constant cache), at the point of use: cpair_args_here() hands out the block's address
+// plus an offset of zero that the compiler cannot see through (an empty asm), so the loads stay behind it -- out of the kernel's
+// entry and, for the cold code, out of the loop's live set.  What a walk reads is fetched at the head of its task.
+// (the kernel's first three arguments as the kernarg segment holds them: by-value arguments follow one another at their natural
+// alignment, as the members of a struct do; the epilogue's block, behind them, is indexed at run time and read as it always was)
+struct CPairKArgs {
+    CPairArgs A;
+    PairConsts c, g;
+};
+static_assert(alignof(CPairArgs) == 8 && alignof(PairConsts) == 8 && sizeof(CPairArgs) % 8 == 0 && sizeof(PairConsts) % 8 == 0,
+              "CPairKArgs must lay out k_cpair's arguments as the kernarg segment does");
+typedef const __attribute__((address_space(4))) CPairKArgs *CPairKArgsP;
+__device__ __forceinline__ CPairKArgsP cpair_args_here() {
+    int zero = 0;
+    asm volatile("" : "+s"(zero));
+    return (CPairKArgsP)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + zero);
+}
+// A wave-uniform value the trip loop selects between per lane (v_cndmask takes its two choices from vector registers: out of a
+// scalar register each is copied to one first, at every use) or has no scalar register left for: kept in a VGPR from here on
+template <bool ON = true, class T>
+__device__ __forceinline__ T cpair_in_vgpr(T x) {
+    if (ON) asm("" : "+v"(x));
+    return x;
+}
+#ifndef AMM_TRIP_VGPR          // measurement: 0 = nowhere
+#define AMM_TRIP_VGPR 1
+#endif
+// Which instantiations do so: those that have the ~11 vector registers.  The damped family with a general switching degree and the
+// fused pass of an Ewald-direct host whose sites are not the water pattern sit at 256 VGPRs with scratch either way, and every
+// register taken there is more scratch (profiles/trip_loop_isa.txt has both builds); they read their arguments in place like the rest.
+constexpr bool cpair_vgpr_room(int fam, int cmode, int gfam, int smask) {
+    return AMM_TRIP_VGPR != 0 && !(fam == AMM_DAMPED && cmode == 0) && !(fam == AMM_NONBONDED && cmode == 1 && gfam >= 0 && smask != 1);
+}
+// a member of the block as a local object: only the fields the caller goes on to read are loaded
+template <class T>
+__device__ __forceinline__ T cpair_arg_copy(const __attribute__((address_space(4))) T *src) {
+    T out;
+    __builtin_memcpy(&out, src, sizeof(T));
+    return out;
+}
+
 // One walk of a wavefront's rows.  IMG: 0 interior rows (no periodic image), 1 one image per molecule pair (from the first
 // atoms), 2 minimum image per atom pair.  GFAM >= 0: the fused step-boundary pass (below).  SS: site-site tables.
 //
@@ -1050,17 +1097,26 @@ struct CPairArgs {
 template <int FAM, int CMODE, int GFAM, int IMG, int SMASK>
 __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts &c, const PairConsts &g, const char *tabh, const char *tabg,
                                            const double *erfcx, const double4 (&pi)[3], const double2 *li, int i_sites, const int (&so)[3],
-                                           const int (&sog)[3], double sign_lj, const int *row, int nfront, int nn, int sub, int lpa,
+                                           const int (&sog)[3], const int *row, int nfront, int nn, int sub, int lpa_s,
                                            int self, double (&f)[9], double (&fg)[9] CWALK_T_PARAM) {
     constexpr bool DUAL = GFAM >= 0;
     constexpr bool SS = SMASK != 0;          // SMASK: the row atoms that can be sites (1: only the first -- water; 7: any)
+    // The trip stride and the base of the sorted copies are read once per trip, by vector instructions: in scalar registers they
+    // were the two values the fused pass still read back from parked lanes on every trip.  The pointer travels as an integer and
+    // comes back as a pointer to GLOBAL memory, so that the gathers stay global loads (through a generic pointer: flat loads).
+    typedef double cwalk_d4 __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(1))) char *cwalk_gptr;
+    constexpr bool VRES = cpair_vgpr_room(FAM, CMODE, GFAM, SMASK);
+    const int lpa = cpair_in_vgpr<VRES>(lpa_s);
+    const cwalk_gptr posq = (cwalk_gptr)cpair_in_vgpr<VRES>((unsigned long long)A.posq);
     const int back = A.cap - 1 + nfront;
     // closer pairs are left out of the main path and redone analytically below (never in a liquid)
     const double r2low = DUAL ? fmax(c.tab.r2min, g.tab.r2min) : c.tab.r2min;
     const double r2low_ss = DUAL ? fmax(c.tab.ss_r2min, g.tab.ss_r2min) : c.tab.ss_r2min;
     auto entry = [&](int k) { return k < nn ? row[k < nfront ? k : back - k] : self; };
     auto load_pos = [&](int e, int b) {
-        return *reinterpret_cast<const double4 *>(reinterpret_cast<const char *>(A.posq) + (size_t)((unsigned)e & 0x1fffffffu) * 96u + 32 * b);
+        const cwalk_d4 p = *(const __attribute__((address_space(1))) cwalk_d4 *)(posq + (size_t)((unsigned)e & 0x1fffffffu) * 96u + 32 * b);
+        return make_double4(p.x, p.y, p.z, p.w);
     };
     auto load_lj = [&](int e, int b) {
         // the Lennard-Jones record only of partner atoms that have a site in some entry of this trip (wave-uniform)
@@ -1080,6 +1136,7 @@ __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts 
     }
     while (__builtin_amdgcn_ballot_w64(k < nn) != 0ull) {
         const bool ok = k < nn;
+        const unsigned long long okm = __builtin_amdgcn_ballot_w64(ok);
         const bool front = k < nfront;
         const bool any_front = DUAL && __builtin_amdgcn_ballot_w64(front) != 0ull;
         const unsigned bits = (unsigned)e >> 29;
@@ -1132,17 +1189,29 @@ __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts 
                         }
                     }
             }
+            // (is any lane low?  One force: 64-bit masks beside the lane conditions -- the ballot of a comparison IS the comparison's
+            // result, and masks are combined and tested on the scalar unit, where the ballot of a combined lane condition is rebuilt
+            // in a VGPR first, two vector instructions.  The fused pass has no scalar registers for the masks: six lane reloads per trip)
+            constexpr bool LOW_MASKS = !DUAL;
+            unsigned long long lowm = 0ull;
             bool any_low = false;
             bool lowp[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                bool low = r2[a] < r2low;
-                // (a site pair below its own table; no branch here: a branch in this loop costs more than it skips)
-                if ((SMASK >> a) & 1) low = low || ((so[a] & mb) != 0 && r2[a] < r2low_ss);
+                const bool low_c = r2[a] < r2low;
+                bool low = low_c;
+                if (LOW_MASKS) lowm |= __builtin_amdgcn_ballot_w64(low_c);
+                // (a site pair below its own table; no branch here: a branch in this loop costs more than it skips -- lane conditions
+                // are combined with & and |, which stay lane masks on the scalar unit: && and || become branches around the second test)
+                if ((SMASK >> a) & 1) {
+                    const bool site_pair = (so[a] & mb) != 0, low_ss = r2[a] < r2low_ss;
+                    low = low | (site_pair & low_ss);
+                    if (LOW_MASKS) lowm |= __builtin_amdgcn_ballot_w64(site_pair) & __builtin_amdgcn_ballot_w64(low_ss);
+                }
                 lowp[a] = low;
-                const bool pass = ok && (r2[a] < c.rc2);
-                any_low = any_low || (ok && low);
-                const double fh = (pass && !low) ? fr[a] : 0.0;
+                const bool pass = ok & (r2[a] < c.rc2) & !low;
+                if (!LOW_MASKS) any_low = any_low | (ok & low);
+                const double fh = pass ? fr[a] : 0.0;
                 f[3 * a] += fh * dx[a];
                 f[3 * a + 1] += fh * dy[a];
                 f[3 * a + 2] += fh * dz[a];
@@ -1156,8 +1225,12 @@ __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts 
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int a = 0; a < 3; ++a) {
-                        const double gr = amm_sum_unfused(((pi[a].w * qb) * A.gfac) * amm_tab_horner(tg[a]), gl[a]);
-                        const bool pass = front && (r2[a] < g.rc2) && !lowp[a];
+                        // (gl: the analytic Lennard-Jones part, which only the kernels without site-site tables have.  With the
+                        // tables the sum was `+ 0.0`, which turns a product of -0 into +0 and nothing else -- and the product enters
+                        // fg, which starts at +0 and so is never -0, through an FMA: the same bits without the add)
+                        double gr = ((pi[a].w * qb) * A.gfac) * amm_tab_horner(tg[a]);
+                        if (!SS) gr = amm_sum_unfused(gr, gl[a]);
+                        const bool pass = front & (r2[a] < g.rc2) & !lowp[a];
                         const double gh = pass ? gr : 0.0;
                         fg[3 * a] += gh * dx[a];
                         fg[3 * a + 1] += gh * dy[a];
@@ -1165,7 +1238,13 @@ __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts 
                     }
                 }
             }
-            if (__builtin_amdgcn_ballot_w64(any_low) != 0ull) {       // closer than a table reaches: analytic
+            if (LOW_MASKS ? (lowm & okm) != 0ull : __builtin_amdgcn_ballot_w64(any_low) != 0ull) {       // closer than a table reaches: analytic
+                // (never in a liquid: what only this path reads of the argument block is read here, not carried through the walk)
+                const CPairKArgsP K = cpair_args_here();
+                const CPairArgs A = cpair_arg_copy(&K->A);
+                PairConsts c = cpair_arg_copy(&K->c), g = cpair_arg_copy(&K->g);
+                const double sign_lj = c.sign;
+                c.sign = g.sign = 1.0;          // (as the caller's: the sign travels with the row atoms' charges and epsilons)
                 for (int a = 0; a < 3; ++a) {
                     const bool low = ok && lowp[a];
                     double sg, e4;
@@ -1570,7 +1649,8 @@ __device__ __forceinline__ int cscan_counts(int ncell, const int *count, int *st
 // kernels with site-site tables need neither strips nor -- in LDS -- the erfcx table (their rare analytic path reads it from HBM)
 template <int FAM, int CMODE, int GFAM, int BS, int SMASK, bool EPI = false>
 __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(AMM_CTAB_WAVES_PER_EU)))
-k_cpair(CPairArgs A, PairConsts c, PairConsts g, CEpiArgs E) {
+k_cpair(CPairArgs A_, PairConsts c_, PairConsts g_, CEpiArgs E) {
+    // (A_, c_, g_: read in place through cpair_args_here(), piece by piece where they are used -- see CPairKArgs)
     constexpr bool DUAL = GFAM >= 0;
     constexpr bool SS = SMASK != 0;
     extern __shared__ __align__(16) char s_lds[];
@@ -1585,10 +1665,14 @@ k_cpair(CPairArgs A, PairConsts c, PairConsts g, CEpiArgs E) {
 #endif
     constexpr int WPB = BS / 64;
     const int lane = threadIdx.x & 63;
-    const double sign = c.sign;
     // one contiguous eighth of the rows per XCD (blockIdx & 7): consecutive cell-sorted rows = one slab of the box per L2
     const int xcd = blockIdx.x & 7, nwx = (gridDim.x >> 3) * WPB;
-    const int row_end = min((xcd + 1) * A.rpx, A.nrows);
+    int row_end, rpx;
+    {
+        const CPairKArgsP K = cpair_args_here();
+        rpx = K->A.rpx;
+        row_end = min((xcd + 1) * rpx, K->A.nrows);
+    }
 #ifdef AMM_CPAIR_SWAP          // measurement: which tasks the last four wavefronts of a block take (is their lag theirs or their rows'?)
     const int wave = (int)(threadIdx.x >> 6) ^ 4;
 #else
@@ -1599,11 +1683,13 @@ k_cpair(CPairArgs A, PairConsts c, PairConsts g, CEpiArgs E) {
     // The wavefront's tasks: task0, task0 + nwx ... of phase 0, then the same of phase 1 ...  `seek` stops at the next one there is.
     int phase = 0, task = task0;
     auto seek = [&]() {
-        while (phase < A.nphase && task >= A.ph_ntask[phase]) {
+        const CPairKArgsP K = cpair_args_here();
+        const int nphase = K->A.nphase;
+        while (phase < nphase && task >= K->A.ph_ntask[phase]) {
             ++phase;
             task = task0;
         }
-        return phase < A.nphase;
+        return phase < nphase;
     };
     // A task's row prologue: the row atoms' records, the rows' lengths and places in the list -- the first of the three dependent
     // round trips to memory a walk begins with (the lanes' first entries and the first partner's records follow inside
@@ -1622,36 +1708,47 @@ k_cpair(CPairArgs A, PairConsts c, PairConsts g, CEpiArgs E) {
     double4 pi[3];
     double2 pl[3];
     auto pre_rows = [&]() {
-        shift = A.ph_shift[phase];
+        const CPairKArgsP K = cpair_args_here();
+        const double4 *posq = K->A.posq;
+        const double2 *ljp = K->A.lj;
+        const int *nnb = K->A.nnb, *nnb_total = K->A.nnb_total;
+        shift = K->A.ph_shift[phase];
         lpa = 1 << shift;
         sub = lane & (lpa - 1);
-        a = xcd * A.rpx + A.ph_off[phase] + task * (64 >> shift) + (lane >> shift);
+        a = xcd * rpx + K->A.ph_off[phase] + task * (64 >> shift) + (lane >> shift);
         valid = a < row_end;
-        cs = A.c_begin + (valid ? a : 0);
+        cs = K->A.c_begin + (valid ? a : 0);
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
-            pi[t] = A.posq[3 * cs + t];
-            pl[t] = A.lj[3 * cs + t];
+            pi[t] = posq[3 * cs + t];
+            pl[t] = ljp[3 * cs + t];
         }
-        nfront = valid ? A.nnb[a] : 0;
-        nn = valid ? (A.nnb_total ? A.nnb_total[a] : nfront) : 0;
-        row = A.nl + (size_t)(valid ? a : 0) * A.cap;
+        nfront = valid ? nnb[a] : 0;
+        nn = valid ? (nnb_total ? nnb_total[a] : nfront) : 0;
+        row = K->A.nl + (size_t)(valid ? a : 0) * K->A.cap;
     };
     bool has = seek();
     if (AHEAD && has) pre_rows();
 
     // the tables: one image in global memory, laid out as LDS is (cpair_tab_image); 20 pieces of BS x 16 bytes are the 160 KB of a CU
-    const int used = A.host_bytes + (DUAL ? A.guest_bytes : 0) + (SS ? A.host_ss_bytes + (DUAL ? A.guest_ss_bytes : 0) : 0);
-    double2 tabs[(160 * 1024) / (BS * 16)];
-    amm_stage_issue<BS>(tabs, A.tab_image, used);
-    amm_stage_commit<BS>(tabs, s_lds, used);
-    amm_stage_rest<BS>(tabs, A.tab_image, s_lds, used);
+    const char *tabh, *tabg;
+    int used;
+    {
+        const CPairKArgsP K = cpair_args_here();
+        const int host_bytes = K->A.host_bytes;
+        used = host_bytes + (DUAL ? K->A.guest_bytes : 0) + (SS ? K->A.host_ss_bytes + (DUAL ? K->A.guest_ss_bytes : 0) : 0);
+        const double *tab_image = K->A.tab_image;
+        double2 tabs[(160 * 1024) / (BS * 16)];
+        amm_stage_issue<BS>(tabs, tab_image, used);
+        amm_stage_commit<BS>(tabs, s_lds, used);
+        amm_stage_rest<BS>(tabs, tab_image, s_lds, used);
 #if defined(AMM_EXP_TAB_GLOBAL)           // measurement only: the table is read through the vector-memory path instead of LDS
-    const char *tabh = reinterpret_cast<const char *>(A.host_tab);
+        tabh = reinterpret_cast<const char *>(K->A.host_tab);
 #else
-    const char *tabh = s_lds;
+        tabh = s_lds;
 #endif
-    const char *tabg = s_lds + A.host_bytes;
+        tabg = s_lds + host_bytes;
+    }
     const double *erfcx = amm_erfcx_table_dev_c;
     double2 *s_li = nullptr;
     if (!SS) {
@@ -1666,11 +1763,27 @@ k_cpair(CPairArgs A, PairConsts c, PairConsts g, CEpiArgs E) {
     t_staged = wall_clock64();
 #endif
 
-    PairConsts c1 = c, g1 = g;
-    c1.sign = 1.0;          // the sign travels with the row atoms' charges and epsilons (every family is linear in both)
-    g1.sign = 1.0;
     while (has) {
         if (!AHEAD) pre_rows();
+        // what this task's walk reads of the argument block (the compiler loads the fields the walk uses, here)
+        const CPairKArgsP K = cpair_args_here();
+        const CPairArgs A = cpair_arg_copy(&K->A);
+        PairConsts c1 = cpair_arg_copy(&K->c), g1 = cpair_arg_copy(&K->g);
+        const double sign = c1.sign, Kc = c1.Kc;
+        c1.sign = 1.0;          // the sign travels with the row atoms' charges and epsilons (every family is linear in both)
+        g1.sign = 1.0;
+        // the look-up's per-lane choices between zone A and zone B of a table (amm_tab_fetch: shift, base, half width)
+        constexpr bool VRES = cpair_vgpr_room(FAM, CMODE, GFAM, SMASK);
+        c1.tab.shiftB = cpair_in_vgpr<VRES>(c1.tab.shiftB);
+        c1.tab.rawB_minus_nA = cpair_in_vgpr<VRES>(c1.tab.rawB_minus_nA);
+        c1.tab.baseA = cpair_in_vgpr<VRES>(c1.tab.baseA);
+        c1.tab.halfB = cpair_in_vgpr<VRES>(c1.tab.halfB);
+        if (DUAL) {
+            g1.tab.shiftB = cpair_in_vgpr<VRES>(g1.tab.shiftB);
+            g1.tab.rawB_minus_nA = cpair_in_vgpr<VRES>(g1.tab.rawB_minus_nA);
+            g1.tab.baseA = cpair_in_vgpr<VRES>(g1.tab.baseA);
+            g1.tab.halfB = cpair_in_vgpr<VRES>(g1.tab.halfB);
+        }
         // (the task's own: the prologue of the next one overwrites them behind the walk)
         const int t_a = a, t_cs = cs, t_sub = sub, t_lpa = lpa;
         const bool t_valid = valid;
@@ -1679,7 +1792,7 @@ k_cpair(CPairArgs A, PairConsts c, PairConsts g, CEpiArgs E) {
         if (!SS) __builtin_amdgcn_wave_barrier();        // the previous task's reads of the strip are done
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
-            pi[t].w *= c.Kc * sign;
+            pi[t].w *= Kc * sign;
             double2 l = pl[t];
             l.y *= sign;
             if (!SS) s_li[64 * t + lane] = l;
@@ -1706,9 +1819,9 @@ k_cpair(CPairArgs A, PairConsts c, PairConsts g, CEpiArgs E) {
         double f[9], fg[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) f[k] = fg[k] = 0.0;
-        if (A.per_pair_image) cwalk_rows<FAM, CMODE, GFAM, 2, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, sign, row, nfront, nn, sub, lpa, cs, f, fg CWALK_T_ARG);
-        else if (interior) cwalk_rows<FAM, CMODE, GFAM, 0, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, sign, row, nfront, nn, sub, lpa, cs, f, fg CWALK_T_ARG);
-        else cwalk_rows<FAM, CMODE, GFAM, 1, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, sign, row, nfront, nn, sub, lpa, cs, f, fg CWALK_T_ARG);
+        if (A.per_pair_image) cwalk_rows<FAM, CMODE, GFAM, 2, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, row, nfront, nn, sub, lpa, cs, f, fg CWALK_T_ARG);
+        else if (interior) cwalk_rows<FAM, CMODE, GFAM, 0, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, row, nfront, nn, sub, lpa, cs, f, fg CWALK_T_ARG);
+        else cwalk_rows<FAM, CMODE, GFAM, 1, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, row, nfront, nn, sub, lpa, cs, f, fg CWALK_T_ARG);
         task += nwx;
         has = seek();
         if (AHEAD && has) pre_rows();
@@ -1720,17 +1833,21 @@ k_cpair(CPairArgs A, PairConsts c, PairConsts g, CEpiArgs E) {
             }
         }
         if (t_valid && t_sub == 0) {
+            const CPairKArgsP Ks = cpair_args_here();
+            const int sorted_out = Ks->A.sorted_out, accumulate = Ks->A.accumulate, g_accumulate = Ks->A.g_accumulate;
+            const int *aperm = Ks->A.aperm;
+            double *force = Ks->A.force, *gforce = Ks->A.gforce;
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
-                const int i = A.sorted_out ? 3 * t_a + t : A.aperm[3 * t_cs + t];
+                const int i = sorted_out ? 3 * t_a + t : aperm[3 * t_cs + t];
 #pragma unroll
                 for (int d = 0; d < 3; ++d) {
                     // (host first: when both forces go to the same buffer the guest adds to what the host just wrote)
-                    if (A.accumulate) A.force[3 * i + d] += f[3 * t + d];
-                    else A.force[3 * i + d] = f[3 * t + d];
+                    if (accumulate) force[3 * i + d] += f[3 * t + d];
+                    else force[3 * i + d] = f[3 * t + d];
                     if (DUAL) {
-                        if (A.g_accumulate) A.gforce[3 * i + d] += fg[3 * t + d];
-                        else A.gforce[3 * i + d] = fg[3 * t + d];
+                        if (g_accumulate) gforce[3 * i + d] += fg[3 * t + d];
+                        else gforce[3 * i + d] = fg[3 * t + d];
                     }
                 }
             }
@@ -1745,16 +1862,19 @@ k_cpair(CPairArgs A, PairConsts c, PairConsts g, CEpiArgs E) {
         // forces were stored by the first lane of each row; the molecule's lanes read them back (wavefront-scope ordering: the
         // stores have left the wavefront before the loads are issued; one L1 serves both)
         // (the ordering fence sits inside cepi_rows, behind the loads that do not depend on this launch's forces)
-        for (int phase = 0; phase < A.nphase; ++phase) {
-            const int shift = A.ph_shift[phase], row0 = xcd * A.rpx + A.ph_off[phase], ntask = A.ph_ntask[phase];
+        const CPairKArgsP K = cpair_args_here();
+        const int nphase = K->A.nphase, c_begin = K->A.c_begin;
+        const Box box = cpair_arg_copy(&K->A.box);
+        for (int phase = 0; phase < nphase; ++phase) {
+            const int shift = K->A.ph_shift[phase], row0 = xcd * rpx + K->A.ph_off[phase], ntask = K->A.ph_ntask[phase];
             const int rpw = 64 >> shift;
             for (int task = (int)(blockIdx.x >> 3) * WPB + (int)(threadIdx.x >> 6); task < ntask; task += nwx) {
                 const int a = row0 + task * rpw + (lane >> shift);
                 const bool valid = a < row_end;
 #ifdef AMM_CPAIR_TIMING
-                cepi_rows(E, A.box, A.c_begin + (valid ? a : 0), valid, lane & ((1 << shift) - 1), t_epi);
+                cepi_rows(E, box, c_begin + (valid ? a : 0), valid, lane & ((1 << shift) - 1), t_epi);
 #else
-                cepi_rows(E, A.box, A.c_begin + (valid ? a : 0), valid, lane & ((1 << shift) - 1));
+                cepi_rows(E, box, c_begin + (valid ? a : 0), valid, lane & ((1 << shift) - 1));
 #endif
             }
         }
@@ -1768,8 +1888,8 @@ k_cpair(CPairArgs A, PairConsts c, PairConsts g, CEpiArgs E) {
         }
     }
 #ifdef AMM_CPAIR_TIMING
-    if (A.wave_times && (threadIdx.x & 63) == 0) {
-        unsigned long long *o = A.wave_times + 4 * ((size_t)blockIdx.x * (BS / 64) + (threadIdx.x >> 6));
+    if (A_.wave_times && (threadIdx.x & 63) == 0) {
+        unsigned long long *o = A_.wave_times + 4 * ((size_t)blockIdx.x * (BS / 64) + (threadIdx.x >> 6));
         o[0] = t_entry;
         o[1] = t_staged;
         o[2] = wall_clock64();
