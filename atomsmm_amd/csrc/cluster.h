@@ -18,6 +18,8 @@
 #pragma once
 #include "amm_ctx.h"
 
+struct CBuildTab;                  // a cell's stencil tables for the list build (cluster.hip)
+
 struct ClusterList {
     int nc = 0;                    // molecules (clusters of 3 atoms: first[m], first[m] + 1, first[m] + 2)
     const int *d_first = nullptr;  // first atom of every molecule (the force's); nullptr: 3 m (every atom of the force is in a molecule)
@@ -32,6 +34,7 @@ struct ClusterList {
     double rext = 0;               // bound on the distance of a molecule's atoms from its first atom (cells, interior margin)
     double rlist_build = 0, rnear_build = 0, skin = 0;
     int *d_cell_count = nullptr, *d_cell_start = nullptr, *d_cell_members = nullptr;
+    CBuildTab *d_build_tabs = nullptr;    // [ncell] written by the rebuild's sort launch, read by every wavefront of the cell in the build
     int *d_cperm = nullptr;        // sorted cluster -> molecule
     int *d_aperm = nullptr;        // sorted atom slot (3 c + a) -> atom (3 m + a): what k_unsort and the stores index with
     float4 *d_pos4f = nullptr;     // [3 nc] fp32 positions at the last build, molecules kept whole; .w: atom 0 extent, atom 1 site bits

@@ -147,16 +147,103 @@ __device__ __forceinline__ void cgather_one(int c, int i0, const double *__restr
     }
 }
 
+// ---- stencil tables of a cell (list build, below) ----
+// The candidate stream of a cell's row molecules is the concatenation of its stencil's cells ("pieces", x fastest, <= 125).  What
+// the build needs to walk it depends on the cell and on cell_start alone, so the rebuild's sort launch makes it ONCE per cell and
+// every wavefront of the cell (`parts` of them) loads it:
+//   rstart[e]   first sorted slot of piece e
+//   rpref[e]    stream position where piece e starts (exclusive prefix of the lengths; beyond the stencil: `total`)
+//   coarse[i]   the piece of stream position i << cshift (the last piece that starts at or before it)
+//   code[l]     periodic shift of the pieces l (low byte) and l + 64 (high byte): two bits per axis, 0 / 1 / 2 = -L / 0 / +L
+#define CB_COARSE 256       // entries of the coarse piece table
+#ifndef CB_HALF_DRAIN
+#define CB_HALF_DRAIN 1     // a row's leftover of <= 64 survivors is drained one per lane (0: always the packed two-halves form)
+#endif
+struct alignas(16) CBuildTab {
+    int rstart[128];
+    int rpref[128];
+    unsigned char coarse[CB_COARSE];
+    unsigned short code[64];
+    int total, cshift, pad[2];
+};
+static_assert(sizeof(CBuildTab) == 1424 && offsetof(CBuildTab, rpref) == 512 && offsetof(CBuildTab, coarse) == 1024, "k_cbuild loads the record in 16-byte pieces");
+
+__device__ __forceinline__ float cshift_of(int code2, float L) { return code2 == 0 ? -L : (code2 == 2 ? L : 0.f); }
+
+// one whole wavefront makes the record of cell c; s_pref: 128 ints of LDS of the wavefront's own (the coarse table searches them)
+__device__ __forceinline__ void cbuild_tables(int c, int lane, const CellGrid &g, const int *__restrict__ cell_start, int *s_pref, CBuildTab *out) {
+    const int ncx = g.nc[0], ncy = g.nc[1], ncz = g.nc[2];
+    const int cx = c % ncx, cy = (c / ncx) % ncy, cz = c / (ncx * ncy);
+    // ---- piece table: a lane describes the stencil cells e = lane and lane + 64 (<= 125), x fastest ----
+    const int nsx = g.nstencil[0], nsy = g.nstencil[1], ne = nsx * nsy * g.nstencil[2];
+    int ecs[2] = {0, 0}, len[2] = {0, 0}, inc[2], code[2] = {0x15, 0x15};
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+        const int e = lane + 64 * hh;
+        if (e < ne) {
+            const int ox = e % nsx, oy = (e / nsx) % nsy, oz = e / (nsx * nsy);
+            int nz = ncz < 2 * g.h[2] + 1 ? oz : cz - g.h[2] + oz;
+            const int kz = nz < 0 ? 0 : (nz >= ncz ? 2 : 1);
+            nz = nz < 0 ? nz + ncz : (nz >= ncz ? nz - ncz : nz);
+            int ny = ncy < 2 * g.h[1] + 1 ? oy : cy - g.h[1] + oy;
+            const int ky = ny < 0 ? 0 : (ny >= ncy ? 2 : 1);
+            ny = ny < 0 ? ny + ncy : (ny >= ncy ? ny - ncy : ny);
+            int nx = ncx < 2 * g.h[0] + 1 ? ox : cx - g.h[0] + ox;
+            const int kx = nx < 0 ? 0 : (nx >= ncx ? 2 : 1);
+            nx = nx < 0 ? nx + ncx : (nx >= ncx ? nx - ncx : nx);
+            const int cc = (nz * ncy + ny) * ncx + nx;
+            ecs[hh] = cell_start[cc];
+            len[hh] = cell_start[cc + 1] - ecs[hh];
+            code[hh] = kx | (ky << 2) | (kz << 4);
+        }
+        inc[hh] = len[hh];
+        for (int off = 1; off < 64; off <<= 1) {
+            const int v = __shfl_up(inc[hh], off);
+            if (lane >= off) inc[hh] += v;
+        }
+    }
+    const int lower = __builtin_amdgcn_readlane(inc[0], 63);
+    const int total = lower + __builtin_amdgcn_readlane(inc[1], 63);
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+        const int pref = (hh ? lower : 0) + inc[hh] - len[hh];       // exclusive prefix; beyond the stencil: `total`
+        out->rstart[lane + 64 * hh] = ecs[hh];
+        out->rpref[lane + 64 * hh] = pref;
+        s_pref[lane + 64 * hh] = pref;
+    }
+    out->code[lane] = (unsigned short)(code[0] | (code[1] << 8));
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // coarse table: the piece of every (1 << cshift)-th stream position (the last piece that starts at or before it)
+    int cshift = 3;
+    while (((total + 127) >> cshift) > CB_COARSE) ++cshift;
+#pragma unroll
+    for (int q = 0; q < CB_COARSE / 64; ++q) {
+        const int idx = (lane + 64 * q) << cshift;
+        int r = 0;
+#pragma unroll
+        for (int step = 64; step > 0; step >>= 1)
+            if (s_pref[r + step] <= idx) r += step;
+        out->coarse[lane + 64 * q] = (unsigned char)r;
+    }
+    if (lane == 0) {
+        out->total = total;
+        out->cshift = cshift;
+    }
+}
+
 // rebuild: one wavefront per cell ranks the cell's molecules by index (deterministic whatever the atomics did), writes the
-// permutation, the fp32 copies with extent and site bits, and the fp64 sorted copies of the evaluation that follows.
-// No rebuild: only those fp64 copies.
+// permutation, the fp32 copies with extent and site bits, the fp64 sorted copies of the evaluation that follows and the cell's
+// stencil tables for the list build.  No rebuild: only those fp64 copies.
 __global__ void __launch_bounds__(256) k_csort_gather(int ncell, int nc, const int *__restrict__ start, const int *__restrict__ members,
                                                       int capc, int *cperm, int *aperm, const double *__restrict__ pos, Box box,
                                                       float4 *pos4f, const int *flags, int *wflags, int force, const double *__restrict__ q,
                                                       const double *__restrict__ hsig, const double *__restrict__ seps2, double4 *posq_s,
                                                       double2 *lj_s, float rext, const double *__restrict__ site_eps,
                                                       const int *__restrict__ first, CZeroRows Z, int copies_current, double *xref,
-                                                      int c_begin, int c_end, int *slice_cells) {
+                                                      int c_begin, int c_end, int *slice_cells, CellGrid g, CBuildTab *tabs) {
+    __shared__ int s_pref[4][128];
     const int gid = blockIdx.x * blockDim.x + threadIdx.x;
     // (hybrid lists: the force rows of the atoms outside the molecules start from zero; the molecule-row kernel writes the others
     // and the per-atom part adds to all of them -- a launch of its own before)
@@ -232,6 +319,7 @@ __global__ void __launch_bounds__(256) k_csort_gather(int ncell, int nc, const i
         pos4f[3 * sl + 1] = pf[1];
         pos4f[3 * sl + 2] = pf[2];
     }
+    cbuild_tables(__builtin_amdgcn_readfirstlane(wave), lane, g, start, s_pref[threadIdx.x >> 6], tabs + wave);
 }
 
 struct CBoxF {
@@ -249,13 +337,13 @@ struct CBoxF {
 //      candidate, the nine atom-pair distances, the smallest decides (< rlist: listed; < rnear: front part), ordered ballot
 //      compaction into the row.
 // A candidate's piece of the stream (which stencil cell, hence which periodic shift) comes from a coarse table (piece of every
-// 8th stream position, built once per wavefront) + a short walk, not from a binary search per candidate.
+// 8th stream position) + a short walk, not from a binary search per candidate.  Piece table, shifts and coarse table are the cell's
+// record (CBuildTab above: made once per rebuild by the cell's wavefront of the sort launch), copied to LDS by every wavefront of the cell.
 // The old per-atom build spent 42 instructions per 64 ATOM-pair tests, mostly compaction; here the compaction is paid per
 // MOLECULE pair and only for a stream that is already 80 % hits.
 #ifndef CB_BATCH
 #define CB_BATCH 5
 #endif
-#define CB_COARSE 256       // entries of the coarse piece table
 #define CB_QCAP 256         // ring of survivors per row molecule: >= 127 + 128 (a drain leaves at most 127 behind, a chunk pair adds 128)
 __device__ __forceinline__ int cq_wrap(int i) { return i & (CB_QCAP - 1); }
 typedef float v2f __attribute__((ext_vector_type(2)));        // two fp32 per lane: v_pk_add / v_pk_mul / v_pk_fma_f32 at the rate of one
@@ -320,13 +408,14 @@ template <bool COUNT_ONLY, bool RINT, bool SLICE = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLICE ? 3 : CB_WAVES))) k_cbuild(int c_begin, int c_end, int parts, const int *__restrict__ cell_start,
                                                 const float4 *__restrict__ pos4f, CBoxF box, CellGrid g, float rlist, float rnear2, int cap,
                                                 int *nl, int *nnb, int *nnb_near, int *flags, unsigned long long *blockstats,
-                                                unsigned long long *counters, int *ticket, int force, const int *slice_cells) {
+                                                unsigned long long *counters, int *ticket, int force, const int *slice_cells,
+                                                const CBuildTab *__restrict__ tabs) {
     if (!force && !flags[0]) return;
-    __shared__ int s_rstart[4][128];
-    __shared__ int s_rpref[4][128];
+    __shared__ __attribute__((aligned(16))) int s_rstart[4][128];
+    __shared__ __attribute__((aligned(16))) int s_rpref[4][128];
     __shared__ float s_rshift[4][3][128];
     __shared__ int s_q[4][CB_BATCH][CB_QCAP];        // per row molecule: ring of survivors of the sphere test (sorted slots)
-    __shared__ unsigned char s_coarse[4][CB_COARSE]; // piece of stream position e << cshift
+    __shared__ __attribute__((aligned(16))) unsigned char s_coarse[4][CB_COARSE]; // piece of stream position e << cshift
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
     const float FAR = 1.0e9f;
@@ -349,64 +438,23 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLICE 
         a_end = min(min(cb0 + (part + 1) * per, cb1), c_end);
     }
     if (a_begin < a_end) {
-        const int ncx = g.nc[0], ncy = g.nc[1], ncz = g.nc[2];
-        const int cx = c % ncx, cy = (c / ncx) % ncy, cz = c / (ncx * ncy);
-        // ---- piece table: a lane describes the stencil cells e = lane and lane + 64 (<= 125), x fastest ----
-        const int nsx = g.nstencil[0], nsy = g.nstencil[1], ne = nsx * nsy * g.nstencil[2];
-        int total;
-        {
-            int ecs[2] = {0, 0}, len[2] = {0, 0}, inc[2];
-            float esx[2] = {0.f, 0.f}, esy[2] = {0.f, 0.f}, esz[2] = {0.f, 0.f};
+        // ---- the cell's stencil tables (cbuild_tables, made by the sort launch of this rebuild) into LDS: 16 bytes of the piece
+        // table, 4 of the coarse table and the shift codes of two pieces per lane; the first batch's atoms ride the same round trip ----
+        const CBuildTab *__restrict__ tab = tabs + c;
+        const int total = __builtin_amdgcn_readfirstlane(tab->total), cshift = __builtin_amdgcn_readfirstlane(tab->cshift);
+        const int4 tab_rp = reinterpret_cast<const int4 *>(tab->rstart)[lane];          // (rstart and rpref are one run of 1 024 bytes)
+        const int tab_co = reinterpret_cast<const int *>(tab->coarse)[lane];
+        const int tab_code = tab->code[lane];
+        // (an unconditional load, of a slot of the batch for every lane: the table loads ahead of it are then waited for alone)
+        const int nt0 = min(CB_BATCH, a_end - a_begin);
+        float4 my = pos4f[3 * a_begin + min(lane, 3 * nt0 - 1)];
+        if (lane >= 3 * nt0) my = make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<int4 *>(lane < 32 ? &s_rstart[w][4 * lane] : &s_rpref[w][4 * (lane - 32)]) = tab_rp;
+        reinterpret_cast<int *>(s_coarse[w])[lane] = tab_co;
 #pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                const int e = lane + 64 * hh;
-                if (e < ne) {
-                    const int ox = e % nsx, oy = (e / nsx) % nsy, oz = e / (nsx * nsy);
-                    int nz = ncz < 2 * g.h[2] + 1 ? oz : cz - g.h[2] + oz;
-                    esz[hh] = nz < 0 ? -box.L[2] : (nz >= ncz ? box.L[2] : 0.f);
-                    nz = nz < 0 ? nz + ncz : (nz >= ncz ? nz - ncz : nz);
-                    int ny = ncy < 2 * g.h[1] + 1 ? oy : cy - g.h[1] + oy;
-                    esy[hh] = ny < 0 ? -box.L[1] : (ny >= ncy ? box.L[1] : 0.f);
-                    ny = ny < 0 ? ny + ncy : (ny >= ncy ? ny - ncy : ny);
-                    int nx = ncx < 2 * g.h[0] + 1 ? ox : cx - g.h[0] + ox;
-                    esx[hh] = nx < 0 ? -box.L[0] : (nx >= ncx ? box.L[0] : 0.f);
-                    nx = nx < 0 ? nx + ncx : (nx >= ncx ? nx - ncx : nx);
-                    const int cc = (nz * ncy + ny) * ncx + nx;
-                    ecs[hh] = cell_start[cc];
-                    len[hh] = cell_start[cc + 1] - ecs[hh];
-                }
-                inc[hh] = len[hh];
-                for (int off = 1; off < 64; off <<= 1) {
-                    const int v = __shfl_up(inc[hh], off);
-                    if (lane >= off) inc[hh] += v;
-                }
-            }
-            const int lower = __builtin_amdgcn_readlane(inc[0], 63);
-            total = lower + __builtin_amdgcn_readlane(inc[1], 63);
+        for (int hh = 0; hh < 2; ++hh)
 #pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                s_rstart[w][lane + 64 * hh] = ecs[hh];
-                s_rpref[w][lane + 64 * hh] = (hh ? lower : 0) + inc[hh] - len[hh];       // exclusive prefix; beyond the stencil: `total`
-                s_rshift[w][0][lane + 64 * hh] = esx[hh];
-                s_rshift[w][1][lane + 64 * hh] = esy[hh];
-                s_rshift[w][2][lane + 64 * hh] = esz[hh];
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-        // coarse table: the piece of every (1 << cshift)-th stream position (the last piece that starts at or before it)
-        int cshift = 3;
-        while (((total + 127) >> cshift) > CB_COARSE) ++cshift;
-#pragma unroll
-        for (int q = 0; q < CB_COARSE / 64; ++q) {
-            const int idx = (lane + 64 * q) << cshift;
-            int r = 0;
-#pragma unroll
-            for (int step = 64; step > 0; step >>= 1)
-                if (s_rpref[w][r + step] <= idx) r += step;
-            s_coarse[w][lane + 64 * q] = (unsigned char)r;
-        }
+            for (int k = 0; k < 3; ++k) s_rshift[w][k][lane + 64 * hh] = cshift_of((tab_code >> (8 * hh + 2 * k)) & 3, box.L[k]);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -418,33 +466,43 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLICE 
             // the batch's atoms: lane 3 t + a holds atom a of row molecule t; the loops over t below are REAL loops (t is a scalar
             // register): coordinates come by v_readlane, the per-row counters live in lane t of three registers -- one copy of the
             // test and of the drain code whatever the batch size
-            float4 my = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (lane < 3 * nt) my = pos4f[3 * tb + lane];
+            if (tb > a_begin) {
+                my = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (lane < 3 * nt) my = pos4f[3 * tb + lane];
+            }
             int row_cnt = 0;          // lane t: entries of row t so far (front | back << 16)
             int q_head = 0, q_cnt = 0;    // lane t: ring of row t (head index, entries waiting)
             auto rl = [&](float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); };
             // ---- pass 2: 128 queued survivors of row t (n of them valid), two per lane (lane, lane + 64) so that the arithmetic runs
             // on packed fp32: nine distances each, the smallest decides; the two halves are filed one after the other (ring order) ----
-            auto drain = [&](int t, int n) {
+            // NU = 1: the row's leftover at the end of the stream when it fits one half (n <= 64) -- one survivor per lane, the same fp32
+            // operations on it unpacked, the same filing: no second half of gathers and arithmetic on lanes that hold nothing
+            auto drain = [&](int t, int n, auto nu_) {
+                constexpr int NU = decltype(nu_)::value;
+                using V = typename std::conditional<NU == 2, v2f, float>::type;
+                auto pk = [](const float (&x)[NU]) -> V { if constexpr (NU == 2) return v2f{x[0], x[1]}; else return x[0]; };
+                auto half = [](V x, int u) -> float { if constexpr (NU == 2) return u ? x.y : x.x; else return x; };
 #ifdef AMM_CBS_TIMING
                 const unsigned long long t_d0 = wall_clock64();
                 n_drain++;
 #endif
                 const int head = __builtin_amdgcn_readlane(q_head, t);
-                int slot[2];
-                bool v[2];
-                float4 A[2][3];
+                int slot[NU];
+                bool v[NU];
+                float4 A[NU][3];
 #pragma unroll
-                for (int u = 0; u < 2; ++u) {
+                for (int u = 0; u < NU; ++u) {
                     const bool v0 = lane + 64 * u < n;
                     slot[u] = v0 ? s_q[w][t][cq_wrap(head + lane + 64 * u)] : tb + t;
                     v[u] = v0 && slot[u] != tb + t;          // (a molecule is not its own partner)
                 }
 #pragma unroll
-                for (int u = 0; u < 2; ++u)
+                for (int u = 0; u < NU; ++u)
 #pragma unroll
                     for (int b = 0; b < 3; ++b) A[u][b] = pos4f[3 * slot[u] + b];
-                const int sites[2] = {__float_as_int(A[0][1].w), __float_as_int(A[1][1].w)};
+                int sites[NU];
+#pragma unroll
+                for (int u = 0; u < NU; ++u) sites[u] = __float_as_int(A[u][1].w);
                 float px[3], py[3], pz[3];
 #pragma unroll
                 for (int a = 0; a < 3; ++a) {
@@ -452,17 +510,24 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLICE 
                     py[a] = rl(my.y, 3 * t + a);
                     pz[a] = rl(my.z, 3 * t + a);
                 }
-                v2f ax[3], ay[3], az[3];
+                V ax[3], ay[3], az[3];
 #pragma unroll
                 for (int b = 0; b < 3; ++b) {
-                    ax[b] = v2f{A[0][b].x, A[1][b].x};
-                    ay[b] = v2f{A[0][b].y, A[1][b].y};
-                    az[b] = v2f{A[0][b].z, A[1][b].z};
+                    float hx[NU], hy[NU], hz[NU];
+#pragma unroll
+                    for (int u = 0; u < NU; ++u) {
+                        hx[u] = A[u][b].x;
+                        hy[u] = A[u][b].y;
+                        hz[u] = A[u][b].z;
+                    }
+                    ax[b] = pk(hx);
+                    ay[b] = pk(hy);
+                    az[b] = pk(hz);
                 }
                 if (!RINT) {          // one periodic image per molecule pair, from the first atoms
-                    const v2f sx = box.L[0] * __builtin_elementwise_rint((ax[0] - px[0]) * box.invL[0]);
-                    const v2f sy = box.L[1] * __builtin_elementwise_rint((ay[0] - py[0]) * box.invL[1]);
-                    const v2f sz = box.L[2] * __builtin_elementwise_rint((az[0] - pz[0]) * box.invL[2]);
+                    const V sx = box.L[0] * __builtin_elementwise_rint((ax[0] - px[0]) * box.invL[0]);
+                    const V sy = box.L[1] * __builtin_elementwise_rint((ay[0] - py[0]) * box.invL[1]);
+                    const V sz = box.L[2] * __builtin_elementwise_rint((az[0] - pz[0]) * box.invL[2]);
 #pragma unroll
                     for (int b = 0; b < 3; ++b) {
                         ax[b] -= sx;
@@ -470,25 +535,27 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLICE 
                         az[b] -= sz;
                     }
                 }
-                v2f m2 = v2f{3.0e38f, 3.0e38f};
+                V m2;
+                if constexpr (NU == 2) m2 = v2f{3.0e38f, 3.0e38f};
+                else m2 = 3.0e38f;
 #pragma unroll
                 for (int a = 0; a < 3; ++a)
 #pragma unroll
                     for (int b = 0; b < 3; ++b) {
-                        v2f dx = px[a] - ax[b], dy = py[a] - ay[b], dz = pz[a] - az[b];
+                        V dx = px[a] - ax[b], dy = py[a] - ay[b], dz = pz[a] - az[b];
                         if (RINT) {
                             dx -= box.L[0] * __builtin_elementwise_rint(dx * box.invL[0]);
                             dy -= box.L[1] * __builtin_elementwise_rint(dy * box.invL[1]);
                             dz -= box.L[2] * __builtin_elementwise_rint(dz * box.invL[2]);
                         }
-                        v2f r2 = dx * dx;
+                        V r2 = dx * dx;
                         r2 = __builtin_elementwise_fma(dy, dy, r2);
                         r2 = __builtin_elementwise_fma(dz, dz, r2);
                         m2 = __builtin_elementwise_min(m2, r2);
                     }
 #pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const float m2u = u ? m2.y : m2.x;
+                for (int u = 0; u < NU; ++u) {
+                    const float m2u = half(m2, u);
                     const bool pass = v[u] && m2u < rlist2;
                     const unsigned long long m_pass = __builtin_amdgcn_ballot_w64(pass);
                     if (m_pass != 0ull) {
@@ -579,7 +646,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLICE 
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                         __builtin_amdgcn_wave_barrier();
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                        drain(t, 128);
+                        drain(t, 128, std::integral_constant<int, 2>());
                     }
                 }
 #pragma unroll
@@ -593,7 +660,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLICE 
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             for (int t = 0; t < nt; ++t) {
                 const int n = __builtin_amdgcn_readlane(q_cnt, t);
-                if (n > 0) drain(t, n);
+#if CB_HALF_DRAIN
+                if (n > 64) drain(t, n, std::integral_constant<int, 2>());
+                else if (n > 0) drain(t, n, std::integral_constant<int, 1>());
+#else
+                if (n > 0) drain(t, n, std::integral_constant<int, 2>());
+#endif
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // the ring reads are done before the next batch refills them
             __builtin_amdgcn_wave_barrier();
@@ -2211,7 +2283,7 @@ static int cluster_chain(amm_ctx *ctx, PairForce *L, ClusterList *cl, const doub
                        cl->d_cell_members, cl->capc, cl->d_cperm, cl->d_aperm, d_pos, ctx->box, cl->d_pos4f, cl->d_flags, cl->d_flags, force,
                        gf ? gf->d_q : nullptr, gf ? gf->d_hsig : nullptr, gf ? gf->d_seps2 : nullptr, gf ? gf->d_posq_s : (double4 *)nullptr,
                        gf ? gf->d_lj_s : (double2 *)nullptr, (float)cl->rext, L->d_seps2, cl->d_first, Z, copies_current,
-                       count_only ? (double *)nullptr : cl->d_xref, cl->c_begin, cl->c_end, cl->d_slice_cells);
+                       count_only ? (double *)nullptr : cl->d_xref, cl->c_begin, cl->c_end, cl->d_slice_cells, cl->grid, cl->d_build_tabs);
     // A rank's slice (rows c_begin .. c_end of the sorted order): blocks for the cells of the slice only (a quarter more than its
     // share of the cells + 4; the kernels stride over the units should the slice span more), and -- k_cbuild_split -- a block per
     // (cell, part) with both passes shared out over its wavefronts
@@ -2233,11 +2305,13 @@ static int cluster_chain(amm_ctx *ctx, PairForce *L, ClusterList *cl, const doub
         if (slice)                                                                                                                  \
             hipLaunchKernelGGL((k_cbuild<CO, RI, true>), grid, dim3(256), 0, st, cl->c_begin, cl->c_end, cl->parts, cl->d_cell_start,    \
                                cl->d_pos4f, bf, cl->grid, rl, rn2, cl->cap, cl->d_nl, cl->d_nnb, cl->d_nnb_near, cl->d_flags,            \
-                               cl->d_blockstats, cl->d_counters, cl->d_ticket + AMM_TICKET_INTS, force, cl->d_slice_cells);              \
+                               cl->d_blockstats, cl->d_counters, cl->d_ticket + AMM_TICKET_INTS, force, cl->d_slice_cells,              \
+                               cl->d_build_tabs);                                                                                        \
         else                                                                                                                        \
             hipLaunchKernelGGL((k_cbuild<CO, RI, false>), grid, dim3(256), 0, st, cl->c_begin, cl->c_end, cl->parts, cl->d_cell_start,   \
                                cl->d_pos4f, bf, cl->grid, rl, rn2, cl->cap, cl->d_nl, cl->d_nnb, cl->d_nnb_near, cl->d_flags,            \
-                               cl->d_blockstats, cl->d_counters, cl->d_ticket + AMM_TICKET_INTS, force, cl->d_slice_cells);              \
+                               cl->d_blockstats, cl->d_counters, cl->d_ticket + AMM_TICKET_INTS, force, cl->d_slice_cells,              \
+                               cl->d_build_tabs);                                                                                        \
     } while (0)
 #define AMM_LAUNCH_CBUILD_SPLIT(RI)                                                                                                  \
     hipLaunchKernelGGL((k_cbuild_split<RI>), grid, dim3(256), 0, st, cl->c_begin, cl->c_end, cl->split_parts, cl->d_cell_start,     \
@@ -2340,6 +2414,7 @@ static int cluster_first_build(amm_ctx *ctx, PairForce *L, const double *d_pos) 
     AMM_HIP(hipStreamSynchronize(ctx->stream));
     cl->capc = 2 * flags[6] + 16;
     AMM_HIP(hipMalloc(&cl->d_cell_members, sizeof(int) * (size_t)ncell * cl->capc));
+    AMM_HIP(hipMalloc(&cl->d_build_tabs, sizeof(CBuildTab) * (size_t)ncell));
     // wavefronts per cell: a wave walks the cell's whole candidate stream once per batch of CB_BATCH row molecules, so batches
     // should be full -- but the build is a chain of dependent reads (piece search, gather, ring, gather) that only more
     // wavefronts hide: 1.5 x the parts that would just fill the batches at the MEAN occupancy measured fastest
@@ -2463,7 +2538,7 @@ int amm_cluster_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, doub
     if (!gathered && !copies_current)
         hipLaunchKernelGGL(k_csort_gather, dim3((std::max(cl->nc, Z.n) + 255) / 256), dim3(256), 0, st, cl->grid.ncell, cl->nc, cl->d_cell_start,
                            cl->d_cell_members, cl->capc, cl->d_cperm, cl->d_aperm, d_pos, ctx->box, cl->d_pos4f, cl->d_flags + 8, cl->d_flags, 0,
-                           pf->d_q, pf->d_hsig, pf->d_seps2, pf->d_posq_s, pf->d_lj_s, (float)cl->rext, L->d_seps2, cl->d_first, Z, 0, (double *)nullptr, 0, 0, (int *)nullptr);     // flags[8] stays 0: copies only
+                           pf->d_q, pf->d_hsig, pf->d_seps2, pf->d_posq_s, pf->d_lj_s, (float)cl->rext, L->d_seps2, cl->d_first, Z, 0, (double *)nullptr, 0, 0, (int *)nullptr, cl->grid, (CBuildTab *)nullptr);     // flags[8] stays 0: copies only
     // (the copies in place are this force's at these positions from here on, whoever wrote them)
     cl->sorted_for = pf;
     cl->sorted_epoch = ctx->pos_epoch;
@@ -2816,7 +2891,7 @@ int amm_cluster_count_within_impl(amm_ctx *ctx, PairForce *pf, const double *d_p
     hipStream_t st = ctx->stream;
     hipLaunchKernelGGL(k_csort_gather, dim3((cl->nc + 255) / 256), dim3(256), 0, st, cl->grid.ncell, cl->nc, cl->d_cell_start, cl->d_cell_members,
                        cl->capc, cl->d_cperm, cl->d_aperm, d_pos, ctx->box, cl->d_pos4f, cl->d_flags + 8, cl->d_flags, 0, pf->d_q, pf->d_hsig,
-                       pf->d_seps2, pf->d_posq_s, pf->d_lj_s, (float)cl->rext, L->d_seps2, cl->d_first, CZeroRows{0, nullptr, nullptr, nullptr}, 0, (double *)nullptr, 0, 0, (int *)nullptr);
+                       pf->d_seps2, pf->d_posq_s, pf->d_lj_s, (float)cl->rext, L->d_seps2, cl->d_first, CZeroRows{0, nullptr, nullptr, nullptr}, 0, (double *)nullptr, 0, 0, (int *)nullptr, cl->grid, (CBuildTab *)nullptr);
     if (cl->sorted_for == pf) {        // (this force's copies in place are those of d_pos now)
         cl->sorted_epoch = ctx->pos_epoch;
         cl->sorted_pos = d_pos;
@@ -2908,6 +2983,7 @@ int amm_cluster_free(ClusterList *cl) {
     for (void *q : {(void *)cl->d_spec_count[0], (void *)cl->d_spec_count[1], (void *)cl->d_spec_ticket})
         if (q) (void)hipFree(q);
     if (cl->d_slice_cells) (void)hipFree(cl->d_slice_cells);
+    if (cl->d_build_tabs) (void)hipFree(cl->d_build_tabs);
     void *ptrs[] = {cl->d_cell_count, cl->d_cell_start, cl->d_cell_members, cl->d_cperm, cl->d_aperm, cl->d_pos4f, cl->d_xref, cl->d_nl,
                     cl->d_nnb, cl->d_nnb_near, cl->d_flags, cl->d_counters, cl->d_blockstats, cl->d_ticket};
     for (void *p : ptrs)

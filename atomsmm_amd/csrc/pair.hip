@@ -2228,9 +2228,9 @@ int amm_pair_count_within_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos,
 extern "C" __attribute__((weak)) const char *amm_variant_tag(void);
 const char *amm_kernel_revision_impl() {
 #ifdef AMM_CLUSTER_TUNE
-    return "r07-triploop-tune";
+    return "r08-buildtabs-tune";
 #else
-    return amm_variant_tag ? "r07-triploop-tune" : "r07-triploop";
+    return amm_variant_tag ? "r08-buildtabs-tune" : "r08-buildtabs";
 #endif
 }
 
