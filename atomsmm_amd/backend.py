@@ -34,6 +34,9 @@ ARITY = {BOND_HARMONIC: 2, ANGLE_HARMONIC: 3, BOND_LJC: 2, BOND_NEAR: 2, TORSION
 NPAR = {BOND_HARMONIC: 2, ANGLE_HARMONIC: 2, BOND_LJC: 3, BOND_NEAR: 3, TORSION_PERIODIC: 3, BOND_EWALD_EXCL: 1,
         BOND_VIRIAL_HARMONIC: 2, BOND_VIRIAL_LJ: 3}
 
+RULE_NAMES = ('plain', 'defer_trailing_kicks', 'inner_components', 'fused_inner', 'dual_eval', 'terms_kicks', 'kicks_move',
+              'plan_offers')      # amm_run_rule_stats: out[0..7]
+
 EXPORTS = [
     'amm_abi_version', 'amm_last_error', 'amm_create', 'amm_destroy', 'amm_set_stream', 'amm_set_slice',
     'amm_synchronize', 'amm_check', 'amm_pair_create', 'amm_pair_set_params', 'amm_pair_share_list', 'amm_bonded_create',
@@ -50,6 +53,7 @@ EXPORTS = [
     'amm_set_box', 'amm_box_stats', 'amm_mol_define', 'amm_mol_scale',
     'amm_pair_expr_create', 'amm_pair_expr_set_globals',
     'amm_term_expr_create', 'amm_term_expr_set_globals', 'amm_term_expr_set_params', 'amm_term_expr_release',
+    'amm_run_rule_stats',
 ]
 
 
@@ -152,6 +156,7 @@ def lib():
         L.amm_comm_destroy.argtypes = [vp]
         L.amm_comm_stats.argtypes = [vp, C.POINTER(C.c_int64)]
         L.amm_run_stats.argtypes = [vp, C.POINTER(C.c_int64)]
+        L.amm_run_rule_stats.argtypes = [vp, C.POINTER(C.c_int64)]
         L.amm_group_set_exchange.argtypes = [vp, C.c_int32, C.c_int32]
         L.amm_bind_exchange.argtypes = [vp, vp, C.c_int64]
         L.amm_exchange_finish.argtypes = [vp]
@@ -506,6 +511,13 @@ class HipContext:
         out = (C.c_int64 * 4)()
         _chk(lib().amm_run_stats(self.h, out))
         return dict(epilogues=out[0], copies_current=out[1], state_exchanges=out[2], scheduled=out[3])
+
+    def run_rule_stats(self):
+        """Who made the scheduling decisions of run_stats()['scheduled']: the plain path and the six fusion rules of csrc/run_ops.hip
+        (their sum is 'scheduled'), and how many evaluations were offered an epilogue plan (carried ones: run_stats()['epilogues'])."""
+        out = (C.c_int64 * 8)()
+        _chk(lib().amm_run_rule_stats(self.h, out))
+        return dict(zip(RULE_NAMES, out))
 
     def bath_define(self, z, kT):
         bid = C.c_int32(-1)

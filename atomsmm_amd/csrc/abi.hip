@@ -1823,6 +1823,13 @@ int amm_run_stats(amm_ctx *ctx, int64_t out[4]) {
     return 0;
 }
 
+int amm_run_rule_stats(amm_ctx *ctx, int64_t out[8]) {
+    if (!ctx || !out) return 1;
+    for (int i = 0; i < 7; ++i) out[i] = ctx->n_rule[i];
+    out[7] = ctx->n_plan_offers;
+    return 0;
+}
+
 int amm_exchange_per(amm_ctx *ctx, int32_t *per) {
     if (!ctx || !per) return 1;
     *per = amm_slice_per(ctx->n, ctx->world);

@@ -377,6 +377,8 @@ struct amm_ctx {
     std::vector<const double *> own_only;
     long long n_sched = 0;             // scheduling decisions of amm_run_ops so far: launches of the step program, an evaluation counted as one
     long long n_copies_current = 0;    // evaluations that found their sorted copies in place (no gather launch)
+    long long n_rule[7] = {0};         // ... per taker: [0] the plain path, [1..6] the fusion rules in run_ops.hip's numbering (their sum is n_sched)
+    long long n_plan_offers = 0;       // evaluations that amm_run_ops offered an epilogue plan (carried or not: n_epilogues counts the carried)
     // tuning / test options (amm_set_option): never read from the environment, so that a stray variable cannot change the
     // order of summation of a production run
     int opt_cluster = 1;           // molecule rows for qualifying forces (0: per-atom rows everywhere)

@@ -428,6 +428,7 @@ struct OpRun {
                              g2->forces.size() == 1 && plan_epilogue(k + 2, plan, q_resume, wraps);
         ctx->epi_request = planned ? &plan : nullptr;
         ctx->epi_done = false;
+        if (planned) ctx->n_plan_offers++;
         const int rc_dual = amm_pair_eval_impl(ctx, guest->host, ctx->d_x, fh, 0, nullptr, guest, fg, 0, g1->exchange);
         ctx->epi_request = nullptr;
         if (rc_dual) return FAILED;
@@ -522,6 +523,7 @@ struct OpRun {
                      (pf->all_q_zero && !pf->cluster_ok && plan_atoms(k + 1, plan, q_resume, wraps)))) return NOT_MINE;
         ctx->epi_request = &plan;
         ctx->epi_done = false;
+        ctx->n_plan_offers++;
         const int rc_one = amm_pair_eval_impl(ctx, pf, ctx->d_x, buf, 0, nullptr, nullptr, nullptr, 0, g.exchange);
         ctx->epi_request = nullptr;
         if (rc_one) return FAILED;
@@ -715,13 +717,18 @@ struct OpRun {
     int step(int &k) {
         if (ndef && !(k == 0 && ops[k].op == AMM_OP_KICK) && flush_deferred()) return FAILED;
         int r;
-        if ((r = rule_defer_trailing_kicks(k)) != NOT_MINE) return r;
-        if ((r = rule_inner_components(k)) != NOT_MINE) return r;
-        if ((r = rule_fused_inner(k)) != NOT_MINE) return r;
-        if ((r = rule_dual_eval(k)) != NOT_MINE) return r;
-        if ((r = rule_terms_kicks(k)) != NOT_MINE) return r;
-        if ((r = rule_kicks_move(k)) != NOT_MINE) return r;
-        return run_plain(k);
+        if ((r = rule_defer_trailing_kicks(k)) != NOT_MINE) return taken(1, r);
+        if ((r = rule_inner_components(k)) != NOT_MINE) return taken(2, r);
+        if ((r = rule_fused_inner(k)) != NOT_MINE) return taken(3, r);
+        if ((r = rule_dual_eval(k)) != NOT_MINE) return taken(4, r);
+        if ((r = rule_terms_kicks(k)) != NOT_MINE) return taken(5, r);
+        if ((r = rule_kicks_move(k)) != NOT_MINE) return taken(6, r);
+        return taken(0, run_plain(k));
+    }
+    // statistics (amm_run_rule_stats): who made the decision that run() counts in n_sched
+    int taken(int rule, int r) {
+        if (r != FAILED) ctx->n_rule[rule]++;
+        return r;
     }
     int run() {
         k_start = cursor ? (int)(*cursor % n_ops) : 0;

@@ -404,6 +404,11 @@ int amm_set_option(amm_ctx *ctx, const char *name, double value);
  * launches on a rank's slice that were followed by an exchange of positions and velocities instead of forces, out[3] = scheduling
  * decisions made so far: one per op or fused run of ops (an evaluation counts as one whatever it launches) -- not kernel launches. */
 int amm_run_stats(amm_ctx *ctx, int64_t out[4]);
+/* Who made those scheduling decisions (tests): out[0] = ops run on their own (the plain path), out[1..6] = decisions of the fusion rules
+ * in the numbering of csrc/run_ops.hip -- 1 trailing kicks deferred, 2 component-parallel inner loop, 3 fused inner iteration, 4 one pass
+ * for two evaluations, 5 term-parallel evaluation + kicks, 6 kicks + move; their sum is out[3] of amm_run_stats.  out[7] = evaluations
+ * that were offered an epilogue plan; those whose launch carried it are out[0] of amm_run_stats. */
+int amm_run_rule_stats(amm_ctx *ctx, int64_t out[8]);
 /* amm_run_ops, resumable (several ranks whose collectives the HOST makes -- torch.distributed over gloo, or RCCL outside the library):
  * starts at op *cursor of the unrolled program (repetition * n_ops + index; 0 at first) and runs to the end (*cursor = repeat * n_ops)
  * or to the first exchanged evaluation that now waits for its exchange: the caller all-gathers the chunks of the exchange buffer,

@@ -14,6 +14,8 @@ torch = pytest.importorskip('torch')
 
 from oracle import oracle as O  # noqa: E402  (checker only)
 
+import ops_ref  # noqa: E402  (tests/ops_ref.py: the shared RESPA op list and its oracle loop)
+
 
 def _backend():
     from atomsmm_amd import backend as B
@@ -1079,24 +1081,10 @@ def test_respa_ops_vs_oracle_trajectory(spcfw, goldens):
     def f2(p):
         return O.pair_eval(dd, p, c['box'], c['charge'], c['sigma'], c['epsilon'], c['exc_pairs'])[1]
 
-    # --- oracle-driven program (exact op order of SURVEY.md 3.2)
-    xo, vo = x.copy(), v.copy()
+    # --- oracle-driven program (exact op order of SURVEY.md 3.2): written out as loops in tests/ops_ref.py, which tests/test_ops_ref_host.py
+    # also holds its op-list interpreter against
     nsteps = 2
-    for _ in range(nsteps):
-        F2 = f2(xo); F1 = f1(xo)
-        O.kick(vo, F2, m, 0.5 * dt, fsub=F1)
-        for _n1 in range(2):
-            O.kick(vo, F1, m, 0.25 * dt)
-            F0 = f0(xo)
-            for _n0 in range(4):
-                O.kick(vo, F0, m, 0.0625 * dt)
-                O.move(xo, vo, 0.125 * dt)
-                F0 = f0(xo)
-                O.kick(vo, F0, m, 0.0625 * dt)
-            F1 = f1(xo)
-            O.kick(vo, F1, m, 0.25 * dt)
-        F2 = f2(xo)
-        O.kick(vo, F2, m, 0.5 * dt, fsub=F1)
+    xo, vo = ops_ref.respa_421_by_hand(f0, f1, f2, x, v, m, dt, nsteps)
     # --- HIP
     ctx = B.HipContext(n, c['box'])
     bid = ctx.bonded_create()
@@ -1111,15 +1099,7 @@ def test_respa_ops_vs_oracle_trajectory(spcfw, goldens):
     for k, b in enumerate(bufs):
         ctx.bind_buffer(k, b)
     ctx.group_define(0, 0, [bid]); ctx.group_define(1, 1, [nid]); ctx.group_define(2, 2, [did])
-    E, K, M, CP = B.OP_EVAL, B.OP_KICK, B.OP_MOVE, B.OP_COPY
-    ops = [B.Op(E, 2, 0, 0, 0.0), B.Op(E, 1, 0, 0, 0.0), B.Op(CP, 3, 2, 0, 0.0), B.Op(K, 3, 1, 0, 0.5 * dt)]
-    for _n1 in range(2):
-        ops += [B.Op(K, 1, -1, 0, 0.25 * dt), B.Op(E, 0, 0, 0, 0.0)]
-        for _n0 in range(4):
-            ops += [B.Op(K, 0, -1, 0, 0.0625 * dt), B.Op(M, 0, 0, 0, 0.125 * dt), B.Op(E, 0, 0, 0, 0.0),
-                    B.Op(K, 0, -1, 0, 0.0625 * dt)]
-        ops += [B.Op(E, 1, 0, 0, 0.0), B.Op(K, 1, -1, 0, 0.25 * dt)]
-    ops += [B.Op(E, 2, 0, 0, 0.0), B.Op(CP, 3, 2, 0, 0.0), B.Op(K, 3, 1, 0, 0.5 * dt)]
+    ops = [B.Op(*op) for op in ops_ref.respa_421_ops(dt)]
     ctx.run_ops(ops, repeat=nsteps)
     ctx.check()
     assert np.abs(xd.cpu().numpy() - xo).max() < 1e-11
