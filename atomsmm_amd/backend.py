@@ -51,7 +51,7 @@ EXPORTS = [
     'amm_min_create', 'amm_min_release', 'amm_min_begin', 'amm_min_advance', 'amm_min_trial', 'amm_min_scalars', 'amm_min_stats',
     'amm_min_read',
     'amm_set_box', 'amm_box_stats', 'amm_mol_define', 'amm_mol_scale',
-    'amm_pair_expr_create', 'amm_pair_expr_set_globals',
+    'amm_pair_expr_create', 'amm_pair_expr_set_globals', 'amm_pair_expr_set_tables',
     'amm_term_expr_create', 'amm_term_expr_set_globals', 'amm_term_expr_set_params', 'amm_term_expr_release',
     'amm_run_rule_stats',
 ]
@@ -166,6 +166,7 @@ def lib():
         L.amm_pair_set_params.argtypes = [vp, C.c_int32, dp, dp, dp]
         L.amm_pair_expr_create.argtypes = [vp, C.POINTER(PairDesc), ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, dp, dp, dp, ip, C.c_int32, C.c_double, ip]
         L.amm_pair_expr_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
+        L.amm_pair_expr_set_tables.argtypes = [vp, C.c_int32, C.c_int32, ip, ip, dp, ip, dp, C.c_int32]
         L.amm_term_expr_create.argtypes = [vp, C.c_int32, ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip, dp, C.c_int32, C.c_int32, C.c_int32, ip]
         L.amm_term_expr_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
         L.amm_term_expr_set_params.argtypes = [vp, C.c_int32, dp, C.c_int32, C.c_int32]
@@ -355,6 +356,24 @@ class HipContext:
     def pair_expr_set_globals(self, fid, globals_):
         g_, gp = _hd(globals_ if len(globals_) else [0.0])
         _chk(lib().amm_pair_expr_set_globals(self.h, fid, gp, len(globals_)))
+
+    def pair_expr_set_tables(self, fid, tables):
+        """The tabulated functions of a generic pair force, in the force's function order: one (kind, nx, ny, lo, hi, doubles) each
+        (atomsmm_amd/tables.py: device_table).  Again with new values of the same sizes: updateParametersInContext."""
+        kinds = np.array([t[0] for t in tables], dtype=np.int32)
+        dims = np.array([[t[1], t[2]] for t in tables], dtype=np.int32).reshape(-1)
+        ranges = np.array([[t[3], t[4]] for t in tables], dtype=np.float64).reshape(-1)
+        blocks = [np.ascontiguousarray(t[5], dtype=np.float64).reshape(-1) for t in tables]
+        offsets = np.zeros(len(tables), dtype=np.int32)
+        if tables:
+            offsets[1:] = np.cumsum([len(b) for b in blocks])[:-1]
+        data = np.concatenate(blocks) if blocks else np.zeros(0)
+        k_, kp = _hi(kinds if len(tables) else [0])
+        d_, dmp = _hi(dims if len(tables) else [0])
+        r_, rp = _hd(ranges if len(tables) else [0.0])
+        o_, op = _hi(offsets if len(tables) else [0])
+        v_, vp = _hd(data if len(data) else [0.0])
+        _chk(lib().amm_pair_expr_set_tables(self.h, fid, len(tables), kp, dmp, rp, op, vp, len(data)))
 
     def pair_share_list(self, fid, host_fid):
         _chk(lib().amm_pair_share_list(self.h, fid, host_fid))

@@ -487,6 +487,7 @@ int amm_pair_expr_create(amm_ctx *ctx, const amm_pair_desc *desc, const int32_t 
     std::copy(code, code + ncode, px->h.code);
     std::copy(consts, consts + nconst, px->h.consts);
     std::copy(globals, globals + nglobal, px->h.globals);
+    amm_pair_expr_scan_tables(px);
     if (amm_pair_expr_upload(ctx, px, false)) {
         amm_pair_expr_free(px);
         return 1;
@@ -512,6 +513,17 @@ int amm_pair_expr_set_globals(amm_ctx *ctx, int32_t force_id, const double *glob
     }
     std::copy(globals, globals + nglobal, pf->expr->h.globals);
     return amm_pair_expr_upload(ctx, pf->expr, true);
+}
+
+int amm_pair_expr_set_tables(amm_ctx *ctx, int32_t force_id, int32_t n_tables, const int32_t *kinds, const int32_t *dims, const double *ranges,
+                             const int32_t *offsets, const double *data, int32_t n_data) {
+    PairForce *pf = get_pair(ctx, force_id);
+    if (!pf) return 1;
+    if (!pf->expr) {
+        amm_set_error("amm_pair_expr_set_tables: not a pair-expression force (AMM_PAIR_EXPR)");
+        return 1;
+    }
+    return amm_pair_expr_tables(ctx, pf->expr, n_tables, kinds, dims, ranges, offsets, data, n_data);
 }
 
 int amm_pair_set_lambda(amm_ctx *ctx, int32_t force_id, double value) {

@@ -514,6 +514,11 @@ int amm_free_lanes_per_row(int n);
 int amm_pair_expr_launch(amm_ctx *ctx, PairForce *pf, const PairArgs &A, dim3 grid, bool en);
 int amm_pair_expr_upload(amm_ctx *ctx, PairExpr *px, bool globals_only);
 void amm_pair_expr_free(PairExpr *px);
+// tabulated functions of such a force: does the program read any (sets PairExpr::uses_tables); check them against the program's
+// table words and copy them to the force's device allocation (amm_pair_expr_set_tables)
+void amm_pair_expr_scan_tables(PairExpr *px);
+int amm_pair_expr_tables(amm_ctx *ctx, PairExpr *px, int n_tables, const int32_t *kinds, const int32_t *dims, const double *ranges,
+                         const int32_t *offsets, const double *data, int n_data);
 // term_expr.hip: a force of type AMM_FORCE_TERM_EXPR
 int amm_term_expr_build(amm_ctx *ctx, TermExprForce *tf, const int32_t *h_idx, const double *h_params);   // device arrays + CSR of a new force
 int amm_term_expr_upload(amm_ctx *ctx, TermExprForce *tf, bool globals_only);

@@ -22,9 +22,11 @@
 #include "pair_expr_vm.h"
 #include "term_expr_vm.h"
 
-template <bool EN>
-__global__ void __launch_bounds__(256) k_pair_expr(PairArgs A, const PairExprProg *__restrict__ prog, double rc2, double rswitch,
-                                                   double inv_sw_dr, int use_switch, double sign) {
+// EN: with the energy.  TAB: the program has tabulated-function words (a kernel of its own, so that a program without them runs the
+// code it ran before there were any).
+template <bool EN, bool TAB>
+__global__ void __launch_bounds__(256) k_pair_expr(PairArgs A, const PairExprProg *__restrict__ prog, const PairTableDesc *__restrict__ tabs,
+                                                   double rc2, double rswitch, double inv_sw_dr, int use_switch, double sign) {
 #pragma clang fp contract(off)
     __shared__ int s_code[AMM_PEXPR_MAXCODE];
     __shared__ double s_consts[AMM_PEXPR_MAXCONST];
@@ -62,7 +64,7 @@ __global__ void __launch_bounds__(256) k_pair_expr(PairArgs A, const PairExprPro
                 const double r = sqrt(r2);
                 const double pb[AMM_PEXPR_PARAMS] = {pj.w, lj.x, lj.y};
                 double e, de;
-                pair_expr_run(s_code, ncode, s_consts, s_globals, r, pa, pb, s_stack + threadIdx.x, e, de);
+                pair_expr_run<TAB>(s_code, ncode, s_consts, s_globals, r, pa, pb, tabs, s_stack + threadIdx.x, e, de);
                 if (use_switch && r > rswitch) {
                     // OpenMM's built-in switch, S = 1 - 10 t^3 + 15 t^4 - 6 t^5, applied after the program
                     const double t = (r - rswitch) * inv_sw_dr;
@@ -117,11 +119,24 @@ int amm_pair_expr_launch(amm_ctx *ctx, PairForce *pf, const PairArgs &A, dim3 gr
         amm_set_error("pair-expression force (AMM_PAIR_EXPR): filtered rows and dual evaluation are not for this family");
         return 1;
     }
+    if (pf->expr->uses_tables && !pf->expr->d_tabs) {
+        amm_set_error("pair-expression force (AMM_PAIR_EXPR): the program reads tabulated functions and none are set: amm_pair_expr_set_tables");
+        return 1;
+    }
     const PairConsts &c = pf->pc;
+    const PairTableDesc *tabs = pf->expr->uses_tables ? pf->expr->d_tabs : nullptr;
     const int use_switch = (c.flags & AMM_SWITCH) ? 1 : 0;
     const double inv_sw_dr = use_switch ? 1.0 / (c.rc - c.rswitch) : 0.0;
-    if (en) hipLaunchKernelGGL(k_pair_expr<true>, grid, dim3(256), 0, ctx->stream, A, pf->expr->d, c.rc2, c.rswitch, inv_sw_dr, use_switch, c.sign);
-    else hipLaunchKernelGGL(k_pair_expr<false>, grid, dim3(256), 0, ctx->stream, A, pf->expr->d, c.rc2, c.rswitch, inv_sw_dr, use_switch, c.sign);
+#define AMM_PEXPR_LAUNCH(EN, TAB) \
+    hipLaunchKernelGGL((k_pair_expr<EN, TAB>), grid, dim3(256), 0, ctx->stream, A, pf->expr->d, tabs, c.rc2, c.rswitch, inv_sw_dr, use_switch, c.sign)
+    if (tabs) {
+        if (en) AMM_PEXPR_LAUNCH(true, true);
+        else AMM_PEXPR_LAUNCH(false, true);
+    } else {
+        if (en) AMM_PEXPR_LAUNCH(true, false);
+        else AMM_PEXPR_LAUNCH(false, false);
+    }
+#undef AMM_PEXPR_LAUNCH
     return 0;
 }
 
@@ -150,6 +165,7 @@ int amm_expr_program_validate(const char *who, const int32_t *code, int ncode, i
         case X_TERM_VAR: pops = 0; if (pair) return fail("opcode " + std::to_string(op) + " is not a pair-expression op"); if (arg < 0 || arg >= term_vars) return fail("variable index out of range (the kind has " + std::to_string(term_vars) + ")"); break;
         case X_TERM_P: pops = 0; if (pair) return fail("opcode " + std::to_string(op) + " is not a pair-expression op"); if (arg < 0 || arg >= term_params) return fail("per-term parameter index out of range (the force has " + std::to_string(term_params) + ")"); break;
         case X_PAIR_P1: case X_PAIR_P2: pops = 0; if (!pair) return fail("opcode " + std::to_string(op) + " is not a term-expression op"); if (arg < 0 || arg >= AMM_PEXPR_PARAMS) return fail("per-particle parameter index out of range (limit " + std::to_string(AMM_PEXPR_PARAMS) + ")"); break;
+        case X_TAB_C1: case X_TAB_D1: case X_TAB_D2: pops = op == X_TAB_D2 ? 2 : 1; if (!pair) return fail("opcode " + std::to_string(op) + " is not a term-expression op"); if (arg < 0 || arg >= AMM_PEXPR_MAXTABLES) return fail("tabulated-function index out of range (limit " + std::to_string(AMM_PEXPR_MAXTABLES) + ")"); break;
         case X_LOAD: pops = 0; if (arg < 0 || arg >= AMM_PEXPR_LOCALS) return fail("local index out of range (limit " + std::to_string(AMM_PEXPR_LOCALS) + ")"); break;
         case X_STORE: pushes = 0; if (arg < 0 || arg >= AMM_PEXPR_LOCALS) return fail("local index out of range (limit " + std::to_string(AMM_PEXPR_LOCALS) + ")"); break;
         case X_ADD: case X_SUB: case X_MUL: case X_DIV: case X_POW: case X_MIN: case X_MAX: case X_ATAN2: pops = 2; break;
@@ -175,8 +191,92 @@ int amm_pair_expr_upload(amm_ctx *ctx, PairExpr *px, bool globals_only) {
     return 0;
 }
 
+// ---- host: tabulated functions ----
+static const char *table_word_name(int op) { return op == X_TAB_C1 ? "TAB_C1 (55)" : (op == X_TAB_D1 ? "TAB_D1 (56)" : "TAB_D2 (57)"); }
+static const char *table_kind_name(int kind) {
+    return kind == AMM_TABLE_CONTINUOUS1D ? "Continuous1DFunction" : (kind == AMM_TABLE_DISCRETE1D ? "Discrete1DFunction" : "Discrete2DFunction");
+}
+// doubles of a table of this kind and size
+static size_t table_doubles(int kind, int nx, int ny) {
+    return kind == AMM_TABLE_CONTINUOUS1D ? 4 * (size_t)(nx - 1) : (size_t)nx * (size_t)(kind == AMM_TABLE_DISCRETE2D ? ny : 1);
+}
+
+void amm_pair_expr_scan_tables(PairExpr *px) {
+    px->uses_tables = false;
+    for (int pc = 0; pc < px->h.ncode; ++pc) {
+        const int op = px->h.code[pc] & 0xff;
+        if (op == X_TAB_C1 || op == X_TAB_D1 || op == X_TAB_D2) px->uses_tables = true;
+    }
+}
+
+int amm_pair_expr_tables(amm_ctx *ctx, PairExpr *px, int n_tables, const int32_t *kinds, const int32_t *dims, const double *ranges,
+                         const int32_t *offsets, const double *data, int n_data) {
+    auto fail = [](const std::string &what) {
+        amm_set_error("amm_pair_expr_set_tables: " + what);
+        return 1;
+    };
+    if (n_tables < 0 || n_tables > AMM_PEXPR_MAXTABLES) return fail(std::to_string(n_tables) + " tabulated functions (limit " + std::to_string(AMM_PEXPR_MAXTABLES) + ")");
+    if (n_data < 0 || (n_tables > 0 && (!kinds || !dims || !ranges || !offsets || !data))) return fail("null argument");
+    // the tables as the device will hold them: every table's doubles start at a multiple of 4
+    PairTableDesc tabs[AMM_PEXPR_MAXTABLES];
+    std::memset(tabs, 0, sizeof(tabs));
+    size_t total = 0;
+    for (int k = 0; k < n_tables; ++k) {
+        PairTableDesc &T = tabs[k];
+        const std::string which = "table " + std::to_string(k);
+        T.kind = kinds[k];
+        if (T.kind != AMM_TABLE_CONTINUOUS1D && T.kind != AMM_TABLE_DISCRETE1D && T.kind != AMM_TABLE_DISCRETE2D) return fail(which + ": unknown kind " + std::to_string(T.kind));
+        T.nx = dims[2 * k];
+        T.ny = T.kind == AMM_TABLE_DISCRETE2D ? dims[2 * k + 1] : 1;
+        if (T.nx < (T.kind == AMM_TABLE_CONTINUOUS1D ? 2 : 1) || T.ny < 1 || T.nx > (1 << 24) || T.ny > (1 << 24) || (size_t)T.nx * (size_t)T.ny > ((size_t)1 << 26))
+            return fail(which + " (" + table_kind_name(T.kind) + "): size " + std::to_string(T.nx) + " x " + std::to_string(T.ny) + " (a continuous function needs 2 knots, any table at most 2^26 values)");
+        if (T.kind == AMM_TABLE_CONTINUOUS1D) {
+            T.lo = ranges[2 * k];
+            T.hi = ranges[2 * k + 1];
+            if (!(T.lo < T.hi) || !std::isfinite(T.lo) || !std::isfinite(T.hi)) return fail(which + " (Continuous1DFunction): needs finite min < max");
+            T.h = (T.hi - T.lo) / (double)(T.nx - 1);
+            T.inv_h = (double)(T.nx - 1) / (T.hi - T.lo);
+        }
+        const size_t need = table_doubles(T.kind, T.nx, T.ny);
+        if (offsets[k] < 0 || (size_t)offsets[k] + need > (size_t)n_data)
+            return fail(which + " (" + table_kind_name(T.kind) + "): " + std::to_string(need) + " doubles at offset " + std::to_string(offsets[k]) + " do not lie in the " + std::to_string(n_data) + " given");
+        T.off = (int)total;
+        total += (need + 3) & ~(size_t)3;
+    }
+    // every table word of the program finds a table of its kind (the kind says how many arguments the word takes)
+    for (int pc = 0; pc < px->h.ncode; ++pc) {
+        const int op = px->h.code[pc] & 0xff, arg = px->h.code[pc] >> 8;
+        if (op != X_TAB_C1 && op != X_TAB_D1 && op != X_TAB_D2) continue;
+        if (arg < 0 || arg >= n_tables) return fail(std::string("word ") + table_word_name(op) + " reads table " + std::to_string(arg) + ": " + std::to_string(n_tables) + " given");
+        const int want = op == X_TAB_C1 ? AMM_TABLE_CONTINUOUS1D : (op == X_TAB_D1 ? AMM_TABLE_DISCRETE1D : AMM_TABLE_DISCRETE2D);
+        if (tabs[arg].kind != want)
+            return fail(std::string("word ") + table_word_name(op) + " takes a " + table_kind_name(want) + " (" + (op == X_TAB_D2 ? "2 arguments" : "1 argument") + "), table " + std::to_string(arg) + " is a " + table_kind_name(tabs[arg].kind));
+    }
+    if (px->d_tabs) {
+        // a re-upload (updateParametersInContext): new values in tables of the same kinds and sizes
+        if (n_tables != px->n_tables) return fail("the force has " + std::to_string(px->n_tables) + " tabulated functions, " + std::to_string(n_tables) + " given: their number cannot change");
+        for (int k = 0; k < n_tables; ++k)
+            if (tabs[k].kind != px->tabs[k].kind || tabs[k].nx != px->tabs[k].nx || tabs[k].ny != px->tabs[k].ny)
+                return fail("table " + std::to_string(k) + " changed its kind or size (" + std::to_string(px->tabs[k].nx) + " x " + std::to_string(px->tabs[k].ny) + " -> " + std::to_string(tabs[k].nx) + " x " + std::to_string(tabs[k].ny) + "): a re-upload carries new values only");
+    }
+    const size_t bytes = sizeof(tabs) + total * sizeof(double);
+    std::vector<char> host(bytes, 0);
+    std::memcpy(host.data(), tabs, sizeof(tabs));
+    double *out = reinterpret_cast<double *>(host.data() + sizeof(tabs));
+    for (int k = 0; k < n_tables; ++k) std::copy(data + offsets[k], data + offsets[k] + table_doubles(tabs[k].kind, tabs[k].nx, tabs[k].ny), out + tabs[k].off);
+    // ordered after any kernel already queued on the stream that reads the old tables
+    AMM_HIP(hipStreamSynchronize(ctx->stream));
+    if (!px->d_tabs) AMM_HIP(hipMalloc(&px->d_tabs, bytes));
+    AMM_HIP(hipMemcpy(px->d_tabs, host.data(), bytes, hipMemcpyHostToDevice));
+    px->n_tables = n_tables;
+    px->n_data = total;
+    std::memcpy(px->tabs, tabs, sizeof(tabs));
+    return 0;
+}
+
 void amm_pair_expr_free(PairExpr *px) {
     if (!px) return;
     if (px->d) (void)hipFree(px->d);
+    if (px->d_tabs) (void)hipFree(px->d_tabs);
     delete px;
 }

@@ -8,6 +8,11 @@
 // zero whatever f'(x) is (sqrt(eps1*eps2) at eps = 0 has f' = inf; the pair's energy does not depend on r through it).
 // Discontinuous ops follow Lepton: step, delta, floor, ceil have derivative 0, abs takes the sign of its operand, min / max / select
 // carry the derivative of the operand they return.
+//
+// Tabulated functions (addTabulatedFunction): X_TAB_C1 / X_TAB_D1 / X_TAB_D2 replace their arguments with the value of
+// table `arg` of the force (pexpr_table).  A Continuous1DFunction carries its spline's derivative through pexpr_chain; the discrete
+// ones have derivative 0.  The tables live in ONE device allocation -- AMM_PEXPR_MAXTABLES descriptors, then the doubles -- read from
+// global memory (every lane reads the same few lines: L2), so the LDS of a block is what it was without them.
 #pragma once
 #include "expr_vm.h"
 
@@ -17,11 +22,14 @@
 #define AMM_PEXPR_STACK 16
 #define AMM_PEXPR_LOCALS 16
 #define AMM_PEXPR_PARAMS 3          // per-particle doubles a neighbour row carries per atom (charge slot, two Lennard-Jones slots)
+#define AMM_PEXPR_MAXTABLES 8       // tabulated functions of one force
 
 // opcodes beside those of expr_vm.h (X_BUF, X_MASS, X_GAUSS, X_UNIFORM, X_DEVG, X_OUT and X_HORNER are not pair ops)
 enum { X_PAIR_R = 50, X_PAIR_P1 = 51, X_PAIR_P2 = 52 };
 // ... and the leaves of a term expression (term_expr_vm.h): the term's geometric variable k, its parameter k
 enum { X_TERM_VAR = 53, X_TERM_P = 54 };
+// ... and the tabulated functions of a pair expression: table `arg` at the top of the stack (X_TAB_D2: at the two topmost, x below y)
+enum { X_TAB_C1 = 55, X_TAB_D1 = 56, X_TAB_D2 = 57 };
 
 // the compiled text as the device holds it: staged into LDS once per block
 struct PairExprProg {
@@ -31,10 +39,23 @@ struct PairExprProg {
     double globals[AMM_PEXPR_MAXGLOBAL];
 };
 
+// One tabulated function as the device reads it.  kind: AMM_TABLE_* (atomsmm_hip.h).  Continuous: nx knots lo .. hi at spacing h, data =
+// nx - 1 records (a, b, c, d) of the interval's cubic a + u (b + u (c + u d)), u = t - knot; discrete: data = nx (* ny) values,
+// values[i + nx * j].  off: where the table's doubles begin behind the descriptors (a multiple of 4: records are 32-byte aligned).
+struct PairTableDesc {
+    int kind, nx, ny, off;
+    double lo, hi, h, inv_h;
+};
+
 // host side of a generic pair force (PairForce::expr)
 struct PairExpr {
     PairExprProg h;
     PairExprProg *d = nullptr;
+    bool uses_tables = false;                   // the program has X_TAB_* words: no launch before amm_pair_expr_set_tables
+    int n_tables = 0;
+    PairTableDesc tabs[AMM_PEXPR_MAXTABLES];    // as uploaded (a re-upload keeps kinds and sizes)
+    size_t n_data = 0;                          // doubles behind the descriptors
+    PairTableDesc *d_tabs = nullptr;            // descriptors [AMM_PEXPR_MAXTABLES], then the doubles: one allocation, freed with the force
 };
 
 // non-zero + message naming the limit that a program exceeds, or a word that is no pair op / leaves the stack or the locals
@@ -86,11 +107,46 @@ static __device__ __noinline__ double3 pexpr_pow(double a, double b, bool with_l
 }
 static __device__ __noinline__ double pexpr_atan2(double y, double x) { return atan2(y, x); }
 
+// (f, f') of tabulated function `idx` at x (X_TAB_D2: at (x, y)).  CALLED, as the transcendental ops are: the descriptor, the address
+// arithmetic and the NaN constant live in here, not across the dispatch loop.  Every index is clamped into its table BEFORE the load,
+// whatever the argument is (NaN, inf, beyond int): no input reads outside the allocation.
+//   continuous: 0 outside [lo, hi] (value and derivative); inside, the cubic of interval k = min(floor((x - lo) / h), nx - 2), so that
+//               x == hi is the end of the last interval; a NaN argument gives NaN through u.
+//   discrete:   values[rint(x)] (values[rint(x) + nx * rint(y)]); an index outside the table, or NaN, gives NaN.  Derivative 0.
+static __device__ __noinline__ double2 pexpr_table(const PairTableDesc *tabs, int op, int idx, double x, double y) {
+#pragma clang fp contract(off)
+    const PairTableDesc *T = tabs + idx;
+    const double *data = reinterpret_cast<const double *>(tabs + AMM_PEXPR_MAXTABLES) + T->off;
+    const int nx = T->nx;
+    if (op == X_TAB_C1) {
+        const double lo = T->lo;
+        if (x < lo || x > T->hi) return make_double2(0.0, 0.0);
+        const double s = (x - lo) * T->inv_h;
+        int k = (s >= 0.0 && s < (double)nx) ? (int)s : 0;         // (NaN: 0)
+        k = min(max(k, 0), nx - 2);
+        const double u = (x - lo) - (double)k * T->h;
+        const double2 ab = *reinterpret_cast<const double2 *>(data + 4 * (size_t)k);
+        const double2 cd = *reinterpret_cast<const double2 *>(data + 4 * (size_t)k + 2);
+        return make_double2(ab.x + u * (ab.y + u * (cd.x + u * cd.y)), ab.y + u * (2.0 * cd.x + u * (3.0 * cd.y)));
+    }
+    const double rx = rint(x), ry = op == X_TAB_D2 ? rint(y) : 0.0;
+    const int ny = op == X_TAB_D2 ? T->ny : 1;
+    const bool inside = rx >= 0.0 && rx < (double)nx && ry >= 0.0 && ry < (double)ny;          // (false for NaN)
+    const int i = min(max(inside ? (int)rx : 0, 0), nx - 1), j = min(max(inside ? (int)ry : 0, 0), ny - 1);
+    const double v = data[(size_t)i + (size_t)nx * j];
+    return make_double2(inside ? v : __builtin_nan(""), 0.0);
+}
+
 // The leaves of a pair expression: r with derivative 1, pa / pb the parameters of the row atom (<name>1) and of the neighbour (<name>2).
+// TAB: the program has X_TAB_* words, and `tabs` the force's tables; without them the words compile to nothing and the interpreter is
+// the one it was before there were any.
+template <bool TAB>
 struct PairLeaves {
     static constexpr bool kPair = true;
+    static constexpr bool kTables = TAB;
     double r;
     const double *pa, *pb;
+    const PairTableDesc *tabs;
 };
 
 // E and its derivative along the leaves' seed.  code / consts / globals: the block's LDS copies.  The program is the same for every
@@ -133,6 +189,28 @@ __device__ __forceinline__ void pexpr_run(const int *code, int ncode, const doub
         case X_PAIR_P2: if constexpr (Leaves::kPair) PEXPR_PUSH(arg == 0 ? leaves.pb[0] : (arg == 1 ? leaves.pb[1] : leaves.pb[2]), 0.0); break;
         case X_TERM_VAR: if constexpr (!Leaves::kPair) PEXPR_PUSH(leaves.var(arg), leaves.seed(arg)); break;
         case X_TERM_P: if constexpr (!Leaves::kPair) PEXPR_PUSH(leaves.param(arg), 0.0); break;
+        // The table words are cases of the instantiation for programs that HAVE them only (PairLeaves<true>): the compiler lowers this
+        // switch to a tree of scalar compares and lays the cases out as it sees fit, and three more cases cost every other word of a
+        // program without tables 1.6 % (as cases) to 8 % (behind a range test in the default) on the MI355X -- DESIGN.md 3.PT.
+        case X_TAB_C1: case X_TAB_D1:
+            if constexpr (Leaves::kPair) {
+                if constexpr (Leaves::kTables) {
+                    const double2 f = pexpr_table(leaves.tabs, op, arg, tv, 0.0);
+                    tv = f.x;
+                    td = op == X_TAB_C1 ? pexpr_chain(f.y, td) : 0.0;
+                }
+            }
+            break;
+        case X_TAB_D2:
+            if constexpr (Leaves::kPair) {
+                if constexpr (Leaves::kTables) {
+                    const double2 lhs = st[(sp - 2) * AMM_PEXPR_STRIDE];
+                    --sp;
+                    tv = pexpr_table(leaves.tabs, op, arg, lhs.x, tv).x;
+                    td = 0.0;
+                }
+            }
+            break;
         case X_LOAD: PEXPR_PUSH(lv[arg], ld[arg]); break;
         case X_STORE: {
             lv[arg] = tv;
@@ -214,8 +292,10 @@ __device__ __forceinline__ void pexpr_run(const int *code, int ncode, const doub
 }
 
 // E(r) and dE/dr of one pair
+template <bool TAB>
 __device__ __forceinline__ void pair_expr_run(const int *code, int ncode, const double *consts, const double *globals, double r,
-                                              const double *pa, const double *pb, double2 *st, double &E, double &dE) {
-    pexpr_run(code, ncode, consts, globals, PairLeaves{r, pa, pb}, st, E, dE);
+                                              const double *pa, const double *pb, const PairTableDesc *tabs, double2 *st, double &E,
+                                              double &dE) {
+    pexpr_run(code, ncode, consts, globals, PairLeaves<TAB>{r, pa, pb, tabs}, st, E, dE);
 }
 #endif

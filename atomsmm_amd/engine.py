@@ -27,6 +27,7 @@ import numpy as np
 from . import backend as B
 from . import expr as X
 from . import openmm as mm
+from . import tables as T
 from . import unit
 from .forces import describe_energy
 from .utils import InputError
@@ -845,20 +846,42 @@ class Engine:
         return B.pair_desc(_FAMILY[family], rc, rc0=rc0, rs0=rs0, flags=flags, sign=d.get('sign', 1.0), Kc=d.get('Kc', B.KC))
 
     @staticmethod
-    def check_pair_symmetry(text, per_particle_names, global_values, samples=6, seed=20240607):
+    def check_pair_symmetry(text, per_particle_names, global_values, samples=6, seed=20240607, tabulated=None):
         """A pair is evaluated from both atoms' rows and counted once (csrc/pair_expr.hip), so the text must not change when the
         particles swap: evaluate it on the host at a handful of seeded random (r, parameters of 1, parameters of 2) and at the
-        swapped parameters.  OpenMM leaves an asymmetric text undefined (which atom is 1 depends on its neighbour list)."""
+        swapped parameters.  OpenMM leaves an asymmetric text undefined (which atom is 1 depends on its neighbour list).
+        tabulated: (name -> callable, the force's particle rows [n][parameters]) of a force with tabulated functions -- the sample
+        parameters are then rows the force HAS (a uniform draw is no type index): every pair of distinct rows when they are few
+        (an asymmetric A(type1, type2) shows at the one pair of types it concerns), seeded draws of pairs otherwise."""
         rng = np.random.default_rng(seed)
-        for _ in range(samples):
+        if tabulated is None:
+            functions, draws = None, [None] * samples
+        else:
+            functions, rows = tabulated
+            if not per_particle_names:
+                return                 # (nothing to swap)
+            rows = np.unique(np.asarray(rows, dtype=np.float64).reshape(-1, len(per_particle_names)), axis=0)
+            if len(rows) <= 24:
+                draws = [(rows[i], rows[j]) for i in range(len(rows)) for j in range(i + 1, len(rows))]
+            else:
+                draws = [(rows[i], rows[j]) for i, j in rng.integers(0, len(rows), size=(16 * samples, 2)) if i != j]
+        for draw in draws:
             r = float(rng.uniform(0.3, 1.2))
-            one = {nm: float(rng.uniform(0.2, 1.5)) for nm in per_particle_names}
-            two = {nm: float(rng.uniform(0.2, 1.5)) for nm in per_particle_names}
+            if draw is None:
+                one = {nm: float(rng.uniform(0.2, 1.5)) for nm in per_particle_names}
+                two = {nm: float(rng.uniform(0.2, 1.5)) for nm in per_particle_names}
+            else:
+                one, two = (dict(zip(per_particle_names, map(float, row))) for row in draw)
             env = dict(global_values, r=r)
             fwd = dict(env, **{nm + '1': one[nm] for nm in per_particle_names}, **{nm + '2': two[nm] for nm in per_particle_names})
             swp = dict(env, **{nm + '1': two[nm] for nm in per_particle_names}, **{nm + '2': one[nm] for nm in per_particle_names})
             try:
-                a, b = X.eval_global(text, fwd), X.eval_global(text, swp)
+                if functions is None:
+                    a, b = X.eval_global(text, fwd), X.eval_global(text, swp)
+                else:
+                    a, b = X.eval_global(text, fwd, functions=functions), X.eval_global(text, swp, functions=functions)
+                    if a != a and b != b:
+                        continue       # (an index outside its table both ways: NaN on the device too, nothing about symmetry)
             except (ArithmeticError, ValueError) as exc:
                 if isinstance(exc, X.ExpressionError):
                     raise
@@ -887,22 +910,45 @@ class Engine:
             raise InputError(generic + 'takes at most %d per-particle parameters (%d given): a neighbour row carries three doubles '
                              'per atom' % (X.PAIR_MAX_PARAMS, len(names)))
         gnames = [force.getGlobalParameterName(k) for k in range(force.getNumGlobalParameters())]
+        # addTabulatedFunction: (name, function) in the force's order -- the order of the table indices in the program
+        functions = list(getattr(force, '_functions', []))
         try:
-            prog = X.compile_pair(text, names, gnames)
+            prog = X.compile_pair(text, names, gnames, T.declared(functions)) if functions else X.compile_pair(text, names, gnames)
         except X.ExpressionError as exc:
             raise InputError('energy expression not recognised by the HIP path as one of the AtomsMM families, and not a pair '
                              'expression the generic kernel can run: %s' % exc)
-        self.check_pair_symmetry(text, names, {g: self.parameters[g] for g in prog.globals_})
+        uses_tables = bool(X.table_words(prog.code))
+        if not uses_tables:
+            self.check_pair_symmetry(text, names, {g: self.parameters[g] for g in prog.globals_})
         n = self.n
         if force.getNumParticles() != n:
             raise mm.OpenMMException('CustomNonbondedForce must have exactly as many particles as the System')
+        direct = T.direct_index_uses(text, functions) if uses_tables else []
 
         def slots():
             allp = np.array(force._particles, dtype=np.float64).reshape(n, -1)
             if allp.shape[1] != len(names):
                 raise mm.OpenMMException('CustomNonbondedForce: every particle needs %d parameters' % len(names))
+            # a per-particle value passed straight into a discrete function is an index: a whole number inside the table
+            for symbol, fname, size in direct:
+                if symbol[:-1] in names and symbol[-1] in '12':
+                    column = allp[:, names.index(symbol[:-1])]
+                    bad = np.nonzero(~((column == np.rint(column)) & (column >= 0) & (column < size)))[0]
+                    if len(bad):
+                        raise mm.OpenMMException('CustomNonbondedForce: particle %d has %s = %r, passed to the tabulated function %s as an '
+                                                 'index: it must be a whole number in 0 .. %d' %
+                                                 (bad[0], symbol[:-1], float(column[bad[0]]), fname, size - 1))
             return [np.ascontiguousarray(allp[:, k]) if k < len(names) else np.zeros(n) for k in range(3)]
 
+        def tables_checked():
+            """What amm_pair_expr_set_tables takes, after the checks the host can make: the particles' indices lie in their tables,
+            and the text is symmetric over the rows the force has."""
+            rows = np.stack(slots()[:len(names)], axis=1) if names else np.zeros((n, 0))
+            self.check_pair_symmetry(text, names, {g: self.parameters[g] for g in prog.globals_},
+                                     tabulated=({name: T.host_callable(fn) for name, fn in functions}, rows))
+            return [T.device_table(fn) for _, fn in functions]
+
+        tables = tables_checked() if uses_tables else None
         rc = force._cutoff
         use_switch = force.getUseSwitchingFunction()
         if use_switch and not (0.0 <= force._switch < rc):
@@ -915,9 +961,14 @@ class Engine:
         entry.pair_ids.append(pid)
         entry.pair_expr = True
         entry.program = prog
+        if uses_tables:
+            self.ctx.pair_expr_set_tables(pid, tables)
 
-        def reload():          # updateParametersInContext: the per-particle parameters are read again
-            self.ctx.pair_set_params(pid, *slots())
+        def reload():          # updateParametersInContext: the per-particle parameters (and the tabulated functions) are read again
+            fresh = slots()
+            if uses_tables:
+                self.ctx.pair_expr_set_tables(pid, tables_checked())
+            self.ctx.pair_set_params(pid, *fresh)
             return 'values'
         entry.reload = reload
         if prog.globals_:

@@ -24,13 +24,18 @@ OPCODES = dict(
 PAIR_OPCODES = dict(PAIR_R=50, PAIR_P1=51, PAIR_P2=52)
 # the words only a term expression has (compile_term; csrc/term_expr_vm.h): the term's geometric variable k and its parameter k
 TERM_OPCODES = dict(TERM_VAR=53, TERM_P=54)
-ALL_OPCODES = dict(OPCODES, **PAIR_OPCODES, **TERM_OPCODES)
+# the tabulated functions of a pair expression (compile_pair with `functions`; csrc/pair_expr_vm.h): a word's arg is the index of its
+# table -- Continuous1DFunction, Discrete1DFunction, Discrete2DFunction
+TABLE_OPCODES = dict(TAB_C1=55, TAB_D1=56, TAB_D2=57)
+TABLE_KINDS = dict(Continuous1D=('TAB_C1', 1), Discrete1D=('TAB_D1', 1), Discrete2D=('TAB_D2', 2))        # kind -> (word, arguments)
+ALL_OPCODES = dict(OPCODES, **PAIR_OPCODES, **TERM_OPCODES, **TABLE_OPCODES)
 _ARITY = {'min': 2, 'max': 2, 'select': 3, 'atan2': 2}
 MAX_LOCALS = 16
 # limits of a pair-expression program (csrc/pair_expr_vm.h)
 PAIR_MAX_CODE, PAIR_MAX_CONSTS, PAIR_MAX_GLOBALS, PAIR_MAX_STACK, PAIR_MAX_LOCALS, PAIR_MAX_PARAMS = 256, 48, 48, 16, 16, 3
 # a term expression shares them, but for its parameters: one row of doubles per term, not a neighbour row's three (csrc/term_expr_vm.h)
 TERM_MAX_PARAMS = 8
+PAIR_MAX_TABLES = 8         # tabulated functions of one force (AMM_PEXPR_MAXTABLES)
 
 
 class ExpressionError(ValueError):
@@ -226,10 +231,11 @@ def _folded_trees(main, defs):
     return fold(_parse(main)), definition
 
 
-def compile_per_dof(text, resolve, what='per-DOF', random_ok=True, fold=False):
+def compile_per_dof(text, resolve, what='per-DOF', random_ok=True, fold=False, functions=None):
     """Compile a per-DOF (or sum) expression.  `resolve(name)` returns ('buf', slot), ('mass',), ('global',), ('op', opcode name, arg)
     or None.  `what` names the kind of expression in error messages; random_ok=False: `gaussian` / `uniform` are errors; fold=True:
-    subexpressions of literals are evaluated here (_folded_trees)."""
+    subexpressions of literals are evaluated here (_folded_trees); functions: name -> (word, arguments, index) of the tabulated
+    functions a call may name (compile_pair only)."""
     main, defs = split_definitions(text)
     prog = Program()
     local_of, in_progress = {}, set()
@@ -290,6 +296,14 @@ def compile_per_dof(text, resolve, what='per-DOF', random_ok=True, fold=False):
             prog.emit({ast.Add: 'ADD', ast.Sub: 'SUB', ast.Mult: 'MUL', ast.Div: 'DIV', ast.Pow: 'POW'}[type(node.op)])
         elif isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and not node.keywords:
             fn = node.func.id
+            if functions and fn in functions:
+                word, arity, index = functions[fn]
+                if len(node.args) != arity:
+                    raise ExpressionError('tabulated function %s takes %d argument%s (%d given)' % (fn, arity, '' if arity == 1 else 's', len(node.args)))
+                for a in node.args:
+                    gen(a)
+                prog.emit(word, index)
+                return
             if fn not in OPCODES or fn.isupper() or len(node.args) != _ARITY.get(fn, 1):
                 raise ExpressionError('unsupported function call: %s/%d' % (fn, len(node.args)))
             for a in node.args:
@@ -303,14 +317,16 @@ def compile_per_dof(text, resolve, what='per-DOF', random_ok=True, fold=False):
 
 
 _STACK_EFFECT = {'CONST': 1, 'GLOBAL': 1, 'PAIR_R': 1, 'PAIR_P1': 1, 'PAIR_P2': 1, 'TERM_VAR': 1, 'TERM_P': 1, 'LOAD': 1, 'STORE': -1, 'ADD': -1, 'SUB': -1, 'MUL': -1,
-                 'DIV': -1, 'POW': -1, 'min': -1, 'max': -1, 'atan2': -1, 'select': -2}
+                 'DIV': -1, 'POW': -1, 'min': -1, 'max': -1, 'atan2': -1, 'select': -2, 'TAB_C1': 0, 'TAB_D1': 0, 'TAB_D2': -1}
 
 
-def compile_pair(text, per_particle_names, global_names):
+def compile_pair(text, per_particle_names, global_names, functions=None):
     """Compile the energy text of a CustomNonbondedForce for the pair-expression kernel (csrc/pair_expr.hip): `r` is PAIR_R, the row
     atom's parameter `<name>1` is PAIR_P1 k and the neighbour's `<name>2` PAIR_P2 k (k: position in per_particle_names), a global
-    parameter GLOBAL k (k: position in the program's globals_); auxiliary definitions, in any order, become locals.  The limits of
-    csrc/pair_expr_vm.h are enforced here, each with an ExpressionError that names it."""
+    parameter GLOBAL k (k: position in the program's globals_); auxiliary definitions, in any order, become locals.  functions: the
+    force's tabulated functions, name -> (kind of TABLE_KINDS, arguments) in the force's order -- a call of one compiles its arguments,
+    then the kind's word TAB_* with the function's index.  The limits of csrc/pair_expr_vm.h are enforced here, each with an
+    ExpressionError that names it."""
     per_particle_names, global_names = list(per_particle_names), set(global_names)
     if len(per_particle_names) > PAIR_MAX_PARAMS:
         raise ExpressionError('a pair expression takes at most %d per-particle parameters (%d given)' % (PAIR_MAX_PARAMS, len(per_particle_names)))
@@ -326,13 +342,35 @@ def compile_pair(text, per_particle_names, global_names):
             return slots[name]
         return ('global',) if name in global_names else None
 
-    return _checked_program(text, resolve, 'pair')
+    words = None
+    if functions:
+        if len(functions) > PAIR_MAX_TABLES:
+            raise ExpressionError('a pair expression takes at most %d tabulated functions (%d given)' % (PAIR_MAX_TABLES, len(functions)))
+        words = {}
+        for index, (name, (kind, arity)) in enumerate(functions.items()):
+            if kind not in TABLE_KINDS:
+                raise ExpressionError('tabulated function %s: kind %s is not one a pair expression evaluates' % (name, kind))
+            if arity != TABLE_KINDS[kind][1]:
+                raise ExpressionError('tabulated function %s: a %sFunction takes %d argument%s (%d declared)' %
+                                      (name, kind, TABLE_KINDS[kind][1], '' if TABLE_KINDS[kind][1] == 1 else 's', arity))
+            if name in _HOST_FUNCS:
+                raise ExpressionError('tabulated function %s shadows the built-in function of that name' % name)
+            if name == 'r' or name in slots or name in per_particle_names or name in global_names:
+                raise ExpressionError('tabulated function %s shadows %s' % (name, 'the distance r' if name == 'r' else 'the parameter of that name'))
+            words[name] = (TABLE_KINDS[kind][0], arity, index)
+    return _checked_program(text, resolve, 'pair', words)
 
 
-def _checked_program(text, resolve, what):
+def table_words(code):
+    """The (word name, table index) of every tabulated-function word of a program's code, in order."""
+    names = {v: k for k, v in TABLE_OPCODES.items()}
+    return [(names[w & 0xff], w >> 8) for w in code if (w & 0xff) in names]
+
+
+def _checked_program(text, resolve, what, functions=None):
     """The folded program of a pair or term energy text, held against the limits of csrc/pair_expr_vm.h."""
     try:
-        prog = compile_per_dof(text, resolve, what=what, random_ok=False, fold=True)
+        prog = compile_per_dof(text, resolve, what=what, random_ok=False, fold=True, functions=functions)
     except ExpressionError as exc:
         if 'too many auxiliary definitions' in str(exc):
             raise ExpressionError('%s expression: more than %d auxiliary definitions (locals)' % (what, PAIR_MAX_LOCALS))
@@ -497,9 +535,10 @@ _HOST_FUNCS = dict(sqrt=math.sqrt, exp=math.exp, log=math.log, sin=math.sin, cos
                    select=lambda c, a, b: a if c != 0 else b)
 
 
-def eval_global(text, env, rng=None):
+def eval_global(text, env, rng=None, functions=None):
     """Value of a global expression (addComputeGlobal) for the variable values in `env`; `rng` (numpy Generator)
-    supplies `gaussian` / `uniform` (one draw of each per evaluation)."""
+    supplies `gaussian` / `uniform` (one draw of each per evaluation); functions: name -> callable of further functions the text may
+    call (the tabulated functions of a pair text, for the symmetry check)."""
     main, defs = split_definitions(text)
     cache, draws, in_progress = {}, {}, set()
 
@@ -550,6 +589,8 @@ def eval_global(text, env, rng=None):
                 raise ExpressionError('deriv() is not available in this context')
             value = env['__deriv__'](node.args[0].id, node.args[1].id)
             return value if isinstance(value, Deferred) else float(value)
+        if functions and isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id in functions and not node.keywords:
+            return float(functions[node.func.id](*[ev(a) for a in node.args]))
         if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id in _HOST_FUNCS and not node.keywords:
             if len(node.args) != _ARITY.get(node.func.id, 1):
                 raise ExpressionError('unsupported function call: %s/%d' % (node.func.id, len(node.args)))

@@ -271,6 +271,86 @@ class NonbondedForce(Force, _GlobalParams):
         return list(self._exception_offsets[index])
 
 
+class TabulatedFunction:
+    """A function given by numbers, for CustomNonbondedForce.addTabulatedFunction.  Evaluated on the GPU by the pair-expression
+    kernel (atomsmm_amd/tables.py): Continuous1DFunction, Discrete1DFunction and Discrete2DFunction."""
+    _amm_table_kind = None
+
+
+def _table_values(values):
+    return [float(md_value(v)) for v in values]
+
+
+class Continuous1DFunction(TabulatedFunction):
+    """The natural cubic spline through `values` at equally spaced knots min .. max; 0 outside [min, max]."""
+    _amm_table_kind = 0
+
+    def __init__(self, values, min, max, periodic=False):
+        if periodic:
+            raise NotImplementedError('Continuous1DFunction(periodic=True): periodic splines are not evaluated by the HIP path')
+        self.setFunctionParameters(values, min, max)
+
+    def getFunctionParameters(self):
+        return list(self._values), self._min, self._max
+
+    def setFunctionParameters(self, values, min, max):
+        values, lo, hi = _table_values(values), float(md_value(min)), float(md_value(max))
+        if len(values) < 2:
+            raise OpenMMException('Continuous1DFunction: must have at least two points')
+        if not lo < hi:
+            raise OpenMMException('Continuous1DFunction: max <= min for a tabulated function.')
+        self._values, self._min, self._max = values, lo, hi
+
+    def getPeriodic(self):
+        return False
+
+
+class Discrete1DFunction(TabulatedFunction):
+    """values[i], i the argument rounded to the nearest integer."""
+    _amm_table_kind = 1
+
+    def __init__(self, values):
+        self.setFunctionParameters(values)
+
+    def getFunctionParameters(self):
+        return list(self._values)
+
+    def setFunctionParameters(self, values):
+        values = _table_values(values)
+        if not values:
+            raise OpenMMException('Discrete1DFunction: must have at least one value')
+        self._values = values
+
+
+class Discrete2DFunction(TabulatedFunction):
+    """values[i + xsize*j], i and j the arguments rounded to the nearest integers."""
+    _amm_table_kind = 2
+
+    def __init__(self, xsize, ysize, values):
+        self.setFunctionParameters(xsize, ysize, values)
+
+    def getFunctionParameters(self):
+        return self._xsize, self._ysize, list(self._values)
+
+    def setFunctionParameters(self, xsize, ysize, values):
+        xsize, ysize, values = int(xsize), int(ysize), _table_values(values)
+        if xsize < 1 or ysize < 1 or xsize * ysize != len(values):
+            raise OpenMMException('Discrete2DFunction: incorrect number of values (xsize*ysize = %d, %d given)' % (xsize * ysize, len(values)))
+        self._xsize, self._ysize, self._values = xsize, ysize, values
+
+
+def _refused_table(name, what):
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError('%s: %s are not evaluated by the HIP path (Continuous1DFunction, Discrete1DFunction and '
+                                  'Discrete2DFunction are)' % (name, what))
+    return type(name, (TabulatedFunction,), dict(__init__=__init__, __doc__='Not supported: the constructor says so.'))
+
+
+Continuous2DFunction = _refused_table('Continuous2DFunction', 'two-dimensional splines')
+Continuous3DFunction = _refused_table('Continuous3DFunction', 'three-dimensional splines')
+Discrete3DFunction = _refused_table('Discrete3DFunction', 'three-dimensional tables')
+
+
 class CustomNonbondedForce(Force, _GlobalParams):
     NoCutoff, CutoffNonPeriodic, CutoffPeriodic = range(3)
 
@@ -288,6 +368,24 @@ class CustomNonbondedForce(Force, _GlobalParams):
         self._lrc = False
         self._groups = []
         self._derivs = []
+        self._functions = []
+
+    def addTabulatedFunction(self, name, function):
+        """The text may call `name(...)`.  The force keeps the object itself, as OpenMM does: setFunctionParameters on it followed by
+        updateParametersInContext reaches the Context."""
+        if not isinstance(function, TabulatedFunction):
+            raise OpenMMException('addTabulatedFunction: not a TabulatedFunction')
+        self._functions.append((str(name), function))
+        return len(self._functions) - 1
+
+    def getNumTabulatedFunctions(self):
+        return len(self._functions)
+
+    def getTabulatedFunction(self, index):
+        return self._functions[index][1]
+
+    def getTabulatedFunctionName(self, index):
+        return self._functions[index][0]
 
     def usesPeriodicBoundaryConditions(self):
         return self._method == self.CutoffPeriodic

@@ -215,6 +215,26 @@ int amm_pair_expr_create(amm_ctx *ctx, const amm_pair_desc *desc, const int32_t 
                          const double *h_p2, const int32_t *h_excl, int32_t n_excl, double skin, int32_t *force_id);
 /* Context.setParameter(name, value) for a global parameter of such a force: all of the program's globals, in its order. */
 int amm_pair_expr_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal);
+/* addTabulatedFunction on such a force: the tables that the words 55 (Continuous1DFunction), 56 (Discrete1DFunction) and 57
+ * (Discrete2DFunction) of its program read -- a word's arg is the index of its table here, the force's function order; compile_pair
+ * emits it behind the word's arguments.  Table k: */
+enum {
+    AMM_TABLE_CONTINUOUS1D = 0, /* dims[2k] = knots (>= 2), equally spaced on ranges[2k] < ranges[2k+1]; its doubles: 4 per interval,
+                                   (a, b, c, d) of a + u (b + u (c + u d)), u = t - the interval's left knot -- the natural cubic
+                                   spline solved by the host (atomsmm_amd/tables.py).  Outside the range: value and derivative 0   */
+    AMM_TABLE_DISCRETE1D = 1,   /* dims[2k] = values; values[rint(t)], derivative 0                                                 */
+    AMM_TABLE_DISCRETE2D = 2    /* dims[2k] x dims[2k+1] values, values[rint(x) + dims[2k] * rint(y)] (OpenMM's layout), derivative 0 */
+};
+/* kinds[n_tables], dims[2 n_tables], ranges[2 n_tables] (read for a continuous table only), offsets[n_tables]: where table k's
+ * doubles begin in data[n_data]; 0 <= n_tables <= 8.  Non-zero with a message naming the word when a table word of the program has
+ * no table (arg >= n_tables) or a table of another kind (and so another number of arguments), when a table does not lie inside
+ * data, a continuous table has fewer than 2 knots or no finite min < max.  The tables are copied to one device allocation that the
+ * force owns.  A discrete index that is NaN or outside its table gives NaN for that pair, and no index of any kind reads outside the
+ * allocation.  Calling it again uploads new VALUES (updateParametersInContext), ordered after every evaluation already queued: the
+ * number of tables, their kinds and their sizes must be those of the first call.  Evaluating a force whose program has table words
+ * before this call returns non-zero and launches nothing; a force whose program has none needs no call. */
+int amm_pair_expr_set_tables(amm_ctx *ctx, int32_t force_id, int32_t n_tables, const int32_t *kinds, const int32_t *dims,
+                             const double *ranges, const int32_t *offsets, const double *data, int32_t n_data);
 /* RESPASystem puts a short-ranged copy (group 1, rcutIn) and the full force (group 2) over the SAME particles and
  * exclusions (systems.py:71-77): let `force_id` traverse the front part of `host_id`'s neighbour rows instead of
  * building its own list.  Call before the first evaluation; exclusions must be identical. */
