@@ -43,7 +43,7 @@ EXPORTS = [
     'amm_bonded_add_terms', 'amm_bonded_finalize', 'amm_bonded_set_sliced', 'amm_bonded_release', 'amm_force_eval', 'amm_kick',
     'amm_move', 'amm_copy', 'amm_mvv', 'amm_bind_state', 'amm_bind_buffer', 'amm_group_define', 'amm_run_ops',
     'amm_set_fuse_inner', 'amm_set_outer_skin',
-    'amm_pair_get_stats', 'amm_profile_enable', 'amm_profile_read', 'amm_pair_count_within', 'amm_pair_row_padding', 'amm_kernel_revision',
+    'amm_pair_get_stats', 'amm_profile_enable', 'amm_profile_read', 'amm_pair_count_within', 'amm_pair_row_padding', 'amm_kernel_revision', 'amm_pair_table_check',
     'amm_pme_create', 'amm_pme_set_charges', 'amm_pme_set_sliced', 'amm_pair_set_lambda', 'amm_pair_set_lambda_dev', 'amm_expr_eval', 'amm_expr_eval_scalar', 'amm_expr_define', 'amm_expr_seed', 'amm_bath_define', 'amm_stock_define', 'amm_bath_define_nhl', 'amm_bath_define_sin', 'amm_iso_define', 'amm_regulated_define', 'amm_bath_define_regulated', 'amm_pair_energy_derivative', 'amm_constraints_create', 'amm_constraints_set_tolerance', 'amm_pair_set_scale',
     'amm_comm_unique_id', 'amm_comm_init', 'amm_comm_destroy', 'amm_comm_allreduce', 'amm_comm_stats', 'amm_group_set_exchange', 'amm_bind_exchange', 'amm_exchange_finish',
     'amm_set_option', 'amm_positions_changed', 'amm_exchange_per', 'amm_run_stats', 'amm_run_ops_from', 'amm_exchange_pending',
@@ -127,6 +127,15 @@ def kernel_revision():
     return lib().amm_kernel_revision().decode()
 
 
+def pair_table_check(desc, site_sigma=0.0, site_eps=0.0, site_q=0.0):
+    """Host-only (no GPU): the radial tables of `desc` (pair_desc) built as amm_pair_create builds them, and the unclamped interval
+    index at the ends and boundaries of the range a counting pair can have.  -> dict(nint, ss_first, points, bad, idx_min, idx_max,
+    n_below_kink, fine); `bad` must be 0."""
+    out = (C.c_int64 * 8)()
+    _chk(lib().amm_pair_table_check(C.byref(desc), float(site_sigma), float(site_eps), float(site_q), out))
+    return dict(zip(('nint', 'ss_first', 'points', 'bad', 'idx_min', 'idx_max', 'n_below_kink', 'fine'), (int(v) for v in out)))
+
+
 def lib():
     """Load libatomsmm_hip.so; raises HipError when it has not been built (no fallback)."""
     global _LIB
@@ -195,6 +204,7 @@ def lib():
         L.amm_pair_row_padding.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
         L.amm_kernel_revision.restype = C.c_char_p
         L.amm_kernel_revision.argtypes = []
+        L.amm_pair_table_check.argtypes = [C.POINTER(PairDesc), C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int64)]
         L.amm_profile_read.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp]
         L.amm_pme_create.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_double, dp, ip]
         L.amm_pme_set_charges.argtypes = [vp, C.c_int32, dp]

@@ -1575,6 +1575,17 @@ int amm_pair_count_within(amm_ctx *ctx, int32_t force_id, const double *d_pos, d
 
 const char *amm_kernel_revision(void) { return amm_kernel_revision_impl(); }
 
+int amm_pair_table_check(const amm_pair_desc *desc, double site_sigma, double site_eps, double site_q, int64_t out[8]) {
+    if (!desc || !out) {
+        amm_set_error("amm_pair_table_check: null argument");
+        return 1;
+    }
+    long long v[8];
+    if (amm_pair_table_check_impl(*desc, site_sigma, site_eps, site_q, v)) return 1;
+    for (int k = 0; k < 8; ++k) out[k] = (int64_t)v[k];
+    return 0;
+}
+
 int amm_set_outer_skin(amm_ctx *ctx, double skin_out) {
     ctx->skin_out = skin_out;
     return 0;

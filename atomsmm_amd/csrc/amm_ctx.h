@@ -539,6 +539,7 @@ int amm_pair_regrid(amm_ctx *ctx, PairForce *pf);
 int amm_pair_build_table(PairForce *pf);
 int amm_pair_count_within_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double r_within, long long *count);
 const char *amm_kernel_revision_impl();
+int amm_pair_table_check_impl(const amm_pair_desc &d, double site_sigma, double site_eps, double site_q, long long out[8]);
 int amm_bonded_eval_impl(amm_ctx *ctx, BondedSet *bs, const double *d_pos, double *d_force, int accumulate,
                          double *d_energy);
 int amm_bonded_finalize_impl(amm_ctx *ctx, BondedSet *bs);

@@ -1128,6 +1128,25 @@ __device__ __forceinline__ T cpair_in_vgpr(T x) {
 constexpr bool cpair_vgpr_room(int fam, int cmode, int gfam, int smask) {
     return AMM_TRIP_VGPR != 0 && !(fam == AMM_DAMPED && cmode == 0) && !(fam == AMM_NONBONDED && cmode == 1 && gfam >= 0 && smask != 1);
 }
+// The zero slot.  A pair that does not count -- beyond the cutoff, a padding lane, below the table -- used to run its look-up like
+// any other and have the product thrown away by a select on the force (two v_cndmask_b32 for the halves of a double).  The kernels
+// with site-site tables keep AMM_CPAIR_ZERO_SLOT bytes of +0.0 behind their tables in LDS instead (written by the block ahead of
+// the staging barrier; the tables and their offsets are what they were): such a pair reads them -- ONE select, on the byte address,
+// ahead of the reads -- and its Horner chain, the product with the charges and the three FMAs into the accumulators add +-0,
+// which leaves an accumulator that started at +0 bit for bit as it was.  The clamp of the interval goes with it: a pair that counts
+// is inside its table (pair_tab.h: amm_tab_fetch_pass).  The kernels with the analytic Lennard-Jones part keep the select: their
+// force over r holds a term that is not from the table.
+#define AMM_CPAIR_ZERO_SLOT AMM_TAB_STRIDE
+// Which instantiations read it: one force -- all with site-site tables; the fused pass -- the water pattern (only the first row atom
+// a site) of the hosts that have registers to spare.  The others sit at 255 / 256 VGPRs with the look-up's conditions live ahead
+// of the reads and took 12 to 32 bytes of scratch more (profiles/zero_slot_isa.txt); they keep the select on the force.
+constexpr bool cpair_zero_slot(int fam, int cmode, int gfam, int smask) {
+#if defined(AMM_EXP_TAB_GLOBAL) || defined(AMM_EXP_NO_ZERO_SLOT)          // measurement builds
+    return false && fam + cmode + gfam + smask != 0;
+#else
+    return smask != 0 && (gfam < 0 || (smask == 1 && !(fam == AMM_DAMPED && cmode == 0) && !(fam == AMM_NONBONDED && cmode == 1)));
+#endif
+}
 // a member of the block as a local object: only the fields the caller goes on to read are loaded
 template <class T>
 __device__ __forceinline__ T cpair_arg_copy(const __attribute__((address_space(4))) T *src) {
@@ -1170,9 +1189,10 @@ template <int FAM, int CMODE, int GFAM, int IMG, int SMASK>
 __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts &c, const PairConsts &g, const char *tabh, const char *tabg,
                                            const double *erfcx, const double4 (&pi)[3], const double2 *li, int i_sites, const int (&so)[3],
                                            const int (&sog)[3], const int *row, int nfront, int nn, int sub, int lpa_s,
-                                           int self, double (&f)[9], double (&fg)[9] CWALK_T_PARAM) {
+                                           int self, int zslot, double (&f)[9], double (&fg)[9] CWALK_T_PARAM) {
     constexpr bool DUAL = GFAM >= 0;
     constexpr bool SS = SMASK != 0;          // SMASK: the row atoms that can be sites (1: only the first -- water; 7: any)
+    constexpr bool ZSLOT = cpair_zero_slot(FAM, CMODE, GFAM, SMASK);          // pairs that do not count read the zero slot, `zslot` bytes behind tabh
     // The trip stride and the base of the sorted copies are read once per trip, by vector instructions: in scalar registers they
     // were the two values the fused pass still read back from parked lanes on every trip.  The pointer travels as an integer and
     // comes back as a pointer to GLOBAL memory, so that the gathers stay global loads (through a generic pointer: flat loads).
@@ -1182,6 +1202,9 @@ __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts 
     const int lpa = cpair_in_vgpr<VRES>(lpa_s);
     const cwalk_gptr posq = (cwalk_gptr)cpair_in_vgpr<VRES>((unsigned long long)A.posq);
     const int back = A.cap - 1 + nfront;
+    // (zero slot: LDS byte addresses of the two Coulomb tables and of the slot -- a choice of the per-lane select: in a VGPR)
+    const unsigned tabh_a = ZSLOT ? amm_lds_addr(tabh) : 0u, tabg_a = (ZSLOT && DUAL) ? amm_lds_addr(tabg) : 0u;
+    const unsigned zaddr = cpair_in_vgpr<VRES && ZSLOT>(tabh_a + (unsigned)zslot);
     // closer pairs are left out of the main path and redone analytically below (never in a liquid)
     const double r2low = DUAL ? fmax(c.tab.r2min, g.tab.r2min) : c.tab.r2min;
     const double r2low_ss = DUAL ? fmax(c.tab.ss_r2min, g.tab.ss_r2min) : c.tab.ss_r2min;
@@ -1225,6 +1248,30 @@ __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts 
             // SS: all ones where the partner atom is a site (bit field extract with sign extension)
             const int mb = SS ? -(int)((bits >> b) & 1u) : 0;
             double dx[3], dy[3], dz[3], r2[3], fr[3], gl[3];
+            // (is any lane low?  One force: 64-bit masks beside the lane conditions -- the ballot of a comparison IS the comparison's
+            // result, and masks are combined and tested on the scalar unit, where the ballot of a combined lane condition is rebuilt
+            // in a VGPR first, two vector instructions.  The fused pass has no scalar registers for the masks: six lane reloads per trip)
+            constexpr bool LOW_MASKS = !DUAL;
+            unsigned long long lowm = 0ull;
+            bool any_low = false;
+            bool lowp[3];
+            unsigned tadr[3];          // (zero slot) the table the host's pair (a, b) reads: LDS address of its interval 0
+            // does the host's pair (a, b) count?  Also files whether it lies below a table (lowp, lowm / any_low: the redo further down)
+            auto host_pass = [&](int a) {
+                const bool low_c = r2[a] < r2low;
+                bool low = low_c;
+                if (LOW_MASKS) lowm |= __builtin_amdgcn_ballot_w64(low_c);
+                // (a site pair below its own table; no branch here: a branch in this loop costs more than it skips -- lane conditions
+                // are combined with & and |, which stay lane masks on the scalar unit: && and || become branches around the second test)
+                if ((SMASK >> a) & 1) {
+                    const bool site_pair = ZSLOT ? tadr[a] != tabh_a : (so[a] & mb) != 0, low_ss = r2[a] < r2low_ss;
+                    low = low | (site_pair & low_ss);
+                    if (LOW_MASKS) lowm |= __builtin_amdgcn_ballot_w64(site_pair) & __builtin_amdgcn_ballot_w64(low_ss);
+                }
+                lowp[a] = low;
+                if (!LOW_MASKS) any_low = any_low | (ok & low);
+                return ok & (r2[a] < c.rc2) & !low;
+            };
             {
                 TabLookup th[3];
 #pragma unroll
@@ -1238,7 +1285,13 @@ __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts 
                         dz[a] = amm_min_image(dz[a], A.box.L[2], A.box.invL[2]);
                     }
                     r2[a] = dx[a] * dx[a] + dy[a] * dy[a] + dz[a] * dz[a];
-                    th[a] = amm_tab_fetch(tabh, c.tab, r2[a], ((SMASK >> a) & 1) ? (unsigned)(so[a] & mb) : 0u);
+                    if (ZSLOT) {
+                        // (site bit of the partner x the row atom's way to its site-site table: one multiply-add)
+                        tadr[a] = ((SMASK >> a) & 1) ? __umul24((bits >> b) & 1u, (unsigned)so[a]) + tabh_a : tabh_a;
+                        th[a] = amm_tab_fetch_pass(tadr[a], c.tab, r2[a], host_pass(a), zaddr);
+                    } else {
+                        th[a] = amm_tab_fetch(tabh, c.tab, r2[a], ((SMASK >> a) & 1) ? (unsigned)(so[a] & mb) : 0u);
+                    }
                     if (DUAL) gl[a] = 0.0;
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -1261,29 +1314,10 @@ __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts 
                         }
                     }
             }
-            // (is any lane low?  One force: 64-bit masks beside the lane conditions -- the ballot of a comparison IS the comparison's
-            // result, and masks are combined and tested on the scalar unit, where the ballot of a combined lane condition is rebuilt
-            // in a VGPR first, two vector instructions.  The fused pass has no scalar registers for the masks: six lane reloads per trip)
-            constexpr bool LOW_MASKS = !DUAL;
-            unsigned long long lowm = 0ull;
-            bool any_low = false;
-            bool lowp[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                const bool low_c = r2[a] < r2low;
-                bool low = low_c;
-                if (LOW_MASKS) lowm |= __builtin_amdgcn_ballot_w64(low_c);
-                // (a site pair below its own table; no branch here: a branch in this loop costs more than it skips -- lane conditions
-                // are combined with & and |, which stay lane masks on the scalar unit: && and || become branches around the second test)
-                if ((SMASK >> a) & 1) {
-                    const bool site_pair = (so[a] & mb) != 0, low_ss = r2[a] < r2low_ss;
-                    low = low | (site_pair & low_ss);
-                    if (LOW_MASKS) lowm |= __builtin_amdgcn_ballot_w64(site_pair) & __builtin_amdgcn_ballot_w64(low_ss);
-                }
-                lowp[a] = low;
-                const bool pass = ok & (r2[a] < c.rc2) & !low;
-                if (!LOW_MASKS) any_low = any_low | (ok & low);
-                const double fh = pass ? fr[a] : 0.0;
+                // (zero slot: a pair that does not count brought +-0 from its look-up)
+                const double fh = ZSLOT ? fr[a] : (host_pass(a) ? fr[a] : 0.0);
                 f[3 * a] += fh * dx[a];
                 f[3 * a + 1] += fh * dy[a];
                 f[3 * a + 2] += fh * dz[a];
@@ -1293,7 +1327,14 @@ __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts 
                 if (any_front) {
                     TabLookup tg[3];
 #pragma unroll
-                    for (int a = 0; a < 3; ++a) tg[a] = amm_tab_fetch(tabg, g.tab, r2[a], ((SMASK >> a) & 1) ? (unsigned)(sog[a] & mb) : 0u);
+                    for (int a = 0; a < 3; ++a) {
+                        if (ZSLOT) {
+                            tg[a] = amm_tab_fetch_pass(((SMASK >> a) & 1) ? __umul24((bits >> b) & 1u, (unsigned)sog[a]) + tabg_a : tabg_a, g.tab, r2[a],
+                                                       front & (r2[a] < g.rc2) & !lowp[a], zaddr);
+                        } else {
+                            tg[a] = amm_tab_fetch(tabg, g.tab, r2[a], ((SMASK >> a) & 1) ? (unsigned)(sog[a] & mb) : 0u);
+                        }
+                    }
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int a = 0; a < 3; ++a) {
@@ -1302,8 +1343,7 @@ __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts 
                         // fg, which starts at +0 and so is never -0, through an FMA: the same bits without the add)
                         double gr = ((pi[a].w * qb) * A.gfac) * amm_tab_horner(tg[a]);
                         if (!SS) gr = amm_sum_unfused(gr, gl[a]);
-                        const bool pass = front & (r2[a] < g.rc2) & !lowp[a];
-                        const double gh = pass ? gr : 0.0;
+                        const double gh = ZSLOT ? gr : ((front & (r2[a] < g.rc2) & !lowp[a]) ? gr : 0.0);
                         fg[3 * a] += gh * dx[a];
                         fg[3 * a + 1] += gh * dy[a];
                         fg[3 * a + 2] += gh * dz[a];
@@ -1820,6 +1860,8 @@ k_cpair(CPairArgs A_, PairConsts c_, PairConsts g_, CEpiArgs E) {
         tabh = s_lds;
 #endif
         tabg = s_lds + host_bytes;
+        // the zero slot, behind the tables (kernels with site-site tables have nothing else there)
+        if (SS && threadIdx.x < AMM_CPAIR_ZERO_SLOT / 16) *reinterpret_cast<double2 *>(s_lds + used + 16 * (int)threadIdx.x) = make_double2(0.0, 0.0);
     }
     const double *erfcx = amm_erfcx_table_dev_c;
     double2 *s_li = nullptr;
@@ -1891,9 +1933,9 @@ k_cpair(CPairArgs A_, PairConsts c_, PairConsts g_, CEpiArgs E) {
         double f[9], fg[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) f[k] = fg[k] = 0.0;
-        if (A.per_pair_image) cwalk_rows<FAM, CMODE, GFAM, 2, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, row, nfront, nn, sub, lpa, cs, f, fg CWALK_T_ARG);
-        else if (interior) cwalk_rows<FAM, CMODE, GFAM, 0, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, row, nfront, nn, sub, lpa, cs, f, fg CWALK_T_ARG);
-        else cwalk_rows<FAM, CMODE, GFAM, 1, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, row, nfront, nn, sub, lpa, cs, f, fg CWALK_T_ARG);
+        if (A.per_pair_image) cwalk_rows<FAM, CMODE, GFAM, 2, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, row, nfront, nn, sub, lpa, cs, used, f, fg CWALK_T_ARG);
+        else if (interior) cwalk_rows<FAM, CMODE, GFAM, 0, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, row, nfront, nn, sub, lpa, cs, used, f, fg CWALK_T_ARG);
+        else cwalk_rows<FAM, CMODE, GFAM, 1, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, row, nfront, nn, sub, lpa, cs, used, f, fg CWALK_T_ARG);
         task += nwx;
         has = seek();
         if (AHEAD && has) pre_rows();
@@ -2076,7 +2118,7 @@ static int launch_cpair_t(amm_ctx *ctx, const CPairArgs &A, const PairConsts &c,
     static CLaunchCfg cfg[64];
     CLaunchCfg &k = cfg[ctx->device & 63];
     int lds = A.host_bytes + (DUAL ? A.guest_bytes : 0);
-    if (SS) lds += A.host_ss_bytes + (DUAL ? A.guest_ss_bytes : 0);
+    if (SS) lds += A.host_ss_bytes + (DUAL ? A.guest_ss_bytes : 0) + AMM_CPAIR_ZERO_SLOT;
     else lds += AMM_ERFCX_NI * AMM_ERFCX_NC * 8 + (BS / 64) * 192 * 16;
     auto kern = k_cpair<FAM, CMODE, GFAM, BS, SMASK, EPI>;
     if (lds > k.lds_set) {
@@ -2134,7 +2176,7 @@ template <int FAM, int CMODE, int GFAM>
 static int launch_cpair_s(amm_ctx *ctx, CPairArgs A, const PairConsts &c, const PairConsts &g, const CEpiArgs *E = nullptr, bool *epi_done = nullptr) {
     constexpr bool DUAL = GFAM >= 0;
     bool ss = ctx->opt_site_tab && A.host_ss_bytes > 0 && (!DUAL || A.guest_ss_bytes > 0);
-    if (ss && A.host_bytes + A.host_ss_bytes + (DUAL ? A.guest_bytes + A.guest_ss_bytes : 0) > AMM_CPAIR_LDS_LIMIT) ss = false;
+    if (ss && A.host_bytes + A.host_ss_bytes + (DUAL ? A.guest_bytes + A.guest_ss_bytes : 0) + AMM_CPAIR_ZERO_SLOT > AMM_CPAIR_LDS_LIMIT) ss = false;
 #ifndef AMM_CLUSTER_TUNE
     if (ss && E) {
         if (epi_done) *epi_done = true;
@@ -2562,7 +2604,7 @@ int amm_cluster_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, doub
         // (the kernels that carry an epilogue: site-site tables, and for two forces the fused pass of launch_cdual)
         bool kernel = ctx->opt_site_tab && ss_bytes_of(pf) > 0 && (!guest || ss_bytes_of(guest) > 0);
         const int lds = pf->pc.tab.nint * AMM_TAB_STRIDE + ss_bytes_of(pf) + (guest ? guest->pc.tab.nint * AMM_TAB_STRIDE + ss_bytes_of(guest) : 0);
-        kernel = kernel && lds <= AMM_CPAIR_LDS_LIMIT;
+        kernel = kernel && lds + AMM_CPAIR_ZERO_SLOT <= AMM_CPAIR_LDS_LIMIT;
         if (guest) kernel = kernel && guest->pc.family == AMM_NEAR_FSWITCH && (pf->pc.family == AMM_DAMPED || pf->pc.family == AMM_NONBONDED);
         state_mode = kernel;
     }

@@ -2228,10 +2228,36 @@ int amm_pair_count_within_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos,
 extern "C" __attribute__((weak)) const char *amm_variant_tag(void);
 const char *amm_kernel_revision_impl() {
 #ifdef AMM_CLUSTER_TUNE
-    return "r08-buildtabs-tune";
+    return "r09-zeroslot-tune";
 #else
-    return amm_variant_tag ? "r08-buildtabs-tune" : "r08-buildtabs";
+    return amm_variant_tag ? "r09-zeroslot-tune" : "r09-zeroslot";
 #endif
+}
+
+// amm_pair_table_check: the tables of a descriptor built on the host as amm_pair_build_table builds them (site-site table: for sites
+// of one sigma, eps and charge; site_eps = 0: none) and the interval of every r2 a counting pair can have at their ends and
+// boundaries (pair_tab.h: amm_tab_indices_in_range).  No device is touched.
+int amm_pair_table_check_impl(const amm_pair_desc &d, double site_sigma, double site_eps, double site_q, long long out[8]) {
+    PairConsts pc;
+    if (amm_pair_build_consts(d, pc)) return 1;
+    std::vector<double> coef;
+    SiteTable ss;
+    ss.want = site_eps > 0.0 && site_sigma > 0.0 && site_q != 0.0;
+    ss.sig = site_sigma;
+    ss.eps4 = 4.0 * site_eps;
+    ss.QQ = pc.Kc * site_q * site_q;
+    amm_build_coulomb_table(pc, coef, &ss);
+    if (ss.coef.empty()) pc.tab.ss_first = -1;
+    const TabIndexCheck R = amm_tab_indices_in_range(pc.tab, amm_tab_pass_rc2(pc));
+    out[0] = pc.tab.nint;
+    out[1] = pc.tab.ss_first;
+    out[2] = R.points;
+    out[3] = R.bad;
+    out[4] = R.idx_min;
+    out[5] = R.idx_max;
+    out[6] = pc.tab.nA;
+    out[7] = AMM_TAB_SHIFT - pc.tab.shiftB;
+    return 0;
 }
 
 // radial Coulomb table of the force-only traversal (pair_tab.h): built from the descriptor alone, once per pair force
@@ -2263,6 +2289,13 @@ int amm_pair_build_table(PairForce *pf) {
     // switching window or a high DAMPED degree can leave the table short of the arithmetic's accuracy.  Such a force keeps
     // the analytic kernels (no table: `tab_ok` is false for it, and a guest without a table disables the one-pass forms).
     if (pf->pc.tab.nint > 0 && !(pf->tab_error <= AMM_TAB_MAX_ERROR)) {
+        pf->pc.tab.nint = 0;
+        coef.clear();
+    }
+    // Likewise the promise that lets the molecule-row kernels read a table without clamping the interval (amm_tab_fetch_pass): a
+    // pair that counts lies inside it.  True by construction (one interval beyond the cutoff, r2min just above the first); a table
+    // that broke it would be read out of bounds, so it is tested on every table, and a force whose table fails keeps the analytic kernels.
+    if (pf->pc.tab.nint > 0 && amm_tab_indices_in_range(pf->pc.tab, amm_tab_pass_rc2(pf->pc)).bad != 0) {
         pf->pc.tab.nint = 0;
         coef.clear();
     }

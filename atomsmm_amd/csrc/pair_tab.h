@@ -291,6 +291,64 @@ static inline double amm_build_coulomb_table(PairConsts &pc, std::vector<double>
     return worst;
 }
 
+// The interval of r2 as the kernels form it (amm_tab_fetch: w = r2 * scale in double, the exponent and the top mantissa bits of w
+// minus the zone's base), WITHOUT the clamp to [0, nint): negative below the table, >= nint beyond it.
+static inline int amm_tab_index_unclamped(const PairTab &T, double r2) {
+    const double w = r2 * T.scale;
+    unsigned long long bits;
+    memcpy(&bits, &w, 8);
+    const unsigned hi = (unsigned)(bits >> 32);
+    const bool above = hi >= 0x3FF00000u;
+    const unsigned raw = hi >> (above ? (unsigned)T.shiftB : (unsigned)AMM_TAB_SHIFT);
+    return (int)(raw - (unsigned)(above ? T.rawB_minus_nA : T.baseA));
+}
+// the cutoff the molecule-row kernels test a pair of this force against (r2 < rc2; a guarded force: its guard radius, cluster.hip)
+static inline double amm_tab_pass_rc2(const PairConsts &pc) {
+    return ((pc.flags & AMM_GUARD_RC0) && pc.rc0 > 0.0) ? std::min(pc.rc2, pc.rc0 * pc.rc0) : pc.rc2;
+}
+// Do the look-ups that read a table without the clamp (amm_tab_fetch_pass) stay inside it?  A pair that passes has
+// r2min <= r2 < rc2, a site pair ss_r2min <= r2 < rc2 as well.  The index is a non-decreasing function of r2 (w = r2 * scale is
+// rounded monotonically, and the index is the leading bits of w), so the two ends decide; the test walks every interval boundary
+// +- 1 ulp all the same, so that a gap or an overlap between the zones would show.  -> points tested, how many fell outside
+// [0, nint) -- site pairs: [ss_first, nint) -- and the smallest and largest index met.
+struct TabIndexCheck {
+    long long points = 0, bad = 0;
+    int idx_min = 0x7fffffff, idx_max = -0x7fffffff - 1;
+};
+static inline TabIndexCheck amm_tab_indices_in_range(const PairTab &T, double rc2) {
+    TabIndexCheck R;
+    if (T.nint <= 0) return R;
+    const double top = std::nextafter(rc2, 0.0);
+    auto test = [&](double r2, double floor_r2, int first) {
+        if (!(r2 >= floor_r2 && r2 <= top)) return;
+        const int idx = amm_tab_index_unclamped(T, r2);
+        ++R.points;
+        if (idx < first || idx >= T.nint) ++R.bad;
+        R.idx_min = std::min(R.idx_min, idx);
+        R.idx_max = std::max(R.idx_max, idx);
+    };
+    for (int site = 0; site < (T.ss_first >= 0 ? 2 : 1); ++site) {
+        const double floor_r2 = site ? std::max(T.r2min, T.ss_r2min) : T.r2min;
+        const int first = site ? T.ss_first : 0;
+        test(floor_r2, floor_r2, first);
+        test(std::nextafter(floor_r2, INFINITY), floor_r2, first);
+        test(top, floor_r2, first);
+        for (int j = 0; j <= T.nint; ++j) {
+            long double lo, width;
+            amm_tab_interval(T, j < T.nint ? j : T.nint - 1, lo, width);
+            const double b = (double)((j < T.nint ? lo : lo + width) / (long double)T.scale);
+            double below = b, above = b;
+            for (int k = 0; k < 3; ++k) {          // (the division rounds: the boundary in r2 lies within an ulp or two of b)
+                test(below, floor_r2, first);
+                if (k) test(above, floor_r2, first);
+                below = std::nextafter(below, 0.0);
+                above = std::nextafter(above, INFINITY);
+            }
+        }
+    }
+    return R;
+}
+
 // ------------------------------------------------------------------------------------------------ device
 #if defined(__HIPCC__)
 #include "pair_math.h"
@@ -381,6 +439,33 @@ __device__ __forceinline__ TabLookup amm_tab_fetch(const char *lds_tab, const Pa
 #else
     L.c45 = cf[2];
 #endif
+    return L;
+}
+// The look-up of a pair whose force counts only if `pass`: a pair that does not pass reads the slot of zeros at `zero_addr` (48 bytes
+// of +0.0, 16-byte aligned), so its Horner chain yields +0 and no select on the force is needed behind it -- one select on the byte
+// address instead of two on the halves of a double.  No clamp of the interval either: `pass` must imply r2min <= r2 < rc2 (and
+// ss_r2min <= r2 where the pair reads a site-site table), which puts the interval inside the table (amm_tab_index_unclamped /
+// amm_tab_indices_in_range above: tested for every table when it is built); the index of any other lane is never used.
+// Addresses are LDS byte addresses (amm_lds_addr): `tab_addr` that of the table's interval 0 -- Coulomb table, or where the
+// site-site table's would lie -- so that interval and table make ONE multiply-add and the select acts on the final address.
+__device__ __forceinline__ unsigned amm_lds_addr(const char *p) {
+    return (unsigned)(size_t)(const __attribute__((address_space(3))) char *)p;
+}
+__device__ __forceinline__ TabLookup amm_tab_fetch_pass(unsigned tab_addr, const PairTab &T, double r2, bool pass, unsigned zero_addr) {
+    const double w = r2 * T.scale;
+    const unsigned hi = (unsigned)__double2hiint(w);
+    const bool above = hi >= 0x3FF00000u;
+    const unsigned sh = above ? (unsigned)T.shiftB : (unsigned)AMM_TAB_SHIFT;
+    const unsigned raw = hi >> sh;
+    const unsigned idx = raw - (unsigned)(above ? T.rawB_minus_nA : T.baseA);
+    const double centre = __hiloint2double((int)((raw << sh) | (unsigned)(above ? T.halfB : (1 << (AMM_TAB_SHIFT - 1)))), 0);
+    TabLookup L;
+    L.t = w - centre;
+    const unsigned at = __umul24(idx, AMM_TAB_STRIDE) + tab_addr;
+    const double2 *cf = (const double2 *)reinterpret_cast<const __attribute__((address_space(3))) double2 *>(pass ? at : zero_addr);
+    L.c01 = cf[0];
+    L.c23 = cf[1];
+    L.c45 = cf[2];
     return L;
 }
 __device__ __forceinline__ double amm_tab_horner(const TabLookup &L) {

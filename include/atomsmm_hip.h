@@ -564,6 +564,13 @@ int amm_pair_row_padding(amm_ctx *ctx, int32_t force_id, int64_t out[2]);
 /* Revision tag of the pair-traversal kernels: measurements kept under profiles/ carry it, and bench.py drops a stored
  * figure (the PMC traffic) once the kernels it was measured on have changed. */
 const char *amm_kernel_revision(void);
+/* Host-only check of a descriptor's radial tables (no device is touched): builds the Coulomb table -- and, for sites of one
+ * (sigma, eps, q), site_eps > 0, the site-site table -- as amm_pair_create does, and forms the interval index WITHOUT the clamp, as
+ * the molecule-row kernels do for a pair that counts, at r2 = r2min, the next double, every interval boundary +- 2 ulp and the
+ * last double below rc^2 (site pairs: from ss_r2min).  out = { intervals, first interval of the site-site table or -1, points
+ * tested, points whose index fell outside the table, smallest index, largest index, intervals below the kink, refinement level of
+ * the switching zone }.  out[3] must be 0: amm_pair_create drops a table for which it is not (analytic kernels). */
+int amm_pair_table_check(const amm_pair_desc *desc, double site_sigma, double site_eps, double site_q, int64_t out[8]);
 /* HIP-event timing of the dominant kernel (pair traversal) on the context stream. */
 /* on = 1: HIP events around every pair-kernel launch; on = -(force_id + 1): only around that force's launches
  * (two event packets per timed launch cost ~4 us of stream time each: time what you report); 0: off. */
