@@ -53,6 +53,7 @@ EXPORTS = [
     'amm_set_box', 'amm_box_stats', 'amm_mol_define', 'amm_mol_scale',
     'amm_pair_expr_create', 'amm_pair_expr_set_globals', 'amm_pair_expr_set_tables',
     'amm_term_expr_create', 'amm_term_expr_set_globals', 'amm_term_expr_set_params', 'amm_term_expr_release',
+    'amm_cv_create', 'amm_cv_set_globals', 'amm_cv_set_variables', 'amm_cv_values', 'amm_cv_energy_derivative', 'amm_cv_release',
     'amm_run_rule_stats',
 ]
 
@@ -180,6 +181,12 @@ def lib():
         L.amm_term_expr_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
         L.amm_term_expr_set_params.argtypes = [vp, C.c_int32, dp, C.c_int32, C.c_int32]
         L.amm_term_expr_release.argtypes = [vp, C.c_int32]
+        L.amm_cv_create.argtypes = [vp, ip, C.c_int32, C.c_int32, ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip]
+        L.amm_cv_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
+        L.amm_cv_set_variables.argtypes = [vp, C.c_int32, dp, C.c_int32]
+        L.amm_cv_values.argtypes = [vp, C.c_int32, vp, dp]
+        L.amm_cv_energy_derivative.argtypes = [vp, C.c_int32, vp, vp]
+        L.amm_cv_release.argtypes = [vp, C.c_int32]
         L.amm_pair_share_list.argtypes = [vp, C.c_int32, C.c_int32]
         L.amm_bonded_create.argtypes = [vp, ip]
         L.amm_bonded_add_terms.argtypes = [vp, C.c_int32, C.c_int32, ip, dp, C.c_int32, C.c_int32, C.POINTER(PairDesc)]
@@ -470,6 +477,41 @@ class HipContext:
     def term_expr_release(self, fid):
         """Free a term-expression force (its id is retired)."""
         _chk(lib().amm_term_expr_release(self.h, fid))
+
+    def cv_create(self, inner_ids, n_deriv, code, consts, globals_):
+        """A CustomCVForce with any energy text (csrc/cv.hip): the ids of the inner forces in the order of the collective variables
+        (bond-list sets or term-expression forces, members of no group, the caller's to release), the program of expr.compile_cv --
+        its variables are the collective variables, then the n_deriv derivative parameters -- and the values of its globals."""
+        i_, ip_ = _hi(inner_ids)
+        c_, cp = _hi(code)
+        k_, kp = _hd(consts if len(consts) else [0.0])
+        g_, gp = _hd(globals_ if len(globals_) else [0.0])
+        fid = C.c_int32()
+        _chk(lib().amm_cv_create(self.h, ip_, len(i_), int(n_deriv), cp, len(c_), kp, len(consts), gp, len(globals_), C.byref(fid)))
+        return fid.value
+
+    def cv_set_globals(self, fid, globals_):
+        g_, gp = _hd(globals_ if len(globals_) else [0.0])
+        _chk(lib().amm_cv_set_globals(self.h, fid, gp, len(globals_)))
+
+    def cv_set_variables(self, fid, values):
+        """Current values of the derivative parameters, in the order of addEnergyParameterDerivative."""
+        v_, vp = _hd(values if len(values) else [0.0])
+        _chk(lib().amm_cv_set_variables(self.h, fid, vp, len(values)))
+
+    def cv_values(self, fid, pos, n_cv):
+        """The collective variables at `pos` (evaluates the inner forces; waits for the stream)."""
+        out = np.zeros(int(n_cv), dtype=np.float64)
+        _chk(lib().amm_cv_values(self.h, fid, _ptr(pos), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def cv_energy_derivative(self, fid, pos, out):
+        """dE/dp of every derivative parameter, added to the device tensor `out` (one double per parameter); no wait."""
+        _chk(lib().amm_cv_energy_derivative(self.h, fid, _ptr(pos), _ptr(out)))
+
+    def cv_release(self, fid):
+        """Free a collective-variable force (its id is retired; the inner forces stay)."""
+        _chk(lib().amm_cv_release(self.h, fid))
 
     def pme_create(self, alpha, grid, q, Kc=KC):
         """Reciprocal space of a PME / Ewald NonbondedForce (smooth PME, order 5) on a grid[0] x grid[1] x grid[2] mesh."""

@@ -20,7 +20,14 @@ int amm_bonded_npar(int kind);
 static thread_local std::string g_error;
 void amm_set_error(const std::string &msg) { g_error = msg; }
 
+// an id of a collective-variable force given to an entry point of another family: the message names the type
+static bool is_cv(amm_ctx *ctx, int id, const char *wanted) {
+    if (!(ctx && id >= 0 && id < (int)ctx->forces.size() && ctx->forces[id].type == AMM_FORCE_CV)) return false;
+    amm_set_error(std::string("not ") + wanted + ": force " + std::to_string(id) + " is a collective-variable force (AMM_FORCE_CV: amm_cv_*)");
+    return true;
+}
 static PairForce *get_pair(amm_ctx *ctx, int id) {
+    if (is_cv(ctx, id, "a pair force")) return nullptr;
     if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_PAIR) {
         amm_set_error("invalid pair force id");
         return nullptr;
@@ -32,6 +39,7 @@ static BondedSet *get_bonded(amm_ctx *ctx, int id) {
         amm_set_error("not a bond-list set: force " + std::to_string(id) + " is a term-expression force (amm_term_expr_*)");
         return nullptr;
     }
+    if (is_cv(ctx, id, "a bond-list set")) return nullptr;
     if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_BONDED) {
         amm_set_error("invalid bonded force id");
         return nullptr;
@@ -48,6 +56,7 @@ int amm_force_eval_dispatch(amm_ctx *ctx, int force_id, const double *d_pos, dou
     if (f.type == AMM_FORCE_PAIR) return amm_pair_eval_impl(ctx, f.pair, d_pos, d_force, accumulate, d_energy);
     if (f.type == AMM_FORCE_PME) return amm_pme_eval_impl(ctx, f.pme, d_pos, d_force, accumulate, d_energy);
     if (f.type == AMM_FORCE_TERM_EXPR) return amm_term_expr_eval_impl(ctx, f.term, d_pos, d_force, accumulate, d_energy);
+    if (f.type == AMM_FORCE_CV) return amm_cv_eval_impl(ctx, f.cv, d_pos, d_force, accumulate, d_energy);
     return amm_bonded_eval_impl(ctx, f.bonded, d_pos, d_force, accumulate, d_energy);
 }
 
@@ -135,6 +144,7 @@ int amm_destroy(amm_ctx *ctx) {
         }
         if (f.pme) amm_pme_free(f.pme);
         if (f.term) amm_term_expr_free(f.term);
+        if (f.cv) amm_cv_free(f.cv);
     }
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
     if (ctx->d_expr_part) (void)hipFree(ctx->d_expr_part);
@@ -962,6 +972,7 @@ int amm_bonded_release(amm_ctx *ctx, int32_t force_id) {
 }
 
 static TermExprForce *get_term_expr(amm_ctx *ctx, int id, const char *who) {
+    if (is_cv(ctx, id, "a term-expression force")) return nullptr;
     if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_TERM_EXPR) {
         amm_set_error(std::string(who) + ": not a term-expression force id");
         return nullptr;
@@ -1051,6 +1062,75 @@ int amm_term_expr_release(amm_ctx *ctx, int32_t force_id) {
     return 0;
 }
 
+static CvForce *get_cv(amm_ctx *ctx, int id, const char *who) {
+    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_CV) {
+        amm_set_error(std::string(who) + ": not the id of a collective-variable force (AMM_FORCE_CV)");
+        return nullptr;
+    }
+    return ctx->forces[id].cv;
+}
+
+// CustomCVForce(any energy text): the compiled text (atomsmm_amd/expr.py: compile_cv) and the inner forces, one per collective variable
+int amm_cv_create(amm_ctx *ctx, const int32_t *inner_ids, int32_t n_cv, int32_t n_deriv, const int32_t *code, int32_t ncode,
+                  const double *consts, int32_t nconst, const double *globals, int32_t nglobal, int32_t *force_id) {
+    if (!ctx || !inner_ids || !code || !force_id || (nconst > 0 && !consts) || (nglobal > 0 && !globals)) {
+        amm_set_error("amm_cv_create: null argument");
+        return 1;
+    }
+    CvForce *cv = nullptr;
+    if (amm_cv_create_impl(ctx, inner_ids, n_cv, n_deriv, code, ncode, consts, nconst, globals, nglobal, &cv)) return 1;
+    ForceObj fo;
+    fo.type = AMM_FORCE_CV;
+    fo.cv = cv;
+    ctx->forces.push_back(fo);
+    *force_id = (int32_t)ctx->forces.size() - 1;
+    return 0;
+}
+
+int amm_cv_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal) {
+    CvForce *cv = get_cv(ctx, force_id, "amm_cv_set_globals");
+    return cv ? amm_cv_set_globals_impl(ctx, cv, globals, nglobal) : 1;
+}
+
+int amm_cv_set_variables(amm_ctx *ctx, int32_t force_id, const double *values, int32_t n_deriv) {
+    CvForce *cv = get_cv(ctx, force_id, "amm_cv_set_variables");
+    return cv ? amm_cv_set_variables_impl(ctx, cv, values, n_deriv) : 1;
+}
+
+int amm_cv_values(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *h_out) {
+    CvForce *cv = get_cv(ctx, force_id, "amm_cv_values");
+    if (!cv) return 1;
+    if (!d_pos || !h_out) {
+        amm_set_error("amm_cv_values: null argument");
+        return 1;
+    }
+    return amm_cv_values_impl(ctx, cv, d_pos, h_out);
+}
+
+int amm_cv_energy_derivative(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *d_out) {
+    CvForce *cv = get_cv(ctx, force_id, "amm_cv_energy_derivative");
+    if (!cv) return 1;
+    if (!d_pos || !d_out) {
+        amm_set_error("amm_cv_energy_derivative: null argument");
+        return 1;
+    }
+    return amm_cv_energy_derivative_impl(ctx, cv, d_pos, d_out);
+}
+
+int amm_cv_release(amm_ctx *ctx, int32_t force_id) {
+    CvForce *cv = get_cv(ctx, force_id, "amm_cv_release");
+    if (!cv) return 1;
+    AMM_HIP(hipStreamSynchronize(ctx->stream));            // nothing in flight may still read it
+    for (int g = 0; g < AMM_MAX_GROUPS; ++g) {
+        std::vector<int> &m = ctx->groups[g].forces;
+        m.erase(std::remove(m.begin(), m.end(), (int)force_id), m.end());
+    }
+    amm_cv_free(cv);
+    ctx->forces[force_id].cv = nullptr;
+    ctx->forces[force_id].type = AMM_FORCE_RELEASED;
+    return 0;
+}
+
 int amm_pme_create(amm_ctx *ctx, double alpha, int32_t nx, int32_t ny, int32_t nz, double Kc, const double *h_q,
                    int32_t *force_id) {
     if (!ctx || !h_q || !force_id) {
@@ -1074,6 +1154,7 @@ int amm_pme_create(amm_ctx *ctx, double alpha, int32_t nx, int32_t ny, int32_t n
 }
 
 static PmeForce *get_pme(amm_ctx *ctx, int id) {
+    if (is_cv(ctx, id, "a PME force")) return nullptr;
     if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_PME) {
         amm_set_error("not a PME force id");
         return nullptr;

@@ -244,13 +244,15 @@ struct ConstraintSet; // constraints.hip
 struct MinObj;        // minimize.hip: one L-BFGS minimisation (history ring, Gram matrix, direction)
 struct TermExprForce; // term_expr_vm.h: bond / angle / torsion / external terms with a compiled energy text (term_expr.hip)
 
-enum : int { AMM_FORCE_RELEASED = 0, AMM_FORCE_PAIR = 1, AMM_FORCE_BONDED = 2, AMM_FORCE_PME = 3, AMM_FORCE_TERM_EXPR = 4 };   // ForceObj::type
+struct CvForce;       // cv.hip: a CustomCVForce -- K inner forces and the compiled outer text over their energies
+enum : int { AMM_FORCE_RELEASED = 0, AMM_FORCE_PAIR = 1, AMM_FORCE_BONDED = 2, AMM_FORCE_PME = 3, AMM_FORCE_TERM_EXPR = 4, AMM_FORCE_CV = 5 };   // ForceObj::type
 struct ForceObj {
     int type = AMM_FORCE_RELEASED;
     PairForce *pair = nullptr;
     BondedSet *bonded = nullptr;
     PmeForce *pme = nullptr;
     TermExprForce *term = nullptr;
+    CvForce *cv = nullptr;
 };
 
 struct ExprDef {
@@ -525,6 +527,15 @@ int amm_term_expr_upload(amm_ctx *ctx, TermExprForce *tf, bool globals_only);
 int amm_term_expr_upload_params(amm_ctx *ctx, TermExprForce *tf, const double *h_params);
 int amm_term_expr_eval_impl(amm_ctx *ctx, TermExprForce *tf, const double *d_pos, double *d_force, int accumulate, double *d_energy);
 void amm_term_expr_free(TermExprForce *tf);
+// cv.hip: a force of type AMM_FORCE_CV (the inner ids stay the caller's; every inner evaluation goes through amm_force_eval_dispatch)
+int amm_cv_create_impl(amm_ctx *ctx, const int32_t *inner_ids, int n_cv, int n_deriv, const int32_t *code, int ncode, const double *consts,
+                       int nconst, const double *globals, int nglobal, CvForce **out);
+int amm_cv_eval_impl(amm_ctx *ctx, CvForce *cv, const double *d_pos, double *d_force, int accumulate, double *d_energy);
+int amm_cv_set_globals_impl(amm_ctx *ctx, CvForce *cv, const double *globals, int nglobal);
+int amm_cv_set_variables_impl(amm_ctx *ctx, CvForce *cv, const double *values, int n_deriv);
+int amm_cv_values_impl(amm_ctx *ctx, CvForce *cv, const double *d_pos, double *h_out);
+int amm_cv_energy_derivative_impl(amm_ctx *ctx, CvForce *cv, const double *d_pos, double *d_out);
+void amm_cv_free(CvForce *cv);
 // implemented in pair.hip / cells.hip / bonded.hip / integrate.hip
 int amm_pair_build_consts(const amm_pair_desc &d, PairConsts &pc);
 int amm_pair_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double *d_force, int accumulate,

@@ -23,6 +23,7 @@
 #define AMM_PEXPR_LOCALS 16
 #define AMM_PEXPR_PARAMS 3          // per-particle doubles a neighbour row carries per atom (charge slot, two Lennard-Jones slots)
 #define AMM_PEXPR_MAXTABLES 8       // tabulated functions of one force
+#define AMM_PEXPR_STRIDE 256        // lanes per block of k_pair_expr / k_term_expr: slot k of lane t is s_stack[k * 256 + t]
 
 // opcodes beside those of expr_vm.h (X_BUF, X_MASS, X_GAUSS, X_UNIFORM, X_DEVG, X_OUT and X_HORNER are not pair ops)
 enum { X_PAIR_R = 50, X_PAIR_P1 = 51, X_PAIR_P2 = 52 };
@@ -144,6 +145,7 @@ template <bool TAB>
 struct PairLeaves {
     static constexpr bool kPair = true;
     static constexpr bool kTables = TAB;
+    static constexpr int kStride = AMM_PEXPR_STRIDE;
     double r;
     const double *pa, *pb;
     const PairTableDesc *tabs;
@@ -154,8 +156,7 @@ struct PairLeaves {
 // (tv, td): a unary op touches no memory, a binary op reads one slot.  The elements below it are the lane's column of an LDS strip --
 // st[k * AMM_PEXPR_STRIDE], one (value, derivative) record of 16 bytes per slot, neighbouring lanes in neighbouring records
 // (conflict-free) -- and the locals are a private array.  `Leaves`: PairLeaves, or the TermLeaves of term_expr_vm.h -- the words of
-// the other kind compile to nothing.
-#define AMM_PEXPR_STRIDE 256        // lanes per block of k_pair_expr / k_term_expr: slot k of lane t is s_stack[k * 256 + t]
+// the other kind compile to nothing -- or the CvLeaves of cv.hip, whose strip is 32 lanes wide (Leaves::kStride: lanes of the strip).
 template <class Leaves>
 __device__ __forceinline__ void pexpr_run(const int *code, int ncode, const double *consts, const double *globals, const Leaves &leaves,
                                           double2 *st, double &E, double &dE) {
@@ -166,7 +167,7 @@ __device__ __forceinline__ void pexpr_run(const int *code, int ncode, const doub
 #define PEXPR_PUSH(V, D)                                                  \
     do {                                                                  \
         const double v_ = (V), d_ = (D);                                  \
-        if (sp) st[(sp - 1) * AMM_PEXPR_STRIDE] = make_double2(tv, td);   \
+        if (sp) st[(sp - 1) * Leaves::kStride] = make_double2(tv, td);   \
         tv = v_;                                                          \
         td = d_;                                                          \
         ++sp;                                                             \
@@ -204,7 +205,7 @@ __device__ __forceinline__ void pexpr_run(const int *code, int ncode, const doub
         case X_TAB_D2:
             if constexpr (Leaves::kPair) {
                 if constexpr (Leaves::kTables) {
-                    const double2 lhs = st[(sp - 2) * AMM_PEXPR_STRIDE];
+                    const double2 lhs = st[(sp - 2) * Leaves::kStride];
                     --sp;
                     tv = pexpr_table(leaves.tabs, op, arg, lhs.x, tv).x;
                     td = 0.0;
@@ -217,13 +218,13 @@ __device__ __forceinline__ void pexpr_run(const int *code, int ncode, const doub
             ld[arg] = td;
             --sp;
             if (sp) {
-                const double2 t = st[(sp - 1) * AMM_PEXPR_STRIDE];
+                const double2 t = st[(sp - 1) * Leaves::kStride];
                 tv = t.x;
                 td = t.y;
             }
         } break;
         case X_ADD: case X_SUB: case X_MUL: case X_DIV: case X_POW: case X_MIN: case X_MAX: case X_ATAN2: {
-            const double2 lhs = st[(sp - 2) * AMM_PEXPR_STRIDE];
+            const double2 lhs = st[(sp - 2) * Leaves::kStride];
             const double a = lhs.x, ad = lhs.y, b = tv, bd = td;
             --sp;
             if (op == X_ADD) {
@@ -258,7 +259,7 @@ __device__ __forceinline__ void pexpr_run(const int *code, int ncode, const doub
             }
         } break;
         case X_SELECT: {
-            const double2 c = st[(sp - 3) * AMM_PEXPR_STRIDE], a = st[(sp - 2) * AMM_PEXPR_STRIDE];
+            const double2 c = st[(sp - 3) * Leaves::kStride], a = st[(sp - 2) * Leaves::kStride];
             sp -= 2;
             const bool first = c.x != 0.0;
             tv = first ? a.x : tv;

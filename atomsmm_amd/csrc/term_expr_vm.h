@@ -35,6 +35,7 @@ int amm_expr_program_validate(const char *who, const int32_t *code, int ncode, i
 template <int NV>
 struct TermLeaves {
     static constexpr bool kPair = false;
+    static constexpr int kStride = AMM_PEXPR_STRIDE;
     double v[3], s[3];
     const double *p;                // the lane's column of the parameter array
     size_t stride;                  // n_terms
@@ -46,6 +47,7 @@ struct TermLeaves {
 template <>
 struct TermLeaves<1> {
     static constexpr bool kPair = false;
+    static constexpr int kStride = AMM_PEXPR_STRIDE;
     double v;
     const double *p;
     size_t stride;

@@ -244,6 +244,8 @@ class _Entry:
         self.program = None         # ... and its compiled program (expr.compile_pair)
         self.term_ids = []          # backend term-expression forces (csrc/term_expr.hip): a bond / angle / torsion / external force with
         self.term_expr = False      # a generic energy text; `program` is then that of expr.compile_term
+        self.cv = None              # a CustomCVForce on the collective-variable kernel (csrc/cv.hip): dict(id, names, derivs, inner, inner_ids);
+                                    # the id is also in term_ids, `program` is that of expr.compile_cv
 
 
 def slice_bounds(n_items, rank, world):
@@ -598,10 +600,21 @@ class Engine:
             self._translate_nonbonded(force, entry)
         elif isinstance(force, mm.CustomNonbondedForce):
             self._translate_custom_nonbonded(force, entry)
-        elif isinstance(force, mm.CustomBondForce):
-            self._translate_custom_bond(force, entry)
         elif isinstance(force, mm.CustomCVForce):
             self._translate_cv(force, entry)
+        elif self._translate_bond_list_force(force, entry):
+            pass
+        else:
+            raise InputError('force type {} is not supported by the HIP path'.format(force.__class__.__name__))
+        self._finish_entry(entry)
+        self.entries.append(entry)
+
+    def _translate_bond_list_force(self, force, entry):
+        """The classes whose terms are lists of atoms -- bonds, angles, torsions, external terms: bond-list terms of the hand-written
+        kinds, or a term-expression force for any other text.  False: `force` is none of them.  (Also the inner forces of a
+        CustomCVForce: _translate_cv_general.)"""
+        if isinstance(force, mm.CustomBondForce):
+            self._translate_custom_bond(force, entry)
         elif isinstance(force, mm.HarmonicBondForce):
             b = np.array([[r[0], r[1]] for r in force._bonds], dtype=np.int32).reshape(-1, 2)
             p = np.array([[r[2], r[3]] for r in force._bonds], dtype=np.float64).reshape(-1, 2)
@@ -627,9 +640,8 @@ class Engine:
             p = np.array([[r[4], r[5], r[6]] for r in force._torsions], dtype=np.float64).reshape(-1, 3)
             entry.terms.append((B.TORSION_PERIODIC, t, p, force.usesPeriodicBoundaryConditions(), None))
         else:
-            raise InputError('force type {} is not supported by the HIP path'.format(force.__class__.__name__))
-        self._finish_entry(entry)
-        self.entries.append(entry)
+            return False
+        return True
 
     def _pair_create(self, desc, q, sigma, eps, excl):
         if self.free_space:
@@ -1151,12 +1163,12 @@ class Engine:
 
     def _translate_cv(self, force, entry):
         """CustomCVForce of AlchemicalRespaSystem (systems.py:738-772): ((gt0-gt1)*S(lambda) + gt1) times ONE collective
-        variable, the energy of a CustomNonbondedForce -- i.e. that pair force with a lambda-dependent overall factor."""
-        if force.getNumCollectiveVariables() != 1:
-            raise NotImplementedError('CustomCVForce with %d collective variables' % force.getNumCollectiveVariables())
+        variable, the energy of a CustomNonbondedForce -- i.e. that pair force with a lambda-dependent overall factor.  Any other
+        CustomCVForce takes the general path (_translate_cv_general)."""
+        if force.getNumCollectiveVariables() != 1 or not isinstance(force.getCollectiveVariable(0), mm.CustomNonbondedForce) or \
+                getattr(force, '_functions', None):
+            return self._translate_cv_general(force, entry)
         name, inner = force.getCollectiveVariableName(0), force.getCollectiveVariable(0)
-        if not isinstance(inner, mm.CustomNonbondedForce):
-            raise NotImplementedError('CustomCVForce over a ' + inner.__class__.__name__)
         text = force.getEnergyFunction()
         used = X.symbols(text) - {name}
         self._register_globals(inner)
@@ -1171,6 +1183,103 @@ class Engine:
             return e1
         d = dict(self._descriptor_of(inner))
         self._translate_alchemical_pair(inner, entry, d, outer=outer, outer_depends=used)
+
+    _CV_INNER_CLASSES = ('HarmonicBondForce', 'HarmonicAngleForce', 'PeriodicTorsionForce', 'CustomBondForce', 'CustomAngleForce',
+                         'CustomTorsionForce', 'CustomExternalForce')
+
+    def _translate_cv_general(self, force, entry):
+        """CustomCVForce with any energy text over several collective variables, each the energy of a bond / angle / torsion / external
+        force: one backend object (csrc/cv.hip, AMM_FORCE_CV) that owns the compiled outer text (expr.compile_cv) and the ids of the
+        inner forces -- bond-list sets for the hand-written kinds, term-expression forces for any other text, members of no group.
+        Its id goes into entry.term_ids, so every loop over an entry's forces reaches it; entry.cv names it, its collective
+        variables and the parameters it differentiates in."""
+        cls = 'CustomCVForce'
+        n_cv = force.getNumCollectiveVariables()
+        if self.world > 1:
+            raise NotImplementedError('%s with a general energy expression (%d collective variables) runs on a single rank' % (cls, n_cv))
+        if getattr(force, '_functions', None):
+            raise NotImplementedError('%s: tabulated functions in the energy expression of collective variables are not supported' % cls)
+        if n_cv < 1:
+            raise InputError('%s without a collective variable' % cls)
+        text = force.getEnergyFunction()
+        names = [force.getCollectiveVariableName(k) for k in range(n_cv)]
+        gnames = [force.getGlobalParameterName(k) for k in range(force.getNumGlobalParameters())]
+        derivs = list(dict.fromkeys(getattr(force, '_derivs', ())))
+        for p in derivs:
+            if p not in gnames:
+                raise InputError('%s: addEnergyParameterDerivative(%r) names no global parameter of the force' % (cls, p))
+        inners = [force.getCollectiveVariable(k) for k in range(n_cv)]
+        for name, inner in zip(names, inners):
+            if not isinstance(inner, tuple(getattr(mm, c) for c in self._CV_INNER_CLASSES)):
+                raise NotImplementedError('%s over a %s (collective variable %s): outside the pattern of AlchemicalRespaSystem, a collective '
+                                          'variable is the energy of one of %s' % (cls, inner.__class__.__name__, name, ', '.join(self._CV_INNER_CLASSES)))
+            if hasattr(inner, 'getEnergyFunction'):
+                inner_globals = {inner.getGlobalParameterName(k) for k in range(inner.getNumGlobalParameters())}
+                shared = sorted(set(derivs) & inner_globals & X.symbols(inner.getEnergyFunction()))
+                if shared:
+                    raise NotImplementedError('%s: the derivative parameter %s is also read by the energy expression of collective variable %s; '
+                                              'parameter derivatives through inner forces are not supported' % (cls, shared[0], name))
+        try:
+            prog = X.compile_cv(text, names, derivs, gnames)
+        except X.ExpressionError as exc:
+            raise InputError('%s: not an energy expression the collective-variable kernel can run: %s' % (cls, exc))
+        subs, inner_ids = [], []
+        for name, inner in zip(names, inners):
+            self._register_globals(inner)
+            sub = _Entry(inner, entry.group)
+            self._translate_bond_list_force(inner, sub)
+            self._finish_entry(sub)
+            ids = ([sub.bonded_id] if sub.bonded_id is not None else []) + sub.term_ids
+            if not ids:          # (a force without terms: an empty bond-list set, energy 0)
+                sub.bonded_id = self._make_bonded([], sliced=False)
+                ids = [sub.bonded_id]
+            if sub.update is not None and not sub.term_expr:
+                raise NotImplementedError('%s: collective variable %s is a %s whose bond-list terms are rebuilt when a global parameter '
+                                          'changes' % (cls, name, inner.__class__.__name__))
+            subs.append(sub)
+            inner_ids.append(ids[0])
+        cid = self.ctx.cv_create(inner_ids, len(derivs), prog.code, prog.consts, [self.parameters[g] for g in prog.globals_])
+        if derivs:
+            self.ctx.cv_set_variables(cid, [self.parameters[p] for p in derivs])
+        entry.term_ids.append(cid)
+        entry.program = prog
+        entry.cv = dict(id=cid, names=names, derivs=derivs, inner=subs, inner_ids=inner_ids)
+        outer, seeded = set(prog.globals_), set(derivs)
+
+        def update(parameters, changed):
+            hit = False
+            if outer & changed:
+                self.ctx.cv_set_globals(cid, [parameters[g] for g in prog.globals_])
+                hit = True
+            if seeded & changed:
+                self.ctx.cv_set_variables(cid, [parameters[p] for p in derivs])
+                hit = True
+            for sub in subs:
+                if sub.update is not None and sub.update(parameters, changed):
+                    hit = True
+            return 'values' if hit else False
+        entry.update = update
+        entry.depends = outer | seeded | set().union(*[sub.depends for sub in subs])
+        reloads = [sub.reload for sub in subs if getattr(sub, 'reload', None) is not None]
+        if reloads:
+            def reload():          # updateParametersInContext: the inner forces that can read their per-term parameters again
+                for one in reloads:
+                    one()
+                return 'values'
+            entry.reload = reload
+
+    def collective_variable_values(self, force):
+        """CustomCVForce.getCollectiveVariableValues(context): the energies of the inner forces at the current positions."""
+        hits = [e for e in self.entries if e.force is force]
+        if not hits:
+            raise mm.OpenMMException('getCollectiveVariableValues: the force does not belong to this Context')
+        cv = getattr(hits[0], 'cv', None)
+        if cv is None:
+            raise NotImplementedError('getCollectiveVariableValues of a CustomCVForce over a CustomNonbondedForce (the pattern of '
+                                      'AlchemicalRespaSystem runs as a scaled pair force: its collective variable is never formed)')
+        values = self.ctx.cv_values(cv['id'], self.x, len(cv['names']))
+        self._check()
+        return tuple(float(v) for v in values)
 
     def _translate_lj_virial(self, force, entry):
         """ComputingSystem's dispersion virial (systems.py:893-897): a CustomNonbondedForce with the cutoff, switch and
@@ -2813,7 +2922,15 @@ class Engine:
                 if self._coll:
                     self._allreduce(out)
                 total += out.item() + sc['constant_derivative'](self.parameters)
+            elif entry.cv is not None and name in entry.cv['derivs']:
+                # the outer text's explicit dependence: the kernel's forward-mode pass seeded in this parameter (csrc/cv.hip)
+                out = torch.zeros(len(entry.cv['derivs']), dtype=torch.float64, device=self.x.device)
+                self.ctx.cv_energy_derivative(entry.cv['id'], self.x, out)
+                total += out[entry.cv['derivs'].index(name)].item()
             elif name in getattr(entry, 'depends', ()):
+                if entry.cv is not None:
+                    raise NotImplementedError('deriv(energy, %s) of a CustomCVForce that did not name the parameter with '
+                                              'addEnergyParameterDerivative' % name)
                 if getattr(entry, 'pair_expr', False):
                     raise NotImplementedError('deriv(energy, %s) of a CustomNonbondedForce with a generic energy expression (the '
                                               'pair-expression kernel differentiates in r only)' % name)

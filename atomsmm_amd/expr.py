@@ -36,6 +36,8 @@ PAIR_MAX_CODE, PAIR_MAX_CONSTS, PAIR_MAX_GLOBALS, PAIR_MAX_STACK, PAIR_MAX_LOCAL
 # a term expression shares them, but for its parameters: one row of doubles per term, not a neighbour row's three (csrc/term_expr_vm.h)
 TERM_MAX_PARAMS = 8
 PAIR_MAX_TABLES = 8         # tabulated functions of one force (AMM_PEXPR_MAXTABLES)
+# a collective-variable expression (compile_cv; csrc/cv.hip): one lane of the outer pass per variable
+CV_MAX_CVS, CV_MAX_DERIVS = 16, 16
 
 
 class ExpressionError(ValueError):
@@ -391,7 +393,7 @@ def _checked_program(text, resolve, what, functions=None):
     return prog
 
 
-def compile_term(text, variables, per_term_names, global_names):
+def compile_term(text, variables, per_term_names, global_names, what='term'):
     """Compile the energy text of a CustomBondForce / CustomAngleForce / CustomTorsionForce / CustomExternalForce for the
     term-expression kernels (csrc/term_expr.hip): variable k of `variables` -- ('r',), ('theta',) or ('x', 'y', 'z') -- is TERM_VAR k,
     per-term parameter k TERM_P k, a global parameter GLOBAL k (k: position in the program's globals_); auxiliary definitions, in any
@@ -409,7 +411,23 @@ def compile_term(text, variables, per_term_names, global_names):
             return ('op', 'TERM_VAR', variables.index(name))
         return ('global',) if name in global_names else None
 
-    return _checked_program(text, resolve, 'term')
+    return _checked_program(text, resolve, what)
+
+
+def compile_cv(text, cv_names, deriv_names, global_names):
+    """Compile the energy text of a CustomCVForce for the collective-variable kernel (csrc/cv.hip): collective variable k of `cv_names`
+    is TERM_VAR k, and the parameters the force asked derivatives for (`deriv_names`) follow as TERM_VAR K + p -- variables, not
+    globals, so that the kernel can seed each of them; every other parameter is GLOBAL k.  compile_term without per-term
+    parameters; the limits are its own plus CV_MAX_CVS and CV_MAX_DERIVS."""
+    cv_names, deriv_names = list(cv_names), list(deriv_names)
+    what = 'collective-variable'
+    if len(cv_names) > CV_MAX_CVS:
+        raise ExpressionError('%s expression: %d collective variables (limit %d)' % (what, len(cv_names), CV_MAX_CVS))
+    if len(deriv_names) > CV_MAX_DERIVS:
+        raise ExpressionError('%s expression: %d energy parameter derivatives (limit %d)' % (what, len(deriv_names), CV_MAX_DERIVS))
+    if len(set(cv_names + deriv_names)) != len(cv_names) + len(deriv_names):
+        raise ExpressionError('%s expression: a name is used twice among the collective variables and the derivative parameters' % what)
+    return compile_term(text, cv_names + deriv_names, [], set(global_names) - set(deriv_names), what=what)
 
 
 def compile_polynomial(coefficients, scale, shift, operand):

@@ -486,9 +486,35 @@ class CustomCVForce(Force, _GlobalParams):
         self._energy = energy
         self._cvs = []
         self._derivs = []
+        self._functions = []
 
     def getEnergyFunction(self):
         return self._energy
+
+    def addTabulatedFunction(self, name, function):
+        """Stored as OpenMM stores it; the HIP path refuses a CustomCVForce that has one when the Context is created."""
+        self._functions.append((name, function))
+        return len(self._functions) - 1
+
+    def getNumTabulatedFunctions(self):
+        return len(self._functions)
+
+    def getNumEnergyParameterDerivatives(self):
+        return len(self._derivs)
+
+    def getEnergyParameterDerivativeName(self, index):
+        return self._derivs[index]
+
+    def usesPeriodicBoundaryConditions(self):
+        return any(force.usesPeriodicBoundaryConditions() for _, force in self._cvs)
+
+    def getCollectiveVariableValues(self, context):
+        """The current values of the collective variables, in the order they were added."""
+        return context._engine.collective_variable_values(self)
+
+    def updateParametersInContext(self, context):
+        """Reload the inner forces that have a reload of their own (per-term parameters of a generic text)."""
+        context._engine.update_force_parameters(self)
 
     def addCollectiveVariable(self, name, force):
         self._cvs.append((name, copy.deepcopy(force)))

@@ -319,6 +319,10 @@ class ComputingSystem(_AtomsMM_System):
                 members = [(stretching_virial(force), 'bonded')]
             elif isinstance(force, openmm.CustomBondForce) and force.getNumBonds() > 0:
                 raise NotImplementedError('ComputingSystem: virial of a user CustomBondForce is not supported')
+            elif isinstance(force, openmm.CustomCVForce) and not (
+                    force.getNumCollectiveVariables() == 1 and isinstance(force.getCollectiveVariable(0), openmm.CustomNonbondedForce)):
+                raise NotImplementedError('ComputingSystem / PressureComputer: virial of a CustomCVForce over bonded collective variables '
+                                          'is not supported')
             else:
                 members = []
             for member, kind in members:

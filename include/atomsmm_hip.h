@@ -302,6 +302,36 @@ int amm_term_expr_set_params(amm_ctx *ctx, int32_t force_id, const double *h_par
 /* Free such a force; as amm_bonded_release, the id is retired and leaves every group definition. */
 int amm_term_expr_release(amm_ctx *ctx, int32_t force_id);
 
+/* CustomCVForce(any energy text) over several collective variables (force type AMM_FORCE_CV): E = f(cv_1 .. cv_K; globals), cv_k the
+ * potential energy of inner force k at the current positions; the atoms get -sum_k df/dcv_k grad cv_k.  An ordinary member of a
+ * group, evaluated through amm_force_eval; the amm_pair_*, amm_bonded_*, amm_term_expr_* and amm_pme_* calls refuse its id naming
+ * AMM_FORCE_CV.  The inner forces are evaluated on the stream, then ONE launch evaluates f and its partial derivatives (one lane
+ * per variable of a forward-mode pass) and combines the inner forces in the order k = 0 .. K-1: no atomics, the same bits run to run,
+ * no host round trip. */
+#define AMM_CV_MAX_CVS 16
+#define AMM_CV_MAX_DERIVS 16
+/* CustomCVForce(energy) + addCollectiveVariable x n_cv + addEnergyParameterDerivative x n_deriv.  inner_ids: n_cv ids of bond-list
+ * sets (amm_bonded_create .. amm_bonded_finalize) or term-expression forces (amm_term_expr_create) that the caller created, keeps in
+ * no group and releases itself; any other type is refused.  code / consts / globals: the program of atomsmm_amd.expr.compile_cv --
+ * the words of amm_term_expr_create with variable k (opcode 53) = collective variable k for k < n_cv and derivative parameter
+ * k - n_cv behind them, no per-term parameters; the same limits, checked here with a walk of the stack.  Scratch: 24 n_cv n bytes. */
+int amm_cv_create(amm_ctx *ctx, const int32_t *inner_ids, int32_t n_cv, int32_t n_deriv, const int32_t *code, int32_t ncode,
+                  const double *consts, int32_t nconst, const double *globals, int32_t nglobal, int32_t *force_id);
+/* Context.setParameter(name, value) for a global parameter of the outer text that is no derivative parameter: all of the program's
+ * globals, in its order. */
+int amm_cv_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal);
+/* Context.setParameter(name, value) for a parameter named by addEnergyParameterDerivative: the current values of all n_deriv. */
+int amm_cv_set_variables(amm_ctx *ctx, int32_t force_id, const double *values, int32_t n_deriv);
+/* CustomCVForce.getCollectiveVariableValues(context): evaluates the inner forces at d_pos and copies their n_cv energies to h_out.
+ * The one call of this family that waits for the stream. */
+int amm_cv_values(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *h_out);
+/* State.getEnergyParameterDerivatives() / deriv(energy, p) of a CustomIntegrator: df/dp of the n_deriv derivative parameters at
+ * d_pos -- the explicit dependence of the outer text -- ADDED to d_out[0 .. n_deriv) (device memory) on the stream; no wait, the
+ * shape of amm_pair_energy_derivative. */
+int amm_cv_energy_derivative(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *d_out);
+/* Free such a force and its scratch; the id is retired and leaves every group definition.  The inner ids stay the caller's. */
+int amm_cv_release(amm_ctx *ctx, int32_t force_id);
+
 /* Reciprocal space of a NonbondedForce with nonbondedMethod PME / Ewald, as RESPASystem and FarNonbondedForce
  * keep it in group 2 with the source force's Ewald tolerance / PME parameters (systems.py:74-75,
  * forces.py:185-188; setReciprocalSpaceForceGroup: utils.py:147-152).  Smooth PME, B-spline order 5, grid
