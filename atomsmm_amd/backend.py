@@ -16,6 +16,7 @@ PAIR_EXPR = 7      # any other CustomNonbondedForce text: compiled (expr.compile
 GUARD_RC0, COULOMB_EWALD, COULOMB_RF, SWITCH, NO_SHIFT, GROUP_LJ, GROUP_Q = 1, 2, 4, 8, 16, 32, 64
 FREE_SPACE = 128   # NoCutoff / CutoffNonPeriodic: all pairs, no box, no list (csrc/free.hip)
 TERM_BOND, TERM_ANGLE, TERM_TORSION, TERM_EXTERNAL = range(4)     # amm_term_kind: the variable of a term-expression force
+CVAR_X, CVAR_Y, CVAR_Z, CVAR_DISTANCE, CVAR_ANGLE, CVAR_DIHEDRAL = range(6)     # amm_compound_var: a variable of a compound-bond force
 BOND_HARMONIC, ANGLE_HARMONIC, BOND_LJC, BOND_NEAR, TORSION_PERIODIC, BOND_EWALD_EXCL = range(6)
 BOND_VIRIAL_HARMONIC, BOND_VIRIAL_LJ = 6, 7
 OP_EVAL, OP_KICK, OP_MOVE, OP_COPY, OP_COMBINE, OP_EXPR, OP_BATH = 1, 2, 3, 4, 5, 6, 7
@@ -54,6 +55,7 @@ EXPORTS = [
     'amm_pair_expr_create', 'amm_pair_expr_set_globals', 'amm_pair_expr_set_tables',
     'amm_term_expr_create', 'amm_term_expr_set_globals', 'amm_term_expr_set_params', 'amm_term_expr_release',
     'amm_cv_create', 'amm_cv_set_globals', 'amm_cv_set_variables', 'amm_cv_values', 'amm_cv_energy_derivative', 'amm_cv_release',
+    'amm_compound_create', 'amm_compound_set_globals', 'amm_compound_set_params', 'amm_compound_set_weights', 'amm_compound_release',
     'amm_run_rule_stats',
 ]
 
@@ -181,6 +183,12 @@ def lib():
         L.amm_term_expr_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
         L.amm_term_expr_set_params.argtypes = [vp, C.c_int32, dp, C.c_int32, C.c_int32]
         L.amm_term_expr_release.argtypes = [vp, C.c_int32]
+        L.amm_compound_create.argtypes = [vp, C.c_int32, ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip, ip, C.c_int32, ip, dp, C.c_int32, C.c_int32,
+                                          C.c_int32, ip, ip, dp, C.c_int32, ip]
+        L.amm_compound_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
+        L.amm_compound_set_params.argtypes = [vp, C.c_int32, dp, C.c_int32, C.c_int32]
+        L.amm_compound_set_weights.argtypes = [vp, C.c_int32, dp, C.c_int32]
+        L.amm_compound_release.argtypes = [vp, C.c_int32]
         L.amm_cv_create.argtypes = [vp, ip, C.c_int32, C.c_int32, ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip]
         L.amm_cv_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
         L.amm_cv_set_variables.argtypes = [vp, C.c_int32, dp, C.c_int32]
@@ -477,6 +485,57 @@ class HipContext:
     def term_expr_release(self, fid):
         """Free a term-expression force (its id is retired)."""
         _chk(lib().amm_term_expr_release(self.h, fid))
+
+    def compound_create(self, n_slots, code, consts, globals_, var_kinds, var_slots, idx, params, periodic=False, groups=None):
+        """A compound-bond force (csrc/compound.hip): the program and the variable table of expr.compile_compound -- var_kinds[k] one of
+        CVAR_*, var_slots[k] up to four positions within the bond --, the values of the program's globals in its order, `idx`
+        (n_bonds x n_slots particles, or groups) and `params` (n_params x n_bonds: parameter-major).  groups: None (the slots are
+        particles), or (ptr, atoms, weights) -- the members and weights of every group, CSR (a CustomCentroidBondForce)."""
+        c_, cp = _hi(code)
+        k_, kp = _hd(consts if len(consts) else [0.0])
+        g_, gp = _hd(globals_ if len(globals_) else [0.0])
+        n_vars = len(var_kinds)
+        vk_, vkp = _hi(var_kinds if n_vars else [0])
+        slots = np.zeros((max(n_vars, 1), 4), dtype=np.int32)
+        for k, row in enumerate(var_slots):
+            slots[k, :len(row)] = row
+        vs_, vsp = _hi(slots)
+        idx_ = np.asarray(idx, dtype=np.int32).reshape(-1, int(n_slots))
+        ix_, ixp = _hi(idx_ if idx_.size else [0])
+        par = np.asarray(params, dtype=np.float64)
+        par = par.reshape(-1, len(idx_)) if len(idx_) else np.zeros((par.shape[0] if par.ndim == 2 else 0, 0))
+        par_, pp = _hd(par if par.size else [0.0])
+        if groups is None:
+            n_groups, gpp, gap, gwp = 0, None, None, None
+        else:
+            ptr_, gpp = _hi(groups[0])
+            at_, gap = _hi(groups[1] if len(groups[1]) else [0])
+            w_, gwp = _hd(groups[2] if len(groups[2]) else [0.0])
+            n_groups = len(groups[0]) - 1
+        fid = C.c_int32(-1)
+        _chk(lib().amm_compound_create(self.h, int(n_slots), cp, len(c_), kp, len(consts), gp, len(globals_), vkp, vsp, n_vars, ixp, pp, len(idx_),
+                                       len(par), int(bool(periodic)), gpp, gap, gwp, n_groups, C.byref(fid)))
+        return fid.value
+
+    def compound_set_globals(self, fid, globals_):
+        g_, gp = _hd(globals_ if len(globals_) else [0.0])
+        _chk(lib().amm_compound_set_globals(self.h, fid, gp, len(globals_)))
+
+    def compound_set_params(self, fid, params, n_bonds):
+        """All per-bond values again (n_params x n_bonds, parameter-major)."""
+        par = np.asarray(params, dtype=np.float64)
+        par = par.reshape(-1, n_bonds) if n_bonds else np.zeros((par.shape[0] if par.ndim == 2 else 0, 0))
+        par_, pp = _hd(par if par.size else [0.0])
+        _chk(lib().amm_compound_set_params(self.h, fid, pp, int(n_bonds), len(par)))
+
+    def compound_set_weights(self, fid, weights):
+        """All group weights again, in the order of the groups' members."""
+        w_, wp = _hd(weights if len(weights) else [0.0])
+        _chk(lib().amm_compound_set_weights(self.h, fid, wp, len(weights)))
+
+    def compound_release(self, fid):
+        """Free a compound-bond force (its id is retired)."""
+        _chk(lib().amm_compound_release(self.h, fid))
 
     def cv_create(self, inner_ids, n_deriv, code, consts, globals_):
         """A CustomCVForce with any energy text (csrc/cv.hip): the ids of the inner forces in the order of the collective variables

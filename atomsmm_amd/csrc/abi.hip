@@ -26,8 +26,14 @@ static bool is_cv(amm_ctx *ctx, int id, const char *wanted) {
     amm_set_error(std::string("not ") + wanted + ": force " + std::to_string(id) + " is a collective-variable force (AMM_FORCE_CV: amm_cv_*)");
     return true;
 }
+// ... and an id of a compound-bond force
+static bool is_compound(amm_ctx *ctx, int id, const char *wanted) {
+    if (!(ctx && id >= 0 && id < (int)ctx->forces.size() && ctx->forces[id].type == AMM_FORCE_COMPOUND)) return false;
+    amm_set_error(std::string("not ") + wanted + ": force " + std::to_string(id) + " is a compound-bond force (AMM_FORCE_COMPOUND: amm_compound_*)");
+    return true;
+}
 static PairForce *get_pair(amm_ctx *ctx, int id) {
-    if (is_cv(ctx, id, "a pair force")) return nullptr;
+    if (is_cv(ctx, id, "a pair force") || is_compound(ctx, id, "a pair force")) return nullptr;
     if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_PAIR) {
         amm_set_error("invalid pair force id");
         return nullptr;
@@ -39,7 +45,7 @@ static BondedSet *get_bonded(amm_ctx *ctx, int id) {
         amm_set_error("not a bond-list set: force " + std::to_string(id) + " is a term-expression force (amm_term_expr_*)");
         return nullptr;
     }
-    if (is_cv(ctx, id, "a bond-list set")) return nullptr;
+    if (is_cv(ctx, id, "a bond-list set") || is_compound(ctx, id, "a bond-list set")) return nullptr;
     if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_BONDED) {
         amm_set_error("invalid bonded force id");
         return nullptr;
@@ -57,6 +63,7 @@ int amm_force_eval_dispatch(amm_ctx *ctx, int force_id, const double *d_pos, dou
     if (f.type == AMM_FORCE_PME) return amm_pme_eval_impl(ctx, f.pme, d_pos, d_force, accumulate, d_energy);
     if (f.type == AMM_FORCE_TERM_EXPR) return amm_term_expr_eval_impl(ctx, f.term, d_pos, d_force, accumulate, d_energy);
     if (f.type == AMM_FORCE_CV) return amm_cv_eval_impl(ctx, f.cv, d_pos, d_force, accumulate, d_energy);
+    if (f.type == AMM_FORCE_COMPOUND) return amm_compound_eval_impl(ctx, f.compound, d_pos, d_force, accumulate, d_energy);
     return amm_bonded_eval_impl(ctx, f.bonded, d_pos, d_force, accumulate, d_energy);
 }
 
@@ -145,6 +152,7 @@ int amm_destroy(amm_ctx *ctx) {
         if (f.pme) amm_pme_free(f.pme);
         if (f.term) amm_term_expr_free(f.term);
         if (f.cv) amm_cv_free(f.cv);
+        if (f.compound) amm_compound_free(f.compound);
     }
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
     if (ctx->d_expr_part) (void)hipFree(ctx->d_expr_part);
@@ -972,7 +980,7 @@ int amm_bonded_release(amm_ctx *ctx, int32_t force_id) {
 }
 
 static TermExprForce *get_term_expr(amm_ctx *ctx, int id, const char *who) {
-    if (is_cv(ctx, id, "a term-expression force")) return nullptr;
+    if (is_cv(ctx, id, "a term-expression force") || is_compound(ctx, id, "a term-expression force")) return nullptr;
     if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_TERM_EXPR) {
         amm_set_error(std::string(who) + ": not a term-expression force id");
         return nullptr;
@@ -1131,6 +1139,67 @@ int amm_cv_release(amm_ctx *ctx, int32_t force_id) {
     return 0;
 }
 
+static CompoundForce *get_compound(amm_ctx *ctx, int id, const char *who) {
+    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_COMPOUND) {
+        amm_set_error(std::string(who) + ": not the id of a compound-bond force (AMM_FORCE_COMPOUND)");
+        return nullptr;
+    }
+    return ctx->forces[id].compound;
+}
+
+// CustomCompoundBondForce / CustomCentroidBondForce(any energy text): the compiled text and its variable table
+// (atomsmm_amd/expr.py: compile_compound), the bonds' particles (or groups) and parameters, and for centroid bonds the groups
+int amm_compound_create(amm_ctx *ctx, int32_t n_slots, const int32_t *code, int32_t ncode, const double *consts, int32_t nconst,
+                        const double *globals, int32_t nglobal, const int32_t *var_kinds, const int32_t *var_slots, int32_t n_vars,
+                        const int32_t *h_idx, const double *h_params, int32_t n_bonds, int32_t n_params, int32_t periodic,
+                        const int32_t *group_ptr, const int32_t *group_atoms, const double *group_weights, int32_t n_groups,
+                        int32_t *force_id) {
+    if (!ctx || !code || !force_id || (nconst > 0 && !consts) || (nglobal > 0 && !globals) || (n_vars > 0 && (!var_kinds || !var_slots)) ||
+        (n_bonds > 0 && !h_idx)) {
+        amm_set_error("amm_compound_create: null argument");
+        return 1;
+    }
+    CompoundForce *cf = nullptr;
+    if (amm_compound_create_impl(ctx, n_slots, code, ncode, consts, nconst, globals, nglobal, var_kinds, var_slots, n_vars, h_idx, h_params,
+                                 n_bonds, n_params, periodic, group_ptr, group_atoms, group_weights, n_groups, &cf))
+        return 1;
+    ForceObj fo;
+    fo.type = AMM_FORCE_COMPOUND;
+    fo.compound = cf;
+    ctx->forces.push_back(fo);
+    *force_id = (int32_t)ctx->forces.size() - 1;
+    return 0;
+}
+
+int amm_compound_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal) {
+    CompoundForce *cf = get_compound(ctx, force_id, "amm_compound_set_globals");
+    return cf ? amm_compound_set_globals_impl(ctx, cf, globals, nglobal) : 1;
+}
+
+int amm_compound_set_params(amm_ctx *ctx, int32_t force_id, const double *h_params, int32_t n_bonds, int32_t n_params) {
+    CompoundForce *cf = get_compound(ctx, force_id, "amm_compound_set_params");
+    return cf ? amm_compound_set_params_impl(ctx, cf, h_params, n_bonds, n_params) : 1;
+}
+
+int amm_compound_set_weights(amm_ctx *ctx, int32_t force_id, const double *weights, int32_t n_members) {
+    CompoundForce *cf = get_compound(ctx, force_id, "amm_compound_set_weights");
+    return cf ? amm_compound_set_weights_impl(ctx, cf, weights, n_members) : 1;
+}
+
+int amm_compound_release(amm_ctx *ctx, int32_t force_id) {
+    CompoundForce *cf = get_compound(ctx, force_id, "amm_compound_release");
+    if (!cf) return 1;
+    AMM_HIP(hipStreamSynchronize(ctx->stream));            // nothing in flight may still read it
+    for (int g = 0; g < AMM_MAX_GROUPS; ++g) {
+        std::vector<int> &m = ctx->groups[g].forces;
+        m.erase(std::remove(m.begin(), m.end(), (int)force_id), m.end());
+    }
+    amm_compound_free(cf);
+    ctx->forces[force_id].compound = nullptr;
+    ctx->forces[force_id].type = AMM_FORCE_RELEASED;
+    return 0;
+}
+
 int amm_pme_create(amm_ctx *ctx, double alpha, int32_t nx, int32_t ny, int32_t nz, double Kc, const double *h_q,
                    int32_t *force_id) {
     if (!ctx || !h_q || !force_id) {
@@ -1154,7 +1223,7 @@ int amm_pme_create(amm_ctx *ctx, double alpha, int32_t nx, int32_t ny, int32_t n
 }
 
 static PmeForce *get_pme(amm_ctx *ctx, int id) {
-    if (is_cv(ctx, id, "a PME force")) return nullptr;
+    if (is_cv(ctx, id, "a PME force") || is_compound(ctx, id, "a PME force")) return nullptr;
     if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_PME) {
         amm_set_error("not a PME force id");
         return nullptr;

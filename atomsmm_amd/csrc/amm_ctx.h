@@ -245,7 +245,9 @@ struct MinObj;        // minimize.hip: one L-BFGS minimisation (history ring, Gr
 struct TermExprForce; // term_expr_vm.h: bond / angle / torsion / external terms with a compiled energy text (term_expr.hip)
 
 struct CvForce;       // cv.hip: a CustomCVForce -- K inner forces and the compiled outer text over their energies
-enum : int { AMM_FORCE_RELEASED = 0, AMM_FORCE_PAIR = 1, AMM_FORCE_BONDED = 2, AMM_FORCE_PME = 3, AMM_FORCE_TERM_EXPR = 4, AMM_FORCE_CV = 5 };   // ForceObj::type
+struct CompoundForce; // compound.hip: a CustomCompoundBondForce / CustomCentroidBondForce -- bonds over several particles or centres
+enum : int { AMM_FORCE_RELEASED = 0, AMM_FORCE_PAIR = 1, AMM_FORCE_BONDED = 2, AMM_FORCE_PME = 3, AMM_FORCE_TERM_EXPR = 4, AMM_FORCE_CV = 5,
+             AMM_FORCE_COMPOUND = 6 };   // ForceObj::type
 struct ForceObj {
     int type = AMM_FORCE_RELEASED;
     PairForce *pair = nullptr;
@@ -253,6 +255,7 @@ struct ForceObj {
     PmeForce *pme = nullptr;
     TermExprForce *term = nullptr;
     CvForce *cv = nullptr;
+    CompoundForce *compound = nullptr;
 };
 
 struct ExprDef {
@@ -536,6 +539,16 @@ int amm_cv_set_variables_impl(amm_ctx *ctx, CvForce *cv, const double *values, i
 int amm_cv_values_impl(amm_ctx *ctx, CvForce *cv, const double *d_pos, double *h_out);
 int amm_cv_energy_derivative_impl(amm_ctx *ctx, CvForce *cv, const double *d_pos, double *d_out);
 void amm_cv_free(CvForce *cv);
+// compound.hip: a force of type AMM_FORCE_COMPOUND (n_groups > 0: the slots of a bond are weighted centres of groups of atoms)
+int amm_compound_create_impl(amm_ctx *ctx, int n_slots, const int32_t *code, int ncode, const double *consts, int nconst, const double *globals,
+                             int nglobal, const int32_t *var_kinds, const int32_t *var_slots, int n_vars, const int32_t *h_idx,
+                             const double *h_params, int n_bonds, int n_params, int periodic, const int32_t *g_ptr, const int32_t *g_atoms,
+                             const double *g_weights, int n_groups, CompoundForce **out);
+int amm_compound_eval_impl(amm_ctx *ctx, CompoundForce *cf, const double *d_pos, double *d_force, int accumulate, double *d_energy);
+int amm_compound_set_globals_impl(amm_ctx *ctx, CompoundForce *cf, const double *globals, int nglobal);
+int amm_compound_set_params_impl(amm_ctx *ctx, CompoundForce *cf, const double *h_params, int n_bonds, int n_params);
+int amm_compound_set_weights_impl(amm_ctx *ctx, CompoundForce *cf, const double *weights, int n_members);
+void amm_compound_free(CompoundForce *cf);
 // implemented in pair.hip / cells.hip / bonded.hip / integrate.hip
 int amm_pair_build_consts(const amm_pair_desc &d, PairConsts &pc);
 int amm_pair_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double *d_force, int accumulate,

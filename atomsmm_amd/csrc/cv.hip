@@ -118,7 +118,7 @@ static const char *cv_type_name(int type) {
     }
 }
 
-// every inner id still names a bond-list set or a term-expression force (who: the entry point, for the message)
+// every inner id still names a bond-list set, a term-expression force or a compound-bond force (who: the entry point, for the message)
 static int cv_check_inner(amm_ctx *ctx, const int32_t *inner, int n_cv, const char *who) {
     for (int k = 0; k < n_cv; ++k) {
         const int id = inner[k];
@@ -127,9 +127,9 @@ static int cv_check_inner(amm_ctx *ctx, const int32_t *inner, int n_cv, const ch
             return 1;
         }
         const int type = ctx->forces[id].type;
-        if (type != AMM_FORCE_BONDED && type != AMM_FORCE_TERM_EXPR) {
+        if (type != AMM_FORCE_BONDED && type != AMM_FORCE_TERM_EXPR && type != AMM_FORCE_COMPOUND) {
             amm_set_error(std::string(who) + ": inner force " + std::to_string(k) + " (id " + std::to_string(id) + ") is " + cv_type_name(type) +
-                          ": a collective variable is the energy of a bond-list set or of a term-expression force");
+                          ": a collective variable is the energy of a bond-list set, of a term-expression force or of a compound-bond force");
             return 1;
         }
     }

@@ -246,6 +246,8 @@ class _Entry:
         self.term_expr = False      # a generic energy text; `program` is then that of expr.compile_term
         self.cv = None              # a CustomCVForce on the collective-variable kernel (csrc/cv.hip): dict(id, names, derivs, inner, inner_ids);
                                     # the id is also in term_ids, `program` is that of expr.compile_cv
+        self.compound = None        # a CustomCompoundBondForce / CustomCentroidBondForce (csrc/compound.hip): dict(id, variables, centroid);
+                                    # the id is also in term_ids, term_expr is set, `program` is that of expr.compile_compound
 
 
 def slice_bounds(n_items, rank, world):
@@ -639,6 +641,8 @@ class Engine:
             t = np.array([r[:4] for r in force._torsions], dtype=np.int32).reshape(-1, 4)
             p = np.array([[r[4], r[5], r[6]] for r in force._torsions], dtype=np.float64).reshape(-1, 3)
             entry.terms.append((B.TORSION_PERIODIC, t, p, force.usesPeriodicBoundaryConditions(), None))
+        elif isinstance(force, (mm.CustomCompoundBondForce, mm.CustomCentroidBondForce)):
+            self._translate_compound(force, entry)
         else:
             return False
         return True
@@ -1185,7 +1189,7 @@ class Engine:
         self._translate_alchemical_pair(inner, entry, d, outer=outer, outer_depends=used)
 
     _CV_INNER_CLASSES = ('HarmonicBondForce', 'HarmonicAngleForce', 'PeriodicTorsionForce', 'CustomBondForce', 'CustomAngleForce',
-                         'CustomTorsionForce', 'CustomExternalForce')
+                         'CustomTorsionForce', 'CustomExternalForce', 'CustomCompoundBondForce', 'CustomCentroidBondForce')
 
     def _translate_cv_general(self, force, entry):
         """CustomCVForce with any energy text over several collective variables, each the energy of a bond / angle / torsion / external
@@ -1482,6 +1486,102 @@ class Engine:
                 if not (depends & changed):
                     return False
                 self.ctx.term_expr_set_globals(tid, [parameters[g] for g in prog.globals_])
+                return 'values'
+            entry.update = update
+            entry.depends = depends
+
+    _COMPOUND_KINDS = dict(x=B.CVAR_X, y=B.CVAR_Y, z=B.CVAR_Z, distance=B.CVAR_DISTANCE, angle=B.CVAR_ANGLE, dihedral=B.CVAR_DIHEDRAL)
+
+    def _translate_compound(self, force, entry):
+        """A CustomCompoundBondForce or CustomCentroidBondForce: the text compiled with its variable table (expr.compile_compound) and
+        evaluated with one lane per (bond, variable) by the compound-bond kernels (csrc/compound.hip).  One backend force per
+        OpenMM force, carried in entry.term_ids as a term-expression force is, so every loop over an entry's forces reaches it."""
+        cls = force.__class__.__name__
+        centroid = isinstance(force, mm.CustomCentroidBondForce)
+        n_slots = force.getNumGroupsPerBond() if centroid else force.getNumParticlesPerBond()
+        if getattr(force, '_functions', None):
+            raise NotImplementedError('%s: tabulated functions in the energy expression are not supported' % cls)
+        if getattr(force, '_derivs', None):
+            raise NotImplementedError('%s: addEnergyParameterDerivative is not supported (the compound-bond kernel differentiates in '
+                                      'the geometric variables only)' % cls)
+        if self.world > 1:
+            raise NotImplementedError('%s runs on a single rank' % cls)
+        periodic = bool(force.usesPeriodicBoundaryConditions())
+        if periodic and self.free_space:
+            raise InputError('%s uses periodic boundary conditions in a System in free space' % cls)
+        names = [force.getPerBondParameterName(k) for k in range(force.getNumPerBondParameters())]
+        gnames = [force.getGlobalParameterName(k) for k in range(force.getNumGlobalParameters())]
+        try:
+            prog, variables = X.compile_compound(force.getEnergyFunction(), n_slots, 'g' if centroid else 'p', names, gnames)
+        except X.ExpressionError as exc:
+            raise InputError('%s: not an energy expression the compound-bond kernel can run: %s' % (cls, exc))
+        kinds = [self._COMPOUND_KINDS[kind] for kind, _ in variables]
+        slots = [list(s) for _, s in variables]
+
+        def groups():
+            masses = self.system._masses
+            ptr, atoms, weights = [0], [], []
+            for g, (particles, w) in enumerate(force._groups):
+                if not particles:
+                    raise mm.OpenMMException('%s: group %d is empty' % (cls, g))
+                if min(particles) < 0 or max(particles) >= self.n:
+                    raise mm.OpenMMException('%s: a particle index of group %d is out of range' % (cls, g))
+                w = list(w) if len(w) else [float(masses[i]) for i in particles]
+                if not (math.fsum(w) != 0.0 and math.isfinite(math.fsum(w))):
+                    raise mm.OpenMMException('%s: the weights of group %d sum to zero' % (cls, g))
+                atoms += list(particles)
+                weights += w
+                ptr.append(len(atoms))
+            return np.array(ptr, dtype=np.int32), np.array(atoms, dtype=np.int32), np.array(weights, dtype=np.float64)
+
+        def tables(limit):
+            rows = force._bonds
+            idx = np.zeros((len(rows), n_slots), dtype=np.int32)
+            par = np.zeros((len(names), len(rows)), dtype=np.float64)
+            for t, (members, p) in enumerate(rows):
+                if len(p) != len(names):
+                    raise mm.OpenMMException('%s: every bond needs %d parameters' % (cls, len(names)))
+                idx[t] = members
+                par[:, t] = p
+            if len(rows) and (idx.min() < 0 or idx.max() >= limit):
+                raise mm.OpenMMException('%s: a %s index is out of range' % (cls, 'group' if centroid else 'particle'))
+            return idx, par
+
+        grp = groups() if centroid else None
+        idx, par = tables(len(grp[0]) - 1 if centroid else self.n)
+        if centroid and len(grp[0]) == 1:
+            grp = None if not len(idx) else grp          # (no groups and no bonds: a force without terms)
+        fid = self.ctx.compound_create(n_slots, prog.code, prog.consts, [self.parameters[g] for g in prog.globals_], kinds, slots, idx, par,
+                                       periodic=periodic, groups=grp)
+        entry.term_ids.append(fid)
+        entry.term_expr = True
+        entry.program = prog
+        entry.compound = dict(id=fid, variables=variables, centroid=centroid)
+
+        def reload():          # updateParametersInContext: per-bond parameters and (centroid bonds) group weights are read again
+            fresh_grp = groups() if centroid else None
+            if centroid and grp is not None:
+                if len(fresh_grp[0]) != len(grp[0]):
+                    raise mm.OpenMMException('updateParametersInContext: the number of groups has changed')
+                if not (np.array_equal(fresh_grp[0], grp[0]) and np.array_equal(fresh_grp[1], grp[1])):
+                    raise mm.OpenMMException('updateParametersInContext: the particles of a group have changed')
+            fresh_idx, fresh = tables(len(fresh_grp[0]) - 1 if centroid else self.n)
+            if len(fresh_idx) != len(idx):
+                raise mm.OpenMMException('updateParametersInContext: the number of bonds has changed')
+            if not np.array_equal(fresh_idx, idx):
+                raise mm.OpenMMException('updateParametersInContext: the %s of a bond have changed' % ('groups' if centroid else 'particles'))
+            self.ctx.compound_set_params(fid, fresh, len(idx))
+            if centroid and grp is not None:
+                self.ctx.compound_set_weights(fid, fresh_grp[2])
+            return 'values'
+        entry.reload = reload
+        if prog.globals_:
+            depends = set(prog.globals_)
+
+            def update(parameters, changed):
+                if not (depends & changed):
+                    return False
+                self.ctx.compound_set_globals(fid, [parameters[g] for g in prog.globals_])
                 return 'values'
             entry.update = update
             entry.depends = depends

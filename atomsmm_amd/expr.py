@@ -233,11 +233,13 @@ def _folded_trees(main, defs):
     return fold(_parse(main)), definition
 
 
-def compile_per_dof(text, resolve, what='per-DOF', random_ok=True, fold=False, functions=None):
+def compile_per_dof(text, resolve, what='per-DOF', random_ok=True, fold=False, functions=None, name_calls=None):
     """Compile a per-DOF (or sum) expression.  `resolve(name)` returns ('buf', slot), ('mass',), ('global',), ('op', opcode name, arg)
     or None.  `what` names the kind of expression in error messages; random_ok=False: `gaussian` / `uniform` are errors; fold=True:
     subexpressions of literals are evaluated here (_folded_trees); functions: name -> (word, arguments, index) of the tabulated
-    functions a call may name (compile_pair only)."""
+    functions a call may name (compile_pair only); name_calls(fn, args): for a call whose arguments are names, not expressions
+    (distance(p1,p2) of compile_compound) -- the syntax nodes of the arguments in, ('op', opcode name, arg) out, or None when `fn`
+    is no such function."""
     main, defs = split_definitions(text)
     prog = Program()
     local_of, in_progress = {}, set()
@@ -298,6 +300,10 @@ def compile_per_dof(text, resolve, what='per-DOF', random_ok=True, fold=False, f
             prog.emit({ast.Add: 'ADD', ast.Sub: 'SUB', ast.Mult: 'MUL', ast.Div: 'DIV', ast.Pow: 'POW'}[type(node.op)])
         elif isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and not node.keywords:
             fn = node.func.id
+            special = name_calls(fn, node.args) if name_calls else None
+            if special is not None:
+                prog.emit(special[1], special[2])
+                return
             if functions and fn in functions:
                 word, arity, index = functions[fn]
                 if len(node.args) != arity:
@@ -369,10 +375,10 @@ def table_words(code):
     return [(names[w & 0xff], w >> 8) for w in code if (w & 0xff) in names]
 
 
-def _checked_program(text, resolve, what, functions=None):
+def _checked_program(text, resolve, what, functions=None, name_calls=None):
     """The folded program of a pair or term energy text, held against the limits of csrc/pair_expr_vm.h."""
     try:
-        prog = compile_per_dof(text, resolve, what=what, random_ok=False, fold=True, functions=functions)
+        prog = compile_per_dof(text, resolve, what=what, random_ok=False, fold=True, functions=functions, name_calls=name_calls)
     except ExpressionError as exc:
         if 'too many auxiliary definitions' in str(exc):
             raise ExpressionError('%s expression: more than %d auxiliary definitions (locals)' % (what, PAIR_MAX_LOCALS))
@@ -412,6 +418,72 @@ def compile_term(text, variables, per_term_names, global_names, what='term'):
         return ('global',) if name in global_names else None
 
     return _checked_program(text, resolve, what)
+
+
+# a compound-bond expression (compile_compound; csrc/compound.hip): particles (or groups) of a bond, geometric variables of a text
+COMPOUND_MAX_SLOTS, COMPOUND_MAX_VARS = 8, 16
+_COMPOUND_CALLS = dict(distance=2, angle=3, dihedral=4)          # function -> particles it takes
+_COMPOUND_REFUSED = ('pointdistance', 'pointangle', 'pointdihedral')
+
+
+def compile_compound(text, n_slots, prefix, per_bond_names, global_names):
+    """Compile the energy text of a CustomCompoundBondForce (prefix 'p') or CustomCentroidBondForce (prefix 'g') for the compound-bond
+    kernel (csrc/compound.hip).  Returns (program, variables): variables[k] = (kind, slots) is what TERM_VAR k reads -- kind 'x', 'y'
+    or 'z' (the raw coordinate <kind><slot + 1>), 'distance', 'angle' or 'dihedral' (a call whose arguments are bare particle names
+    <prefix>1 .. <prefix>N), slots the 0-based positions within the bond -- in the order of first use; identical calls share one
+    variable.  Per-bond parameter k is TERM_P k, a global parameter GLOBAL k; auxiliary definitions become locals.  The limits are
+    those of compile_term plus COMPOUND_MAX_SLOTS and COMPOUND_MAX_VARS, each an error that names it."""
+    per_bond_names, global_names = list(per_bond_names), set(global_names)
+    what = 'compound-bond'
+    unit_ = 'groups' if prefix == 'g' else 'particles'
+    if not 1 <= int(n_slots) <= COMPOUND_MAX_SLOTS:
+        raise InputError('a %s expression takes 1 to %d %s per bond (%d given)' % (what, COMPOUND_MAX_SLOTS, unit_, n_slots))
+    if len(per_bond_names) > TERM_MAX_PARAMS:
+        raise InputError('a %s expression takes at most %d per-bond parameters (%d given)' % (what, TERM_MAX_PARAMS, len(per_bond_names)))
+    if re.search(r'\bperiodicdistance\s*\(', text):
+        raise ExpressionError('periodicdistance(...) is not supported in a %s expression' % what)
+    particles = {'%s%d' % (prefix, k + 1): k for k in range(int(n_slots))}
+    coordinates = {'%s%d' % (axis, k + 1): (axis, (k,)) for axis in 'xyz' for k in range(int(n_slots))}
+    for name in per_bond_names + sorted(global_names):
+        if name in particles or name in coordinates:
+            raise ExpressionError('%s expression: the parameter %s shadows the %s of that name' % (
+                what, name, 'coordinate' if name in coordinates else unit_[:-1]))
+    variables = []
+
+    def variable(entry):
+        if entry not in variables:
+            if len(variables) >= COMPOUND_MAX_VARS:
+                raise ExpressionError('%s expression: more than %d distinct geometric variables' % (what, COMPOUND_MAX_VARS))
+            variables.append(entry)
+        return ('op', 'TERM_VAR', variables.index(entry))
+
+    def resolve(name):
+        if name in per_bond_names:
+            return ('op', 'TERM_P', per_bond_names.index(name))
+        if name in coordinates:
+            return variable(coordinates[name])
+        if name in particles:
+            raise ExpressionError('%s expression: %s names one of the %s; it stands only as an argument of distance, angle or dihedral' % (what, name, unit_))
+        return ('global',) if name in global_names else None
+
+    def name_calls(fn, args):
+        if fn in _COMPOUND_REFUSED:
+            raise ExpressionError('%s(...) is not supported in a %s expression' % (fn, what))
+        if fn not in _COMPOUND_CALLS:
+            return None
+        if len(args) != _COMPOUND_CALLS[fn]:
+            raise ExpressionError('%s takes %d %s (%d given)' % (fn, _COMPOUND_CALLS[fn], unit_, len(args)))
+        slots = []
+        for a in args:
+            if not isinstance(a, ast.Name):
+                raise ExpressionError('%s expression: the arguments of %s are bare names of %s (%s1 .. %s%d), not expressions' % (
+                    what, fn, unit_, prefix, prefix, n_slots))
+            if a.id not in particles:
+                raise ExpressionError('%s expression: %s is none of the %s of a bond (%s1 .. %s%d)' % (what, a.id, unit_, prefix, prefix, n_slots))
+            slots.append(particles[a.id])
+        return variable((fn, tuple(slots)))
+
+    return _checked_program(text, resolve, what, name_calls=name_calls), variables
 
 
 def compile_cv(text, cv_names, deriv_names, global_names):

@@ -825,6 +825,127 @@ class CustomExternalForce(Force, _GlobalParams):
         context._engine.update_force_parameters(self)
 
 
+class _CompoundBonds(Force, _GlobalParams):
+    """What CustomCompoundBondForce and CustomCentroidBondForce share: the energy text, per-bond and global parameters, the bonds
+    (each a list of particles or groups plus parameters), stored tabulated functions and derivative names (both refused at
+    translation), the periodic flag."""
+
+    def __init__(self, number, energy):
+        Force.__init__(self)
+        self._init_globals()
+        self._n = int(number)
+        self._energy = energy
+        self._bnames = []
+        self._bonds = []           # [[slot entries], [parameters]]
+        self._derivs = []
+        self._functions = []
+        self._periodic = False
+
+    def getEnergyFunction(self):
+        return self._energy
+
+    def setEnergyFunction(self, energy):
+        self._energy = energy
+
+    def addPerBondParameter(self, name):
+        self._bnames.append(name)
+        return len(self._bnames) - 1
+
+    def getNumPerBondParameters(self):
+        return len(self._bnames)
+
+    def getPerBondParameterName(self, index):
+        return self._bnames[index]
+
+    def addEnergyParameterDerivative(self, name):
+        self._derivs.append(name)
+
+    def getNumEnergyParameterDerivatives(self):
+        return len(self._derivs)
+
+    def addTabulatedFunction(self, name, function):
+        self._functions.append((str(name), function))
+        return len(self._functions) - 1
+
+    def getNumTabulatedFunctions(self):
+        return len(self._functions)
+
+    def _row(self, members, parameters):
+        members = [int(m) for m in members]
+        if len(members) != self._n:
+            raise OpenMMException('%s: a bond takes %d %s (%d given)' % (self.__class__.__name__, self._n, self._unit, len(members)))
+        return [members, [float(md_value(p)) for p in parameters]]
+
+    def addBond(self, members, parameters=()):
+        self._bonds.append(self._row(members, parameters))
+        return len(self._bonds) - 1
+
+    def getNumBonds(self):
+        return len(self._bonds)
+
+    def getBondParameters(self, index):
+        members, p = self._bonds[index]
+        return [tuple(members), tuple(p)]
+
+    def setBondParameters(self, index, members, parameters=()):
+        self._bonds[index] = self._row(members, parameters)
+
+    def setUsesPeriodicBoundaryConditions(self, periodic):
+        self._periodic = bool(periodic)
+
+    def usesPeriodicBoundaryConditions(self):
+        return self._periodic
+
+    def updateParametersInContext(self, context):
+        """Upload the per-bond parameters (and group weights) again; the members and the number of bonds must not have changed."""
+        context._engine.update_force_parameters(self)
+
+
+class CustomCompoundBondForce(_CompoundBonds):
+    """Bonds over N particles p1 .. pN with any energy text in x1, y1, z1 .. zN (raw coordinates), distance(pa,pb), angle(pa,pb,pc)
+    and dihedral(pa,pb,pc,pd), per-bond and global parameters."""
+    _unit = 'particles'
+
+    def __init__(self, numParticles, energy):
+        _CompoundBonds.__init__(self, numParticles, energy)
+
+    def getNumParticlesPerBond(self):
+        return self._n
+
+
+class CustomCentroidBondForce(_CompoundBonds):
+    """Bonds over N groups g1 .. gN, each the weighted centre of a set of particles; the text is CustomCompoundBondForce's with g
+    names, x1 .. the coordinates of the centre of group 1."""
+    _unit = 'groups'
+
+    def __init__(self, numGroups, energy):
+        _CompoundBonds.__init__(self, numGroups, energy)
+        self._groups = []           # [[particles], [weights]]; no weights: the particles' masses
+
+    def getNumGroupsPerBond(self):
+        return self._n
+
+    def addGroup(self, particles, weights=()):
+        particles, weights = [int(p) for p in particles], [float(md_value(w)) for w in (weights or ())]
+        if weights and len(weights) != len(particles):
+            raise OpenMMException('CustomCentroidBondForce: a group needs one weight per particle, or none (the masses)')
+        self._groups.append([particles, weights])
+        return len(self._groups) - 1
+
+    def getNumGroups(self):
+        return len(self._groups)
+
+    def getGroupParameters(self, index):
+        particles, weights = self._groups[index]
+        return [tuple(particles), tuple(weights)]
+
+    def setGroupParameters(self, index, particles, weights=()):
+        particles, weights = [int(p) for p in particles], [float(md_value(w)) for w in (weights or ())]
+        if weights and len(weights) != len(particles):
+            raise OpenMMException('CustomCentroidBondForce: a group needs one weight per particle, or none (the masses)')
+        self._groups[index] = [particles, weights]
+
+
 class CMMotionRemover(Force):
     """Accepted and ignored (removes centre-of-mass motion in OpenMM; no energy)."""
 
@@ -1342,6 +1463,8 @@ def molecules_of(system):
         elif isinstance(force, (PeriodicTorsionForce, CustomTorsionForce)):
             pairs += [(r[0], r[1]) for r in force._torsions] + [(r[1], r[2]) for r in force._torsions] + \
                      [(r[2], r[3]) for r in force._torsions]
+        elif isinstance(force, CustomCompoundBondForce):       # consecutive particles, as an angle or torsion (a centroid bond joins nothing)
+            pairs += [(a, b) for members, _ in force._bonds for a, b in zip(members[:-1], members[1:])]
     for i, j in pairs:
         a, b = find(int(i)), find(int(j))
         if a != b:

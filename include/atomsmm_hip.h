@@ -311,8 +311,8 @@ int amm_term_expr_release(amm_ctx *ctx, int32_t force_id);
 #define AMM_CV_MAX_CVS 16
 #define AMM_CV_MAX_DERIVS 16
 /* CustomCVForce(energy) + addCollectiveVariable x n_cv + addEnergyParameterDerivative x n_deriv.  inner_ids: n_cv ids of bond-list
- * sets (amm_bonded_create .. amm_bonded_finalize) or term-expression forces (amm_term_expr_create) that the caller created, keeps in
- * no group and releases itself; any other type is refused.  code / consts / globals: the program of atomsmm_amd.expr.compile_cv --
+ * sets (amm_bonded_create .. amm_bonded_finalize), term-expression forces (amm_term_expr_create) or compound-bond forces
+ * (amm_compound_create) that the caller created, keeps in no group and releases itself; any other type is refused.  code / consts / globals: the program of atomsmm_amd.expr.compile_cv --
  * the words of amm_term_expr_create with variable k (opcode 53) = collective variable k for k < n_cv and derivative parameter
  * k - n_cv behind them, no per-term parameters; the same limits, checked here with a walk of the stack.  Scratch: 24 n_cv n bytes. */
 int amm_cv_create(amm_ctx *ctx, const int32_t *inner_ids, int32_t n_cv, int32_t n_deriv, const int32_t *code, int32_t ncode,
@@ -331,6 +331,48 @@ int amm_cv_values(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *h
 int amm_cv_energy_derivative(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *d_out);
 /* Free such a force and its scratch; the id is retired and leaves every group definition.  The inner ids stay the caller's. */
 int amm_cv_release(amm_ctx *ctx, int32_t force_id);
+
+/* CustomCompoundBondForce / CustomCentroidBondForce(any energy text) (force type AMM_FORCE_COMPOUND): a bond is n_slots particles --
+ * or, with groups, n_slots weighted centres of groups of atoms -- and its text reads up to AMM_COMPOUND_MAX_VARS geometric
+ * variables over them.  An ordinary member of a group, evaluated through amm_force_eval, and a legal inner force of amm_cv_create;
+ * the amm_pair_*, amm_bonded_*, amm_term_expr_* and amm_pme_* calls refuse its id naming AMM_FORCE_COMPOUND.  One lane per (bond,
+ * variable) computes the variable and its gradient, then dE/dvariable by a forward-mode pass seeded in it; forces are parked per
+ * (bond, variable, role) and every atom adds its records in that order: no atomics, the same bits run to run, and the forces of an
+ * evaluation with and without energy are the same numbers. */
+typedef enum {
+    AMM_CVAR_X = 0,          /* slots[1]: raw x of the particle (never wrapped); AMM_CVAR_Y, AMM_CVAR_Z likewise */
+    AMM_CVAR_Y = 1,
+    AMM_CVAR_Z = 2,
+    AMM_CVAR_DISTANCE = 3,   /* slots[2]: |x_a - x_b|                                                              */
+    AMM_CVAR_ANGLE = 4,      /* slots[3]: the angle at the second slot, in [0, pi] (AMM_TERM_ANGLE's)              */
+    AMM_CVAR_DIHEDRAL = 5    /* slots[4]: the dihedral in (-pi, pi] (AMM_TERM_TORSION's)                           */
+} amm_compound_var;
+#define AMM_COMPOUND_MAX_SLOTS 8
+#define AMM_COMPOUND_MAX_VARS 16
+/* code / consts / globals: the program of atomsmm_amd.expr.compile_compound -- the words of amm_term_expr_create with variable k
+ * (opcode 53) = entry k of the variable table and parameter k (54) the bond's parameter k; the same limits, checked here with a walk
+ * of the stack.  var_kinds: n_vars amm_compound_var; var_slots: n_vars x 4 positions within the bond, read up to the kind's arity;
+ * a position outside [0, n_slots) is refused.  h_idx: n_bonds x n_slots atom indices (group indices with groups); an index outside
+ * [0, n) (outside [0, n_groups)) is refused.  h_params: n_params x n_bonds doubles, PARAMETER-major, n_params <=
+ * AMM_TERM_MAX_PARAMS; NULL when n_params = 0.  periodic: displacements inside distance / angle / dihedral take the minimum image
+ * (needs a context with a box); raw coordinates never do.  n_groups = 0: the slots are particles and the three group arrays are
+ * NULL.  n_groups > 0: group g has the members group_atoms[group_ptr[g] .. group_ptr[g + 1]) with the weights group_weights[..];
+ * its centre is sum w_i x_i / sum w_i over the positions as given (a group is taken to be whole), and atom i of the group receives
+ * w_i / W_g times the force on the centre.  An empty group, or weights that sum to zero, is refused. */
+int amm_compound_create(amm_ctx *ctx, int32_t n_slots, const int32_t *code, int32_t ncode, const double *consts, int32_t nconst,
+                        const double *globals, int32_t nglobal, const int32_t *var_kinds, const int32_t *var_slots, int32_t n_vars,
+                        const int32_t *h_idx, const double *h_params, int32_t n_bonds, int32_t n_params, int32_t periodic,
+                        const int32_t *group_ptr, const int32_t *group_atoms, const double *group_weights, int32_t n_groups,
+                        int32_t *force_id);
+/* Context.setParameter(name, value) for a global parameter of such a force: all of the program's globals, in its order. */
+int amm_compound_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal);
+/* setBondParameters + updateParametersInContext: all per-bond values again, laid out as at creation (same n_bonds, n_params; the
+ * particles or groups of a bond do not change). */
+int amm_compound_set_params(amm_ctx *ctx, int32_t force_id, const double *h_params, int32_t n_bonds, int32_t n_params);
+/* setGroupParameters + updateParametersInContext: all weights again, in the order of group_atoms (the members do not change). */
+int amm_compound_set_weights(amm_ctx *ctx, int32_t force_id, const double *weights, int32_t n_members);
+/* Free such a force; the id is retired and leaves every group definition. */
+int amm_compound_release(amm_ctx *ctx, int32_t force_id);
 
 /* Reciprocal space of a NonbondedForce with nonbondedMethod PME / Ewald, as RESPASystem and FarNonbondedForce
  * keep it in group 2 with the source force's Ewald tolerance / PME parameters (systems.py:74-75,
