@@ -1320,12 +1320,13 @@ int amm_constraints_create(amm_ctx *ctx, const int32_t *h_pairs, const double *h
         amm_set_error("amm_constraints_create: bad arguments");
         return 1;
     }
-    if (ctx->constraints) {
-        amm_constraints_free(ctx->constraints);
-        ctx->constraints = nullptr;
-    }
     AMM_HIP(hipSetDevice(ctx->device));
-    return amm_constraints_create_impl(ctx, h_pairs, h_dist, n_constraints, tolerance, &ctx->constraints);
+    // the new set first: a refused call leaves the previous set in force
+    ConstraintSet *fresh = nullptr;
+    if (amm_constraints_create_impl(ctx, h_pairs, h_dist, n_constraints, tolerance, &fresh)) return 1;
+    if (ctx->constraints) amm_constraints_free(ctx->constraints);
+    ctx->constraints = fresh;
+    return 0;
 }
 
 int amm_constraints_set_tolerance(amm_ctx *ctx, double tolerance) {

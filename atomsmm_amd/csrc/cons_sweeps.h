@@ -97,7 +97,8 @@ __device__ __forceinline__ bool amm_shake_sweeps(const S &s, double (&p)[NA][3],
                 pp += dp[j] * dp[j];
                 rp += dr[j] * dp[j];
             }
-            if (pp < lower * d2 || pp > upper * d2) {
+            // (negated, so that a NaN also counts as "not there yet": a cluster that is not finite runs out of sweeps and fails)
+            if (!(pp >= lower * d2 && pp <= upper * d2)) {
                 done = false;
                 const double g = (d2 - pp) / (2.0 * (im[ij.x] + im[ij.y]) * rp);
 #pragma unroll
@@ -128,8 +129,8 @@ __device__ __forceinline__ bool amm_rattle_sweeps(const S &s, const double (&p)[
                 dot += dp[j] * (w[ij.x][j] - w[ij.y][j]);
                 pp += dp[j] * dp[j];
             }
-            // relative rate of change of the bond length, d ln|r| / dt, against the tolerance (1/ps)
-            if (fabs(dot) > tol * pp) {
+            // relative rate of change of the bond length, d ln|r| / dt, against the tolerance (1/ps); negated: NaN also triggers
+            if (!(fabs(dot) <= tol * pp)) {
                 done = false;
                 const double g = -dot / ((im[ij.x] + im[ij.y]) * pp);
 #pragma unroll

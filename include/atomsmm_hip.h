@@ -186,7 +186,9 @@ int amm_exchange_pending(amm_ctx *ctx, int32_t *nf);
  * neighbours in memory are merged into one message) */
 int amm_comm_stats(amm_ctx *ctx, int64_t out[2]);
 int amm_synchronize(amm_ctx *ctx);
-/* Raises pending device-side errors (neighbour-list overflow, NaN guard): returns non-zero + message. Synchronises. */
+/* Raises pending device-side errors (neighbour-list overflow, NaN guard): returns non-zero + message. Synchronises.
+ * A constraint cluster that the solvers left unconverged is one of them, and a cluster whose positions or velocities are not finite
+ * (NaN or infinite, on entry or by a blow-up of the sweep) counts as unconverged; the flag is cleared by the call that reports it. */
 int amm_check(amm_ctx *ctx);
 
 /* CustomNonbondedForce(energy) + addParticle + addExclusion  (forces.py:225, 299-312; systems.py:97-111).
@@ -418,7 +420,11 @@ int amm_expr_eval_scalar(amm_ctx *ctx, const int32_t *code, int32_t n_code, cons
 
 /* System.addConstraint(i, j, distance) x n (forcefield.createSystem(constraints=HBonds, rigidWater=True) in the
  * reference's tests, tests/test_propagators.py:11-18).  Clusters of coupled constraints (<= 8 atoms, <= 16 constraints)
- * are solved by one thread each; tolerance as CustomIntegrator.getConstraintTolerance() (<= 0: 1e-5). */
+ * are solved by one thread each; tolerance as CustomIntegrator.getConstraintTolerance() (<= 0: 1e-5).  The new set replaces the
+ * context's previous one; a refused call (a bad index or distance, a cluster beyond the limits) leaves the previous set in force.
+ * The solvers are plain Gauss-Seidel sweeps (SHAKE / RATTLE) with a cap of 500 sweeps: trees converge in tens of sweeps, rigid
+ * clusters with cycles slowly (a six-ring with its 1-3 distances needed up to 278 sweeps at a tolerance of 1e-13 and 110 at
+ * 1e-5, a methyl group with its H-H distances 182 and 76, a rigid water 65 and 29: tests/test_constraint_cases_host.py). */
 int amm_constraints_create(amm_ctx *ctx, const int32_t *h_pairs, const double *h_dist, int32_t n_constraints, double tolerance);
 /* A new tolerance for the solvers of the existing constraint set (setConstraintTolerance of a bound integrator); <= 0: 1e-5. */
 int amm_constraints_set_tolerance(amm_ctx *ctx, double tolerance);

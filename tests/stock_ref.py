@@ -85,7 +85,7 @@ def _shake_batch(P, R, IM, local, D, tol):
             dp, dr = P[:, i] - P[:, j], R[:, i] - R[:, j]
             pp, rp = _dot3(dp, dp), _dot3(dr, dp)
             d2 = D[:, q] * D[:, q]
-            hit = active & ((pp < lower * d2) | (pp > upper * d2))
+            hit = active & ~((pp >= lower * d2) & (pp <= upper * d2))       # (negated as in the kernel: NaN also triggers)
             if hit.any():
                 g = (d2[hit] - pp[hit]) / (2.0 * (IM[hit, i] + IM[hit, j]) * rp[hit])
                 P[hit, i] += (g * IM[hit, i])[:, None] * dr[hit]
@@ -107,7 +107,7 @@ def _rattle_batch(P, W, IM, local, tol):
         for i, j in local:
             dp = P[:, i] - P[:, j]
             dot, pp = _dot3(dp, W[:, i] - W[:, j]), _dot3(dp, dp)
-            hit = active & (np.abs(dot) > tol * pp)
+            hit = active & ~(np.abs(dot) <= tol * pp)
             if hit.any():
                 g = -dot[hit] / ((IM[hit, i] + IM[hit, j]) * pp[hit])
                 W[hit, i] += (g * IM[hit, i])[:, None] * dp[hit]
