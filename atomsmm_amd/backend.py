@@ -57,6 +57,7 @@ EXPORTS = [
     'amm_cv_create', 'amm_cv_set_globals', 'amm_cv_set_variables', 'amm_cv_values', 'amm_cv_energy_derivative', 'amm_cv_release',
     'amm_compound_create', 'amm_compound_set_globals', 'amm_compound_set_params', 'amm_compound_set_weights', 'amm_compound_release',
     'amm_run_rule_stats',
+    'amm_gb_create', 'amm_gb_set_params', 'amm_gb_born_radii', 'amm_gb_release',
 ]
 
 
@@ -189,6 +190,10 @@ def lib():
         L.amm_compound_set_params.argtypes = [vp, C.c_int32, dp, C.c_int32, C.c_int32]
         L.amm_compound_set_weights.argtypes = [vp, C.c_int32, dp, C.c_int32]
         L.amm_compound_release.argtypes = [vp, C.c_int32]
+        L.amm_gb_create.argtypes = [vp, dp, dp, dp, C.c_double, C.c_double, C.c_double, C.c_double, ip]
+        L.amm_gb_set_params.argtypes = [vp, C.c_int32, dp, dp, dp, C.c_double, C.c_double, C.c_double, C.c_double]
+        L.amm_gb_born_radii.argtypes = [vp, C.c_int32, vp, dp]
+        L.amm_gb_release.argtypes = [vp, C.c_int32]
         L.amm_cv_create.argtypes = [vp, ip, C.c_int32, C.c_int32, ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip]
         L.amm_cv_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
         L.amm_cv_set_variables.argtypes = [vp, C.c_int32, dp, C.c_int32]
@@ -536,6 +541,31 @@ class HipContext:
     def compound_release(self, fid):
         """Free a compound-bond force (its id is retired)."""
         _chk(lib().amm_compound_release(self.h, fid))
+
+    def gb_create(self, q, radius, scale, eps_in=1.0, eps_out=78.3, sa_energy=2.25936, rc=0.0):
+        """A GBSAOBCForce in free space (csrc/gb.hip): charge, radius (nm) and scale of every atom, the solute and solvent dielectric,
+        the surface-area energy (kJ/mol/nm^2) and the cutoff (rc <= 0: NoCutoff)."""
+        q_, qp = _hd(q); r_, rp = _hd(radius); s_, sp = _hd(scale)
+        assert len(q_) == len(r_) == len(s_) == self.n
+        fid = C.c_int32(-1)
+        _chk(lib().amm_gb_create(self.h, qp, rp, sp, float(eps_in), float(eps_out), float(sa_energy), float(rc), C.byref(fid)))
+        return fid.value
+
+    def gb_set_params(self, fid, q, radius, scale, eps_in=1.0, eps_out=78.3, sa_energy=2.25936, rc=0.0):
+        """Everything again (updateParametersInContext), checked as at creation."""
+        q_, qp = _hd(q); r_, rp = _hd(radius); s_, sp = _hd(scale)
+        assert len(q_) == len(r_) == len(s_) == self.n
+        _chk(lib().amm_gb_set_params(self.h, fid, qp, rp, sp, float(eps_in), float(eps_out), float(sa_energy), float(rc)))
+
+    def gb_born_radii(self, fid, pos):
+        """The Born radii at `pos` as a numpy array (runs the first pass; waits for the stream)."""
+        out = np.zeros(self.n, dtype=np.float64)
+        _chk(lib().amm_gb_born_radii(self.h, fid, _ptr(pos), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def gb_release(self, fid):
+        """Free a generalized-Born force (its id is retired)."""
+        _chk(lib().amm_gb_release(self.h, fid))
 
     def cv_create(self, inner_ids, n_deriv, code, consts, globals_):
         """A CustomCVForce with any energy text (csrc/cv.hip): the ids of the inner forces in the order of the collective variables

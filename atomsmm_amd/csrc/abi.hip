@@ -32,8 +32,14 @@ static bool is_compound(amm_ctx *ctx, int id, const char *wanted) {
     amm_set_error(std::string("not ") + wanted + ": force " + std::to_string(id) + " is a compound-bond force (AMM_FORCE_COMPOUND: amm_compound_*)");
     return true;
 }
+// ... and an id of a generalized-Born force
+static bool is_gb(amm_ctx *ctx, int id, const char *wanted) {
+    if (!(ctx && id >= 0 && id < (int)ctx->forces.size() && ctx->forces[id].type == AMM_FORCE_GB)) return false;
+    amm_set_error(std::string("not ") + wanted + ": force " + std::to_string(id) + " is a generalized-Born force (AMM_FORCE_GB: amm_gb_*)");
+    return true;
+}
 static PairForce *get_pair(amm_ctx *ctx, int id) {
-    if (is_cv(ctx, id, "a pair force") || is_compound(ctx, id, "a pair force")) return nullptr;
+    if (is_cv(ctx, id, "a pair force") || is_compound(ctx, id, "a pair force") || is_gb(ctx, id, "a pair force")) return nullptr;
     if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_PAIR) {
         amm_set_error("invalid pair force id");
         return nullptr;
@@ -45,7 +51,7 @@ static BondedSet *get_bonded(amm_ctx *ctx, int id) {
         amm_set_error("not a bond-list set: force " + std::to_string(id) + " is a term-expression force (amm_term_expr_*)");
         return nullptr;
     }
-    if (is_cv(ctx, id, "a bond-list set") || is_compound(ctx, id, "a bond-list set")) return nullptr;
+    if (is_cv(ctx, id, "a bond-list set") || is_compound(ctx, id, "a bond-list set") || is_gb(ctx, id, "a bond-list set")) return nullptr;
     if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_BONDED) {
         amm_set_error("invalid bonded force id");
         return nullptr;
@@ -64,6 +70,7 @@ int amm_force_eval_dispatch(amm_ctx *ctx, int force_id, const double *d_pos, dou
     if (f.type == AMM_FORCE_TERM_EXPR) return amm_term_expr_eval_impl(ctx, f.term, d_pos, d_force, accumulate, d_energy);
     if (f.type == AMM_FORCE_CV) return amm_cv_eval_impl(ctx, f.cv, d_pos, d_force, accumulate, d_energy);
     if (f.type == AMM_FORCE_COMPOUND) return amm_compound_eval_impl(ctx, f.compound, d_pos, d_force, accumulate, d_energy);
+    if (f.type == AMM_FORCE_GB) return amm_gb_eval_impl(ctx, f.gb, d_pos, d_force, accumulate, d_energy);
     return amm_bonded_eval_impl(ctx, f.bonded, d_pos, d_force, accumulate, d_energy);
 }
 
@@ -153,6 +160,7 @@ int amm_destroy(amm_ctx *ctx) {
         if (f.term) amm_term_expr_free(f.term);
         if (f.cv) amm_cv_free(f.cv);
         if (f.compound) amm_compound_free(f.compound);
+        if (f.gb) amm_gb_free(f.gb);
     }
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
     if (ctx->d_expr_part) (void)hipFree(ctx->d_expr_part);
@@ -180,6 +188,10 @@ int amm_set_slice(amm_ctx *ctx, int32_t rank, int32_t world) {
     for (auto &f : ctx->forces) {
         if (f.pair && f.pair->free_space && world > 1) {
             amm_set_error("amm_set_slice: a free-space pair force runs on a single rank");
+            return 1;
+        }
+        if (f.gb && world > 1) {
+            amm_set_error("amm_set_slice: a generalized-Born force (AMM_FORCE_GB) runs on a single rank");
             return 1;
         }
         if (f.pair && f.pair->built) {
@@ -980,7 +992,8 @@ int amm_bonded_release(amm_ctx *ctx, int32_t force_id) {
 }
 
 static TermExprForce *get_term_expr(amm_ctx *ctx, int id, const char *who) {
-    if (is_cv(ctx, id, "a term-expression force") || is_compound(ctx, id, "a term-expression force")) return nullptr;
+    if (is_cv(ctx, id, "a term-expression force") || is_compound(ctx, id, "a term-expression force") || is_gb(ctx, id, "a term-expression force"))
+        return nullptr;
     if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_TERM_EXPR) {
         amm_set_error(std::string(who) + ": not a term-expression force id");
         return nullptr;
@@ -1200,6 +1213,63 @@ int amm_compound_release(amm_ctx *ctx, int32_t force_id) {
     return 0;
 }
 
+static GbForce *get_gb(amm_ctx *ctx, int id, const char *who) {
+    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_GB) {
+        amm_set_error(std::string(who) + ": not the id of a generalized-Born force (AMM_FORCE_GB)");
+        return nullptr;
+    }
+    return ctx->forces[id].gb;
+}
+
+// GBSAOBCForce in free space (csrc/gb.hip): addParticle(charge, radius, scale) x n, the two dielectrics, the surface-area energy and
+// the cutoff (rc <= 0: NoCutoff)
+int amm_gb_create(amm_ctx *ctx, const double *h_q, const double *h_radius, const double *h_scale, double eps_in, double eps_out,
+                  double sa_energy, double rc, int32_t *force_id) {
+    if (!ctx || !h_q || !h_radius || !h_scale || !force_id) {
+        amm_set_error("amm_gb_create: null argument");
+        return 1;
+    }
+    AMM_HIP(hipSetDevice(ctx->device));
+    GbForce *gb = nullptr;
+    if (amm_gb_create_impl(ctx, h_q, h_radius, h_scale, eps_in, eps_out, sa_energy, rc, &gb)) return 1;
+    ForceObj fo;
+    fo.type = AMM_FORCE_GB;
+    fo.gb = gb;
+    ctx->forces.push_back(fo);
+    *force_id = (int32_t)ctx->forces.size() - 1;
+    return 0;
+}
+
+int amm_gb_set_params(amm_ctx *ctx, int32_t force_id, const double *h_q, const double *h_radius, const double *h_scale, double eps_in,
+                      double eps_out, double sa_energy, double rc) {
+    GbForce *gb = get_gb(ctx, force_id, "amm_gb_set_params");
+    return gb ? amm_gb_set_params_impl(ctx, gb, h_q, h_radius, h_scale, eps_in, eps_out, sa_energy, rc) : 1;
+}
+
+int amm_gb_born_radii(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *h_out) {
+    GbForce *gb = get_gb(ctx, force_id, "amm_gb_born_radii");
+    if (!gb) return 1;
+    if (!d_pos || !h_out) {
+        amm_set_error("amm_gb_born_radii: null argument");
+        return 1;
+    }
+    return amm_gb_born_radii_impl(ctx, gb, d_pos, h_out);
+}
+
+int amm_gb_release(amm_ctx *ctx, int32_t force_id) {
+    GbForce *gb = get_gb(ctx, force_id, "amm_gb_release");
+    if (!gb) return 1;
+    AMM_HIP(hipStreamSynchronize(ctx->stream));            // nothing in flight may still read it
+    for (int g = 0; g < AMM_MAX_GROUPS; ++g) {
+        std::vector<int> &m = ctx->groups[g].forces;
+        m.erase(std::remove(m.begin(), m.end(), (int)force_id), m.end());
+    }
+    amm_gb_free(gb);
+    ctx->forces[force_id].gb = nullptr;
+    ctx->forces[force_id].type = AMM_FORCE_RELEASED;
+    return 0;
+}
+
 int amm_pme_create(amm_ctx *ctx, double alpha, int32_t nx, int32_t ny, int32_t nz, double Kc, const double *h_q,
                    int32_t *force_id) {
     if (!ctx || !h_q || !force_id) {
@@ -1223,7 +1293,7 @@ int amm_pme_create(amm_ctx *ctx, double alpha, int32_t nx, int32_t ny, int32_t n
 }
 
 static PmeForce *get_pme(amm_ctx *ctx, int id) {
-    if (is_cv(ctx, id, "a PME force") || is_compound(ctx, id, "a PME force")) return nullptr;
+    if (is_cv(ctx, id, "a PME force") || is_compound(ctx, id, "a PME force") || is_gb(ctx, id, "a PME force")) return nullptr;
     if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_PME) {
         amm_set_error("not a PME force id");
         return nullptr;
@@ -1775,6 +1845,13 @@ int amm_set_option(amm_ctx *ctx, const char *name, double value) {
     else if (k == "spec_assign") ctx->opt_spec_assign = v;
     else if (k == "chargeless") ctx->opt_chargeless = v;
     else if (k == "state_exchange") ctx->opt_state_exchange = v;
+    else if (k == "gb_lanes_per_row") {
+        if (v < 0 || v > 64 || (v & (v - 1))) {
+            amm_set_error("amm_set_option: gb_lanes_per_row is 0 (automatic) or a power of two up to 64");
+            return 1;
+        }
+        ctx->opt_gb_lpr = v;
+    }
     else {
         amm_set_error("amm_set_option: unknown option '" + k + "'");
         return 1;

@@ -246,8 +246,9 @@ struct TermExprForce; // term_expr_vm.h: bond / angle / torsion / external terms
 
 struct CvForce;       // cv.hip: a CustomCVForce -- K inner forces and the compiled outer text over their energies
 struct CompoundForce; // compound.hip: a CustomCompoundBondForce / CustomCentroidBondForce -- bonds over several particles or centres
+struct GbForce;       // gb.hip: a GBSAOBCForce -- generalized-Born (OBC2) implicit solvent with a surface-area term, free space only
 enum : int { AMM_FORCE_RELEASED = 0, AMM_FORCE_PAIR = 1, AMM_FORCE_BONDED = 2, AMM_FORCE_PME = 3, AMM_FORCE_TERM_EXPR = 4, AMM_FORCE_CV = 5,
-             AMM_FORCE_COMPOUND = 6 };   // ForceObj::type
+             AMM_FORCE_COMPOUND = 6, AMM_FORCE_GB = 7 };   // ForceObj::type
 struct ForceObj {
     int type = AMM_FORCE_RELEASED;
     PairForce *pair = nullptr;
@@ -256,6 +257,7 @@ struct ForceObj {
     TermExprForce *term = nullptr;
     CvForce *cv = nullptr;
     CompoundForce *compound = nullptr;
+    GbForce *gb = nullptr;
 };
 
 struct ExprDef {
@@ -402,6 +404,7 @@ struct amm_ctx {
     int opt_row_phases = 1;             // molecule rows: the remainder of the rows after whole rounds of tasks goes out in smaller tasks (cpair_plan)
     int opt_fuse_rows = 1;              // molecule rows: host + guest force of a shared list in ONE launch when a fused kernel exists
     int opt_terms_from = 8192, opt_no_term_lanes = 0;
+    int opt_gb_lpr = 0;                 // lanes per row of the generalized-Born passes (gb.hip): 0 = amm_free_lanes_per_row(n); 1, 2, 4 .. 64
     ListWatch watched[AMM_MAX_WATCH];
     int n_watched = 0;
     int device = 0;
@@ -549,6 +552,14 @@ int amm_compound_set_globals_impl(amm_ctx *ctx, CompoundForce *cf, const double 
 int amm_compound_set_params_impl(amm_ctx *ctx, CompoundForce *cf, const double *h_params, int n_bonds, int n_params);
 int amm_compound_set_weights_impl(amm_ctx *ctx, CompoundForce *cf, const double *weights, int n_members);
 void amm_compound_free(CompoundForce *cf);
+// gb.hip: a force of type AMM_FORCE_GB (rc <= 0: no cutoff)
+int amm_gb_create_impl(amm_ctx *ctx, const double *h_q, const double *h_radius, const double *h_scale, double eps_in, double eps_out,
+                       double sa_energy, double rc, GbForce **out);
+int amm_gb_set_params_impl(amm_ctx *ctx, GbForce *gb, const double *h_q, const double *h_radius, const double *h_scale, double eps_in,
+                           double eps_out, double sa_energy, double rc);
+int amm_gb_eval_impl(amm_ctx *ctx, GbForce *gb, const double *d_pos, double *d_force, int accumulate, double *d_energy);
+int amm_gb_born_radii_impl(amm_ctx *ctx, GbForce *gb, const double *d_pos, double *h_out);
+void amm_gb_free(GbForce *gb);
 // implemented in pair.hip / cells.hip / bonded.hip / integrate.hip
 int amm_pair_build_consts(const amm_pair_desc &d, PairConsts &pc);
 int amm_pair_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double *d_force, int accumulate,

@@ -248,6 +248,7 @@ class _Entry:
                                     # the id is also in term_ids, `program` is that of expr.compile_cv
         self.compound = None        # a CustomCompoundBondForce / CustomCentroidBondForce (csrc/compound.hip): dict(id, variables, centroid);
                                     # the id is also in term_ids, term_expr is set, `program` is that of expr.compile_compound
+        self.gb = None              # a GBSAOBCForce (csrc/gb.hip): its backend id, which is also in term_ids
 
 
 def slice_bounds(n_items, rank, world):
@@ -326,6 +327,7 @@ class Engine:
         # measure its host-side cost on a single GPU
         self._coll = self.world > 1 or (os.environ.get('AMM_FORCE_COLLECTIVES') == '1' and dist.is_available()
                                         and dist.is_initialized())
+        self._check_gb(system, integrator)
         if self.free_space and self.world > 1:
             raise InputError('a System in free space (NoCutoff / CutoffNonPeriodic) runs on a single rank: its pair forces walk all pairs '
                              'and are not sliced')
@@ -422,13 +424,22 @@ class Engine:
         force uses periodic boundary conditions and the System holds a force (box vectors may be absent; present ones are ignored).
         False: all nonbonded forces periodic, as ever.  A mixture is an InputError."""
         def pair_forces(force):
-            if isinstance(force, (mm.NonbondedForce, mm.CustomNonbondedForce)):
+            if isinstance(force, (mm.NonbondedForce, mm.CustomNonbondedForce, mm.GBSAOBCForce)):
                 return [force]
             if isinstance(force, mm.CustomCVForce):
                 return [f for k in range(force.getNumCollectiveVariables()) for f in pair_forces(force.getCollectiveVariable(k))]
             return []
         forces = list(system.getForces())
         pairs = [f for force in forces for f in pair_forces(force)]
+        # a generalized-Born force runs in free space only (csrc/gb.hip): refused by name, not as a mixture
+        if any(isinstance(f, mm.GBSAOBCForce) for f in pairs):
+            for f in pairs:
+                if isinstance(f, mm.GBSAOBCForce) and f.usesPeriodicBoundaryConditions():
+                    raise InputError('GBSAOBCForce: CutoffPeriodic is not supported: generalized-Born solvent runs in free space only '
+                                     '(NoCutoff / CutoffNonPeriodic)')
+                if f.usesPeriodicBoundaryConditions():
+                    raise InputError('a GBSAOBCForce in a System with a box-periodic %s: generalized-Born solvent runs in free space '
+                                     'only (every nonbonded method NoCutoff or CutoffNonPeriodic)' % f.__class__.__name__)
         free = [f for f in pairs if not f.usesPeriodicBoundaryConditions()]
         if free and len(free) != len(pairs):
             raise InputError('the System mixes periodic and non-periodic nonbonded methods: every NonbondedForce / CustomNonbondedForce '
@@ -440,6 +451,58 @@ class Engine:
             raise InputError('the System mixes non-periodic nonbonded methods (or no box) with a %s that uses periodic boundary '
                              'conditions' % periodic[0].__class__.__name__)
         return True
+
+    GB_MAX_ATOMS = 32768      # csrc/amm_ctx.h: AMM_FREE_MAX_ATOMS
+
+    def _check_gb(self, system, integrator):
+        """What a GBSAOBCForce cannot run with, refused by name when the Context is created (CutoffPeriodic and box-periodic
+        companions: _free_space_mode)."""
+        gbs = [f for f in system.getForces() if isinstance(f, mm.GBSAOBCForce)]
+        if not gbs:
+            return
+        n = system.getNumParticles()
+        for gb in gbs:
+            if gb.getNumParticles() != n:
+                raise mm.OpenMMException('GBSAOBCForce must have exactly as many particles as the System it belongs to (%d, the System '
+                                         'has %d)' % (gb.getNumParticles(), n))
+        if self.world > 1:
+            raise InputError('a GBSAOBCForce runs on a single rank: its passes walk all pairs and are not sliced')
+        if n > self.GB_MAX_ATOMS:
+            raise InputError('a GBSAOBCForce walks all n^2 pairs three times per evaluation and takes at most %d atoms (the System has %d)'
+                             % (self.GB_MAX_ATOMS, n))
+        for _kind, _target, expr in getattr(integrator, '_steps', []):
+            if expr and 'deriv(' in expr:
+                raise NotImplementedError('deriv(energy, ...) through a GBSAOBCForce is not supported: the generalized-Born kernels have '
+                                          'no parameter-derivative evaluation (step: %s)' % expr)
+
+    def _translate_gb(self, force, entry):
+        """A GBSAOBCForce: one backend force (csrc/gb.hip) carried in entry.term_ids, so every loop over an entry's forces reaches it
+        and the scheduler's fusion rules decline its group, as they do for a term-expression force."""
+        def arrays():
+            if force.getNumParticles() != self.n:
+                raise mm.OpenMMException('GBSAOBCForce must have exactly as many particles as the System it belongs to')
+            par = np.array(force._particles, dtype=np.float64).reshape(-1, 3)
+            if force.usesPeriodicBoundaryConditions():
+                raise InputError('GBSAOBCForce: CutoffPeriodic is not supported: generalized-Born solvent runs in free space only')
+            rc = force._cutoff if force.getNonbondedMethod() == force.CutoffNonPeriodic else 0.0
+            return (par[:, 0], par[:, 1], par[:, 2]), dict(eps_in=force.getSoluteDielectric(), eps_out=force.getSolventDielectric(),
+                                                            sa_energy=force._sa_energy, rc=rc)
+        try:
+            per_atom, scalars = arrays()
+            gid = self.ctx.gb_create(*per_atom, **scalars)
+        except B.HipError as exc:
+            raise InputError('GBSAOBCForce: %s' % exc)
+        entry.term_ids.append(gid)
+        entry.gb = gid
+
+        def reload():          # updateParametersInContext: everything is read again
+            per_atom, scalars = arrays()
+            try:
+                self.ctx.gb_set_params(gid, *per_atom, **scalars)
+            except B.HipError as exc:
+                raise InputError('GBSAOBCForce: %s' % exc)
+            return 'values'
+        entry.reload = reload
 
     # ------------------------------------------------------------------------------- constant pressure
     def _init_barostat(self):
@@ -604,6 +667,8 @@ class Engine:
             self._translate_custom_nonbonded(force, entry)
         elif isinstance(force, mm.CustomCVForce):
             self._translate_cv(force, entry)
+        elif isinstance(force, mm.GBSAOBCForce):
+            self._translate_gb(force, entry)
         elif self._translate_bond_list_force(force, entry):
             pass
         else:
@@ -3008,6 +3073,9 @@ class Engine:
         * parameter offsets of a NonbondedForce (SolvationSystem's `lambda_coul`, systems.py:289-308): the energy is a
           quadratic form of the charges, so the central difference over a whole unit of lambda is exact; offsets that act
           on sigma / epsilon (`use_softcore=False`, systems.py:309-312) take a small central step instead (O(h^2))."""
+        if any(getattr(entry, 'gb', None) is not None for entry in self.entries):
+            raise NotImplementedError('deriv(energy, %s) through a GBSAOBCForce is not supported: the generalized-Born kernels have no '
+                                      'parameter-derivative evaluation' % name)
         self._refuse_in_free_space('deriv(energy, %s)' % name)
         if name not in self.parameters:
             raise mm.OpenMMException('deriv(energy, %s): no such Context parameter' % name)

@@ -271,6 +271,72 @@ class NonbondedForce(Force, _GlobalParams):
         return list(self._exception_offsets[index])
 
 
+class GBSAOBCForce(Force):
+    """Generalized-Born implicit solvent (OBC2) with a surface-area term, for free-space systems: NoCutoff and CutoffNonPeriodic
+    (csrc/gb.hip).  Every particle of the System takes part; exclusions and exceptions of other forces play no role."""
+    NoCutoff, CutoffNonPeriodic, CutoffPeriodic = range(3)
+
+    def __init__(self):
+        Force.__init__(self)
+        self._particles = []       # [q, radius, scale]
+        self._method = self.NoCutoff
+        self._cutoff = 1.0
+        self._solvent_dielectric = 78.3
+        self._solute_dielectric = 1.0
+        self._sa_energy = 2.25936  # kJ/mol/nm^2
+
+    def usesPeriodicBoundaryConditions(self):
+        return self._method == self.CutoffPeriodic
+
+    def getNumParticles(self):
+        return len(self._particles)
+
+    def addParticle(self, charge, radius, scalingFactor):
+        self._particles.append([float(md_value(charge)), float(md_value(radius)), float(scalingFactor)])
+        return len(self._particles) - 1
+
+    def getParticleParameters(self, index):
+        q, r, s = self._particles[index]
+        return [Quantity(q, _unit.elementary_charge), Quantity(r, nm), s]
+
+    def setParticleParameters(self, index, charge, radius, scalingFactor):
+        self._particles[index] = [float(md_value(charge)), float(md_value(radius)), float(scalingFactor)]
+
+    def updateParametersInContext(self, context):
+        """Upload the particle parameters, the dielectrics and the surface-area energy again."""
+        context._engine.update_force_parameters(self)
+
+    def getSolventDielectric(self):
+        return self._solvent_dielectric
+
+    def setSolventDielectric(self, dielectric):
+        self._solvent_dielectric = float(dielectric)
+
+    def getSoluteDielectric(self):
+        return self._solute_dielectric
+
+    def setSoluteDielectric(self, dielectric):
+        self._solute_dielectric = float(dielectric)
+
+    def getSurfaceAreaEnergy(self):
+        return Quantity(self._sa_energy, kjmol / nm ** 2)
+
+    def setSurfaceAreaEnergy(self, energy):
+        self._sa_energy = float(md_value(energy))
+
+    def getNonbondedMethod(self):
+        return self._method
+
+    def setNonbondedMethod(self, method):
+        self._method = int(method)
+
+    def getCutoffDistance(self):
+        return Quantity(self._cutoff, nm)
+
+    def setCutoffDistance(self, distance):
+        self._cutoff = float(md_value(distance))
+
+
 class TabulatedFunction:
     """A function given by numbers, for CustomNonbondedForce.addTabulatedFunction.  Evaluated on the GPU by the pair-expression
     kernel (atomsmm_amd/tables.py): Continuous1DFunction, Discrete1DFunction and Discrete2DFunction."""

@@ -21,7 +21,7 @@ import xml.etree.ElementTree as ET
 
 import numpy as np
 
-from . import (CMMotionRemover, Context, HarmonicAngleForce, HarmonicBondForce, NonbondedForce,  # noqa: F401
+from . import (CMMotionRemover, Context, GBSAOBCForce, HarmonicAngleForce, HarmonicBondForce, NonbondedForce,  # noqa: F401
                PeriodicTorsionForce, Platform, System, Vec3)
 from .. import unit as _unit
 from ..unit import Quantity, md_value
@@ -272,6 +272,7 @@ class ForceField:
         self._scales = (1.0, 1.0)
         self._has_nonbonded = False
         self._charge_from_residue = False
+        self._gb, self._gb_charge_from_residue = None, False        # <GBSAOBCForce>: type or ('class', c) -> (radius, scale, charge or None)
         for f in files:
             self.loadFile(f)
 
@@ -317,6 +318,13 @@ class ForceField:
                 self._lj[key] = (float(a.get('sigma')), float(a.get('epsilon')))
                 if a.get('charge') is not None:
                     self._charge_by_type[key] = float(a.get('charge'))
+        gb = root.find('GBSAOBCForce')
+        if gb is not None:
+            self._gb = {} if self._gb is None else self._gb
+            self._gb_charge_from_residue = any(u.get('name') == 'charge' for u in gb.findall('UseAttributeFromResidue'))
+            for a in gb.findall('Atom'):
+                key = a.get('type') if a.get('type') is not None else ('class', a.get('class'))
+                self._gb[key] = (float(a.get('radius')), float(a.get('scale')), None if a.get('charge') is None else float(a.get('charge')))
 
     # -- look-ups
     def _lookup(self, table, types, classes):
@@ -336,6 +344,19 @@ class ForceField:
             return key
         raise ValueError('No nonbonded parameters defined for atom type %s' % type_name)
 
+    def _gb_of(self, type_name, residue_charge):
+        """(charge, radius, scale) of an atom of this type in the <GBSAOBCForce> section: the type's entry before its class's; the
+        charge from the residue template (UseAttributeFromResidue) or from the entry."""
+        for key in (type_name, ('class', self._types[type_name]['cls'])):
+            if key in self._gb:
+                radius, scale, q = self._gb[key]
+                if self._gb_charge_from_residue:
+                    q = residue_charge
+                elif q is None:
+                    raise ValueError('GBSAOBCForce: no charge for atom type %s (no charge attribute, no UseAttributeFromResidue)' % type_name)
+                return q, radius, scale
+        raise ValueError('No GBSAOBC parameters defined for atom type %s' % type_name)
+
     def describe(self, topology):
         """Match templates and tables; returns plain arrays (MD units) describing the system createSystem would build:
         type, charge, sigma, epsilon, mass per atom; bonds, angles, proper torsions with parameters; the exception list
@@ -352,6 +373,7 @@ class ForceField:
                 atype[members[name]] = type_name
                 charge[members[name]] = q
             bonds += [(members[a], members[b]) for (a, b) in tmpl['bonds']]
+        residue_charge = charge.copy()
         if not self._charge_from_residue:
             for i in range(n):
                 charge[i] = self._charge_by_type.get(self._nonbonded_of(atype[i]), charge[i]) if self._has_nonbonded else charge[i]
@@ -364,6 +386,8 @@ class ForceField:
             partners[j].append(i)
         out = dict(type=np.array(atype), charge=charge, mass=mass, sigma=np.array([s for s, _ in lj]),
                    epsilon=np.array([e for _, e in lj]), all_bonds=np.array(bonds, dtype=np.int32).reshape(-1, 2))
+        if self._gb is not None:
+            out['gb'] = np.array([self._gb_of(t, q) for t, q in zip(atype, residue_charge)], dtype=np.float64).reshape(-1, 3)
         # harmonic bonds
         rows = []
         for (i, j) in bonds:
@@ -418,7 +442,8 @@ class ForceField:
 
     def createSystem(self, topology, nonbondedMethod=NoCutoff, nonbondedCutoff=1.0 * _unit.nanometer, constraints=None,
                      rigidWater=True, removeCMMotion=True, hydrogenMass=None, residueTemplates=None, ignoreExternalBonds=False,
-                     switchDistance=None, flexibleConstraints=False, ewaldErrorTolerance=0.0005, useDispersionCorrection=True):
+                     switchDistance=None, flexibleConstraints=False, ewaldErrorTolerance=0.0005, useDispersionCorrection=True,
+                     soluteDielectric=1.0, solventDielectric=78.3):
         if hydrogenMass is not None or residueTemplates:
             raise NotImplementedError('createSystem: hydrogenMass / residueTemplates are not supported')
         if constraints not in (None, HBonds):
@@ -487,6 +512,17 @@ class ForceField:
             nb.setEwaldErrorTolerance(ewaldErrorTolerance)
             nb.setUseDispersionCorrection(bool(useDispersionCorrection))
             system.addForce(nb)
+        if self._gb is not None:
+            # the implicit solvent takes the System's nonbonded method and cutoff (a periodic one is refused when a Context is created)
+            gb = GBSAOBCForce()
+            for q, radius, scale in d['gb']:
+                gb.addParticle(float(q), float(radius), float(scale))
+            methods = {NoCutoff: gb.NoCutoff, CutoffNonPeriodic: gb.CutoffNonPeriodic}
+            gb.setNonbondedMethod(methods.get(nonbondedMethod, gb.CutoffPeriodic))
+            gb.setCutoffDistance(nonbondedCutoff)
+            gb.setSoluteDielectric(soluteDielectric)
+            gb.setSolventDielectric(solventDielectric)
+            system.addForce(gb)
         if removeCMMotion:
             system.addForce(CMMotionRemover())
         assert system.getNumParticles() == n

@@ -376,6 +376,24 @@ int amm_compound_set_weights(amm_ctx *ctx, int32_t force_id, const double *weigh
 /* Free such a force; the id is retired and leaves every group definition. */
 int amm_compound_release(amm_ctx *ctx, int32_t force_id);
 
+/* GBSAOBCForce: generalized-Born implicit solvent (OBC2: alpha 1, beta 0.8, gamma 4.85; dielectric offset 0.009 nm) with the
+ * surface-area term 4 pi sa_energy (R + 0.14)^2 (R / B)^6, for free-space systems (csrc/gb.hip).  h_q,
+ * h_radius (nm), h_scale: n_atoms doubles each -- addParticle(charge, radius, scale); eps_in / eps_out: solute and solvent
+ * dielectric; sa_energy in kJ/mol/nm^2; rc <= 0: NoCutoff, otherwise CutoffNonPeriodic with the predicate r^2 < rc^2.  All pairs
+ * of atoms take part (exclusions of other forces play no role), the diagonal is left out by index.  Refused: a radius <= 0.009, a
+ * negative scale, a dielectric <= 0, more than 32768 atoms, more than one rank.  The force is a group member like any other:
+ * amm_force_eval and amm_run_ops evaluate it, force-only or with energy; it is legal in a context created without a box.  Three
+ * launches per evaluation (Born radii, pair sums, chain rule), no atomics: the same positions give the same bits. */
+int amm_gb_create(amm_ctx *ctx, const double *h_q, const double *h_radius, const double *h_scale, double eps_in, double eps_out,
+                  double sa_energy, double rc, int32_t *force_id);
+/* setParticleParameters / setSolventDielectric / ... + updateParametersInContext: everything again, checked as at creation. */
+int amm_gb_set_params(amm_ctx *ctx, int32_t force_id, const double *h_q, const double *h_radius, const double *h_scale, double eps_in,
+                      double eps_out, double sa_energy, double rc);
+/* The Born radii at d_pos (device, [n][3]) into h_out (host, n doubles): runs the first pass and waits (tests, diagnostics). */
+int amm_gb_born_radii(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *h_out);
+/* Free such a force; the id is retired and leaves every group definition. */
+int amm_gb_release(amm_ctx *ctx, int32_t force_id);
+
 /* Reciprocal space of a NonbondedForce with nonbondedMethod PME / Ewald, as RESPASystem and FarNonbondedForce
  * keep it in group 2 with the source force's Ewald tolerance / PME parameters (systems.py:74-75,
  * forces.py:185-188; setReciprocalSpaceForceGroup: utils.py:147-152).  Smooth PME, B-spline order 5, grid
@@ -494,7 +512,8 @@ int amm_set_outer_skin(amm_ctx *ctx, double skin_out);
  * pair kernel runs the kicks and the inner RESPA loop that follow its EVAL in the step program as its epilogue when the innermost group
  * is one bond-list set of three-site molecules -- propagators.py:933-973 unrolled; 0: launches of their own), "comm_timeout" (seconds
  * amm_check / amm_synchronize / amm_comm_destroy wait for the stream while the context owns an RCCL communicator before they abort it and
- * fail; default 0 = no deadline, the asynchronous error alone is polled).  Unknown names are an error. */
+ * fail; default 0 = no deadline, the asynchronous error alone is polled), "gb_lanes_per_row" (lanes that sum one row of the
+ * generalized-Born passes: 0 = chosen from n as for free-space pair forces; 1, 2, 4 .. 64).  Unknown names are an error. */
 int amm_set_option(amm_ctx *ctx, const char *name, double value);
 /* What amm_run_ops fused so far (statistics for tests and bench.py): out[0] = pair-kernel launches that carried the inner RESPA loop
  * of their molecules as an epilogue (the reference runs it as CustomIntegrator steps, propagators.py:933-973), out[1] = pair
