@@ -24,6 +24,7 @@ OP_SAVE_REF, OP_CONSTRAIN_X, OP_CONSTRAIN_V = 8, 9, 10
 OP_ALLREDUCE = 11
 OP_STOCK = 12
 STOCK_VERLET, STOCK_LANGEVIN_MIDDLE, STOCK_LANGEVIN, STOCK_BROWNIAN = range(4)   # amm_stock_define kinds
+VSITE_AVERAGE2, VSITE_AVERAGE3, VSITE_OUT_OF_PLANE = range(3)                     # amm_vsite_define kinds
 EXCHANGE_REDUCE, EXCHANGE_GATHER = 0, 1
 COMM_ID_BYTES = 128
 MAX_SLOTS, SLOT_X, SLOT_V = 64, 62, 63
@@ -58,6 +59,7 @@ EXPORTS = [
     'amm_compound_create', 'amm_compound_set_globals', 'amm_compound_set_params', 'amm_compound_set_weights', 'amm_compound_release',
     'amm_run_rule_stats',
     'amm_gb_create', 'amm_gb_set_params', 'amm_gb_born_radii', 'amm_gb_release',
+    'amm_vsite_define', 'amm_vsite_place', 'amm_vsite_spread', 'amm_vsite_stats',
 ]
 
 
@@ -262,6 +264,10 @@ def lib():
         L.amm_box_stats.argtypes = [vp, C.POINTER(C.c_int64)]
         L.amm_mol_define.argtypes = [vp, ip, ip, C.c_int32]
         L.amm_mol_scale.argtypes = [vp, vp, vp, dp]
+        L.amm_vsite_define.argtypes = [vp, C.c_int32, ip, ip, ip, dp]
+        L.amm_vsite_place.argtypes = [vp, vp]
+        L.amm_vsite_spread.argtypes = [vp, vp, vp]
+        L.amm_vsite_stats.argtypes = [vp, C.POINTER(C.c_int64)]
         for name in EXPORTS:
             if name not in ('amm_last_error', 'amm_kernel_revision'):
                 getattr(L, name).restype = C.c_int
@@ -863,6 +869,33 @@ class HipContext:
         """x <- x + (scale - 1) * centre of the atom's molecule, per axis; saved (or None) <- the old x, bit for bit."""
         s_, sp = _hd(np.asarray(scale, dtype=np.float64).reshape(3))
         _chk(lib().amm_mol_scale(self.h, _ptr(x), _ptr(saved), sp))
+
+    # ---- virtual sites
+    def vsite_define(self, sites, kinds, parents, weights):
+        """Virtual sites: atom index and kind (VSITE_*) per site, parents [n_sites][3] (-1 pads a site of two parents), weights
+        [n_sites][3]; replaces an earlier definition, no sites removes it."""
+        n = len(sites)
+        if n == 0:
+            _chk(lib().amm_vsite_define(self.h, 0, None, None, None, None))
+            return
+        s_, sp = _hi(np.asarray(sites).reshape(n))
+        k_, kp = _hi(np.asarray(kinds).reshape(n))
+        p_, pp = _hi(np.asarray(parents).reshape(n, 3))
+        w_, wp = _hd(np.asarray(weights, dtype=np.float64).reshape(n, 3))
+        _chk(lib().amm_vsite_define(self.h, n, sp, kp, pp, wp))
+
+    def vsite_place(self, x):
+        """Sites <- their parents' positions in x (a no-op without sites)."""
+        _chk(lib().amm_vsite_place(self.h, _ptr(x)))
+
+    def vsite_spread(self, x, f):
+        """The sites' rows of f go to their parents' (J^T f at x) and become 0 (a no-op without sites)."""
+        _chk(lib().amm_vsite_spread(self.h, _ptr(x), _ptr(f)))
+
+    def vsite_stats(self):
+        out = (C.c_int64 * 4)()
+        _chk(lib().amm_vsite_stats(self.h, out))
+        return dict(places=out[0], spreads=out[1], launches=out[2], sites=out[3])
 
     def exchange_per(self):
         """Slots of the cell-sorted order per rank (whole molecules of three): chunk geometry of the exchange buffer."""

@@ -171,6 +171,7 @@ int amm_destroy(amm_ctx *ctx) {
     if (ctx->alt_v) (void)hipFree(ctx->alt_v);
     if (ctx->alt_f) (void)hipFree(ctx->alt_f);
     amm_mol_free(ctx);
+    amm_vsite_free(ctx);
     delete ctx;
     return 0;
 }
@@ -1357,12 +1358,45 @@ int amm_kick(amm_ctx *ctx, double *d_v, const double *d_f, const double *d_f2, i
     return amm_kick_impl(ctx, d_v, d_f, d_f2, plus, d_mass, coef);
 }
 int amm_move(amm_ctx *ctx, double *d_x, const double *d_v, double coef) {
+    if (amm_move_impl(ctx, d_x, d_v, coef)) return 1;
+    if (d_x == ctx->d_x && amm_vsite_place_impl(ctx, d_x)) return 1;     // (sites follow every update of the bound positions)
     ctx->pos_epoch++;
-    return amm_move_impl(ctx, d_x, d_v, coef);
+    return 0;
 }
 int amm_copy(amm_ctx *ctx, double *d_dst, const double *d_src) {
+    if (amm_copy_impl(ctx, d_dst, d_src)) return 1;
+    if (d_dst == ctx->d_x && amm_vsite_place_impl(ctx, d_dst)) return 1;
     ctx->pos_epoch++;
-    return amm_copy_impl(ctx, d_dst, d_src);
+    return 0;
+}
+
+int amm_vsite_define(amm_ctx *ctx, int32_t n_sites, const int32_t *h_site, const int32_t *h_kind, const int32_t *h_parents,
+                     const double *h_weights) {
+    if (!ctx || n_sites < 0 || (n_sites > 0 && (!h_site || !h_kind || !h_parents || !h_weights))) {
+        amm_set_error("amm_vsite_define: bad arguments");
+        return 1;
+    }
+    return amm_vsite_define_impl(ctx, n_sites, h_site, h_kind, h_parents, h_weights);
+}
+int amm_vsite_place(amm_ctx *ctx, double *d_x) {
+    if (!ctx || !d_x) {
+        amm_set_error("amm_vsite_place: null argument");
+        return 1;
+    }
+    if (amm_vsite_place_impl(ctx, d_x)) return 1;
+    ctx->pos_epoch++;
+    return 0;
+}
+int amm_vsite_spread(amm_ctx *ctx, const double *d_x, double *d_f) {
+    if (!ctx || !d_x || !d_f) {
+        amm_set_error("amm_vsite_spread: null argument");
+        return 1;
+    }
+    return amm_vsite_spread_impl(ctx, d_x, d_f);
+}
+int amm_vsite_stats(amm_ctx *ctx, int64_t out[4]) {
+    if (!ctx || !out) return 1;
+    return amm_vsite_stats_impl(ctx, out);
 }
 int amm_mvv(amm_ctx *ctx, const double *d_v, const double *d_m, double *d_out) { return amm_mvv_impl(ctx, d_v, d_m, d_out); }
 

@@ -423,6 +423,7 @@ struct amm_ctx {
     double *d_expr_part = nullptr; // block partial sums of amm_expr_eval
     double *d_fscratch = nullptr;  // [n][3] force sink of amm_pair_energy_derivative
     ConstraintSet *constraints = nullptr;   // distance constraints of the System (AMM_OP_CONSTRAIN_*)
+    struct VsiteSet *vsites = nullptr;      // virtual sites of the System (vsite.hip); null: none
     std::vector<MinObj *> minimizers;       // amm_min_create (ids are positions, never reused)
     std::vector<ExprDef> exprs;    // registered per-DOF expressions (AMM_OP_EXPR)
     std::vector<BathDef> baths;    // registered baths (AMM_OP_BATH)
@@ -497,6 +498,13 @@ int amm_exchange_finish_impl(amm_ctx *ctx);
 int amm_mol_define_impl(amm_ctx *ctx, const int32_t *h_ptr, const int32_t *h_atoms, int n_mol);
 int amm_mol_scale_impl(amm_ctx *ctx, double *d_x, double *d_x_saved, const double scale[3]);
 int amm_mol_free(amm_ctx *ctx);
+// vsite.hip: virtual sites.  place / spread do nothing and return 0 on a context without sites
+int amm_vsite_define_impl(amm_ctx *ctx, int n_sites, const int32_t *h_site, const int32_t *h_kind, const int32_t *h_parents,
+                          const double *h_weights);
+int amm_vsite_place_impl(amm_ctx *ctx, double *d_x);
+int amm_vsite_spread_impl(amm_ctx *ctx, const double *d_x, double *d_f);
+int amm_vsite_stats_impl(amm_ctx *ctx, int64_t out[4]);
+int amm_vsite_free(amm_ctx *ctx);
 
 // group.hip
 void amm_small_group_forget(SmallGroup *sg);      // the companion list is about to change under it (amm_set_box): candidates start over

@@ -21,8 +21,13 @@ __global__ void __launch_bounds__(256) k_expr(int n3, ExprProg P, double *dst, d
     const int dof = blockIdx.x * blockDim.x + threadIdx.x;
     double val = 0.0;
     if (dof < n3) {
-        val = expr_run(P, dof);
-        if (dst) dst[dof] = val;
+        // (OpenMM's computePerDof / computeSum rule: the destination of a massless particle's degrees of freedom stays as it is, and
+        // they add nothing to a sum -- `m*v*v` is 0 there anyway, `v*v/m` would be 0/0)
+        if (P.mass && P.mass[dof / 3] == 0.0) val = 0.0;
+        else {
+            val = expr_run(P, dof);
+            if (dst) dst[dof] = val;
+        }
     }
     if (part) {
         __shared__ double red[4];
@@ -204,7 +209,10 @@ int amm_expr_eval_impl(amm_ctx *ctx, const int32_t *code, int n_code, const doub
         AMM_HIP(hipMemsetAsync(d_sum, 0, sizeof(double), ctx->stream));
         if (amm_reduce_add(ctx, ctx->d_expr_part, nblk, 1.0, d_sum)) return 1;
     }
-    if (d_dst == ctx->d_x) ctx->pos_epoch++;
+    if (d_dst == ctx->d_x) {
+        if (amm_vsite_place_impl(ctx, ctx->d_x)) return 1;       // (sites follow every update of the bound positions)
+        ctx->pos_epoch++;
+    }
     return 0;
 }
 
@@ -257,7 +265,9 @@ __global__ void k_bath_ou(int n3, double *v, const double *__restrict__ mass, do
                           unsigned long long counter) {
     const int dof = blockIdx.x * blockDim.x + threadIdx.x;
     if (dof >= n3) return;
-    v[dof] = amm_ou_step(v[dof], mass[dof / 3], z, kT, amm_gaussian(seed, counter, (unsigned)dof));
+    const double m = mass[dof / 3];
+    if (m == 0.0) return;                 // (a massless particle has no thermal velocity)
+    v[dof] = amm_ou_step(v[dof], m, z, kT, amm_gaussian(seed, counter, (unsigned)dof));
 }
 
 __global__ void k_bath_nhl(int n3, double *v, double *w, const double *__restrict__ mass, BathDef b, unsigned long long seed,

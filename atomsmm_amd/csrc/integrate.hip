@@ -19,8 +19,10 @@ __global__ void k_kick(int n3, double *__restrict__ v, const double *__restrict_
     if (t >= n3) return;
     double ff = f[t];
     if (f2) ff = plus ? ff + f2[t] : ff - f2[t];
+    const double m = mass[t / 3];
+    if (m == 0.0) return;                 // a massless particle (a virtual site) takes no kick: OpenMM skips it in every step
     const double num = coef * ff;
-    const double dv = num / mass[t / 3];
+    const double dv = num / m;
     v[t] = v[t] + dv;
 }
 
@@ -44,6 +46,7 @@ __global__ void k_kicks_move(int n3, double *__restrict__ x, double *__restrict_
     if (t >= n3) return;
     double vt = v[t];
     const double m = mass[t / 3];
+    if (m == 0.0) return;                 // (massless: neither kicked nor moved -- its velocity is 0)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         if (k < K.n) {
@@ -68,6 +71,7 @@ __global__ void k_kicks_move_atoms(int n, double *__restrict__ x, double *__rest
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const double m = mass[i];
+    if (m == 0.0) return;                 // (massless: neither kicked nor moved -- its velocity is 0)
     double xn[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {

@@ -89,6 +89,13 @@ struct OpRun {
         }
         return true;
     }
+    // Behind an op that wrote the bound positions: virtual sites follow their parents at once (OpenMM places after every position
+    // update; an evaluation never places), then the epoch moves on -- once, for the positions as they now stand.
+    int x_written() {
+        if (amm_vsite_place_impl(ctx, ctx->d_x)) return FAILED;          // (nothing without sites)
+        ctx->pos_epoch++;
+        return DONE;
+    }
     bool in_own_only(const double *b) const { return b && std::find(ctx->own_only.begin(), ctx->own_only.end(), b) != ctx->own_only.end(); }
     // Buffers that hold this rank's rows only (state exchange, cluster.hip).  complete(buf): before an op reads `buf` for ALL atoms --
     // a bond-list group's buffer is evaluated again (every rank can: positions are whole after every exchange; the same numbers the
@@ -181,7 +188,7 @@ struct OpRun {
 
     // ---- epilogue plans ----
     // (regulated mode: the epilogue's moves are plain ones -- not planned, the ops run on the paths that know the mode)
-    bool plans_allowed() const { return ctx->fuse_inner && ctx->opt_fuse_epilogue && !ctx->iso.on && !ctx->reg.on && !swapped && f0_slot < 0; }
+    bool plans_allowed() const { return !ctx->vsites && ctx->fuse_inner && ctx->opt_fuse_epilogue && !ctx->iso.on && !ctx->reg.on && !swapped && f0_slot < 0; }
     // The run of at most `cap` kicks at op `after`.  When the program ENDS with them (the closing half kicks of an outer step) and
     // another repetition follows, the run goes on with the kicks that open that repetition (`wraps`; what the deferred kicks do for
     // the stand-alone launches).  Answers their number; j: the op behind the run.
@@ -594,7 +601,12 @@ struct OpRun {
     }
     int run_plain(int &k) {
         const amm_op &op = ops[k];
-        if (op.op == AMM_OP_EVAL) return run_eval(k);
+        if (op.op == AMM_OP_EVAL) {
+            // (with virtual sites: what the sites collected goes to their parents as soon as the group's buffer is full)
+            const int r = run_eval(k);
+            if (r != DONE || !ctx->vsites) return r;
+            return amm_vsite_spread_impl(ctx, ctx->d_x, ctx->slots[ctx->groups[op.a].slot]) ? FAILED : DONE;
+        }
         switch (op.op) {
         case AMM_OP_KICK: {
             const double *fa, *fb;
@@ -609,11 +621,11 @@ struct OpRun {
         } break;
         case AMM_OP_MOVE:
             if (amm_move_impl(ctx, ctx->d_x, ctx->d_v, op.coef)) return FAILED;
-            ctx->pos_epoch++;
+            if (x_written()) return FAILED;
             break;
         case AMM_OP_COPY:
             if (copy_op(op, true)) return FAILED;
-            if (slot(op.a) == ctx->d_x) ctx->pos_epoch++;
+            if (slot(op.a) == ctx->d_x && x_written()) return FAILED;
             break;
         case AMM_OP_COMBINE: {
             double *dst = slot(op.a), *sa = slot(op.b), *sb = slot(op.c);
@@ -623,7 +635,7 @@ struct OpRun {
             }
             if (complete(sa) || complete(sb)) return FAILED;
             if (amm_combine_impl(ctx, dst, sa, sb, op.coef)) return FAILED;
-            if (dst == ctx->d_x) ctx->pos_epoch++;
+            if (dst == ctx->d_x && x_written()) return FAILED;
         } break;
         case AMM_OP_EXPR: {
             double *dst = slot(op.b);
@@ -649,7 +661,7 @@ struct OpRun {
                 if (amm_constraints_save_reference(ctx, ctx->constraints, ctx->d_x)) return FAILED;
             } else if (op.op == AMM_OP_CONSTRAIN_X) {
                 if (amm_constrain_positions(ctx, ctx->constraints, ctx->d_x)) return FAILED;
-                ctx->pos_epoch++;
+                if (x_written()) return FAILED;
             } else if (amm_constrain_velocities(ctx, ctx->constraints, ctx->d_x, ctx->d_v)) return FAILED;
         } break;
         case AMM_OP_BATH: {
@@ -675,8 +687,9 @@ struct OpRun {
             }
             if (complete(f)) return FAILED;
             if (amm_stock_step_impl(ctx, ctx->stocks[op.a], f, (1ull << 63) | ++ctx->expr_counter)) return FAILED;
-            ctx->pos_epoch++;
-            amm_watch_moved(ctx);
+            if (x_written()) return FAILED;
+            // (the launch evaluated the lists' displacement triggers -- for the atoms it moved, not for sites placed since)
+            if (!ctx->vsites) amm_watch_moved(ctx);
         } break;
         case AMM_OP_ALLREDUCE: {
             if (!slot(op.a)) {
@@ -716,6 +729,10 @@ struct OpRun {
     // (Deferred kicks reach 2, 3 and 6 only: anything but a KICK at op 0 flushes them first.)
     int step(int &k) {
         if (ndef && !(k == 0 && ops[k].op == AMM_OP_KICK) && flush_deferred()) return FAILED;
+        // virtual sites: every position update is followed by a placement and every evaluation by a spread, which no fused launch
+        // does -- every op runs on its own (the near force riding on the outer force's traversal inside run_eval fills the same
+        // buffer and stays)
+        if (ctx->vsites) return taken(0, run_plain(k));
         int r;
         if ((r = rule_defer_trailing_kicks(k)) != NOT_MINE) return taken(1, r);
         if ((r = rule_inner_components(k)) != NOT_MINE) return taken(2, r);

@@ -177,6 +177,7 @@ __global__ void __launch_bounds__(256) k_stock(StockArgs A) {
         const int q = u - A.o_free;
         if (q >= A.n_free) return;
         const int idx[1] = {A.units ? A.units[A.n_tri + A.n_two + A.n_gen + q] : q};
+        if (A.mass[idx[0]] == 0.0) return;       // a massless particle (a virtual site; never in a cluster) stores nothing
         stock_unit(A, ConsShapeNone(), idx, 1);
     }
 }

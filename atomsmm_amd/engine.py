@@ -290,6 +290,7 @@ class Engine:
         n = system.getNumParticles()
         if n == 0:
             raise mm.OpenMMException('System has no particles')
+        mm.check_virtual_sites(system)
         try:
             vecs = system._box
         except AttributeError:
@@ -328,6 +329,7 @@ class Engine:
         self._coll = self.world > 1 or (os.environ.get('AMM_FORCE_COLLECTIVES') == '1' and dist.is_available()
                                         and dist.is_initialized())
         self._check_gb(system, integrator)
+        self._check_massless(system, integrator)
         if self.free_space and self.world > 1:
             raise InputError('a System in free space (NoCutoff / CutoffNonPeriodic) runs on a single rank: its pair forces walk all pairs '
                              'and are not sliced')
@@ -408,6 +410,7 @@ class Engine:
         self._fwork = torch.zeros((n, 3), dtype=f64, device=dev)
         self._fwork2 = torch.zeros((n, 3), dtype=f64, device=dev)
         self.ctx.bind_state(self.x, self.v, self.mass)
+        self._define_vsites(system)
         self._has_constraints = system.getNumConstraints() > 0
         if self._has_constraints:
             cons = system._constraints
@@ -417,6 +420,50 @@ class Engine:
             integrator._n_hint = n
         if self.barostat is not None:
             self._init_barostat()
+
+    def _check_massless(self, system, integrator):
+        """Massless particles (virtual sites among them) never move: the stock integrators, plain kicks and moves, the
+        Ornstein-Uhlenbeck bath and per-DOF expressions skip them as OpenMM does.  What has not learnt the rule is refused by name."""
+        self._massless = bool(getattr(system, '_vsites', None)) or any(m == 0.0 for m in system._masses)
+        if not self._massless:
+            return
+        texts = [e.replace(' ', '') for _, _, e in getattr(integrator, '_steps', []) if isinstance(e, str)]
+        what = None
+        if any(c.__name__ == 'AdiabaticDynamicsIntegrator' for c in type(integrator).__mro__):
+            what = 'AdiabaticDynamicsIntegrator'
+        elif any(c.__name__ == 'ComputingSystem' for c in type(system).__mro__):
+            what = 'ComputingSystem / PressureComputer'
+        elif self.world > 1:
+            what = 'a run on several ranks'
+        elif any('deriv(energy' in t for t in texts):
+            what = 'a step program with deriv(energy, ...) steps'
+        elif any('cosh(z)' in t and 'LkT' in t for t in texts):
+            what = 'the SIN(R) / isokinetic path'
+        elif any('tanh(' in t for t in texts):
+            what = 'the regulated path'
+        elif any(self._NHL_UPDATE.fullmatch(t) for t in texts):
+            what = 'the native Nose-Hoover-Langevin bath'
+        if what is not None:
+            raise InputError('a System with massless particles or virtual sites does not run with %s' % what)
+
+    def _define_vsites(self, system):
+        sites = sorted(getattr(system, '_vsites', {}).items())
+        if sites:
+            parents = np.full((len(sites), 3), -1, dtype=np.int32)
+            weights = np.zeros((len(sites), 3))
+            for row, (_, site) in enumerate(sites):
+                parents[row, :site.getNumParticles()] = site._particles
+                weights[row, :len(site._weights)] = site._weights
+            self.ctx.vsite_define([index for index, _ in sites], [site._kind for _, site in sites], parents, weights)
+        elif self._massless and hasattr(self.ctx, 'set_fuse_inner'):
+            # (the fused launches of amm_run_ops divide by every mass; with sites defined the library keeps them out itself)
+            self.ctx.set_fuse_inner(False)
+        self._has_vsites = bool(sites)
+
+    def compute_virtual_sites(self):
+        if self._has_vsites:
+            self.ctx.vsite_place(self.x)
+            self._invalidate_forces()
 
     @staticmethod
     def _free_space_mode(system, has_box):
@@ -612,6 +659,8 @@ class Engine:
         valid = dict(self._valid)
         self.set_box(box0 * s)
         self.ctx.mol_scale(self.x, [s, s, s], self._x_saved)
+        if self._has_vsites:
+            self.ctx.vsite_place(self.x)
         e1 = self._potential_energy()
         w = e1 - e0 + pressure * delta - self._n_molecules * kT * math.log(new_volume / volume)
         u2 = None
@@ -1932,7 +1981,10 @@ class Engine:
                 if want_energy:
                     self._allreduce(e_pair)
             if want_forces:
-                forces = (fp + fb).cpu().numpy()
+                total = fp + fb
+                if self._has_vsites:          # what the sites collected goes to their parents
+                    self.ctx.vsite_spread(self.x, total)
+                forces = total.cpu().numpy()
             if want_energy:
                 energy = e_pair.item() + e_bond.item() + const
         kinetic = None
@@ -2083,6 +2135,7 @@ class Engine:
             raise ValueError('minimize: the tolerance must be positive')
         torch = self.torch
         dev = self.x.device
+        self.compute_virtual_sites()          # (the first energy and gradient are taken with the sites on their parents)
         result = dict(iterations=0, evaluations=0, passes=0, restraint_strength=0.0)
         if self._has_constraints:
             cons = self.system._constraints
@@ -2138,6 +2191,8 @@ class Engine:
                     ctx.force_eval(entry.recip, self.x, force, accumulate=True, energy=scal)
             if restraint is not None:
                 ctx.force_eval(restraint, self.x, force, accumulate=True, energy=scal)
+            if self._has_vsites:              # the gradient with respect to the parents; the sites' own rows become 0
+                ctx.vsite_spread(self.x, force)
             result['evaluations'] += 1
             if not read:
                 return None
@@ -2158,6 +2213,8 @@ class Engine:
         def moved():
             # the Verlet lists' displacement checks must see the move (amm_min_trial says so itself; this is the engine's own rule
             # for every write of self.x)
+            if self._has_vsites:              # (a trial leaves the massless sites where they were: they follow their parents here)
+                ctx.vsite_place(self.x)
             ctx.positions_changed()
             self._invalidate_forces()
 

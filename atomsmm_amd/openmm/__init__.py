@@ -1077,6 +1077,92 @@ class MonteCarloBarostat(Force):
         return False
 
 
+# ------------------------------------------------------------------------------------------------ virtual sites
+class VirtualSite:
+    """openmm.VirtualSite: a massless particle whose position is computed from other particles (System.setVirtualSite)."""
+    _kind = -1
+
+    def __init__(self, particles, weights):
+        self._particles = tuple(int(p) for p in particles)
+        self._weights = tuple(float(w) for w in weights)
+
+    def getNumParticles(self):
+        return len(self._particles)
+
+    def getParticle(self, particle):
+        return self._particles[particle]
+
+
+class TwoParticleAverageSite(VirtualSite):
+    """s = w1 r1 + w2 r2"""
+    _kind = 0
+
+    def __init__(self, particle1, particle2, weight1, weight2):
+        super().__init__((particle1, particle2), (weight1, weight2))
+
+    def getWeight(self, particle):
+        return self._weights[particle]
+
+
+class ThreeParticleAverageSite(VirtualSite):
+    """s = w1 r1 + w2 r2 + w3 r3"""
+    _kind = 1
+
+    def __init__(self, particle1, particle2, particle3, weight1, weight2, weight3):
+        super().__init__((particle1, particle2, particle3), (weight1, weight2, weight3))
+
+    def getWeight(self, particle):
+        return self._weights[particle]
+
+
+class OutOfPlaneSite(VirtualSite):
+    """s = r1 + w12 r12 + w13 r13 + wCross (r12 x r13), r12 = r2 - r1, r13 = r3 - r1"""
+    _kind = 2
+
+    def __init__(self, particle1, particle2, particle3, weight12, weight13, weightCross):
+        super().__init__((particle1, particle2, particle3), (weight12, weight13, weightCross))
+
+    def getWeight12(self):
+        return self._weights[0]
+
+    def getWeight13(self):
+        return self._weights[1]
+
+    def getWeightCross(self):
+        return self._weights[2]
+
+
+class LocalCoordinatesSite(VirtualSite):
+    """Exists so that a script that names it fails with a message of its own: the HIP path has no such site."""
+
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError('LocalCoordinatesSite is not supported by the HIP path (TwoParticleAverageSite, '
+                                  'ThreeParticleAverageSite and OutOfPlaneSite are)')
+
+
+def check_virtual_sites(system):
+    """What OpenMM checks when a Context is created over a System with virtual sites or massless particles."""
+    n = system.getNumParticles()
+    sites = getattr(system, '_vsites', {})
+    for index, site in sorted(sites.items()):
+        if system._masses[index] != 0.0:
+            raise OpenMMException('Virtual site %d has nonzero mass (%g)' % (index, system._masses[index]))
+        for k in range(site.getNumParticles()):
+            p = site.getParticle(k)
+            if not 0 <= p < n:
+                raise OpenMMException('Virtual site %d: particle index %d is out of range' % (index, p))
+            if p in sites:
+                raise OpenMMException('Virtual site %d depends on particle %d, which is a virtual site itself' % (index, p))
+            if p == index or p in [site.getParticle(j) for j in range(k)]:
+                raise OpenMMException('Virtual site %d names particle %d twice' % (index, p))
+    for p1, p2, _ in system._constraints:
+        for p in (p1, p2):
+            if p in sites:
+                raise OpenMMException('A constraint cannot involve a virtual site (particle %d)' % p)
+            if 0 <= p < n and system._masses[p] == 0.0:
+                raise OpenMMException('A constraint cannot involve a massless particle (particle %d)' % p)
+
+
 # ------------------------------------------------------------------------------------------------ system
 class System:
     def __init__(self):
@@ -1084,6 +1170,23 @@ class System:
         self._forces = []
         self._box = None
         self._constraints = []
+        self._vsites = {}
+
+    def setVirtualSite(self, index, virtualSite):
+        index = int(index)
+        if not 0 <= index < len(self._masses):
+            raise OpenMMException('setVirtualSite: particle index %d is out of range' % index)
+        if not isinstance(virtualSite, VirtualSite):
+            raise TypeError('setVirtualSite: a VirtualSite is expected')
+        self._vsites[index] = virtualSite
+
+    def isVirtualSite(self, index):
+        return int(index) in self._vsites
+
+    def getVirtualSite(self, index):
+        if int(index) not in self._vsites:
+            raise OpenMMException('This particle is not a virtual site')
+        return self._vsites[int(index)]
 
     def addParticle(self, mass):
         self._masses.append(float(md_value(mass)))
@@ -1531,6 +1634,9 @@ def molecules_of(system):
                      [(r[2], r[3]) for r in force._torsions]
         elif isinstance(force, CustomCompoundBondForce):       # consecutive particles, as an angle or torsion (a centroid bond joins nothing)
             pairs += [(a, b) for members, _ in force._bonds for a, b in zip(members[:-1], members[1:])]
+    # (a virtual site belongs to the molecule of its parents, as in OpenMM's getMolecules)
+    pairs += [(index, site.getParticle(k)) for index, site in sorted(getattr(system, '_vsites', {}).items())
+              for k in range(site.getNumParticles()) if 0 <= site.getParticle(k) < n]
     for i, j in pairs:
         a, b = find(int(i)), find(int(j))
         if a != b:
@@ -1588,6 +1694,10 @@ class Context:
 
     def applyVelocityConstraints(self, tol=None):
         self._engine.apply_velocity_constraints()
+
+    def computeVirtualSites(self):
+        """Put every virtual site where its parents' current positions say (a no-op for a System without sites)."""
+        self._engine.compute_virtual_sites()
 
     def setParameter(self, name, value):
         if name == MonteCarloBarostat.Pressure() and isinstance(value, Quantity):

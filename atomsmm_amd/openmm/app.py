@@ -22,7 +22,7 @@ import xml.etree.ElementTree as ET
 import numpy as np
 
 from . import (CMMotionRemover, Context, GBSAOBCForce, HarmonicAngleForce, HarmonicBondForce, NonbondedForce,  # noqa: F401
-               PeriodicTorsionForce, Platform, System, Vec3)
+               OutOfPlaneSite, PeriodicTorsionForce, Platform, System, ThreeParticleAverageSite, TwoParticleAverageSite, Vec3)
 from .. import unit as _unit
 from ..unit import Quantity, md_value
 from ..utils import InputError
@@ -288,7 +288,7 @@ class ForceField:
                     bonds.append((b.get('atomName1'), b.get('atomName2')))
                 else:
                     bonds.append((atoms[int(b.get('from'))][0], atoms[int(b.get('to'))][0]))
-            self._templates[r.get('name')] = dict(atoms=atoms, bonds=bonds)
+            self._templates[r.get('name')] = dict(atoms=atoms, bonds=bonds, sites=self._read_sites(r, atoms))
 
         def types_of(node, n):
             """type1..n or class1..n attributes -> tuple of (kind, value)"""
@@ -325,6 +325,37 @@ class ForceField:
             for a in gb.findall('Atom'):
                 key = a.get('type') if a.get('type') is not None else ('class', a.get('class'))
                 self._gb[key] = (float(a.get('radius')), float(a.get('scale')), None if a.get('charge') is None else float(a.get('charge')))
+
+    _SITE_KINDS = {'average2': (2, ('weight1', 'weight2')), 'average3': (3, ('weight1', 'weight2', 'weight3')),
+                   'outOfPlane': (3, ('weight12', 'weight13', 'weightCross'))}
+
+    @classmethod
+    def _read_sites(cls, residue, atoms):
+        """The <VirtualSite> entries of a residue template: (site name, type, parent names, weights).  Both spellings of OpenMM's
+        files: `index` / `atom1..3` (positions in the residue's atom list) and `siteName` / `atomName1..3`."""
+        sites = []
+        for v in residue.findall('VirtualSite'):
+            kind = v.get('type')
+            where = 'residue %s' % residue.get('name')
+            if kind == 'localCoords':
+                raise NotImplementedError('%s: <VirtualSite type="localCoords"> (LocalCoordinatesSite) is not supported' % where)
+            if kind not in cls._SITE_KINDS:
+                raise ValueError('%s: unknown <VirtualSite> type %r' % (where, kind))
+            if v.get('excludeWith') is not None:
+                raise NotImplementedError('%s: the excludeWith attribute of <VirtualSite> is not supported (a site takes its '
+                                          'exclusions as if bonded to its first parent)' % where)
+            count, weight_names = cls._SITE_KINDS[kind]
+            if v.get('siteName') is not None:
+                site = v.get('siteName')
+                parents = [v.get('atomName%d' % k) for k in range(1, count + 1)]
+            else:
+                site = atoms[int(v.get('index'))][0]
+                parents = [atoms[int(v.get('atom%d' % k))][0] for k in range(1, count + 1)]
+            names = [a[0] for a in atoms]
+            if site not in names or any(p not in names for p in parents):
+                raise ValueError('%s: a <VirtualSite> names an atom the residue does not have' % where)
+            sites.append((site, kind, tuple(parents), tuple(float(v.get(w)) for w in weight_names)))
+        return sites
 
     # -- look-ups
     def _lookup(self, table, types, classes):
@@ -363,7 +394,7 @@ class ForceField:
         (1-2 and 1-3 pairs excluded, 1-4 pairs scaled: OpenMM's createExceptionsFromBonds)."""
         atoms = list(topology.atoms())
         n = len(atoms)
-        atype, charge, bonds = [None] * n, np.zeros(n), []
+        atype, charge, bonds, vsites = [None] * n, np.zeros(n), [], []
         for res in topology.residues():
             tmpl = self._templates.get(res.name)
             members = {a.name: a.index for a in res.atoms()}
@@ -373,6 +404,8 @@ class ForceField:
                 atype[members[name]] = type_name
                 charge[members[name]] = q
             bonds += [(members[a], members[b]) for (a, b) in tmpl['bonds']]
+            vsites += [(members[site], kind, tuple(members[p] for p in parents), weights)
+                       for (site, kind, parents, weights) in tmpl.get('sites', ())]
         residue_charge = charge.copy()
         if not self._charge_from_residue:
             for i in range(n):
@@ -385,7 +418,7 @@ class ForceField:
             partners[i].append(j)
             partners[j].append(i)
         out = dict(type=np.array(atype), charge=charge, mass=mass, sigma=np.array([s for s, _ in lj]),
-                   epsilon=np.array([e for _, e in lj]), all_bonds=np.array(bonds, dtype=np.int32).reshape(-1, 2))
+                   epsilon=np.array([e for _, e in lj]), all_bonds=np.array(bonds, dtype=np.int32).reshape(-1, 2), vsites=vsites)
         if self._gb is not None:
             out['gb'] = np.array([self._gb_of(t, q) for t, q in zip(atype, residue_charge)], dtype=np.float64).reshape(-1, 3)
         # harmonic bonds
@@ -407,11 +440,27 @@ class ForceField:
         out['angles'] = np.array([r[:3] for r in rows], dtype=np.int32).reshape(-1, 3)
         out['angle_theta0'] = np.array([r[3] for r in rows])
         out['angle_k'] = np.array([r[4] for r in rows])
-        # proper torsions i-j-k-l over every bond j-k; the same walk yields the 1-4 pairs
+        # proper torsions i-j-k-l over every bond j-k; the same walk over the exception graph yields the 1-4 pairs.  In that graph a
+        # virtual site counts as bonded to its first parent and to nothing else (the M of a four-site water: 1-2 with O, 1-3 with H)
+        xbonds = bonds + [(site, parents[0]) for (site, _, parents, _) in vsites]
+        xpartners = [list(p) for p in partners]
+        for (i, j) in xbonds[len(bonds):]:
+            xpartners[i].append(j)
+            xpartners[j].append(i)
         rows, one_four = [], set()
-        excluded = set((min(i, j), max(i, j)) for (i, j) in bonds)
+        excluded = set((min(i, j), max(i, j)) for (i, j) in xbonds)
         for j in range(n):
-            excluded.update((min(a, b), max(a, b)) for a, b in itertools.combinations(partners[j], 2))
+            excluded.update((min(a, b), max(a, b)) for a, b in itertools.combinations(xpartners[j], 2))
+        for (j, k) in xbonds:
+            for i in xpartners[j]:
+                if i == k:
+                    continue
+                for l in xpartners[k]:
+                    if l == j or l == i:
+                        continue
+                    pair = (min(i, l), max(i, l))
+                    if pair not in excluded:
+                        one_four.add(pair)
         for (j, k) in bonds:
             for i in partners[j]:
                 if i == k:
@@ -419,9 +468,6 @@ class ForceField:
                 for l in partners[k]:
                     if l == j or l == i:
                         continue
-                    pair = (min(i, l), max(i, l))
-                    if pair not in excluded:
-                        one_four.add(pair)
                     v = self._lookup(self._propers, (atype[i], atype[j], atype[k], atype[l]), (cls[i], cls[j], cls[k], cls[l]))
                     if v is not None:
                         rows += [(i, j, k, l, per, phase, kk) for (per, phase, kk) in v[0]]
@@ -457,14 +503,19 @@ class ForceField:
         if box is not None:
             system.setDefaultPeriodicBoxVectors(*[tuple(v) for v in box._value])
         # constraints: rigid three-site waters (both bonds + the H-H distance), then bonds to hydrogens
-        is_h = d['mass'] < 1.5
+        kinds = {'average2': TwoParticleAverageSite, 'average3': ThreeParticleAverageSite, 'outOfPlane': OutOfPlaneSite}
+        for site, kind, parents, weights in d['vsites']:
+            system.setVirtualSite(site, kinds[kind](*parents, *weights))
+        is_h = (d['mass'] < 1.5) & (d['mass'] > 0)              # (a massless virtual site is no hydrogen)
         r0_of = {}
         for (i, j), r0 in zip(d['bonds'], d['bond_r0']):
             r0_of[(int(i), int(j))] = r0_of[(int(j), int(i))] = float(r0)
         constrained, dropped_angles = set(), set()
         if rigidWater:
-            size_of = {res.index: len(res) for res in topology.residues()}
             res_of = [a.residue.index for a in topology.atoms()]
+            size_of = {res.index: len(res) for res in topology.residues()}          # (atoms of the residue without its virtual sites)
+            for site, _, _, _ in d['vsites']:
+                size_of[res_of[site]] -= 1
             for idx, ((i, j, k), theta0) in enumerate(zip(d['angles'].tolist(), d['angle_theta0'])):
                 water = is_h[i] and is_h[k] and not is_h[j] and res_of[i] == res_of[j] == res_of[k] and size_of[res_of[j]] == 3
                 if water and (i, j) in r0_of and (k, j) in r0_of:

@@ -569,6 +569,44 @@ int amm_mol_define(amm_ctx *ctx, const int32_t *h_ptr, const int32_t *h_atoms, i
  * molecule of up to 8 atoms, one wavefront per longer one); counts as amm_positions_changed. */
 int amm_mol_scale(amm_ctx *ctx, double *d_x, double *d_x_saved, const double scale[3]);
 
+/* ---- virtual sites and massless particles ------------------------------------------------------ */
+/* System.setVirtualSite of OpenMM: a particle of mass 0 whose position is a function of up to three parents (the M site of TIP4P-class
+ * water, the lone pairs of TIP5P or of a ligand).  csrc/vsite.hip; DESIGN.md section 3.VS.
+ *   AMM_VSITE_AVERAGE2      TwoParticleAverageSite     s = w1 r1 + w2 r2                            weights (w1, w2, -)
+ *   AMM_VSITE_AVERAGE3      ThreeParticleAverageSite   s = w1 r1 + w2 r2 + w3 r3                    weights (w1, w2, w3)
+ *   AMM_VSITE_OUT_OF_PLANE  OutOfPlaneSite             s = r1 + w12 r12 + w13 r13 + wc (r12 x r13)  weights (w12, w13, wCross)
+ * with r12 = r2 - r1, r13 = r3 - r1 taken as plain differences (no minimum image: the parents of a site belong to one molecule, and
+ * molecules are never split across the box).  LocalCoordinatesSite is not offered.
+ * amm_vsite_define: h_site[n_sites] the sites' atom indices, h_kind[n_sites], h_parents[3 n_sites] (a site of two parents pads with
+ * -1), h_weights[3 n_sites].  Refused: an index out of range, an atom that is a site twice, a parent that is a site, a parent named
+ * twice, an unknown kind, a weight that is not finite.  Replaces an earlier definition (waits for the stream); n_sites = 0 removes it.
+ * amm_vsite_place: d_x [n][3], sites <- their parents; one launch over the sites, fp64 without contraction.  Other rows are not read
+ *   or written.  No-op without sites.
+ * amm_vsite_spread: the force each site collected in d_f goes to its parents (J^T f at the positions d_x) and the site's row becomes
+ *   0: average sites f_k += w_k f; out-of-plane f2 += w12 f + wc (r13 x f), f3 += w13 f + wc (f x r12), f1 += f - those two.
+ *   Owner-computes: one lane per parent atom adds its (site, role) entries in the order of the sites -- no atomics, the same bits
+ *   from run to run; the rows of the sites are zeroed by a second launch.  No-op without sites.
+ * While sites are defined, amm_run_ops (a) places them after every op that writes the bound positions (MOVE, STOCK, CONSTRAIN_X,
+ * EXPR / COPY / COMBINE into them), as amm_move / amm_copy / amm_expr_eval do when they write the bound buffer; the displacement
+ * check of the launch that moved the atoms has not seen the sites' new positions, so the neighbour lists run their own check;
+ * (b) spreads a group's buffer after every EVAL; (c) runs every op on its own: no fusion rule and no epilogue plan applies.
+ * amm_force_eval neither places nor spreads: its caller does.
+ * Massless particles (sites or not) are skipped by what integrates: AMM_OP_KICK, AMM_OP_BATH's Ornstein-Uhlenbeck step and
+ * AMM_OP_STOCK leave their rows as they are, and AMM_OP_EXPR / amm_expr_eval leave the destination of their degrees of freedom
+ * unwritten and add nothing to its sum (OpenMM's computePerDof / computeSum rule).  The Nose-Hoover-Langevin, isokinetic and
+ * regulated baths and kicks do not know them.  Nor do the FUSED launches of amm_run_ops (the inner loop, the pair kernels' epilogues,
+ * kicks carried by a gather: they divide by every mass, and a massless row becomes NaN): the library keeps them out by itself only
+ * while sites are defined -- a caller whose mass array holds a zero without any site calls amm_set_fuse_inner(ctx, 0), as the
+ * engine does, and must not switch it back on.
+ * amm_vsite_stats: out[0] = amm_vsite_place launches, out[1] = spreads (two launches each), out[2] = kernel launches of both,
+ * out[3] = sites defined; counted since the last amm_vsite_define. */
+enum { AMM_VSITE_AVERAGE2 = 0, AMM_VSITE_AVERAGE3 = 1, AMM_VSITE_OUT_OF_PLANE = 2 };
+int amm_vsite_define(amm_ctx *ctx, int32_t n_sites, const int32_t *h_site, const int32_t *h_kind, const int32_t *h_parents,
+                     const double *h_weights);
+int amm_vsite_place(amm_ctx *ctx, double *d_x);
+int amm_vsite_spread(amm_ctx *ctx, const double *d_x, double *d_f);
+int amm_vsite_stats(amm_ctx *ctx, int64_t out[4]);
+
 /* ---- energy minimisation --------------------------------------------------------------------- */
 /* LocalEnergyMinimizer::minimize(context, tolerance, maxIterations) of OpenMM, which the reference reaches through
  * app.Simulation.minimizeEnergy (the line every AtomsMM script runs before simulation.step): OpenMM runs L-BFGS on the host over
