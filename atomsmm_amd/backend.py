@@ -59,6 +59,7 @@ EXPORTS = [
     'amm_compound_create', 'amm_compound_set_globals', 'amm_compound_set_params', 'amm_compound_set_weights', 'amm_compound_release',
     'amm_run_rule_stats',
     'amm_gb_create', 'amm_gb_set_params', 'amm_gb_born_radii', 'amm_gb_release',
+    'amm_cmap_create', 'amm_cmap_set_params', 'amm_cmap_release',
     'amm_vsite_define', 'amm_vsite_place', 'amm_vsite_spread', 'amm_vsite_stats',
 ]
 
@@ -196,6 +197,9 @@ def lib():
         L.amm_gb_set_params.argtypes = [vp, C.c_int32, dp, dp, dp, C.c_double, C.c_double, C.c_double, C.c_double]
         L.amm_gb_born_radii.argtypes = [vp, C.c_int32, vp, dp]
         L.amm_gb_release.argtypes = [vp, C.c_int32]
+        L.amm_cmap_create.argtypes = [vp, C.c_int32, ip, dp, ip, ip, C.c_int32, C.c_int32, ip]
+        L.amm_cmap_set_params.argtypes = [vp, C.c_int32, dp, ip, C.c_int32, C.c_int32]
+        L.amm_cmap_release.argtypes = [vp, C.c_int32]
         L.amm_cv_create.argtypes = [vp, ip, C.c_int32, C.c_int32, ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip]
         L.amm_cv_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
         L.amm_cv_set_variables.argtypes = [vp, C.c_int32, dp, C.c_int32]
@@ -347,6 +351,7 @@ class HipContext:
         if world > 1:
             _chk(L.amm_set_slice(self.h, rank, world))
         self._keep = []
+        self._cmap_doubles = {}         # CMAP force id -> number of coefficients it was created with (amm_cmap_set_params reads as many)
 
     def close(self):
         """Release the context (and its RCCL communicator) NOW.  Idempotent.  Contexts still open when the interpreter exits are
@@ -572,6 +577,34 @@ class HipContext:
     def gb_release(self, fid):
         """Free a generalized-Born force (its id is retired)."""
         _chk(lib().amm_gb_release(self.h, fid))
+
+    def cmap_create(self, sizes, coeffs, map_of_term, idx, periodic=False):
+        """A CMAPTorsionForce (csrc/cmap.hip): the grid size of every map, the bicubic coefficients of all maps concatenated
+        (tables.cmap_coefficients: 16 per cell), the map of every term and its eight atoms (n_terms x 8)."""
+        s_, sp = _hi(sizes if len(sizes) else [0])
+        c_, cp = _hd(coeffs if len(coeffs) else [0.0])
+        assert len(coeffs) == 0 or c_.size == 16 * int(sum(int(k) * int(k) for k in sizes))
+        m_, mp = _hi(map_of_term if len(map_of_term) else [0])
+        idx_ = np.asarray(idx, dtype=np.int32).reshape(-1, 8)
+        assert len(idx_) == len(map_of_term)
+        ix_, ixp = _hi(idx_ if idx_.size else [0])
+        fid = C.c_int32(-1)
+        _chk(lib().amm_cmap_create(self.h, len(sizes), sp, cp, mp, ixp, len(idx_), int(bool(periodic)), C.byref(fid)))
+        self._cmap_doubles[fid.value] = len(coeffs)
+        return fid.value
+
+    def cmap_set_params(self, fid, coeffs, map_of_term, n_maps):
+        """All coefficients and all map indices again (updateParametersInContext): same maps, sizes and terms."""
+        c_, cp = _hd(coeffs if len(coeffs) else [0.0])
+        m_, mp = _hi(map_of_term if len(map_of_term) else [0])
+        made_with = self._cmap_doubles.get(fid)
+        if made_with is not None and len(coeffs) != made_with:
+            raise HipError('cmap_set_params: %d coefficients given, the force was created with %d' % (len(coeffs), made_with))
+        _chk(lib().amm_cmap_set_params(self.h, fid, cp, mp, int(n_maps), len(map_of_term)))
+
+    def cmap_release(self, fid):
+        """Free a CMAP force (its id is retired)."""
+        _chk(lib().amm_cmap_release(self.h, fid))
 
     def cv_create(self, inner_ids, n_deriv, code, consts, globals_):
         """A CustomCVForce with any energy text (csrc/cv.hip): the ids of the inner forces in the order of the collective variables

@@ -38,8 +38,15 @@ static bool is_gb(amm_ctx *ctx, int id, const char *wanted) {
     amm_set_error(std::string("not ") + wanted + ": force " + std::to_string(id) + " is a generalized-Born force (AMM_FORCE_GB: amm_gb_*)");
     return true;
 }
+// ... and an id of a CMAP force
+static bool is_cmap(amm_ctx *ctx, int id, const char *wanted) {
+    if (!(ctx && id >= 0 && id < (int)ctx->forces.size() && ctx->forces[id].type == AMM_FORCE_CMAP)) return false;
+    amm_set_error(std::string("not ") + wanted + ": force " + std::to_string(id) + " is a CMAP force (AMM_FORCE_CMAP: amm_cmap_*)");
+    return true;
+}
 static PairForce *get_pair(amm_ctx *ctx, int id) {
-    if (is_cv(ctx, id, "a pair force") || is_compound(ctx, id, "a pair force") || is_gb(ctx, id, "a pair force")) return nullptr;
+    if (is_cv(ctx, id, "a pair force") || is_compound(ctx, id, "a pair force") || is_gb(ctx, id, "a pair force") || is_cmap(ctx, id, "a pair force"))
+        return nullptr;
     if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_PAIR) {
         amm_set_error("invalid pair force id");
         return nullptr;
@@ -51,7 +58,9 @@ static BondedSet *get_bonded(amm_ctx *ctx, int id) {
         amm_set_error("not a bond-list set: force " + std::to_string(id) + " is a term-expression force (amm_term_expr_*)");
         return nullptr;
     }
-    if (is_cv(ctx, id, "a bond-list set") || is_compound(ctx, id, "a bond-list set") || is_gb(ctx, id, "a bond-list set")) return nullptr;
+    if (is_cv(ctx, id, "a bond-list set") || is_compound(ctx, id, "a bond-list set") || is_gb(ctx, id, "a bond-list set") ||
+        is_cmap(ctx, id, "a bond-list set"))
+        return nullptr;
     if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_BONDED) {
         amm_set_error("invalid bonded force id");
         return nullptr;
@@ -71,6 +80,7 @@ int amm_force_eval_dispatch(amm_ctx *ctx, int force_id, const double *d_pos, dou
     if (f.type == AMM_FORCE_CV) return amm_cv_eval_impl(ctx, f.cv, d_pos, d_force, accumulate, d_energy);
     if (f.type == AMM_FORCE_COMPOUND) return amm_compound_eval_impl(ctx, f.compound, d_pos, d_force, accumulate, d_energy);
     if (f.type == AMM_FORCE_GB) return amm_gb_eval_impl(ctx, f.gb, d_pos, d_force, accumulate, d_energy);
+    if (f.type == AMM_FORCE_CMAP) return amm_cmap_eval_impl(ctx, f.cmap, d_pos, d_force, accumulate, d_energy);
     return amm_bonded_eval_impl(ctx, f.bonded, d_pos, d_force, accumulate, d_energy);
 }
 
@@ -161,6 +171,7 @@ int amm_destroy(amm_ctx *ctx) {
         if (f.cv) amm_cv_free(f.cv);
         if (f.compound) amm_compound_free(f.compound);
         if (f.gb) amm_gb_free(f.gb);
+        if (f.cmap) amm_cmap_free(f.cmap);
     }
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
     if (ctx->d_expr_part) (void)hipFree(ctx->d_expr_part);
@@ -993,7 +1004,8 @@ int amm_bonded_release(amm_ctx *ctx, int32_t force_id) {
 }
 
 static TermExprForce *get_term_expr(amm_ctx *ctx, int id, const char *who) {
-    if (is_cv(ctx, id, "a term-expression force") || is_compound(ctx, id, "a term-expression force") || is_gb(ctx, id, "a term-expression force"))
+    if (is_cv(ctx, id, "a term-expression force") || is_compound(ctx, id, "a term-expression force") || is_gb(ctx, id, "a term-expression force") ||
+        is_cmap(ctx, id, "a term-expression force"))
         return nullptr;
     if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_TERM_EXPR) {
         amm_set_error(std::string(who) + ": not a term-expression force id");
@@ -1154,6 +1166,7 @@ int amm_cv_release(amm_ctx *ctx, int32_t force_id) {
 }
 
 static CompoundForce *get_compound(amm_ctx *ctx, int id, const char *who) {
+    if (is_cmap(ctx, id, "a compound-bond force")) return nullptr;
     if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_COMPOUND) {
         amm_set_error(std::string(who) + ": not the id of a compound-bond force (AMM_FORCE_COMPOUND)");
         return nullptr;
@@ -1271,6 +1284,51 @@ int amm_gb_release(amm_ctx *ctx, int32_t force_id) {
     return 0;
 }
 
+static CmapForce *get_cmap(amm_ctx *ctx, int id, const char *who) {
+    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_CMAP) {
+        amm_set_error(std::string(who) + ": not the id of a CMAP force (AMM_FORCE_CMAP)");
+        return nullptr;
+    }
+    return ctx->forces[id].cmap;
+}
+
+// CMAPTorsionForce (csrc/cmap.hip): addMap x n_maps as the bicubic coefficients of atomsmm_amd/tables.py (cmap_coefficients),
+// addTorsion x n_terms as a map index and eight atoms each
+int amm_cmap_create(amm_ctx *ctx, int32_t n_maps, const int32_t *h_sizes, const double *h_coeffs, const int32_t *h_map_of_term,
+                    const int32_t *h_idx, int32_t n_terms, int32_t periodic, int32_t *force_id) {
+    if (!ctx || !force_id || (n_maps > 0 && (!h_sizes || !h_coeffs)) || (n_terms > 0 && (!h_map_of_term || !h_idx))) {
+        amm_set_error("amm_cmap_create: null argument");
+        return 1;
+    }
+    CmapForce *cm = nullptr;
+    if (amm_cmap_create_impl(ctx, n_maps, h_sizes, h_coeffs, h_map_of_term, h_idx, n_terms, periodic, &cm)) return 1;
+    ForceObj fo;
+    fo.type = AMM_FORCE_CMAP;
+    fo.cmap = cm;
+    ctx->forces.push_back(fo);
+    *force_id = (int32_t)ctx->forces.size() - 1;
+    return 0;
+}
+
+int amm_cmap_set_params(amm_ctx *ctx, int32_t force_id, const double *h_coeffs, const int32_t *h_map_of_term, int32_t n_maps, int32_t n_terms) {
+    CmapForce *cm = get_cmap(ctx, force_id, "amm_cmap_set_params");
+    return cm ? amm_cmap_set_params_impl(ctx, cm, h_coeffs, h_map_of_term, n_maps, n_terms) : 1;
+}
+
+int amm_cmap_release(amm_ctx *ctx, int32_t force_id) {
+    CmapForce *cm = get_cmap(ctx, force_id, "amm_cmap_release");
+    if (!cm) return 1;
+    AMM_HIP(hipStreamSynchronize(ctx->stream));            // nothing in flight may still read it
+    for (int g = 0; g < AMM_MAX_GROUPS; ++g) {
+        std::vector<int> &m = ctx->groups[g].forces;
+        m.erase(std::remove(m.begin(), m.end(), (int)force_id), m.end());
+    }
+    amm_cmap_free(cm);
+    ctx->forces[force_id].cmap = nullptr;
+    ctx->forces[force_id].type = AMM_FORCE_RELEASED;
+    return 0;
+}
+
 int amm_pme_create(amm_ctx *ctx, double alpha, int32_t nx, int32_t ny, int32_t nz, double Kc, const double *h_q,
                    int32_t *force_id) {
     if (!ctx || !h_q || !force_id) {
@@ -1294,7 +1352,7 @@ int amm_pme_create(amm_ctx *ctx, double alpha, int32_t nx, int32_t ny, int32_t n
 }
 
 static PmeForce *get_pme(amm_ctx *ctx, int id) {
-    if (is_cv(ctx, id, "a PME force") || is_compound(ctx, id, "a PME force") || is_gb(ctx, id, "a PME force")) return nullptr;
+    if (is_cv(ctx, id, "a PME force") || is_compound(ctx, id, "a PME force") || is_gb(ctx, id, "a PME force") || is_cmap(ctx, id, "a PME force")) return nullptr;
     if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_PME) {
         amm_set_error("not a PME force id");
         return nullptr;

@@ -247,8 +247,9 @@ struct TermExprForce; // term_expr_vm.h: bond / angle / torsion / external terms
 struct CvForce;       // cv.hip: a CustomCVForce -- K inner forces and the compiled outer text over their energies
 struct CompoundForce; // compound.hip: a CustomCompoundBondForce / CustomCentroidBondForce -- bonds over several particles or centres
 struct GbForce;       // gb.hip: a GBSAOBCForce -- generalized-Born (OBC2) implicit solvent with a surface-area term, free space only
+struct CmapForce;     // cmap.hip: a CMAPTorsionForce -- bicubic maps over pairs of dihedrals
 enum : int { AMM_FORCE_RELEASED = 0, AMM_FORCE_PAIR = 1, AMM_FORCE_BONDED = 2, AMM_FORCE_PME = 3, AMM_FORCE_TERM_EXPR = 4, AMM_FORCE_CV = 5,
-             AMM_FORCE_COMPOUND = 6, AMM_FORCE_GB = 7 };   // ForceObj::type
+             AMM_FORCE_COMPOUND = 6, AMM_FORCE_GB = 7, AMM_FORCE_CMAP = 8 };   // ForceObj::type
 struct ForceObj {
     int type = AMM_FORCE_RELEASED;
     PairForce *pair = nullptr;
@@ -258,6 +259,7 @@ struct ForceObj {
     CvForce *cv = nullptr;
     CompoundForce *compound = nullptr;
     GbForce *gb = nullptr;
+    CmapForce *cmap = nullptr;
 };
 
 struct ExprDef {
@@ -568,6 +570,12 @@ int amm_gb_set_params_impl(amm_ctx *ctx, GbForce *gb, const double *h_q, const d
 int amm_gb_eval_impl(amm_ctx *ctx, GbForce *gb, const double *d_pos, double *d_force, int accumulate, double *d_energy);
 int amm_gb_born_radii_impl(amm_ctx *ctx, GbForce *gb, const double *d_pos, double *h_out);
 void amm_gb_free(GbForce *gb);
+// cmap.hip: a force of type AMM_FORCE_CMAP (h_coeffs: 16 doubles per cell, the maps concatenated; h_idx: n_terms x 8)
+int amm_cmap_create_impl(amm_ctx *ctx, int n_maps, const int32_t *h_sizes, const double *h_coeffs, const int32_t *h_map_of_term,
+                         const int32_t *h_idx, int n_terms, int periodic, CmapForce **out);
+int amm_cmap_set_params_impl(amm_ctx *ctx, CmapForce *cm, const double *h_coeffs, const int32_t *h_map_of_term, int n_maps, int n_terms);
+int amm_cmap_eval_impl(amm_ctx *ctx, CmapForce *cm, const double *d_pos, double *d_force, int accumulate, double *d_energy);
+void amm_cmap_free(CmapForce *cm);
 // implemented in pair.hip / cells.hip / bonded.hip / integrate.hip
 int amm_pair_build_consts(const amm_pair_desc &d, PairConsts &pc);
 int amm_pair_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double *d_force, int accumulate,

@@ -115,6 +115,7 @@ static const char *cv_type_name(int type) {
     case AMM_FORCE_PME: return "a reciprocal-space force";
     case AMM_FORCE_CV: return "a collective-variable force (AMM_FORCE_CV)";
     case AMM_FORCE_GB: return "a generalized-Born force (AMM_FORCE_GB)";
+    case AMM_FORCE_CMAP: return "a CMAP force (AMM_FORCE_CMAP)";
     default: return "a force of an unknown type";
     }
 }

@@ -249,6 +249,7 @@ class _Entry:
         self.compound = None        # a CustomCompoundBondForce / CustomCentroidBondForce (csrc/compound.hip): dict(id, variables, centroid);
                                     # the id is also in term_ids, term_expr is set, `program` is that of expr.compile_compound
         self.gb = None              # a GBSAOBCForce (csrc/gb.hip): its backend id, which is also in term_ids
+        self.cmap = None            # a CMAPTorsionForce (csrc/cmap.hip): its backend id, which is also in term_ids
 
 
 def slice_bounds(n_items, rank, world):
@@ -718,6 +719,10 @@ class Engine:
             self._translate_cv(force, entry)
         elif isinstance(force, mm.GBSAOBCForce):
             self._translate_gb(force, entry)
+        elif isinstance(force, mm.CMAPTorsionForce):
+            self._translate_cmap(force, entry)
+        elif isinstance(force, mm.RBTorsionForce):
+            self._translate_rb(force, entry)
         elif self._translate_bond_list_force(force, entry):
             pass
         else:
@@ -1603,6 +1608,76 @@ class Engine:
                 return 'values'
             entry.update = update
             entry.depends = depends
+
+    RB_TEXT = 'c0 + cp*(c1 + cp*(c2 + cp*(c3 + cp*(c4 + cp*c5)))); cp = -cos(theta)'
+
+    def _translate_rb(self, force, entry):
+        """An RBTorsionForce: sum_n c_n cos(psi)^n with cos(psi) = -cos(phi), lowered to the torsion text RB_TEXT with the six
+        per-torsion parameters c0 .. c5 on the term-expression kernel (_translate_term_expression): no kernel of its own."""
+        if self.world > 1:
+            raise NotImplementedError('RBTorsionForce runs on a single rank')
+        if force.usesPeriodicBoundaryConditions() and self.free_space:
+            raise InputError('RBTorsionForce uses periodic boundary conditions in a System in free space')
+        text = mm.CustomTorsionForce(self.RB_TEXT)
+        for k in range(6):
+            text.addPerTorsionParameter('c%d' % k)
+
+        def restate():
+            rows = [[r[0], r[1], r[2], r[3], list(r[4:])] for r in force._torsions]
+            if any(not 0 <= a < self.n for r in rows for a in r[:4]):
+                raise mm.OpenMMException('RBTorsionForce: a particle index is out of range')
+            text._torsions = rows
+            text.setUsesPeriodicBoundaryConditions(force.usesPeriodicBoundaryConditions())
+        restate()
+        self._translate_term_expression(text, entry)
+        upload = entry.reload
+
+        def reload():          # updateParametersInContext: the coefficients are read again
+            restate()
+            return upload()
+        entry.reload = reload
+
+    def _translate_cmap(self, force, entry):
+        """A CMAPTorsionForce: every map as the 16 coefficients per cell of tables.cmap_coefficients, every torsion as a map index and
+        eight atoms, evaluated with one lane per torsion by the CMAP kernels (csrc/cmap.hip).  One backend force carried in
+        entry.term_ids, so every loop over an entry's forces reaches it and the scheduler's fusion rules decline its group, as they
+        do for a term-expression force."""
+        cls = 'CMAPTorsionForce'
+        if self.world > 1:
+            raise NotImplementedError('%s runs on a single rank' % cls)
+        periodic = bool(force.usesPeriodicBoundaryConditions())
+        if periodic and self.free_space:
+            raise InputError('%s uses periodic boundary conditions in a System in free space' % cls)
+
+        def tables():
+            sizes = np.array([size for size, _ in force._maps], dtype=np.int32)
+            coeffs = [T.cmap_coefficients(size, energy).reshape(-1) for size, energy in force._maps]
+            coeffs = np.concatenate(coeffs) if coeffs else np.zeros(0)
+            rows = np.array(force._torsions, dtype=np.int32).reshape(-1, 9)
+            if len(rows) and (rows[:, 0].min() < 0 or rows[:, 0].max() >= len(sizes)):
+                raise mm.OpenMMException('%s: a map index is out of range' % cls)
+            if len(rows) and (rows[:, 1:].min() < 0 or rows[:, 1:].max() >= self.n):
+                raise mm.OpenMMException('%s: a particle index is out of range' % cls)
+            return sizes, coeffs, np.ascontiguousarray(rows[:, 0]), np.ascontiguousarray(rows[:, 1:])
+
+        sizes, coeffs, maps, idx = tables()
+        fid = self.ctx.cmap_create(sizes, coeffs, maps, idx, periodic=periodic)
+        entry.term_ids.append(fid)
+        entry.cmap = fid
+
+        def reload():          # updateParametersInContext: the maps' values and the torsions' map indices are read again
+            fresh_sizes, fresh_coeffs, fresh_maps, fresh_idx = tables()
+            if len(fresh_sizes) != len(sizes):
+                raise mm.OpenMMException('updateParametersInContext: the number of maps has changed')
+            if not np.array_equal(fresh_sizes, sizes):
+                raise mm.OpenMMException('updateParametersInContext: the size of a map has changed')
+            if len(fresh_idx) != len(idx):
+                raise mm.OpenMMException('updateParametersInContext: the number of torsions has changed')
+            if not np.array_equal(fresh_idx, idx):
+                raise mm.OpenMMException('updateParametersInContext: the particles of a torsion have changed')
+            self.ctx.cmap_set_params(fid, fresh_coeffs, fresh_maps, len(sizes))
+            return 'values'
+        entry.reload = reload
 
     _COMPOUND_KINDS = dict(x=B.CVAR_X, y=B.CVAR_Y, z=B.CVAR_Z, distance=B.CVAR_DISTANCE, angle=B.CVAR_ANGLE, dihedral=B.CVAR_DIHEDRAL)
 

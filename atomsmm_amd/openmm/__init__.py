@@ -786,6 +786,108 @@ class PeriodicTorsionForce(Force):
         return self._periodic
 
 
+class RBTorsionForce(Force):
+    """Ryckaert-Bellemans torsions: E = sum_n c_n cos(psi)^n, n = 0 .. 5, with psi = phi - pi and phi the dihedral of
+    PeriodicTorsionForce (so cos(psi) = -cos(phi)).  Lowered to the term-expression kernel (engine.py: _translate_rb)."""
+
+    def __init__(self):
+        Force.__init__(self)
+        self._torsions = []
+        self._periodic = False
+
+    @staticmethod
+    def _row(p1, p2, p3, p4, c):
+        if len(c) != 6:
+            raise OpenMMException('RBTorsionForce: a torsion takes the six coefficients c0 .. c5 (%d given)' % len(c))
+        return [int(p1), int(p2), int(p3), int(p4)] + [float(md_value(v)) for v in c]
+
+    def addTorsion(self, particle1, particle2, particle3, particle4, c0, c1, c2, c3, c4, c5):
+        self._torsions.append(self._row(particle1, particle2, particle3, particle4, (c0, c1, c2, c3, c4, c5)))
+        return len(self._torsions) - 1
+
+    def getNumTorsions(self):
+        return len(self._torsions)
+
+    def getTorsionParameters(self, index):
+        row = self._torsions[index]
+        return row[:4] + [Quantity(v, kjmol) for v in row[4:]]
+
+    def setTorsionParameters(self, index, particle1, particle2, particle3, particle4, c0, c1, c2, c3, c4, c5):
+        self._torsions[index] = self._row(particle1, particle2, particle3, particle4, (c0, c1, c2, c3, c4, c5))
+
+    def setUsesPeriodicBoundaryConditions(self, periodic):
+        self._periodic = bool(periodic)
+
+    def usesPeriodicBoundaryConditions(self):
+        return self._periodic
+
+    def updateParametersInContext(self, context):
+        """Upload the coefficients again (the atoms and the number of torsions must not have changed)."""
+        context._engine.update_force_parameters(self)
+
+
+class CMAPTorsionForce(Force):
+    """Pairs of dihedrals (phi, psi) whose energy is read from a map over [0, 2 pi)^2 by bicubic interpolation: the tensor-product
+    periodic cubic spline through the map's values (tables.cmap_coefficients; csrc/cmap.hip).  A map of size n holds n * n values in
+    kJ/mol, energy[i + n * j] at phi = 2 pi i / n and psi = 2 pi j / n: the first angle runs fastest."""
+
+    def __init__(self):
+        Force.__init__(self)
+        self._maps = []             # [size, [size * size values]]
+        self._torsions = []         # [map, a1, a2, a3, a4, b1, b2, b3, b4]
+        self._periodic = False
+
+    @staticmethod
+    def _map(size, energy):
+        size = int(size)
+        if isinstance(energy, Quantity):
+            energy = Quantity(np.asarray(energy._value, dtype=np.float64), energy.unit)
+        energy = [float(v) for v in np.asarray(md_value(energy), dtype=np.float64).reshape(-1)]
+        if size < 2:
+            raise OpenMMException('CMAPTorsionForce: the size of a map must be at least 2')
+        if len(energy) != size * size:
+            raise OpenMMException('CMAPTorsionForce: a map of size %d takes %d energies (%d given)' % (size, size * size, len(energy)))
+        return [size, energy]
+
+    def addMap(self, size, energy):
+        self._maps.append(self._map(size, energy))
+        return len(self._maps) - 1
+
+    def getNumMaps(self):
+        return len(self._maps)
+
+    def getMapParameters(self, index):
+        size, energy = self._maps[index]
+        return [size, Quantity(list(energy), kjmol)]
+
+    def setMapParameters(self, index, size, energy):
+        self._maps[index] = self._map(size, energy)
+
+    def addTorsion(self, map, a1, a2, a3, a4, b1, b2, b3, b4):
+        self._torsions.append([int(v) for v in (map, a1, a2, a3, a4, b1, b2, b3, b4)])
+        return len(self._torsions) - 1
+
+    def getNumTorsions(self):
+        return len(self._torsions)
+
+    def getTorsionParameters(self, index):
+        return list(self._torsions[index])
+
+    def setTorsionParameters(self, index, map, a1, a2, a3, a4, b1, b2, b3, b4):
+        self._torsions[index] = [int(v) for v in (map, a1, a2, a3, a4, b1, b2, b3, b4)]
+
+    def setUsesPeriodicBoundaryConditions(self, periodic):
+        self._periodic = bool(periodic)
+
+    def usesPeriodicBoundaryConditions(self):
+        return self._periodic
+
+    def updateParametersInContext(self, context):
+        """Upload the maps' values and the torsions' map indices again.  The number of maps, a map's size, the number of torsions and
+        a torsion's atoms must not have changed."""
+        context._engine.update_force_parameters(self)
+
+
 class CustomTorsionForce(Force, _GlobalParams):
     """Torsions with any energy text in `theta`, the dihedral angle in (-pi, pi] (PeriodicTorsionForce's convention)."""
 
@@ -1629,9 +1731,11 @@ def molecules_of(system):
             pairs += [(b[0], b[1]) for b in force._bonds]
         elif isinstance(force, (HarmonicAngleForce, CustomAngleForce)):
             pairs += [(r[0], r[1]) for r in force._angles] + [(r[1], r[2]) for r in force._angles]
-        elif isinstance(force, (PeriodicTorsionForce, CustomTorsionForce)):
+        elif isinstance(force, (PeriodicTorsionForce, CustomTorsionForce, RBTorsionForce)):
             pairs += [(r[0], r[1]) for r in force._torsions] + [(r[1], r[2]) for r in force._torsions] + \
                      [(r[2], r[3]) for r in force._torsions]
+        elif isinstance(force, CMAPTorsionForce):              # both dihedrals of every term, each as a torsion
+            pairs += [(r[k], r[k + 1]) for r in force._torsions for k in (1, 2, 3, 5, 6, 7)]
         elif isinstance(force, CustomCompoundBondForce):       # consecutive particles, as an angle or torsion (a centroid bond joins nothing)
             pairs += [(a, b) for members, _ in force._bonds for a, b in zip(members[:-1], members[1:])]
     # (a virtual site belongs to the molecule of its parents, as in OpenMM's getMolecules)

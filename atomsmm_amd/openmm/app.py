@@ -11,18 +11,20 @@ tests/test_systems.py:12-19, tests/test_propagators.py:12-17):
 This module provides them for the subset of the two file formats the reference's data uses: PDB `CRYST1` /
 `ATOM` / `HETATM` / `CONECT` records with an orthorhombic cell, and force-field XML with `AtomTypes`, `Residues`
 (templates matched by residue name and atom names), `HarmonicBondForce`, `HarmonicAngleForce`,
-`PeriodicTorsionForce` (`Proper` / `Improper`, wildcard types) and `NonbondedForce` (`coulomb14scale`,
+`PeriodicTorsionForce` (`Proper` / `Improper`, wildcard types), `RBTorsionForce` (`Proper`), `CMAPTorsionForce` (`Map`, `Torsion`
+over chains of five bonded atoms) and `NonbondedForce` (`coulomb14scale`,
 `lj14scale`, charges from the residue templates or from the `Atom` entries).  No arithmetic happens here: the result is
 a `System` of the object model in `atomsmm_amd.openmm`, evaluated by the HIP path once a `Context` is created.
 """
 import itertools
+import math
 import os
 import xml.etree.ElementTree as ET
 
 import numpy as np
 
-from . import (CMMotionRemover, Context, GBSAOBCForce, HarmonicAngleForce, HarmonicBondForce, NonbondedForce,  # noqa: F401
-               OutOfPlaneSite, PeriodicTorsionForce, Platform, System, ThreeParticleAverageSite, TwoParticleAverageSite, Vec3)
+from . import (CMAPTorsionForce, CMMotionRemover, Context, GBSAOBCForce, HarmonicAngleForce, HarmonicBondForce, NonbondedForce,  # noqa: F401
+               OutOfPlaneSite, PeriodicTorsionForce, Platform, RBTorsionForce, System, ThreeParticleAverageSite, TwoParticleAverageSite, Vec3)
 from .. import unit as _unit
 from ..unit import Quantity, md_value
 from ..utils import InputError
@@ -273,6 +275,8 @@ class ForceField:
         self._has_nonbonded = False
         self._charge_from_residue = False
         self._gb, self._gb_charge_from_residue = None, False        # <GBSAOBCForce>: type or ('class', c) -> (radius, scale, charge or None)
+        self._rb_propers = []                   # <RBTorsionForce>: (pattern, (c0 .. c5))
+        self._cmap_maps, self._cmap_torsions = [], []           # <CMAPTorsionForce>: (size, values as the file has them), (pattern, map)
         for f in files:
             self.loadFile(f)
 
@@ -308,6 +312,24 @@ class ForceField:
                         break
                     terms.append((int(t.get('periodicity%d' % n)), float(t.get('phase%d' % n)), float(t.get('k%d' % n))))
                 table.append((types_of(t, 4), terms))
+        for rb in root.findall('RBTorsionForce'):
+            if rb.find('Improper') is not None:
+                raise NotImplementedError('<RBTorsionForce>: <Improper> entries are not supported')
+            for t in rb.findall('Proper'):
+                self._rb_propers.append((types_of(t, 4), tuple(float(t.get('c%d' % k)) for k in range(6))))
+        for cm in root.findall('CMAPTorsionForce'):
+            first = len(self._cmap_maps)            # (the map attribute of a <Torsion> counts the <Map> children of its own section)
+            for m in cm.findall('Map'):
+                values = [float(v) for v in (m.text or '').split()]
+                size = int(round(math.sqrt(len(values))))
+                if size < 2 or size * size != len(values):
+                    raise ValueError('<CMAPTorsionForce>: a <Map> holds size*size values with a size of at least 2 (%d given)' % len(values))
+                self._cmap_maps.append((size, values))
+            for t in cm.findall('Torsion'):
+                index = first + int(t.get('map'))
+                if not first <= index < len(self._cmap_maps):
+                    raise ValueError('<CMAPTorsionForce>: a <Torsion> names map %s, which its section does not define' % t.get('map'))
+                self._cmap_torsions.append((types_of(t, 5), index))
         nb = root.find('NonbondedForce')
         if nb is not None:
             self._has_nonbonded = True
@@ -387,6 +409,39 @@ class ForceField:
                     raise ValueError('GBSAOBCForce: no charge for atom type %s (no charge attribute, no UseAttributeFromResidue)' % type_name)
                 return q, radius, scale
         raise ValueError('No GBSAOBC parameters defined for atom type %s' % type_name)
+
+    def _cmap_chains(self, partners, atype, cls):
+        """(map, a, b, c, d, e) for every chain of five atoms bonded in sequence that a <Torsion> of a <CMAPTorsionForce> matches, read
+        in the direction in which it matches: phi is then a-b-c-d and psi b-c-d-e.  Every chain is visited once; entries without a
+        wildcard are tried first."""
+        def lookup(chain):
+            types, classes = [atype[i] for i in chain], [cls[i] for i in chain]
+            for wildcard_pass in (False, True):
+                for (kind, pattern), index in self._cmap_torsions:
+                    if ('' in pattern) != wildcard_pass:
+                        continue
+                    if all(p == '' or p == k for p, k in zip(pattern, types if kind == 'type' else classes)):
+                        return index
+            return None
+
+        found = []
+        for c in range(len(partners)):
+            for b in partners[c]:
+                for d in partners[c]:
+                    if d == b:
+                        continue
+                    for a in partners[b]:
+                        if a in (c, d):
+                            continue
+                        for e in partners[d]:
+                            if e in (a, b, c) or a > e:          # (a > e: the same chain read from its other end)
+                                continue
+                            for chain in ((a, b, c, d, e), (e, d, c, b, a)):
+                                index = lookup(chain)
+                                if index is not None:
+                                    found.append((index,) + chain)
+                                    break
+        return found
 
     def describe(self, topology):
         """Match templates and tables; returns plain arrays (MD units) describing the system createSystem would build:
@@ -471,6 +526,22 @@ class ForceField:
                     v = self._lookup(self._propers, (atype[i], atype[j], atype[k], atype[l]), (cls[i], cls[j], cls[k], cls[l]))
                     if v is not None:
                         rows += [(i, j, k, l, per, phase, kk) for (per, phase, kk) in v[0]]
+        if self._rb_propers:
+            # Ryckaert-Bellemans propers: the same walk and the same look-up as the periodic ones
+            rb = []
+            for (j, k) in bonds:
+                for i in partners[j]:
+                    if i == k:
+                        continue
+                    for l in partners[k]:
+                        if l == j or l == i:
+                            continue
+                        v = self._lookup(self._rb_propers, (atype[i], atype[j], atype[k], atype[l]), (cls[i], cls[j], cls[k], cls[l]))
+                        if v is not None:
+                            rb.append((i, j, k, l) + tuple(v[0]))
+            out['rb_torsions'] = rb
+        if self._cmap_torsions:
+            out['cmap_torsions'] = self._cmap_chains(partners, atype, cls)
         out['torsions'] = np.array([r[:4] for r in rows], dtype=np.int32).reshape(-1, 4)
         out['torsion_n'] = np.array([r[4] for r in rows], dtype=np.int32)
         out['torsion_phase'] = np.array([r[5] for r in rows])
@@ -546,6 +617,20 @@ class ForceField:
             force = PeriodicTorsionForce()
             for (a, b, c, e), per, phase, kk in zip(d['torsions'].tolist(), d['torsion_n'], d['torsion_phase'], d['torsion_k']):
                 force.addTorsion(a, b, c, e, int(per), float(phase), float(kk))
+            system.addForce(force)
+        if d.get('rb_torsions'):
+            force = RBTorsionForce()
+            for row in d['rb_torsions']:
+                force.addTorsion(*row)
+            system.addForce(force)
+        if d.get('cmap_torsions'):
+            force = CMAPTorsionForce()
+            for size, values in self._cmap_maps:
+                # the file's values start at -180 degrees; CMAPTorsionForce's at 0: both indices move by half the map
+                half = size // 2
+                force.addMap(size, [values[(i + half) % size + size * ((j + half) % size)] for j in range(size) for i in range(size)])
+            for index, p1, p2, p3, p4, p5 in d['cmap_torsions']:
+                force.addTorsion(index, p1, p2, p3, p4, p2, p3, p4, p5)
             system.addForce(force)
         if self._has_nonbonded:
             nb = NonbondedForce()

@@ -80,6 +80,75 @@ def spline_eval(coef, lo, hi, t):
     return np.where(outside, 0.0, value), np.where(outside, 0.0, slope)
 
 
+def _periodic_node_slopes(y):
+    """dS/du at the nodes of the periodic cubic spline through y along axis 0, in units of the node spacing (u = node index):
+    d[k-1] + 4 d[k] + d[k+1] = 3 (y[k+1] - y[k-1]) with the indices taken modulo len(y).  The cyclic system is solved directly (the
+    sizes are tens); with two nodes both neighbours are the other node and the slopes come out 0."""
+    n = y.shape[0]
+    a = np.zeros((n, n))
+    for k in range(n):
+        a[k, k] += 4.0
+        a[k, (k - 1) % n] += 1.0
+        a[k, (k + 1) % n] += 1.0
+    return np.linalg.solve(a, 3.0 * (np.roll(y, -1, axis=0) - np.roll(y, 1, axis=0)))
+
+
+# cubic Hermite basis in monomial form: (p(0), p(1), p'(0), p'(1)) -> the coefficients of 1, u, u^2, u^3
+_HERMITE = np.array([[1.0, 0.0, 0.0, 0.0], [0.0, 0.0, 1.0, 0.0], [-3.0, 3.0, -2.0, -1.0], [2.0, -2.0, 1.0, 1.0]])
+
+
+def cmap_coefficients(size, energy):
+    """The map of a CMAPTorsionForce as the device reads it (csrc/cmap.hip): [size * size][16] coefficients, row
+    s + size * t for the cell phi in [s, s + 1) delta, psi in [t, t + 1) delta (delta = 2 pi / size), with
+
+        E = sum_ij c[4 i + j] da^i db^j,   da, db in [0, 1) the fractional positions of phi and psi within the cell.
+
+    energy[i + size * j] is the value at phi = i delta, psi = j delta.  The interpolant is the tensor-product periodic cubic spline
+    through the map (what OpenMM's CMAPTorsionForceImpl builds): dE/dphi at the nodes from the periodic spline through every row,
+    dE/dpsi from every column, d2E/dphi dpsi from the periodic spline through the dE/dphi values along psi; a cell's patch matches
+    the four quantities at its four corners.  Derivatives are in cell units here: the kernel divides by delta."""
+    size = int(size)
+    y = np.asarray(energy, dtype=np.float64).reshape(-1)
+    if size < 2 or len(y) != size * size:
+        raise ValueError('a CMAP map of size %d needs %d values, and a size of at least 2' % (size, size * size))
+    f = y.reshape(size, size).T                     # f[i, j]: phi index i, psi index j
+    fx = _periodic_node_slopes(f)                   # along phi
+    fy = _periodic_node_slopes(f.T).T               # along psi
+    fxy = _periodic_node_slopes(fx.T).T             # dE/dphi, splined along psi
+    nxt = np.arange(1, size + 1) % size
+    corner = np.empty((size, size, 4, 4))           # [s, t][(f | d/dphi) at s, s + 1][(f | d/dpsi) at t, t + 1]
+    for a, rows in enumerate((np.arange(size), nxt)):
+        for b, cols in enumerate((np.arange(size), nxt)):
+            corner[:, :, a, b] = f[np.ix_(rows, cols)]
+            corner[:, :, 2 + a, b] = fx[np.ix_(rows, cols)]
+            corner[:, :, a, 2 + b] = fy[np.ix_(rows, cols)]
+            corner[:, :, 2 + a, 2 + b] = fxy[np.ix_(rows, cols)]
+    c = np.einsum('ia,stab,jb->stij', _HERMITE, corner, _HERMITE)
+    return np.ascontiguousarray(c.transpose(1, 0, 2, 3).reshape(size * size, 16))
+
+
+def cmap_eval(coef, size, phi, psi):
+    """(E, dE/dphi, dE/dpsi) at angles in radians as k_cmap of csrc/cmap.hip takes them, operation by operation: the angle brought to
+    [0, 2 pi), u = angle / delta, the cell (int)u reduced modulo size, nested Horner.  phi, psi: numbers or arrays."""
+    coef = np.asarray(coef, dtype=np.float64).reshape(size * size, 16)
+    delta = 2.0 * np.pi / size
+
+    def cell(angle):
+        angle = np.asarray(angle, dtype=np.float64)
+        u = np.where(angle < 0.0, angle + 2.0 * np.pi, angle) / delta
+        s = u.astype(np.int64)
+        return s % size, u - s
+
+    (s, da), (t, db) = cell(phi), cell(psi)
+    c = coef[s + size * t]
+    r = [((c[..., 4 * i + 3] * db + c[..., 4 * i + 2]) * db + c[..., 4 * i + 1]) * db + c[..., 4 * i] for i in range(4)]
+    d = [(3.0 * c[..., 4 * i + 3] * db + 2.0 * c[..., 4 * i + 2]) * db + c[..., 4 * i + 1] for i in range(4)]
+    e = ((r[3] * da + r[2]) * da + r[1]) * da + r[0]
+    de_da = (3.0 * r[3] * da + 2.0 * r[2]) * da + r[1]
+    de_db = ((d[3] * da + d[2]) * da + d[1]) * da + d[0]
+    return e, de_da / delta, de_db / delta
+
+
 def kind_of(function):
     """AMM_TABLE_* of an openmm tabulated-function object."""
     return function._amm_table_kind

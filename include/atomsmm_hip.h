@@ -394,6 +394,27 @@ int amm_gb_born_radii(amm_ctx *ctx, int32_t force_id, const double *d_pos, doubl
 /* Free such a force; the id is retired and leaves every group definition. */
 int amm_gb_release(amm_ctx *ctx, int32_t force_id);
 
+/* CMAPTorsionForce (force type AMM_FORCE_CMAP; csrc/cmap.hip): a term is two dihedrals, phi over the first
+ * four of its eight atoms and psi over the last four (the dihedral of AMM_TORSION_PERIODIC, minimum image when periodic), and its
+ * energy the value at (phi, psi) of one of n_maps maps over [0, 2 pi)^2, interpolated by the tensor-product periodic cubic spline.
+ * h_sizes: n_maps grid sizes, each >= 2.  h_coeffs: the maps concatenated, 16 doubles per cell as atomsmm_amd.tables.cmap_coefficients
+ * gives them: cell (s, t) of a map is row s + size * t, and E = sum_ij c[4 i + j] da^i db^j with da, db in [0, 1) the fractional
+ * positions of phi and psi within the cell; sum size^2 * 16 doubles in all.  h_map_of_term: n_terms map indices; h_idx: n_terms x 8
+ * atom indices (an atom may appear more than once in a term).  Refused: an atom index outside [0, n), a map index outside
+ * [0, n_maps), a size below 2, periodic in a context without a box, several ranks.  The cell index is reduced modulo the size before
+ * the read, so no position indexes past a map.  An ordinary member of a group, evaluated through amm_force_eval; the amm_pair_*,
+ * amm_bonded_*, amm_term_expr_*, amm_compound_* and amm_pme_* calls and amm_cv_create refuse its id naming AMM_FORCE_CMAP.  Two
+ * launches per evaluation (terms, then one lane per atom over its records in order), no atomics: the same positions give the same
+ * bits, and the forces of an evaluation with and without energy are the same numbers. */
+int amm_cmap_create(amm_ctx *ctx, int32_t n_maps, const int32_t *h_sizes, const double *h_coeffs, const int32_t *h_map_of_term,
+                    const int32_t *h_idx, int32_t n_terms, int32_t periodic, int32_t *force_id);
+/* setMapParameters / setTorsionParameters + updateParametersInContext: all coefficients and all map indices again, laid out as at
+ * creation (same n_maps, sizes, n_terms; the atoms of a term do not change). */
+int amm_cmap_set_params(amm_ctx *ctx, int32_t force_id, const double *h_coeffs, const int32_t *h_map_of_term, int32_t n_maps,
+                        int32_t n_terms);
+/* Free such a force; the id is retired and leaves every group definition. */
+int amm_cmap_release(amm_ctx *ctx, int32_t force_id);
+
 /* Reciprocal space of a NonbondedForce with nonbondedMethod PME / Ewald, as RESPASystem and FarNonbondedForce
  * keep it in group 2 with the source force's Ewald tolerance / PME parameters (systems.py:74-75,
  * forces.py:185-188; setReciprocalSpaceForceGroup: utils.py:147-152).  Smooth PME, B-spline order 5, grid
