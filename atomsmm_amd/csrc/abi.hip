@@ -7,7 +7,6 @@
 #include "amm_ctx.h"
 #include "cluster.h"
 #include "pair_expr_vm.h"
-#include "term_expr_vm.h"
 
 int amm_pair_setup_grid(amm_ctx *ctx, PairForce *pf);
 static bool amm_family_allows_cluster(int family, int flags) {
@@ -19,70 +18,6 @@ int amm_bonded_npar(int kind);
 
 static thread_local std::string g_error;
 void amm_set_error(const std::string &msg) { g_error = msg; }
-
-// an id of a collective-variable force given to an entry point of another family: the message names the type
-static bool is_cv(amm_ctx *ctx, int id, const char *wanted) {
-    if (!(ctx && id >= 0 && id < (int)ctx->forces.size() && ctx->forces[id].type == AMM_FORCE_CV)) return false;
-    amm_set_error(std::string("not ") + wanted + ": force " + std::to_string(id) + " is a collective-variable force (AMM_FORCE_CV: amm_cv_*)");
-    return true;
-}
-// ... and an id of a compound-bond force
-static bool is_compound(amm_ctx *ctx, int id, const char *wanted) {
-    if (!(ctx && id >= 0 && id < (int)ctx->forces.size() && ctx->forces[id].type == AMM_FORCE_COMPOUND)) return false;
-    amm_set_error(std::string("not ") + wanted + ": force " + std::to_string(id) + " is a compound-bond force (AMM_FORCE_COMPOUND: amm_compound_*)");
-    return true;
-}
-// ... and an id of a generalized-Born force
-static bool is_gb(amm_ctx *ctx, int id, const char *wanted) {
-    if (!(ctx && id >= 0 && id < (int)ctx->forces.size() && ctx->forces[id].type == AMM_FORCE_GB)) return false;
-    amm_set_error(std::string("not ") + wanted + ": force " + std::to_string(id) + " is a generalized-Born force (AMM_FORCE_GB: amm_gb_*)");
-    return true;
-}
-// ... and an id of a CMAP force
-static bool is_cmap(amm_ctx *ctx, int id, const char *wanted) {
-    if (!(ctx && id >= 0 && id < (int)ctx->forces.size() && ctx->forces[id].type == AMM_FORCE_CMAP)) return false;
-    amm_set_error(std::string("not ") + wanted + ": force " + std::to_string(id) + " is a CMAP force (AMM_FORCE_CMAP: amm_cmap_*)");
-    return true;
-}
-static PairForce *get_pair(amm_ctx *ctx, int id) {
-    if (is_cv(ctx, id, "a pair force") || is_compound(ctx, id, "a pair force") || is_gb(ctx, id, "a pair force") || is_cmap(ctx, id, "a pair force"))
-        return nullptr;
-    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_PAIR) {
-        amm_set_error("invalid pair force id");
-        return nullptr;
-    }
-    return ctx->forces[id].pair;
-}
-static BondedSet *get_bonded(amm_ctx *ctx, int id) {
-    if (ctx && id >= 0 && id < (int)ctx->forces.size() && ctx->forces[id].type == AMM_FORCE_TERM_EXPR) {
-        amm_set_error("not a bond-list set: force " + std::to_string(id) + " is a term-expression force (amm_term_expr_*)");
-        return nullptr;
-    }
-    if (is_cv(ctx, id, "a bond-list set") || is_compound(ctx, id, "a bond-list set") || is_gb(ctx, id, "a bond-list set") ||
-        is_cmap(ctx, id, "a bond-list set"))
-        return nullptr;
-    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_BONDED) {
-        amm_set_error("invalid bonded force id");
-        return nullptr;
-    }
-    return ctx->forces[id].bonded;
-}
-// one force of any type (also the members of a group: run_ops.hip)
-int amm_force_eval_dispatch(amm_ctx *ctx, int force_id, const double *d_pos, double *d_force, int accumulate, double *d_energy) {
-    ForceObj &f = ctx->forces[force_id];
-    if (f.type == AMM_FORCE_RELEASED) {
-        amm_set_error("evaluation of a released force id");
-        return 1;
-    }
-    if (f.type == AMM_FORCE_PAIR) return amm_pair_eval_impl(ctx, f.pair, d_pos, d_force, accumulate, d_energy);
-    if (f.type == AMM_FORCE_PME) return amm_pme_eval_impl(ctx, f.pme, d_pos, d_force, accumulate, d_energy);
-    if (f.type == AMM_FORCE_TERM_EXPR) return amm_term_expr_eval_impl(ctx, f.term, d_pos, d_force, accumulate, d_energy);
-    if (f.type == AMM_FORCE_CV) return amm_cv_eval_impl(ctx, f.cv, d_pos, d_force, accumulate, d_energy);
-    if (f.type == AMM_FORCE_COMPOUND) return amm_compound_eval_impl(ctx, f.compound, d_pos, d_force, accumulate, d_energy);
-    if (f.type == AMM_FORCE_GB) return amm_gb_eval_impl(ctx, f.gb, d_pos, d_force, accumulate, d_energy);
-    if (f.type == AMM_FORCE_CMAP) return amm_cmap_eval_impl(ctx, f.cmap, d_pos, d_force, accumulate, d_energy);
-    return amm_bonded_eval_impl(ctx, f.bonded, d_pos, d_force, accumulate, d_energy);
-}
 
 template <typename T>
 static int upload(T **dst, const T *src, size_t n) {
@@ -157,22 +92,7 @@ int amm_destroy(amm_ctx *ctx) {
     // (with a communicator the wait is bounded and a stuck collective is aborted: comm.hip; then the stream drains)
     amm_comm_destroy_impl(ctx);
     (void)hipStreamSynchronize(ctx->stream);
-    for (auto &f : ctx->forces) {
-        if (f.pair) {
-            amm_pair_free(f.pair);
-            delete f.pair;
-        }
-        if (f.bonded) {
-            amm_bonded_free(f.bonded);
-            delete f.bonded;
-        }
-        if (f.pme) amm_pme_free(f.pme);
-        if (f.term) amm_term_expr_free(f.term);
-        if (f.cv) amm_cv_free(f.cv);
-        if (f.compound) amm_compound_free(f.compound);
-        if (f.gb) amm_gb_free(f.gb);
-        if (f.cmap) amm_cmap_free(f.cmap);
-    }
+    for (auto &f : ctx->forces) amm_family(f.type).free(f.obj);
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
     if (ctx->d_expr_part) (void)hipFree(ctx->d_expr_part);
     if (ctx->d_fscratch) (void)hipFree(ctx->d_fscratch);
@@ -198,15 +118,16 @@ int amm_set_slice(amm_ctx *ctx, int32_t rank, int32_t world) {
         return 1;
     }
     for (auto &f : ctx->forces) {
-        if (f.pair && f.pair->free_space && world > 1) {
+        const PairForce *pf = f.pair();
+        if (pf && pf->free_space && world > 1) {
             amm_set_error("amm_set_slice: a free-space pair force runs on a single rank");
             return 1;
         }
-        if (f.gb && world > 1) {
-            amm_set_error("amm_set_slice: a generalized-Born force (AMM_FORCE_GB) runs on a single rank");
+        if (amm_family(f.type).single_rank && world > 1) {
+            amm_set_error(std::string("amm_set_slice: ") + amm_family(f.type).noun + " (" + amm_family(f.type).tag + ") runs on a single rank");
             return 1;
         }
-        if (f.pair && f.pair->built) {
+        if (pf && pf->built) {
             amm_set_error("amm_set_slice must be called before the first force evaluation");
             return 1;
         }
@@ -227,7 +148,7 @@ int amm_check(amm_ctx *ctx) {
         return 2;
     }
     for (size_t id = 0; id < ctx->forces.size(); ++id) {
-        PairForce *pf = ctx->forces[id].pair;
+        PairForce *pf = ctx->forces[id].pair();
         if (pf && pf->cl && pf->cl->built) {
             int cf[8];
             AMM_HIP(hipMemcpy(cf, pf->cl->d_flags, sizeof(cf), hipMemcpyDeviceToHost));
@@ -342,11 +263,11 @@ static int pair_create_common(amm_ctx *ctx, const amm_pair_desc *desc, const dou
     pf->free_space = free_space;
     if (ctx->n >= (1 << 26)) {      // the traversal addresses the sorted copies with 32-bit byte offsets (32 B per slot)
         amm_set_error("amm_pair_create: more than 2^26 atoms are not supported");
-        delete pf;
+        amm_pair_free(pf);
         return 1;
     }
     if (amm_pair_build_consts(*desc, pf->pc) || (!free_space && amm_pair_build_table(pf))) {
-        delete pf;
+        amm_pair_free(pf);
         return 1;
     }
     const int n = ctx->n;
@@ -358,7 +279,7 @@ static int pair_create_common(amm_ctx *ctx, const amm_pair_desc *desc, const dou
         std::memset(&pf->grid, 0, sizeof(pf->grid));
         std::vector<int> ptr, idx;
         if (amm_excl_csr(n, h_excl, n_excl, ptr, idx)) {
-            delete pf;
+            amm_pair_free(pf);
             return 1;
         }
         // (the kernel reads the charges and one (sigma/2, 2 sqrt(eps)) record per atom: no separate sigma / epsilon arrays)
@@ -366,15 +287,9 @@ static int pair_create_common(amm_ctx *ctx, const amm_pair_desc *desc, const dou
             hipMalloc(&pf->d_q, sizeof(double) * n) != hipSuccess || hipMalloc(&pf->d_lj_s, sizeof(double2) * n) != hipSuccess) {
             amm_set_error("amm_pair_create: device allocation failed");
             amm_pair_free(pf);
-            delete pf;
             return 1;
         }
-        ForceObj fo;
-        fo.type = AMM_FORCE_PAIR;
-        fo.pair = pf;
-        ctx->forces.push_back(fo);
-        *force_id = (int)ctx->forces.size() - 1;
-        pf->id = *force_id;
+        *force_id = pf->id = amm_force_register(ctx, AMM_FORCE_PAIR, pf);
         return amm_pair_set_params(ctx, *force_id, h_q, h_sigma, h_eps);
     }
     // default Verlet buffer: 0.1 nm on one GPU (C3: list build 0.58 x 320 us per step against +30 % pair work at 0.2 nm);
@@ -384,18 +299,17 @@ static int pair_create_common(amm_ctx *ctx, const amm_pair_desc *desc, const dou
     pf->skin_req = skin;
     pair_derive_buffers(ctx, pf);
     if (amm_pair_setup_grid(ctx, pf)) {
-        delete pf;
+        amm_pair_free(pf);
         return 1;
     }
     // exclusions -> symmetric CSR in original atom indices
     std::vector<int> ptr, idx;
     if (amm_excl_csr(n, h_excl, n_excl, ptr, idx)) {
-        delete pf;
+        amm_pair_free(pf);
         return 1;
     }
     if (upload(&pf->d_excl_ptr, ptr.data(), ptr.size()) || upload(&pf->d_excl_idx, idx.data(), idx.size())) {
         amm_pair_free(pf);
-        delete pf;
         return 1;
     }
     if (desc->family == AMM_SOFTCORE || (desc->flags & (AMM_GROUP_LJ | AMM_GROUP_Q))) {
@@ -447,12 +361,7 @@ static int pair_create_common(amm_ctx *ctx, const amm_pair_desc *desc, const dou
     AMM_HIP(hipMalloc(&pf->d_counters, sizeof(unsigned long long) * 8));
     AMM_HIP(hipMemset(pf->d_counters, 0, sizeof(unsigned long long) * 8));
     pf->expr = expr;          // (the force owns the program once it is registered: amm_pair_free)
-    ForceObj fo;
-    fo.type = AMM_FORCE_PAIR;
-    fo.pair = pf;
-    ctx->forces.push_back(fo);
-    *force_id = (int)ctx->forces.size() - 1;
-    pf->id = *force_id;
+    *force_id = pf->id = amm_force_register(ctx, AMM_FORCE_PAIR, pf);
     if (amm_pair_set_params(ctx, *force_id, h_q, h_sigma, h_eps)) return 1;
     if (pf->hybrid) {
         // the child: same particles, parameters, exclusions and Verlet buffer; its list keeps the pairs with a rest atom (code 2)
@@ -463,7 +372,7 @@ static int pair_create_common(amm_ctx *ctx, const amm_pair_desc *desc, const dou
         const int rc = amm_pair_create(ctx, desc, h_q, h_sigma, h_eps, h_excl, n_excl, pf->skin * ctx->opt_rest_skin_factor, &child_id);
         ctx->creating_rest = false;
         if (rc) return 1;
-        PairForce *child = ctx->forces[child_id].pair;
+        PairForce *child = ctx->forces[child_id].pair();
         child->hybrid_rest = true;
         child->profile_id = pf->id;
         std::vector<float> code(n, 1.0f);
@@ -543,7 +452,7 @@ int amm_pair_expr_create(amm_ctx *ctx, const amm_pair_desc *desc, const int32_t 
 }
 
 int amm_pair_expr_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal) {
-    PairForce *pf = get_pair(ctx, force_id);
+    PairForce *pf = amm_force_get<PairForce>(ctx, force_id);
     if (!pf) return 1;
     if (!pf->expr) {
         amm_set_error("amm_pair_expr_set_globals: not a pair-expression force (AMM_PAIR_EXPR)");
@@ -559,7 +468,7 @@ int amm_pair_expr_set_globals(amm_ctx *ctx, int32_t force_id, const double *glob
 
 int amm_pair_expr_set_tables(amm_ctx *ctx, int32_t force_id, int32_t n_tables, const int32_t *kinds, const int32_t *dims, const double *ranges,
                              const int32_t *offsets, const double *data, int32_t n_data) {
-    PairForce *pf = get_pair(ctx, force_id);
+    PairForce *pf = amm_force_get<PairForce>(ctx, force_id);
     if (!pf) return 1;
     if (!pf->expr) {
         amm_set_error("amm_pair_expr_set_tables: not a pair-expression force (AMM_PAIR_EXPR)");
@@ -569,7 +478,7 @@ int amm_pair_expr_set_tables(amm_ctx *ctx, int32_t force_id, int32_t n_tables, c
 }
 
 int amm_pair_set_lambda(amm_ctx *ctx, int32_t force_id, double value) {
-    PairForce *pf = get_pair(ctx, force_id);
+    PairForce *pf = amm_force_get<PairForce>(ctx, force_id);
     if (!pf) return 1;
     if (pf->expr) {
         amm_set_error("amm_pair_set_lambda: not for a pair-expression force (AMM_PAIR_EXPR): its globals go through amm_pair_expr_set_globals");
@@ -589,7 +498,7 @@ int amm_pair_set_lambda(amm_ctx *ctx, int32_t force_id, double value) {
 }
 
 int amm_pair_set_lambda_dev(amm_ctx *ctx, int32_t force_id, const double *d_lambda) {
-    PairForce *pf = get_pair(ctx, force_id);
+    PairForce *pf = amm_force_get<PairForce>(ctx, force_id);
     if (!pf) return 1;
     if (pf->expr) {
         amm_set_error("amm_pair_set_lambda_dev: not for a pair-expression force (AMM_PAIR_EXPR)");
@@ -612,21 +521,21 @@ int amm_pair_set_lambda_dev(amm_ctx *ctx, int32_t force_id, const double *d_lamb
 }
 
 int amm_pair_set_scale(amm_ctx *ctx, int32_t force_id, double scale) {
-    PairForce *pf = get_pair(ctx, force_id);
+    PairForce *pf = amm_force_get<PairForce>(ctx, force_id);
     if (!pf) return 1;
     pf->desc.sign = scale;
     pf->pc.sign = scale;
     // the pairings cached for the one-pass evaluations depend on the sign (host sign == 1): decide them again
     pf->dual_ok = pf->fuse_ok = -1;
     for (auto &fo : ctx->forces)
-        if (fo.type == AMM_FORCE_PAIR && fo.pair->host == pf) fo.pair->dual_ok = fo.pair->fuse_ok = -1;
+        if (fo.type == AMM_FORCE_PAIR && fo.pair()->host == pf) fo.pair()->dual_ok = fo.pair()->fuse_ok = -1;
     // (a hybrid list's per-atom part is a force of its own with its own constants: same scale)
     if (pf->rest) return amm_pair_set_scale(ctx, pf->rest->id, scale);
     return 0;
 }
 
 int amm_pair_energy_derivative(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *d_out) {
-    PairForce *pf = get_pair(ctx, force_id);
+    PairForce *pf = amm_force_get<PairForce>(ctx, force_id);
     if (!pf || !d_pos || !d_out) return 1;
     if (pf->expr) {
         amm_set_error("amm_pair_energy_derivative: not for a pair-expression force (AMM_PAIR_EXPR): the interpreter differentiates in r only");
@@ -652,7 +561,7 @@ int amm_pair_energy_derivative(amm_ctx *ctx, int32_t force_id, const double *d_p
 }
 
 int amm_pair_energy_states(amm_ctx *ctx, int32_t force_id, const double *d_pos, const double *d_lambdas, int32_t n_states, double *d_out) {
-    PairForce *pf = get_pair(ctx, force_id);
+    PairForce *pf = amm_force_get<PairForce>(ctx, force_id);
     if (!pf) return 1;
     if (pf->expr) {
         amm_set_error("amm_pair_energy_states: not for a pair-expression force (AMM_PAIR_EXPR)");
@@ -742,7 +651,7 @@ static int share_list_pf(amm_ctx *ctx, PairForce *g, PairForce *h) {
 }
 
 int amm_pair_share_list(amm_ctx *ctx, int32_t force_id, int32_t host_id) {
-    PairForce *g = get_pair(ctx, force_id), *h = get_pair(ctx, host_id);
+    PairForce *g = amm_force_get<PairForce>(ctx, force_id), *h = amm_force_get<PairForce>(ctx, host_id);
     if (!g || !h) return 1;
     if (g->hybrid_rest || h->hybrid_rest) {
         amm_set_error("amm_pair_share_list: not a force of the caller's");
@@ -760,7 +669,7 @@ int amm_pair_share_list(amm_ctx *ctx, int32_t force_id, int32_t host_id) {
 }
 
 int amm_pair_set_params(amm_ctx *ctx, int32_t force_id, const double *h_q, const double *h_sigma, const double *h_eps) {
-    PairForce *pf = get_pair(ctx, force_id);
+    PairForce *pf = amm_force_get<PairForce>(ctx, force_id);
     if (!pf) return 1;
     const int n = pf->n;
     if (pf->expr) {
@@ -884,7 +793,7 @@ int amm_pair_set_params(amm_ctx *ctx, int32_t force_id, const double *h_q, const
         pf->h_cls = cls;
         pf->sites_match = -1;
         for (auto &fo : ctx->forces)
-            if (fo.type == AMM_FORCE_PAIR && fo.pair->host == pf) fo.pair->sites_match = -1;
+            if (fo.type == AMM_FORCE_PAIR && fo.pair()->host == pf) fo.pair()->sites_match = -1;
     }
     // the sorted copies of the parameters that a launch wrote ahead of time (epilogues: pair.hip, cluster.hip) were made with the old
     // ones: no later evaluation may take them for current, whichever force of the list (this one or a guest) they belong to
@@ -896,7 +805,7 @@ int amm_pair_set_params(amm_ctx *ctx, int32_t force_id, const double *h_q, const
     // dual evaluation needs bitwise equal parameters on guest and host: re-check after any change
     pf->dual_ok = pf->fuse_ok = -1;
     for (auto &fo : ctx->forces)
-        if (fo.type == AMM_FORCE_PAIR && fo.pair->host == pf) fo.pair->dual_ok = fo.pair->fuse_ok = -1;
+        if (fo.type == AMM_FORCE_PAIR && fo.pair()->host == pf) fo.pair()->dual_ok = fo.pair()->fuse_ok = -1;
     if (pf->rest) return amm_pair_set_params(ctx, pf->rest->id, h_q, h_sigma, h_eps);
     return 0;
 }
@@ -904,17 +813,13 @@ int amm_pair_set_params(amm_ctx *ctx, int32_t force_id, const double *h_q, const
 int amm_bonded_create(amm_ctx *ctx, int32_t *force_id) {
     BondedSet *bs = new BondedSet();
     std::memset(&bs->near_pc, 0, sizeof(bs->near_pc));
-    ForceObj fo;
-    fo.type = AMM_FORCE_BONDED;
-    fo.bonded = bs;
-    ctx->forces.push_back(fo);
-    *force_id = (int)ctx->forces.size() - 1;
+    *force_id = amm_force_register(ctx, AMM_FORCE_BONDED, bs);
     return 0;
 }
 
 int amm_bonded_add_terms(amm_ctx *ctx, int32_t force_id, int32_t kind, const int32_t *h_idx, const double *h_params,
                          int32_t n_terms, int32_t periodic, const amm_pair_desc *desc) {
-    BondedSet *bs = get_bonded(ctx, force_id);
+    BondedSet *bs = amm_force_get<BondedSet>(ctx, force_id);
     if (!bs) return 1;
     if (bs->finalized) {
         amm_set_error("amm_bonded_add_terms after finalize");
@@ -974,360 +879,19 @@ int amm_bonded_add_terms(amm_ctx *ctx, int32_t force_id, int32_t kind, const int
 }
 
 int amm_bonded_finalize(amm_ctx *ctx, int32_t force_id) {
-    BondedSet *bs = get_bonded(ctx, force_id);
+    BondedSet *bs = amm_force_get<BondedSet>(ctx, force_id);
     if (!bs) return 1;
     return amm_bonded_finalize_impl(ctx, bs);
 }
 
 int amm_bonded_set_sliced(amm_ctx *ctx, int32_t force_id, int32_t on) {
-    BondedSet *bs = get_bonded(ctx, force_id);
+    BondedSet *bs = amm_force_get<BondedSet>(ctx, force_id);
     if (!bs) return 1;
     bs->sliced = on != 0;
     return 0;
 }
 
-// A bond-list set that the host has replaced (parameter offsets rebuild the exception terms, groups are merged anew): its
-// device arrays are freed and the id stays retired -- ids are positions in the force table and are never reused.
-int amm_bonded_release(amm_ctx *ctx, int32_t force_id) {
-    BondedSet *bs = get_bonded(ctx, force_id);
-    if (!bs) return 1;
-    AMM_HIP(hipStreamSynchronize(ctx->stream));            // nothing in flight may still read it
-    for (int g = 0; g < AMM_MAX_GROUPS; ++g) {
-        std::vector<int> &m = ctx->groups[g].forces;
-        m.erase(std::remove(m.begin(), m.end(), (int)force_id), m.end());
-    }
-    amm_bonded_free(bs);
-    delete bs;
-    ctx->forces[force_id].bonded = nullptr;
-    ctx->forces[force_id].type = AMM_FORCE_RELEASED;
-    return 0;
-}
-
-static TermExprForce *get_term_expr(amm_ctx *ctx, int id, const char *who) {
-    if (is_cv(ctx, id, "a term-expression force") || is_compound(ctx, id, "a term-expression force") || is_gb(ctx, id, "a term-expression force") ||
-        is_cmap(ctx, id, "a term-expression force"))
-        return nullptr;
-    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_TERM_EXPR) {
-        amm_set_error(std::string(who) + ": not a term-expression force id");
-        return nullptr;
-    }
-    return ctx->forces[id].term;
-}
-
-// Custom{Bond,Angle,Torsion,External}Force(any energy text): the compiled text (atomsmm_amd/expr.py: compile_term), the terms' atoms
-// and their parameters, parameter-major
-int amm_term_expr_create(amm_ctx *ctx, int32_t kind, const int32_t *code, int32_t ncode, const double *consts, int32_t nconst,
-                         const double *globals, int32_t nglobal, const int32_t *h_idx, const double *h_params, int32_t n_terms,
-                         int32_t n_params, int32_t periodic, int32_t *force_id) {
-    auto fail = [](const std::string &what) {
-        amm_set_error("amm_term_expr_create: " + what);
-        return 1;
-    };
-    if (!ctx || !code || !force_id || (nconst > 0 && !consts) || (nglobal > 0 && !globals) || n_terms < 0 || (n_terms > 0 && !h_idx)) return fail("null argument");
-    if (kind < AMM_TERM_BOND || kind > AMM_TERM_EXTERNAL) return fail("unknown kind " + std::to_string(kind));
-    if (n_params < 0 || n_params > AMM_TERM_MAX_PARAMS) return fail(std::to_string(n_params) + " per-term parameters (limit " + std::to_string(AMM_TERM_MAX_PARAMS) + ")");
-    if (n_params > 0 && n_terms > 0 && !h_params) return fail("null parameter array");
-    if (periodic && kind == AMM_TERM_EXTERNAL) return fail("an external term reads raw coordinates: it is never periodic");
-    if (periodic && !ctx->has_box) return fail("periodic terms, but the context has no periodic box");
-    if (amm_expr_program_validate("amm_term_expr_create", code, ncode, nconst, nglobal, kind == AMM_TERM_EXTERNAL ? 3 : 1, n_params)) return 1;
-    for (int t = 0; t < n_terms; ++t)
-        for (int r = 0; r < amm_term_arity(kind); ++r) {
-            const int a = h_idx[(size_t)t * 4 + r];
-            if (a < 0 || a >= ctx->n) return fail("atom index " + std::to_string(a) + " of term " + std::to_string(t) + " is out of range");
-        }
-    AMM_HIP(hipSetDevice(ctx->device));
-    TermExprForce *tf = new TermExprForce();
-    tf->kind = kind;
-    tf->periodic = periodic ? 1 : 0;
-    tf->n_terms = n_terms;
-    tf->n_params = n_params;
-    std::memset(&tf->h, 0, sizeof(tf->h));
-    tf->h.ncode = ncode;
-    tf->h.nconst = nconst;
-    tf->h.nglobal = nglobal;
-    std::copy(code, code + ncode, tf->h.code);
-    std::copy(consts, consts + nconst, tf->h.consts);
-    std::copy(globals, globals + nglobal, tf->h.globals);
-    if (amm_term_expr_build(ctx, tf, h_idx, h_params)) {
-        amm_term_expr_free(tf);
-        return 1;
-    }
-    ForceObj fo;
-    fo.type = AMM_FORCE_TERM_EXPR;
-    fo.term = tf;
-    ctx->forces.push_back(fo);
-    *force_id = (int32_t)ctx->forces.size() - 1;
-    return 0;
-}
-
-int amm_term_expr_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal) {
-    TermExprForce *tf = get_term_expr(ctx, force_id, "amm_term_expr_set_globals");
-    if (!tf) return 1;
-    if (nglobal != tf->h.nglobal || (nglobal > 0 && !globals)) {
-        amm_set_error("amm_term_expr_set_globals: the program reads " + std::to_string(tf->h.nglobal) + " globals, " + std::to_string(nglobal) + " given");
-        return 1;
-    }
-    std::copy(globals, globals + nglobal, tf->h.globals);
-    return amm_term_expr_upload(ctx, tf, true);
-}
-
-int amm_term_expr_set_params(amm_ctx *ctx, int32_t force_id, const double *h_params, int32_t n_terms, int32_t n_params) {
-    TermExprForce *tf = get_term_expr(ctx, force_id, "amm_term_expr_set_params");
-    if (!tf) return 1;
-    if (n_terms != tf->n_terms || n_params != tf->n_params || ((size_t)n_terms * n_params > 0 && !h_params)) {
-        amm_set_error("amm_term_expr_set_params: the force has " + std::to_string(tf->n_terms) + " terms of " + std::to_string(tf->n_params) +
-                      " parameters, " + std::to_string(n_terms) + " x " + std::to_string(n_params) + " given");
-        return 1;
-    }
-    return amm_term_expr_upload_params(ctx, tf, h_params);
-}
-
-int amm_term_expr_release(amm_ctx *ctx, int32_t force_id) {
-    TermExprForce *tf = get_term_expr(ctx, force_id, "amm_term_expr_release");
-    if (!tf) return 1;
-    AMM_HIP(hipStreamSynchronize(ctx->stream));            // nothing in flight may still read it
-    for (int g = 0; g < AMM_MAX_GROUPS; ++g) {
-        std::vector<int> &m = ctx->groups[g].forces;
-        m.erase(std::remove(m.begin(), m.end(), (int)force_id), m.end());
-    }
-    amm_term_expr_free(tf);
-    ctx->forces[force_id].term = nullptr;
-    ctx->forces[force_id].type = AMM_FORCE_RELEASED;
-    return 0;
-}
-
-static CvForce *get_cv(amm_ctx *ctx, int id, const char *who) {
-    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_CV) {
-        amm_set_error(std::string(who) + ": not the id of a collective-variable force (AMM_FORCE_CV)");
-        return nullptr;
-    }
-    return ctx->forces[id].cv;
-}
-
-// CustomCVForce(any energy text): the compiled text (atomsmm_amd/expr.py: compile_cv) and the inner forces, one per collective variable
-int amm_cv_create(amm_ctx *ctx, const int32_t *inner_ids, int32_t n_cv, int32_t n_deriv, const int32_t *code, int32_t ncode,
-                  const double *consts, int32_t nconst, const double *globals, int32_t nglobal, int32_t *force_id) {
-    if (!ctx || !inner_ids || !code || !force_id || (nconst > 0 && !consts) || (nglobal > 0 && !globals)) {
-        amm_set_error("amm_cv_create: null argument");
-        return 1;
-    }
-    CvForce *cv = nullptr;
-    if (amm_cv_create_impl(ctx, inner_ids, n_cv, n_deriv, code, ncode, consts, nconst, globals, nglobal, &cv)) return 1;
-    ForceObj fo;
-    fo.type = AMM_FORCE_CV;
-    fo.cv = cv;
-    ctx->forces.push_back(fo);
-    *force_id = (int32_t)ctx->forces.size() - 1;
-    return 0;
-}
-
-int amm_cv_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal) {
-    CvForce *cv = get_cv(ctx, force_id, "amm_cv_set_globals");
-    return cv ? amm_cv_set_globals_impl(ctx, cv, globals, nglobal) : 1;
-}
-
-int amm_cv_set_variables(amm_ctx *ctx, int32_t force_id, const double *values, int32_t n_deriv) {
-    CvForce *cv = get_cv(ctx, force_id, "amm_cv_set_variables");
-    return cv ? amm_cv_set_variables_impl(ctx, cv, values, n_deriv) : 1;
-}
-
-int amm_cv_values(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *h_out) {
-    CvForce *cv = get_cv(ctx, force_id, "amm_cv_values");
-    if (!cv) return 1;
-    if (!d_pos || !h_out) {
-        amm_set_error("amm_cv_values: null argument");
-        return 1;
-    }
-    return amm_cv_values_impl(ctx, cv, d_pos, h_out);
-}
-
-int amm_cv_energy_derivative(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *d_out) {
-    CvForce *cv = get_cv(ctx, force_id, "amm_cv_energy_derivative");
-    if (!cv) return 1;
-    if (!d_pos || !d_out) {
-        amm_set_error("amm_cv_energy_derivative: null argument");
-        return 1;
-    }
-    return amm_cv_energy_derivative_impl(ctx, cv, d_pos, d_out);
-}
-
-int amm_cv_release(amm_ctx *ctx, int32_t force_id) {
-    CvForce *cv = get_cv(ctx, force_id, "amm_cv_release");
-    if (!cv) return 1;
-    AMM_HIP(hipStreamSynchronize(ctx->stream));            // nothing in flight may still read it
-    for (int g = 0; g < AMM_MAX_GROUPS; ++g) {
-        std::vector<int> &m = ctx->groups[g].forces;
-        m.erase(std::remove(m.begin(), m.end(), (int)force_id), m.end());
-    }
-    amm_cv_free(cv);
-    ctx->forces[force_id].cv = nullptr;
-    ctx->forces[force_id].type = AMM_FORCE_RELEASED;
-    return 0;
-}
-
-static CompoundForce *get_compound(amm_ctx *ctx, int id, const char *who) {
-    if (is_cmap(ctx, id, "a compound-bond force")) return nullptr;
-    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_COMPOUND) {
-        amm_set_error(std::string(who) + ": not the id of a compound-bond force (AMM_FORCE_COMPOUND)");
-        return nullptr;
-    }
-    return ctx->forces[id].compound;
-}
-
-// CustomCompoundBondForce / CustomCentroidBondForce(any energy text): the compiled text and its variable table
-// (atomsmm_amd/expr.py: compile_compound), the bonds' particles (or groups) and parameters, and for centroid bonds the groups
-int amm_compound_create(amm_ctx *ctx, int32_t n_slots, const int32_t *code, int32_t ncode, const double *consts, int32_t nconst,
-                        const double *globals, int32_t nglobal, const int32_t *var_kinds, const int32_t *var_slots, int32_t n_vars,
-                        const int32_t *h_idx, const double *h_params, int32_t n_bonds, int32_t n_params, int32_t periodic,
-                        const int32_t *group_ptr, const int32_t *group_atoms, const double *group_weights, int32_t n_groups,
-                        int32_t *force_id) {
-    if (!ctx || !code || !force_id || (nconst > 0 && !consts) || (nglobal > 0 && !globals) || (n_vars > 0 && (!var_kinds || !var_slots)) ||
-        (n_bonds > 0 && !h_idx)) {
-        amm_set_error("amm_compound_create: null argument");
-        return 1;
-    }
-    CompoundForce *cf = nullptr;
-    if (amm_compound_create_impl(ctx, n_slots, code, ncode, consts, nconst, globals, nglobal, var_kinds, var_slots, n_vars, h_idx, h_params,
-                                 n_bonds, n_params, periodic, group_ptr, group_atoms, group_weights, n_groups, &cf))
-        return 1;
-    ForceObj fo;
-    fo.type = AMM_FORCE_COMPOUND;
-    fo.compound = cf;
-    ctx->forces.push_back(fo);
-    *force_id = (int32_t)ctx->forces.size() - 1;
-    return 0;
-}
-
-int amm_compound_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal) {
-    CompoundForce *cf = get_compound(ctx, force_id, "amm_compound_set_globals");
-    return cf ? amm_compound_set_globals_impl(ctx, cf, globals, nglobal) : 1;
-}
-
-int amm_compound_set_params(amm_ctx *ctx, int32_t force_id, const double *h_params, int32_t n_bonds, int32_t n_params) {
-    CompoundForce *cf = get_compound(ctx, force_id, "amm_compound_set_params");
-    return cf ? amm_compound_set_params_impl(ctx, cf, h_params, n_bonds, n_params) : 1;
-}
-
-int amm_compound_set_weights(amm_ctx *ctx, int32_t force_id, const double *weights, int32_t n_members) {
-    CompoundForce *cf = get_compound(ctx, force_id, "amm_compound_set_weights");
-    return cf ? amm_compound_set_weights_impl(ctx, cf, weights, n_members) : 1;
-}
-
-int amm_compound_release(amm_ctx *ctx, int32_t force_id) {
-    CompoundForce *cf = get_compound(ctx, force_id, "amm_compound_release");
-    if (!cf) return 1;
-    AMM_HIP(hipStreamSynchronize(ctx->stream));            // nothing in flight may still read it
-    for (int g = 0; g < AMM_MAX_GROUPS; ++g) {
-        std::vector<int> &m = ctx->groups[g].forces;
-        m.erase(std::remove(m.begin(), m.end(), (int)force_id), m.end());
-    }
-    amm_compound_free(cf);
-    ctx->forces[force_id].compound = nullptr;
-    ctx->forces[force_id].type = AMM_FORCE_RELEASED;
-    return 0;
-}
-
-static GbForce *get_gb(amm_ctx *ctx, int id, const char *who) {
-    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_GB) {
-        amm_set_error(std::string(who) + ": not the id of a generalized-Born force (AMM_FORCE_GB)");
-        return nullptr;
-    }
-    return ctx->forces[id].gb;
-}
-
-// GBSAOBCForce in free space (csrc/gb.hip): addParticle(charge, radius, scale) x n, the two dielectrics, the surface-area energy and
-// the cutoff (rc <= 0: NoCutoff)
-int amm_gb_create(amm_ctx *ctx, const double *h_q, const double *h_radius, const double *h_scale, double eps_in, double eps_out,
-                  double sa_energy, double rc, int32_t *force_id) {
-    if (!ctx || !h_q || !h_radius || !h_scale || !force_id) {
-        amm_set_error("amm_gb_create: null argument");
-        return 1;
-    }
-    AMM_HIP(hipSetDevice(ctx->device));
-    GbForce *gb = nullptr;
-    if (amm_gb_create_impl(ctx, h_q, h_radius, h_scale, eps_in, eps_out, sa_energy, rc, &gb)) return 1;
-    ForceObj fo;
-    fo.type = AMM_FORCE_GB;
-    fo.gb = gb;
-    ctx->forces.push_back(fo);
-    *force_id = (int32_t)ctx->forces.size() - 1;
-    return 0;
-}
-
-int amm_gb_set_params(amm_ctx *ctx, int32_t force_id, const double *h_q, const double *h_radius, const double *h_scale, double eps_in,
-                      double eps_out, double sa_energy, double rc) {
-    GbForce *gb = get_gb(ctx, force_id, "amm_gb_set_params");
-    return gb ? amm_gb_set_params_impl(ctx, gb, h_q, h_radius, h_scale, eps_in, eps_out, sa_energy, rc) : 1;
-}
-
-int amm_gb_born_radii(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *h_out) {
-    GbForce *gb = get_gb(ctx, force_id, "amm_gb_born_radii");
-    if (!gb) return 1;
-    if (!d_pos || !h_out) {
-        amm_set_error("amm_gb_born_radii: null argument");
-        return 1;
-    }
-    return amm_gb_born_radii_impl(ctx, gb, d_pos, h_out);
-}
-
-int amm_gb_release(amm_ctx *ctx, int32_t force_id) {
-    GbForce *gb = get_gb(ctx, force_id, "amm_gb_release");
-    if (!gb) return 1;
-    AMM_HIP(hipStreamSynchronize(ctx->stream));            // nothing in flight may still read it
-    for (int g = 0; g < AMM_MAX_GROUPS; ++g) {
-        std::vector<int> &m = ctx->groups[g].forces;
-        m.erase(std::remove(m.begin(), m.end(), (int)force_id), m.end());
-    }
-    amm_gb_free(gb);
-    ctx->forces[force_id].gb = nullptr;
-    ctx->forces[force_id].type = AMM_FORCE_RELEASED;
-    return 0;
-}
-
-static CmapForce *get_cmap(amm_ctx *ctx, int id, const char *who) {
-    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_CMAP) {
-        amm_set_error(std::string(who) + ": not the id of a CMAP force (AMM_FORCE_CMAP)");
-        return nullptr;
-    }
-    return ctx->forces[id].cmap;
-}
-
-// CMAPTorsionForce (csrc/cmap.hip): addMap x n_maps as the bicubic coefficients of atomsmm_amd/tables.py (cmap_coefficients),
-// addTorsion x n_terms as a map index and eight atoms each
-int amm_cmap_create(amm_ctx *ctx, int32_t n_maps, const int32_t *h_sizes, const double *h_coeffs, const int32_t *h_map_of_term,
-                    const int32_t *h_idx, int32_t n_terms, int32_t periodic, int32_t *force_id) {
-    if (!ctx || !force_id || (n_maps > 0 && (!h_sizes || !h_coeffs)) || (n_terms > 0 && (!h_map_of_term || !h_idx))) {
-        amm_set_error("amm_cmap_create: null argument");
-        return 1;
-    }
-    CmapForce *cm = nullptr;
-    if (amm_cmap_create_impl(ctx, n_maps, h_sizes, h_coeffs, h_map_of_term, h_idx, n_terms, periodic, &cm)) return 1;
-    ForceObj fo;
-    fo.type = AMM_FORCE_CMAP;
-    fo.cmap = cm;
-    ctx->forces.push_back(fo);
-    *force_id = (int32_t)ctx->forces.size() - 1;
-    return 0;
-}
-
-int amm_cmap_set_params(amm_ctx *ctx, int32_t force_id, const double *h_coeffs, const int32_t *h_map_of_term, int32_t n_maps, int32_t n_terms) {
-    CmapForce *cm = get_cmap(ctx, force_id, "amm_cmap_set_params");
-    return cm ? amm_cmap_set_params_impl(ctx, cm, h_coeffs, h_map_of_term, n_maps, n_terms) : 1;
-}
-
-int amm_cmap_release(amm_ctx *ctx, int32_t force_id) {
-    CmapForce *cm = get_cmap(ctx, force_id, "amm_cmap_release");
-    if (!cm) return 1;
-    AMM_HIP(hipStreamSynchronize(ctx->stream));            // nothing in flight may still read it
-    for (int g = 0; g < AMM_MAX_GROUPS; ++g) {
-        std::vector<int> &m = ctx->groups[g].forces;
-        m.erase(std::remove(m.begin(), m.end(), (int)force_id), m.end());
-    }
-    amm_cmap_free(cm);
-    ctx->forces[force_id].cmap = nullptr;
-    ctx->forces[force_id].type = AMM_FORCE_RELEASED;
-    return 0;
-}
+int amm_bonded_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_BONDED, nullptr); }
 
 int amm_pme_create(amm_ctx *ctx, double alpha, int32_t nx, int32_t ny, int32_t nz, double Kc, const double *h_q,
                    int32_t *force_id) {
@@ -1343,31 +907,18 @@ int amm_pme_create(amm_ctx *ctx, double alpha, int32_t nx, int32_t ny, int32_t n
     const int K[3] = {nx, ny, nz};
     PmeForce *pm = nullptr;
     if (amm_pme_create_impl(ctx, alpha, K, Kc, h_q, &pm)) return 1;
-    ForceObj fo;
-    fo.type = AMM_FORCE_PME;
-    fo.pme = pm;
-    ctx->forces.push_back(fo);
-    *force_id = (int32_t)ctx->forces.size() - 1;
+    *force_id = amm_force_register(ctx, AMM_FORCE_PME, pm);
     return 0;
 }
 
-static PmeForce *get_pme(amm_ctx *ctx, int id) {
-    if (is_cv(ctx, id, "a PME force") || is_compound(ctx, id, "a PME force") || is_gb(ctx, id, "a PME force") || is_cmap(ctx, id, "a PME force")) return nullptr;
-    if (!ctx || id < 0 || id >= (int)ctx->forces.size() || ctx->forces[id].type != AMM_FORCE_PME) {
-        amm_set_error("not a PME force id");
-        return nullptr;
-    }
-    return ctx->forces[id].pme;
-}
-
 int amm_pme_set_charges(amm_ctx *ctx, int32_t force_id, const double *h_q) {
-    PmeForce *pm = get_pme(ctx, force_id);
+    PmeForce *pm = amm_force_get<PmeForce>(ctx, force_id);
     if (!pm || !h_q) return 1;
     return amm_pme_set_charges_impl(ctx, pm, h_q);
 }
 
 int amm_pme_set_sliced(amm_ctx *ctx, int32_t force_id, int32_t on) {
-    PmeForce *pm = get_pme(ctx, force_id);
+    PmeForce *pm = amm_force_get<PmeForce>(ctx, force_id);
     if (!pm) return 1;
     return amm_pme_set_sliced_impl(pm, on);
 }
@@ -1777,7 +1328,7 @@ int amm_run_ops_from(amm_ctx *ctx, const amm_op *ops, int32_t n_ops, int32_t rep
 }
 
 int amm_pair_get_stats(amm_ctx *ctx, int32_t force_id, amm_pair_stats *out) {
-    PairForce *pf = get_pair(ctx, force_id);
+    PairForce *pf = amm_force_get<PairForce>(ctx, force_id);
     if (!pf || !out) return 1;
     std::memset(out, 0, sizeof(*out));
     AMM_HIP(hipStreamSynchronize(ctx->stream));
@@ -1846,7 +1397,7 @@ int amm_pair_get_stats(amm_ctx *ctx, int32_t force_id, amm_pair_stats *out) {
 }
 
 int amm_pair_row_padding(amm_ctx *ctx, int32_t force_id, int64_t out[2]) {
-    PairForce *pf = get_pair(ctx, force_id);
+    PairForce *pf = amm_force_get<PairForce>(ctx, force_id);
     if (!pf || !out) {
         amm_set_error("amm_pair_row_padding: null argument or not a pair force");
         return 1;
@@ -1863,7 +1414,7 @@ int amm_pair_row_padding(amm_ctx *ctx, int32_t force_id, int64_t out[2]) {
 }
 
 int amm_pair_count_within(amm_ctx *ctx, int32_t force_id, const double *d_pos, double r_within, int64_t *count) {
-    PairForce *pf = get_pair(ctx, force_id);
+    PairForce *pf = amm_force_get<PairForce>(ctx, force_id);
     if (!pf || !d_pos || !count) {
         amm_set_error("amm_pair_count_within: null argument or not a pair force");
         return 1;
@@ -1986,8 +1537,8 @@ static int box_apply(amm_ctx *ctx, bool &regrid, bool &waited) {
     // 1. every force's buffers as amm_pair_create would derive them in this box (a hybrid list's per-atom part asks for a multiple of
     // its parent's: the parent comes first in ctx->forces)
     for (auto &fo : ctx->forces) {
-        if (fo.type != AMM_FORCE_PAIR || fo.pair->free_space) continue;
-        PairForce *pf = fo.pair;
+        if (fo.type != AMM_FORCE_PAIR || fo.pair()->free_space) continue;
+        PairForce *pf = fo.pair();
         pair_derive_buffers(ctx, pf);
         if (pf->rest) pf->rest->skin_req = pf->skin * ctx->opt_rest_skin_factor;
     }
@@ -2000,8 +1551,8 @@ static int box_apply(amm_ctx *ctx, bool &regrid, bool &waited) {
         return 0;
     };
     for (auto &fo : ctx->forces) {
-        if (fo.type != AMM_FORCE_PAIR || fo.pair->host || fo.pair->free_space) continue;
-        PairForce *L = fo.pair;
+        if (fo.type != AMM_FORCE_PAIR || fo.pair()->host || fo.pair()->free_space) continue;
+        PairForce *L = fo.pair();
         const bool dual = L->skin_out > L->skin * (1 + 1e-9);
         const double full_skin = L->skin;
         // per-atom rows
@@ -2060,16 +1611,16 @@ static int box_apply(amm_ctx *ctx, bool &regrid, bool &waited) {
     }
     // 3. shared lists, as amm_pair_share_list left them
     for (auto &fo : ctx->forces)
-        if (fo.type == AMM_FORCE_PAIR && fo.pair->host) {
-            PairForce *g = fo.pair, *h = g->host;
+        if (fo.type == AMM_FORCE_PAIR && fo.pair()->host) {
+            PairForce *g = fo.pair(), *h = g->host;
             g->rlist_build = std::min(g->rlist_build, h->desc.rc + std::min(g->skin, h->skin) + 2e-4);
             share_buffers(g, h);
         }
     // 4. nothing made for the old box survives: lists are rebuilt by their next evaluation, sorted copies gathered again, the
     // displacement triggers start from the positions of that rebuild, candidate sets start over
     for (auto &fo : ctx->forces) {
-        if (fo.type != AMM_FORCE_PAIR || fo.pair->free_space) continue;
-        PairForce *pf = fo.pair;
+        if (fo.type != AMM_FORCE_PAIR || fo.pair()->free_space) continue;
+        PairForce *pf = fo.pair();
         pf->a_sorted_for = nullptr;
         pf->a_sorted_epoch = pf->checked_epoch = pf->pre_epoch = -1;
         if (pf->built) pf->force_rebuild = true;
@@ -2100,9 +1651,9 @@ int amm_set_box(amm_ctx *ctx, const double h_box[3]) {
         return 1;
     }
     for (auto &fo : ctx->forces)
-        if (fo.type == AMM_FORCE_PAIR && !fo.pair->free_space)
+        if (fo.type == AMM_FORCE_PAIR && !fo.pair()->free_space)
             for (int k = 0; k < 3; ++k)
-                if (fo.pair->desc.rc > 0.5 * h_box[k] * (1 + 1e-12)) {
+                if (fo.pair()->desc.rc > 0.5 * h_box[k] * (1 + 1e-12)) {
                     amm_set_error("pair cutoff exceeds half the box edge (minimum image needs rc <= L/2)");
                     return 1;           // (nothing was touched: the old box stays in force)
                 }
@@ -2191,7 +1742,7 @@ int amm_profile_enable(amm_ctx *ctx, int32_t on) {
 }
 
 int amm_profile_read(amm_ctx *ctx, int32_t force_id, int64_t *n_launches, double *total_ms) {
-    PairForce *pf = get_pair(ctx, force_id);
+    PairForce *pf = amm_force_get<PairForce>(ctx, force_id);
     if (!pf) return 1;
     AMM_HIP(hipStreamSynchronize(ctx->stream));
     double tot = 0.0;

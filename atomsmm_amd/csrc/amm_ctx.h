@@ -248,18 +248,35 @@ struct CvForce;       // cv.hip: a CustomCVForce -- K inner forces and the compi
 struct CompoundForce; // compound.hip: a CustomCompoundBondForce / CustomCentroidBondForce -- bonds over several particles or centres
 struct GbForce;       // gb.hip: a GBSAOBCForce -- generalized-Born (OBC2) implicit solvent with a surface-area term, free space only
 struct CmapForce;     // cmap.hip: a CMAPTorsionForce -- bicubic maps over pairs of dihedrals
+// The force families.  A family is described ONCE: its tag here, the struct that goes with the tag in amm_force_type, and its row of
+// the table behind amm_family (families.hip).  The typed lookup and its refusals, amm_force_eval_dispatch, release, amm_destroy, amm_set_slice and
+// cv.hip's messages all read the row -- a new family adds these three lines, its own .hip file and its extern "C" entry points.
 enum : int { AMM_FORCE_RELEASED = 0, AMM_FORCE_PAIR = 1, AMM_FORCE_BONDED = 2, AMM_FORCE_PME = 3, AMM_FORCE_TERM_EXPR = 4, AMM_FORCE_CV = 5,
-             AMM_FORCE_COMPOUND = 6, AMM_FORCE_GB = 7, AMM_FORCE_CMAP = 8 };   // ForceObj::type
+             AMM_FORCE_COMPOUND = 6, AMM_FORCE_GB = 7, AMM_FORCE_CMAP = 8, AMM_FORCE_TYPES = 9 };   // ForceObj::type, the row amm_family returns
+template <class T> inline constexpr int amm_force_type = -1;
+template <> inline constexpr int amm_force_type<PairForce> = AMM_FORCE_PAIR;
+template <> inline constexpr int amm_force_type<BondedSet> = AMM_FORCE_BONDED;
+template <> inline constexpr int amm_force_type<PmeForce> = AMM_FORCE_PME;
+template <> inline constexpr int amm_force_type<TermExprForce> = AMM_FORCE_TERM_EXPR;
+template <> inline constexpr int amm_force_type<CvForce> = AMM_FORCE_CV;
+template <> inline constexpr int amm_force_type<CompoundForce> = AMM_FORCE_COMPOUND;
+template <> inline constexpr int amm_force_type<GbForce> = AMM_FORCE_GB;
+template <> inline constexpr int amm_force_type<CmapForce> = AMM_FORCE_CMAP;
+struct ForceFamily {
+    const char *noun, *tag, *prefix;   // "a CMAP force", "AMM_FORCE_CMAP", "amm_cmap_*"
+    const char *bad_id;                // what the family's entry points say of an id that is not theirs (behind "<entry point>: " if they name themselves)
+    bool single_rank;                  // amm_set_slice refuses world > 1 while such a force lives
+    int (*eval)(amm_ctx *ctx, void *obj, const double *d_pos, double *d_force, int accumulate, double *d_energy);
+    void (*free)(void *obj);           // the device memory AND the object
+};
+const ForceFamily &amm_family(int type);   // the row of AMM_FORCE_<type>
+// one object of the family `type` says; a released id holds none
 struct ForceObj {
     int type = AMM_FORCE_RELEASED;
-    PairForce *pair = nullptr;
-    BondedSet *bonded = nullptr;
-    PmeForce *pme = nullptr;
-    TermExprForce *term = nullptr;
-    CvForce *cv = nullptr;
-    CompoundForce *compound = nullptr;
-    GbForce *gb = nullptr;
-    CmapForce *cmap = nullptr;
+    void *obj = nullptr;
+    template <class T> T *as() const { return type == amm_force_type<T> ? static_cast<T *>(obj) : nullptr; }    // null: another family's
+    PairForce *pair() const { return as<PairForce>(); }
+    BondedSet *bonded() const { return as<BondedSet>(); }
 };
 
 struct ExprDef {
@@ -482,9 +499,18 @@ struct WatchArgs {
 void amm_collect_watches(amm_ctx *ctx, WatchArgs &W);
 void amm_watch_moved(amm_ctx *ctx);
 
-// run_ops.hip: the op scheduler (validated arguments, n_ops > 0, repeat > 0); abi.hip: one force of any type
+// run_ops.hip: the op scheduler (validated arguments, n_ops > 0, repeat > 0)
 int amm_run_ops_impl(amm_ctx *ctx, const amm_op *ops, int n_ops, int repeat, int64_t *cursor);
+// families.hip: one force of any type; a new force's id; the object behind an id of family `type` -- any other id is refused with
+// the family's wording (who: the entry point, for the families that name it), a live id of another family named by its owner;
+// the end of a force whose id stays retired (ids are positions in ctx->forces and are never reused)
 int amm_force_eval_dispatch(amm_ctx *ctx, int force_id, const double *d_pos, double *d_force, int accumulate, double *d_energy);
+int amm_force_register(amm_ctx *ctx, int type, void *obj);
+void *amm_force_lookup(amm_ctx *ctx, int id, int type, const char *who);
+int amm_force_release(amm_ctx *ctx, int id, int type, const char *who);
+template <class T> T *amm_force_get(amm_ctx *ctx, int id, const char *who = nullptr) {
+    return static_cast<T *>(amm_force_lookup(ctx, id, amm_force_type<T>, who));
+}
 // comm.hip
 int amm_comm_unique_id_impl(const char *rccl_path, unsigned char *out);
 int amm_comm_init_impl(amm_ctx *ctx, const char *rccl_path, const unsigned char *id_bytes, int rank, int world);
@@ -583,7 +609,7 @@ int amm_pair_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double 
                        int exchange = 0);
 bool amm_pair_can_eval_dual(amm_ctx *ctx, PairForce *guest, PairForce *host);
 bool amm_pair_can_fuse_discount(amm_ctx *ctx, PairForce *guest, PairForce *host);
-int amm_pair_free(PairForce *pf);
+int amm_pair_free(PairForce *pf);            // (like every family's free: the device memory and the object)
 // amm_set_box: drop the per-atom rows and their capacities and choose the cell counts again for the context's box (the next evaluation
 // builds and sizes them as the first one did); frees device memory -- the caller has waited for the stream
 int amm_pair_regrid(amm_ctx *ctx, PairForce *pf);

@@ -1206,11 +1206,11 @@ void amm_collect_watches(amm_ctx *ctx, WatchArgs &W) {
         W.n++;
     };
     for (auto &fo : ctx->forces)
-        if (fo.type == 1 && fo.pair->cl && fo.pair->cl->built && fo.pair->last_kind >= 1)
-            watch(fo.pair->cl->d_xref, fo.pair->cl->skin, fo.pair->cl->d_flags, &fo.pair->cl->pre_epoch, &fo.pair->cl->pre_pos);
+        if (PairForce *pf = fo.pair(); pf && pf->cl && pf->cl->built && pf->last_kind >= 1)
+            watch(pf->cl->d_xref, pf->cl->skin, pf->cl->d_flags, &pf->cl->pre_epoch, &pf->cl->pre_pos);
     for (auto &fo : ctx->forces)
-        if (fo.type == 1 && fo.pair->built && !fo.pair->host && !fo.pair->dual && !(fo.pair->cl && fo.pair->last_kind >= 1))
-            watch(fo.pair->d_xref, fo.pair->skin, fo.pair->d_flags, &fo.pair->pre_epoch, &fo.pair->pre_pos);
+        if (PairForce *pf = fo.pair(); pf && pf->built && !pf->host && !pf->dual && !(pf->cl && pf->last_kind >= 1))
+            watch(pf->d_xref, pf->skin, pf->d_flags, &pf->pre_epoch, &pf->pre_pos);
     ctx->n_watched = W.n;
 }
 
@@ -1238,6 +1238,7 @@ int amm_bonded_free(BondedSet *bs) {
     if (bs->d_comp_ptr) (void)hipFree(bs->d_comp_ptr);
     if (bs->d_comp_atoms) (void)hipFree(bs->d_comp_atoms);
     if (bs->d_epart) (void)hipFree(bs->d_epart);
+    delete bs;
     return 0;
 }
 

@@ -108,18 +108,6 @@ __global__ void __launch_bounds__(AMM_CV_BLOCK) k_cv_apply(CvArgs A, const PairE
     }
 }
 
-static const char *cv_type_name(int type) {
-    switch (type) {
-    case AMM_FORCE_RELEASED: return "a released id";
-    case AMM_FORCE_PAIR: return "a pair force";
-    case AMM_FORCE_PME: return "a reciprocal-space force";
-    case AMM_FORCE_CV: return "a collective-variable force (AMM_FORCE_CV)";
-    case AMM_FORCE_GB: return "a generalized-Born force (AMM_FORCE_GB)";
-    case AMM_FORCE_CMAP: return "a CMAP force (AMM_FORCE_CMAP)";
-    default: return "a force of an unknown type";
-    }
-}
-
 // every inner id still names a bond-list set, a term-expression force or a compound-bond force (who: the entry point, for the message)
 static int cv_check_inner(amm_ctx *ctx, const int32_t *inner, int n_cv, const char *who) {
     for (int k = 0; k < n_cv; ++k) {
@@ -130,8 +118,8 @@ static int cv_check_inner(amm_ctx *ctx, const int32_t *inner, int n_cv, const ch
         }
         const int type = ctx->forces[id].type;
         if (type != AMM_FORCE_BONDED && type != AMM_FORCE_TERM_EXPR && type != AMM_FORCE_COMPOUND) {
-            amm_set_error(std::string(who) + ": inner force " + std::to_string(k) + " (id " + std::to_string(id) + ") is " + cv_type_name(type) +
-                          ": a collective variable is the energy of a bond-list set, of a term-expression force or of a compound-bond force");
+            amm_set_error(std::string(who) + ": inner force " + std::to_string(k) + " (id " + std::to_string(id) + ") is " + amm_family(type).noun +
+                          " (" + amm_family(type).tag + "): a collective variable is the energy of a bond-list set, of a term-expression force or of a compound-bond force");
             return 1;
         }
     }

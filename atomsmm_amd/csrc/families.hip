@@ -1,0 +1,294 @@
+// atomsmm_amd/csrc/families.hip -- the table of force families (amm_ctx.h: ForceFamily) and everything derived from it: the typed lookup
+// with its refusals, registration, release and the dispatch of an evaluation; then the extern "C" entry points of the families whose
+// implementation is a .hip file of its own (term expressions, collective variables, compound bonds, generalized Born, CMAP).
+#include <algorithm>
+#include <cstring>
+
+#include "amm_ctx.h"
+#include "term_expr_vm.h"
+
+// the families' own eval and free functions behind the table's one signature
+template <class T, auto Eval> static int eval_as(amm_ctx *ctx, void *obj, const double *d_pos, double *d_force, int accumulate, double *d_energy) {
+    return Eval(ctx, static_cast<T *>(obj), d_pos, d_force, accumulate, d_energy);
+}
+template <class T, auto Free> static void free_as(void *obj) { Free(static_cast<T *>(obj)); }
+static int pair_eval(amm_ctx *ctx, PairForce *pf, const double *d_pos, double *d_force, int accumulate, double *d_energy) {
+    return amm_pair_eval_impl(ctx, pf, d_pos, d_force, accumulate, d_energy);      // (no guest, no exchange)
+}
+static int released_eval(amm_ctx *, void *, const double *, double *, int, double *) {
+    amm_set_error("evaluation of a released force id");
+    return 1;
+}
+static void released_free(void *) {}
+
+// One row per AMM_FORCE_* value, in the enum's order: noun phrase, tag, entry points, bad-id wording, single rank, eval, free.
+const ForceFamily &amm_family(int type) {
+    static const ForceFamily rows[AMM_FORCE_TYPES] = {
+        {"a released id", "AMM_FORCE_RELEASED", "none", "released force id", false, released_eval, released_free},
+        {"a pair force", "AMM_FORCE_PAIR", "amm_pair_*", "invalid pair force id", false,
+         eval_as<PairForce, pair_eval>, free_as<PairForce, amm_pair_free>},
+        {"a bond-list set", "AMM_FORCE_BONDED", "amm_bonded_*", "invalid bonded force id", false,
+         eval_as<BondedSet, amm_bonded_eval_impl>, free_as<BondedSet, amm_bonded_free>},
+        {"a PME force", "AMM_FORCE_PME", "amm_pme_*", "not a PME force id", false,
+         eval_as<PmeForce, amm_pme_eval_impl>, free_as<PmeForce, amm_pme_free>},
+        // (not single_rank: the library runs term expressions on a slice's context; it is the engine that refuses them on several ranks)
+        {"a term-expression force", "AMM_FORCE_TERM_EXPR", "amm_term_expr_*", "not a term-expression force id", false,
+         eval_as<TermExprForce, amm_term_expr_eval_impl>, free_as<TermExprForce, amm_term_expr_free>},
+        {"a collective-variable force", "AMM_FORCE_CV", "amm_cv_*", "not the id of a collective-variable force (AMM_FORCE_CV)", true,
+         eval_as<CvForce, amm_cv_eval_impl>, free_as<CvForce, amm_cv_free>},
+        {"a compound-bond force", "AMM_FORCE_COMPOUND", "amm_compound_*", "not the id of a compound-bond force (AMM_FORCE_COMPOUND)", true,
+         eval_as<CompoundForce, amm_compound_eval_impl>, free_as<CompoundForce, amm_compound_free>},
+        {"a generalized-Born force", "AMM_FORCE_GB", "amm_gb_*", "not the id of a generalized-Born force (AMM_FORCE_GB)", true,
+         eval_as<GbForce, amm_gb_eval_impl>, free_as<GbForce, amm_gb_free>},
+        {"a CMAP force", "AMM_FORCE_CMAP", "amm_cmap_*", "not the id of a CMAP force (AMM_FORCE_CMAP)", true,
+         eval_as<CmapForce, amm_cmap_eval_impl>, free_as<CmapForce, amm_cmap_free>},
+    };
+    return rows[type];
+}
+
+// one force of any type (also the members of a group: run_ops.hip)
+int amm_force_eval_dispatch(amm_ctx *ctx, int force_id, const double *d_pos, double *d_force, int accumulate, double *d_energy) {
+    const ForceObj &f = ctx->forces[force_id];
+    return amm_family(f.type).eval(ctx, f.obj, d_pos, d_force, accumulate, d_energy);
+}
+
+int amm_force_register(amm_ctx *ctx, int type, void *obj) {
+    ForceObj fo;
+    fo.type = type;
+    fo.obj = obj;
+    ctx->forces.push_back(fo);
+    return (int)ctx->forces.size() - 1;
+}
+
+void *amm_force_lookup(amm_ctx *ctx, int id, int type, const char *who) {
+    const bool known = ctx && id >= 0 && id < (int)ctx->forces.size();
+    if (known && ctx->forces[id].type == type) return ctx->forces[id].obj;
+    std::string msg = (who ? std::string(who) + ": " : std::string()) + amm_family(type).bad_id;
+    if (known && ctx->forces[id].type != AMM_FORCE_RELEASED) {
+        const ForceFamily &owner = amm_family(ctx->forces[id].type);
+        msg += ": force " + std::to_string(id) + " is " + owner.noun + " (" + owner.tag + ": " + owner.prefix + ")";
+    }
+    amm_set_error(msg);
+    return nullptr;
+}
+
+// A force that the host has replaced (parameter offsets rebuild the exception terms, groups are merged anew, a Context goes away): its
+// device arrays are freed, no group lists it any more and the id stays retired.
+int amm_force_release(amm_ctx *ctx, int id, int type, const char *who) {
+    void *obj = amm_force_lookup(ctx, id, type, who);
+    if (!obj) return 1;
+    AMM_HIP(hipStreamSynchronize(ctx->stream));            // nothing in flight may still read it
+    for (int g = 0; g < AMM_MAX_GROUPS; ++g) {
+        std::vector<int> &m = ctx->groups[g].forces;
+        m.erase(std::remove(m.begin(), m.end(), id), m.end());
+    }
+    amm_family(type).free(obj);
+    ctx->forces[id] = ForceObj();
+    return 0;
+}
+
+extern "C" {
+
+// Custom{Bond,Angle,Torsion,External}Force(any energy text): the compiled text (atomsmm_amd/expr.py: compile_term), the terms' atoms
+// and their parameters, parameter-major
+int amm_term_expr_create(amm_ctx *ctx, int32_t kind, const int32_t *code, int32_t ncode, const double *consts, int32_t nconst,
+                         const double *globals, int32_t nglobal, const int32_t *h_idx, const double *h_params, int32_t n_terms,
+                         int32_t n_params, int32_t periodic, int32_t *force_id) {
+    auto fail = [](const std::string &what) {
+        amm_set_error("amm_term_expr_create: " + what);
+        return 1;
+    };
+    if (!ctx || !code || !force_id || (nconst > 0 && !consts) || (nglobal > 0 && !globals) || n_terms < 0 || (n_terms > 0 && !h_idx)) return fail("null argument");
+    if (kind < AMM_TERM_BOND || kind > AMM_TERM_EXTERNAL) return fail("unknown kind " + std::to_string(kind));
+    if (n_params < 0 || n_params > AMM_TERM_MAX_PARAMS) return fail(std::to_string(n_params) + " per-term parameters (limit " + std::to_string(AMM_TERM_MAX_PARAMS) + ")");
+    if (n_params > 0 && n_terms > 0 && !h_params) return fail("null parameter array");
+    if (periodic && kind == AMM_TERM_EXTERNAL) return fail("an external term reads raw coordinates: it is never periodic");
+    if (periodic && !ctx->has_box) return fail("periodic terms, but the context has no periodic box");
+    if (amm_expr_program_validate("amm_term_expr_create", code, ncode, nconst, nglobal, kind == AMM_TERM_EXTERNAL ? 3 : 1, n_params)) return 1;
+    for (int t = 0; t < n_terms; ++t)
+        for (int r = 0; r < amm_term_arity(kind); ++r) {
+            const int a = h_idx[(size_t)t * 4 + r];
+            if (a < 0 || a >= ctx->n) return fail("atom index " + std::to_string(a) + " of term " + std::to_string(t) + " is out of range");
+        }
+    AMM_HIP(hipSetDevice(ctx->device));
+    TermExprForce *tf = new TermExprForce();
+    tf->kind = kind;
+    tf->periodic = periodic ? 1 : 0;
+    tf->n_terms = n_terms;
+    tf->n_params = n_params;
+    std::memset(&tf->h, 0, sizeof(tf->h));
+    tf->h.ncode = ncode;
+    tf->h.nconst = nconst;
+    tf->h.nglobal = nglobal;
+    std::copy(code, code + ncode, tf->h.code);
+    std::copy(consts, consts + nconst, tf->h.consts);
+    std::copy(globals, globals + nglobal, tf->h.globals);
+    if (amm_term_expr_build(ctx, tf, h_idx, h_params)) {
+        amm_term_expr_free(tf);
+        return 1;
+    }
+    *force_id = amm_force_register(ctx, AMM_FORCE_TERM_EXPR, tf);
+    return 0;
+}
+
+int amm_term_expr_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal) {
+    TermExprForce *tf = amm_force_get<TermExprForce>(ctx, force_id, "amm_term_expr_set_globals");
+    if (!tf) return 1;
+    if (nglobal != tf->h.nglobal || (nglobal > 0 && !globals)) {
+        amm_set_error("amm_term_expr_set_globals: the program reads " + std::to_string(tf->h.nglobal) + " globals, " + std::to_string(nglobal) + " given");
+        return 1;
+    }
+    std::copy(globals, globals + nglobal, tf->h.globals);
+    return amm_term_expr_upload(ctx, tf, true);
+}
+
+int amm_term_expr_set_params(amm_ctx *ctx, int32_t force_id, const double *h_params, int32_t n_terms, int32_t n_params) {
+    TermExprForce *tf = amm_force_get<TermExprForce>(ctx, force_id, "amm_term_expr_set_params");
+    if (!tf) return 1;
+    if (n_terms != tf->n_terms || n_params != tf->n_params || ((size_t)n_terms * n_params > 0 && !h_params)) {
+        amm_set_error("amm_term_expr_set_params: the force has " + std::to_string(tf->n_terms) + " terms of " + std::to_string(tf->n_params) +
+                      " parameters, " + std::to_string(n_terms) + " x " + std::to_string(n_params) + " given");
+        return 1;
+    }
+    return amm_term_expr_upload_params(ctx, tf, h_params);
+}
+
+int amm_term_expr_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_TERM_EXPR, "amm_term_expr_release"); }
+
+// CustomCVForce(any energy text): the compiled text (atomsmm_amd/expr.py: compile_cv) and the inner forces, one per collective variable
+int amm_cv_create(amm_ctx *ctx, const int32_t *inner_ids, int32_t n_cv, int32_t n_deriv, const int32_t *code, int32_t ncode,
+                  const double *consts, int32_t nconst, const double *globals, int32_t nglobal, int32_t *force_id) {
+    if (!ctx || !inner_ids || !code || !force_id || (nconst > 0 && !consts) || (nglobal > 0 && !globals)) {
+        amm_set_error("amm_cv_create: null argument");
+        return 1;
+    }
+    CvForce *cv = nullptr;
+    if (amm_cv_create_impl(ctx, inner_ids, n_cv, n_deriv, code, ncode, consts, nconst, globals, nglobal, &cv)) return 1;
+    *force_id = amm_force_register(ctx, AMM_FORCE_CV, cv);
+    return 0;
+}
+
+int amm_cv_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal) {
+    CvForce *cv = amm_force_get<CvForce>(ctx, force_id, "amm_cv_set_globals");
+    return cv ? amm_cv_set_globals_impl(ctx, cv, globals, nglobal) : 1;
+}
+
+int amm_cv_set_variables(amm_ctx *ctx, int32_t force_id, const double *values, int32_t n_deriv) {
+    CvForce *cv = amm_force_get<CvForce>(ctx, force_id, "amm_cv_set_variables");
+    return cv ? amm_cv_set_variables_impl(ctx, cv, values, n_deriv) : 1;
+}
+
+int amm_cv_values(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *h_out) {
+    CvForce *cv = amm_force_get<CvForce>(ctx, force_id, "amm_cv_values");
+    if (!cv) return 1;
+    if (!d_pos || !h_out) {
+        amm_set_error("amm_cv_values: null argument");
+        return 1;
+    }
+    return amm_cv_values_impl(ctx, cv, d_pos, h_out);
+}
+
+int amm_cv_energy_derivative(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *d_out) {
+    CvForce *cv = amm_force_get<CvForce>(ctx, force_id, "amm_cv_energy_derivative");
+    if (!cv) return 1;
+    if (!d_pos || !d_out) {
+        amm_set_error("amm_cv_energy_derivative: null argument");
+        return 1;
+    }
+    return amm_cv_energy_derivative_impl(ctx, cv, d_pos, d_out);
+}
+
+int amm_cv_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_CV, "amm_cv_release"); }
+
+// CustomCompoundBondForce / CustomCentroidBondForce(any energy text): the compiled text and its variable table
+// (atomsmm_amd/expr.py: compile_compound), the bonds' particles (or groups) and parameters, and for centroid bonds the groups
+int amm_compound_create(amm_ctx *ctx, int32_t n_slots, const int32_t *code, int32_t ncode, const double *consts, int32_t nconst,
+                        const double *globals, int32_t nglobal, const int32_t *var_kinds, const int32_t *var_slots, int32_t n_vars,
+                        const int32_t *h_idx, const double *h_params, int32_t n_bonds, int32_t n_params, int32_t periodic,
+                        const int32_t *group_ptr, const int32_t *group_atoms, const double *group_weights, int32_t n_groups,
+                        int32_t *force_id) {
+    if (!ctx || !code || !force_id || (nconst > 0 && !consts) || (nglobal > 0 && !globals) || (n_vars > 0 && (!var_kinds || !var_slots)) ||
+        (n_bonds > 0 && !h_idx)) {
+        amm_set_error("amm_compound_create: null argument");
+        return 1;
+    }
+    CompoundForce *cf = nullptr;
+    if (amm_compound_create_impl(ctx, n_slots, code, ncode, consts, nconst, globals, nglobal, var_kinds, var_slots, n_vars, h_idx, h_params,
+                                 n_bonds, n_params, periodic, group_ptr, group_atoms, group_weights, n_groups, &cf))
+        return 1;
+    *force_id = amm_force_register(ctx, AMM_FORCE_COMPOUND, cf);
+    return 0;
+}
+
+int amm_compound_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal) {
+    CompoundForce *cf = amm_force_get<CompoundForce>(ctx, force_id, "amm_compound_set_globals");
+    return cf ? amm_compound_set_globals_impl(ctx, cf, globals, nglobal) : 1;
+}
+
+int amm_compound_set_params(amm_ctx *ctx, int32_t force_id, const double *h_params, int32_t n_bonds, int32_t n_params) {
+    CompoundForce *cf = amm_force_get<CompoundForce>(ctx, force_id, "amm_compound_set_params");
+    return cf ? amm_compound_set_params_impl(ctx, cf, h_params, n_bonds, n_params) : 1;
+}
+
+int amm_compound_set_weights(amm_ctx *ctx, int32_t force_id, const double *weights, int32_t n_members) {
+    CompoundForce *cf = amm_force_get<CompoundForce>(ctx, force_id, "amm_compound_set_weights");
+    return cf ? amm_compound_set_weights_impl(ctx, cf, weights, n_members) : 1;
+}
+
+int amm_compound_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_COMPOUND, "amm_compound_release"); }
+
+// GBSAOBCForce in free space (csrc/gb.hip): addParticle(charge, radius, scale) x n, the two dielectrics, the surface-area energy and
+// the cutoff (rc <= 0: NoCutoff)
+int amm_gb_create(amm_ctx *ctx, const double *h_q, const double *h_radius, const double *h_scale, double eps_in, double eps_out,
+                  double sa_energy, double rc, int32_t *force_id) {
+    if (!ctx || !h_q || !h_radius || !h_scale || !force_id) {
+        amm_set_error("amm_gb_create: null argument");
+        return 1;
+    }
+    AMM_HIP(hipSetDevice(ctx->device));
+    GbForce *gb = nullptr;
+    if (amm_gb_create_impl(ctx, h_q, h_radius, h_scale, eps_in, eps_out, sa_energy, rc, &gb)) return 1;
+    *force_id = amm_force_register(ctx, AMM_FORCE_GB, gb);
+    return 0;
+}
+
+int amm_gb_set_params(amm_ctx *ctx, int32_t force_id, const double *h_q, const double *h_radius, const double *h_scale, double eps_in,
+                      double eps_out, double sa_energy, double rc) {
+    GbForce *gb = amm_force_get<GbForce>(ctx, force_id, "amm_gb_set_params");
+    return gb ? amm_gb_set_params_impl(ctx, gb, h_q, h_radius, h_scale, eps_in, eps_out, sa_energy, rc) : 1;
+}
+
+int amm_gb_born_radii(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *h_out) {
+    GbForce *gb = amm_force_get<GbForce>(ctx, force_id, "amm_gb_born_radii");
+    if (!gb) return 1;
+    if (!d_pos || !h_out) {
+        amm_set_error("amm_gb_born_radii: null argument");
+        return 1;
+    }
+    return amm_gb_born_radii_impl(ctx, gb, d_pos, h_out);
+}
+
+int amm_gb_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_GB, "amm_gb_release"); }
+
+// CMAPTorsionForce (csrc/cmap.hip): addMap x n_maps as the bicubic coefficients of atomsmm_amd/tables.py (cmap_coefficients),
+// addTorsion x n_terms as a map index and eight atoms each
+int amm_cmap_create(amm_ctx *ctx, int32_t n_maps, const int32_t *h_sizes, const double *h_coeffs, const int32_t *h_map_of_term,
+                    const int32_t *h_idx, int32_t n_terms, int32_t periodic, int32_t *force_id) {
+    if (!ctx || !force_id || (n_maps > 0 && (!h_sizes || !h_coeffs)) || (n_terms > 0 && (!h_map_of_term || !h_idx))) {
+        amm_set_error("amm_cmap_create: null argument");
+        return 1;
+    }
+    CmapForce *cm = nullptr;
+    if (amm_cmap_create_impl(ctx, n_maps, h_sizes, h_coeffs, h_map_of_term, h_idx, n_terms, periodic, &cm)) return 1;
+    *force_id = amm_force_register(ctx, AMM_FORCE_CMAP, cm);
+    return 0;
+}
+
+int amm_cmap_set_params(amm_ctx *ctx, int32_t force_id, const double *h_coeffs, const int32_t *h_map_of_term, int32_t n_maps, int32_t n_terms) {
+    CmapForce *cm = amm_force_get<CmapForce>(ctx, force_id, "amm_cmap_set_params");
+    return cm ? amm_cmap_set_params_impl(ctx, cm, h_coeffs, h_map_of_term, n_maps, n_terms) : 1;
+}
+
+int amm_cmap_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_CMAP, "amm_cmap_release"); }
+
+}   // extern "C"

@@ -618,8 +618,8 @@ int amm_small_group_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, 
         // outside the molecules too); the caller reads this force's rows from the force's own buffer
         const ClusterList *cl = nullptr;
         for (auto &fo : ctx->forces)
-            if (fo.type == 1 && fo.pair->cl && fo.pair->cl->built && fo.pair->last_kind >= 1 && !fo.pair->host) {
-                cl = fo.pair->cl;
+            if (const PairForce *o = fo.pair(); o && o->cl && o->cl->built && o->last_kind >= 1 && !o->host) {
+                cl = o->cl;
                 break;
             }
         if (cl) {
@@ -741,8 +741,8 @@ int amm_small_group_energy_states(amm_ctx *ctx, PairForce *pf, const double *d_p
         // (the companion an evaluation would take: its candidates serve only if they were made against it)
         const ClusterList *cl = nullptr;
         for (auto &fo : ctx->forces)
-            if (fo.type == 1 && fo.pair->cl && fo.pair->cl->built && fo.pair->last_kind >= 1 && !fo.pair->host) {
-                cl = fo.pair->cl;
+            if (const PairForce *o = fo.pair(); o && o->cl && o->cl->built && o->last_kind >= 1 && !o->host) {
+                cl = o->cl;
                 break;
             }
         if (cl && sg->companion == (const void *)cl) {

@@ -2350,17 +2350,13 @@ int amm_pair_free(PairForce *pf) {
                     pf->d_row_order, pf->d_member, pf->d_active, pf->d_cell_sets, pf->d_nnb_lj, pf->d_mol_first, pf->d_rest_idx};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
-    for (PairForce::TabImage &im : pf->tab_image) {
+    for (PairForce::TabImage &im : pf->tab_image)
         if (im.d) (void)hipFree(im.d);
-        im = PairForce::TabImage();
-    }
     for (hipEvent_t e : pf->ev) (void)hipEventDestroy(e);
     if (pf->cl) amm_cluster_free(pf->cl);
-    pf->cl = nullptr;
     if (pf->small) amm_small_group_free(pf->small);
-    pf->small = nullptr;
     amm_pair_expr_free(pf->expr);
-    pf->expr = nullptr;
+    delete pf;
     return 0;
 }
 

@@ -59,7 +59,7 @@ struct OpRun {
     bool is_kick(int k) const { return k < n_ops && ops[k].op == AMM_OP_KICK; }
     // the group's first member when that is a pair force (further members are added after its pass)
     PairForce *first_pair(const GroupDef &g) const {
-        return !g.forces.empty() && ctx->forces[g.forces[0]].type == AMM_FORCE_PAIR ? ctx->forces[g.forces[0]].pair : nullptr;
+        return !g.forces.empty() ? ctx->forces[g.forces[0]].pair() : nullptr;
     }
     // the group is exactly one pair force with a neighbour list (a free-space force has none: no plan rides on it, no slices)
     PairForce *sole_listed_pair(const GroupDef &g) const {
@@ -68,9 +68,8 @@ struct OpRun {
     }
     // the group is exactly one bond-list set that this rank evaluates for every atom (a sliced set on several ranks: its rows only)
     BondedSet *sole_unsliced_bonded(const GroupDef &g) const {
-        if (g.forces.size() != 1 || ctx->forces[g.forces[0]].type != AMM_FORCE_BONDED) return nullptr;
-        BondedSet *bs = ctx->forces[g.forces[0]].bonded;
-        return bs->sliced && ctx->world > 1 ? nullptr : bs;
+        BondedSet *bs = g.forces.size() == 1 ? ctx->forces[g.forces[0]].bonded() : nullptr;
+        return bs && bs->sliced && ctx->world > 1 ? nullptr : bs;
     }
     // The buffers of a run of kicks: the deferred kicks first (`lead`), then ops[from, to) -- all KICKs -- appended at index n of
     // fa / fb / plus / coef.  Stops at the first kick with an unbound buffer and answers false; what follows is the caller's to decide
@@ -110,11 +109,11 @@ struct OpRun {
             GroupDef &g = ctx->groups[gi];
             if (g.slot < 0 || ctx->slots[g.slot] != buf || g.forces.empty()) continue;
             bool bonded_only = true;
-            for (int fid : g.forces) bonded_only = bonded_only && ctx->forces[fid].type == AMM_FORCE_BONDED && !ctx->forces[fid].bonded->sliced;
+            for (int fid : g.forces) bonded_only = bonded_only && ctx->forces[fid].bonded() && !ctx->forces[fid].bonded()->sliced;
             if (!bonded_only) break;
             bool first = true;
             for (int fid : g.forces) {
-                if (amm_bonded_eval_impl(ctx, ctx->forces[fid].bonded, ctx->d_x, ctx->slots[g.slot], first ? 0 : 1, nullptr)) return FAILED;
+                if (amm_bonded_eval_impl(ctx, ctx->forces[fid].bonded(), ctx->d_x, ctx->slots[g.slot], first ? 0 : 1, nullptr)) return FAILED;
                 first = false;
             }
             forget_own_only(buf);
@@ -460,9 +459,10 @@ struct OpRun {
         PairForce *ps = nullptr;
         bool plain = g->forces.size() >= 1 && g->forces.size() <= 2;
         for (int fid : g->forces) {
-            ForceObj &fo = ctx->forces[fid];
-            if (fo.type == AMM_FORCE_BONDED && !bs) bs = fo.bonded;
-            else if (fo.type == AMM_FORCE_PAIR && !ps && fo.pair->small && ctx->opt_small_group && !fo.pair->built && amm_small_group_supported(fo.pair)) ps = fo.pair;
+            const ForceObj &fo = ctx->forces[fid];
+            PairForce *pf = fo.pair();
+            if (fo.bonded() && !bs) bs = fo.bonded();
+            else if (pf && !ps && pf->small && ctx->opt_small_group && !pf->built && amm_small_group_supported(pf)) ps = pf;
             else plain = false;
         }
         double *buf = ctx->slots[g->slot];
@@ -567,7 +567,7 @@ struct OpRun {
         // (guarded near force, sign -1) shares the total's neighbour list, both are evaluated in ONE traversal that
         // accumulates into the same buffer (the reference, and OpenMM, run two passes)
         const size_t nf = g.forces.size();
-        auto pair_of = [&](size_t i) { return ctx->forces[g.forces[i]].type == AMM_FORCE_PAIR ? ctx->forces[g.forces[i]].pair : nullptr; };
+        auto pair_of = [&](size_t i) { return ctx->forces[g.forces[i]].pair(); };
         std::vector<char> done(nf, 0);
         bool first = true;
         for (size_t j = 0; j < nf; ++j) {

@@ -9,7 +9,7 @@
 #pragma once
 #include "pair_expr_vm.h"
 
-// host side of one such force (ForceObj::term)
+// host side of one such force (AMM_FORCE_TERM_EXPR)
 struct TermExprForce {
     int kind = 0, periodic = 0;
     int n_terms = 0, n_params = 0, arity = 0;
