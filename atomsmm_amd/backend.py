@@ -60,6 +60,8 @@ EXPORTS = [
     'amm_run_rule_stats',
     'amm_gb_create', 'amm_gb_set_params', 'amm_gb_born_radii', 'amm_gb_release',
     'amm_cmap_create', 'amm_cmap_set_params', 'amm_cmap_release',
+    'amm_custom_gb_create', 'amm_custom_gb_set_params', 'amm_custom_gb_set_globals', 'amm_custom_gb_set_tables', 'amm_custom_gb_values',
+    'amm_custom_gb_release',
     'amm_vsite_define', 'amm_vsite_place', 'amm_vsite_spread', 'amm_vsite_stats',
 ]
 
@@ -200,6 +202,12 @@ def lib():
         L.amm_cmap_create.argtypes = [vp, C.c_int32, ip, dp, ip, ip, C.c_int32, C.c_int32, ip]
         L.amm_cmap_set_params.argtypes = [vp, C.c_int32, dp, ip, C.c_int32, C.c_int32]
         L.amm_cmap_release.argtypes = [vp, C.c_int32]
+        L.amm_custom_gb_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, ip, ip, ip, dp, ip, dp, C.c_int32, dp, ip, C.c_int32, C.c_double, ip]
+        L.amm_custom_gb_set_params.argtypes = [vp, C.c_int32, dp, C.c_int32, C.c_int32]
+        L.amm_custom_gb_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
+        L.amm_custom_gb_set_tables.argtypes = [vp, C.c_int32, C.c_int32, ip, ip, dp, ip, dp, C.c_int32]
+        L.amm_custom_gb_values.argtypes = [vp, C.c_int32, vp, dp]
+        L.amm_custom_gb_release.argtypes = [vp, C.c_int32]
         L.amm_cv_create.argtypes = [vp, ip, C.c_int32, C.c_int32, ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip]
         L.amm_cv_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
         L.amm_cv_set_variables.argtypes = [vp, C.c_int32, dp, C.c_int32]
@@ -401,6 +409,11 @@ class HipContext:
     def pair_expr_set_tables(self, fid, tables):
         """The tabulated functions of a generic pair force, in the force's function order: one (kind, nx, ny, lo, hi, doubles) each
         (atomsmm_amd/tables.py: device_table).  Again with new values of the same sizes: updateParametersInContext."""
+        _chk(lib().amm_pair_expr_set_tables(self.h, fid, *self._table_arguments(tables)))
+
+    def _table_arguments(self, tables):
+        """(n_tables, kinds, dims, ranges, offsets, data, n_data) of amm_pair_expr_set_tables / amm_custom_gb_set_tables; the arrays
+        stay alive in self._table_keep until the next call."""
         kinds = np.array([t[0] for t in tables], dtype=np.int32)
         dims = np.array([[t[1], t[2]] for t in tables], dtype=np.int32).reshape(-1)
         ranges = np.array([[t[3], t[4]] for t in tables], dtype=np.float64).reshape(-1)
@@ -414,7 +427,8 @@ class HipContext:
         r_, rp = _hd(ranges if len(tables) else [0.0])
         o_, op = _hi(offsets if len(tables) else [0])
         v_, vp = _hd(data if len(data) else [0.0])
-        _chk(lib().amm_pair_expr_set_tables(self.h, fid, len(tables), kp, dmp, rp, op, vp, len(data)))
+        self._table_keep = (k_, d_, r_, o_, v_)
+        return len(tables), kp, dmp, rp, op, vp, len(data)
 
     def pair_share_list(self, fid, host_fid):
         _chk(lib().amm_pair_share_list(self.h, fid, host_fid))
@@ -605,6 +619,56 @@ class HipContext:
     def cmap_release(self, fid):
         """Free a CMAP force (its id is retired)."""
         _chk(lib().amm_cmap_release(self.h, fid))
+
+    def custom_gb_create(self, n_values, types, programs, globals_, params, excl_pairs=None, rc=0.0):
+        """A CustomGBForce in free space (csrc/custom_gb.hip).  types: SingleParticle 0 / ParticlePair 1 / ParticlePairNoExclusions 2 of
+        the n_values computed values, then of the energy terms; programs: their (code, consts), as expr.compile_custom_gb emits them;
+        globals_: the values of the force's globals in its order; params: n_params x n, parameter-major; rc <= 0: NoCutoff."""
+        types = [int(t) for t in types]
+        assert len(types) == len(programs) and 0 <= int(n_values) <= len(types)
+        code_ptr = np.concatenate([[0], np.cumsum([len(c) for c, _ in programs])]).astype(np.int32)
+        const_ptr = np.concatenate([[0], np.cumsum([len(k) for _, k in programs])]).astype(np.int32)
+        code = np.concatenate([np.asarray(c, dtype=np.int32).reshape(-1) for c, _ in programs] + [np.zeros(0, np.int32)])
+        consts = np.concatenate([np.asarray(k, dtype=np.float64).reshape(-1) for _, k in programs] + [np.zeros(0)])
+        par = np.asarray(params, dtype=np.float64).reshape(-1, self.n) if np.size(params) else np.zeros((0, self.n))
+        t_, tp = _hi(types if types else [0])
+        c_, cp = _hi(code if len(code) else [0])
+        cp_, cpp = _hi(code_ptr)
+        k_, kp = _hd(consts if len(consts) else [0.0])
+        kp_, kpp = _hi(const_ptr)
+        g_, gp = _hd(globals_ if len(globals_) else [0.0])
+        p_, pp = _hd(par if par.size else [0.0])
+        ex = np.zeros((0, 2), np.int32) if excl_pairs is None else np.asarray(excl_pairs, dtype=np.int32).reshape(-1, 2)
+        ex_, exp_ = _hi(ex if len(ex) else [0])
+        fid = C.c_int32(-1)
+        _chk(lib().amm_custom_gb_create(self.h, len(par), int(n_values), len(types) - int(n_values), tp, cp, cpp, kp, kpp, gp, len(globals_),
+                                        pp, exp_, len(ex), float(rc), C.byref(fid)))
+        return fid.value
+
+    def custom_gb_set_params(self, fid, params):
+        """All per-particle values again (n_params x n, parameter-major)."""
+        par = np.asarray(params, dtype=np.float64).reshape(-1, self.n) if np.size(params) else np.zeros((0, self.n))
+        p_, pp = _hd(par if par.size else [0.0])
+        _chk(lib().amm_custom_gb_set_params(self.h, fid, pp, len(par), self.n))
+
+    def custom_gb_set_globals(self, fid, globals_):
+        g_, gp = _hd(globals_ if len(globals_) else [0.0])
+        _chk(lib().amm_custom_gb_set_globals(self.h, fid, gp, len(globals_)))
+
+    def custom_gb_set_tables(self, fid, tables):
+        """The tabulated functions of such a force, in its function order: one (kind, nx, ny, lo, hi, doubles) each, as
+        pair_expr_set_tables takes them."""
+        _chk(lib().amm_custom_gb_set_tables(self.h, fid, *self._table_arguments(tables)))
+
+    def custom_gb_values(self, fid, pos, n_values):
+        """The computed values at `pos` as a numpy array [n_values][n] (runs the value passes; waits for the stream)."""
+        out = np.zeros((max(int(n_values), 1), self.n), dtype=np.float64)
+        _chk(lib().amm_custom_gb_values(self.h, fid, _ptr(pos), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out[:int(n_values)]
+
+    def custom_gb_release(self, fid):
+        """Free a custom generalized-Born force (its id is retired)."""
+        _chk(lib().amm_custom_gb_release(self.h, fid))
 
     def cv_create(self, inner_ids, n_deriv, code, consts, globals_):
         """A CustomCVForce with any energy text (csrc/cv.hip): the ids of the inner forces in the order of the collective variables

@@ -1495,6 +1495,13 @@ int amm_set_option(amm_ctx *ctx, const char *name, double value) {
         }
         ctx->opt_gb_lpr = v;
     }
+    else if (k == "cgb_lanes_per_row") {
+        if (v < 0 || v > 64 || (v & (v - 1))) {
+            amm_set_error("amm_set_option: cgb_lanes_per_row is 0 (automatic) or a power of two up to 64");
+            return 1;
+        }
+        ctx->opt_cgb_lpr = v;
+    }
     else {
         amm_set_error("amm_set_option: unknown option '" + k + "'");
         return 1;

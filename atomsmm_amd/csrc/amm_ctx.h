@@ -248,11 +248,13 @@ struct CvForce;       // cv.hip: a CustomCVForce -- K inner forces and the compi
 struct CompoundForce; // compound.hip: a CustomCompoundBondForce / CustomCentroidBondForce -- bonds over several particles or centres
 struct GbForce;       // gb.hip: a GBSAOBCForce -- generalized-Born (OBC2) implicit solvent with a surface-area term, free space only
 struct CmapForce;     // cmap.hip: a CMAPTorsionForce -- bicubic maps over pairs of dihedrals
+struct CustomGbForce; // custom_gb.hip: a CustomGBForce -- computed per-particle values and energy terms written as text, free space only
 // The force families.  A family is described ONCE: its tag here, the struct that goes with the tag in amm_force_type, and its row of
 // the table behind amm_family (families.hip).  The typed lookup and its refusals, amm_force_eval_dispatch, release, amm_destroy, amm_set_slice and
 // cv.hip's messages all read the row -- a new family adds these three lines, its own .hip file and its extern "C" entry points.
+// Nine families today (and the tag of a released id).
 enum : int { AMM_FORCE_RELEASED = 0, AMM_FORCE_PAIR = 1, AMM_FORCE_BONDED = 2, AMM_FORCE_PME = 3, AMM_FORCE_TERM_EXPR = 4, AMM_FORCE_CV = 5,
-             AMM_FORCE_COMPOUND = 6, AMM_FORCE_GB = 7, AMM_FORCE_CMAP = 8, AMM_FORCE_TYPES = 9 };   // ForceObj::type, the row amm_family returns
+             AMM_FORCE_COMPOUND = 6, AMM_FORCE_GB = 7, AMM_FORCE_CMAP = 8, AMM_FORCE_CUSTOM_GB = 9, AMM_FORCE_TYPES = 10 };   // ForceObj::type, the row amm_family returns
 template <class T> inline constexpr int amm_force_type = -1;
 template <> inline constexpr int amm_force_type<PairForce> = AMM_FORCE_PAIR;
 template <> inline constexpr int amm_force_type<BondedSet> = AMM_FORCE_BONDED;
@@ -262,6 +264,7 @@ template <> inline constexpr int amm_force_type<CvForce> = AMM_FORCE_CV;
 template <> inline constexpr int amm_force_type<CompoundForce> = AMM_FORCE_COMPOUND;
 template <> inline constexpr int amm_force_type<GbForce> = AMM_FORCE_GB;
 template <> inline constexpr int amm_force_type<CmapForce> = AMM_FORCE_CMAP;
+template <> inline constexpr int amm_force_type<CustomGbForce> = AMM_FORCE_CUSTOM_GB;
 struct ForceFamily {
     const char *noun, *tag, *prefix;   // "a CMAP force", "AMM_FORCE_CMAP", "amm_cmap_*"
     const char *bad_id;                // what the family's entry points say of an id that is not theirs (behind "<entry point>: " if they name themselves)
@@ -424,6 +427,7 @@ struct amm_ctx {
     int opt_fuse_rows = 1;              // molecule rows: host + guest force of a shared list in ONE launch when a fused kernel exists
     int opt_terms_from = 8192, opt_no_term_lanes = 0;
     int opt_gb_lpr = 0;                 // lanes per row of the generalized-Born passes (gb.hip): 0 = amm_free_lanes_per_row(n); 1, 2, 4 .. 64
+    int opt_cgb_lpr = 0;                // ... and of the custom generalized-Born passes (custom_gb.hip)
     ListWatch watched[AMM_MAX_WATCH];
     int n_watched = 0;
     int device = 0;
@@ -602,6 +606,17 @@ int amm_cmap_create_impl(amm_ctx *ctx, int n_maps, const int32_t *h_sizes, const
 int amm_cmap_set_params_impl(amm_ctx *ctx, CmapForce *cm, const double *h_coeffs, const int32_t *h_map_of_term, int n_maps, int n_terms);
 int amm_cmap_eval_impl(amm_ctx *ctx, CmapForce *cm, const double *d_pos, double *d_force, int accumulate, double *d_energy);
 void amm_cmap_free(CmapForce *cm);
+// custom_gb.hip: a force of type AMM_FORCE_CUSTOM_GB (types / code_ptr / const_ptr: the values' programs, then the energy terms')
+int amm_custom_gb_create_impl(amm_ctx *ctx, int n_params, int n_values, int n_terms, const int32_t *types, const int32_t *code,
+                              const int32_t *code_ptr, const double *consts, const int32_t *const_ptr, const double *globals, int nglobal,
+                              const double *h_params, const int32_t *h_excl, int n_excl, double rc, CustomGbForce **out);
+int amm_custom_gb_set_params_impl(amm_ctx *ctx, CustomGbForce *cg, const double *h_params, int n_params, int n_atoms);
+int amm_custom_gb_set_globals_impl(amm_ctx *ctx, CustomGbForce *cg, const double *globals, int nglobal);
+int amm_custom_gb_set_tables_impl(amm_ctx *ctx, CustomGbForce *cg, int n_tables, const int32_t *kinds, const int32_t *dims, const double *ranges,
+                                  const int32_t *offsets, const double *data, int n_data);
+int amm_custom_gb_eval_impl(amm_ctx *ctx, CustomGbForce *cg, const double *d_pos, double *d_force, int accumulate, double *d_energy);
+int amm_custom_gb_values_impl(amm_ctx *ctx, CustomGbForce *cg, const double *d_pos, double *h_out);
+void amm_custom_gb_free(CustomGbForce *cg);
 // implemented in pair.hip / cells.hip / bonded.hip / integrate.hip
 int amm_pair_build_consts(const amm_pair_desc &d, PairConsts &pc);
 int amm_pair_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double *d_force, int accumulate,

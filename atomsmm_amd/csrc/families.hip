@@ -1,6 +1,7 @@
 // atomsmm_amd/csrc/families.hip -- the table of force families (amm_ctx.h: ForceFamily) and everything derived from it: the typed lookup
 // with its refusals, registration, release and the dispatch of an evaluation; then the extern "C" entry points of the families whose
-// implementation is a .hip file of its own (term expressions, collective variables, compound bonds, generalized Born, CMAP).
+// implementation is a .hip file of its own (term expressions, collective variables, compound bonds, generalized Born, CMAP, custom
+// generalized Born).
 #include <algorithm>
 #include <cstring>
 
@@ -21,7 +22,7 @@ static int released_eval(amm_ctx *, void *, const double *, double *, int, doubl
 }
 static void released_free(void *) {}
 
-// One row per AMM_FORCE_* value, in the enum's order: noun phrase, tag, entry points, bad-id wording, single rank, eval, free.
+// One row per AMM_FORCE_* value (a released id and the nine families), in the enum's order: noun phrase, tag, entry points, bad-id wording, single rank, eval, free.
 const ForceFamily &amm_family(int type) {
     static const ForceFamily rows[AMM_FORCE_TYPES] = {
         {"a released id", "AMM_FORCE_RELEASED", "none", "released force id", false, released_eval, released_free},
@@ -42,6 +43,8 @@ const ForceFamily &amm_family(int type) {
          eval_as<GbForce, amm_gb_eval_impl>, free_as<GbForce, amm_gb_free>},
         {"a CMAP force", "AMM_FORCE_CMAP", "amm_cmap_*", "not the id of a CMAP force (AMM_FORCE_CMAP)", true,
          eval_as<CmapForce, amm_cmap_eval_impl>, free_as<CmapForce, amm_cmap_free>},
+        {"a custom generalized-Born force", "AMM_FORCE_CUSTOM_GB", "amm_custom_gb_*", "not the id of a custom generalized-Born force (AMM_FORCE_CUSTOM_GB)", true,
+         eval_as<CustomGbForce, amm_custom_gb_eval_impl>, free_as<CustomGbForce, amm_custom_gb_free>},
     };
     return rows[type];
 }
@@ -290,5 +293,57 @@ int amm_cmap_set_params(amm_ctx *ctx, int32_t force_id, const double *h_coeffs, 
 }
 
 int amm_cmap_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_CMAP, "amm_cmap_release"); }
+
+// CustomGBForce in free space (csrc/custom_gb.hip): the programs of atomsmm_amd/expr.py (compile_custom_gb) -- the computed values',
+// then the energy terms', concatenated -- the per-particle parameters, parameter-major, the exclusions and the cutoff (rc <= 0: NoCutoff)
+int amm_custom_gb_create(amm_ctx *ctx, int32_t n_params, int32_t n_values, int32_t n_terms, const int32_t *types, const int32_t *code,
+                         const int32_t *code_ptr, const double *consts, const int32_t *const_ptr, const double *globals, int32_t nglobal,
+                         const double *h_params, const int32_t *h_excl, int32_t n_excl, double rc, int32_t *force_id) {
+    const bool programs = n_values + n_terms > 0;
+    if (!ctx || !force_id || !code_ptr || !const_ptr || (programs && (!types || !code)) || (nglobal > 0 && !globals) || (n_params > 0 && !h_params) ||
+        (n_excl > 0 && !h_excl) || n_excl < 0) {
+        amm_set_error("amm_custom_gb_create: null argument");
+        return 1;
+    }
+    if (programs && const_ptr[n_values + n_terms] > 0 && !consts) {
+        amm_set_error("amm_custom_gb_create: null argument");
+        return 1;
+    }
+    AMM_HIP(hipSetDevice(ctx->device));
+    CustomGbForce *cg = nullptr;
+    if (amm_custom_gb_create_impl(ctx, n_params, n_values, n_terms, types, code, code_ptr, consts, const_ptr, globals, nglobal, h_params, h_excl,
+                                  n_excl, rc, &cg))
+        return 1;
+    *force_id = amm_force_register(ctx, AMM_FORCE_CUSTOM_GB, cg);
+    return 0;
+}
+
+int amm_custom_gb_set_params(amm_ctx *ctx, int32_t force_id, const double *h_params, int32_t n_params, int32_t n_atoms) {
+    CustomGbForce *cg = amm_force_get<CustomGbForce>(ctx, force_id, "amm_custom_gb_set_params");
+    return cg ? amm_custom_gb_set_params_impl(ctx, cg, h_params, n_params, n_atoms) : 1;
+}
+
+int amm_custom_gb_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal) {
+    CustomGbForce *cg = amm_force_get<CustomGbForce>(ctx, force_id, "amm_custom_gb_set_globals");
+    return cg ? amm_custom_gb_set_globals_impl(ctx, cg, globals, nglobal) : 1;
+}
+
+int amm_custom_gb_set_tables(amm_ctx *ctx, int32_t force_id, int32_t n_tables, const int32_t *kinds, const int32_t *dims, const double *ranges,
+                             const int32_t *offsets, const double *data, int32_t n_data) {
+    CustomGbForce *cg = amm_force_get<CustomGbForce>(ctx, force_id, "amm_custom_gb_set_tables");
+    return cg ? amm_custom_gb_set_tables_impl(ctx, cg, n_tables, kinds, dims, ranges, offsets, data, n_data) : 1;
+}
+
+int amm_custom_gb_values(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *h_out) {
+    CustomGbForce *cg = amm_force_get<CustomGbForce>(ctx, force_id, "amm_custom_gb_values");
+    if (!cg) return 1;
+    if (!d_pos || !h_out) {
+        amm_set_error("amm_custom_gb_values: null argument");
+        return 1;
+    }
+    return amm_custom_gb_values_impl(ctx, cg, d_pos, h_out);
+}
+
+int amm_custom_gb_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_CUSTOM_GB, "amm_custom_gb_release"); }
 
 }   // extern "C"

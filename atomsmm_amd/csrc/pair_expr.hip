@@ -145,7 +145,8 @@ int amm_pair_expr_validate(const int32_t *code, int ncode, int nconst, int nglob
     return amm_expr_program_validate("amm_pair_expr_create", code, ncode, nconst, nglobal, -1, 0);
 }
 
-int amm_expr_program_validate(const char *who, const int32_t *code, int ncode, int nconst, int nglobal, int term_vars, int term_params) {
+int amm_expr_program_validate(const char *who, const int32_t *code, int ncode, int nconst, int nglobal, int term_vars, int term_params,
+                              bool term_tables) {
     auto fail = [who](const std::string &what) {
         amm_set_error(std::string(who) + ": " + what);
         return 1;
@@ -165,7 +166,7 @@ int amm_expr_program_validate(const char *who, const int32_t *code, int ncode, i
         case X_TERM_VAR: pops = 0; if (pair) return fail("opcode " + std::to_string(op) + " is not a pair-expression op"); if (arg < 0 || arg >= term_vars) return fail("variable index out of range (the kind has " + std::to_string(term_vars) + ")"); break;
         case X_TERM_P: pops = 0; if (pair) return fail("opcode " + std::to_string(op) + " is not a pair-expression op"); if (arg < 0 || arg >= term_params) return fail("per-term parameter index out of range (the force has " + std::to_string(term_params) + ")"); break;
         case X_PAIR_P1: case X_PAIR_P2: pops = 0; if (!pair) return fail("opcode " + std::to_string(op) + " is not a term-expression op"); if (arg < 0 || arg >= AMM_PEXPR_PARAMS) return fail("per-particle parameter index out of range (limit " + std::to_string(AMM_PEXPR_PARAMS) + ")"); break;
-        case X_TAB_C1: case X_TAB_D1: case X_TAB_D2: pops = op == X_TAB_D2 ? 2 : 1; if (!pair) return fail("opcode " + std::to_string(op) + " is not a term-expression op"); if (arg < 0 || arg >= AMM_PEXPR_MAXTABLES) return fail("tabulated-function index out of range (limit " + std::to_string(AMM_PEXPR_MAXTABLES) + ")"); break;
+        case X_TAB_C1: case X_TAB_D1: case X_TAB_D2: pops = op == X_TAB_D2 ? 2 : 1; if (!pair && !term_tables) return fail("opcode " + std::to_string(op) + " is not a term-expression op"); if (arg < 0 || arg >= AMM_PEXPR_MAXTABLES) return fail("tabulated-function index out of range (limit " + std::to_string(AMM_PEXPR_MAXTABLES) + ")"); break;
         case X_LOAD: pops = 0; if (arg < 0 || arg >= AMM_PEXPR_LOCALS) return fail("local index out of range (limit " + std::to_string(AMM_PEXPR_LOCALS) + ")"); break;
         case X_STORE: pushes = 0; if (arg < 0 || arg >= AMM_PEXPR_LOCALS) return fail("local index out of range (limit " + std::to_string(AMM_PEXPR_LOCALS) + ")"); break;
         case X_ADD: case X_SUB: case X_MUL: case X_DIV: case X_POW: case X_MIN: case X_MAX: case X_ATAN2: pops = 2; break;

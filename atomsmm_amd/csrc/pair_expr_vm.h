@@ -151,12 +151,25 @@ struct PairLeaves {
     const PairTableDesc *tabs;
 };
 
+// Does a leaves type run the table words?  Only one that says so with a member kTables (and then has `tabs`): PairLeaves<true>, and
+// the CgbLeaves of custom_gb.hip, whose other leaves are the term words.  TermLeaves and CvLeaves declare nothing and compile the
+// words to nothing, as before.
+template <class L, class = void>
+struct pexpr_has_tables {
+    static constexpr bool value = false;
+};
+template <class L>
+struct pexpr_has_tables<L, decltype((void)L::kTables)> {
+    static constexpr bool value = L::kTables;
+};
+
 // E and its derivative along the leaves' seed.  code / consts / globals: the block's LDS copies.  The program is the same for every
 // lane, so the word is made scalar (readfirstlane) and the dispatch is a scalar branch.  The top of the stack lives in registers
 // (tv, td): a unary op touches no memory, a binary op reads one slot.  The elements below it are the lane's column of an LDS strip --
 // st[k * AMM_PEXPR_STRIDE], one (value, derivative) record of 16 bytes per slot, neighbouring lanes in neighbouring records
 // (conflict-free) -- and the locals are a private array.  `Leaves`: PairLeaves, or the TermLeaves of term_expr_vm.h -- the words of
-// the other kind compile to nothing -- or the CvLeaves of cv.hip, whose strip is 32 lanes wide (Leaves::kStride: lanes of the strip).
+// the other kind compile to nothing -- or the CvLeaves of cv.hip, whose strip is 32 lanes wide (Leaves::kStride: lanes of the strip), or
+// the CgbLeaves of custom_gb.hip (term words and table words).
 template <class Leaves>
 __device__ __forceinline__ void pexpr_run(const int *code, int ncode, const double *consts, const double *globals, const Leaves &leaves,
                                           double2 *st, double &E, double &dE) {
@@ -194,22 +207,18 @@ __device__ __forceinline__ void pexpr_run(const int *code, int ncode, const doub
         // switch to a tree of scalar compares and lays the cases out as it sees fit, and three more cases cost every other word of a
         // program without tables 1.6 % (as cases) to 8 % (behind a range test in the default) on the MI355X -- DESIGN.md 3.PT.
         case X_TAB_C1: case X_TAB_D1:
-            if constexpr (Leaves::kPair) {
-                if constexpr (Leaves::kTables) {
-                    const double2 f = pexpr_table(leaves.tabs, op, arg, tv, 0.0);
-                    tv = f.x;
-                    td = op == X_TAB_C1 ? pexpr_chain(f.y, td) : 0.0;
-                }
+            if constexpr (pexpr_has_tables<Leaves>::value) {
+                const double2 f = pexpr_table(leaves.tabs, op, arg, tv, 0.0);
+                tv = f.x;
+                td = op == X_TAB_C1 ? pexpr_chain(f.y, td) : 0.0;
             }
             break;
         case X_TAB_D2:
-            if constexpr (Leaves::kPair) {
-                if constexpr (Leaves::kTables) {
-                    const double2 lhs = st[(sp - 2) * Leaves::kStride];
-                    --sp;
-                    tv = pexpr_table(leaves.tabs, op, arg, lhs.x, tv).x;
-                    td = 0.0;
-                }
+            if constexpr (pexpr_has_tables<Leaves>::value) {
+                const double2 lhs = st[(sp - 2) * Leaves::kStride];
+                --sp;
+                tv = pexpr_table(leaves.tabs, op, arg, lhs.x, tv).x;
+                td = 0.0;
             }
             break;
         case X_LOAD: PEXPR_PUSH(lv[arg], ld[arg]); break;

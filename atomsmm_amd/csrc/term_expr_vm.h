@@ -26,9 +26,10 @@ struct TermExprForce {
 
 // non-zero + message (prefixed with `who`) naming the limit that a program exceeds, or a word that is no op of its kind / leaves the
 // stack or the locals.  term_vars < 0: a pair program (X_PAIR_* leaves); else a term program over that many variables and
-// term_params parameters (X_TERM_* leaves).
+// term_params parameters (X_TERM_* leaves); term_tables: ... that may also hold the table words (custom_gb.hip).
 int amm_term_arity(int kind);     // atoms of a term of kind AMM_TERM_*: 2, 3, 4, 1 (term_expr.hip)
-int amm_expr_program_validate(const char *who, const int32_t *code, int ncode, int nconst, int nglobal, int term_vars, int term_params);
+int amm_expr_program_validate(const char *who, const int32_t *code, int ncode, int nconst, int nglobal, int term_vars, int term_params,
+                              bool term_tables = false);
 
 #ifdef __HIPCC__
 // NV: the kind's variables.  3: x, y, z and the seed of this pass, indexed by the word's argument.

@@ -250,6 +250,8 @@ class _Entry:
                                     # the id is also in term_ids, term_expr is set, `program` is that of expr.compile_compound
         self.gb = None              # a GBSAOBCForce (csrc/gb.hip): its backend id, which is also in term_ids
         self.cmap = None            # a CMAPTorsionForce (csrc/cmap.hip): its backend id, which is also in term_ids
+        self.custom_gb = None       # a CustomGBForce (csrc/custom_gb.hip): dict(id, n_values); the id is also in term_ids, `program`
+                                    # is what expr.compile_custom_gb returned
 
 
 def slice_bounds(n_items, rank, world):
@@ -330,6 +332,7 @@ class Engine:
         self._coll = self.world > 1 or (os.environ.get('AMM_FORCE_COLLECTIVES') == '1' and dist.is_available()
                                         and dist.is_initialized())
         self._check_gb(system, integrator)
+        self._check_custom_gb(system, integrator)
         self._check_massless(system, integrator)
         if self.free_space and self.world > 1:
             raise InputError('a System in free space (NoCutoff / CutoffNonPeriodic) runs on a single rank: its pair forces walk all pairs '
@@ -472,7 +475,7 @@ class Engine:
         force uses periodic boundary conditions and the System holds a force (box vectors may be absent; present ones are ignored).
         False: all nonbonded forces periodic, as ever.  A mixture is an InputError."""
         def pair_forces(force):
-            if isinstance(force, (mm.NonbondedForce, mm.CustomNonbondedForce, mm.GBSAOBCForce)):
+            if isinstance(force, (mm.NonbondedForce, mm.CustomNonbondedForce, mm.GBSAOBCForce, mm.CustomGBForce)):
                 return [force]
             if isinstance(force, mm.CustomCVForce):
                 return [f for k in range(force.getNumCollectiveVariables()) for f in pair_forces(force.getCollectiveVariable(k))]
@@ -480,14 +483,16 @@ class Engine:
         forces = list(system.getForces())
         pairs = [f for force in forces for f in pair_forces(force)]
         # a generalized-Born force runs in free space only (csrc/gb.hip): refused by name, not as a mixture
-        if any(isinstance(f, mm.GBSAOBCForce) for f in pairs):
+        for cls in (mm.GBSAOBCForce, mm.CustomGBForce):
+            if not any(isinstance(f, cls) for f in pairs):
+                continue
             for f in pairs:
-                if isinstance(f, mm.GBSAOBCForce) and f.usesPeriodicBoundaryConditions():
-                    raise InputError('GBSAOBCForce: CutoffPeriodic is not supported: generalized-Born solvent runs in free space only '
-                                     '(NoCutoff / CutoffNonPeriodic)')
+                if isinstance(f, cls) and f.usesPeriodicBoundaryConditions():
+                    raise InputError('%s: CutoffPeriodic is not supported: generalized-Born solvent runs in free space only '
+                                     '(NoCutoff / CutoffNonPeriodic)' % cls.__name__)
                 if f.usesPeriodicBoundaryConditions():
-                    raise InputError('a GBSAOBCForce in a System with a box-periodic %s: generalized-Born solvent runs in free space '
-                                     'only (every nonbonded method NoCutoff or CutoffNonPeriodic)' % f.__class__.__name__)
+                    raise InputError('a %s in a System with a box-periodic %s: generalized-Born solvent runs in free space '
+                                     'only (every nonbonded method NoCutoff or CutoffNonPeriodic)' % (cls.__name__, f.__class__.__name__))
         free = [f for f in pairs if not f.usesPeriodicBoundaryConditions()]
         if free and len(free) != len(pairs):
             raise InputError('the System mixes periodic and non-periodic nonbonded methods: every NonbondedForce / CustomNonbondedForce '
@@ -522,6 +527,144 @@ class Engine:
             if expr and 'deriv(' in expr:
                 raise NotImplementedError('deriv(energy, ...) through a GBSAOBCForce is not supported: the generalized-Born kernels have '
                                           'no parameter-derivative evaluation (step: %s)' % expr)
+
+    def _check_custom_gb(self, system, integrator):
+        """What a CustomGBForce cannot run with, refused by name when the Context is created (CutoffPeriodic and box-periodic
+        companions: _free_space_mode; its texts and limits: _translate_custom_gb)."""
+        cgs = [f for f in system.getForces() if isinstance(f, mm.CustomGBForce)]
+        if not cgs:
+            return
+        n = system.getNumParticles()
+        for cg in cgs:
+            if cg.getNumParticles() != n:
+                raise mm.OpenMMException('CustomGBForce must have exactly as many particles as the System it belongs to (%d, the System '
+                                         'has %d)' % (cg.getNumParticles(), n))
+            if cg.getNumEnergyParameterDerivatives():
+                raise NotImplementedError('CustomGBForce.addEnergyParameterDerivative(%r) is not supported: the custom generalized-Born '
+                                          'kernels differentiate in positions only' % cg.getEnergyParameterDerivativeName(0))
+        if self.world > 1:
+            raise InputError('a CustomGBForce runs on a single rank: its passes walk all pairs and are not sliced')
+        if n > self.GB_MAX_ATOMS:
+            raise InputError('a CustomGBForce walks all n^2 pairs up to three times per evaluation and takes at most %d atoms (the System '
+                             'has %d)' % (self.GB_MAX_ATOMS, n))
+        for _kind, _target, expr in getattr(integrator, '_steps', []):
+            if expr and 'deriv(' in expr:
+                raise NotImplementedError('deriv(energy, ...) through a CustomGBForce is not supported: the custom generalized-Born '
+                                          'kernels have no parameter-derivative evaluation (step: %s)' % expr)
+
+    @staticmethod
+    def check_custom_gb_symmetry(text, per_particle_names, value_names, global_values, rows, functions=None, samples=6, seed=20240607):
+        """A pair energy term is evaluated from both rows and counted half (csrc/custom_gb.hip), so it must not change when the
+        particles swap -- parameters AND computed values: check_pair_symmetry with the values among the swapped names.  The sample
+        parameters are rows the force has (`rows`: [n][parameters]; a type index is no uniform draw), the values seeded draws."""
+        rng = np.random.default_rng(seed)
+        rows = np.unique(np.asarray(rows, dtype=np.float64).reshape(-1, len(per_particle_names)), axis=0) if per_particle_names else np.zeros((1, 0))
+        for _ in range(samples):
+            a, b = rows[rng.integers(0, len(rows))], rows[rng.integers(0, len(rows))]
+            one = dict(zip(per_particle_names, map(float, a)), **{nm: float(rng.uniform(0.2, 1.5)) for nm in value_names})
+            two = dict(zip(per_particle_names, map(float, b)), **{nm: float(rng.uniform(0.2, 1.5)) for nm in value_names})
+            env = dict(global_values, r=float(rng.uniform(0.3, 1.2)))
+            fwd = dict(env, **{nm + '1': v for nm, v in one.items()}, **{nm + '2': v for nm, v in two.items()})
+            swp = dict(env, **{nm + '1': v for nm, v in two.items()}, **{nm + '2': v for nm, v in one.items()})
+            try:
+                x, y = X.eval_global(text, fwd, functions=functions), X.eval_global(text, swp, functions=functions)
+            except (ArithmeticError, ValueError) as exc:
+                if isinstance(exc, X.ExpressionError):
+                    raise
+                continue               # (outside the text's domain at this draw: says nothing about symmetry)
+            if x != x and y != y:
+                continue
+            if not abs(x - y) <= 1e-12 * max(abs(x), abs(y), 1e-300):
+                raise InputError('CustomGBForce: the pair energy term %r is not symmetric in particles 1 and 2' % text.split(';')[0])
+
+    def _translate_custom_gb(self, force, entry):
+        """A CustomGBForce: its texts compiled here (expr.compile_custom_gb), one backend force (csrc/custom_gb.hip) carried in
+        entry.term_ids, so every loop over an entry's forces reaches it and the scheduler's fusion rules decline its group."""
+        cls = 'CustomGBForce'
+        if force.usesPeriodicBoundaryConditions():
+            raise InputError('%s: CutoffPeriodic is not supported: generalized-Born solvent runs in free space only' % cls)
+        if force.getNumEnergyParameterDerivatives():
+            raise NotImplementedError('%s.addEnergyParameterDerivative is not supported' % cls)
+        names = [force.getPerParticleParameterName(k) for k in range(force.getNumPerParticleParameters())]
+        gnames = [force.getGlobalParameterName(k) for k in range(force.getNumGlobalParameters())]
+        values = [tuple(force.getComputedValueParameters(k)) for k in range(force.getNumComputedValues())]
+        terms = [tuple(force.getEnergyTermParameters(k)) for k in range(force.getNumEnergyTerms())]
+        functions = list(force._functions)
+        try:
+            progs = X.compile_custom_gb(names, gnames, values, terms, T.declared(functions) if functions else None)
+        except X.ExpressionError as exc:
+            raise InputError('%s: not a model the custom generalized-Born kernels can run: %s' % (cls, exc))
+        uses_tables = any(X.table_words(p.code) for p in progs.programs)
+        n = self.n
+
+        def params():
+            if force.getNumParticles() != n:
+                raise mm.OpenMMException('%s must have exactly as many particles as the System it belongs to' % cls)
+            allp = np.array(force._particles, dtype=np.float64).reshape(n, -1) if names else np.zeros((n, 0))
+            if allp.shape[1] != len(names):
+                raise mm.OpenMMException('%s: every particle needs %d parameters' % (cls, len(names)))
+            return allp
+
+        def checked():
+            """The particles' rows after the checks the host can make: every pair energy term is symmetric over them."""
+            rows = params()
+            callables = {name: T.host_callable(fn) for name, fn in functions} or None
+            for text, kind in terms:
+                if kind != force.SingleParticle:
+                    self.check_custom_gb_symmetry(text, names, [v[0] for v in values], {g: self.parameters[g] for g in gnames}, rows,
+                                                  functions=callables)
+            return rows
+
+        rows = checked()
+        rc = force._cutoff if force.getNonbondedMethod() == force.CutoffNonPeriodic else 0.0
+        excl = np.array(force._exclusions, dtype=np.int32).reshape(-1, 2)
+        frozen = (len(values), len(terms), [list(v) for v in values], [list(t) for t in terms], excl.copy(), len(functions))
+        try:
+            gid = self.ctx.custom_gb_create(len(values), progs.types, [(p.code, p.consts) for p in progs.programs],
+                                            [self.parameters[g] for g in gnames], np.ascontiguousarray(rows.T), excl, rc)
+            if uses_tables or functions:
+                self.ctx.custom_gb_set_tables(gid, [T.device_table(fn) for _, fn in functions])
+        except B.HipError as exc:
+            raise InputError('%s: %s' % (cls, exc))
+        entry.term_ids.append(gid)
+        entry.custom_gb = dict(id=gid, n_values=len(values))
+        entry.program = progs
+
+        def reload():          # updateParametersInContext: the per-particle parameters and the tables' values are read again
+            now = (force.getNumComputedValues(), force.getNumEnergyTerms(), [list(v) for v in force._values], [list(t) for t in force._terms],
+                   np.array(force._exclusions, dtype=np.int32).reshape(-1, 2), len(force._functions))
+            if now[:4] != frozen[:4] or now[5] != frozen[5] or not np.array_equal(now[4], frozen[4]):
+                raise mm.OpenMMException('%s.updateParametersInContext: the computed values, energy terms, exclusions and the number of '
+                                         'tabulated functions cannot change in a live Context' % cls)
+            fresh = checked()
+            try:
+                if functions:
+                    self.ctx.custom_gb_set_tables(gid, [T.device_table(fn) for _, fn in functions])
+                self.ctx.custom_gb_set_params(gid, np.ascontiguousarray(fresh.T))
+            except B.HipError as exc:
+                raise InputError('%s: %s' % (cls, exc))
+            return 'values'
+        entry.reload = reload
+        if gnames:
+            depends = set(gnames)
+
+            def update(parameters, changed):
+                if not (depends & changed):
+                    return False
+                self.ctx.custom_gb_set_globals(gid, [parameters[g] for g in gnames])
+                return 'values'
+            entry.update = update
+            entry.depends = depends
+
+    def custom_gb_values(self, force):
+        """CustomGBForce.getComputedValues(context): the computed values at the current positions, [value][particle]."""
+        hits = [e for e in self.entries if e.force is force and getattr(e, 'custom_gb', None) is not None]
+        if not hits:
+            raise mm.OpenMMException('getComputedValues: the force does not belong to this Context')
+        cg = hits[0].custom_gb
+        out = self.ctx.custom_gb_values(cg['id'], self.x, cg['n_values'])
+        self._check()
+        return out
 
     def _translate_gb(self, force, entry):
         """A GBSAOBCForce: one backend force (csrc/gb.hip) carried in entry.term_ids, so every loop over an entry's forces reaches it
@@ -719,6 +862,8 @@ class Engine:
             self._translate_cv(force, entry)
         elif isinstance(force, mm.GBSAOBCForce):
             self._translate_gb(force, entry)
+        elif isinstance(force, mm.CustomGBForce):
+            self._translate_custom_gb(force, entry)
         elif isinstance(force, mm.CMAPTorsionForce):
             self._translate_cmap(force, entry)
         elif isinstance(force, mm.RBTorsionForce):
@@ -3208,6 +3353,9 @@ class Engine:
         if any(getattr(entry, 'gb', None) is not None for entry in self.entries):
             raise NotImplementedError('deriv(energy, %s) through a GBSAOBCForce is not supported: the generalized-Born kernels have no '
                                       'parameter-derivative evaluation' % name)
+        if any(getattr(entry, 'custom_gb', None) is not None for entry in self.entries):
+            raise NotImplementedError('deriv(energy, %s) through a CustomGBForce is not supported: the custom generalized-Born kernels '
+                                      'have no parameter-derivative evaluation' % name)
         self._refuse_in_free_space('deriv(energy, %s)' % name)
         if name not in self.parameters:
             raise mm.OpenMMException('deriv(energy, %s): no such Context parameter' % name)

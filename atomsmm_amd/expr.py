@@ -10,6 +10,7 @@ freedom, as in OpenMM (every occurrence inside one expression sees the same valu
 """
 import ast
 import functools
+import keyword
 import math
 import re
 
@@ -125,7 +126,8 @@ def split_definitions(text):
     return parts[0], defs
 
 
-_KEYWORD = re.compile(r'\b(lambda)\b')       # a legal OpenMM variable name (tests/test_systems.py:165), a Python keyword
+# legal OpenMM variable names that are Python keywords: lambda (tests/test_systems.py:165), or (the offset radius of the GB texts) ...
+_KEYWORD = re.compile(r'\b(%s)\b' % '|'.join(keyword.kwlist))
 
 
 def _name(node_id):
@@ -500,6 +502,119 @@ def compile_cv(text, cv_names, deriv_names, global_names):
     if len(set(cv_names + deriv_names)) != len(cv_names) + len(deriv_names):
         raise ExpressionError('%s expression: a name is used twice among the collective variables and the derivative parameters' % what)
     return compile_term(text, cv_names + deriv_names, [], set(global_names) - set(deriv_names), what=what)
+
+
+# a custom generalized-Born force (compile_custom_gb; csrc/custom_gb.hip): computed values, energy terms and their types
+CGB_MAX_VALUES, CGB_MAX_TERMS = 4, 8
+CGB_SINGLE, CGB_PAIR, CGB_PAIR_NOEXCL = 0, 1, 2          # CustomGBForce.SingleParticle / ParticlePair / ParticlePairNoExclusions
+CGB_VAR_V1, CGB_VAR_V2, CGB_P2 = 1, 5, 8                 # TERM_VAR 0 is r, 1 + k / 5 + k value k of particle 1 / 2; TERM_P 8 + k parameter k of particle 2
+
+
+class CustomGBPrograms:
+    """What compile_custom_gb returns: `values` and `terms` (one Program each, in the force's order), `types` (the values', then the
+    terms'), `value_reads[m]` / `term_reads[t]` (the indices of the computed values that the text reads of particle 1 -- of the
+    particle itself in a single-particle text: what the kernels differentiate it in), and `globals_`, the force's global parameters
+    in ITS order: GLOBAL k of every program is entry k of this one list."""
+
+    def __init__(self, values, terms, types, value_reads, term_reads, globals_):
+        self.values, self.terms, self.types = values, terms, types
+        self.value_reads, self.term_reads, self.globals_ = value_reads, term_reads, globals_
+
+    @property
+    def programs(self):
+        return self.values + self.terms
+
+
+def compile_custom_gb(per_particle_names, global_names, values, terms, functions=None):
+    """Compile a CustomGBForce for the kernels of csrc/custom_gb.hip.  values: [(name, text, type)] of addComputedValue; terms:
+    [(text, type)] of addEnergyTerm; functions: as for compile_pair.  In a pair text `r` is TERM_VAR 0, `<parameter>1` / `<parameter>2`
+    TERM_P k / TERM_P 8 + k and `<value>1` / `<value>2` TERM_VAR 1 + k / 5 + k; in a single-particle text the bare names are TERM_P k
+    and TERM_VAR 1 + k.  A computed value sees the values before it (a pair-type value, legal in first place only, none); an energy
+    term sees all.  A global parameter is GLOBAL k, k its position among the force's globals.  The limits are those of
+    csrc/pair_expr_vm.h per program plus TERM_MAX_PARAMS parameters, CGB_MAX_VALUES values, CGB_MAX_TERMS terms and PAIR_MAX_TABLES
+    functions, each an ExpressionError that names it."""
+    what = 'custom-GB'
+    pnames, gnames = list(per_particle_names), list(global_names)
+    values, terms = [tuple(v) for v in values], [tuple(t) for t in terms]
+    vnames = [v[0] for v in values]
+    if len(pnames) > TERM_MAX_PARAMS:
+        raise ExpressionError('a %s force takes at most %d per-particle parameters (%d given)' % (what, TERM_MAX_PARAMS, len(pnames)))
+    if len(values) > CGB_MAX_VALUES:
+        raise ExpressionError('a %s force takes at most %d computed values (%d given)' % (what, CGB_MAX_VALUES, len(values)))
+    if len(terms) > CGB_MAX_TERMS:
+        raise ExpressionError('a %s force takes at most %d energy terms (%d given)' % (what, CGB_MAX_TERMS, len(terms)))
+    if len(gnames) > PAIR_MAX_GLOBALS:
+        raise ExpressionError('a %s force takes at most %d global parameters (%d given)' % (what, PAIR_MAX_GLOBALS, len(gnames)))
+    functions = dict(functions or {})
+    if len(functions) > PAIR_MAX_TABLES:
+        raise ExpressionError('a %s force takes at most %d tabulated functions (%d given)' % (what, PAIR_MAX_TABLES, len(functions)))
+    declared = pnames + vnames + gnames + list(functions)
+    for name in declared:
+        if declared.count(name) > 1:
+            raise ExpressionError('%s force: the name %s is used twice among the per-particle parameters, computed values, global '
+                                  'parameters and tabulated functions' % (what, name))
+        if name == 'r' or name in _HOST_FUNCS:
+            raise ExpressionError('%s force: the name %s shadows %s' % (what, name, 'the distance r' if name == 'r' else 'the built-in function of that name'))
+    words = {}
+    for index, (name, (kind, arity)) in enumerate(functions.items()):
+        if kind not in TABLE_KINDS:
+            raise ExpressionError('tabulated function %s: kind %s is not one a %s expression evaluates' % (name, kind, what))
+        if arity != TABLE_KINDS[kind][1]:
+            raise ExpressionError('tabulated function %s: a %sFunction takes %d argument%s (%d declared)' %
+                                  (name, kind, TABLE_KINDS[kind][1], '' if TABLE_KINDS[kind][1] == 1 else 's', arity))
+        words[name] = (TABLE_KINDS[kind][0], arity, index)
+    types = [int(v[2]) for v in values] + [int(t[1]) for t in terms]
+    for kind in types:
+        if kind not in (CGB_SINGLE, CGB_PAIR, CGB_PAIR_NOEXCL):
+            raise ExpressionError('%s force: unknown computation type %r' % (what, kind))
+    for place, (name, _, kind) in enumerate(values):
+        if place > 0 and int(kind) != CGB_SINGLE:
+            raise ExpressionError('%s force: the computed value %s is a sum over pairs in place %d; only the first computed value may be '
+                                  'of a pair type' % (what, name, place))
+
+    def one(text, kind, visible, label):
+        """The program of one text that sees the first `visible` computed values."""
+        coordinates = sorted(symbols(text) & {'x', 'y', 'z'} - set(declared))
+        if coordinates:
+            raise ExpressionError('%s: the particle coordinate %s in a text is not supported (a %s text reads r, parameters, computed '
+                                  'values and global parameters)' % (label, coordinates[0], what))
+        slots = {}
+        if kind == CGB_SINGLE:
+            for k, name in enumerate(pnames):
+                slots[name] = ('op', 'TERM_P', k)
+            for k, name in enumerate(vnames[:visible]):
+                slots[name] = ('op', 'TERM_VAR', CGB_VAR_V1 + k)
+        else:
+            slots['r'] = ('op', 'TERM_VAR', 0)
+            for k, name in enumerate(pnames):
+                slots[name + '1'] = ('op', 'TERM_P', k)
+                slots[name + '2'] = ('op', 'TERM_P', CGB_P2 + k)
+            for k, name in enumerate(vnames[:visible]):
+                slots[name + '1'] = ('op', 'TERM_VAR', CGB_VAR_V1 + k)
+                slots[name + '2'] = ('op', 'TERM_VAR', CGB_VAR_V2 + k)
+
+        def resolve(name):
+            if name in slots:
+                return slots[name]
+            return ('global',) if name in gnames else None
+
+        try:
+            prog = _checked_program(text, resolve, what, words or None)
+        except ExpressionError as exc:
+            raise ExpressionError('%s: %s' % (label, exc))
+        # GLOBAL k: from the program's own order of first use to the force's order
+        for pc, word in enumerate(prog.code):
+            if word & 0xff == OPCODES['GLOBAL']:
+                prog.code[pc] = OPCODES['GLOBAL'] | (gnames.index(prog.globals_[word >> 8]) << 8)
+        prog.globals_ = list(gnames)
+        reads = sorted({(w >> 8) - CGB_VAR_V1 for w in prog.code
+                        if w & 0xff == TERM_OPCODES['TERM_VAR'] and CGB_VAR_V1 <= (w >> 8) < CGB_VAR_V2})
+        return prog, tuple(reads)
+
+    compiled_values = [one(text, int(kind), place, 'computed value %s' % name) for place, (name, text, kind) in enumerate(values)]
+    compiled_terms = [one(text, int(kind), len(values), 'energy term %d' % k) for k, (text, kind) in enumerate(terms)]
+    return CustomGBPrograms([p for p, _ in compiled_values], [p for p, _ in compiled_terms], types,
+                            [r for _, r in compiled_values], [r for _, r in compiled_terms], list(gnames))
 
 
 def compile_polynomial(coefficients, scale, shift, operand):

@@ -543,6 +543,146 @@ class CustomNonbondedForce(Force, _GlobalParams):
         self._derivs.append(name)
 
 
+class CustomGBForce(Force, _GlobalParams):
+    """A generalized-Born model written as text: computed per-particle values and energy terms, for free-space systems (NoCutoff and
+    CutoffNonPeriodic; csrc/custom_gb.hip).  Only the first computed value may be a sum over pairs."""
+    NoCutoff, CutoffNonPeriodic, CutoffPeriodic = range(3)
+    SingleParticle, ParticlePair, ParticlePairNoExclusions = range(3)
+
+    def __init__(self):
+        Force.__init__(self)
+        self._init_globals()
+        self._pnames = []
+        self._particles = []
+        self._exclusions = []
+        self._values = []          # [name, text, type]
+        self._terms = []           # [text, type]
+        self._functions = []
+        self._derivs = []
+        self._method = self.NoCutoff
+        self._cutoff = 1.0
+
+    def usesPeriodicBoundaryConditions(self):
+        return self._method == self.CutoffPeriodic
+
+    def addPerParticleParameter(self, name):
+        self._pnames.append(str(name))
+        return len(self._pnames) - 1
+
+    def getNumPerParticleParameters(self):
+        return len(self._pnames)
+
+    def getPerParticleParameterName(self, index):
+        return self._pnames[index]
+
+    def setPerParticleParameterName(self, index, name):
+        self._pnames[index] = str(name)
+
+    def addParticle(self, parameters=()):
+        self._particles.append([float(md_value(p)) for p in parameters])
+        return len(self._particles) - 1
+
+    def getNumParticles(self):
+        return len(self._particles)
+
+    def getParticleParameters(self, index):
+        return tuple(self._particles[index])
+
+    def setParticleParameters(self, index, parameters):
+        self._particles[index] = [float(md_value(p)) for p in parameters]
+
+    def addComputedValue(self, name, expression, type):
+        self._values.append([str(name), str(expression), int(type)])
+        return len(self._values) - 1
+
+    def getNumComputedValues(self):
+        return len(self._values)
+
+    def getComputedValueParameters(self, index):
+        return list(self._values[index])
+
+    def setComputedValueParameters(self, index, name, expression, type):
+        self._values[index] = [str(name), str(expression), int(type)]
+
+    def addEnergyTerm(self, expression, type):
+        self._terms.append([str(expression), int(type)])
+        return len(self._terms) - 1
+
+    def getNumEnergyTerms(self):
+        return len(self._terms)
+
+    def getEnergyTermParameters(self, index):
+        return list(self._terms[index])
+
+    def setEnergyTermParameters(self, index, expression, type):
+        self._terms[index] = [str(expression), int(type)]
+
+    def addExclusion(self, particle1, particle2):
+        self._exclusions.append((int(particle1), int(particle2)))
+        return len(self._exclusions) - 1
+
+    def getNumExclusions(self):
+        return len(self._exclusions)
+
+    def getExclusionParticles(self, index):
+        return list(self._exclusions[index])
+
+    def setExclusionParticles(self, index, particle1, particle2):
+        self._exclusions[index] = (int(particle1), int(particle2))
+
+    def addTabulatedFunction(self, name, function):
+        """The texts may call `name(...)`.  The force keeps the object itself: setFunctionParameters on it followed by
+        updateParametersInContext reaches the Context."""
+        if not isinstance(function, TabulatedFunction):
+            raise OpenMMException('addTabulatedFunction: not a TabulatedFunction')
+        self._functions.append((str(name), function))
+        return len(self._functions) - 1
+
+    addFunction = addTabulatedFunction
+
+    def getNumTabulatedFunctions(self):
+        return len(self._functions)
+
+    getNumFunctions = getNumTabulatedFunctions
+
+    def getTabulatedFunction(self, index):
+        return self._functions[index][1]
+
+    def getTabulatedFunctionName(self, index):
+        return self._functions[index][0]
+
+    def addEnergyParameterDerivative(self, name):
+        """Recorded; a Context refuses the force by name (the kernels differentiate in positions only)."""
+        self._derivs.append(str(name))
+
+    def getNumEnergyParameterDerivatives(self):
+        return len(self._derivs)
+
+    def getEnergyParameterDerivativeName(self, index):
+        return self._derivs[index]
+
+    def getNonbondedMethod(self):
+        return self._method
+
+    def setNonbondedMethod(self, method):
+        self._method = int(method)
+
+    def getCutoffDistance(self):
+        return Quantity(self._cutoff, nm)
+
+    def setCutoffDistance(self, distance):
+        self._cutoff = float(md_value(distance))
+
+    def updateParametersInContext(self, context):
+        """Upload the per-particle parameters and the tabulated functions' values again.  Counts, texts and exclusions must not have
+        changed."""
+        context._engine.update_force_parameters(self)
+
+    def getComputedValues(self, context):
+        """The computed values at the Context's positions, [value][particle] (a diagnostic OpenMM does not have)."""
+        return context._engine.custom_gb_values(self)
+
+
 class CustomCVForce(Force, _GlobalParams):
     """Energy = function of collective variables, each the energy of an inner Force object."""
 

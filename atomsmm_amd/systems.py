@@ -279,6 +279,9 @@ class ComputingSystem(_AtomsMM_System):
         if any(isinstance(force, openmm.GBSAOBCForce) for force in system.getForces()):
             raise NotImplementedError('ComputingSystem / PressureComputer: the virial of a GBSAOBCForce is not supported (generalized-Born '
                                       'solvent runs in free space only, where there is no pressure)')
+        if any(isinstance(force, openmm.CustomGBForce) for force in system.getForces()):
+            raise NotImplementedError('ComputingSystem / PressureComputer: the virial of a CustomGBForce is not supported (generalized-Born '
+                                      'solvent runs in free space only, where there is no pressure)')
         if any(isinstance(force, (openmm.NonbondedForce, openmm.CustomNonbondedForce)) and not force.usesPeriodicBoundaryConditions()
                for force in system.getForces()):
             raise utils.InputError('ComputingSystem / PressureComputer need a periodic box: a System in free space (NoCutoff / '

@@ -415,6 +415,53 @@ int amm_cmap_set_params(amm_ctx *ctx, int32_t force_id, const double *h_coeffs, 
 /* Free such a force; the id is retired and leaves every group definition. */
 int amm_cmap_release(amm_ctx *ctx, int32_t force_id);
 
+/* CustomGBForce (force type AMM_FORCE_CUSTOM_GB; csrc/custom_gb.hip): a generalized-Born model written as
+ * text, for free-space systems -- what OpenMM compiles with Lepton from addComputedValue / addEnergyTerm (HCT, OBC1, OBC2, GBn ...;
+ * the hand-written OBC2 of amm_gb_create stays as it is).  n_values <= AMM_CGB_MAX_VALUES computed values and n_terms <=
+ * AMM_CGB_MAX_TERMS energy terms, each of a type: */
+typedef enum {
+    AMM_CGB_SINGLE = 0,      /* SingleParticle: a text of the parameters and the values of one particle                      */
+    AMM_CGB_PAIR = 1,        /* ParticlePair: a text of r and both particles, over the pairs that take part and are not excluded */
+    AMM_CGB_PAIR_NOEXCL = 2  /* ParticlePairNoExclusions: ... over the pairs that take part                                     */
+} amm_cgb_type;
+#define AMM_CGB_MAX_VALUES 4
+#define AMM_CGB_MAX_TERMS 8
+/* A pair (i, j), i != j, takes part when rc <= 0 (NoCutoff) or r^2 < rc^2 (CutoffNonPeriodic).  Only computed value 0 may be of a
+ * pair type: V0_i = sum over j of its text at (r; parameters of i as particle 1, of j as particle 2), ordered pairs, no symmetry
+ * asked.  Value k of type SINGLE is its text at the parameters of i and V0_i .. V(k-1)_i.  The energy is the sum over i of the SINGLE
+ * terms (parameters and all values of i) plus the sum over the unordered pairs of the pair terms (r, parameters and values of
+ * both); a pair term is evaluated from both rows and counted half, so it must not change under 1 <-> 2 (the host checks).  Forces
+ * are the full chain rule through the values.
+ * types / code_ptr / const_ptr: n_values + n_terms entries (+ 1 for the two pointers), the values' programs first: program p is
+ * code[code_ptr[p] .. code_ptr[p+1]) with constants consts[const_ptr[p] .. const_ptr[p+1]).  A program is what
+ * atomsmm_amd.expr.compile_custom_gb emits: the words of amm_term_expr_create (variable 53, parameter 54) plus the table words 55 ..
+ * 57 of amm_pair_expr_set_tables, over these leaves -- variable 0 = r, 1 + k = value k of particle 1 (in a SINGLE text: of the
+ * particle), 5 + k = value k of particle 2; parameter k = of particle 1 (of the particle), 8 + k = of particle 2; global k = entry k
+ * of `globals`, ONE list for all programs.  Each program obeys the limits of csrc/pair_expr_vm.h (walked here), and may read only
+ * the leaves its place has (a value only the values before it; value 0 of a pair type only r and parameters).  h_params: n_params x
+ * n_atoms doubles, PARAMETER-major, n_params <= AMM_TERM_MAX_PARAMS.  h_excl: n_excl pairs for the texts of type PAIR.
+ * Refused: more than 32768 atoms, more than one rank, a pair-type value behind the first, a leaf outside its place, an exclusion
+ * that names no pair.  An ordinary member of a group, evaluated through amm_force_eval and amm_run_ops, legal in a context without
+ * a box; every other family's entry points refuse its id naming AMM_FORCE_CUSTOM_GB.  Up to four launches per evaluation (value 0,
+ * the other values with their Jacobian, energy terms, chain rule), no atomics: the same positions give the same bits. */
+int amm_custom_gb_create(amm_ctx *ctx, int32_t n_params, int32_t n_values, int32_t n_terms, const int32_t *types, const int32_t *code,
+                         const int32_t *code_ptr, const double *consts, const int32_t *const_ptr, const double *globals, int32_t nglobal,
+                         const double *h_params, const int32_t *h_excl, int32_t n_excl, double rc, int32_t *force_id);
+/* setParticleParameters + updateParametersInContext: all per-particle values again, laid out as at creation. */
+int amm_custom_gb_set_params(amm_ctx *ctx, int32_t force_id, const double *h_params, int32_t n_params, int32_t n_atoms);
+/* Context.setParameter(name, value) for a global parameter of such a force: all of its globals, in the order of creation. */
+int amm_custom_gb_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal);
+/* addTabulatedFunction on such a force: the tables its programs' words 55 .. 57 read, with the arguments of
+ * amm_pair_expr_set_tables; again with new values of the same kinds and sizes (updateParametersInContext).  A force whose programs
+ * have such words evaluates only after this call. */
+int amm_custom_gb_set_tables(amm_ctx *ctx, int32_t force_id, int32_t n_tables, const int32_t *kinds, const int32_t *dims,
+                             const double *ranges, const int32_t *offsets, const double *data, int32_t n_data);
+/* The computed values at d_pos (device, [n][3]) into h_out (host, n_values x n doubles, value-major): runs the value passes and
+ * waits (tests, diagnostics; OpenMM has no such call). */
+int amm_custom_gb_values(amm_ctx *ctx, int32_t force_id, const double *d_pos, double *h_out);
+/* Free such a force; the id is retired and leaves every group definition. */
+int amm_custom_gb_release(amm_ctx *ctx, int32_t force_id);
+
 /* Reciprocal space of a NonbondedForce with nonbondedMethod PME / Ewald, as RESPASystem and FarNonbondedForce
  * keep it in group 2 with the source force's Ewald tolerance / PME parameters (systems.py:74-75,
  * forces.py:185-188; setReciprocalSpaceForceGroup: utils.py:147-152).  Smooth PME, B-spline order 5, grid
@@ -534,7 +581,8 @@ int amm_set_outer_skin(amm_ctx *ctx, double skin_out);
  * is one bond-list set of three-site molecules -- propagators.py:933-973 unrolled; 0: launches of their own), "comm_timeout" (seconds
  * amm_check / amm_synchronize / amm_comm_destroy wait for the stream while the context owns an RCCL communicator before they abort it and
  * fail; default 0 = no deadline, the asynchronous error alone is polled), "gb_lanes_per_row" (lanes that sum one row of the
- * generalized-Born passes: 0 = chosen from n as for free-space pair forces; 1, 2, 4 .. 64).  Unknown names are an error. */
+ * generalized-Born passes: 0 = chosen from n as for free-space pair forces; 1, 2, 4 .. 64), "cgb_lanes_per_row" (the same for the
+ * passes of a custom generalized-Born force).  Unknown names are an error. */
 int amm_set_option(amm_ctx *ctx, const char *name, double value);
 /* What amm_run_ops fused so far (statistics for tests and bench.py): out[0] = pair-kernel launches that carried the inner RESPA loop
  * of their molecules as an epilogue (the reference runs it as CustomIntegrator steps, propagators.py:933-973), out[1] = pair
