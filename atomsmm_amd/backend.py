@@ -62,6 +62,7 @@ EXPORTS = [
     'amm_cmap_create', 'amm_cmap_set_params', 'amm_cmap_release',
     'amm_custom_gb_create', 'amm_custom_gb_set_params', 'amm_custom_gb_set_globals', 'amm_custom_gb_set_tables', 'amm_custom_gb_values',
     'amm_custom_gb_release',
+    'amm_hbond_create', 'amm_hbond_set_params', 'amm_hbond_set_globals', 'amm_hbond_stats', 'amm_hbond_release',
     'amm_vsite_define', 'amm_vsite_place', 'amm_vsite_spread', 'amm_vsite_stats',
 ]
 
@@ -208,6 +209,12 @@ def lib():
         L.amm_custom_gb_set_tables.argtypes = [vp, C.c_int32, C.c_int32, ip, ip, dp, ip, dp, C.c_int32]
         L.amm_custom_gb_values.argtypes = [vp, C.c_int32, vp, dp]
         L.amm_custom_gb_release.argtypes = [vp, C.c_int32]
+        L.amm_hbond_create.argtypes = [vp, ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip, ip, C.c_int32, ip, C.c_int32, ip, C.c_int32, dp, C.c_int32,
+                                       dp, C.c_int32, ip, C.c_int32, C.c_double, C.c_int32, ip]
+        L.amm_hbond_set_params.argtypes = [vp, C.c_int32, dp, C.c_int32, C.c_int32, dp, C.c_int32, C.c_int32]
+        L.amm_hbond_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
+        L.amm_hbond_stats.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
+        L.amm_hbond_release.argtypes = [vp, C.c_int32]
         L.amm_cv_create.argtypes = [vp, ip, C.c_int32, C.c_int32, ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip]
         L.amm_cv_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
         L.amm_cv_set_variables.argtypes = [vp, C.c_int32, dp, C.c_int32]
@@ -669,6 +676,59 @@ class HipContext:
     def custom_gb_release(self, fid):
         """Free a custom generalized-Born force (its id is retired)."""
         _chk(lib().amm_custom_gb_release(self.h, fid))
+
+    def hbond_create(self, code, consts, globals_, var_kinds, var_slots, donors, acceptors, donor_params, acceptor_params, excl_pairs=None,
+                     rc=0.0, periodic=False):
+        """A hydrogen-bond force (csrc/hbond.hip): the program and the variable table of expr.compile_hbond -- var_kinds[k] one of
+        CVAR_DISTANCE / CVAR_ANGLE / CVAR_DIHEDRAL, var_slots[k] its slots of the pair (0 .. 2 = d1 d2 d3, 3 .. 5 = a1 a2 a3) --
+        donors / acceptors: n x 3 atoms (-1: the slot is not there); donor_params / acceptor_params: n_params x n, parameter-major;
+        excl_pairs: (donor, acceptor) indices; rc <= 0: NoCutoff; periodic: CutoffPeriodic."""
+        c_, cp = _hi(np.asarray(code, dtype=np.int32).reshape(-1))
+        k_, kp = _hd(consts if len(consts) else [0.0])
+        g_, gp = _hd(globals_ if len(globals_) else [0.0])
+        n_vars = len(var_kinds)
+        slots = np.zeros((max(n_vars, 1), 4), dtype=np.int32)
+        for k, s in enumerate(var_slots):
+            slots[k, :len(s)] = s
+        vk_, vkp = _hi(var_kinds if n_vars else [0])
+        vs_, vsp = _hi(slots)
+        dn = np.asarray(donors, dtype=np.int32).reshape(-1, 3)
+        ac = np.asarray(acceptors, dtype=np.int32).reshape(-1, 3)
+        dpar = np.asarray(donor_params, dtype=np.float64).reshape(-1, len(dn)) if np.size(donor_params) else np.zeros((0, len(dn)))
+        apar = np.asarray(acceptor_params, dtype=np.float64).reshape(-1, len(ac)) if np.size(acceptor_params) else np.zeros((0, len(ac)))
+        ex = np.zeros((0, 2), np.int32) if excl_pairs is None else np.asarray(excl_pairs, dtype=np.int32).reshape(-1, 2)
+        dn_, dnp = _hi(dn if len(dn) else [0])
+        ac_, acp = _hi(ac if len(ac) else [0])
+        dp_, dpp = _hd(dpar if dpar.size else [0.0])
+        ap_, app = _hd(apar if apar.size else [0.0])
+        ex_, exp_ = _hi(ex if len(ex) else [0])
+        fid = C.c_int32(-1)
+        _chk(lib().amm_hbond_create(self.h, cp, len(c_), kp, len(consts), gp, len(globals_), vkp, vsp, n_vars, dnp, len(dn), acp, len(ac), dpp,
+                                    len(dpar), app, len(apar), exp_, len(ex), float(rc), 1 if periodic else 0, C.byref(fid)))
+        return fid.value
+
+    def hbond_set_params(self, fid, donor_params, n_donors, acceptor_params, n_acceptors):
+        """All per-donor and per-acceptor values again (n_params x n each, parameter-major)."""
+        dpar = np.asarray(donor_params, dtype=np.float64).reshape(-1, int(n_donors)) if np.size(donor_params) else np.zeros((0, int(n_donors)))
+        apar = np.asarray(acceptor_params, dtype=np.float64).reshape(-1, int(n_acceptors)) if np.size(acceptor_params) else np.zeros((0, int(n_acceptors)))
+        dp_, dpp = _hd(dpar if dpar.size else [0.0])
+        ap_, app = _hd(apar if apar.size else [0.0])
+        _chk(lib().amm_hbond_set_params(self.h, fid, dpp, int(n_donors), len(dpar), app, int(n_acceptors), len(apar)))
+
+    def hbond_set_globals(self, fid, globals_):
+        g_, gp = _hd(globals_ if len(globals_) else [0.0])
+        _chk(lib().amm_hbond_set_globals(self.h, fid, gp, len(globals_)))
+
+    def hbond_stats(self, fid):
+        """dict(scanned, survivors, launches, chunks): the ordered pairs one pass scans, those that passed the cutoff and the
+        exclusions in the last evaluation, kernel launches so far, column chunks per donor row (waits for the stream)."""
+        out = (C.c_int64 * 4)()
+        _chk(lib().amm_hbond_stats(self.h, fid, out))
+        return dict(scanned=int(out[0]), survivors=int(out[1]), launches=int(out[2]), chunks=int(out[3]))
+
+    def hbond_release(self, fid):
+        """Free a hydrogen-bond force (its id is retired)."""
+        _chk(lib().amm_hbond_release(self.h, fid))
 
     def cv_create(self, inner_ids, n_deriv, code, consts, globals_):
         """A CustomCVForce with any energy text (csrc/cv.hip): the ids of the inner forces in the order of the collective variables

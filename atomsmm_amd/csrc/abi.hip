@@ -1502,6 +1502,14 @@ int amm_set_option(amm_ctx *ctx, const char *name, double value) {
         }
         ctx->opt_cgb_lpr = v;
     }
+    else if (k == "hbond_chunks") {
+        if (v < 0 || v > 512) {
+            amm_set_error("amm_set_option: hbond_chunks is 0 (automatic) or 1 .. 512 column chunks per row");
+            return 1;
+        }
+        ctx->opt_hbond_chunks = v;
+    }
+    else if (k == "hbond_compact") ctx->opt_hbond_compact = v != 0;
     else {
         amm_set_error("amm_set_option: unknown option '" + k + "'");
         return 1;

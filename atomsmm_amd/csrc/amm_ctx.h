@@ -249,12 +249,14 @@ struct CompoundForce; // compound.hip: a CustomCompoundBondForce / CustomCentroi
 struct GbForce;       // gb.hip: a GBSAOBCForce -- generalized-Born (OBC2) implicit solvent with a surface-area term, free space only
 struct CmapForce;     // cmap.hip: a CMAPTorsionForce -- bicubic maps over pairs of dihedrals
 struct CustomGbForce; // custom_gb.hip: a CustomGBForce -- computed per-particle values and energy terms written as text, free space only
+struct HbondForce;    // hbond.hip: a CustomHbondForce -- donors against acceptors over all pairs, the energy written as text
 // The force families.  A family is described ONCE: its tag here, the struct that goes with the tag in amm_force_type, and its row of
 // the table behind amm_family (families.hip).  The typed lookup and its refusals, amm_force_eval_dispatch, release, amm_destroy, amm_set_slice and
 // cv.hip's messages all read the row -- a new family adds these three lines, its own .hip file and its extern "C" entry points.
-// Nine families today (and the tag of a released id).
+// Ten families today (and the tag of a released id).
 enum : int { AMM_FORCE_RELEASED = 0, AMM_FORCE_PAIR = 1, AMM_FORCE_BONDED = 2, AMM_FORCE_PME = 3, AMM_FORCE_TERM_EXPR = 4, AMM_FORCE_CV = 5,
-             AMM_FORCE_COMPOUND = 6, AMM_FORCE_GB = 7, AMM_FORCE_CMAP = 8, AMM_FORCE_CUSTOM_GB = 9, AMM_FORCE_TYPES = 10 };   // ForceObj::type, the row amm_family returns
+             AMM_FORCE_COMPOUND = 6, AMM_FORCE_GB = 7, AMM_FORCE_CMAP = 8, AMM_FORCE_CUSTOM_GB = 9, AMM_FORCE_HBOND = 10,
+             AMM_FORCE_TYPES = 11 };   // ForceObj::type, the row amm_family returns
 template <class T> inline constexpr int amm_force_type = -1;
 template <> inline constexpr int amm_force_type<PairForce> = AMM_FORCE_PAIR;
 template <> inline constexpr int amm_force_type<BondedSet> = AMM_FORCE_BONDED;
@@ -265,6 +267,7 @@ template <> inline constexpr int amm_force_type<CompoundForce> = AMM_FORCE_COMPO
 template <> inline constexpr int amm_force_type<GbForce> = AMM_FORCE_GB;
 template <> inline constexpr int amm_force_type<CmapForce> = AMM_FORCE_CMAP;
 template <> inline constexpr int amm_force_type<CustomGbForce> = AMM_FORCE_CUSTOM_GB;
+template <> inline constexpr int amm_force_type<HbondForce> = AMM_FORCE_HBOND;
 struct ForceFamily {
     const char *noun, *tag, *prefix;   // "a CMAP force", "AMM_FORCE_CMAP", "amm_cmap_*"
     const char *bad_id;                // what the family's entry points say of an id that is not theirs (behind "<entry point>: " if they name themselves)
@@ -428,6 +431,8 @@ struct amm_ctx {
     int opt_terms_from = 8192, opt_no_term_lanes = 0;
     int opt_gb_lpr = 0;                 // lanes per row of the generalized-Born passes (gb.hip): 0 = amm_free_lanes_per_row(n); 1, 2, 4 .. 64
     int opt_cgb_lpr = 0;                // ... and of the custom generalized-Born passes (custom_gb.hip)
+    int opt_hbond_chunks = 0;           // column chunks per row of a hydrogen-bond force created from now on (hbond.hip): 0 = chosen from the row count
+    int opt_hbond_compact = 1;          // ... and whether its survivors queue up for the interpreter (0: drained batch by batch -- a measurement)
     ListWatch watched[AMM_MAX_WATCH];
     int n_watched = 0;
     int device = 0;
@@ -617,6 +622,17 @@ int amm_custom_gb_set_tables_impl(amm_ctx *ctx, CustomGbForce *cg, int n_tables,
 int amm_custom_gb_eval_impl(amm_ctx *ctx, CustomGbForce *cg, const double *d_pos, double *d_force, int accumulate, double *d_energy);
 int amm_custom_gb_values_impl(amm_ctx *ctx, CustomGbForce *cg, const double *d_pos, double *h_out);
 void amm_custom_gb_free(CustomGbForce *cg);
+// hbond.hip: a force of type AMM_FORCE_HBOND
+int amm_hbond_create_impl(amm_ctx *ctx, const int32_t *code, int ncode, const double *consts, int nconst, const double *globals, int nglobal,
+                          const int32_t *var_kinds, const int32_t *var_slots, int n_vars, const int32_t *h_donors, int n_donors,
+                          const int32_t *h_acceptors, int n_acceptors, const double *h_dpar, int n_dpar, const double *h_apar, int n_apar,
+                          const int32_t *h_excl, int n_excl, double rc, int periodic, HbondForce **out);
+int amm_hbond_set_params_impl(amm_ctx *ctx, HbondForce *hb, const double *h_dpar, int n_donors, int n_dpar, const double *h_apar, int n_acceptors,
+                              int n_apar);
+int amm_hbond_set_globals_impl(amm_ctx *ctx, HbondForce *hb, const double *globals, int nglobal);
+int amm_hbond_eval_impl(amm_ctx *ctx, HbondForce *hb, const double *d_pos, double *d_force, int accumulate, double *d_energy);
+int amm_hbond_stats_impl(amm_ctx *ctx, HbondForce *hb, int64_t out[4]);
+void amm_hbond_free(HbondForce *hb);
 // implemented in pair.hip / cells.hip / bonded.hip / integrate.hip
 int amm_pair_build_consts(const amm_pair_desc &d, PairConsts &pc);
 int amm_pair_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double *d_force, int accumulate,

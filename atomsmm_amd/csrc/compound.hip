@@ -31,6 +31,7 @@
 
 #include "amm_ctx.h"
 #include "bonded_terms.h"
+#include "compound_geom.h"
 #include "term_expr_vm.h"
 
 #define AMM_CB_BLOCK 256
@@ -117,61 +118,7 @@ __global__ void __launch_bounds__(AMM_CB_BLOCK) k_compound(CompoundArgs A, const
         const int4 sl = s_slot[k];
         const int *ix = A.idx + (size_t)bond * A.n_slots;
         const PosPlain pos{A.pos};
-        if (kind <= AMM_CVAR_Z) {               // a raw coordinate: never wrapped
-            const int a = ix[sl.x];
-            v = pos.get(a, kind);
-            g0[0] = kind == AMM_CVAR_X ? 1.0 : 0.0;
-            g0[1] = kind == AMM_CVAR_Y ? 1.0 : 0.0;
-            g0[2] = kind == AMM_CVAR_Z ? 1.0 : 0.0;
-        } else if (kind == AMM_CVAR_DISTANCE) {
-            double d[3];
-            delta3(pos, ix[sl.x], ix[sl.y], A.box, A.periodic, d);
-            rr = sqrt(dot3(d, d));
-            v = rr;
-#pragma unroll
-            for (int x = 0; x < 3; ++x) {       // (grad r = d / r: the division goes into the coefficient, as k_term_expr has it)
-                g0[x] = d[x];
-                g1[x] = -d[x];
-            }
-        } else if (kind == AMM_CVAR_ANGLE) {
-            double d1[3], d2[3];
-            delta3(pos, ix[sl.x], ix[sl.y], A.box, A.periodic, d1);
-            delta3(pos, ix[sl.z], ix[sl.y], A.box, A.periodic, d2);
-            const double i1 = amm_rsqrt(dot3(d1, d1)), i2 = amm_rsqrt(dot3(d2, d2));
-            double c = dot3(d1, d2) * i1 * i2;
-            c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
-            v = acos(c);
-            double s2 = 1.0 - c * c;
-            if (s2 < 1e-24) s2 = 1e-24;
-            const double rs = amm_rsqrt(s2);
-#pragma unroll
-            for (int x = 0; x < 3; ++x) {
-                const double u1 = d1[x] * i1, u2 = d2[x] * i2;      // unit vectors
-                const double gi = -(rs * (u2 - c * u1) * i1);
-                const double gk = -(rs * (u1 - c * u2) * i2);
-                g0[x] = gi;
-                g1[x] = -(gi + gk);
-                g2[x] = gk;
-            }
-        } else {                                // AMM_CVAR_DIHEDRAL
-            double F[3], G[3], H[3], Av[3], Bv[3], BA[3];
-            delta3(pos, ix[sl.x], ix[sl.y], A.box, A.periodic, F);
-            delta3(pos, ix[sl.y], ix[sl.z], A.box, A.periodic, G);
-            delta3(pos, ix[sl.w], ix[sl.z], A.box, A.periodic, H);
-            cross3(F, G, Av);
-            cross3(H, G, Bv);
-            cross3(Bv, Av, BA);
-            const double Gn = sqrt(dot3(G, G));
-            v = atan2(dot3(BA, G) / Gn, dot3(Av, Bv));
-            const double A2 = dot3(Av, Av), B2 = dot3(Bv, Bv), FG = dot3(F, G), HG = dot3(H, G);
-#pragma unroll
-            for (int x = 0; x < 3; ++x) {
-                g0[x] = -Gn / A2 * Av[x];
-                g1[x] = Gn / A2 * Av[x] + FG / (A2 * Gn) * Av[x] - HG / (B2 * Gn) * Bv[x];
-                g2[x] = -Gn / B2 * Bv[x] - FG / (A2 * Gn) * Av[x] + HG / (B2 * Gn) * Bv[x];
-                g3[x] = Gn / B2 * Bv[x];
-            }
-        }
+        compound_variable(pos, kind, ix[sl.x], ix[sl.y], ix[sl.z], ix[sl.w], A.box, A.periodic, v, rr, g0, g1, g2, g3);     // compound_geom.h
     }
     s_val[threadIdx.x] = v;
     __syncthreads();

@@ -1,7 +1,7 @@
 // atomsmm_amd/csrc/families.hip -- the table of force families (amm_ctx.h: ForceFamily) and everything derived from it: the typed lookup
 // with its refusals, registration, release and the dispatch of an evaluation; then the extern "C" entry points of the families whose
 // implementation is a .hip file of its own (term expressions, collective variables, compound bonds, generalized Born, CMAP, custom
-// generalized Born).
+// generalized Born, hydrogen bonds).
 #include <algorithm>
 #include <cstring>
 
@@ -22,7 +22,7 @@ static int released_eval(amm_ctx *, void *, const double *, double *, int, doubl
 }
 static void released_free(void *) {}
 
-// One row per AMM_FORCE_* value (a released id and the nine families), in the enum's order: noun phrase, tag, entry points, bad-id wording, single rank, eval, free.
+// One row per AMM_FORCE_* value (a released id and the ten families), in the enum's order: noun phrase, tag, entry points, bad-id wording, single rank, eval, free.
 const ForceFamily &amm_family(int type) {
     static const ForceFamily rows[AMM_FORCE_TYPES] = {
         {"a released id", "AMM_FORCE_RELEASED", "none", "released force id", false, released_eval, released_free},
@@ -45,6 +45,8 @@ const ForceFamily &amm_family(int type) {
          eval_as<CmapForce, amm_cmap_eval_impl>, free_as<CmapForce, amm_cmap_free>},
         {"a custom generalized-Born force", "AMM_FORCE_CUSTOM_GB", "amm_custom_gb_*", "not the id of a custom generalized-Born force (AMM_FORCE_CUSTOM_GB)", true,
          eval_as<CustomGbForce, amm_custom_gb_eval_impl>, free_as<CustomGbForce, amm_custom_gb_free>},
+        {"a hydrogen-bond force", "AMM_FORCE_HBOND", "amm_hbond_*", "not the id of a hydrogen-bond force (AMM_FORCE_HBOND)", true,
+         eval_as<HbondForce, amm_hbond_eval_impl>, free_as<HbondForce, amm_hbond_free>},
     };
     return rows[type];
 }
@@ -345,5 +347,49 @@ int amm_custom_gb_values(amm_ctx *ctx, int32_t force_id, const double *d_pos, do
 }
 
 int amm_custom_gb_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_CUSTOM_GB, "amm_custom_gb_release"); }
+
+// CustomHbondForce(any energy text) (csrc/hbond.hip): the compiled text and its variable table (atomsmm_amd/expr.py: compile_hbond),
+// the donors' and acceptors' particles and parameters, the excluded (donor, acceptor) pairs, the cutoff (rc <= 0: NoCutoff) and
+// whether displacements take the minimum image
+int amm_hbond_create(amm_ctx *ctx, const int32_t *code, int32_t ncode, const double *consts, int32_t nconst, const double *globals, int32_t nglobal,
+                     const int32_t *var_kinds, const int32_t *var_slots, int32_t n_vars, const int32_t *h_donors, int32_t n_donors,
+                     const int32_t *h_acceptors, int32_t n_acceptors, const double *h_donor_params, int32_t n_donor_params,
+                     const double *h_acceptor_params, int32_t n_acceptor_params, const int32_t *h_excl, int32_t n_excl, double rc, int32_t periodic,
+                     int32_t *force_id) {
+    if (!ctx || !code || !force_id || (nconst > 0 && !consts) || (nglobal > 0 && !globals) || (n_vars > 0 && (!var_kinds || !var_slots)) ||
+        (n_donors > 0 && !h_donors) || (n_acceptors > 0 && !h_acceptors) || (n_excl > 0 && !h_excl)) {
+        amm_set_error("amm_hbond_create: null argument");
+        return 1;
+    }
+    HbondForce *hb = nullptr;
+    if (amm_hbond_create_impl(ctx, code, ncode, consts, nconst, globals, nglobal, var_kinds, var_slots, n_vars, h_donors, n_donors, h_acceptors,
+                              n_acceptors, h_donor_params, n_donor_params, h_acceptor_params, n_acceptor_params, h_excl, n_excl, rc, periodic, &hb))
+        return 1;
+    *force_id = amm_force_register(ctx, AMM_FORCE_HBOND, hb);
+    return 0;
+}
+
+int amm_hbond_set_params(amm_ctx *ctx, int32_t force_id, const double *h_donor_params, int32_t n_donors, int32_t n_donor_params,
+                         const double *h_acceptor_params, int32_t n_acceptors, int32_t n_acceptor_params) {
+    HbondForce *hb = amm_force_get<HbondForce>(ctx, force_id, "amm_hbond_set_params");
+    return hb ? amm_hbond_set_params_impl(ctx, hb, h_donor_params, n_donors, n_donor_params, h_acceptor_params, n_acceptors, n_acceptor_params) : 1;
+}
+
+int amm_hbond_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal) {
+    HbondForce *hb = amm_force_get<HbondForce>(ctx, force_id, "amm_hbond_set_globals");
+    return hb ? amm_hbond_set_globals_impl(ctx, hb, globals, nglobal) : 1;
+}
+
+int amm_hbond_stats(amm_ctx *ctx, int32_t force_id, int64_t *out) {
+    HbondForce *hb = amm_force_get<HbondForce>(ctx, force_id, "amm_hbond_stats");
+    if (!hb) return 1;
+    if (!out) {
+        amm_set_error("amm_hbond_stats: null argument");
+        return 1;
+    }
+    return amm_hbond_stats_impl(ctx, hb, out);
+}
+
+int amm_hbond_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_HBOND, "amm_hbond_release"); }
 
 }   // extern "C"

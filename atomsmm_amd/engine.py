@@ -252,6 +252,8 @@ class _Entry:
         self.cmap = None            # a CMAPTorsionForce (csrc/cmap.hip): its backend id, which is also in term_ids
         self.custom_gb = None       # a CustomGBForce (csrc/custom_gb.hip): dict(id, n_values); the id is also in term_ids, `program`
                                     # is what expr.compile_custom_gb returned
+        self.hbond = None           # a CustomHbondForce (csrc/hbond.hip): dict(id, variables); the id is also in term_ids, term_expr is
+                                    # set, `program` is that of expr.compile_hbond
 
 
 def slice_bounds(n_items, rank, world):
@@ -333,6 +335,7 @@ class Engine:
                                         and dist.is_initialized())
         self._check_gb(system, integrator)
         self._check_custom_gb(system, integrator)
+        self._check_hbond(system, integrator)
         self._check_massless(system, integrator)
         if self.free_space and self.world > 1:
             raise InputError('a System in free space (NoCutoff / CutoffNonPeriodic) runs on a single rank: its pair forces walk all pairs '
@@ -666,6 +669,117 @@ class Engine:
         self._check()
         return out
 
+    HBOND_MAX = 32768         # csrc/hbond.hip: AMM_HB_MAX_ROWS donors, and as many acceptors
+
+    def _check_hbond(self, system, integrator):
+        """What a CustomHbondForce cannot run with, refused by name when the Context is created (its text and limits:
+        _translate_hbond; as a collective variable: _translate_cv_general names the classes it takes)."""
+        if not any(isinstance(f, mm.CustomHbondForce) for f in system.getForces()):
+            return
+        if self.world > 1:
+            raise InputError('a CustomHbondForce runs on a single rank: its passes walk all donor-acceptor pairs and are not sliced')
+        for _kind, _target, expr in getattr(integrator, '_steps', []):
+            if expr and 'deriv(' in expr:
+                raise NotImplementedError('deriv(energy, ...) through a CustomHbondForce is not supported: the hydrogen-bond kernel '
+                                          'differentiates in the geometric variables only (step: %s)' % expr)
+
+    def _translate_hbond(self, force, entry):
+        """A CustomHbondForce: the text compiled with its variable table (expr.compile_hbond) and evaluated over all donor-acceptor
+        pairs by the hydrogen-bond kernels (csrc/hbond.hip).  One backend force, carried in entry.term_ids as a term-expression
+        force is, so every loop over an entry's forces reaches it and the scheduler's fusion rules decline its group."""
+        cls = 'CustomHbondForce'
+        if getattr(force, '_functions', None):
+            raise NotImplementedError('%s: tabulated functions in the energy expression are not supported' % cls)
+        if self.world > 1:
+            raise InputError('a %s runs on a single rank' % cls)
+        method = force.getNonbondedMethod()
+        periodic = method == force.CutoffPeriodic
+        if periodic and self.free_space:
+            raise InputError('%s uses CutoffPeriodic in a System in free space' % cls)
+        dnames = [force.getPerDonorParameterName(k) for k in range(force.getNumPerDonorParameters())]
+        anames = [force.getPerAcceptorParameterName(k) for k in range(force.getNumPerAcceptorParameters())]
+        gnames = [force.getGlobalParameterName(k) for k in range(force.getNumGlobalParameters())]
+        try:
+            prog, variables = X.compile_hbond(force.getEnergyFunction(), dnames, anames, gnames)
+        except X.ExpressionError as exc:
+            raise InputError('%s: not an energy expression the hydrogen-bond kernel can run: %s' % (cls, exc))
+        kinds = [self._COMPOUND_KINDS[kind] for kind, _ in variables]
+        slots = [list(s) for _, s in variables]
+        named = sorted({s for _, ss in variables for s in ss})
+        slot_names = ('d1', 'd2', 'd3', 'a1', 'a2', 'a3')
+        n = self.n
+
+        def tables():
+            out = []
+            for side, rows, names, limit in (('donor', force._donors, dnames, 0), ('acceptor', force._acceptors, anames, 3)):
+                if len(rows) > self.HBOND_MAX:
+                    raise InputError('%s: %d %ss (limit %d)' % (cls, len(rows), side, self.HBOND_MAX))
+                idx = np.zeros((len(rows), 3), dtype=np.int32)
+                par = np.zeros((len(names), len(rows)), dtype=np.float64)
+                for t, (members, p) in enumerate(rows):
+                    if len(p) != len(names):
+                        raise mm.OpenMMException('%s: every %s needs %d parameters' % (cls, side, len(names)))
+                    if not 0 <= members[0] < n or any(not -1 <= m < n for m in members[1:]):
+                        raise mm.OpenMMException('%s: a particle index of %s %d is out of range' % (cls, side, t))
+                    for r in range(3):
+                        if members[r] == -1 and limit + r in named:
+                            raise InputError('%s: the energy expression names %s, which %s %d leaves at -1' % (cls, slot_names[limit + r], side, t))
+                    idx[t] = members
+                    par[:, t] = p
+                out += [idx, par]
+            return out
+
+        def exclusions():
+            ex = np.array(force._exclusions, dtype=np.int32).reshape(-1, 2)
+            if len(ex) and (ex.min() < 0 or ex[:, 0].max() >= force.getNumDonors() or ex[:, 1].max() >= force.getNumAcceptors()):
+                raise mm.OpenMMException('%s: an exclusion names a donor or an acceptor that does not exist (the indices are those of '
+                                         'donors and acceptors, not of atoms)' % cls)
+            return ex
+
+        didx, dpar, aidx, apar = tables()
+        excl = exclusions()
+        rc = 0.0 if method == force.NoCutoff else float(force._cutoff)
+        if method != force.NoCutoff and not rc > 0.0:
+            raise InputError('%s: the cutoff distance must be above zero' % cls)
+        try:
+            fid = self.ctx.hbond_create(prog.code, prog.consts, [self.parameters[g] for g in prog.globals_], kinds, slots, didx, aidx, dpar, apar,
+                                        excl, rc=rc, periodic=periodic)
+        except B.HipError as exc:
+            raise InputError('%s: %s' % (cls, exc))
+        entry.term_ids.append(fid)
+        entry.term_expr = True
+        entry.program = prog
+        entry.hbond = dict(id=fid, variables=variables)
+
+        def reload():          # updateParametersInContext: the per-donor and per-acceptor parameters are read again
+            f_didx, f_dpar, f_aidx, f_apar = tables()
+            if len(f_didx) != len(didx) or len(f_aidx) != len(aidx):
+                raise mm.OpenMMException('updateParametersInContext: the number of donors or acceptors has changed')
+            if not (np.array_equal(f_didx, didx) and np.array_equal(f_aidx, aidx)):
+                raise mm.OpenMMException('updateParametersInContext: the particles of a donor or an acceptor have changed')
+            if not np.array_equal(exclusions(), excl):
+                raise mm.OpenMMException('updateParametersInContext: the exclusions have changed')
+            self.ctx.hbond_set_params(fid, f_dpar, len(didx), f_apar, len(aidx))
+            return 'values'
+        entry.reload = reload
+        if prog.globals_:
+            depends = set(prog.globals_)
+
+            def update(parameters, changed):
+                if not (depends & changed):
+                    return False
+                self.ctx.hbond_set_globals(fid, [parameters[g] for g in prog.globals_])
+                return 'values'
+            entry.update = update
+            entry.depends = depends
+
+    def hbond_stats(self, force):
+        """dict(scanned, survivors, launches, chunks) of a CustomHbondForce of this Context (backend.HipContext.hbond_stats)."""
+        hits = [e for e in self.entries if e.force is force and getattr(e, 'hbond', None) is not None]
+        if not hits:
+            raise mm.OpenMMException('hbond_stats: the force does not belong to this Context')
+        return self.ctx.hbond_stats(hits[0].hbond['id'])
+
     def _translate_gb(self, force, entry):
         """A GBSAOBCForce: one backend force (csrc/gb.hip) carried in entry.term_ids, so every loop over an entry's forces reaches it
         and the scheduler's fusion rules decline its group, as they do for a term-expression force."""
@@ -864,6 +978,8 @@ class Engine:
             self._translate_gb(force, entry)
         elif isinstance(force, mm.CustomGBForce):
             self._translate_custom_gb(force, entry)
+        elif isinstance(force, mm.CustomHbondForce):
+            self._translate_hbond(force, entry)
         elif isinstance(force, mm.CMAPTorsionForce):
             self._translate_cmap(force, entry)
         elif isinstance(force, mm.RBTorsionForce):
@@ -3356,6 +3472,9 @@ class Engine:
         if any(getattr(entry, 'custom_gb', None) is not None for entry in self.entries):
             raise NotImplementedError('deriv(energy, %s) through a CustomGBForce is not supported: the custom generalized-Born kernels '
                                       'have no parameter-derivative evaluation' % name)
+        if any(getattr(entry, 'hbond', None) is not None for entry in self.entries):
+            raise NotImplementedError('deriv(energy, %s) through a CustomHbondForce is not supported: the hydrogen-bond kernel '
+                                      'differentiates in the geometric variables only' % name)
         self._refuse_in_free_space('deriv(energy, %s)' % name)
         if name not in self.parameters:
             raise mm.OpenMMException('deriv(energy, %s): no such Context parameter' % name)

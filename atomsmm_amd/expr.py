@@ -446,7 +446,15 @@ def compile_compound(text, n_slots, prefix, per_bond_names, global_names):
         raise ExpressionError('periodicdistance(...) is not supported in a %s expression' % what)
     particles = {'%s%d' % (prefix, k + 1): k for k in range(int(n_slots))}
     coordinates = {'%s%d' % (axis, k + 1): (axis, (k,)) for axis in 'xyz' for k in range(int(n_slots))}
-    for name in per_bond_names + sorted(global_names):
+    return _geometric_program(text, what, unit_, 'a bond (%s1 .. %s%d)' % (prefix, prefix, n_slots), '%s1 .. %s%d' % (prefix, prefix, n_slots),
+                              particles, coordinates, per_bond_names, global_names)
+
+
+def _geometric_program(text, what, unit_, owner, names_hint, particles, coordinates, parameter_names, global_names, refused_names=None):
+    """The body compile_compound and compile_hbond share.  particles: name -> slot of the names that stand as arguments of distance /
+    angle / dihedral; coordinates: name -> (axis, (slot,)) of the raw coordinates the text may read; parameter k of parameter_names is
+    TERM_P k; refused_names(name): raises for a name the kind of text refuses, else returns None.  Returns (program, variables)."""
+    for name in parameter_names + sorted(global_names):
         if name in particles or name in coordinates:
             raise ExpressionError('%s expression: the parameter %s shadows the %s of that name' % (
                 what, name, 'coordinate' if name in coordinates else unit_[:-1]))
@@ -460,13 +468,17 @@ def compile_compound(text, n_slots, prefix, per_bond_names, global_names):
         return ('op', 'TERM_VAR', variables.index(entry))
 
     def resolve(name):
-        if name in per_bond_names:
-            return ('op', 'TERM_P', per_bond_names.index(name))
+        if name in parameter_names:
+            return ('op', 'TERM_P', parameter_names.index(name))
         if name in coordinates:
             return variable(coordinates[name])
         if name in particles:
             raise ExpressionError('%s expression: %s names one of the %s; it stands only as an argument of distance, angle or dihedral' % (what, name, unit_))
-        return ('global',) if name in global_names else None
+        if name in global_names:
+            return ('global',)
+        if refused_names is not None:
+            refused_names(name)
+        return None
 
     def name_calls(fn, args):
         if fn in _COMPOUND_REFUSED:
@@ -478,14 +490,45 @@ def compile_compound(text, n_slots, prefix, per_bond_names, global_names):
         slots = []
         for a in args:
             if not isinstance(a, ast.Name):
-                raise ExpressionError('%s expression: the arguments of %s are bare names of %s (%s1 .. %s%d), not expressions' % (
-                    what, fn, unit_, prefix, prefix, n_slots))
+                raise ExpressionError('%s expression: the arguments of %s are bare names of %s (%s), not expressions' % (
+                    what, fn, unit_, names_hint))
             if a.id not in particles:
-                raise ExpressionError('%s expression: %s is none of the %s of a bond (%s1 .. %s%d)' % (what, a.id, unit_, prefix, prefix, n_slots))
+                raise ExpressionError('%s expression: %s is none of the %s of %s' % (what, a.id, unit_, owner))
             slots.append(particles[a.id])
         return variable((fn, tuple(slots)))
 
     return _checked_program(text, resolve, what, name_calls=name_calls), variables
+
+
+HBOND_SLOTS = dict(d1=0, d2=1, d3=2, a1=3, a2=4, a3=5)      # the six particles of a donor-acceptor pair
+
+
+def compile_hbond(text, per_donor_names, per_acceptor_names, global_names):
+    """Compile the energy text of a CustomHbondForce for the hydrogen-bond kernel (csrc/hbond.hip).  Returns (program, variables) as
+    compile_compound does: variables[k] = (kind, slots), kind 'distance', 'angle' or 'dihedral' over the bare names d1 d2 d3 a1 a2 a3
+    = slots 0 .. 5, in the order of first use, identical calls sharing one variable.  Per-donor parameter k is TERM_P k, the
+    per-acceptor parameters follow the per-donor ones; a global parameter is GLOBAL k.  The class has no coordinate variables: x1 ...
+    are refused by name, as are pointdistance and its kin and periodicdistance.  The limits are TERM_MAX_PARAMS parameters (donors' and
+    acceptors' together) and COMPOUND_MAX_VARS variables, each an error that names it."""
+    per_donor_names, per_acceptor_names, global_names = list(per_donor_names), list(per_acceptor_names), set(global_names)
+    what = 'hydrogen-bond'
+    names = per_donor_names + per_acceptor_names
+    if len(names) > TERM_MAX_PARAMS:
+        raise InputError('a %s expression takes at most %d per-donor and per-acceptor parameters together (%d + %d given)' % (
+            what, TERM_MAX_PARAMS, len(per_donor_names), len(per_acceptor_names)))
+    for name in names:
+        if names.count(name) > 1:
+            raise ExpressionError('%s expression: the parameter %s is declared twice among the per-donor and per-acceptor parameters' % (what, name))
+    if re.search(r'\bperiodicdistance\s*\(', text):
+        raise ExpressionError('periodicdistance(...) is not supported in a %s expression' % what)
+
+    def refused_names(name):
+        if re.fullmatch(r'[xyz][0-9]+', name):
+            raise ExpressionError('%s expression: the raw coordinate %s is not supported (a CustomHbondForce text reads distance, angle and '
+                                  'dihedral of d1 d2 d3 a1 a2 a3 only)' % (what, name))
+
+    return _geometric_program(text, what, 'particles', 'a donor-acceptor pair (d1 d2 d3 a1 a2 a3)', 'd1 d2 d3 a1 a2 a3', dict(HBOND_SLOTS), {},
+                              names, global_names, refused_names)
 
 
 def compile_cv(text, cv_names, deriv_names, global_names):

@@ -683,6 +683,140 @@ class CustomGBForce(Force, _GlobalParams):
         return context._engine.custom_gb_values(self)
 
 
+class CustomHbondForce(Force, _GlobalParams):
+    """Donors (d1, d2, d3) against acceptors (a1, a2, a3): every pair that is not excluded and whose distance(d1, a1) lies inside the
+    cutoff contributes the energy text -- distance, angle and dihedral over the six particles, per-donor, per-acceptor and global
+    parameters (csrc/hbond.hip).  d2, d3, a2, a3 may be -1 when the text does not name them."""
+    NoCutoff, CutoffNonPeriodic, CutoffPeriodic = range(3)
+
+    def __init__(self, energy):
+        Force.__init__(self)
+        self._init_globals()
+        self._energy = str(energy)
+        self._dnames = []
+        self._anames = []
+        self._donors = []          # [[d1, d2, d3], [parameters]]
+        self._acceptors = []       # [[a1, a2, a3], [parameters]]
+        self._exclusions = []      # (donor, acceptor): indices of donors and acceptors, not of atoms
+        self._functions = []
+        self._method = self.NoCutoff
+        self._cutoff = 1.0
+
+    def usesPeriodicBoundaryConditions(self):
+        return self._method == self.CutoffPeriodic
+
+    def getEnergyFunction(self):
+        return self._energy
+
+    def setEnergyFunction(self, energy):
+        self._energy = str(energy)
+
+    def addPerDonorParameter(self, name):
+        self._dnames.append(str(name))
+        return len(self._dnames) - 1
+
+    def getNumPerDonorParameters(self):
+        return len(self._dnames)
+
+    def getPerDonorParameterName(self, index):
+        return self._dnames[index]
+
+    def setPerDonorParameterName(self, index, name):
+        self._dnames[index] = str(name)
+
+    def addPerAcceptorParameter(self, name):
+        self._anames.append(str(name))
+        return len(self._anames) - 1
+
+    def getNumPerAcceptorParameters(self):
+        return len(self._anames)
+
+    def getPerAcceptorParameterName(self, index):
+        return self._anames[index]
+
+    def setPerAcceptorParameterName(self, index, name):
+        self._anames[index] = str(name)
+
+    def setGlobalParameterName(self, index, name):
+        self._gnames[index] = str(name)
+
+    @staticmethod
+    def _row(p1, p2, p3, parameters):
+        return [[int(p1), int(p2), int(p3)], [float(md_value(p)) for p in parameters]]
+
+    def addDonor(self, d1, d2, d3, parameters=()):
+        self._donors.append(self._row(d1, d2, d3, parameters))
+        return len(self._donors) - 1
+
+    def getNumDonors(self):
+        return len(self._donors)
+
+    def getDonorParameters(self, index):
+        (d1, d2, d3), p = self._donors[index]
+        return [d1, d2, d3, tuple(p)]
+
+    def setDonorParameters(self, index, d1, d2, d3, parameters=()):
+        self._donors[index] = self._row(d1, d2, d3, parameters)
+
+    def addAcceptor(self, a1, a2, a3, parameters=()):
+        self._acceptors.append(self._row(a1, a2, a3, parameters))
+        return len(self._acceptors) - 1
+
+    def getNumAcceptors(self):
+        return len(self._acceptors)
+
+    def getAcceptorParameters(self, index):
+        (a1, a2, a3), p = self._acceptors[index]
+        return [a1, a2, a3, tuple(p)]
+
+    def setAcceptorParameters(self, index, a1, a2, a3, parameters=()):
+        self._acceptors[index] = self._row(a1, a2, a3, parameters)
+
+    def addExclusion(self, donor, acceptor):
+        self._exclusions.append((int(donor), int(acceptor)))
+        return len(self._exclusions) - 1
+
+    def getNumExclusions(self):
+        return len(self._exclusions)
+
+    def getExclusionParticles(self, index):
+        return list(self._exclusions[index])
+
+    def setExclusionParticles(self, index, donor, acceptor):
+        self._exclusions[index] = (int(donor), int(acceptor))
+
+    def addTabulatedFunction(self, name, function):
+        """Recorded; a Context refuses the force by name (the hydrogen-bond kernel runs no tabulated functions)."""
+        self._functions.append((str(name), function))
+        return len(self._functions) - 1
+
+    addFunction = addTabulatedFunction
+
+    def getNumTabulatedFunctions(self):
+        return len(self._functions)
+
+    getNumFunctions = getNumTabulatedFunctions
+
+    def getNonbondedMethod(self):
+        return self._method
+
+    def setNonbondedMethod(self, method):
+        if int(method) not in (self.NoCutoff, self.CutoffNonPeriodic, self.CutoffPeriodic):
+            raise OpenMMException('CustomHbondForce: Illegal value for nonbonded method')
+        self._method = int(method)
+
+    def getCutoffDistance(self):
+        return Quantity(self._cutoff, nm)
+
+    def setCutoffDistance(self, distance):
+        self._cutoff = float(md_value(distance))
+
+    def updateParametersInContext(self, context):
+        """Upload the per-donor and per-acceptor parameters again.  The particles, the counts, the text and the exclusions must not
+        have changed."""
+        context._engine.update_force_parameters(self)
+
+
 class CustomCVForce(Force, _GlobalParams):
     """Energy = function of collective variables, each the energy of an inner Force object."""
 

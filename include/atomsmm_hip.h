@@ -462,6 +462,45 @@ int amm_custom_gb_values(amm_ctx *ctx, int32_t force_id, const double *d_pos, do
 /* Free such a force; the id is retired and leaves every group definition. */
 int amm_custom_gb_release(amm_ctx *ctx, int32_t force_id);
 
+/* CustomHbondForce(any energy text) (force type AMM_FORCE_HBOND; csrc/hbond.hip): n_donors donors (d1, d2, d3)
+ * against n_acceptors acceptors (a1, a2, a3).  Every (donor, acceptor) pair that is not excluded and, with a cutoff, has
+ * |x_d1 - x_a1| < rc contributes the text; the cutoff looks at that one distance only.  rc <= 0: NoCutoff; rc > 0 and periodic = 0:
+ * CutoffNonPeriodic; periodic != 0: CutoffPeriodic -- the cutoff distance AND every displacement inside distance / angle / dihedral
+ * take the minimum image, each on its own (needs a context with a box; the live box of amm_set_box is read at every evaluation).
+ * code / consts / globals: the program of atomsmm_amd.expr.compile_hbond -- the words of amm_term_expr_create with variable k (opcode
+ * 53) = entry k of the variable table and parameter k (54) = the donor's parameter k, behind the n_donor_params of them the
+ * acceptor's; the same limits, checked here with a walk of the stack.  var_kinds: n_vars <= AMM_COMPOUND_MAX_VARS of
+ * AMM_CVAR_DISTANCE / AMM_CVAR_ANGLE / AMM_CVAR_DIHEDRAL (raw coordinates are refused); var_slots: n_vars x 4 slots of the pair, 0 ..
+ * 2 = d1 d2 d3, 3 .. 5 = a1 a2 a3, read up to the kind's arity.  h_donors / h_acceptors: n x 3 atom indices; the second and third may
+ * be -1 (the slot is not there), and then no variable may name that slot.  h_donor_params: n_donor_params x n_donors doubles,
+ * PARAMETER-major, h_acceptor_params likewise; n_donor_params + n_acceptor_params <= AMM_TERM_MAX_PARAMS.  h_excl: n_excl pairs
+ * (donor index, acceptor index) -- indices of donors and acceptors, not of atoms.
+ * Refused, each by name: more than 32768 donors or acceptors, the parameter and variable limits, an atom index or an exclusion index
+ * out of range, a named slot left at -1, CutoffPeriodic without a box, a periodic cutoff above half the shortest box edge (also at
+ * an evaluation, after the box has shrunk), more than one rank.  An ordinary member of a group, evaluated through amm_force_eval and
+ * amm_run_ops, legal in a context without a box; every other family's entry points refuse its id naming AMM_FORCE_HBOND.
+ * Three launches per evaluation: donor rows against acceptor columns (forces on the donors' atoms, the energy), acceptor rows
+ * against donor columns (forces on the acceptors' atoms), and a gather, one lane per atom.  A wavefront owns a row (or one of its
+ * "hbond_chunks" column chunks, amm_set_option), scans 64 columns at a time and queues the survivors in LDS; the interpreter runs
+ * on full queues only.  No atomics: the same positions give the same bits, with and without energy. */
+int amm_hbond_create(amm_ctx *ctx, const int32_t *code, int32_t ncode, const double *consts, int32_t nconst, const double *globals,
+                     int32_t nglobal, const int32_t *var_kinds, const int32_t *var_slots, int32_t n_vars, const int32_t *h_donors,
+                     int32_t n_donors, const int32_t *h_acceptors, int32_t n_acceptors, const double *h_donor_params,
+                     int32_t n_donor_params, const double *h_acceptor_params, int32_t n_acceptor_params, const int32_t *h_excl,
+                     int32_t n_excl, double rc, int32_t periodic, int32_t *force_id);
+/* setDonorParameters / setAcceptorParameters + updateParametersInContext: all per-donor and per-acceptor values again, laid out as
+ * at creation (the same counts; the particles do not change). */
+int amm_hbond_set_params(amm_ctx *ctx, int32_t force_id, const double *h_donor_params, int32_t n_donors, int32_t n_donor_params,
+                         const double *h_acceptor_params, int32_t n_acceptors, int32_t n_acceptor_params);
+/* Context.setParameter(name, value) for a global parameter of such a force: all of the program's globals, in its order. */
+int amm_hbond_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal);
+/* Waits for the stream.  out[0]: the ordered pairs one pass scans (n_donors x n_acceptors); out[1]: the pairs that passed the cutoff
+ * and the exclusions in the last evaluation (0 before the first); out[2]: kernel launches so far; out[3]: column chunks per donor
+ * row. */
+int amm_hbond_stats(amm_ctx *ctx, int32_t force_id, int64_t *out);
+/* Free such a force; the id is retired and leaves every group definition. */
+int amm_hbond_release(amm_ctx *ctx, int32_t force_id);
+
 /* Reciprocal space of a NonbondedForce with nonbondedMethod PME / Ewald, as RESPASystem and FarNonbondedForce
  * keep it in group 2 with the source force's Ewald tolerance / PME parameters (systems.py:74-75,
  * forces.py:185-188; setReciprocalSpaceForceGroup: utils.py:147-152).  Smooth PME, B-spline order 5, grid
@@ -582,7 +621,10 @@ int amm_set_outer_skin(amm_ctx *ctx, double skin_out);
  * amm_check / amm_synchronize / amm_comm_destroy wait for the stream while the context owns an RCCL communicator before they abort it and
  * fail; default 0 = no deadline, the asynchronous error alone is polled), "gb_lanes_per_row" (lanes that sum one row of the
  * generalized-Born passes: 0 = chosen from n as for free-space pair forces; 1, 2, 4 .. 64), "cgb_lanes_per_row" (the same for the
- * passes of a custom generalized-Born force).  Unknown names are an error. */
+ * passes of a custom generalized-Born force), "hbond_chunks" (column chunks a row of a hydrogen-bond force created from now on is
+ * split into, one wavefront each: 0 = chosen from the number of rows; 1 .. 512), "hbond_compact" (0: such a force runs the
+ * interpreter after every batch of 64 columns that has a survivor instead of on full queues -- for measurements; default 1).
+ * Unknown names are an error. */
 int amm_set_option(amm_ctx *ctx, const char *name, double value);
 /* What amm_run_ops fused so far (statistics for tests and bench.py): out[0] = pair-kernel launches that carried the inner RESPA loop
  * of their molecules as an epilogue (the reference runs it as CustomIntegrator steps, propagators.py:933-973), out[1] = pair
