@@ -63,6 +63,7 @@ EXPORTS = [
     'amm_custom_gb_create', 'amm_custom_gb_set_params', 'amm_custom_gb_set_globals', 'amm_custom_gb_set_tables', 'amm_custom_gb_values',
     'amm_custom_gb_release',
     'amm_hbond_create', 'amm_hbond_set_params', 'amm_hbond_set_globals', 'amm_hbond_stats', 'amm_hbond_release',
+    'amm_many_create', 'amm_many_set_params', 'amm_many_set_globals', 'amm_many_stats', 'amm_many_release',
     'amm_vsite_define', 'amm_vsite_place', 'amm_vsite_spread', 'amm_vsite_stats',
 ]
 
@@ -215,6 +216,12 @@ def lib():
         L.amm_hbond_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
         L.amm_hbond_stats.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
         L.amm_hbond_release.argtypes = [vp, C.c_int32]
+        L.amm_many_create.argtypes = [vp, ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip, ip, C.c_int32, C.c_int32, dp, C.c_int32, ip, C.c_int32, ip,
+                                      ip, C.c_int32, C.c_double, C.c_int32, C.c_int32, ip]
+        L.amm_many_set_params.argtypes = [vp, C.c_int32, dp, C.c_int32, C.c_int32, ip, C.c_int32, ip]
+        L.amm_many_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
+        L.amm_many_stats.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
+        L.amm_many_release.argtypes = [vp, C.c_int32]
         L.amm_cv_create.argtypes = [vp, ip, C.c_int32, C.c_int32, ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip]
         L.amm_cv_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
         L.amm_cv_set_variables.argtypes = [vp, C.c_int32, dp, C.c_int32]
@@ -729,6 +736,59 @@ class HipContext:
     def hbond_release(self, fid):
         """Free a hydrogen-bond force (its id is retired)."""
         _chk(lib().amm_hbond_release(self.h, fid))
+
+    def many_create(self, code, consts, globals_, var_kinds, var_slots, params, types, n_types, perm_table, excl_pairs=None, rc=0.0,
+                    periodic=False, central=False):
+        """A many-particle force over sets of three (csrc/manyparticle.hip): the program and the variable table of
+        expr.compile_many_particle -- var_kinds[k] one of CVAR_*, var_slots[k] its slots 0 .. 2 = p1 p2 p3 -- params: n_params x n,
+        parameter-major; types: the dense type index of every particle; perm_table: n_types^3 permutation codes (-1: skip;
+        engine.many_particle_table); excl_pairs: pairs of particles; rc <= 0: NoCutoff; periodic: CutoffPeriodic; central:
+        UniqueCentralParticle."""
+        c_, cp = _hi(np.asarray(code, dtype=np.int32).reshape(-1))
+        k_, kp = _hd(consts if len(consts) else [0.0])
+        g_, gp = _hd(globals_ if len(globals_) else [0.0])
+        n_vars = len(var_kinds)
+        slots = np.zeros((max(n_vars, 1), 4), dtype=np.int32)
+        for k, s in enumerate(var_slots):
+            slots[k, :len(s)] = s
+        vk_, vkp = _hi(var_kinds if n_vars else [0])
+        vs_, vsp = _hi(slots)
+        ty = np.asarray(types, dtype=np.int32).reshape(-1)
+        par = np.asarray(params, dtype=np.float64).reshape(-1, len(ty)) if np.size(params) else np.zeros((0, len(ty)))
+        ex = np.zeros((0, 2), np.int32) if excl_pairs is None else np.asarray(excl_pairs, dtype=np.int32).reshape(-1, 2)
+        p_, pp = _hd(par if par.size else [0.0])
+        t_, tp = _hi(ty if len(ty) else [0])
+        m_, mp = _hi(np.asarray(perm_table, dtype=np.int32).reshape(-1))
+        ex_, exp_ = _hi(ex if len(ex) else [0])
+        fid = C.c_int32(-1)
+        _chk(lib().amm_many_create(self.h, cp, len(c_), kp, len(consts), gp, len(globals_), vkp, vsp, n_vars, len(ty), pp, len(par), tp, int(n_types),
+                                   mp, exp_, len(ex), float(rc), 1 if periodic else 0, 1 if central else 0, C.byref(fid)))
+        return fid.value
+
+    def many_set_params(self, fid, params, types, n_types, perm_table):
+        """All per-particle values (n_params x n, parameter-major), the types and the permutation table again."""
+        ty = np.asarray(types, dtype=np.int32).reshape(-1)
+        par = np.asarray(params, dtype=np.float64).reshape(-1, len(ty)) if np.size(params) else np.zeros((0, len(ty)))
+        p_, pp = _hd(par if par.size else [0.0])
+        t_, tp = _hi(ty if len(ty) else [0])
+        m_, mp = _hi(np.asarray(perm_table, dtype=np.int32).reshape(-1))
+        _chk(lib().amm_many_set_params(self.h, fid, pp, len(ty), len(par), tp, int(n_types), mp))
+
+    def many_set_globals(self, fid, globals_):
+        g_, gp = _hd(globals_ if len(globals_) else [0.0])
+        _chk(lib().amm_many_set_globals(self.h, fid, gp, len(globals_)))
+
+    def many_stats(self, fid):
+        """dict(particles, sets, launches, fullest, capacity): the evaluations of the text whose energy the last evaluation summed
+        (SinglePermutation: the sets; UniqueCentralParticle: one per set and centre), kernel launches so far, the fullest neighbour
+        row of the last evaluation and the capacity of a row (waits for the stream)."""
+        out = (C.c_int64 * 5)()
+        _chk(lib().amm_many_stats(self.h, fid, out))
+        return dict(particles=int(out[0]), sets=int(out[1]), launches=int(out[2]), fullest=int(out[3]), capacity=int(out[4]))
+
+    def many_release(self, fid):
+        """Free a many-particle force (its id is retired)."""
+        _chk(lib().amm_many_release(self.h, fid))
 
     def cv_create(self, inner_ids, n_deriv, code, consts, globals_):
         """A CustomCVForce with any energy text (csrc/cv.hip): the ids of the inner forces in the order of the collective variables

@@ -148,6 +148,20 @@ int amm_check(amm_ctx *ctx) {
         return 2;
     }
     for (size_t id = 0; id < ctx->forces.size(); ++id) {
+        if (ManyForce *mf = ctx->forces[id].as<ManyForce>()) {
+            int need = 0, capacity = 0;
+            const int over = amm_many_overflow(mf, &need, &capacity);
+            if (over < 0) {
+                amm_set_error("amm_check: reading the flag of many-particle force " + std::to_string(id) + " failed");
+                return 1;
+            }
+            if (over) {
+                amm_set_error("neighbour table overflow in many-particle force " + std::to_string(id) + " (AMM_FORCE_MANY_PARTICLE): a particle has " +
+                              std::to_string(need) + " neighbours > capacity " + std::to_string(capacity) +
+                              " (option many_capacity); the energy and the forces of that evaluation are unspecified");
+                return 2;
+            }
+        }
         PairForce *pf = ctx->forces[id].pair();
         if (pf && pf->cl && pf->cl->built) {
             int cf[8];
@@ -1510,6 +1524,13 @@ int amm_set_option(amm_ctx *ctx, const char *name, double value) {
         ctx->opt_hbond_chunks = v;
     }
     else if (k == "hbond_compact") ctx->opt_hbond_compact = v != 0;
+    else if (k == "many_capacity") {
+        if (v < 64 || v > 4096 || v % 64 != 0) {
+            amm_set_error("amm_set_option: many_capacity is a multiple of 64 from 64 to 4096 neighbours per row");
+            return 1;
+        }
+        ctx->opt_many_capacity = v;
+    }
     else {
         amm_set_error("amm_set_option: unknown option '" + k + "'");
         return 1;

@@ -1,7 +1,7 @@
 // atomsmm_amd/csrc/families.hip -- the table of force families (amm_ctx.h: ForceFamily) and everything derived from it: the typed lookup
 // with its refusals, registration, release and the dispatch of an evaluation; then the extern "C" entry points of the families whose
 // implementation is a .hip file of its own (term expressions, collective variables, compound bonds, generalized Born, CMAP, custom
-// generalized Born, hydrogen bonds).
+// generalized Born, hydrogen bonds, many-particle sets).
 #include <algorithm>
 #include <cstring>
 
@@ -22,7 +22,7 @@ static int released_eval(amm_ctx *, void *, const double *, double *, int, doubl
 }
 static void released_free(void *) {}
 
-// One row per AMM_FORCE_* value (a released id and the ten families), in the enum's order: noun phrase, tag, entry points, bad-id wording, single rank, eval, free.
+// One row per AMM_FORCE_* value (a released id and the eleven families), in the enum's order: noun phrase, tag, entry points, bad-id wording, single rank, eval, free.
 const ForceFamily &amm_family(int type) {
     static const ForceFamily rows[AMM_FORCE_TYPES] = {
         {"a released id", "AMM_FORCE_RELEASED", "none", "released force id", false, released_eval, released_free},
@@ -47,6 +47,8 @@ const ForceFamily &amm_family(int type) {
          eval_as<CustomGbForce, amm_custom_gb_eval_impl>, free_as<CustomGbForce, amm_custom_gb_free>},
         {"a hydrogen-bond force", "AMM_FORCE_HBOND", "amm_hbond_*", "not the id of a hydrogen-bond force (AMM_FORCE_HBOND)", true,
          eval_as<HbondForce, amm_hbond_eval_impl>, free_as<HbondForce, amm_hbond_free>},
+        {"a many-particle force", "AMM_FORCE_MANY_PARTICLE", "amm_many_*", "not the id of a many-particle force (AMM_FORCE_MANY_PARTICLE)", true,
+         eval_as<ManyForce, amm_many_eval_impl>, free_as<ManyForce, amm_many_free>},
     };
     return rows[type];
 }
@@ -391,5 +393,49 @@ int amm_hbond_stats(amm_ctx *ctx, int32_t force_id, int64_t *out) {
 }
 
 int amm_hbond_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_HBOND, "amm_hbond_release"); }
+
+// CustomManyParticleForce(3, any energy text) (csrc/manyparticle.hip): the compiled text and its variable table (atomsmm_amd/expr.py:
+// compile_many_particle), the per-particle parameters, parameter-major, the dense type index of every particle and the permutation
+// table over them, the excluded pairs of particles, the cutoff (rc <= 0: NoCutoff), whether displacements take the minimum image and
+// the permutation mode (central != 0: UniqueCentralParticle)
+int amm_many_create(amm_ctx *ctx, const int32_t *code, int32_t ncode, const double *consts, int32_t nconst, const double *globals, int32_t nglobal,
+                    const int32_t *var_kinds, const int32_t *var_slots, int32_t n_vars, int32_t n_particles, const double *h_params,
+                    int32_t n_params, const int32_t *h_types, int32_t n_types, const int32_t *h_perm, const int32_t *h_excl, int32_t n_excl,
+                    double rc, int32_t periodic, int32_t central, int32_t *force_id) {
+    if (!ctx || !code || !force_id || (nconst > 0 && !consts) || (nglobal > 0 && !globals) || (n_vars > 0 && (!var_kinds || !var_slots)) ||
+        (n_particles > 0 && !h_types) || !h_perm || (n_excl > 0 && !h_excl)) {
+        amm_set_error("amm_many_create: null argument");
+        return 1;
+    }
+    ManyForce *mf = nullptr;
+    if (amm_many_create_impl(ctx, code, ncode, consts, nconst, globals, nglobal, var_kinds, var_slots, n_vars, n_particles, h_params, n_params,
+                             h_types, n_types, h_perm, h_excl, n_excl, rc, periodic, central, &mf))
+        return 1;
+    *force_id = amm_force_register(ctx, AMM_FORCE_MANY_PARTICLE, mf);
+    return 0;
+}
+
+int amm_many_set_params(amm_ctx *ctx, int32_t force_id, const double *h_params, int32_t n_particles, int32_t n_params, const int32_t *h_types,
+                        int32_t n_types, const int32_t *h_perm) {
+    ManyForce *mf = amm_force_get<ManyForce>(ctx, force_id, "amm_many_set_params");
+    return mf ? amm_many_set_params_impl(ctx, mf, h_params, n_particles, n_params, h_types, n_types, h_perm) : 1;
+}
+
+int amm_many_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal) {
+    ManyForce *mf = amm_force_get<ManyForce>(ctx, force_id, "amm_many_set_globals");
+    return mf ? amm_many_set_globals_impl(ctx, mf, globals, nglobal) : 1;
+}
+
+int amm_many_stats(amm_ctx *ctx, int32_t force_id, int64_t *out) {
+    ManyForce *mf = amm_force_get<ManyForce>(ctx, force_id, "amm_many_stats");
+    if (!mf) return 1;
+    if (!out) {
+        amm_set_error("amm_many_stats: null argument");
+        return 1;
+    }
+    return amm_many_stats_impl(ctx, mf, out);
+}
+
+int amm_many_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_MANY_PARTICLE, "amm_many_release"); }
 
 }   // extern "C"

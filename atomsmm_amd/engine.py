@@ -254,6 +254,32 @@ class _Entry:
                                     # is what expr.compile_custom_gb returned
         self.hbond = None           # a CustomHbondForce (csrc/hbond.hip): dict(id, variables); the id is also in term_ids, term_expr is
                                     # set, `program` is that of expr.compile_hbond
+        self.many = None            # a CustomManyParticleForce (csrc/manyparticle.hip): dict(id, variables, types); carried as hbond is,
+                                    # `program` is that of expr.compile_many_particle
+
+
+MANY_PERMUTATIONS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))     # of a tuple's positions, in lexicographic order
+
+
+def many_particle_table(filters, types, central):
+    """The permutation table of a CustomManyParticleForce over sets of three (csrc/manyparticle.hip).  filters[r]: the
+    set of types role r takes (empty: any); types: the sorted distinct types of the particles, whose positions are the dense type
+    indices.  Entry [a][b][c] speaks for a set whose tuple -- its particles in ascending order or, in central mode, the centre first
+    and the satellites ascending -- has the dense types (a, b, c): the code k of the first permutation MANY_PERMUTATIONS[k] = perm,
+    in lexicographic order, for which every role r takes the type of the tuple's element perm[r], or -1 when there is none (the set
+    is skipped).  Central mode keeps the centre at p1: codes 0 and 1 only.  Returns an int32 array [T][T][T]."""
+    T = len(types)
+    table = np.full((T, T, T), -1, dtype=np.int32)
+    candidates = MANY_PERMUTATIONS[:2] if central else MANY_PERMUTATIONS
+    for a in range(T):
+        for b in range(T):
+            for c in range(T):
+                tuple_types = (types[a], types[b], types[c])
+                for code, perm in enumerate(candidates):
+                    if all(not filters[r] or tuple_types[perm[r]] in filters[r] for r in range(3)):
+                        table[a, b, c] = code
+                        break
+    return table
 
 
 def slice_bounds(n_items, rank, world):
@@ -336,6 +362,7 @@ class Engine:
         self._check_gb(system, integrator)
         self._check_custom_gb(system, integrator)
         self._check_hbond(system, integrator)
+        self._check_many_particle(system, integrator)
         self._check_massless(system, integrator)
         if self.free_space and self.world > 1:
             raise InputError('a System in free space (NoCutoff / CutoffNonPeriodic) runs on a single rank: its pair forces walk all pairs '
@@ -780,6 +807,121 @@ class Engine:
             raise mm.OpenMMException('hbond_stats: the force does not belong to this Context')
         return self.ctx.hbond_stats(hits[0].hbond['id'])
 
+    MANY_MAX = 32768          # csrc/manyparticle.hip: AMM_MP_MAX_PARTICLES
+    MANY_MAX_NOCUTOFF = 2048  # ... AMM_MP_MAX_NOCUTOFF: the neighbour table is n x (n - 1) without a cutoff
+    MANY_MAX_TYPES = 16       # ... AMM_MP_MAX_TYPES
+
+    def _check_many_particle(self, system, integrator):
+        """What a CustomManyParticleForce cannot run with, refused by name when the Context is created (its text and limits:
+        _translate_many_particle; as a collective variable: _translate_cv_general names the classes it takes)."""
+        if not any(isinstance(f, mm.CustomManyParticleForce) for f in system.getForces()):
+            return
+        if self.world > 1:
+            raise InputError('a CustomManyParticleForce runs on a single rank: its wavefronts walk the neighbours of every particle and are not sliced')
+        for _kind, _target, expr in getattr(integrator, '_steps', []):
+            if expr and 'deriv(' in expr:
+                raise NotImplementedError('deriv(energy, ...) through a CustomManyParticleForce is not supported: the many-particle kernel '
+                                          'differentiates in the geometric variables only (step: %s)' % expr)
+
+    def _translate_many_particle(self, force, entry):
+        """A CustomManyParticleForce over sets of three: the text compiled with its variable table (expr.compile_many_particle), the
+        type filters turned into the permutation table (many_particle_table) and the sets enumerated on the device by the
+        many-particle kernels (csrc/manyparticle.hip).  One backend force, carried in entry.term_ids as a hydrogen-bond force is, so
+        every loop over an entry's forces reaches it and the scheduler's fusion rules decline its group."""
+        cls = 'CustomManyParticleForce'
+        per_set = force.getNumParticlesPerSet()
+        if per_set != 3:
+            raise NotImplementedError('%s: sets of %d particles are not supported (the many-particle kernel enumerates sets of three)' % (cls, per_set))
+        if getattr(force, '_functions', None):
+            raise NotImplementedError('%s: tabulated functions in the energy expression are not supported' % cls)
+        if self.world > 1:
+            raise InputError('a %s runs on a single rank' % cls)
+        method = force.getNonbondedMethod()
+        periodic = method == force.CutoffPeriodic
+        if periodic and self.free_space:
+            raise InputError('%s uses CutoffPeriodic in a System in free space' % cls)
+        central = force.getPermutationMode() == force.UniqueCentralParticle
+        pnames = [force.getPerParticleParameterName(k) for k in range(force.getNumPerParticleParameters())]
+        gnames = [force.getGlobalParameterName(k) for k in range(force.getNumGlobalParameters())]
+        try:
+            prog, variables = X.compile_many_particle(force.getEnergyFunction(), 3, pnames, gnames)
+        except X.ExpressionError as exc:
+            raise InputError('%s: not an energy expression the many-particle kernel can run: %s' % (cls, exc))
+        kinds = [self._COMPOUND_KINDS[kind] for kind, _ in variables]
+        slots = [list(s) for _, s in variables]
+        n = self.n
+        if force.getNumParticles() != n:
+            raise mm.OpenMMException('%s: the force has %d particles, the System %d' % (cls, force.getNumParticles(), n))
+        if n > self.MANY_MAX:
+            raise InputError('%s: %d particles (limit %d)' % (cls, n, self.MANY_MAX))
+        if method == force.NoCutoff and n > self.MANY_MAX_NOCUTOFF:
+            raise InputError('%s: %d particles under NoCutoff (limit %d: the neighbour table is n x (n - 1); use a cutoff)' % (cls, n, self.MANY_MAX_NOCUTOFF))
+
+        def tables():
+            par = np.zeros((len(pnames), n), dtype=np.float64)
+            raw = np.zeros(n, dtype=np.int64)
+            for t, (p, kind) in enumerate(force._particles):
+                if len(p) != len(pnames):
+                    raise mm.OpenMMException('%s: every particle needs %d parameters' % (cls, len(pnames)))
+                par[:, t] = p
+                raw[t] = kind
+            known = sorted(set(raw.tolist()))
+            if len(known) > self.MANY_MAX_TYPES:
+                raise InputError('%s: %d distinct particle types (limit %d)' % (cls, len(known), self.MANY_MAX_TYPES))
+            known = known or [0]
+            dense = np.array([known.index(t) for t in raw.tolist()], dtype=np.int32)
+            filters = [force.getTypeFilter(r) for r in range(3)]
+            return par, dense, len(known), many_particle_table(filters, known, central)
+
+        def exclusions():
+            ex = np.array(force._exclusions, dtype=np.int32).reshape(-1, 2)
+            if len(ex) and (ex.min() < 0 or ex.max() >= n):
+                raise mm.OpenMMException('%s: an exclusion names a particle that does not exist' % cls)
+            return ex
+
+        par, dense, n_types, table = tables()
+        excl = exclusions()
+        rc = 0.0 if method == force.NoCutoff else float(force._cutoff)
+        if method != force.NoCutoff and not rc > 0.0:
+            raise InputError('%s: the cutoff distance must be above zero' % cls)
+        try:
+            fid = self.ctx.many_create(prog.code, prog.consts, [self.parameters[g] for g in prog.globals_], kinds, slots, par, dense, n_types, table,
+                                       excl, rc=rc, periodic=periodic, central=central)
+        except B.HipError as exc:
+            raise InputError('%s: %s' % (cls, exc))
+        entry.term_ids.append(fid)
+        entry.term_expr = True
+        entry.program = prog
+        entry.many = dict(id=fid, variables=variables, types=n_types)
+
+        def reload():          # updateParametersInContext: the per-particle parameters, the types and the filters are read again
+            if force.getNumParticles() != n:
+                raise mm.OpenMMException('updateParametersInContext: the number of particles has changed')
+            if not np.array_equal(exclusions(), excl):
+                raise mm.OpenMMException('updateParametersInContext: the exclusions have changed')
+            f_par, f_dense, f_types, f_table = tables()
+            self.ctx.many_set_params(fid, f_par, f_dense, f_types, f_table)
+            entry.many['types'] = f_types
+            return 'values'
+        entry.reload = reload
+        if prog.globals_:
+            depends = set(prog.globals_)
+
+            def update(parameters, changed):
+                if not (depends & changed):
+                    return False
+                self.ctx.many_set_globals(fid, [parameters[g] for g in prog.globals_])
+                return 'values'
+            entry.update = update
+            entry.depends = depends
+
+    def many_stats(self, force):
+        """dict(particles, sets, launches, fullest, capacity) of a CustomManyParticleForce of this Context (backend.HipContext.many_stats)."""
+        hits = [e for e in self.entries if e.force is force and getattr(e, 'many', None) is not None]
+        if not hits:
+            raise mm.OpenMMException('many_stats: the force does not belong to this Context')
+        return self.ctx.many_stats(hits[0].many['id'])
+
     def _translate_gb(self, force, entry):
         """A GBSAOBCForce: one backend force (csrc/gb.hip) carried in entry.term_ids, so every loop over an entry's forces reaches it
         and the scheduler's fusion rules decline its group, as they do for a term-expression force."""
@@ -980,6 +1122,8 @@ class Engine:
             self._translate_custom_gb(force, entry)
         elif isinstance(force, mm.CustomHbondForce):
             self._translate_hbond(force, entry)
+        elif isinstance(force, mm.CustomManyParticleForce):
+            self._translate_many_particle(force, entry)
         elif isinstance(force, mm.CMAPTorsionForce):
             self._translate_cmap(force, entry)
         elif isinstance(force, mm.RBTorsionForce):
@@ -3474,6 +3618,9 @@ class Engine:
                                       'have no parameter-derivative evaluation' % name)
         if any(getattr(entry, 'hbond', None) is not None for entry in self.entries):
             raise NotImplementedError('deriv(energy, %s) through a CustomHbondForce is not supported: the hydrogen-bond kernel '
+                                      'differentiates in the geometric variables only' % name)
+        if any(getattr(entry, 'many', None) is not None for entry in self.entries):
+            raise NotImplementedError('deriv(energy, %s) through a CustomManyParticleForce is not supported: the many-particle kernel '
                                       'differentiates in the geometric variables only' % name)
         self._refuse_in_free_space('deriv(energy, %s)' % name)
         if name not in self.parameters:

@@ -531,6 +531,49 @@ def compile_hbond(text, per_donor_names, per_acceptor_names, global_names):
                               names, global_names, refused_names)
 
 
+MANY_PARTICLE_MAX_PARAMS = 2     # per-particle parameters of a many-particle text: three suffixed copies each
+
+
+def many_particle_parameter_names(n_slots, per_particle_names):
+    """The names a many-particle text reads its per-particle parameters by, in the order of TERM_P: role by role (sigma1, eps1,
+    sigma2, eps2, sigma3, eps3)."""
+    return ['%s%d' % (name, r + 1) for r in range(int(n_slots)) for name in per_particle_names]
+
+
+def compile_many_particle(text, n_slots, per_particle_names, global_names):
+    """Compile the energy text of a CustomManyParticleForce for the many-particle kernel (csrc/manyparticle.hip).  Returns (program,
+    variables) as compile_compound does: variables[k] = (kind, slots), kind 'distance', 'angle' or 'dihedral' over the bare names
+    p1 .. p<n_slots>, or 'x', 'y', 'z' for the raw coordinates x1 .. z<n_slots> (never wrapped), in the order of first use,
+    identical calls sharing one variable.  Per-particle parameter k of the particle in role r (named <name><r + 1>) is TERM_P
+    r * P + k; a global parameter is GLOBAL k.  pointdistance and its kin and periodicdistance are refused by name.  The limits are
+    MANY_PARTICLE_MAX_PARAMS per-particle parameters (n_slots * P <= TERM_MAX_PARAMS) and COMPOUND_MAX_VARS variables, each an error
+    that names it."""
+    per_particle_names, global_names = list(per_particle_names), set(global_names)
+    what = 'many-particle'
+    n_slots = int(n_slots)
+    if not 1 <= n_slots <= COMPOUND_MAX_SLOTS:
+        raise InputError('a %s expression takes 1 to %d particles per set (%d given)' % (what, COMPOUND_MAX_SLOTS, n_slots))
+    if len(per_particle_names) > MANY_PARTICLE_MAX_PARAMS or n_slots * len(per_particle_names) > TERM_MAX_PARAMS:
+        raise InputError('a %s expression takes at most %d per-particle parameters (%d given; each has %d suffixed copies, at most %d '
+                         'together)' % (what, MANY_PARTICLE_MAX_PARAMS, len(per_particle_names), n_slots, TERM_MAX_PARAMS))
+    for name in per_particle_names:
+        if per_particle_names.count(name) > 1:
+            raise ExpressionError('%s expression: the per-particle parameter %s is declared twice' % (what, name))
+    if re.search(r'\bperiodicdistance\s*\(', text):
+        raise ExpressionError('periodicdistance(...) is not supported in a %s expression' % what)
+    particles = {'p%d' % (k + 1): k for k in range(n_slots)}
+    coordinates = {'%s%d' % (axis, k + 1): (axis, (k,)) for axis in 'xyz' for k in range(n_slots)}
+    hint = 'p1 .. p%d' % n_slots
+
+    def refused_names(name):
+        if name in per_particle_names:
+            raise ExpressionError('%s expression: the per-particle parameter %s is read with the suffix of its particle (%s1 .. %s%d)' % (
+                what, name, name, name, n_slots))
+
+    return _geometric_program(text, what, 'particles', 'a set (%s)' % hint, hint, particles, coordinates,
+                              many_particle_parameter_names(n_slots, per_particle_names), global_names, refused_names)
+
+
 def compile_cv(text, cv_names, deriv_names, global_names):
     """Compile the energy text of a CustomCVForce for the collective-variable kernel (csrc/cv.hip): collective variable k of `cv_names`
     is TERM_VAR k, and the parameters the force asked derivatives for (`deriv_names`) follow as TERM_VAR K + p -- variables, not

@@ -817,6 +817,163 @@ class CustomHbondForce(Force, _GlobalParams):
         context._engine.update_force_parameters(self)
 
 
+class CustomManyParticleForce(Force, _GlobalParams):
+    """Sets of `particlesPerSet` particles: every set of distinct particles no pair of which is excluded and which lies inside the
+    cutoff contributes the energy text -- distance, angle and dihedral over p1 p2 ..., the raw coordinates x1 ..., per-particle
+    parameters suffixed with the role (sigma1, sigma2, ...) and global parameters.  A Context runs sets of three
+    (csrc/manyparticle.hip); the class stores any value."""
+    NoCutoff, CutoffNonPeriodic, CutoffPeriodic = range(3)
+    SinglePermutation, UniqueCentralParticle = range(2)
+
+    def __init__(self, particlesPerSet, energy):
+        Force.__init__(self)
+        self._init_globals()
+        self._per_set = int(particlesPerSet)
+        self._energy = str(energy)
+        self._pnames = []
+        self._particles = []       # [[parameters], type]
+        self._exclusions = []
+        self._filters = {}         # role index -> set of types; a role without an entry takes every type
+        self._functions = []
+        self._method = self.NoCutoff
+        self._mode = self.SinglePermutation
+        self._cutoff = 1.0
+
+    def usesPeriodicBoundaryConditions(self):
+        return self._method == self.CutoffPeriodic
+
+    def getNumParticlesPerSet(self):
+        return self._per_set
+
+    def getEnergyFunction(self):
+        return self._energy
+
+    def setEnergyFunction(self, energy):
+        self._energy = str(energy)
+
+    def getNonbondedMethod(self):
+        return self._method
+
+    def setNonbondedMethod(self, method):
+        if int(method) not in (self.NoCutoff, self.CutoffNonPeriodic, self.CutoffPeriodic):
+            raise OpenMMException('CustomManyParticleForce: Illegal value for nonbonded method')
+        self._method = int(method)
+
+    def getPermutationMode(self):
+        return self._mode
+
+    def setPermutationMode(self, mode):
+        if int(mode) not in (self.SinglePermutation, self.UniqueCentralParticle):
+            raise OpenMMException('CustomManyParticleForce: Illegal value for permutation mode')
+        self._mode = int(mode)
+
+    def getCutoffDistance(self):
+        return Quantity(self._cutoff, nm)
+
+    def setCutoffDistance(self, distance):
+        self._cutoff = float(md_value(distance))
+
+    def addPerParticleParameter(self, name):
+        self._pnames.append(str(name))
+        return len(self._pnames) - 1
+
+    def getNumPerParticleParameters(self):
+        return len(self._pnames)
+
+    def getPerParticleParameterName(self, index):
+        return self._pnames[index]
+
+    def setPerParticleParameterName(self, index, name):
+        self._pnames[index] = str(name)
+
+    def setGlobalParameterName(self, index, name):
+        self._gnames[index] = str(name)
+
+    def addParticle(self, parameters=(), type=0):
+        self._particles.append([[float(md_value(p)) for p in parameters], int(type)])
+        return len(self._particles) - 1
+
+    def getNumParticles(self):
+        return len(self._particles)
+
+    def getParticleParameters(self, index):
+        p, t = self._particles[index]
+        return [tuple(p), t]
+
+    def setParticleParameters(self, index, parameters, type=0):
+        self._particles[index] = [[float(md_value(p)) for p in parameters], int(type)]
+
+    def addExclusion(self, particle1, particle2):
+        self._exclusions.append((int(particle1), int(particle2)))
+        return len(self._exclusions) - 1
+
+    def getNumExclusions(self):
+        return len(self._exclusions)
+
+    def getExclusionParticles(self, index):
+        return list(self._exclusions[index])
+
+    def setExclusionParticles(self, index, particle1, particle2):
+        self._exclusions[index] = (int(particle1), int(particle2))
+
+    def createExclusionsFromBonds(self, bonds, bondCutoff):
+        """Exclude every pair of particles that at most `bondCutoff` bonds separate."""
+        if int(bondCutoff) < 1:
+            return
+        n = len(self._particles)
+        partners = [set() for _ in range(n)]
+        for a, b in bonds:
+            a, b = int(a), int(b)
+            if not (0 <= a < n and 0 <= b < n):
+                raise OpenMMException('createExclusionsFromBonds: Illegal particle index in list of bonds')
+            partners[a].add(b)
+            partners[b].add(a)
+        have = {(min(a, b), max(a, b)) for a, b in self._exclusions}
+        for start in range(n):
+            reached, frontier = {start}, {start}
+            for _ in range(int(bondCutoff)):
+                frontier = {b for a in frontier for b in partners[a]} - reached
+                reached |= frontier
+            for other in sorted(reached):
+                if other > start and (start, other) not in have:
+                    have.add((start, other))
+                    self.addExclusion(start, other)
+
+    def getTypeFilter(self, index):
+        """The types the particle in role `index` may have; an empty set: any."""
+        if not 0 <= int(index) < self._per_set:
+            raise OpenMMException('CustomManyParticleForce: Index out of range')
+        return set(self._filters.get(int(index), ()))
+
+    def setTypeFilter(self, index, types):
+        if not 0 <= int(index) < self._per_set:
+            raise OpenMMException('CustomManyParticleForce: Index out of range')
+        self._filters[int(index)] = {int(t) for t in types}
+
+    def addTabulatedFunction(self, name, function):
+        """Recorded; a Context refuses the force by name (the many-particle kernel runs no tabulated functions)."""
+        self._functions.append((str(name), function))
+        return len(self._functions) - 1
+
+    addFunction = addTabulatedFunction
+
+    def getNumTabulatedFunctions(self):
+        return len(self._functions)
+
+    getNumFunctions = getNumTabulatedFunctions
+
+    def getTabulatedFunction(self, index):
+        return self._functions[index][1]
+
+    def getTabulatedFunctionName(self, index):
+        return self._functions[index][0]
+
+    def updateParametersInContext(self, context):
+        """Upload the per-particle parameters, the types and the type filters again.  The number of particles, the text and the
+        exclusions must not have changed."""
+        context._engine.update_force_parameters(self)
+
+
 class CustomCVForce(Force, _GlobalParams):
     """Energy = function of collective variables, each the energy of an inner Force object."""
 

@@ -282,6 +282,9 @@ class ComputingSystem(_AtomsMM_System):
         if any(isinstance(force, openmm.CustomHbondForce) for force in system.getForces()):
             raise NotImplementedError('ComputingSystem / PressureComputer: the virial of a CustomHbondForce is not supported (the '
                                       'hydrogen-bond kernel parks forces per donor and acceptor, not the pair virial)')
+        if any(isinstance(force, openmm.CustomManyParticleForce) for force in system.getForces()):
+            raise NotImplementedError('ComputingSystem / PressureComputer: the virial of a CustomManyParticleForce is not supported (the '
+                                      'many-particle kernel keeps the force on the owning particle of a set, not the set\'s virial)')
         if any(isinstance(force, openmm.CustomGBForce) for force in system.getForces()):
             raise NotImplementedError('ComputingSystem / PressureComputer: the virial of a CustomGBForce is not supported (generalized-Born '
                                       'solvent runs in free space only, where there is no pressure)')

@@ -501,6 +501,51 @@ int amm_hbond_stats(amm_ctx *ctx, int32_t force_id, int64_t *out);
 /* Free such a force; the id is retired and leaves every group definition. */
 int amm_hbond_release(amm_ctx *ctx, int32_t force_id);
 
+/* CustomManyParticleForce(3, any energy text) (force type AMM_FORCE_MANY_PARTICLE; csrc/manyparticle.hip):
+ * every set of three distinct particles {i, j, k} no pair of which is excluded contributes the text.  n_particles is 0 or the
+ * context's atom count: particle i is atom i.  rc <= 0: NoCutoff (at most 2048 particles: the neighbour table is n x (n - 1));
+ * rc > 0 and periodic = 0: CutoffNonPeriodic; periodic != 0: CutoffPeriodic -- the cutoff test AND every displacement inside a
+ * variable take the minimum image, each on its own (needs a context with a box; the live box of amm_set_box is read at every
+ * evaluation).  central = 0: SinglePermutation -- a set counts when all three distances are inside the cutoff and is evaluated once;
+ * central != 0: UniqueCentralParticle -- a set counts for the centre c when the two distances from c are inside the cutoff (the
+ * distance between the satellites is not tested) and is evaluated once for every such centre, which plays p1.
+ * code / consts / globals: the program of atomsmm_amd.expr.compile_many_particle -- the words of amm_term_expr_create with variable k
+ * (opcode 53) = entry k of the variable table and parameter k (54) = per-particle parameter k % n_params of the particle in role
+ * k / n_params.  var_kinds: n_vars <= AMM_COMPOUND_MAX_VARS of AMM_CVAR_*; var_slots: n_vars x 4 slots 0 .. 2 = p1 p2 p3, read up
+ * to the kind's arity.  h_params: n_params x n_particles doubles, PARAMETER-major, n_params <= 2.  h_types: the dense type index of
+ * every particle, 0 .. n_types - 1, n_types <= 16.  h_perm: n_types^3 entries [t1][t2][t3] over the types of the set's tuple -- its
+ * particles in ascending order, or the centre first and the satellites ascending -- each the code of the permutation of the tuple
+ * that is evaluated (0 .. 5: the permutations of (0, 1, 2) in lexicographic order, role r played by element perm[r]; central mode
+ * keeps the centre at p1: 0 or 1) or -1: the set is skipped.  h_excl: n_excl pairs of particles.
+ * Refused, each by name: more than 32768 particles, more than 2048 under NoCutoff, another particle count than the context's, the
+ * parameter, variable and type limits, an index out of range, CutoffPeriodic without a box, a periodic cutoff above half the shortest
+ * box edge (also at an evaluation, after the box has shrunk), more than one rank.  An ordinary member of a group, evaluated through
+ * amm_force_eval and amm_run_ops, legal in a context without a box; every other family's entry points refuse its id naming
+ * AMM_FORCE_MANY_PARTICLE.
+ * Two launches per evaluation, one wavefront per particle each: the neighbour scan (all columns 64 at a time, the survivors
+ * appended in ascending order to the particle's row of a table n x capacity -- with a cutoff the option "many_capacity",
+ * amm_set_option, else n - 1 rounded up to 64) and the evaluation, in which the wavefront of particle i enumerates every set that
+ * contains i, queues the survivors in LDS, runs the interpreter on full queues and adds the force on i alone: every set is
+ * interpreted three times.  A row that needs more than the capacity is clamped and raises a flag that amm_check reports with both
+ * numbers; the energy and forces of that evaluation are unspecified, but no access leaves the table.  No atomics: the same positions
+ * give the same bits, with and without energy. */
+int amm_many_create(amm_ctx *ctx, const int32_t *code, int32_t ncode, const double *consts, int32_t nconst, const double *globals,
+                    int32_t nglobal, const int32_t *var_kinds, const int32_t *var_slots, int32_t n_vars, int32_t n_particles,
+                    const double *h_params, int32_t n_params, const int32_t *h_types, int32_t n_types, const int32_t *h_perm,
+                    const int32_t *h_excl, int32_t n_excl, double rc, int32_t periodic, int32_t central, int32_t *force_id);
+/* setParticleParameters / setTypeFilter + updateParametersInContext: all per-particle values, the types and the permutation table
+ * again, laid out as at creation (the same particle count; n_types may differ). */
+int amm_many_set_params(amm_ctx *ctx, int32_t force_id, const double *h_params, int32_t n_particles, int32_t n_params,
+                        const int32_t *h_types, int32_t n_types, const int32_t *h_perm);
+/* Context.setParameter(name, value) for a global parameter of such a force: all of the program's globals, in its order. */
+int amm_many_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal);
+/* Waits for the stream.  out[0]: particles; out[1]: evaluations of the text whose energy the last evaluation summed (SinglePermutation:
+ * the sets; UniqueCentralParticle: one per set and centre; 0 before the first); out[2]: kernel launches so far; out[3]: the fullest
+ * neighbour row of the last evaluation, unclamped; out[4]: the capacity of a row. */
+int amm_many_stats(amm_ctx *ctx, int32_t force_id, int64_t *out);
+/* Free such a force; the id is retired and leaves every group definition. */
+int amm_many_release(amm_ctx *ctx, int32_t force_id);
+
 /* Reciprocal space of a NonbondedForce with nonbondedMethod PME / Ewald, as RESPASystem and FarNonbondedForce
  * keep it in group 2 with the source force's Ewald tolerance / PME parameters (systems.py:74-75,
  * forces.py:185-188; setReciprocalSpaceForceGroup: utils.py:147-152).  Smooth PME, B-spline order 5, grid
@@ -623,8 +668,9 @@ int amm_set_outer_skin(amm_ctx *ctx, double skin_out);
  * generalized-Born passes: 0 = chosen from n as for free-space pair forces; 1, 2, 4 .. 64), "cgb_lanes_per_row" (the same for the
  * passes of a custom generalized-Born force), "hbond_chunks" (column chunks a row of a hydrogen-bond force created from now on is
  * split into, one wavefront each: 0 = chosen from the number of rows; 1 .. 512), "hbond_compact" (0: such a force runs the
- * interpreter after every batch of 64 columns that has a survivor instead of on full queues -- for measurements; default 1).
- * Unknown names are an error. */
+ * interpreter after every batch of 64 columns that has a survivor instead of on full queues -- for measurements; default 1),
+ * "many_capacity" (neighbours a row of a many-particle force with a cutoff created from now on can hold: a multiple of 64 from 64
+ * to 4096; default 256).  Unknown names are an error. */
 int amm_set_option(amm_ctx *ctx, const char *name, double value);
 /* What amm_run_ops fused so far (statistics for tests and bench.py): out[0] = pair-kernel launches that carried the inner RESPA loop
  * of their molecules as an epilogue (the reference runs it as CustomIntegrator steps, propagators.py:933-973), out[1] = pair
