@@ -1410,6 +1410,17 @@ int amm_pair_get_stats(amm_ctx *ctx, int32_t force_id, amm_pair_stats *out) {
     return 0;
 }
 
+int amm_pair_guest_factor(amm_ctx *ctx, int32_t force_id, double out[2]) {
+    PairForce *pf = amm_force_get<PairForce>(ctx, force_id);
+    if (!pf || !out) {
+        amm_set_error("amm_pair_guest_factor: null argument or not a pair force");
+        return 1;
+    }
+    out[0] = pf->last_gfac;
+    out[1] = pf->last_gunit ? 1.0 : 0.0;
+    return 0;
+}
+
 int amm_pair_row_padding(amm_ctx *ctx, int32_t force_id, int64_t out[2]) {
     PairForce *pf = amm_force_get<PairForce>(ctx, force_id);
     if (!pf || !out) {

@@ -99,6 +99,8 @@ struct PairForce {
     bool all_q_zero = false;       // every charge is zero (set_params): the per-atom-row kernel has an instantiation without the Coulomb table
     int last_chargeless = 0;       // ... and the last force-only evaluation ran it (statistics)
     int last_fused = 0;            // 1: the last force-only evaluation rode on the list owner's launch (molecule rows, fused pass)
+    double last_gfac = 0;          // ... then: this force's factor relative to the host, (Kc sign)_guest / (Kc sign)_host, and
+    int last_gunit = 0;            // whether the launch took the kernel that leaves the product by it out (gfac == 1.0; statistics)
     int last_kind = 0;             // list walked by the last evaluation: 0 per-atom rows, 1 molecule rows, 2 hybrid (statistics)
     PairConsts pc;
     int n = 0;

@@ -1185,7 +1185,7 @@ __device__ __forceinline__ T cpair_arg_copy(const __attribute__((address_space(4
 #define CWALK_T_PARAM
 #define CWALK_T_ARG
 #endif
-template <int FAM, int CMODE, int GFAM, int IMG, int SMASK>
+template <int FAM, int CMODE, int GFAM, int IMG, int SMASK, bool GUNIT = false>
 __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts &c, const PairConsts &g, const char *tabh, const char *tabg,
                                            const double *erfcx, const double4 (&pi)[3], const double2 *li, int i_sites, const int (&so)[3],
                                            const int (&sog)[3], const int *row, int nfront, int nn, int sub, int lpa_s,
@@ -1205,6 +1205,18 @@ __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts 
     // (zero slot: LDS byte addresses of the two Coulomb tables and of the slot -- a choice of the per-lane select: in a VGPR)
     const unsigned tabh_a = ZSLOT ? amm_lds_addr(tabh) : 0u, tabg_a = (ZSLOT && DUAL) ? amm_lds_addr(tabg) : 0u;
     const unsigned zaddr = cpair_in_vgpr<VRES && ZSLOT>(tabh_a + (unsigned)zslot);
+    // (zero slot: a table's address less 48 x the base interval of zone A / of zone B -- what the look-up's zone select delivers in
+    // place of the base, pair_tab.h: amm_tab_fetch_pass; choices of a per-lane select like the bases they replace: in VGPRs.  Where
+    // there is no room for that the finished offset is pinned in a scalar register: left to itself the compiler takes the offset
+    // apart again and subtracts per pair)
+    auto zone_off = [](unsigned tab_a, int base) {
+        unsigned off = amm_tab_zone_offset(tab_a, base);
+        if (VRES) asm("" : "+v"(off));
+        else asm("" : "+s"(off));
+        return off;
+    };
+    const unsigned hoff_a = ZSLOT ? zone_off(tabh_a, c.tab.baseA) : 0u, hoff_b = ZSLOT ? zone_off(tabh_a, c.tab.rawB_minus_nA) : 0u;
+    const unsigned goff_a = (ZSLOT && DUAL) ? zone_off(tabg_a, g.tab.baseA) : 0u, goff_b = (ZSLOT && DUAL) ? zone_off(tabg_a, g.tab.rawB_minus_nA) : 0u;
     // closer pairs are left out of the main path and redone analytically below (never in a liquid)
     const double r2low = DUAL ? fmax(c.tab.r2min, g.tab.r2min) : c.tab.r2min;
     const double r2low_ss = DUAL ? fmax(c.tab.ss_r2min, g.tab.ss_r2min) : c.tab.ss_r2min;
@@ -1255,7 +1267,7 @@ __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts 
             unsigned long long lowm = 0ull;
             bool any_low = false;
             bool lowp[3];
-            unsigned tadr[3];          // (zero slot) the table the host's pair (a, b) reads: LDS address of its interval 0
+            unsigned sstep[3];         // (zero slot) the way from the Coulomb table to the table the host's pair (a, b) reads: 0, or to the site-site table
             // does the host's pair (a, b) count?  Also files whether it lies below a table (lowp, lowm / any_low: the redo further down)
             auto host_pass = [&](int a) {
                 const bool low_c = r2[a] < r2low;
@@ -1264,7 +1276,7 @@ __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts 
                 // (a site pair below its own table; no branch here: a branch in this loop costs more than it skips -- lane conditions
                 // are combined with & and |, which stay lane masks on the scalar unit: && and || become branches around the second test)
                 if ((SMASK >> a) & 1) {
-                    const bool site_pair = ZSLOT ? tadr[a] != tabh_a : (so[a] & mb) != 0, low_ss = r2[a] < r2low_ss;
+                    const bool site_pair = ZSLOT ? sstep[a] != 0u : (so[a] & mb) != 0, low_ss = r2[a] < r2low_ss;
                     low = low | (site_pair & low_ss);
                     if (LOW_MASKS) lowm |= __builtin_amdgcn_ballot_w64(site_pair) & __builtin_amdgcn_ballot_w64(low_ss);
                 }
@@ -1286,9 +1298,9 @@ __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts 
                     }
                     r2[a] = dx[a] * dx[a] + dy[a] * dy[a] + dz[a] * dz[a];
                     if (ZSLOT) {
-                        // (site bit of the partner x the row atom's way to its site-site table: one multiply-add)
-                        tadr[a] = ((SMASK >> a) & 1) ? __umul24((bits >> b) & 1u, (unsigned)so[a]) + tabh_a : tabh_a;
-                        th[a] = amm_tab_fetch_pass(tadr[a], c.tab, r2[a], host_pass(a), zaddr);
+                        // (site bit of the partner x the row atom's way to its site-site table)
+                        sstep[a] = ((SMASK >> a) & 1) ? __umul24((bits >> b) & 1u, (unsigned)so[a]) : 0u;
+                        th[a] = amm_tab_fetch_pass(hoff_a, hoff_b, sstep[a], c.tab, r2[a], host_pass(a), zaddr);
                     } else {
                         th[a] = amm_tab_fetch(tabh, c.tab, r2[a], ((SMASK >> a) & 1) ? (unsigned)(so[a] & mb) : 0u);
                     }
@@ -1329,7 +1341,7 @@ __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts 
 #pragma unroll
                     for (int a = 0; a < 3; ++a) {
                         if (ZSLOT) {
-                            tg[a] = amm_tab_fetch_pass(((SMASK >> a) & 1) ? __umul24((bits >> b) & 1u, (unsigned)sog[a]) + tabg_a : tabg_a, g.tab, r2[a],
+                            tg[a] = amm_tab_fetch_pass(goff_a, goff_b, ((SMASK >> a) & 1) ? __umul24((bits >> b) & 1u, (unsigned)sog[a]) : 0u, g.tab, r2[a],
                                                        front & (r2[a] < g.rc2) & !lowp[a], zaddr);
                         } else {
                             tg[a] = amm_tab_fetch(tabg, g.tab, r2[a], ((SMASK >> a) & 1) ? (unsigned)(sog[a] & mb) : 0u);
@@ -1341,7 +1353,8 @@ __device__ __forceinline__ void cwalk_rows(const CPairArgs &A, const PairConsts 
                         // (gl: the analytic Lennard-Jones part, which only the kernels without site-site tables have.  With the
                         // tables the sum was `+ 0.0`, which turns a product of -0 into +0 and nothing else -- and the product enters
                         // fg, which starts at +0 and so is never -0, through an FMA: the same bits without the add)
-                        double gr = ((pi[a].w * qb) * A.gfac) * amm_tab_horner(tg[a]);
+                        // (GUNIT: the launcher saw gfac == 1.0 exactly -- the product by it changes no bit and is left out)
+                        double gr = (GUNIT ? pi[a].w * qb : (pi[a].w * qb) * A.gfac) * amm_tab_horner(tg[a]);
                         if (!SS) gr = amm_sum_unfused(gr, gl[a]);
                         const double gh = ZSLOT ? gr : ((front & (r2[a] < g.rc2) & !lowp[a]) ? gr : 0.0);
                         fg[3 * a] += gh * dx[a];
@@ -1759,7 +1772,7 @@ __device__ __forceinline__ int cscan_counts(int ncell, const int *count, int *st
 #endif
 // LDS: [host Coulomb table][guest Coulomb table][host site-site table][guest site-site table][erfcx table][parameter strips];
 // kernels with site-site tables need neither strips nor -- in LDS -- the erfcx table (their rare analytic path reads it from HBM)
-template <int FAM, int CMODE, int GFAM, int BS, int SMASK, bool EPI = false>
+template <int FAM, int CMODE, int GFAM, int BS, int SMASK, bool EPI = false, bool GUNIT = false>
 __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(AMM_CTAB_WAVES_PER_EU)))
 k_cpair(CPairArgs A_, PairConsts c_, PairConsts g_, CEpiArgs E) {
     // (A_, c_, g_: read in place through cpair_args_here(), piece by piece where they are used -- see CPairKArgs)
@@ -1887,15 +1900,16 @@ k_cpair(CPairArgs A_, PairConsts c_, PairConsts g_, CEpiArgs E) {
         c1.sign = 1.0;          // the sign travels with the row atoms' charges and epsilons (every family is linear in both)
         g1.sign = 1.0;
         // the look-up's per-lane choices between zone A and zone B of a table (amm_tab_fetch: shift, base, half width)
-        constexpr bool VRES = cpair_vgpr_room(FAM, CMODE, GFAM, SMASK);
+        // (zero slot: the walk keeps the two bases folded into the tables' addresses instead -- cwalk_rows)
+        constexpr bool VRES = cpair_vgpr_room(FAM, CMODE, GFAM, SMASK), VBASE = VRES && !cpair_zero_slot(FAM, CMODE, GFAM, SMASK);
         c1.tab.shiftB = cpair_in_vgpr<VRES>(c1.tab.shiftB);
-        c1.tab.rawB_minus_nA = cpair_in_vgpr<VRES>(c1.tab.rawB_minus_nA);
-        c1.tab.baseA = cpair_in_vgpr<VRES>(c1.tab.baseA);
+        c1.tab.rawB_minus_nA = cpair_in_vgpr<VBASE>(c1.tab.rawB_minus_nA);
+        c1.tab.baseA = cpair_in_vgpr<VBASE>(c1.tab.baseA);
         c1.tab.halfB = cpair_in_vgpr<VRES>(c1.tab.halfB);
         if (DUAL) {
             g1.tab.shiftB = cpair_in_vgpr<VRES>(g1.tab.shiftB);
-            g1.tab.rawB_minus_nA = cpair_in_vgpr<VRES>(g1.tab.rawB_minus_nA);
-            g1.tab.baseA = cpair_in_vgpr<VRES>(g1.tab.baseA);
+            g1.tab.rawB_minus_nA = cpair_in_vgpr<VBASE>(g1.tab.rawB_minus_nA);
+            g1.tab.baseA = cpair_in_vgpr<VBASE>(g1.tab.baseA);
             g1.tab.halfB = cpair_in_vgpr<VRES>(g1.tab.halfB);
         }
         // (the task's own: the prologue of the next one overwrites them behind the walk)
@@ -1933,9 +1947,9 @@ k_cpair(CPairArgs A_, PairConsts c_, PairConsts g_, CEpiArgs E) {
         double f[9], fg[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) f[k] = fg[k] = 0.0;
-        if (A.per_pair_image) cwalk_rows<FAM, CMODE, GFAM, 2, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, row, nfront, nn, sub, lpa, cs, used, f, fg CWALK_T_ARG);
-        else if (interior) cwalk_rows<FAM, CMODE, GFAM, 0, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, row, nfront, nn, sub, lpa, cs, used, f, fg CWALK_T_ARG);
-        else cwalk_rows<FAM, CMODE, GFAM, 1, SMASK>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, row, nfront, nn, sub, lpa, cs, used, f, fg CWALK_T_ARG);
+        if (A.per_pair_image) cwalk_rows<FAM, CMODE, GFAM, 2, SMASK, GUNIT>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, row, nfront, nn, sub, lpa, cs, used, f, fg CWALK_T_ARG);
+        else if (interior) cwalk_rows<FAM, CMODE, GFAM, 0, SMASK, GUNIT>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, row, nfront, nn, sub, lpa, cs, used, f, fg CWALK_T_ARG);
+        else cwalk_rows<FAM, CMODE, GFAM, 1, SMASK, GUNIT>(A, c1, g1, tabh, tabg, erfcx, pi, li, i_sites, so, sog, row, nfront, nn, sub, lpa, cs, used, f, fg CWALK_T_ARG);
         task += nwx;
         has = seek();
         if (AHEAD && has) pre_rows();
@@ -2108,19 +2122,29 @@ struct CLaunchCfg {
 };
 static int g_num_cu_c[64] = {0};
 
+static thread_local int g_cpair_unit_gfac = 0;          // the last launch_cpair_t took a GUNIT kernel (statistics: PairForce::last_gunit)
 // 2 wavefronts per SIMD (187 registers one force, 240 fused): one block of 512 per CU; 8 rows per wavefront then deal 2 tasks to
 // every wavefront at 98 304 atoms (768 threads: 1.33 -- a third of the chip idles in the tail)
-template <int FAM, int CMODE, int GFAM, int SMASK, bool EPI = false>
+// GUNIT: the guest's factor relative to the host (CPairArgs::gfac) is exactly 1.0 -- both forces with the same Coulomb constant and
+// sign, what RESPASystem builds -- and the kernel leaves the product by it out (the fused zero-slot instantiations only; any other
+// gfac takes the kernel that multiplies)
+template <int FAM, int CMODE, int GFAM, int SMASK, bool EPI = false, bool GUNIT = false>
 static int launch_cpair_t(amm_ctx *ctx, const CPairArgs &A, const PairConsts &c, const PairConsts &g, const CEpiArgs &E = CEpiArgs()) {
     constexpr bool DUAL = GFAM >= 0;
     constexpr int BS = DUAL ? AMM_CBS_SINGLE : AMM_CBS_NEAR;
     constexpr bool SS = SMASK != 0;
+#ifndef AMM_EXP_NO_GUNIT          // measurement builds
+    if constexpr (!GUNIT && DUAL && cpair_zero_slot(FAM, CMODE, GFAM, SMASK)) {
+        if (A.gfac == 1.0) return launch_cpair_t<FAM, CMODE, GFAM, SMASK, EPI, true>(ctx, A, c, g, E);
+    }
+#endif
+    g_cpair_unit_gfac = GUNIT ? 1 : 0;
     static CLaunchCfg cfg[64];
     CLaunchCfg &k = cfg[ctx->device & 63];
     int lds = A.host_bytes + (DUAL ? A.guest_bytes : 0);
     if (SS) lds += A.host_ss_bytes + (DUAL ? A.guest_ss_bytes : 0) + AMM_CPAIR_ZERO_SLOT;
     else lds += AMM_ERFCX_NI * AMM_ERFCX_NC * 8 + (BS / 64) * 192 * 16;
-    auto kern = k_cpair<FAM, CMODE, GFAM, BS, SMASK, EPI>;
+    auto kern = k_cpair<FAM, CMODE, GFAM, BS, SMASK, EPI, GUNIT>;
     if (lds > k.lds_set) {
         AMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         k.lds_set = lds;
@@ -2789,8 +2813,13 @@ int amm_cluster_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, doub
             const int r = launch_cdual(ctx, D, pf->pc, gpc, Ep, &epi_launched);
             if (r > 0) return 1;
             fused = r == 0;
-            if (fused) guest->last_fused = 1;
-            else epi_launched = false;
+            if (fused) {
+                guest->last_fused = 1;
+                guest->last_gfac = D.gfac;
+                guest->last_gunit = g_cpair_unit_gfac;
+            } else {
+                epi_launched = false;
+            }
         }
         if (!fused) rc_ = launch_cpair(ctx, A, pf->pc, guest ? nullptr : Ep, &epi_launched);
         if (timed) AMM_HIP(hipEventRecord(e1, st));          // (the guest's launch below is timed under the guest's own id)

@@ -302,6 +302,23 @@ static inline int amm_tab_index_unclamped(const PairTab &T, double r2) {
     const unsigned raw = hi >> (above ? (unsigned)T.shiftB : (unsigned)AMM_TAB_SHIFT);
     return (int)(raw - (unsigned)(above ? T.rawB_minus_nA : T.baseA));
 }
+// The same look-up as the zero-slot kernels form its byte address (amm_tab_fetch_pass): the zone's base is folded into a per-zone
+// offset from the table's address, address = raw x 48 + offset(zone), all in unsigned 32-bit arithmetic.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline unsigned amm_tab_zone_offset(unsigned tab_addr, int base) {
+    return tab_addr - (unsigned)AMM_TAB_STRIDE * (unsigned)base;
+}
+static inline unsigned amm_tab_address_unclamped(const PairTab &T, double r2, unsigned tab_addr) {
+    const double w = r2 * T.scale;
+    unsigned long long bits;
+    memcpy(&bits, &w, 8);
+    const unsigned hi = (unsigned)(bits >> 32);
+    const bool above = hi >= 0x3FF00000u;
+    const unsigned raw = hi >> (above ? (unsigned)T.shiftB : (unsigned)AMM_TAB_SHIFT);
+    return (raw & 0xffffffu) * (unsigned)AMM_TAB_STRIDE + amm_tab_zone_offset(tab_addr, above ? T.rawB_minus_nA : T.baseA);
+}
 // the cutoff the molecule-row kernels test a pair of this force against (r2 < rc2; a guarded force: its guard radius, cluster.hip)
 static inline double amm_tab_pass_rc2(const PairConsts &pc) {
     return ((pc.flags & AMM_GUARD_RC0) && pc.rc0 > 0.0) ? std::min(pc.rc2, pc.rc0 * pc.rc0) : pc.rc2;
@@ -323,7 +340,11 @@ static inline TabIndexCheck amm_tab_indices_in_range(const PairTab &T, double rc
         if (!(r2 >= floor_r2 && r2 <= top)) return;
         const int idx = amm_tab_index_unclamped(T, r2);
         ++R.points;
-        if (idx < first || idx >= T.nint) ++R.bad;
+        // (the address with the zone's base folded into an offset is the interval's, wherever the table lies in LDS)
+        bool same = true;
+        for (unsigned tab : {0u, 0x10u, 0x25ff0u})
+            same = same && amm_tab_address_unclamped(T, r2, tab) == tab + (unsigned)AMM_TAB_STRIDE * (unsigned)idx;
+        if (idx < first || idx >= T.nint || !same) ++R.bad;
         R.idx_min = std::min(R.idx_min, idx);
         R.idx_max = std::max(R.idx_max, idx);
     };
@@ -446,22 +467,27 @@ __device__ __forceinline__ TabLookup amm_tab_fetch(const char *lds_tab, const Pa
 // address instead of two on the halves of a double.  No clamp of the interval either: `pass` must imply r2min <= r2 < rc2 (and
 // ss_r2min <= r2 where the pair reads a site-site table), which puts the interval inside the table (amm_tab_index_unclamped /
 // amm_tab_indices_in_range above: tested for every table when it is built); the index of any other lane is never used.
-// Addresses are LDS byte addresses (amm_lds_addr): `tab_addr` that of the table's interval 0 -- Coulomb table, or where the
-// site-site table's would lie -- so that interval and table make ONE multiply-add and the select acts on the final address.
+// Addresses are LDS byte addresses (amm_lds_addr), so that interval and table make ONE multiply-add and the select acts on the
+// final address.
 __device__ __forceinline__ unsigned amm_lds_addr(const char *p) {
     return (unsigned)(size_t)(const __attribute__((address_space(3))) char *)p;
 }
-__device__ __forceinline__ TabLookup amm_tab_fetch_pass(unsigned tab_addr, const PairTab &T, double r2, bool pass, unsigned zero_addr) {
+// The zone's base interval is not subtracted from the raw interval per pair: it is folded into the address the zone select delivers,
+//     address = raw x 48 + (above ? off_b : off_a) + step,     off_a / off_b = amm_tab_zone_offset(table address, baseA / rawB_minus_nA)
+// -- per-force constants the caller keeps where it kept the two bases -- and `step` the way from the Coulomb table to the site-site
+// table for a site pair, 0 otherwise.  Modulo 2^32 that is (raw - base) x 48 + table + step, the address the subtraction gave (raw
+// < 2^24: shifts are 7 or more); amm_tab_indices_in_range forms both.
+__device__ __forceinline__ TabLookup amm_tab_fetch_pass(unsigned off_a, unsigned off_b, unsigned step, const PairTab &T, double r2, bool pass,
+                                                        unsigned zero_addr) {
     const double w = r2 * T.scale;
     const unsigned hi = (unsigned)__double2hiint(w);
     const bool above = hi >= 0x3FF00000u;
     const unsigned sh = above ? (unsigned)T.shiftB : (unsigned)AMM_TAB_SHIFT;
     const unsigned raw = hi >> sh;
-    const unsigned idx = raw - (unsigned)(above ? T.rawB_minus_nA : T.baseA);
     const double centre = __hiloint2double((int)((raw << sh) | (unsigned)(above ? T.halfB : (1 << (AMM_TAB_SHIFT - 1)))), 0);
     TabLookup L;
     L.t = w - centre;
-    const unsigned at = __umul24(idx, AMM_TAB_STRIDE) + tab_addr;
+    const unsigned at = __umul24(raw, AMM_TAB_STRIDE) + (above ? off_b : off_a) + step;
     const double2 *cf = (const double2 *)reinterpret_cast<const __attribute__((address_space(3))) double2 *>(pass ? at : zero_addr);
     L.c01 = cf[0];
     L.c23 = cf[1];

@@ -853,6 +853,10 @@ int amm_pair_count_within(amm_ctx *ctx, int32_t force_id, const double *d_pos, d
    64 / lanes_per_row rows until the longest is done), out[1] = row entries; their ratio is the padding of the walk.  Zeros for
    per-atom rows.  Synchronises. */
 int amm_pair_row_padding(amm_ctx *ctx, int32_t force_id, int64_t out[2]);
+/* A force whose last force-only evaluation rode on its list owner's fused pass (amm_pair_stats::rode_along): out[0] = its factor
+   relative to the host, (Kc sign)_guest / (Kc sign)_host, out[1] = 1.0 if the launch took the kernel that leaves the product by a
+   factor of exactly 1.0 out, else 0.0.  Zeros for a force that never rode along. */
+int amm_pair_guest_factor(amm_ctx *ctx, int32_t force_id, double out[2]);
 /* Revision tag of the pair-traversal kernels: measurements kept under profiles/ carry it, and bench.py drops a stored
  * figure (the PMC traffic) once the kernels it was measured on have changed. */
 const char *amm_kernel_revision(void);

@@ -31,19 +31,23 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MIN_VALU = 250
 COLD_VALU = 100
 VARIANTS = ('interior', 'image/molecule', 'image/pair')
-# <FAM, CMODE, GFAM, BS, SMASK, EPI> of the launches of bench.py (C3 headline, its PME variant, the C5 leg): FAM 2 = near force with
-# force switch, 3 = damped, 4 = NonbondedForce (CMODE 1: Ewald direct space); GFAM 2: the near force rides along; -1: one force
+# <FAM, CMODE, GFAM, BS, SMASK, EPI, GUNIT> of the launches of bench.py (C3 headline, its PME variant, the C5 leg): FAM 2 = near force
+# with force switch, 3 = damped, 4 = NonbondedForce (CMODE 1: Ewald direct space); GFAM 2: the near force rides along; -1: one force;
+# GUNIT: the guest's factor relative to the host is exactly 1.0 and the product by it is left out (what RESPASystem builds)
 BENCH = [
-    ((3, 1, 2, 512, 1, True), 'fused pass, damped host + near guest, epilogue (C3 step boundary)'),
-    ((2, 0, -1, 512, 1, True), 'near pass, epilogue (C3 middle evaluation)'),
-    ((3, 1, 2, 512, 1, False), 'fused pass without epilogue (C5 molecule rows)'),
-    ((2, 0, -1, 512, 1, False), 'near pass without epilogue (C5 molecule rows)'),
-    ((4, 1, 2, 512, 1, False), 'fused pass, Ewald direct host + near guest (PME variant)'),
+    ((3, 1, 2, 512, 1, True, True), 'fused pass, damped host + near guest, epilogue (C3 step boundary)'),
+    ((2, 0, -1, 512, 1, True, False), 'near pass, epilogue (C3 middle evaluation)'),
+    ((3, 1, 2, 512, 1, False, True), 'fused pass without epilogue (C5 molecule rows)'),
+    ((2, 0, -1, 512, 1, False, False), 'near pass without epilogue (C5 molecule rows)'),
+    ((4, 1, 2, 512, 1, False, False), 'fused pass, Ewald direct host + near guest (PME variant)'),
+    ((3, 1, 2, 512, 1, True, False), 'fused pass with epilogue for a guest factor other than 1.0 (not launched by the bench)'),
+    ((3, 1, 2, 512, 1, False, False), 'fused pass without epilogue for a guest factor other than 1.0 (not launched by the bench)'),
 ]
 
 
 def demangle_args(sym):
-    """_Z7k_cpairILi3ELi1ELi2ELi512ELi1ELb1EE... -> (3, 1, 2, 512, 1, True), or None."""
+    """_Z7k_cpairILi3ELi1ELi2ELi512ELi1ELb1ELb0EE... -> (3, 1, 2, 512, 1, True, False), or None (an assembly file of a build from
+    before the GUNIT flag has six arguments: the seventh is taken as False)."""
     m = re.match(r'_Z7k_cpairI((?:L[ib]n?\d+E)+)E', sym)
     if not m:
         return None
@@ -51,6 +55,8 @@ def demangle_args(sym):
     for kind, neg, val in re.findall(r'L([ib])(n?)(\d+)E', m.group(1)):
         v = -int(val) if neg else int(val)
         out.append(bool(v) if kind == 'b' else v)
+    if len(out) == 6:
+        out.append(False)
     return tuple(out)
 
 
@@ -185,12 +191,12 @@ def report(lines, label, want_all):
     by_args = {demangle_args(s): s for s in ks}
     print('== %s: %d k_cpair instantiations' % (label, len(ks)))
     rows = BENCH if not want_all else [(a, '') for a in sorted(by_args, key=str)]
-    print('%-34s %5s %5s %8s %8s   %s' % ('k_cpair<FAM,CMODE,GFAM,BS,SMASK,EPI>', 'VGPR', 'SGPR', 'scratch', 'kernarg',
+    print('%-36s %5s %5s %8s %8s   %s' % ('k_cpair<FAM,CMODE,GFAM,BS,SMASK,EPI,GUNIT>', 'VGPR', 'SGPR', 'scratch', 'kernarg',
                                            'per trip: VALU / lane moves (+ cold: analytic redo)'))
     for args, what in rows:
         sym = by_args.get(args)
         if sym is None:
-            print('%-34s not in this build' % (args,))
+            print('%-36s not in this build' % (args,))
             continue
         m = md.get(sym, dict(vgpr=-1, sgpr=-1, scratch=-1, kernarg=-1))
         trips = trip_loops(lines, *ks[sym])
@@ -199,9 +205,9 @@ def report(lines, label, want_all):
         for k, (valu, lane, cvalu, clane) in enumerate(trips):
             tag = VARIANTS[k] if len(trips) == 3 else 'loop %d' % k
             cells.append('%s %d / %d (+ %d / %d)' % (tag, valu, lane, cvalu, clane))
-        print('%-34s %5d %5d %8d %8d   %s' % (name, m['vgpr'], m['sgpr'], m['scratch'], m['kernarg'], ' | '.join(cells)))
+        print('%-36s %5d %5d %8d %8d   %s' % (name, m['vgpr'], m['sgpr'], m['scratch'], m['kernarg'], ' | '.join(cells)))
         if what:
-            print('%-34s %s' % ('', what))
+            print('%-36s %s' % ('', what))
     worst = max((md[s]['vgpr'] for s in ks if s in md), default=-1)
     print('largest VGPR count of all instantiations: %d; with scratch: %d of %d; total scratch bytes %d' % (
         worst, sum(1 for s in ks if md.get(s, {}).get('scratch', 0) > 0), len(ks), sum(md.get(s, {}).get('scratch', 0) for s in ks)))
