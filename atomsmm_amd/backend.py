@@ -340,6 +340,45 @@ def _hi(a):
     return a, a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+def _globals(globals_):
+    """(pointer, count) of the values of a program's globals (a pointer keeps its array alive)."""
+    g_, gp = _hd(globals_ if len(globals_) else [0.0])
+    return gp, len(globals_)
+
+
+def _program(code, consts, globals_):
+    """The six arguments every text-driven entry point takes for its program: code, constants, globals, each with its count."""
+    c_, cp = _hi(np.asarray(code, dtype=np.int32).reshape(-1))
+    k_, kp = _hd(consts if len(consts) else [0.0])
+    return (cp, len(c_), kp, len(consts)) + _globals(globals_)
+
+
+def _var_table(var_kinds, var_slots):
+    """(kinds, slots n_vars x 4 padded with 0, n_vars) of a variable table (expr.compile_compound / compile_hbond / compile_many_particle)."""
+    n_vars = len(var_kinds)
+    slots = np.zeros((max(n_vars, 1), 4), dtype=np.int32)
+    for k, row in enumerate(var_slots):
+        slots[k, :len(row)] = row
+    return _hi(var_kinds if n_vars else [0])[1], _hi(slots)[1], n_vars
+
+
+def _param_major(params, n, keep_rows=False):
+    """(pointer, n_params) of a parameter-major array n_params x n.  Anything empty: no parameters -- or, with keep_rows, those
+    of a 2-D array without columns (a force without terms whose text still reads its parameters)."""
+    par = np.asarray(params, dtype=np.float64)
+    if n and par.size:
+        par = par.reshape(-1, n)
+    else:
+        par = np.zeros((par.shape[0] if keep_rows and not n and par.ndim == 2 else 0, n))
+    return _hd(par if par.size else [0.0])[1], len(par)
+
+
+def _pairs(excl_pairs):
+    """(pointer, count) of a list of index pairs (None: none)."""
+    ex = np.zeros((0, 2), np.int32) if excl_pairs is None else np.asarray(excl_pairs, dtype=np.int32).reshape(-1, 2)
+    return _hi(ex if len(ex) else [0])[1], len(ex)
+
+
 def _ptr(t):
     """Device pointer of a torch tensor (fp64, contiguous, on the GPU) or None."""
     if t is None:
@@ -392,6 +431,10 @@ class HipContext:
         except Exception:
             pass
 
+    def _set_globals(self, entry_point, fid, globals_):
+        """New values of the globals of a text-driven force, in the program's order."""
+        _chk(entry_point(self.h, fid, *_globals(globals_)))
+
     # ---- forces
     def pair_create(self, desc, q, sigma, eps, excl_pairs=None, skin=-1.0):
         q_, qp = _hd(q); s_, sp = _hd(sigma); e_, ep = _hd(eps)
@@ -405,21 +448,17 @@ class HipContext:
     def pair_expr_create(self, desc, code, consts, globals_, p0, p1, p2, excl_pairs=None, skin=-1.0):
         """A generic pair force (family PAIR_EXPR): the program of expr.compile_pair, the values of its globals in the program's order
         and the three per-particle parameter slots, stored raw (None: all zero)."""
-        c_, cp = _hi(code)
-        k_, kp = _hd(consts if len(consts) else [0.0])
-        g_, gp = _hd(globals_ if len(globals_) else [0.0])
         slots = [None if p is None else _hd(p) for p in (p0, p1, p2)]
         assert all(s is None or len(s[0]) == self.n for s in slots)
         ex = np.zeros((0, 2), np.int32) if excl_pairs is None else np.asarray(excl_pairs, dtype=np.int32).reshape(-1, 2)
         ex_, exp_ = _hi(ex)
         fid = C.c_int32(-1)
-        _chk(lib().amm_pair_expr_create(self.h, C.byref(desc), cp, len(c_), kp, len(consts), gp, len(globals_),
+        _chk(lib().amm_pair_expr_create(self.h, C.byref(desc), *_program(code, consts, globals_),
                                         *[None if s is None else s[1] for s in slots], exp_, len(ex_), float(skin), C.byref(fid)))
         return fid.value
 
     def pair_expr_set_globals(self, fid, globals_):
-        g_, gp = _hd(globals_ if len(globals_) else [0.0])
-        _chk(lib().amm_pair_expr_set_globals(self.h, fid, gp, len(globals_)))
+        self._set_globals(lib().amm_pair_expr_set_globals, fid, globals_)
 
     def pair_expr_set_tables(self, fid, tables):
         """The tabulated functions of a generic pair force, in the force's function order: one (kind, nx, ny, lo, hi, doubles) each
@@ -504,28 +543,20 @@ class HipContext:
     def term_expr_create(self, kind, code, consts, globals_, idx, params, periodic=False):
         """A generic term force (csrc/term_expr.hip): the program of expr.compile_term, the values of its globals in the program's
         order, `idx` (n_terms x 4, padded with -1) and `params` (n_params x n_terms: parameter-major)."""
-        c_, cp = _hi(code)
-        k_, kp = _hd(consts if len(consts) else [0.0])
-        g_, gp = _hd(globals_ if len(globals_) else [0.0])
         idx_, ixp = _hi(np.asarray(idx, dtype=np.int32).reshape(-1, 4))
-        par = np.asarray(params, dtype=np.float64)
-        par = par.reshape(-1, len(idx_)) if len(idx_) else np.zeros((par.shape[0] if par.ndim == 2 else 0, 0))
-        par_, pp = _hd(par if par.size else [0.0])
+        pp, n_params = _param_major(params, len(idx_), keep_rows=True)
         fid = C.c_int32(-1)
-        _chk(lib().amm_term_expr_create(self.h, int(kind), cp, len(c_), kp, len(consts), gp, len(globals_), ixp, pp, len(idx_), len(par),
+        _chk(lib().amm_term_expr_create(self.h, int(kind), *_program(code, consts, globals_), ixp, pp, len(idx_), n_params,
                                         int(bool(periodic)), C.byref(fid)))
         return fid.value
 
     def term_expr_set_globals(self, fid, globals_):
-        g_, gp = _hd(globals_ if len(globals_) else [0.0])
-        _chk(lib().amm_term_expr_set_globals(self.h, fid, gp, len(globals_)))
+        self._set_globals(lib().amm_term_expr_set_globals, fid, globals_)
 
     def term_expr_set_params(self, fid, params, n_terms):
         """All per-term values again (n_params x n_terms, parameter-major)."""
-        par = np.asarray(params, dtype=np.float64)
-        par = par.reshape(-1, n_terms) if n_terms else np.zeros((par.shape[0] if par.ndim == 2 else 0, 0))
-        par_, pp = _hd(par if par.size else [0.0])
-        _chk(lib().amm_term_expr_set_params(self.h, fid, pp, int(n_terms), len(par)))
+        pp, n_params = _param_major(params, int(n_terms), keep_rows=True)
+        _chk(lib().amm_term_expr_set_params(self.h, fid, pp, int(n_terms), n_params))
 
     def term_expr_release(self, fid):
         """Free a term-expression force (its id is retired)."""
@@ -536,20 +567,9 @@ class HipContext:
         CVAR_*, var_slots[k] up to four positions within the bond --, the values of the program's globals in its order, `idx`
         (n_bonds x n_slots particles, or groups) and `params` (n_params x n_bonds: parameter-major).  groups: None (the slots are
         particles), or (ptr, atoms, weights) -- the members and weights of every group, CSR (a CustomCentroidBondForce)."""
-        c_, cp = _hi(code)
-        k_, kp = _hd(consts if len(consts) else [0.0])
-        g_, gp = _hd(globals_ if len(globals_) else [0.0])
-        n_vars = len(var_kinds)
-        vk_, vkp = _hi(var_kinds if n_vars else [0])
-        slots = np.zeros((max(n_vars, 1), 4), dtype=np.int32)
-        for k, row in enumerate(var_slots):
-            slots[k, :len(row)] = row
-        vs_, vsp = _hi(slots)
         idx_ = np.asarray(idx, dtype=np.int32).reshape(-1, int(n_slots))
         ix_, ixp = _hi(idx_ if idx_.size else [0])
-        par = np.asarray(params, dtype=np.float64)
-        par = par.reshape(-1, len(idx_)) if len(idx_) else np.zeros((par.shape[0] if par.ndim == 2 else 0, 0))
-        par_, pp = _hd(par if par.size else [0.0])
+        pp, n_params = _param_major(params, len(idx_), keep_rows=True)
         if groups is None:
             n_groups, gpp, gap, gwp = 0, None, None, None
         else:
@@ -558,20 +578,17 @@ class HipContext:
             w_, gwp = _hd(groups[2] if len(groups[2]) else [0.0])
             n_groups = len(groups[0]) - 1
         fid = C.c_int32(-1)
-        _chk(lib().amm_compound_create(self.h, int(n_slots), cp, len(c_), kp, len(consts), gp, len(globals_), vkp, vsp, n_vars, ixp, pp, len(idx_),
-                                       len(par), int(bool(periodic)), gpp, gap, gwp, n_groups, C.byref(fid)))
+        _chk(lib().amm_compound_create(self.h, int(n_slots), *_program(code, consts, globals_), *_var_table(var_kinds, var_slots), ixp, pp,
+                                       len(idx_), n_params, int(bool(periodic)), gpp, gap, gwp, n_groups, C.byref(fid)))
         return fid.value
 
     def compound_set_globals(self, fid, globals_):
-        g_, gp = _hd(globals_ if len(globals_) else [0.0])
-        _chk(lib().amm_compound_set_globals(self.h, fid, gp, len(globals_)))
+        self._set_globals(lib().amm_compound_set_globals, fid, globals_)
 
     def compound_set_params(self, fid, params, n_bonds):
         """All per-bond values again (n_params x n_bonds, parameter-major)."""
-        par = np.asarray(params, dtype=np.float64)
-        par = par.reshape(-1, n_bonds) if n_bonds else np.zeros((par.shape[0] if par.ndim == 2 else 0, 0))
-        par_, pp = _hd(par if par.size else [0.0])
-        _chk(lib().amm_compound_set_params(self.h, fid, pp, int(n_bonds), len(par)))
+        pp, n_params = _param_major(params, int(n_bonds), keep_rows=True)
+        _chk(lib().amm_compound_set_params(self.h, fid, pp, int(n_bonds), n_params))
 
     def compound_set_weights(self, fid, weights):
         """All group weights again, in the order of the groups' members."""
@@ -645,30 +662,24 @@ class HipContext:
         const_ptr = np.concatenate([[0], np.cumsum([len(k) for _, k in programs])]).astype(np.int32)
         code = np.concatenate([np.asarray(c, dtype=np.int32).reshape(-1) for c, _ in programs] + [np.zeros(0, np.int32)])
         consts = np.concatenate([np.asarray(k, dtype=np.float64).reshape(-1) for _, k in programs] + [np.zeros(0)])
-        par = np.asarray(params, dtype=np.float64).reshape(-1, self.n) if np.size(params) else np.zeros((0, self.n))
+        pp, n_params = _param_major(params, self.n)
         t_, tp = _hi(types if types else [0])
         c_, cp = _hi(code if len(code) else [0])
         cp_, cpp = _hi(code_ptr)
         k_, kp = _hd(consts if len(consts) else [0.0])
         kp_, kpp = _hi(const_ptr)
-        g_, gp = _hd(globals_ if len(globals_) else [0.0])
-        p_, pp = _hd(par if par.size else [0.0])
-        ex = np.zeros((0, 2), np.int32) if excl_pairs is None else np.asarray(excl_pairs, dtype=np.int32).reshape(-1, 2)
-        ex_, exp_ = _hi(ex if len(ex) else [0])
         fid = C.c_int32(-1)
-        _chk(lib().amm_custom_gb_create(self.h, len(par), int(n_values), len(types) - int(n_values), tp, cp, cpp, kp, kpp, gp, len(globals_),
-                                        pp, exp_, len(ex), float(rc), C.byref(fid)))
+        _chk(lib().amm_custom_gb_create(self.h, n_params, int(n_values), len(types) - int(n_values), tp, cp, cpp, kp, kpp, *_globals(globals_),
+                                        pp, *_pairs(excl_pairs), float(rc), C.byref(fid)))
         return fid.value
 
     def custom_gb_set_params(self, fid, params):
         """All per-particle values again (n_params x n, parameter-major)."""
-        par = np.asarray(params, dtype=np.float64).reshape(-1, self.n) if np.size(params) else np.zeros((0, self.n))
-        p_, pp = _hd(par if par.size else [0.0])
-        _chk(lib().amm_custom_gb_set_params(self.h, fid, pp, len(par), self.n))
+        pp, n_params = _param_major(params, self.n)
+        _chk(lib().amm_custom_gb_set_params(self.h, fid, pp, n_params, self.n))
 
     def custom_gb_set_globals(self, fid, globals_):
-        g_, gp = _hd(globals_ if len(globals_) else [0.0])
-        _chk(lib().amm_custom_gb_set_globals(self.h, fid, gp, len(globals_)))
+        self._set_globals(lib().amm_custom_gb_set_globals, fid, globals_)
 
     def custom_gb_set_tables(self, fid, tables):
         """The tabulated functions of such a force, in its function order: one (kind, nx, ny, lo, hi, doubles) each, as
@@ -691,41 +702,24 @@ class HipContext:
         CVAR_DISTANCE / CVAR_ANGLE / CVAR_DIHEDRAL, var_slots[k] its slots of the pair (0 .. 2 = d1 d2 d3, 3 .. 5 = a1 a2 a3) --
         donors / acceptors: n x 3 atoms (-1: the slot is not there); donor_params / acceptor_params: n_params x n, parameter-major;
         excl_pairs: (donor, acceptor) indices; rc <= 0: NoCutoff; periodic: CutoffPeriodic."""
-        c_, cp = _hi(np.asarray(code, dtype=np.int32).reshape(-1))
-        k_, kp = _hd(consts if len(consts) else [0.0])
-        g_, gp = _hd(globals_ if len(globals_) else [0.0])
-        n_vars = len(var_kinds)
-        slots = np.zeros((max(n_vars, 1), 4), dtype=np.int32)
-        for k, s in enumerate(var_slots):
-            slots[k, :len(s)] = s
-        vk_, vkp = _hi(var_kinds if n_vars else [0])
-        vs_, vsp = _hi(slots)
         dn = np.asarray(donors, dtype=np.int32).reshape(-1, 3)
         ac = np.asarray(acceptors, dtype=np.int32).reshape(-1, 3)
-        dpar = np.asarray(donor_params, dtype=np.float64).reshape(-1, len(dn)) if np.size(donor_params) else np.zeros((0, len(dn)))
-        apar = np.asarray(acceptor_params, dtype=np.float64).reshape(-1, len(ac)) if np.size(acceptor_params) else np.zeros((0, len(ac)))
-        ex = np.zeros((0, 2), np.int32) if excl_pairs is None else np.asarray(excl_pairs, dtype=np.int32).reshape(-1, 2)
         dn_, dnp = _hi(dn if len(dn) else [0])
         ac_, acp = _hi(ac if len(ac) else [0])
-        dp_, dpp = _hd(dpar if dpar.size else [0.0])
-        ap_, app = _hd(apar if apar.size else [0.0])
-        ex_, exp_ = _hi(ex if len(ex) else [0])
         fid = C.c_int32(-1)
-        _chk(lib().amm_hbond_create(self.h, cp, len(c_), kp, len(consts), gp, len(globals_), vkp, vsp, n_vars, dnp, len(dn), acp, len(ac), dpp,
-                                    len(dpar), app, len(apar), exp_, len(ex), float(rc), 1 if periodic else 0, C.byref(fid)))
+        _chk(lib().amm_hbond_create(self.h, *_program(code, consts, globals_), *_var_table(var_kinds, var_slots), dnp, len(dn), acp, len(ac),
+                                    *_param_major(donor_params, len(dn)), *_param_major(acceptor_params, len(ac)), *_pairs(excl_pairs),
+                                    float(rc), 1 if periodic else 0, C.byref(fid)))
         return fid.value
 
     def hbond_set_params(self, fid, donor_params, n_donors, acceptor_params, n_acceptors):
         """All per-donor and per-acceptor values again (n_params x n each, parameter-major)."""
-        dpar = np.asarray(donor_params, dtype=np.float64).reshape(-1, int(n_donors)) if np.size(donor_params) else np.zeros((0, int(n_donors)))
-        apar = np.asarray(acceptor_params, dtype=np.float64).reshape(-1, int(n_acceptors)) if np.size(acceptor_params) else np.zeros((0, int(n_acceptors)))
-        dp_, dpp = _hd(dpar if dpar.size else [0.0])
-        ap_, app = _hd(apar if apar.size else [0.0])
-        _chk(lib().amm_hbond_set_params(self.h, fid, dpp, int(n_donors), len(dpar), app, int(n_acceptors), len(apar)))
+        dpp, n_dpar = _param_major(donor_params, int(n_donors))
+        app, n_apar = _param_major(acceptor_params, int(n_acceptors))
+        _chk(lib().amm_hbond_set_params(self.h, fid, dpp, int(n_donors), n_dpar, app, int(n_acceptors), n_apar))
 
     def hbond_set_globals(self, fid, globals_):
-        g_, gp = _hd(globals_ if len(globals_) else [0.0])
-        _chk(lib().amm_hbond_set_globals(self.h, fid, gp, len(globals_)))
+        self._set_globals(lib().amm_hbond_set_globals, fid, globals_)
 
     def hbond_stats(self, fid):
         """dict(scanned, survivors, launches, chunks): the ordered pairs one pass scans, those that passed the cutoff and the
@@ -745,39 +739,25 @@ class HipContext:
         parameter-major; types: the dense type index of every particle; perm_table: n_types^3 permutation codes (-1: skip;
         engine.many_particle_table); excl_pairs: pairs of particles; rc <= 0: NoCutoff; periodic: CutoffPeriodic; central:
         UniqueCentralParticle."""
-        c_, cp = _hi(np.asarray(code, dtype=np.int32).reshape(-1))
-        k_, kp = _hd(consts if len(consts) else [0.0])
-        g_, gp = _hd(globals_ if len(globals_) else [0.0])
-        n_vars = len(var_kinds)
-        slots = np.zeros((max(n_vars, 1), 4), dtype=np.int32)
-        for k, s in enumerate(var_slots):
-            slots[k, :len(s)] = s
-        vk_, vkp = _hi(var_kinds if n_vars else [0])
-        vs_, vsp = _hi(slots)
         ty = np.asarray(types, dtype=np.int32).reshape(-1)
-        par = np.asarray(params, dtype=np.float64).reshape(-1, len(ty)) if np.size(params) else np.zeros((0, len(ty)))
-        ex = np.zeros((0, 2), np.int32) if excl_pairs is None else np.asarray(excl_pairs, dtype=np.int32).reshape(-1, 2)
-        p_, pp = _hd(par if par.size else [0.0])
         t_, tp = _hi(ty if len(ty) else [0])
         m_, mp = _hi(np.asarray(perm_table, dtype=np.int32).reshape(-1))
-        ex_, exp_ = _hi(ex if len(ex) else [0])
         fid = C.c_int32(-1)
-        _chk(lib().amm_many_create(self.h, cp, len(c_), kp, len(consts), gp, len(globals_), vkp, vsp, n_vars, len(ty), pp, len(par), tp, int(n_types),
-                                   mp, exp_, len(ex), float(rc), 1 if periodic else 0, 1 if central else 0, C.byref(fid)))
+        _chk(lib().amm_many_create(self.h, *_program(code, consts, globals_), *_var_table(var_kinds, var_slots), len(ty),
+                                   *_param_major(params, len(ty)), tp, int(n_types), mp, *_pairs(excl_pairs), float(rc), 1 if periodic else 0,
+                                   1 if central else 0, C.byref(fid)))
         return fid.value
 
     def many_set_params(self, fid, params, types, n_types, perm_table):
         """All per-particle values (n_params x n, parameter-major), the types and the permutation table again."""
         ty = np.asarray(types, dtype=np.int32).reshape(-1)
-        par = np.asarray(params, dtype=np.float64).reshape(-1, len(ty)) if np.size(params) else np.zeros((0, len(ty)))
-        p_, pp = _hd(par if par.size else [0.0])
+        pp, n_params = _param_major(params, len(ty))
         t_, tp = _hi(ty if len(ty) else [0])
         m_, mp = _hi(np.asarray(perm_table, dtype=np.int32).reshape(-1))
-        _chk(lib().amm_many_set_params(self.h, fid, pp, len(ty), len(par), tp, int(n_types), mp))
+        _chk(lib().amm_many_set_params(self.h, fid, pp, len(ty), n_params, tp, int(n_types), mp))
 
     def many_set_globals(self, fid, globals_):
-        g_, gp = _hd(globals_ if len(globals_) else [0.0])
-        _chk(lib().amm_many_set_globals(self.h, fid, gp, len(globals_)))
+        self._set_globals(lib().amm_many_set_globals, fid, globals_)
 
     def many_stats(self, fid):
         """dict(particles, sets, launches, fullest, capacity): the evaluations of the text whose energy the last evaluation summed
@@ -796,16 +776,12 @@ class HipContext:
         (bond-list sets or term-expression forces, members of no group, the caller's to release), the program of expr.compile_cv --
         its variables are the collective variables, then the n_deriv derivative parameters -- and the values of its globals."""
         i_, ip_ = _hi(inner_ids)
-        c_, cp = _hi(code)
-        k_, kp = _hd(consts if len(consts) else [0.0])
-        g_, gp = _hd(globals_ if len(globals_) else [0.0])
         fid = C.c_int32()
-        _chk(lib().amm_cv_create(self.h, ip_, len(i_), int(n_deriv), cp, len(c_), kp, len(consts), gp, len(globals_), C.byref(fid)))
+        _chk(lib().amm_cv_create(self.h, ip_, len(i_), int(n_deriv), *_program(code, consts, globals_), C.byref(fid)))
         return fid.value
 
     def cv_set_globals(self, fid, globals_):
-        g_, gp = _hd(globals_ if len(globals_) else [0.0])
-        _chk(lib().amm_cv_set_globals(self.h, fid, gp, len(globals_)))
+        self._set_globals(lib().amm_cv_set_globals, fid, globals_)
 
     def cv_set_variables(self, fid, values):
         """Current values of the derivative parameters, in the order of addEnergyParameterDerivative."""
@@ -844,11 +820,8 @@ class HipContext:
         _chk(lib().amm_constraints_set_tolerance(self.h, float(tolerance)))
 
     def expr_define(self, code, consts, globals_):
-        c_, cp = _hi(code)
-        k_, kp = _hd(consts if len(consts) else [0.0])
-        g_, gp = _hd(globals_ if len(globals_) else [0.0])
         eid = C.c_int32(-1)
-        _chk(lib().amm_expr_define(self.h, cp, len(c_), kp, len(consts), gp, len(globals_), C.byref(eid)))
+        _chk(lib().amm_expr_define(self.h, *_program(code, consts, globals_), C.byref(eid)))
         return eid.value
 
     def constraints_create(self, pairs, distances, tolerance=1e-5):
@@ -943,10 +916,7 @@ class HipContext:
 
     def expr_eval(self, code, consts, globals_, seed, counter, dst=None, total=None):
         """Per-DOF postfix program (atomsmm_amd.expr): dst <- values, total <- their sum (device tensors or None)."""
-        c_, cp = _hi(code)
-        k_, kp = _hd(consts if len(consts) else [0.0])
-        g_, gp = _hd(globals_ if len(globals_) else [0.0])
-        _chk(lib().amm_expr_eval(self.h, cp, len(c_), kp, len(consts), gp, len(globals_), int(seed) & (2 ** 64 - 1),
+        _chk(lib().amm_expr_eval(self.h, *_program(code, consts, globals_), int(seed) & (2 ** 64 - 1),
                                  int(counter) & (2 ** 64 - 1), _ptr(dst), _ptr(total)))
 
     def force_eval(self, fid, pos, force, accumulate=False, energy=None):

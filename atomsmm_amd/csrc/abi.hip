@@ -445,15 +445,9 @@ int amm_pair_expr_create(amm_ctx *ctx, const amm_pair_desc *desc, const int32_t 
     d.rc = desc->rc;
     d.rswitch = (desc->flags & AMM_SWITCH) ? desc->rswitch : 0.0;
     PairExpr *px = new PairExpr();
-    std::memset(&px->h, 0, sizeof(px->h));
-    px->h.ncode = ncode;
-    px->h.nconst = nconst;
-    px->h.nglobal = nglobal;
-    std::copy(code, code + ncode, px->h.code);
-    std::copy(consts, consts + nconst, px->h.consts);
-    std::copy(globals, globals + nglobal, px->h.globals);
+    px->prog.fill(code, ncode, consts, nconst, globals, nglobal);
     amm_pair_expr_scan_tables(px);
-    if (amm_pair_expr_upload(ctx, px, false)) {
+    if (px->prog.upload(ctx, false)) {
         amm_pair_expr_free(px);
         return 1;
     }
@@ -472,12 +466,7 @@ int amm_pair_expr_set_globals(amm_ctx *ctx, int32_t force_id, const double *glob
         amm_set_error("amm_pair_expr_set_globals: not a pair-expression force (AMM_PAIR_EXPR)");
         return 1;
     }
-    if (nglobal != pf->expr->h.nglobal || (nglobal > 0 && !globals)) {
-        amm_set_error("amm_pair_expr_set_globals: the program reads " + std::to_string(pf->expr->h.nglobal) + " globals, " + std::to_string(nglobal) + " given");
-        return 1;
-    }
-    std::copy(globals, globals + nglobal, pf->expr->h.globals);
-    return amm_pair_expr_upload(ctx, pf->expr, true);
+    return pf->expr->prog.set_globals(ctx, "amm_pair_expr_set_globals", globals, nglobal);
 }
 
 int amm_pair_expr_set_tables(amm_ctx *ctx, int32_t force_id, int32_t n_tables, const int32_t *kinds, const int32_t *dims, const double *ranges,
@@ -687,7 +676,7 @@ int amm_pair_set_params(amm_ctx *ctx, int32_t force_id, const double *h_q, const
     if (!pf) return 1;
     const int n = pf->n;
     if (pf->expr) {
-        // a pair-expression force: the program reads the three slots as the text's own per-particle parameters -- RAW values (any
+        // a pair-expression force: its program takes the three slots as the text's own per-particle parameters -- RAW values (any
         // sign), a NULL array = all zero.  Every atom counts as a site (no row is cut short), no charge-less or one-class shortcut.
         const std::vector<double> zero(n, 0.0);
         AMM_HIP(hipStreamSynchronize(ctx->stream));

@@ -22,6 +22,13 @@ void amm_set_error(const std::string &msg);
             return 1;                                                                            \
         }                                                                                        \
     } while (0)
+// a device array of its own for `count` host values (one element when there are none: the pointer is never null)
+template <typename T>
+inline int amm_upload(T **dst, const T *src, size_t count) {
+    AMM_HIP(hipMalloc(dst, sizeof(T) * (count ? count : 1)));
+    if (count) AMM_HIP(hipMemcpy(*dst, src, sizeof(T) * count, hipMemcpyHostToDevice));
+    return 0;
+}
 
 // Radial Coulomb table of a pair force (pair_tab.h): abscissa w = r^2 * scale, interval = (hi32(w) >> 13) - base.
 struct PairTab {
@@ -570,7 +577,6 @@ int amm_free_lanes_per_row(int n);
 #define AMM_FREE_MAX_ATOMS 32768   // an evaluation is O(n^2): about 10^9 distance tests at the limit
 // pair_expr.hip: a force of family AMM_PAIR_EXPR on the per-atom rows of pair.hip
 int amm_pair_expr_launch(amm_ctx *ctx, PairForce *pf, const PairArgs &A, dim3 grid, bool en);
-int amm_pair_expr_upload(amm_ctx *ctx, PairExpr *px, bool globals_only);
 void amm_pair_expr_free(PairExpr *px);
 // tabulated functions of such a force: does the program read any (sets PairExpr::uses_tables); check them against the program's
 // table words and copy them to the force's device allocation (amm_pair_expr_set_tables)
@@ -579,7 +585,6 @@ int amm_pair_expr_tables(amm_ctx *ctx, PairExpr *px, int n_tables, const int32_t
                          const int32_t *offsets, const double *data, int n_data);
 // term_expr.hip: a force of type AMM_FORCE_TERM_EXPR
 int amm_term_expr_build(amm_ctx *ctx, TermExprForce *tf, const int32_t *h_idx, const double *h_params);   // device arrays + CSR of a new force
-int amm_term_expr_upload(amm_ctx *ctx, TermExprForce *tf, bool globals_only);
 int amm_term_expr_upload_params(amm_ctx *ctx, TermExprForce *tf, const double *h_params);
 int amm_term_expr_eval_impl(amm_ctx *ctx, TermExprForce *tf, const double *d_pos, double *d_force, int accumulate, double *d_energy);
 void amm_term_expr_free(TermExprForce *tf);

@@ -26,6 +26,7 @@
 
 #include "amm_ctx.h"
 #include "bonded_terms.h"
+#include "device_utils.h"
 
 #define AMM_CMAP_BLOCK 256
 
@@ -141,13 +142,7 @@ __global__ void __launch_bounds__(AMM_CMAP_BLOCK) k_cmap(CmapArgs A) {
             for (int x = 0; x < 3; ++x) out[3 * role + x] = -(de * g[role][x]);
         }
     }
-    if (EN) {
-        __shared__ double red[4];
-        for (int off = 32; off > 0; off >>= 1) e += __shfl_xor(e, off);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = e;
-        __syncthreads();
-        if (threadIdx.x == 0) A.epart[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-    }
+    if (EN) block_energy_store_256(e, A.epart);
 }
 
 // one lane per atom: its records, in record order (k_term_expr_gather's sum)
@@ -164,11 +159,7 @@ __global__ void __launch_bounds__(256) k_cmap_gather(int n, const int *__restric
         f1 += p[1];
         f2 += p[2];
     }
-    if (accumulate) {
-        force[3 * i] += f0; force[3 * i + 1] += f1; force[3 * i + 2] += f2;
-    } else {
-        force[3 * i] = f0; force[3 * i + 1] = f1; force[3 * i + 2] = f2;
-    }
+    store_force_row(force, i, f0, f1, f2, accumulate);
 }
 
 int amm_cmap_eval_impl(amm_ctx *ctx, CmapForce *cm, const double *d_pos, double *d_force, int accumulate, double *d_energy) {
@@ -198,13 +189,6 @@ int amm_cmap_eval_impl(amm_ctx *ctx, CmapForce *cm, const double *d_pos, double 
 }
 
 // ---- host ----
-template <typename T>
-static int cm_upload(T **dst, const T *src, size_t count) {
-    AMM_HIP(hipMalloc(dst, sizeof(T) * std::max<size_t>(count, 1)));
-    if (count) AMM_HIP(hipMemcpy(*dst, src, sizeof(T) * count, hipMemcpyHostToDevice));
-    return 0;
-}
-
 static int cm_check_maps(const char *who, const int32_t *h_map_of_term, int n_terms, int n_maps) {
     for (int t = 0; t < n_terms; ++t)
         if (h_map_of_term[t] < 0 || h_map_of_term[t] >= n_maps) {
@@ -254,12 +238,12 @@ int amm_cmap_create_impl(amm_ctx *ctx, int n_maps, const int32_t *h_sizes, const
         for (size_t k = 0; k < (size_t)n_terms * 8; ++k) src[fill[h_idx[k]]++] = (int)k;
     }
     auto alloc = [&]() {
-        if (cm_upload(&cm->d_map, map.data(), map.size())) return 1;
-        if (cm_upload(&cm->d_coef, h_coeffs, n_cells * 16)) return 1;       // (hipMalloc aligns to 256 B: every row is 128-byte aligned)
-        if (cm_upload(&cm->d_map_of_term, h_map_of_term, (size_t)n_terms)) return 1;
-        if (cm_upload(&cm->d_idx, h_idx, (size_t)n_terms * 8)) return 1;
-        if (cm_upload(&cm->d_ref_ptr, ptr.data(), ptr.size())) return 1;
-        if (cm_upload(&cm->d_rec_src, src.data(), src.size())) return 1;
+        if (amm_upload(&cm->d_map, map.data(), map.size())) return 1;
+        if (amm_upload(&cm->d_coef, h_coeffs, n_cells * 16)) return 1;       // (hipMalloc aligns to 256 B: every row is 128-byte aligned)
+        if (amm_upload(&cm->d_map_of_term, h_map_of_term, (size_t)n_terms)) return 1;
+        if (amm_upload(&cm->d_idx, h_idx, (size_t)n_terms * 8)) return 1;
+        if (amm_upload(&cm->d_ref_ptr, ptr.data(), ptr.size())) return 1;
+        if (amm_upload(&cm->d_rec_src, src.data(), src.size())) return 1;
         const size_t park = std::max<size_t>((size_t)n_terms * 24, 1);
         AMM_HIP(hipMalloc(&cm->d_park, sizeof(double) * park));
         AMM_HIP(hipMemset(cm->d_park, 0, sizeof(double) * park));

@@ -1,7 +1,7 @@
 // atomsmm_amd/csrc/compound.hip -- CustomCompoundBondForce and CustomCentroidBondForce with ANY energy text (AMM_FORCE_COMPOUND): a
 // bond is N particles (or N weighted centres of groups of atoms) and its text reads up to 16 geometric variables over them --
 // raw coordinates, distance(pa,pb), angle(pa,pb,pc), dihedral(pa,pb,pc,pd) -- compiled by atomsmm_amd/expr.py (compile_compound)
-// into the program of pair_expr_vm.h plus a variable table (kind, slots within the bond).
+// into the program of pair_expr_vm.h plus a variable table (kind, slots within the bond: VarTable, expr_force.h).
 //
 // Takes over what OpenMM does for these two classes: per bond, the variables, the energy expression at them and its partial
 // derivatives (Lepton differentiates the text; here the interpreter carries one derivative along per lane), and
@@ -32,21 +32,16 @@
 #include "amm_ctx.h"
 #include "bonded_terms.h"
 #include "compound_geom.h"
+#include "device_utils.h"
 #include "term_expr_vm.h"
 
 #define AMM_CB_BLOCK 256
 
-struct CompoundTable {                  // the variable table as the device holds it
-    int kind[AMM_COMPOUND_MAX_VARS];    // AMM_CVAR_*
-    int4 slot[AMM_COMPOUND_MAX_VARS];   // positions within the bond of the variable's roles (0 behind its arity)
-};
-
 struct CompoundForce {
     int n_slots = 0, n_vars = 0, shift = 0, n_bonds = 0, n_params = 0, periodic = 0, n_blocks = 1;
     int n_groups = 0, n_members = 0;    // n_groups > 0: the slots of a bond are groups (centroid bonds)
-    PairExprProg h;
-    PairExprProg *d = nullptr;
-    CompoundTable *d_tab = nullptr;
+    ExprProgram prog;
+    VarTable *d_tab = nullptr;
     int *d_idx = nullptr;               // [n_bonds][n_slots] atoms, or groups
     double *d_params = nullptr;         // [n_params][n_bonds]
     double *d_park = nullptr;           // [n_bonds][n_vars][4][3] parked forces of the variables' roles
@@ -88,7 +83,7 @@ struct CompoundArgs {
 
 template <bool EN>
 __global__ void __launch_bounds__(AMM_CB_BLOCK) k_compound(CompoundArgs A, const PairExprProg *__restrict__ prog,
-                                                           const CompoundTable *__restrict__ tab) {
+                                                           const VarTable *__restrict__ tab) {
 #pragma clang fp contract(off)
     __shared__ int s_code[AMM_PEXPR_MAXCODE];
     __shared__ double s_consts[AMM_PEXPR_MAXCONST];
@@ -98,13 +93,8 @@ __global__ void __launch_bounds__(AMM_CB_BLOCK) k_compound(CompoundArgs A, const
     __shared__ int4 s_slot[AMM_COMPOUND_MAX_VARS];
     __shared__ double2 s_stack[(AMM_PEXPR_STACK - 1) * AMM_PEXPR_STRIDE];      // all but the top of every lane's stack
     const int ncode = prog->ncode;
-    for (int k = threadIdx.x; k < ncode; k += blockDim.x) s_code[k] = prog->code[k];
-    for (int k = threadIdx.x; k < prog->nconst; k += blockDim.x) s_consts[k] = prog->consts[k];
-    for (int k = threadIdx.x; k < prog->nglobal; k += blockDim.x) s_globals[k] = prog->globals[k];
-    if (threadIdx.x < AMM_COMPOUND_MAX_VARS) {
-        s_kind[threadIdx.x] = tab->kind[threadIdx.x];
-        s_slot[threadIdx.x] = tab->slot[threadIdx.x];
-    }
+    pexpr_stage(prog, s_code, s_consts, s_globals);
+    var_table_stage(tab, s_kind, s_slot);
     __syncthreads();
     const int k = threadIdx.x & ((1 << A.shift) - 1);
     const int bond = blockIdx.x * (AMM_CB_BLOCK >> A.shift) + (threadIdx.x >> A.shift);
@@ -144,13 +134,7 @@ __global__ void __launch_bounds__(AMM_CB_BLOCK) k_compound(CompoundArgs A, const
         }
         if (k != 0) e = 0.0;
     }
-    if (EN) {
-        __shared__ double red[4];
-        for (int off = 32; off > 0; off >>= 1) e += __shfl_xor(e, off);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = e;
-        __syncthreads();
-        if (threadIdx.x == 0) A.epart[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-    }
+    if (EN) block_energy_store_256(e, A.epart);
 }
 
 // one lane per atom: its records, in record order (k_term_expr_gather's loop)
@@ -167,11 +151,7 @@ __global__ void __launch_bounds__(256) k_compound_gather(int n, const int *__res
         f1 += p[1];
         f2 += p[2];
     }
-    if (accumulate) {
-        force[3 * i] += f0; force[3 * i + 1] += f1; force[3 * i + 2] += f2;
-    } else {
-        force[3 * i] = f0; force[3 * i + 1] = f1; force[3 * i + 2] = f2;
-    }
+    store_force_row(force, i, f0, f1, f2, accumulate);
 }
 
 // one wavefront per group: W = sum w_i and sum w_i x_i over the raw positions, members lane-strided, then a fixed-order butterfly
@@ -230,11 +210,7 @@ __global__ void __launch_bounds__(256) k_compound_spread(int n, const int *__res
         f1 += s * F1;
         f2 += s * F2;
     }
-    if (accumulate) {
-        force[3 * i] += f0; force[3 * i + 1] += f1; force[3 * i + 2] += f2;
-    } else {
-        force[3 * i] = f0; force[3 * i + 1] = f1; force[3 * i + 2] = f2;
-    }
+    store_force_row(force, i, f0, f1, f2, accumulate);
 }
 
 int amm_compound_eval_impl(amm_ctx *ctx, CompoundForce *cf, const double *d_pos, double *d_force, int accumulate, double *d_energy) {
@@ -258,8 +234,8 @@ int amm_compound_eval_impl(amm_ctx *ctx, CompoundForce *cf, const double *d_pos,
         A.park = cf->d_park;
         A.epart = cf->d_epart;
         A.box = ctx->box;
-        if (d_energy) hipLaunchKernelGGL((k_compound<true>), dim3(cf->n_blocks), dim3(AMM_CB_BLOCK), 0, ctx->stream, A, cf->d, cf->d_tab);
-        else hipLaunchKernelGGL((k_compound<false>), dim3(cf->n_blocks), dim3(AMM_CB_BLOCK), 0, ctx->stream, A, cf->d, cf->d_tab);
+        if (d_energy) hipLaunchKernelGGL((k_compound<true>), dim3(cf->n_blocks), dim3(AMM_CB_BLOCK), 0, ctx->stream, A, cf->prog.d, cf->d_tab);
+        else hipLaunchKernelGGL((k_compound<false>), dim3(cf->n_blocks), dim3(AMM_CB_BLOCK), 0, ctx->stream, A, cf->prog.d, cf->d_tab);
         AMM_HIP(hipGetLastError());
     }
     // (a force without bonds still writes its rows: it may be the first member of its group)
@@ -275,15 +251,6 @@ int amm_compound_eval_impl(amm_ctx *ctx, CompoundForce *cf, const double *d_pos,
 }
 
 // ---- host ----
-static int cvar_arity(int kind) { return kind <= AMM_CVAR_Z ? 1 : kind - 1; }      // 1, 1, 1, 2, 3, 4
-
-template <typename T>
-static int cb_upload(T **dst, const T *src, size_t count) {
-    AMM_HIP(hipMalloc(dst, sizeof(T) * std::max<size_t>(count, 1)));
-    if (count) AMM_HIP(hipMemcpy(*dst, src, sizeof(T) * count, hipMemcpyHostToDevice));
-    return 0;
-}
-
 static int cb_upload_weights(amm_ctx *ctx, CompoundForce *cf, const double *w) {
     std::vector<double> aw(cf->n_members);
     for (int m = 0; m < cf->n_members; ++m) aw[m] = w[cf->a_member[m]];
@@ -324,15 +291,10 @@ int amm_compound_create_impl(amm_ctx *ctx, int n_slots, const int32_t *code, int
     if (periodic && !ctx->has_box) return fail("periodic bonds, but the context has no periodic box");
     if (ctx->world > 1) return fail("a compound-bond force (AMM_FORCE_COMPOUND) runs on a single rank");
     if ((long long)n_bonds * std::max(n_vars, 1) * 4 > (long long)INT_MAX) return fail("too many (bond, variable, role) records for a 32-bit index");
-    for (int k = 0; k < n_vars; ++k) {
-        const int kind = var_kinds[k];
-        if (kind < AMM_CVAR_X || kind > AMM_CVAR_DIHEDRAL) return fail("variable " + std::to_string(k) + " has the unknown kind " + std::to_string(kind));
-        for (int r = 0; r < cvar_arity(kind); ++r) {
-            const int s = var_slots[4 * k + r];
-            if (s < 0 || s >= n_slots)
-                return fail("variable " + std::to_string(k) + " names slot " + std::to_string(s) + " beyond the bond (" + std::to_string(n_slots) + " slots)");
-        }
-    }
+    VarTable tab;
+    if (var_table_fill("amm_compound_create", var_kinds, var_slots, n_vars, n_slots, AMM_CVAR_X, "the unknown kind ", "",
+                       "beyond the bond (" + std::to_string(n_slots) + " slots)", tab, nullptr))
+        return 1;
     if (amm_expr_program_validate("amm_compound_create", code, ncode, nconst, nglobal, n_vars, n_params)) return 1;
     const bool centroid = n_groups > 0;
     int n_members = 0;
@@ -362,63 +324,38 @@ int amm_compound_create_impl(amm_ctx *ctx, int n_slots, const int32_t *code, int
     cf->n_members = n_members;
     const int per_block = AMM_CB_BLOCK >> cf->shift;
     cf->n_blocks = std::max(1, (n_bonds + per_block - 1) / per_block);
-    std::memset(&cf->h, 0, sizeof(cf->h));
-    cf->h.ncode = ncode;
-    cf->h.nconst = nconst;
-    cf->h.nglobal = nglobal;
-    std::copy(code, code + ncode, cf->h.code);
-    std::copy(consts, consts + nconst, cf->h.consts);
-    std::copy(globals, globals + nglobal, cf->h.globals);
-    CompoundTable tab;
-    std::memset(&tab, 0, sizeof(tab));
-    for (int k = 0; k < n_vars; ++k) {
-        tab.kind[k] = var_kinds[k];
-        const int ar = cvar_arity(var_kinds[k]);
-        tab.slot[k] = make_int4(var_slots[4 * k], ar > 1 ? var_slots[4 * k + 1] : 0, ar > 2 ? var_slots[4 * k + 2] : 0, ar > 3 ? var_slots[4 * k + 3] : 0);
-    }
+    cf->prog.fill(code, ncode, consts, nconst, globals, nglobal);
     // CSR of the records per atom (or per group): bond order, then variable, then role
-    std::vector<int> ptr(limit + 1, 0), src;
-    auto target = [&](int b, int k, int r) { return h_idx[(size_t)b * n_slots + var_slots[4 * k + r]]; };
-    for (int b = 0; b < n_bonds; ++b)
-        for (int k = 0; k < n_vars; ++k)
-            for (int r = 0; r < cvar_arity(var_kinds[k]); ++r) ptr[target(b, k, r) + 1]++;
-    for (int i = 0; i < limit; ++i) ptr[i + 1] += ptr[i];
-    src.resize(ptr[limit]);
-    {
-        std::vector<int> fill(ptr.begin(), ptr.end() - 1);
+    std::vector<int> ptr, src;
+    csr_of_records(limit, [&](auto &&visit) {
         for (int b = 0; b < n_bonds; ++b)
             for (int k = 0; k < n_vars; ++k)
-                for (int r = 0; r < cvar_arity(var_kinds[k]); ++r) src[fill[target(b, k, r)]++] = (b * n_vars + k) * 4 + r;
-    }
+                for (int r = 0; r < cvar_arity(var_kinds[k]); ++r) visit(h_idx[(size_t)b * n_slots + var_slots[4 * k + r]], (b * n_vars + k) * 4 + r);
+    }, ptr, src);
     auto alloc = [&]() {
-        AMM_HIP(hipMalloc(&cf->d, sizeof(PairExprProg)));
-        AMM_HIP(hipMemcpy(cf->d, &cf->h, sizeof(PairExprProg), hipMemcpyHostToDevice));
-        if (cb_upload(&cf->d_tab, &tab, 1)) return 1;
-        if (cb_upload(&cf->d_idx, h_idx, (size_t)n_bonds * n_slots)) return 1;
-        if (cb_upload(&cf->d_params, h_params, (size_t)n_bonds * n_params)) return 1;
-        if (cb_upload(&cf->d_ref_ptr, ptr.data(), ptr.size())) return 1;
-        if (cb_upload(&cf->d_rec_src, src.data(), src.size())) return 1;
+        if (cf->prog.upload(ctx, false)) return 1;
+        if (amm_upload(&cf->d_tab, &tab, 1)) return 1;
+        if (amm_upload(&cf->d_idx, h_idx, (size_t)n_bonds * n_slots)) return 1;
+        if (amm_upload(&cf->d_params, h_params, (size_t)n_bonds * n_params)) return 1;
+        if (amm_upload(&cf->d_ref_ptr, ptr.data(), ptr.size())) return 1;
+        if (amm_upload(&cf->d_rec_src, src.data(), src.size())) return 1;
         const size_t park = std::max<size_t>((size_t)n_bonds * n_vars * 12, 1);
         AMM_HIP(hipMalloc(&cf->d_park, sizeof(double) * park));
         AMM_HIP(hipMemset(cf->d_park, 0, sizeof(double) * park));
         AMM_HIP(hipMalloc(&cf->d_epart, sizeof(double) * cf->n_blocks));
         if (centroid) {
             // memberships per atom, in group order (and member order within a group)
-            std::vector<int> aptr(n + 1, 0), agrp(n_members);
-            cf->a_member.resize(n_members);
-            for (int m = 0; m < n_members; ++m) aptr[g_atoms[m] + 1]++;
-            for (int i = 0; i < n; ++i) aptr[i + 1] += aptr[i];
-            std::vector<int> fill(aptr.begin(), aptr.end() - 1);
+            std::vector<int> aptr, agrp(n_members), group_of(n_members);
             for (int g = 0; g < n_groups; ++g)
-                for (int m = g_ptr[g]; m < g_ptr[g + 1]; ++m) {
-                    const int at = fill[g_atoms[m]]++;
-                    agrp[at] = g;
-                    cf->a_member[at] = m;
-                }
-            if (cb_upload(&cf->d_g_ptr, g_ptr, (size_t)n_groups + 1)) return 1;
-            if (cb_upload(&cf->d_g_atom, g_atoms, (size_t)n_members)) return 1;
-            if (cb_upload(&cf->d_a_ptr, aptr.data(), aptr.size())) return 1;
-            if (cb_upload(&cf->d_a_grp, agrp.data(), agrp.size())) return 1;
+                for (int m = g_ptr[g]; m < g_ptr[g + 1]; ++m) group_of[m] = g;
+            csr_of_records(n, [&](auto &&visit) {
+                for (int m = 0; m < n_members; ++m) visit(g_atoms[m], m);
+            }, aptr, cf->a_member);
+            for (int at = 0; at < n_members; ++at) agrp[at] = group_of[cf->a_member[at]];
+            if (amm_upload(&cf->d_g_ptr, g_ptr, (size_t)n_groups + 1)) return 1;
+            if (amm_upload(&cf->d_g_atom, g_atoms, (size_t)n_members)) return 1;
+            if (amm_upload(&cf->d_a_ptr, aptr.data(), aptr.size())) return 1;
+            if (amm_upload(&cf->d_a_grp, agrp.data(), agrp.size())) return 1;
             AMM_HIP(hipMalloc(&cf->d_g_w, sizeof(double) * n_members));
             AMM_HIP(hipMalloc(&cf->d_a_w, sizeof(double) * n_members));
             AMM_HIP(hipMalloc(&cf->d_centre, sizeof(double) * 3 * n_groups));
@@ -436,14 +373,7 @@ int amm_compound_create_impl(amm_ctx *ctx, int n_slots, const int32_t *code, int
 }
 
 int amm_compound_set_globals_impl(amm_ctx *ctx, CompoundForce *cf, const double *globals, int nglobal) {
-    if (nglobal != cf->h.nglobal || (nglobal > 0 && !globals)) {
-        amm_set_error("amm_compound_set_globals: the program reads " + std::to_string(cf->h.nglobal) + " globals, " + std::to_string(nglobal) + " given");
-        return 1;
-    }
-    std::copy(globals, globals + nglobal, cf->h.globals);
-    AMM_HIP(hipStreamSynchronize(ctx->stream));
-    AMM_HIP(hipMemcpy(cf->d->globals, cf->h.globals, sizeof(cf->h.globals), hipMemcpyHostToDevice));
-    return 0;
+    return cf->prog.set_globals(ctx, "amm_compound_set_globals", globals, nglobal);
 }
 
 int amm_compound_set_params_impl(amm_ctx *ctx, CompoundForce *cf, const double *h_params, int n_bonds, int n_params) {
@@ -476,7 +406,7 @@ int amm_compound_set_weights_impl(amm_ctx *ctx, CompoundForce *cf, const double 
 
 void amm_compound_free(CompoundForce *cf) {
     if (!cf) return;
-    for (void *p : {(void *)cf->d, (void *)cf->d_tab, (void *)cf->d_idx, (void *)cf->d_params, (void *)cf->d_park, (void *)cf->d_epart,
+    for (void *p : {(void *)cf->prog.d, (void *)cf->d_tab, (void *)cf->d_idx, (void *)cf->d_params, (void *)cf->d_park, (void *)cf->d_epart,
                     (void *)cf->d_ref_ptr, (void *)cf->d_rec_src, (void *)cf->d_g_ptr, (void *)cf->d_g_atom, (void *)cf->d_g_w, (void *)cf->d_centre,
                     (void *)cf->d_W, (void *)cf->d_a_ptr, (void *)cf->d_a_grp, (void *)cf->d_a_w})
         if (p) (void)hipFree(p);

@@ -69,4 +69,16 @@ __device__ __forceinline__ void compound_variable(const P &pos, int kind, int a0
         }
     }
 }
+
+// The tail of a drain: the `take` entries at the front of the queue are done, what is left (fewer than 64) moves to the front.
+// Every lane of the block (one wavefront) reaches the two barriers.  Returns the entries left.
+template <class T>
+__device__ __forceinline__ int queue_keep_rest(T *s_queue, int qn, int take) {
+    const int rest = qn - take;
+    const T moved = (int)threadIdx.x < rest ? s_queue[AMM_WAVE + threadIdx.x] : T{};
+    __syncthreads();
+    if ((int)threadIdx.x < rest) s_queue[threadIdx.x] = moved;
+    __syncthreads();
+    return rest;
+}
 #endif

@@ -586,7 +586,7 @@ int amm_custom_gb_create_impl(amm_ctx *ctx, int n_params, int n_values, int n_te
         ptr[a + 1] = (int)idx.size();
     }
     cg->tabx = new PairExpr();
-    std::memset(&cg->tabx->h, 0, sizeof(cg->tabx->h));
+    std::memset(&cg->tabx->prog.h, 0, sizeof(cg->tabx->prog.h));
     const size_t bytes = sizeof(double) * n;
     bool ok = true;
     ok = ok && hipMalloc(&cg->d_code, sizeof(int) * std::max<size_t>(cg->h_code.size(), 1)) == hipSuccess;

@@ -31,8 +31,7 @@
 struct CvForce {
     int n_cv = 0, n_deriv = 0;
     int inner[AMM_CV_MAX_CVS];
-    PairExprProg h;                     // the outer program: layout and limits of a pair expression's
-    PairExprProg *d = nullptr;
+    ExprProgram prog;                   // the outer program: layout and limits of a pair expression's
     double h_vars[AMM_CV_MAX_DERIVS];   // current values of the derivative parameters
     double *d_vars = nullptr;           // [P] the same on the device
     double *d_cv = nullptr;             // [K] the inner energies of the evaluation in flight
@@ -73,9 +72,7 @@ __global__ void __launch_bounds__(AMM_CV_BLOCK) k_cv_apply(CvArgs A, const PairE
     __shared__ double s_energy;
     __shared__ double2 s_stack[(AMM_PEXPR_STACK - 1) * AMM_CV_LANES];
     const int ncode = prog->ncode, nv = A.K + A.P;
-    for (int k = threadIdx.x; k < ncode; k += blockDim.x) s_code[k] = prog->code[k];
-    for (int k = threadIdx.x; k < prog->nconst; k += blockDim.x) s_consts[k] = prog->consts[k];
-    for (int k = threadIdx.x; k < prog->nglobal; k += blockDim.x) s_globals[k] = prog->globals[k];
+    pexpr_stage(prog, s_code, s_consts, s_globals);
     if (threadIdx.x < AMM_CV_LANES) s_var[threadIdx.x] = threadIdx.x < A.K ? A.cv[threadIdx.x] : (threadIdx.x < nv ? A.vars[threadIdx.x - A.K] : 0.0);
     __syncthreads();
     if (threadIdx.x < nv) {             // (nv <= 32: half of the first wavefront, one lane per partial derivative)
@@ -151,7 +148,7 @@ static int cv_apply(amm_ctx *ctx, CvForce *cv, double *d_force, int accumulate, 
     A.dout = d_dout;
     const long per_block = AMM_CV_BLOCK * AMM_CV_PER_LANE;
     const int blocks = d_force ? (int)std::max<long>(1, (A.n3 + per_block - 1) / per_block) : 1;
-    hipLaunchKernelGGL(k_cv_apply, dim3(blocks), dim3(AMM_CV_BLOCK), 0, ctx->stream, A, cv->d);
+    hipLaunchKernelGGL(k_cv_apply, dim3(blocks), dim3(AMM_CV_BLOCK), 0, ctx->stream, A, cv->prog.d);
     AMM_HIP(hipGetLastError());
     return 0;
 }
@@ -159,13 +156,6 @@ static int cv_apply(amm_ctx *ctx, CvForce *cv, double *d_force, int accumulate, 
 int amm_cv_eval_impl(amm_ctx *ctx, CvForce *cv, const double *d_pos, double *d_force, int accumulate, double *d_energy) {
     if (cv_eval_inner(ctx, cv, d_pos, "evaluation of a collective-variable force (AMM_FORCE_CV)")) return 1;
     return cv_apply(ctx, cv, d_force, accumulate, d_energy, nullptr);
-}
-
-static int cv_upload(amm_ctx *ctx, CvForce *cv, bool globals_only) {
-    AMM_HIP(hipStreamSynchronize(ctx->stream));     // ordered after any kernel already queued on the stream that reads the old values
-    if (globals_only) AMM_HIP(hipMemcpy(cv->d->globals, cv->h.globals, sizeof(cv->h.globals), hipMemcpyHostToDevice));
-    else AMM_HIP(hipMemcpy(cv->d, &cv->h, sizeof(PairExprProg), hipMemcpyHostToDevice));
-    return 0;
 }
 
 int amm_cv_create_impl(amm_ctx *ctx, const int32_t *inner_ids, int n_cv, int n_deriv, const int32_t *code, int ncode, const double *consts,
@@ -184,17 +174,10 @@ int amm_cv_create_impl(amm_ctx *ctx, const int32_t *inner_ids, int n_cv, int n_d
     cv->n_cv = n_cv;
     cv->n_deriv = n_deriv;
     std::copy(inner_ids, inner_ids + n_cv, cv->inner);
-    std::memset(&cv->h, 0, sizeof(cv->h));
     std::memset(cv->h_vars, 0, sizeof(cv->h_vars));
-    cv->h.ncode = ncode;
-    cv->h.nconst = nconst;
-    cv->h.nglobal = nglobal;
-    std::copy(code, code + ncode, cv->h.code);
-    std::copy(consts, consts + nconst, cv->h.consts);
-    std::copy(globals, globals + nglobal, cv->h.globals);
+    cv->prog.fill(code, ncode, consts, nconst, globals, nglobal);
     const size_t n3 = 3 * (size_t)ctx->n;
     auto alloc = [&]() {
-        AMM_HIP(hipMalloc(&cv->d, sizeof(PairExprProg)));
         AMM_HIP(hipMalloc(&cv->d_vars, sizeof(double) * AMM_CV_MAX_DERIVS));
         AMM_HIP(hipMalloc(&cv->d_cv, sizeof(double) * AMM_CV_MAX_CVS));
         AMM_HIP(hipMalloc(&cv->d_coef, sizeof(double) * (AMM_CV_MAX_CVS + AMM_CV_MAX_DERIVS + AMM_CV_MAX_CVS)));
@@ -202,7 +185,7 @@ int amm_cv_create_impl(amm_ctx *ctx, const int32_t *inner_ids, int n_cv, int n_d
         AMM_HIP(hipMemset(cv->d_vars, 0, sizeof(double) * AMM_CV_MAX_DERIVS));
         AMM_HIP(hipMemset(cv->d_cv, 0, sizeof(double) * AMM_CV_MAX_CVS));
         AMM_HIP(hipMemset(cv->d_coef, 0, sizeof(double) * (AMM_CV_MAX_CVS + AMM_CV_MAX_DERIVS + AMM_CV_MAX_CVS)));
-        return cv_upload(ctx, cv, false);
+        return cv->prog.upload(ctx, false);
     };
     if (alloc()) {
         amm_cv_free(cv);
@@ -213,12 +196,7 @@ int amm_cv_create_impl(amm_ctx *ctx, const int32_t *inner_ids, int n_cv, int n_d
 }
 
 int amm_cv_set_globals_impl(amm_ctx *ctx, CvForce *cv, const double *globals, int nglobal) {
-    if (nglobal != cv->h.nglobal || (nglobal > 0 && !globals)) {
-        amm_set_error("amm_cv_set_globals: the program reads " + std::to_string(cv->h.nglobal) + " globals, " + std::to_string(nglobal) + " given");
-        return 1;
-    }
-    std::copy(globals, globals + nglobal, cv->h.globals);
-    return cv_upload(ctx, cv, true);
+    return cv->prog.set_globals(ctx, "amm_cv_set_globals", globals, nglobal);
 }
 
 int amm_cv_set_variables_impl(amm_ctx *ctx, CvForce *cv, const double *values, int n_deriv) {
@@ -249,7 +227,7 @@ int amm_cv_energy_derivative_impl(amm_ctx *ctx, CvForce *cv, const double *d_pos
 
 void amm_cv_free(CvForce *cv) {
     if (!cv) return;
-    for (void *p : {(void *)cv->d, (void *)cv->d_vars, (void *)cv->d_cv, (void *)cv->d_fcv, (void *)cv->d_coef})
+    for (void *p : {(void *)cv->prog.d, (void *)cv->d_vars, (void *)cv->d_cv, (void *)cv->d_fcv, (void *)cv->d_coef})
         if (p) (void)hipFree(p);
     delete cv;
 }

@@ -63,6 +63,23 @@ __device__ __forceinline__ void amm_st_l2(unsigned long long *p, unsigned long l
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// row i of a force buffer: added to, or written (a kernel that does not accumulate writes every row)
+__device__ __forceinline__ void store_force_row(double *force, int i, double f0, double f1, double f2, int accumulate) {
+    if (accumulate) {
+        force[3 * i] += f0; force[3 * i + 1] += f1; force[3 * i + 2] += f2;
+    } else {
+        force[3 * i] = f0; force[3 * i + 1] = f1; force[3 * i + 2] = f2;
+    }
+}
+// the energy of a block of 256 lanes in a fixed order -- a butterfly per wavefront, then the four wavefronts in index order -- times
+// `scale`, into epart[blockIdx.x].  Every lane of the block calls (there is a barrier inside).
+__device__ __forceinline__ void block_energy_store_256(double e, double *epart, double scale = 1.0) {
+    __shared__ double red[4];
+    for (int off = 32; off > 0; off >>= 1) e += __shfl_xor(e, off);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = e;
+    __syncthreads();
+    if (threadIdx.x == 0) epart[blockIdx.x] = scale * (((red[0] + red[1]) + red[2]) + red[3]);
+}
 
 // Two histograms in one word -- count[c] = atoms of cell c (low 16 bits) | those of them with a Lennard-Jones site << 16 -- and
 // both exclusive scans in one sweep: start[0..ncell] and start_hi[0..ncell]; count <- 0; returns the largest cell count.

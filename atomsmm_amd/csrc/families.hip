@@ -123,13 +123,7 @@ int amm_term_expr_create(amm_ctx *ctx, int32_t kind, const int32_t *code, int32_
     tf->periodic = periodic ? 1 : 0;
     tf->n_terms = n_terms;
     tf->n_params = n_params;
-    std::memset(&tf->h, 0, sizeof(tf->h));
-    tf->h.ncode = ncode;
-    tf->h.nconst = nconst;
-    tf->h.nglobal = nglobal;
-    std::copy(code, code + ncode, tf->h.code);
-    std::copy(consts, consts + nconst, tf->h.consts);
-    std::copy(globals, globals + nglobal, tf->h.globals);
+    tf->prog.fill(code, ncode, consts, nconst, globals, nglobal);
     if (amm_term_expr_build(ctx, tf, h_idx, h_params)) {
         amm_term_expr_free(tf);
         return 1;
@@ -141,12 +135,7 @@ int amm_term_expr_create(amm_ctx *ctx, int32_t kind, const int32_t *code, int32_
 int amm_term_expr_set_globals(amm_ctx *ctx, int32_t force_id, const double *globals, int32_t nglobal) {
     TermExprForce *tf = amm_force_get<TermExprForce>(ctx, force_id, "amm_term_expr_set_globals");
     if (!tf) return 1;
-    if (nglobal != tf->h.nglobal || (nglobal > 0 && !globals)) {
-        amm_set_error("amm_term_expr_set_globals: the program reads " + std::to_string(tf->h.nglobal) + " globals, " + std::to_string(nglobal) + " given");
-        return 1;
-    }
-    std::copy(globals, globals + nglobal, tf->h.globals);
-    return amm_term_expr_upload(ctx, tf, true);
+    return tf->prog.set_globals(ctx, "amm_term_expr_set_globals", globals, nglobal);
 }
 
 int amm_term_expr_set_params(amm_ctx *ctx, int32_t force_id, const double *h_params, int32_t n_terms, int32_t n_params) {

@@ -1,7 +1,7 @@
 // atomsmm_amd/csrc/hbond.hip -- CustomHbondForce with ANY energy text (AMM_FORCE_HBOND): D donors (d1, d2, d3) against A acceptors
 // (a1, a2, a3), every pair that is not excluded and whose distance(d1, a1) lies inside the cutoff contributes the text -- up to 16
 // geometric variables distance / angle / dihedral over the six particles, per-donor, per-acceptor and global parameters -- compiled by
-// atomsmm_amd/expr.py (compile_hbond) into the program of pair_expr_vm.h plus the variable table of compound.hip (slots 0 .. 2 the
+// atomsmm_amd/expr.py (compile_hbond) into the program of pair_expr_vm.h plus the variable table of expr_force.h (slots 0 .. 2 the
 // donor's particles, 3 .. 5 the acceptor's).
 //
 // A compound-bond force is a short explicit list; this one is D x A pairs of which the cutoff (or the text) keeps a few per cent.  So
@@ -27,15 +27,11 @@
 #include "amm_ctx.h"
 #include "bonded_terms.h"
 #include "compound_geom.h"
+#include "device_utils.h"
 #include "term_expr_vm.h"
 
 #define AMM_HB_LANES 64
 #define AMM_HB_MAX_ROWS 32768
-
-struct HbondTable {                     // CompoundTable's layout
-    int kind[AMM_COMPOUND_MAX_VARS];
-    int4 slot[AMM_COMPOUND_MAX_VARS];
-};
 
 struct HbondPass {                      // rows against columns: 0 donors against acceptors, 1 acceptors against donors
     int n_rows = 0, n_cols = 0, chunks = 1, chunk_len = 64;
@@ -47,9 +43,8 @@ struct HbondForce {
     int D = 0, A = 0, n_vars = 0, n_dp = 0, n_ap = 0, periodic = 0, cutoff = 0;
     double rc = 0.0;
     int compact = 1;
-    PairExprProg h;
-    PairExprProg *d = nullptr;
-    HbondTable *d_tab = nullptr;
+    ExprProgram prog;
+    VarTable *d_tab = nullptr;
     int *d_donors = nullptr, *d_acceptors = nullptr;    // [D][3], [A][3]; -1: the slot is not there
     double *d_dpar = nullptr, *d_apar = nullptr;        // [n_dp][D], [n_ap][A]
     HbondPass pass[2];
@@ -97,7 +92,7 @@ __device__ __forceinline__ int hb_pick(int s, int i0, int i1, int i2, int i3, in
 // EN: the donor pass of an evaluation with energy.  COMPACT = false drains after every batch of 64 columns that has a survivor (the
 // measurement of DESIGN.md 3.HB; option hbond_compact).
 template <bool EN, bool COMPACT>
-__global__ void __launch_bounds__(AMM_HB_LANES) k_hbond(HbondArgs A, const PairExprProg *__restrict__ prog, const HbondTable *__restrict__ tab) {
+__global__ void __launch_bounds__(AMM_HB_LANES) k_hbond(HbondArgs A, const PairExprProg *__restrict__ prog, const VarTable *__restrict__ tab) {
 #pragma clang fp contract(off)
     __shared__ int s_code[AMM_PEXPR_MAXCODE];
     __shared__ double s_consts[AMM_PEXPR_MAXCONST];
@@ -109,13 +104,8 @@ __global__ void __launch_bounds__(AMM_HB_LANES) k_hbond(HbondArgs A, const PairE
     __shared__ int s_queue[2 * AMM_HB_LANES];                                       // surviving columns that wait for the interpreter
     const int lane = threadIdx.x;
     const int ncode = prog->ncode;
-    for (int k = lane; k < ncode; k += AMM_HB_LANES) s_code[k] = prog->code[k];
-    for (int k = lane; k < prog->nconst; k += AMM_HB_LANES) s_consts[k] = prog->consts[k];
-    for (int k = lane; k < prog->nglobal; k += AMM_HB_LANES) s_globals[k] = prog->globals[k];
-    if (lane < AMM_COMPOUND_MAX_VARS) {
-        s_kind[lane] = tab->kind[lane];
-        s_slot[lane] = tab->slot[lane];
-    }
+    pexpr_stage(prog, s_code, s_consts, s_globals);
+    var_table_stage(tab, s_kind, s_slot);
     __syncthreads();
     const int row = blockIdx.x / A.chunks, chunk = blockIdx.x - row * A.chunks;     // (the grid is n_rows * chunks)
     const int begin = min(chunk * A.chunk_len, A.n_cols), end = min(begin + A.chunk_len, A.n_cols);
@@ -148,15 +138,7 @@ __global__ void __launch_bounds__(AMM_HB_LANES) k_hbond(HbondArgs A, const PairE
                     dz = amm_min_image(dz, A.box.L[2], A.box.invL[2]);
                 }
                 if (A.cutoff) keep = dx * dx + dy * dy + dz * dz < A.rc2;
-                if (keep && ex_end > ex_begin) {        // the row's excluded columns, sorted: a binary search
-                    int lo = ex_begin, hi = ex_end;
-                    while (lo < hi) {
-                        const int mid = (lo + hi) >> 1;
-                        if (A.ex_col[mid] < col) lo = mid + 1;
-                        else hi = mid;
-                    }
-                    if (lo < ex_end && A.ex_col[lo] == col) keep = false;
-                }
+                if (keep && ex_end > ex_begin) keep = !sorted_contains(A.ex_col, ex_begin, ex_end, col);      // the row's excluded columns
             }
             const unsigned long long mask = __ballot(keep);
             if (keep) s_queue[qn + __popcll(mask & ((1ull << lane) - 1ull))] = col;      // (qn < 64 here: at most 127 entries)
@@ -218,7 +200,7 @@ __global__ void __launch_bounds__(AMM_HB_LANES) k_hbond(HbondArgs A, const PairE
                     if (k == 0) e_sum += e;
                     if (k < V) {
                         const double coef = -de / rr;       // (rr = 1 but for a distance)
-                        const int arity = kind <= AMM_CVAR_Z ? 1 : kind - 1;
+                        const int arity = cvar_arity(kind);
                         const int o0 = sl.x - base, o1 = arity > 1 ? sl.y - base : -1, o2 = arity > 2 ? sl.z - base : -1,
                                   o3 = arity > 3 ? sl.w - base : -1;
 #pragma unroll
@@ -241,13 +223,7 @@ __global__ void __launch_bounds__(AMM_HB_LANES) k_hbond(HbondArgs A, const PairE
                 }
                 ++n_pass;
             }
-            // what is left moves to the front
-            const int rest = qn - take;
-            const int moved = lane < rest ? s_queue[AMM_HB_LANES + lane] : 0;
-            __syncthreads();
-            if (lane < rest) s_queue[lane] = moved;
-            __syncthreads();
-            qn = rest;
+            qn = queue_keep_rest(s_queue, qn, take);        // what is left moves to the front
         }
         if (last) break;
     }
@@ -298,31 +274,21 @@ __global__ void __launch_bounds__(256) k_hbond_gather(int n, int D, int chunks0,
             f2 += p[2];
         }
     }
-    if (accumulate) {
-        force[3 * i] += f0; force[3 * i + 1] += f1; force[3 * i + 2] += f2;
-    } else {
-        force[3 * i] = f0; force[3 * i + 1] = f1; force[3 * i + 2] = f2;
-    }
+    store_force_row(force, i, f0, f1, f2, accumulate);
 }
 
 template <bool EN>
 static void hb_launch(amm_ctx *ctx, HbondForce *hb, const HbondArgs &A, int blocks) {
-    if (hb->compact) hipLaunchKernelGGL((k_hbond<EN, true>), dim3(blocks), dim3(AMM_HB_LANES), 0, ctx->stream, A, hb->d, hb->d_tab);
-    else hipLaunchKernelGGL((k_hbond<EN, false>), dim3(blocks), dim3(AMM_HB_LANES), 0, ctx->stream, A, hb->d, hb->d_tab);
+    if (hb->compact) hipLaunchKernelGGL((k_hbond<EN, true>), dim3(blocks), dim3(AMM_HB_LANES), 0, ctx->stream, A, hb->prog.d, hb->d_tab);
+    else hipLaunchKernelGGL((k_hbond<EN, false>), dim3(blocks), dim3(AMM_HB_LANES), 0, ctx->stream, A, hb->prog.d, hb->d_tab);
 }
 
 int amm_hbond_eval_impl(amm_ctx *ctx, HbondForce *hb, const double *d_pos, double *d_force, int accumulate, double *d_energy) {
     const int n = ctx->n;
     const bool pairs = hb->D > 0 && hb->A > 0;
     if (pairs) {
-        if (hb->periodic && hb->cutoff) {       // the box may have changed since creation (a barostat)
-            const double shortest = std::min(ctx->box.L[0], std::min(ctx->box.L[1], ctx->box.L[2]));
-            if (hb->rc > 0.5 * shortest) {
-                amm_set_error("hydrogen-bond force (AMM_FORCE_HBOND): the cutoff " + std::to_string(hb->rc) + " exceeds half the shortest box edge (" +
-                              std::to_string(shortest) + ")");
-                return 1;
-            }
-        }
+        // (the box may have changed since creation: a barostat)
+        if (hb->periodic && hb->cutoff && !amm_cutoff_fits_box(ctx, hb->rc, "hydrogen-bond force (AMM_FORCE_HBOND)")) return 1;
         for (int p = 0; p < 2; ++p) {
             const HbondPass &P = hb->pass[p];
             HbondArgs A;
@@ -368,15 +334,6 @@ int amm_hbond_eval_impl(amm_ctx *ctx, HbondForce *hb, const double *d_pos, doubl
 }
 
 // ---- host ----
-static int hb_arity(int kind) { return kind - 1; }      // distance 2, angle 3, dihedral 4
-
-template <typename T>
-static int hb_upload(T **dst, const T *src, size_t count) {
-    AMM_HIP(hipMalloc(dst, sizeof(T) * std::max<size_t>(count, 1)));
-    if (count) AMM_HIP(hipMemcpy(*dst, src, sizeof(T) * count, hipMemcpyHostToDevice));
-    return 0;
-}
-
 int amm_hbond_create_impl(amm_ctx *ctx, const int32_t *code, int ncode, const double *consts, int nconst, const double *globals, int nglobal,
                           const int32_t *var_kinds, const int32_t *var_slots, int n_vars, const int32_t *h_donors, int n_donors,
                           const int32_t *h_acceptors, int n_acceptors, const double *h_dpar, int n_dpar, const double *h_apar, int n_apar,
@@ -398,22 +355,12 @@ int amm_hbond_create_impl(amm_ctx *ctx, const int32_t *code, int ncode, const do
     if (!std::isfinite(rc)) return fail("the cutoff is not finite");
     if (periodic && !(rc > 0.0)) return fail("CutoffPeriodic needs a cutoff distance above zero");
     if (periodic && !ctx->has_box) return fail("CutoffPeriodic, but the context has no periodic box");
-    if (periodic) {
-        const double shortest = std::min(ctx->box.L[0], std::min(ctx->box.L[1], ctx->box.L[2]));
-        if (rc > 0.5 * shortest)
-            return fail("the cutoff " + std::to_string(rc) + " exceeds half the shortest box edge (" + std::to_string(shortest) + ")");
-    }
+    if (periodic && !amm_cutoff_fits_box(ctx, rc, "amm_hbond_create")) return 1;
     bool used[6] = {false, false, false, false, false, false};
-    for (int k = 0; k < n_vars; ++k) {
-        const int kind = var_kinds[k];
-        if (kind < AMM_CVAR_DISTANCE || kind > AMM_CVAR_DIHEDRAL)
-            return fail("variable " + std::to_string(k) + " has the kind " + std::to_string(kind) + " (a hydrogen-bond text reads distance, angle and dihedral only)");
-        for (int r = 0; r < hb_arity(kind); ++r) {
-            const int s = var_slots[4 * k + r];
-            if (s < 0 || s >= 6) return fail("variable " + std::to_string(k) + " names slot " + std::to_string(s) + " beyond the pair (6 slots: d1 d2 d3 a1 a2 a3)");
-            used[s] = true;
-        }
-    }
+    VarTable tab;
+    if (var_table_fill("amm_hbond_create", var_kinds, var_slots, n_vars, 6, AMM_CVAR_DISTANCE, "the kind ",
+                       " (a hydrogen-bond text reads distance, angle and dihedral only)", "beyond the pair (6 slots: d1 d2 d3 a1 a2 a3)", tab, used))
+        return 1;
     if (amm_expr_program_validate("amm_hbond_create", code, ncode, nconst, nglobal, n_vars, n_dpar + n_apar)) return 1;
     static const char *slot_name[6] = {"d1", "d2", "d3", "a1", "a2", "a3"};
     for (int side = 0; side < 2; ++side) {
@@ -436,8 +383,6 @@ int amm_hbond_create_impl(amm_ctx *ctx, const int32_t *code, int ncode, const do
             return fail("exclusion " + std::to_string(e) + " (donor " + std::to_string(d) + ", acceptor " + std::to_string(a) + ") is out of range");
         ex[e] = {d, a};
     }
-    std::sort(ex.begin(), ex.end());
-    ex.erase(std::unique(ex.begin(), ex.end()), ex.end());
     AMM_HIP(hipSetDevice(ctx->device));
     HbondForce *hb = new HbondForce();
     hb->D = D;
@@ -449,20 +394,7 @@ int amm_hbond_create_impl(amm_ctx *ctx, const int32_t *code, int ncode, const do
     hb->cutoff = rc > 0.0 ? 1 : 0;
     hb->rc = rc > 0.0 ? rc : 0.0;
     hb->compact = ctx->opt_hbond_compact;
-    std::memset(&hb->h, 0, sizeof(hb->h));
-    hb->h.ncode = ncode;
-    hb->h.nconst = nconst;
-    hb->h.nglobal = nglobal;
-    std::copy(code, code + ncode, hb->h.code);
-    std::copy(consts, consts + nconst, hb->h.consts);
-    std::copy(globals, globals + nglobal, hb->h.globals);
-    HbondTable tab;
-    std::memset(&tab, 0, sizeof(tab));
-    for (int k = 0; k < n_vars; ++k) {
-        tab.kind[k] = var_kinds[k];
-        const int ar = hb_arity(var_kinds[k]);
-        tab.slot[k] = make_int4(var_slots[4 * k], var_slots[4 * k + 1], ar > 2 ? var_slots[4 * k + 2] : 0, ar > 3 ? var_slots[4 * k + 3] : 0);
-    }
+    hb->prog.fill(code, ncode, consts, nconst, globals, nglobal);
     // the passes: a row is split into chunks of columns (a multiple of 64 each) when there are few rows -- option hbond_chunks, or
     // enough wavefronts to fill the device
     for (int p = 0; p < 2; ++p) {
@@ -479,52 +411,34 @@ int amm_hbond_create_impl(amm_ctx *ctx, const int32_t *code, int ncode, const do
     hb->pass[0].park_base = 0;
     hb->pass[1].park_base = (size_t)D * hb->pass[0].chunks;
     const size_t records = hb->pass[1].park_base + (size_t)A * hb->pass[1].chunks;
-    // the exclusions per row: donors' sorted by acceptor (ex is), acceptors' sorted by donor
-    std::vector<int> ptr0(D + 1, 0), col0(ex.size()), ptr1(A + 1, 0), col1(ex.size());
-    for (const auto &e : ex) {
-        ptr0[e.first + 1]++;
-        ptr1[e.second + 1]++;
-    }
-    for (int i = 0; i < D; ++i) ptr0[i + 1] += ptr0[i];
-    for (int i = 0; i < A; ++i) ptr1[i + 1] += ptr1[i];
-    {
-        std::vector<int> fill(ptr1.begin(), ptr1.end() - 1);
-        for (size_t e = 0; e < ex.size(); ++e) {
-            col0[e] = ex[e].second;
-            col1[fill[ex[e].second]++] = ex[e].first;       // (donors ascend within an acceptor: ex is sorted by donor first)
-        }
-    }
+    // the exclusions per row: a donor's acceptors ascending, then (the pairs turned round) an acceptor's donors ascending
+    std::vector<int> ptr0, col0, ptr1, col1;
+    csr_of_pairs(D, ex, ptr0, col0);
+    for (auto &e : ex) std::swap(e.first, e.second);
+    csr_of_pairs(A, ex, ptr1, col1);
     // CSR of the records per atom: donors in index order, role by role, then acceptors
-    std::vector<int> ptr(n + 1, 0), src;
-    auto each = [&](auto &&visit) {
+    std::vector<int> ptr, src;
+    csr_of_records(n, [&](auto &&visit) {
         for (int t = 0; t < D; ++t)
             for (int r = 0; r < 3; ++r)
                 if (h_donors[3 * t + r] >= 0) visit(h_donors[3 * t + r], t * 3 + r);
         for (int t = 0; t < A; ++t)
             for (int r = 0; r < 3; ++r)
                 if (h_acceptors[3 * t + r] >= 0) visit(h_acceptors[3 * t + r], (D + t) * 3 + r);
-    };
-    each([&](int atom, int) { ptr[atom + 1]++; });
-    for (int i = 0; i < n; ++i) ptr[i + 1] += ptr[i];
-    src.resize(ptr[n]);
-    {
-        std::vector<int> fill(ptr.begin(), ptr.end() - 1);
-        each([&](int atom, int rec) { src[fill[atom]++] = rec; });
-    }
+    }, ptr, src);
     auto alloc = [&]() {
-        AMM_HIP(hipMalloc(&hb->d, sizeof(PairExprProg)));
-        AMM_HIP(hipMemcpy(hb->d, &hb->h, sizeof(PairExprProg), hipMemcpyHostToDevice));
-        if (hb_upload(&hb->d_tab, &tab, 1)) return 1;
-        if (hb_upload(&hb->d_donors, h_donors, (size_t)D * 3)) return 1;
-        if (hb_upload(&hb->d_acceptors, h_acceptors, (size_t)A * 3)) return 1;
-        if (hb_upload(&hb->d_dpar, h_dpar, (size_t)D * n_dpar)) return 1;
-        if (hb_upload(&hb->d_apar, h_apar, (size_t)A * n_apar)) return 1;
-        if (hb_upload(&hb->pass[0].d_ex_ptr, ptr0.data(), ptr0.size())) return 1;
-        if (hb_upload(&hb->pass[0].d_ex_col, col0.data(), col0.size())) return 1;
-        if (hb_upload(&hb->pass[1].d_ex_ptr, ptr1.data(), ptr1.size())) return 1;
-        if (hb_upload(&hb->pass[1].d_ex_col, col1.data(), col1.size())) return 1;
-        if (hb_upload(&hb->d_ref_ptr, ptr.data(), ptr.size())) return 1;
-        if (hb_upload(&hb->d_rec_src, src.data(), src.size())) return 1;
+        if (hb->prog.upload(ctx, false)) return 1;
+        if (amm_upload(&hb->d_tab, &tab, 1)) return 1;
+        if (amm_upload(&hb->d_donors, h_donors, (size_t)D * 3)) return 1;
+        if (amm_upload(&hb->d_acceptors, h_acceptors, (size_t)A * 3)) return 1;
+        if (amm_upload(&hb->d_dpar, h_dpar, (size_t)D * n_dpar)) return 1;
+        if (amm_upload(&hb->d_apar, h_apar, (size_t)A * n_apar)) return 1;
+        if (amm_upload(&hb->pass[0].d_ex_ptr, ptr0.data(), ptr0.size())) return 1;
+        if (amm_upload(&hb->pass[0].d_ex_col, col0.data(), col0.size())) return 1;
+        if (amm_upload(&hb->pass[1].d_ex_ptr, ptr1.data(), ptr1.size())) return 1;
+        if (amm_upload(&hb->pass[1].d_ex_col, col1.data(), col1.size())) return 1;
+        if (amm_upload(&hb->d_ref_ptr, ptr.data(), ptr.size())) return 1;
+        if (amm_upload(&hb->d_rec_src, src.data(), src.size())) return 1;
         const size_t park = std::max<size_t>(records * 9, 1), parts = std::max<size_t>((size_t)D * hb->pass[0].chunks, 1);
         AMM_HIP(hipMalloc(&hb->d_park, sizeof(double) * park));
         AMM_HIP(hipMemset(hb->d_park, 0, sizeof(double) * park));
@@ -542,14 +456,7 @@ int amm_hbond_create_impl(amm_ctx *ctx, const int32_t *code, int ncode, const do
 }
 
 int amm_hbond_set_globals_impl(amm_ctx *ctx, HbondForce *hb, const double *globals, int nglobal) {
-    if (nglobal != hb->h.nglobal || (nglobal > 0 && !globals)) {
-        amm_set_error("amm_hbond_set_globals: the program reads " + std::to_string(hb->h.nglobal) + " globals, " + std::to_string(nglobal) + " given");
-        return 1;
-    }
-    std::copy(globals, globals + nglobal, hb->h.globals);
-    AMM_HIP(hipStreamSynchronize(ctx->stream));     // ordered after any kernel already queued on the stream that reads the old values
-    AMM_HIP(hipMemcpy(hb->d->globals, hb->h.globals, sizeof(hb->h.globals), hipMemcpyHostToDevice));
-    return 0;
+    return hb->prog.set_globals(ctx, "amm_hbond_set_globals", globals, nglobal);
 }
 
 int amm_hbond_set_params_impl(amm_ctx *ctx, HbondForce *hb, const double *h_dpar, int n_donors, int n_dpar, const double *h_apar, int n_acceptors,
@@ -587,7 +494,7 @@ int amm_hbond_stats_impl(amm_ctx *ctx, HbondForce *hb, int64_t out[4]) {
 
 void amm_hbond_free(HbondForce *hb) {
     if (!hb) return;
-    for (void *p : {(void *)hb->d, (void *)hb->d_tab, (void *)hb->d_donors, (void *)hb->d_acceptors, (void *)hb->d_dpar, (void *)hb->d_apar,
+    for (void *p : {(void *)hb->prog.d, (void *)hb->d_tab, (void *)hb->d_donors, (void *)hb->d_acceptors, (void *)hb->d_dpar, (void *)hb->d_apar,
                     (void *)hb->pass[0].d_ex_ptr, (void *)hb->pass[0].d_ex_col, (void *)hb->pass[1].d_ex_ptr, (void *)hb->pass[1].d_ex_col,
                     (void *)hb->d_park, (void *)hb->d_epart, (void *)hb->d_count, (void *)hb->d_ref_ptr, (void *)hb->d_rec_src})
         if (p) (void)hipFree(p);

@@ -2,7 +2,7 @@
 // (AMM_FORCE_MANY_PARTICLE): every set {i, j, k} of distinct particles no pair of which is excluded and which lies inside the cutoff
 // contributes the text -- up to 16 geometric variables distance / angle / dihedral / raw coordinates over p1 p2 p3, per-particle
 // parameters suffixed with the role, global parameters -- compiled by atomsmm_amd/expr.py (compile_many_particle) into the program
-// of pair_expr_vm.h plus the variable table of compound.hip (slots 0 .. 2 = p1 p2 p3).  DESIGN.md 3.MP has the semantics.
+// of pair_expr_vm.h plus the variable table of expr_force.h (slots 0 .. 2 = p1 p2 p3).  DESIGN.md 3.MP has the semantics.
 //
 // Two launches per evaluation, one wavefront (a block of 64 lanes) per particle in both:
 //  k_many_neighbors  row i scans all columns 64 at a time -- j != i, inside the cutoff (the displacement taken as lower index minus
@@ -32,6 +32,7 @@
 #include "amm_ctx.h"
 #include "bonded_terms.h"
 #include "compound_geom.h"
+#include "device_utils.h"
 #include "term_expr_vm.h"
 
 #define AMM_MP_LANES 64
@@ -40,17 +41,11 @@
 #define AMM_MP_MAX_TYPES 16
 #define AMM_MP_MAX_PARAMS 2
 
-struct ManyTable {                      // CompoundTable's layout
-    int kind[AMM_COMPOUND_MAX_VARS];
-    int4 slot[AMM_COMPOUND_MAX_VARS];
-};
-
 struct ManyForce {
     int n = 0, n_vars = 0, n_par = 0, n_types = 1, periodic = 0, cutoff = 0, central = 0, capacity = 64;
     double rc = 0.0;
-    PairExprProg h;
-    PairExprProg *d = nullptr;
-    ManyTable *d_tab = nullptr;
+    ExprProgram prog;
+    VarTable *d_tab = nullptr;
     double *d_par = nullptr;            // [n_par][n]
     int *d_type = nullptr;              // [n] dense type indices
     int *d_perm = nullptr;              // [T][T][T] permutation code 0 .. 5 of the tuple's types, -1: the set is skipped
@@ -96,17 +91,6 @@ struct ManyArgs {
     Box box;
 };
 
-// is `col` in the sorted list ex_col[lo .. hi)?
-__device__ __forceinline__ bool mp_excluded(const int *__restrict__ ex_col, int lo, int hi, int col) {
-    const int end = hi;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (ex_col[mid] < col) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < end && ex_col[lo] == col;
-}
-
 // |x_a - x_b|^2 with a < b (lower index minus higher index: every wavefront that tests the pair tests the same number)
 __device__ __forceinline__ double mp_dist2(const double *__restrict__ pos, int a, int b, const Box &box, int periodic) {
 #pragma clang fp contract(off)
@@ -130,7 +114,7 @@ __global__ void __launch_bounds__(AMM_MP_LANES) k_many_neighbors(ManyArgs A) {
         const int col = j0 + lane;
         bool keep = col < A.n && col != i;
         if (keep && A.cutoff) keep = mp_dist2(A.pos, i, col, A.box, A.periodic) < A.rc2;
-        if (keep && ex_end > ex_begin) keep = !mp_excluded(A.ex_col, ex_begin, ex_end, col);
+        if (keep && ex_end > ex_begin) keep = !sorted_contains(A.ex_col, ex_begin, ex_end, col);
         const unsigned long long mask = __ballot(keep);
         const int at = count + __popcll(mask & ((1ull << lane) - 1ull));
         if (keep && at < A.capacity) row[at] = col;
@@ -155,7 +139,7 @@ __device__ __forceinline__ void mp_permute(int code, int t0, int t1, int t2, int
     p3 = mp_pick(e2, t0, t1, t2);
 }
 
-__global__ void __launch_bounds__(AMM_MP_LANES) k_many(ManyArgs A, const PairExprProg *__restrict__ prog, const ManyTable *__restrict__ tab) {
+__global__ void __launch_bounds__(AMM_MP_LANES) k_many(ManyArgs A, const PairExprProg *__restrict__ prog, const VarTable *__restrict__ tab) {
 #pragma clang fp contract(off)
     __shared__ int s_code[AMM_PEXPR_MAXCODE];
     __shared__ double s_consts[AMM_PEXPR_MAXCONST];
@@ -167,13 +151,8 @@ __global__ void __launch_bounds__(AMM_MP_LANES) k_many(ManyArgs A, const PairExp
     __shared__ int4 s_queue[2 * AMM_MP_LANES];                                      // (p1, p2, p3, owner's role | energy << 2) that wait
     const int lane = threadIdx.x;
     const int ncode = prog->ncode;
-    for (int k = lane; k < ncode; k += AMM_MP_LANES) s_code[k] = prog->code[k];
-    for (int k = lane; k < prog->nconst; k += AMM_MP_LANES) s_consts[k] = prog->consts[k];
-    for (int k = lane; k < prog->nglobal; k += AMM_MP_LANES) s_globals[k] = prog->globals[k];
-    if (lane < AMM_COMPOUND_MAX_VARS) {
-        s_kind[lane] = tab->kind[lane];
-        s_slot[lane] = tab->slot[lane];
-    }
+    pexpr_stage(prog, s_code, s_consts, s_globals);
+    var_table_stage(tab, s_kind, s_slot);
     __syncthreads();
     const int i = blockIdx.x;                   // (the grid is n)
     const int cap = A.capacity, T = A.n_types;
@@ -229,7 +208,7 @@ __global__ void __launch_bounds__(AMM_MP_LANES) k_many(ManyArgs A, const PairExp
                     if (!A.central && A.cutoff) keep = mp_dist2(A.pos, j, k, A.box, A.periodic) < A.rc2;
                     if (keep) {
                         const int lo = A.ex_ptr[j], hi = A.ex_ptr[j + 1];
-                        if (hi > lo) keep = !mp_excluded(A.ex_col, lo, hi, k);
+                        if (hi > lo) keep = !sorted_contains(A.ex_col, lo, hi, k);
                     }
                     if (keep) {
                         int t0, t1, t2;
@@ -257,7 +236,7 @@ __global__ void __launch_bounds__(AMM_MP_LANES) k_many(ManyArgs A, const PairExp
                 if (q < mc) {
                     const int k = A.nbr[(size_t)c * cap + (int)q];
                     keep = k != i;
-                    if (keep && ex_i1 > ex_i0) keep = !mp_excluded(A.ex_col, ex_i0, ex_i1, k);
+                    if (keep && ex_i1 > ex_i0) keep = !sorted_contains(A.ex_col, ex_i0, ex_i1, k);
                     if (keep) {
                         const int t1 = min(i, k), t2 = max(i, k);
                         const int code = A.perm[(A.type[c] * T + (i < k ? type_i : A.type[k])) * T + (i < k ? A.type[k] : type_i)];
@@ -316,7 +295,7 @@ __global__ void __launch_bounds__(AMM_MP_LANES) k_many(ManyArgs A, const PairExp
                     }
                     if (k < V) {
                         const double coef = -de / rr;       // (rr = 1 but for a distance)
-                        const int arity = kind <= AMM_CVAR_Z ? 1 : kind - 1;
+                        const int arity = cvar_arity(kind);
                         const bool o0 = sl.x == role, o1 = arity > 1 && sl.y == role, o2 = arity > 2 && sl.z == role, o3 = arity > 3 && sl.w == role;
                         if (o0) {
                             fx += coef * g0[0];
@@ -341,13 +320,7 @@ __global__ void __launch_bounds__(AMM_MP_LANES) k_many(ManyArgs A, const PairExp
                     }
                 }
             }
-            // what is left moves to the front
-            const int rest = qn - take;
-            const int4 moved = lane < rest ? s_queue[AMM_MP_LANES + lane] : make_int4(0, 0, 0, 0);
-            __syncthreads();
-            if (lane < rest) s_queue[lane] = moved;
-            __syncthreads();
-            qn = rest;
+            qn = queue_keep_rest(s_queue, qn, take);        // what is left moves to the front
         }
         if (last) break;
     }
@@ -359,16 +332,7 @@ __global__ void __launch_bounds__(AMM_MP_LANES) k_many(ManyArgs A, const PairExp
         n_sets += __shfl_xor(n_sets, off);
     }
     if (lane == 0) {
-        double *out = A.force + 3 * (size_t)i;
-        if (A.accumulate) {
-            out[0] += fx;
-            out[1] += fy;
-            out[2] += fz;
-        } else {
-            out[0] = fx;
-            out[1] = fy;
-            out[2] = fz;
-        }
+        store_force_row(A.force, i, fx, fy, fz, A.accumulate);
         A.epart[i] = e_sum;
         A.sets[i] = n_sets;
     }
@@ -378,15 +342,6 @@ __global__ void __launch_bounds__(AMM_MP_LANES) k_many(ManyArgs A, const PairExp
 __global__ void __launch_bounds__(256) k_many_zero(int n3, double *__restrict__ force) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t < n3) force[t] = 0.0;
-}
-
-static int mp_box_check(amm_ctx *ctx, const ManyForce *mf, const char *who) {
-    const double shortest = std::min(ctx->box.L[0], std::min(ctx->box.L[1], ctx->box.L[2]));
-    if (mf->rc > 0.5 * shortest) {
-        amm_set_error(std::string(who) + ": the cutoff " + std::to_string(mf->rc) + " exceeds half the shortest box edge (" + std::to_string(shortest) + ")");
-        return 1;
-    }
-    return 0;
 }
 
 int amm_many_eval_impl(amm_ctx *ctx, ManyForce *mf, const double *d_pos, double *d_force, int accumulate, double *d_energy) {
@@ -399,7 +354,7 @@ int amm_many_eval_impl(amm_ctx *ctx, ManyForce *mf, const double *d_pos, double 
         return 0;
     }
     // the box may have changed since creation (a barostat)
-    if (mf->periodic && mf->cutoff && mp_box_check(ctx, mf, "many-particle force (AMM_FORCE_MANY_PARTICLE)")) return 1;
+    if (mf->periodic && mf->cutoff && !amm_cutoff_fits_box(ctx, mf->rc, "many-particle force (AMM_FORCE_MANY_PARTICLE)")) return 1;
     ManyArgs A;
     A.n = n;
     A.n_vars = mf->n_vars;
@@ -426,7 +381,7 @@ int amm_many_eval_impl(amm_ctx *ctx, ManyForce *mf, const double *d_pos, double 
     A.box = ctx->box;
     hipLaunchKernelGGL(k_many_neighbors, dim3(n), dim3(AMM_MP_LANES), 0, ctx->stream, A);
     AMM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_many, dim3(n), dim3(AMM_MP_LANES), 0, ctx->stream, A, mf->d, mf->d_tab);
+    hipLaunchKernelGGL(k_many, dim3(n), dim3(AMM_MP_LANES), 0, ctx->stream, A, mf->prog.d, mf->d_tab);
     AMM_HIP(hipGetLastError());
     mf->launches += 2;
     mf->evaluated = true;
@@ -435,13 +390,6 @@ int amm_many_eval_impl(amm_ctx *ctx, ManyForce *mf, const double *d_pos, double 
 }
 
 // ---- host ----
-template <typename T>
-static int mp_upload(T **dst, const T *src, size_t count) {
-    AMM_HIP(hipMalloc(dst, sizeof(T) * std::max<size_t>(count, 1)));
-    if (count) AMM_HIP(hipMemcpy(*dst, src, sizeof(T) * count, hipMemcpyHostToDevice));
-    return 0;
-}
-
 // the types and the permutation table of a creation or an update; what names the caller
 static int mp_check_types(const char *who, int n, const int32_t *h_types, int n_types, const int32_t *h_perm, int central) {
     auto fail = [&](const std::string &what) {
@@ -480,15 +428,9 @@ int amm_many_create_impl(amm_ctx *ctx, const int32_t *code, int ncode, const dou
     if (n_params > 0 && n > 0 && !h_params) return fail("null parameter array");
     if (periodic && !(rc > 0.0)) return fail("CutoffPeriodic needs a cutoff distance above zero");
     if (periodic && !ctx->has_box) return fail("CutoffPeriodic, but the context has no periodic box");
-    for (int k = 0; k < n_vars; ++k) {
-        const int kind = var_kinds[k];
-        if (kind < AMM_CVAR_X || kind > AMM_CVAR_DIHEDRAL) return fail("variable " + std::to_string(k) + " has the kind " + std::to_string(kind));
-        const int arity = kind <= AMM_CVAR_Z ? 1 : kind - 1;
-        for (int r = 0; r < arity; ++r) {
-            const int s = var_slots[4 * k + r];
-            if (s < 0 || s >= 3) return fail("variable " + std::to_string(k) + " names slot " + std::to_string(s) + " beyond the set (3 slots: p1 p2 p3)");
-        }
-    }
+    VarTable tab;
+    if (var_table_fill("amm_many_create", var_kinds, var_slots, n_vars, 3, AMM_CVAR_X, "the kind ", "", "beyond the set (3 slots: p1 p2 p3)", tab, nullptr))
+        return 1;
     if (amm_expr_program_validate("amm_many_create", code, ncode, nconst, nglobal, n_vars, 3 * n_params)) return 1;
     if (mp_check_types("amm_many_create", n, h_types, n_types, h_perm, central)) return 1;
     std::vector<std::pair<int, int>> ex;
@@ -501,8 +443,6 @@ int amm_many_create_impl(amm_ctx *ctx, const int32_t *code, int ncode, const dou
         ex.push_back({a, b});
         ex.push_back({b, a});
     }
-    std::sort(ex.begin(), ex.end());
-    ex.erase(std::unique(ex.begin(), ex.end()), ex.end());
     AMM_HIP(hipSetDevice(ctx->device));
     ManyForce *mf = new ManyForce();
     mf->n = n;
@@ -514,37 +454,21 @@ int amm_many_create_impl(amm_ctx *ctx, const int32_t *code, int ncode, const dou
     mf->rc = rc > 0.0 ? rc : 0.0;
     mf->central = central ? 1 : 0;
     mf->capacity = mf->cutoff ? ctx->opt_many_capacity : std::max(64, (n - 1 + 63) / 64 * 64);
-    if (mf->periodic && mp_box_check(ctx, mf, "amm_many_create")) {
+    if (mf->periodic && !amm_cutoff_fits_box(ctx, mf->rc, "amm_many_create")) {
         delete mf;
         return 1;
     }
-    std::memset(&mf->h, 0, sizeof(mf->h));
-    mf->h.ncode = ncode;
-    mf->h.nconst = nconst;
-    mf->h.nglobal = nglobal;
-    std::copy(code, code + ncode, mf->h.code);
-    std::copy(consts, consts + nconst, mf->h.consts);
-    std::copy(globals, globals + nglobal, mf->h.globals);
-    ManyTable tab;
-    std::memset(&tab, 0, sizeof(tab));
-    for (int k = 0; k < n_vars; ++k) {
-        tab.kind[k] = var_kinds[k];
-        const int ar = var_kinds[k] <= AMM_CVAR_Z ? 1 : var_kinds[k] - 1;
-        tab.slot[k] = make_int4(var_slots[4 * k], ar > 1 ? var_slots[4 * k + 1] : 0, ar > 2 ? var_slots[4 * k + 2] : 0, ar > 3 ? var_slots[4 * k + 3] : 0);
-    }
-    std::vector<int> ptr(n + 1, 0), col(ex.size());
-    for (const auto &e : ex) ptr[e.first + 1]++;
-    for (int i = 0; i < n; ++i) ptr[i + 1] += ptr[i];
-    for (size_t e = 0; e < ex.size(); ++e) col[e] = ex[e].second;       // (ex is sorted by row, then by column)
+    mf->prog.fill(code, ncode, consts, nconst, globals, nglobal);
+    std::vector<int> ptr, col;
+    csr_of_pairs(n, ex, ptr, col);
     auto alloc = [&]() {
-        AMM_HIP(hipMalloc(&mf->d, sizeof(PairExprProg)));
-        AMM_HIP(hipMemcpy(mf->d, &mf->h, sizeof(PairExprProg), hipMemcpyHostToDevice));
-        if (mp_upload(&mf->d_tab, &tab, 1)) return 1;
-        if (mp_upload(&mf->d_par, h_params, (size_t)n * n_params)) return 1;
-        if (mp_upload(&mf->d_type, h_types, (size_t)n)) return 1;
-        if (mp_upload(&mf->d_perm, h_perm, (size_t)n_types * n_types * n_types)) return 1;
-        if (mp_upload(&mf->d_ex_ptr, ptr.data(), ptr.size())) return 1;
-        if (mp_upload(&mf->d_ex_col, col.data(), col.size())) return 1;
+        if (mf->prog.upload(ctx, false)) return 1;
+        if (amm_upload(&mf->d_tab, &tab, 1)) return 1;
+        if (amm_upload(&mf->d_par, h_params, (size_t)n * n_params)) return 1;
+        if (amm_upload(&mf->d_type, h_types, (size_t)n)) return 1;
+        if (amm_upload(&mf->d_perm, h_perm, (size_t)n_types * n_types * n_types)) return 1;
+        if (amm_upload(&mf->d_ex_ptr, ptr.data(), ptr.size())) return 1;
+        if (amm_upload(&mf->d_ex_col, col.data(), col.size())) return 1;
         const size_t rows = std::max<size_t>(n, 1);
         AMM_HIP(hipMalloc(&mf->d_nbr, sizeof(int) * rows * mf->capacity));
         AMM_HIP(hipMemset(mf->d_nbr, 0, sizeof(int) * rows * mf->capacity));
@@ -567,14 +491,7 @@ int amm_many_create_impl(amm_ctx *ctx, const int32_t *code, int ncode, const dou
 }
 
 int amm_many_set_globals_impl(amm_ctx *ctx, ManyForce *mf, const double *globals, int nglobal) {
-    if (nglobal != mf->h.nglobal || (nglobal > 0 && !globals)) {
-        amm_set_error("amm_many_set_globals: the program reads " + std::to_string(mf->h.nglobal) + " globals, " + std::to_string(nglobal) + " given");
-        return 1;
-    }
-    std::copy(globals, globals + nglobal, mf->h.globals);
-    AMM_HIP(hipStreamSynchronize(ctx->stream));     // ordered after any kernel already queued on the stream that reads the old values
-    AMM_HIP(hipMemcpy(mf->d->globals, mf->h.globals, sizeof(mf->h.globals), hipMemcpyHostToDevice));
-    return 0;
+    return mf->prog.set_globals(ctx, "amm_many_set_globals", globals, nglobal);
 }
 
 int amm_many_set_params_impl(amm_ctx *ctx, ManyForce *mf, const double *h_params, int n_particles, int n_params, const int32_t *h_types, int n_types,
@@ -592,7 +509,7 @@ int amm_many_set_params_impl(amm_ctx *ctx, ManyForce *mf, const double *h_params
     const size_t cells = (size_t)n_types * n_types * n_types;
     if (n_types != mf->n_types) {           // another number of types: the table has another size
         int *fresh = nullptr;
-        if (mp_upload(&fresh, h_perm, cells)) return 1;
+        if (amm_upload(&fresh, h_perm, cells)) return 1;
         (void)hipFree(mf->d_perm);
         mf->d_perm = fresh;
         mf->n_types = n_types;
@@ -638,7 +555,7 @@ int amm_many_overflow(ManyForce *mf, int *need, int *capacity) {
 
 void amm_many_free(ManyForce *mf) {
     if (!mf) return;
-    for (void *p : {(void *)mf->d, (void *)mf->d_tab, (void *)mf->d_par, (void *)mf->d_type, (void *)mf->d_perm, (void *)mf->d_ex_ptr,
+    for (void *p : {(void *)mf->prog.d, (void *)mf->d_tab, (void *)mf->d_par, (void *)mf->d_type, (void *)mf->d_perm, (void *)mf->d_ex_ptr,
                     (void *)mf->d_ex_col, (void *)mf->d_nbr, (void *)mf->d_nbr_count, (void *)mf->d_flag, (void *)mf->d_epart, (void *)mf->d_sets})
         if (p) (void)hipFree(p);
     delete mf;

@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "amm_ctx.h"
+#include "device_utils.h"
 #include "pair_args.h"
 #include "pair_math.h"
 #include "pair_expr_vm.h"
@@ -33,9 +34,7 @@ __global__ void __launch_bounds__(256) k_pair_expr(PairArgs A, const PairExprPro
     __shared__ double s_globals[AMM_PEXPR_MAXGLOBAL];
     __shared__ double2 s_stack[(AMM_PEXPR_STACK - 1) * AMM_PEXPR_STRIDE];      // all but the top of every lane's stack
     const int ncode = prog->ncode;
-    for (int k = threadIdx.x; k < ncode; k += blockDim.x) s_code[k] = prog->code[k];
-    for (int k = threadIdx.x; k < prog->nconst; k += blockDim.x) s_consts[k] = prog->consts[k];
-    for (int k = threadIdx.x; k < prog->nglobal; k += blockDim.x) s_globals[k] = prog->globals[k];
+    pexpr_stage(prog, s_code, s_consts, s_globals);
     __syncthreads();
     const int lpa = 1 << A.lpa_shift;
     const int tid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -100,18 +99,12 @@ __global__ void __launch_bounds__(256) k_pair_expr(PairArgs A, const PairExprPro
             A.force[3 * i + 2] = fz;
         }
     }
-    if (EN) {
-        __shared__ double red[4];
-        for (int off = 32; off > 0; off >>= 1) esum += __shfl_xor(esum, off);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = esum;
-        __syncthreads();
-        if (threadIdx.x == 0) A.epart[blockIdx.x] = 0.5 * (((red[0] + red[1]) + red[2]) + red[3]);
-    }
+    if (EN) block_energy_store_256(esum, A.epart, 0.5);
 }
 
 // the launch of amm_pair_eval_impl for a force of family AMM_PAIR_EXPR (grid: one lane group per row of the slice, as k_pair_nlist)
 int amm_pair_expr_launch(amm_ctx *ctx, PairForce *pf, const PairArgs &A, dim3 grid, bool en) {
-    if (!pf->expr || !pf->expr->d) {
+    if (!pf->expr || !pf->expr->prog.d) {
         amm_set_error("pair-expression force (AMM_PAIR_EXPR) without a program");
         return 1;
     }
@@ -128,7 +121,7 @@ int amm_pair_expr_launch(amm_ctx *ctx, PairForce *pf, const PairArgs &A, dim3 gr
     const int use_switch = (c.flags & AMM_SWITCH) ? 1 : 0;
     const double inv_sw_dr = use_switch ? 1.0 / (c.rc - c.rswitch) : 0.0;
 #define AMM_PEXPR_LAUNCH(EN, TAB) \
-    hipLaunchKernelGGL((k_pair_expr<EN, TAB>), grid, dim3(256), 0, ctx->stream, A, pf->expr->d, tabs, c.rc2, c.rswitch, inv_sw_dr, use_switch, c.sign)
+    hipLaunchKernelGGL((k_pair_expr<EN, TAB>), grid, dim3(256), 0, ctx->stream, A, pf->expr->prog.d, tabs, c.rc2, c.rswitch, inv_sw_dr, use_switch, c.sign)
     if (tabs) {
         if (en) AMM_PEXPR_LAUNCH(true, true);
         else AMM_PEXPR_LAUNCH(false, true);
@@ -140,7 +133,7 @@ int amm_pair_expr_launch(amm_ctx *ctx, PairForce *pf, const PairArgs &A, dim3 gr
     return 0;
 }
 
-// ---- host: program checks, upload ----
+// ---- host: program checks ----
 int amm_pair_expr_validate(const int32_t *code, int ncode, int nconst, int nglobal) {
     return amm_expr_program_validate("amm_pair_expr_create", code, ncode, nconst, nglobal, -1, 0);
 }
@@ -183,15 +176,6 @@ int amm_expr_program_validate(const char *who, const int32_t *code, int ncode, i
     return 0;
 }
 
-int amm_pair_expr_upload(amm_ctx *ctx, PairExpr *px, bool globals_only) {
-    // ordered after any kernel already queued on the stream that reads the old program
-    AMM_HIP(hipStreamSynchronize(ctx->stream));
-    if (!px->d) AMM_HIP(hipMalloc(&px->d, sizeof(PairExprProg)));
-    if (globals_only) AMM_HIP(hipMemcpy(px->d->globals, px->h.globals, sizeof(px->h.globals), hipMemcpyHostToDevice));
-    else AMM_HIP(hipMemcpy(px->d, &px->h, sizeof(PairExprProg), hipMemcpyHostToDevice));
-    return 0;
-}
-
 // ---- host: tabulated functions ----
 static const char *table_word_name(int op) { return op == X_TAB_C1 ? "TAB_C1 (55)" : (op == X_TAB_D1 ? "TAB_D1 (56)" : "TAB_D2 (57)"); }
 static const char *table_kind_name(int kind) {
@@ -204,8 +188,8 @@ static size_t table_doubles(int kind, int nx, int ny) {
 
 void amm_pair_expr_scan_tables(PairExpr *px) {
     px->uses_tables = false;
-    for (int pc = 0; pc < px->h.ncode; ++pc) {
-        const int op = px->h.code[pc] & 0xff;
+    for (int pc = 0; pc < px->prog.h.ncode; ++pc) {
+        const int op = px->prog.h.code[pc] & 0xff;
         if (op == X_TAB_C1 || op == X_TAB_D1 || op == X_TAB_D2) px->uses_tables = true;
     }
 }
@@ -245,8 +229,8 @@ int amm_pair_expr_tables(amm_ctx *ctx, PairExpr *px, int n_tables, const int32_t
         total += (need + 3) & ~(size_t)3;
     }
     // every table word of the program finds a table of its kind (the kind says how many arguments the word takes)
-    for (int pc = 0; pc < px->h.ncode; ++pc) {
-        const int op = px->h.code[pc] & 0xff, arg = px->h.code[pc] >> 8;
+    for (int pc = 0; pc < px->prog.h.ncode; ++pc) {
+        const int op = px->prog.h.code[pc] & 0xff, arg = px->prog.h.code[pc] >> 8;
         if (op != X_TAB_C1 && op != X_TAB_D1 && op != X_TAB_D2) continue;
         if (arg < 0 || arg >= n_tables) return fail(std::string("word ") + table_word_name(op) + " reads table " + std::to_string(arg) + ": " + std::to_string(n_tables) + " given");
         const int want = op == X_TAB_C1 ? AMM_TABLE_CONTINUOUS1D : (op == X_TAB_D1 ? AMM_TABLE_DISCRETE1D : AMM_TABLE_DISCRETE2D);
@@ -277,7 +261,7 @@ int amm_pair_expr_tables(amm_ctx *ctx, PairExpr *px, int n_tables, const int32_t
 
 void amm_pair_expr_free(PairExpr *px) {
     if (!px) return;
-    if (px->d) (void)hipFree(px->d);
+    px->prog.release();
     if (px->d_tabs) (void)hipFree(px->d_tabs);
     delete px;
 }

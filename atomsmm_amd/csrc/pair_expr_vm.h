@@ -14,11 +14,9 @@
 // ones have derivative 0.  The tables live in ONE device allocation -- AMM_PEXPR_MAXTABLES descriptors, then the doubles -- read from
 // global memory (every lane reads the same few lines: L2), so the LDS of a block is what it was without them.
 #pragma once
+#include "expr_force.h"        // PairExprProg and its limits, the program holder
 #include "expr_vm.h"
 
-#define AMM_PEXPR_MAXCODE 256
-#define AMM_PEXPR_MAXCONST 48
-#define AMM_PEXPR_MAXGLOBAL 48
 #define AMM_PEXPR_STACK 16
 #define AMM_PEXPR_LOCALS 16
 #define AMM_PEXPR_PARAMS 3          // per-particle doubles a neighbour row carries per atom (charge slot, two Lennard-Jones slots)
@@ -32,14 +30,6 @@ enum { X_TERM_VAR = 53, X_TERM_P = 54 };
 // ... and the tabulated functions of a pair expression: table `arg` at the top of the stack (X_TAB_D2: at the two topmost, x below y)
 enum { X_TAB_C1 = 55, X_TAB_D1 = 56, X_TAB_D2 = 57 };
 
-// the compiled text as the device holds it: staged into LDS once per block
-struct PairExprProg {
-    int ncode, nconst, nglobal, pad_;
-    int code[AMM_PEXPR_MAXCODE];            // opcode | arg << 8
-    double consts[AMM_PEXPR_MAXCONST];
-    double globals[AMM_PEXPR_MAXGLOBAL];
-};
-
 // One tabulated function as the device reads it.  kind: AMM_TABLE_* (atomsmm_hip.h).  Continuous: nx knots lo .. hi at spacing h, data =
 // nx - 1 records (a, b, c, d) of the interval's cubic a + u (b + u (c + u d)), u = t - knot; discrete: data = nx (* ny) values,
 // values[i + nx * j].  off: where the table's doubles begin behind the descriptors (a multiple of 4: records are 32-byte aligned).
@@ -50,8 +40,7 @@ struct PairTableDesc {
 
 // host side of a generic pair force (PairForce::expr)
 struct PairExpr {
-    PairExprProg h;
-    PairExprProg *d = nullptr;
+    ExprProgram prog;
     bool uses_tables = false;                   // the program has X_TAB_* words: no launch before amm_pair_expr_set_tables
     int n_tables = 0;
     PairTableDesc tabs[AMM_PEXPR_MAXTABLES];    // as uploaded (a re-upload keeps kinds and sizes)

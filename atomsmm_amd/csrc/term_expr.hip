@@ -24,6 +24,7 @@
 
 #include "amm_ctx.h"
 #include "bonded_terms.h"
+#include "device_utils.h"
 #include "term_expr_vm.h"
 
 struct TermArgs {
@@ -44,9 +45,7 @@ __global__ void __launch_bounds__(256) k_term_expr(TermArgs A, const PairExprPro
     __shared__ double s_globals[AMM_PEXPR_MAXGLOBAL];
     __shared__ double2 s_stack[(AMM_PEXPR_STACK - 1) * AMM_PEXPR_STRIDE];      // all but the top of every lane's stack
     const int ncode = prog->ncode;
-    for (int k = threadIdx.x; k < ncode; k += blockDim.x) s_code[k] = prog->code[k];
-    for (int k = threadIdx.x; k < prog->nconst; k += blockDim.x) s_consts[k] = prog->consts[k];
-    for (int k = threadIdx.x; k < prog->nglobal; k += blockDim.x) s_globals[k] = prog->globals[k];
+    pexpr_stage(prog, s_code, s_consts, s_globals);
     __syncthreads();
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     double e = 0.0;
@@ -134,13 +133,7 @@ __global__ void __launch_bounds__(256) k_term_expr(TermArgs A, const PairExprPro
             out[2] = -dz;
         }
     }
-    if (EN) {
-        __shared__ double red[4];
-        for (int off = 32; off > 0; off >>= 1) e += __shfl_xor(e, off);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = e;
-        __syncthreads();
-        if (threadIdx.x == 0) A.epart[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-    }
+    if (EN) block_energy_store_256(e, A.epart);
 }
 
 // one lane per atom: its records, in record order (k_terms_gather's loop: four records in flight)
@@ -166,7 +159,7 @@ __global__ void __launch_bounds__(256) k_term_expr_gather(int n, const int *__re
                 for (int x = 0; x < 3; ++x) f[x] += g[u][x];
             }
     }
-    if (accumulate) {
+    if (accumulate) {        // (not store_force_row of device_utils.h: this gather keeps the parent's instructions, profiles/expr_kit_cost.txt)
         force[3 * i] += f[0]; force[3 * i + 1] += f[1]; force[3 * i + 2] += f[2];
     } else {
         force[3 * i] = f[0]; force[3 * i + 1] = f[1]; force[3 * i + 2] = f[2];
@@ -175,8 +168,8 @@ __global__ void __launch_bounds__(256) k_term_expr_gather(int n, const int *__re
 
 template <int KIND>
 static void launch_terms(amm_ctx *ctx, TermExprForce *tf, const TermArgs &A, bool en) {
-    if (en) hipLaunchKernelGGL((k_term_expr<KIND, true>), dim3(tf->n_blocks), dim3(256), 0, ctx->stream, A, tf->d);
-    else hipLaunchKernelGGL((k_term_expr<KIND, false>), dim3(tf->n_blocks), dim3(256), 0, ctx->stream, A, tf->d);
+    if (en) hipLaunchKernelGGL((k_term_expr<KIND, true>), dim3(tf->n_blocks), dim3(256), 0, ctx->stream, A, tf->prog.d);
+    else hipLaunchKernelGGL((k_term_expr<KIND, false>), dim3(tf->n_blocks), dim3(256), 0, ctx->stream, A, tf->prog.d);
 }
 
 int amm_term_expr_eval_impl(amm_ctx *ctx, TermExprForce *tf, const double *d_pos, double *d_force, int accumulate, double *d_energy) {
@@ -218,16 +211,15 @@ int amm_term_expr_build(amm_ctx *ctx, TermExprForce *tf, const int32_t *h_idx, c
     tf->arity = ar;
     tf->n_blocks = std::max(1, (nt + 255) / 256);
     std::vector<int4> atoms(nt);
-    std::vector<int> ptr(n + 1, 0), src((size_t)nt * ar);
     for (int t = 0; t < nt; ++t) {
         const int32_t *ix = h_idx + (size_t)t * 4;
         atoms[t] = make_int4(ix[0], ar > 1 ? ix[1] : -1, ar > 2 ? ix[2] : -1, ar > 3 ? ix[3] : -1);
-        for (int r = 0; r < ar; ++r) ptr[ix[r] + 1]++;
     }
-    for (int i = 0; i < n; ++i) ptr[i + 1] += ptr[i];
-    std::vector<int> fill(ptr.begin(), ptr.end() - 1);
-    for (int t = 0; t < nt; ++t)                   // term order, role order: the records of an atom come out in that order
-        for (int r = 0; r < ar; ++r) src[fill[h_idx[(size_t)t * 4 + r]]++] = t * 4 + r;
+    std::vector<int> ptr, src;
+    csr_of_records(n, [&](auto &&visit) {           // term order, role order: the records of an atom come out in that order
+        for (int t = 0; t < nt; ++t)
+            for (int r = 0; r < ar; ++r) visit(h_idx[(size_t)t * 4 + r], t * 4 + r);
+    }, ptr, src);
     AMM_HIP(hipMalloc(&tf->d_atoms, sizeof(int4) * std::max(nt, 1)));
     AMM_HIP(hipMalloc(&tf->d_params, sizeof(double) * std::max<size_t>((size_t)nt * tf->n_params, 1)));
     AMM_HIP(hipMalloc(&tf->d_ref_ptr, sizeof(int) * (n + 1)));
@@ -239,7 +231,7 @@ int amm_term_expr_build(amm_ctx *ctx, TermExprForce *tf, const int32_t *h_idx, c
     AMM_HIP(hipMemcpy(tf->d_ref_ptr, ptr.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice));
     if (!src.empty()) AMM_HIP(hipMemcpy(tf->d_rec_src, src.data(), sizeof(int) * src.size(), hipMemcpyHostToDevice));
     if (amm_term_expr_upload_params(ctx, tf, h_params)) return 1;
-    return amm_term_expr_upload(ctx, tf, false);
+    return tf->prog.upload(ctx, false);
 }
 
 int amm_term_expr_upload_params(amm_ctx *ctx, TermExprForce *tf, const double *h_params) {
@@ -250,17 +242,9 @@ int amm_term_expr_upload_params(amm_ctx *ctx, TermExprForce *tf, const double *h
     return 0;
 }
 
-int amm_term_expr_upload(amm_ctx *ctx, TermExprForce *tf, bool globals_only) {
-    AMM_HIP(hipStreamSynchronize(ctx->stream));
-    if (!tf->d) AMM_HIP(hipMalloc(&tf->d, sizeof(PairExprProg)));
-    if (globals_only) AMM_HIP(hipMemcpy(tf->d->globals, tf->h.globals, sizeof(tf->h.globals), hipMemcpyHostToDevice));
-    else AMM_HIP(hipMemcpy(tf->d, &tf->h, sizeof(PairExprProg), hipMemcpyHostToDevice));
-    return 0;
-}
-
 void amm_term_expr_free(TermExprForce *tf) {
     if (!tf) return;
-    for (void *p : {(void *)tf->d, (void *)tf->d_atoms, (void *)tf->d_params, (void *)tf->d_ref_ptr, (void *)tf->d_rec_src, (void *)tf->d_tf,
+    for (void *p : {(void *)tf->prog.d, (void *)tf->d_atoms, (void *)tf->d_params, (void *)tf->d_ref_ptr, (void *)tf->d_rec_src, (void *)tf->d_tf,
                     (void *)tf->d_epart})
         if (p) (void)hipFree(p);
     delete tf;

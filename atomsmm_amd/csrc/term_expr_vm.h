@@ -13,8 +13,7 @@
 struct TermExprForce {
     int kind = 0, periodic = 0;
     int n_terms = 0, n_params = 0, arity = 0;
-    PairExprProg h;                 // the program: same layout and limits as a pair expression's
-    PairExprProg *d = nullptr;
+    ExprProgram prog;               // the program: same layout and limits as a pair expression's
     int4 *d_atoms = nullptr;        // [n_terms] atoms of the term (-1 padded)
     double *d_params = nullptr;     // [n_params][n_terms]
     int *d_ref_ptr = nullptr;       // [n + 1] CSR per atom of its (term, role) records ...
