@@ -64,6 +64,7 @@ EXPORTS = [
     'amm_custom_gb_release',
     'amm_hbond_create', 'amm_hbond_set_params', 'amm_hbond_set_globals', 'amm_hbond_stats', 'amm_hbond_release',
     'amm_many_create', 'amm_many_set_params', 'amm_many_set_globals', 'amm_many_stats', 'amm_many_release',
+    'amm_rmsd_create', 'amm_rmsd_set_reference', 'amm_rmsd_stats', 'amm_rmsd_release',
     'amm_vsite_define', 'amm_vsite_place', 'amm_vsite_spread', 'amm_vsite_stats',
 ]
 
@@ -222,6 +223,10 @@ def lib():
         L.amm_many_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
         L.amm_many_stats.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
         L.amm_many_release.argtypes = [vp, C.c_int32]
+        L.amm_rmsd_create.argtypes = [vp, ip, C.c_int32, dp, ip]
+        L.amm_rmsd_set_reference.argtypes = [vp, C.c_int32, ip, C.c_int32, dp]
+        L.amm_rmsd_stats.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
+        L.amm_rmsd_release.argtypes = [vp, C.c_int32]
         L.amm_cv_create.argtypes = [vp, ip, C.c_int32, C.c_int32, ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip]
         L.amm_cv_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
         L.amm_cv_set_variables.argtypes = [vp, C.c_int32, dp, C.c_int32]
@@ -770,6 +775,31 @@ class HipContext:
     def many_release(self, fid):
         """Free a many-particle force (its id is retired)."""
         _chk(lib().amm_many_release(self.h, fid))
+
+    def rmsd_create(self, particles, reference):
+        """An RMSD force (csrc/rmsd.hip): the selected particles and the reference rows of THOSE particles, [len(particles)][3] in nm,
+        in the list's order; the library centres them."""
+        p_, pp = _hi(np.asarray(particles, dtype=np.int32).reshape(-1) if len(particles) else [0])
+        r_, rp = _hd(np.asarray(reference, dtype=np.float64).reshape(-1, 3) if len(particles) else [0.0])
+        fid = C.c_int32(-1)
+        _chk(lib().amm_rmsd_create(self.h, pp, len(particles), rp, C.byref(fid)))
+        return fid.value
+
+    def rmsd_set_reference(self, fid, particles, reference):
+        """New particles and / or a new reference, laid out as at creation; their number may change (waits for the stream)."""
+        p_, pp = _hi(np.asarray(particles, dtype=np.int32).reshape(-1) if len(particles) else [0])
+        r_, rp = _hd(np.asarray(reference, dtype=np.float64).reshape(-1, 3) if len(particles) else [0.0])
+        _chk(lib().amm_rmsd_set_reference(self.h, fid, pp, len(particles), rp))
+
+    def rmsd_stats(self, fid):
+        """dict(particles, blocks, launches_per_eval, launches): the path the force takes (1 block: one launch; else three)."""
+        out = (C.c_int64 * 4)()
+        _chk(lib().amm_rmsd_stats(self.h, fid, out))
+        return dict(particles=int(out[0]), blocks=int(out[1]), launches_per_eval=int(out[2]), launches=int(out[3]))
+
+    def rmsd_release(self, fid):
+        """Free an RMSD force (its id is retired)."""
+        _chk(lib().amm_rmsd_release(self.h, fid))
 
     def cv_create(self, inner_ids, n_deriv, code, consts, globals_):
         """A CustomCVForce with any energy text (csrc/cv.hip): the ids of the inner forces in the order of the collective variables

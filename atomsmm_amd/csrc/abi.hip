@@ -1531,6 +1531,13 @@ int amm_set_option(amm_ctx *ctx, const char *name, double value) {
         }
         ctx->opt_many_capacity = v;
     }
+    else if (k == "rmsd_blocks") {
+        if (v < 0 || v > 1024) {
+            amm_set_error("amm_set_option: rmsd_blocks is 0 (chosen from the selection's size), 1 (the single block) or 2 .. 1024 blocks");
+            return 1;
+        }
+        ctx->opt_rmsd_blocks = v;
+    }
     else {
         amm_set_error("amm_set_option: unknown option '" + k + "'");
         return 1;

@@ -260,13 +260,14 @@ struct CmapForce;     // cmap.hip: a CMAPTorsionForce -- bicubic maps over pairs
 struct CustomGbForce; // custom_gb.hip: a CustomGBForce -- computed per-particle values and energy terms written as text, free space only
 struct HbondForce;    // hbond.hip: a CustomHbondForce -- donors against acceptors over all pairs, the energy written as text
 struct ManyForce;     // manyparticle.hip: a CustomManyParticleForce -- sets of three particles under a cutoff, the energy written as text
+struct RmsdForce;     // rmsd.hip: an RMSDForce -- the deviation of selected particles from a reference after the best rigid fit
 // The force families.  A family is described ONCE: its tag here, the struct that goes with the tag in amm_force_type, and its row of
 // the table behind amm_family (families.hip).  The typed lookup and its refusals, amm_force_eval_dispatch, release, amm_destroy, amm_set_slice and
 // cv.hip's messages all read the row -- a new family adds these three lines, its own .hip file and its extern "C" entry points.
-// Eleven families today (and the tag of a released id).
+// Twelve families today (and the tag of a released id).
 enum : int { AMM_FORCE_RELEASED = 0, AMM_FORCE_PAIR = 1, AMM_FORCE_BONDED = 2, AMM_FORCE_PME = 3, AMM_FORCE_TERM_EXPR = 4, AMM_FORCE_CV = 5,
              AMM_FORCE_COMPOUND = 6, AMM_FORCE_GB = 7, AMM_FORCE_CMAP = 8, AMM_FORCE_CUSTOM_GB = 9, AMM_FORCE_HBOND = 10,
-             AMM_FORCE_MANY_PARTICLE = 11, AMM_FORCE_TYPES = 12 };   // ForceObj::type, the row amm_family returns
+             AMM_FORCE_MANY_PARTICLE = 11, AMM_FORCE_RMSD = 12, AMM_FORCE_TYPES = 13 };   // ForceObj::type, the row amm_family returns
 template <class T> inline constexpr int amm_force_type = -1;
 template <> inline constexpr int amm_force_type<PairForce> = AMM_FORCE_PAIR;
 template <> inline constexpr int amm_force_type<BondedSet> = AMM_FORCE_BONDED;
@@ -279,6 +280,7 @@ template <> inline constexpr int amm_force_type<CmapForce> = AMM_FORCE_CMAP;
 template <> inline constexpr int amm_force_type<CustomGbForce> = AMM_FORCE_CUSTOM_GB;
 template <> inline constexpr int amm_force_type<HbondForce> = AMM_FORCE_HBOND;
 template <> inline constexpr int amm_force_type<ManyForce> = AMM_FORCE_MANY_PARTICLE;
+template <> inline constexpr int amm_force_type<RmsdForce> = AMM_FORCE_RMSD;
 struct ForceFamily {
     const char *noun, *tag, *prefix;   // "a CMAP force", "AMM_FORCE_CMAP", "amm_cmap_*"
     const char *bad_id;                // what the family's entry points say of an id that is not theirs (behind "<entry point>: " if they name themselves)
@@ -445,6 +447,7 @@ struct amm_ctx {
     int opt_hbond_chunks = 0;           // column chunks per row of a hydrogen-bond force created from now on (hbond.hip): 0 = chosen from the row count
     int opt_hbond_compact = 1;          // ... and whether its survivors queue up for the interpreter (0: drained batch by batch -- a measurement)
     int opt_many_capacity = 256;        // neighbours a row of a many-particle force with a cutoff created from now on can hold (manyparticle.hip): a multiple of 64
+    int opt_rmsd_blocks = 0;            // blocks of an RMSD force created from now on (rmsd.hip): 0 = chosen from the selection's size, 1 = the single block, 2 .. 1024
     ListWatch watched[AMM_MAX_WATCH];
     int n_watched = 0;
     int device = 0;
@@ -655,6 +658,12 @@ int amm_many_eval_impl(amm_ctx *ctx, ManyForce *mf, const double *d_pos, double 
 int amm_many_stats_impl(amm_ctx *ctx, ManyForce *mf, int64_t out[5]);
 int amm_many_overflow(ManyForce *mf, int *need, int *capacity);   // amm_check: 1 when a neighbour row overflowed, 0 when none did, -1 on a HIP error
 void amm_many_free(ManyForce *mf);
+// rmsd.hip: a force of type AMM_FORCE_RMSD (h_ref: the reference rows of the listed particles, in the list's order)
+int amm_rmsd_create_impl(amm_ctx *ctx, const int32_t *h_particles, int n_sel, const double *h_ref, RmsdForce **out);
+int amm_rmsd_set_reference_impl(amm_ctx *ctx, RmsdForce *rf, const int32_t *h_particles, int n_sel, const double *h_ref);
+int amm_rmsd_eval_impl(amm_ctx *ctx, RmsdForce *rf, const double *d_pos, double *d_force, int accumulate, double *d_energy);
+int amm_rmsd_stats_impl(RmsdForce *rf, int64_t out[4]);
+void amm_rmsd_free(RmsdForce *rf);
 // implemented in pair.hip / cells.hip / bonded.hip / integrate.hip
 int amm_pair_build_consts(const amm_pair_desc &d, PairConsts &pc);
 int amm_pair_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double *d_force, int accumulate,

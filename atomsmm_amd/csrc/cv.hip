@@ -114,9 +114,9 @@ static int cv_check_inner(amm_ctx *ctx, const int32_t *inner, int n_cv, const ch
             return 1;
         }
         const int type = ctx->forces[id].type;
-        if (type != AMM_FORCE_BONDED && type != AMM_FORCE_TERM_EXPR && type != AMM_FORCE_COMPOUND) {
+        if (type != AMM_FORCE_BONDED && type != AMM_FORCE_TERM_EXPR && type != AMM_FORCE_COMPOUND && type != AMM_FORCE_RMSD) {
             amm_set_error(std::string(who) + ": inner force " + std::to_string(k) + " (id " + std::to_string(id) + ") is " + amm_family(type).noun +
-                          " (" + amm_family(type).tag + "): a collective variable is the energy of a bond-list set, of a term-expression force or of a compound-bond force");
+                          " (" + amm_family(type).tag + "): a collective variable is the energy of a bond-list set, of a term-expression force, of a compound-bond force or of an RMSD force");
             return 1;
         }
     }

@@ -1,7 +1,7 @@
 // atomsmm_amd/csrc/families.hip -- the table of force families (amm_ctx.h: ForceFamily) and everything derived from it: the typed lookup
 // with its refusals, registration, release and the dispatch of an evaluation; then the extern "C" entry points of the families whose
 // implementation is a .hip file of its own (term expressions, collective variables, compound bonds, generalized Born, CMAP, custom
-// generalized Born, hydrogen bonds, many-particle sets).
+// generalized Born, hydrogen bonds, many-particle sets, RMSD).
 #include <algorithm>
 #include <cstring>
 
@@ -22,7 +22,7 @@ static int released_eval(amm_ctx *, void *, const double *, double *, int, doubl
 }
 static void released_free(void *) {}
 
-// One row per AMM_FORCE_* value (a released id and the eleven families), in the enum's order: noun phrase, tag, entry points, bad-id wording, single rank, eval, free.
+// One row per AMM_FORCE_* value (a released id and the twelve families), in the enum's order: noun phrase, tag, entry points, bad-id wording, single rank, eval, free.
 const ForceFamily &amm_family(int type) {
     static const ForceFamily rows[AMM_FORCE_TYPES] = {
         {"a released id", "AMM_FORCE_RELEASED", "none", "released force id", false, released_eval, released_free},
@@ -49,6 +49,8 @@ const ForceFamily &amm_family(int type) {
          eval_as<HbondForce, amm_hbond_eval_impl>, free_as<HbondForce, amm_hbond_free>},
         {"a many-particle force", "AMM_FORCE_MANY_PARTICLE", "amm_many_*", "not the id of a many-particle force (AMM_FORCE_MANY_PARTICLE)", true,
          eval_as<ManyForce, amm_many_eval_impl>, free_as<ManyForce, amm_many_free>},
+        {"an RMSD force", "AMM_FORCE_RMSD", "amm_rmsd_*", "not the id of an RMSD force (AMM_FORCE_RMSD)", true,
+         eval_as<RmsdForce, amm_rmsd_eval_impl>, free_as<RmsdForce, amm_rmsd_free>},
     };
     return rows[type];
 }
@@ -426,5 +428,39 @@ int amm_many_stats(amm_ctx *ctx, int32_t force_id, int64_t *out) {
 }
 
 int amm_many_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_MANY_PARTICLE, "amm_many_release"); }
+
+// RMSDForce (csrc/rmsd.hip): the selected particles and the reference rows of those particles, in the list's order
+int amm_rmsd_create(amm_ctx *ctx, const int32_t *h_particles, int32_t n_sel, const double *h_ref, int32_t *force_id) {
+    if (!ctx || !force_id || (n_sel > 0 && (!h_particles || !h_ref))) {
+        amm_set_error("amm_rmsd_create: null argument");
+        return 1;
+    }
+    RmsdForce *rf = nullptr;
+    if (amm_rmsd_create_impl(ctx, h_particles, n_sel, h_ref, &rf)) return 1;
+    *force_id = amm_force_register(ctx, AMM_FORCE_RMSD, rf);
+    return 0;
+}
+
+int amm_rmsd_set_reference(amm_ctx *ctx, int32_t force_id, const int32_t *h_particles, int32_t n_sel, const double *h_ref) {
+    RmsdForce *rf = amm_force_get<RmsdForce>(ctx, force_id, "amm_rmsd_set_reference");
+    if (!rf) return 1;
+    if (n_sel > 0 && (!h_particles || !h_ref)) {
+        amm_set_error("amm_rmsd_set_reference: null argument");
+        return 1;
+    }
+    return amm_rmsd_set_reference_impl(ctx, rf, h_particles, n_sel, h_ref);
+}
+
+int amm_rmsd_stats(amm_ctx *ctx, int32_t force_id, int64_t *out) {
+    RmsdForce *rf = amm_force_get<RmsdForce>(ctx, force_id, "amm_rmsd_stats");
+    if (!rf) return 1;
+    if (!out) {
+        amm_set_error("amm_rmsd_stats: null argument");
+        return 1;
+    }
+    return amm_rmsd_stats_impl(rf, out);
+}
+
+int amm_rmsd_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_RMSD, "amm_rmsd_release"); }
 
 }   // extern "C"

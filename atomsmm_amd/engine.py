@@ -254,6 +254,7 @@ class _Entry:
                                     # is what expr.compile_custom_gb returned
         self.hbond = None           # a CustomHbondForce (csrc/hbond.hip): dict(id, variables); the id is also in term_ids, term_expr is
                                     # set, `program` is that of expr.compile_hbond
+        self.rmsd = None            # an RMSDForce (csrc/rmsd.hip): its backend id, which is also in term_ids
         self.many = None            # a CustomManyParticleForce (csrc/manyparticle.hip): dict(id, variables, types); carried as hbond is,
                                     # `program` is that of expr.compile_many_particle
 
@@ -1167,9 +1168,44 @@ class Engine:
             entry.terms.append((B.TORSION_PERIODIC, t, p, force.usesPeriodicBoundaryConditions(), None))
         elif isinstance(force, (mm.CustomCompoundBondForce, mm.CustomCentroidBondForce)):
             self._translate_compound(force, entry)
+        elif isinstance(force, mm.RMSDForce):
+            self._translate_rmsd(force, entry)
         else:
             return False
         return True
+
+    def _translate_rmsd(self, force, entry):
+        """An RMSDForce: the selected particles and the reference rows of those particles go to the RMSD kernels (csrc/rmsd.hip), which
+        centre the reference, fit and differentiate.  One backend force carried in entry.term_ids, so every loop over an entry's forces
+        reaches it and the scheduler's fusion rules decline its group, as they do for a term-expression force.  (Also an inner force
+        of a CustomCVForce: _translate_cv_general.)  It reads no parameter: deriv(energy, p) sees no dependence through it."""
+        cls = 'RMSDForce'
+        if self.world > 1:
+            raise NotImplementedError('%s runs on a single rank' % cls)
+        n = self.n
+
+        def tables():
+            reference = np.array(force._reference, dtype=np.float64).reshape(-1, 3)
+            if len(reference) != n:
+                raise mm.OpenMMException('%s: %d reference positions, the System has %d particles' % (cls, len(reference), n))
+            particles = force.getParticles() or list(range(n))
+            if min(particles) < 0 or max(particles) >= n:
+                raise mm.OpenMMException('%s: a particle index is out of range' % cls)
+            if len(set(particles)) != len(particles):
+                raise mm.OpenMMException('%s: a particle is listed twice' % cls)
+            if not np.isfinite(reference).all():
+                raise mm.OpenMMException('%s: a reference position is not finite' % cls)
+            particles = np.array(particles, dtype=np.int32)
+            return particles, np.ascontiguousarray(reference[particles])
+
+        fid = self.ctx.rmsd_create(*tables())
+        entry.term_ids.append(fid)
+        entry.rmsd = fid
+
+        def reload():          # updateParametersInContext: the reference and the particle list are read again
+            self.ctx.rmsd_set_reference(fid, *tables())
+            return 'values'
+        entry.reload = reload
 
     def _pair_create(self, desc, q, sigma, eps, excl):
         if self.free_space:
@@ -1713,7 +1749,7 @@ class Engine:
         self._translate_alchemical_pair(inner, entry, d, outer=outer, outer_depends=used)
 
     _CV_INNER_CLASSES = ('HarmonicBondForce', 'HarmonicAngleForce', 'PeriodicTorsionForce', 'CustomBondForce', 'CustomAngleForce',
-                         'CustomTorsionForce', 'CustomExternalForce', 'CustomCompoundBondForce', 'CustomCentroidBondForce')
+                         'CustomTorsionForce', 'CustomExternalForce', 'CustomCompoundBondForce', 'CustomCentroidBondForce', 'RMSDForce')
 
     def _translate_cv_general(self, force, entry):
         """CustomCVForce with any energy text over several collective variables, each the energy of a bond / angle / torsion / external

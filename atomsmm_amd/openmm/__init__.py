@@ -974,6 +974,44 @@ class CustomManyParticleForce(Force, _GlobalParams):
         context._engine.update_force_parameters(self)
 
 
+class RMSDForce(Force):
+    """Energy = the root-mean-square deviation, in nm, of `particles` from `referencePositions` after the optimal rigid superposition
+    (translation and proper rotation; csrc/rmsd.hip).  Reference positions are given for EVERY particle of the System,
+    with units or in plain nm; an empty particle list means all particles.  Positions are read raw: no periodic image is taken."""
+
+    def __init__(self, referencePositions, particles=()):
+        Force.__init__(self)
+        self.setReferencePositions(referencePositions)
+        self.setParticles(particles)
+
+    def getReferencePositions(self):
+        return Quantity([Vec3(*row) for row in self._reference], nm)
+
+    def setReferencePositions(self, positions):
+        v = md_value(positions)
+        if isinstance(v, (list, tuple)) and len(v) and isinstance(v[0], Quantity):
+            v = [md_value(r) for r in v]
+        arr = np.array(v, dtype=np.float64)
+        if arr.size == 0:
+            arr = arr.reshape(0, 3)
+        if arr.ndim != 2 or arr.shape[1] != 3:
+            raise OpenMMException('RMSDForce: reference positions are one (x, y, z) per particle')
+        self._reference = [tuple(float(c) for c in row) for row in arr]
+
+    def getParticles(self):
+        return list(self._rmsd_particles)
+
+    def setParticles(self, particles):
+        self._rmsd_particles = [int(p) for p in particles]
+
+    def usesPeriodicBoundaryConditions(self):
+        return False
+
+    def updateParametersInContext(self, context):
+        """Upload the reference positions and the particle list again; their number may have changed."""
+        context._engine.update_force_parameters(self)
+
+
 class CustomCVForce(Force, _GlobalParams):
     """Energy = function of collective variables, each the energy of an inner Force object."""
 

@@ -313,8 +313,8 @@ int amm_term_expr_release(amm_ctx *ctx, int32_t force_id);
 #define AMM_CV_MAX_CVS 16
 #define AMM_CV_MAX_DERIVS 16
 /* CustomCVForce(energy) + addCollectiveVariable x n_cv + addEnergyParameterDerivative x n_deriv.  inner_ids: n_cv ids of bond-list
- * sets (amm_bonded_create .. amm_bonded_finalize), term-expression forces (amm_term_expr_create) or compound-bond forces
- * (amm_compound_create) that the caller created, keeps in no group and releases itself; any other type is refused.  code / consts / globals: the program of atomsmm_amd.expr.compile_cv --
+ * sets (amm_bonded_create .. amm_bonded_finalize), term-expression forces (amm_term_expr_create), compound-bond forces
+ * (amm_compound_create) or RMSD forces (amm_rmsd_create) that the caller created, keeps in no group and releases itself; any other type is refused.  code / consts / globals: the program of atomsmm_amd.expr.compile_cv --
  * the words of amm_term_expr_create with variable k (opcode 53) = collective variable k for k < n_cv and derivative parameter
  * k - n_cv behind them, no per-term parameters; the same limits, checked here with a walk of the stack.  Scratch: 24 n_cv n bytes. */
 int amm_cv_create(amm_ctx *ctx, const int32_t *inner_ids, int32_t n_cv, int32_t n_deriv, const int32_t *code, int32_t ncode,
@@ -546,6 +546,27 @@ int amm_many_stats(amm_ctx *ctx, int32_t force_id, int64_t *out);
 /* Free such a force; the id is retired and leaves every group definition. */
 int amm_many_release(amm_ctx *ctx, int32_t force_id);
 
+/* RMSDForce (force type AMM_FORCE_RMSD; csrc/rmsd.hip): the root-mean-square deviation, in nm, of the n_sel
+ * particles h_particles from the reference rows h_ref[n_sel][3] (row k belongs to particle h_particles[k]) after the optimal rigid
+ * superposition -- translation and PROPER rotation, by Horn's quaternion -- as an energy, with force -d_i / (n_sel rmsd) on
+ * particle i, d_i its residual after the fit.  The library centres the reference in extended precision.  Positions are read raw: no
+ * box, no minimum image.  A mean square deviation below 1e-20 nm^2 gives energy 0 and zero rows, never a NaN.
+ * Refused, each with AMM_FORCE_RMSD in the message: n_sel < 1, an index outside [0, n), an index listed twice, a reference
+ * coordinate that is not finite, more than one rank (also amm_set_slice while such a force lives).  An ordinary member of a group,
+ * evaluated through amm_force_eval and amm_run_ops, legal in a context without a box, and a legal inner force of amm_cv_create; every
+ * other family's entry points refuse its id naming AMM_FORCE_RMSD.
+ * fp64, no atomics, fixed order of summation: the same positions give the same bits.  One launch of one block up to a selection size
+ * measured on an MI355X, three launches of several blocks above it; the option "rmsd_blocks" (amm_set_option, read when the force is
+ * created) forces either.  Without `accumulate` the rows of the particles outside the selection are written as zeros. */
+int amm_rmsd_create(amm_ctx *ctx, const int32_t *h_particles, int32_t n_sel, const double *h_ref, int32_t *force_id);
+/* setReferencePositions / setParticles + updateParametersInContext: new particles and / or a new reference, laid out as at creation;
+ * n_sel may change.  Waits for the stream.  A refused call leaves the force as it was. */
+int amm_rmsd_set_reference(amm_ctx *ctx, int32_t force_id, const int32_t *h_particles, int32_t n_sel, const double *h_ref);
+/* out[0]: selected particles; out[1]: blocks (1: the single block); out[2]: launches per evaluation (1 or 3); out[3]: launches so far. */
+int amm_rmsd_stats(amm_ctx *ctx, int32_t force_id, int64_t *out);
+/* Free such a force; the id is retired and leaves every group definition. */
+int amm_rmsd_release(amm_ctx *ctx, int32_t force_id);
+
 /* Reciprocal space of a NonbondedForce with nonbondedMethod PME / Ewald, as RESPASystem and FarNonbondedForce
  * keep it in group 2 with the source force's Ewald tolerance / PME parameters (systems.py:74-75,
  * forces.py:185-188; setReciprocalSpaceForceGroup: utils.py:147-152).  Smooth PME, B-spline order 5, grid
@@ -670,7 +691,8 @@ int amm_set_outer_skin(amm_ctx *ctx, double skin_out);
  * split into, one wavefront each: 0 = chosen from the number of rows; 1 .. 512), "hbond_compact" (0: such a force runs the
  * interpreter after every batch of 64 columns that has a survivor instead of on full queues -- for measurements; default 1),
  * "many_capacity" (neighbours a row of a many-particle force with a cutoff created from now on can hold: a multiple of 64 from 64
- * to 4096; default 256).  Unknown names are an error. */
+ * to 4096; default 256), "rmsd_blocks" (blocks of an RMSD force created from now on: 0 = one block up to the measured crossover and
+ * one per 1024 particles above it, 1 = the single block, 2 .. 1024 = that many; default 0).  Unknown names are an error. */
 int amm_set_option(amm_ctx *ctx, const char *name, double value);
 /* What amm_run_ops fused so far (statistics for tests and bench.py): out[0] = pair-kernel launches that carried the inner RESPA loop
  * of their molecules as an epilogue (the reference runs it as CustomIntegrator steps, propagators.py:933-973), out[1] = pair
