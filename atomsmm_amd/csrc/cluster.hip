@@ -341,6 +341,9 @@ struct CBoxF {
 // record (CBuildTab above: made once per rebuild by the cell's wavefront of the sort launch), copied to LDS by every wavefront of the cell.
 // The old per-atom build spent 42 instructions per 64 ATOM-pair tests, mostly compaction; here the compaction is paid per
 // MOLECULE pair and only for a stream that is already 80 % hits.
+// Bookkeeping stays off the vector unit: the test is unrolled over the batch, a row's first atom, radius and
+// ring state are scalar registers over the whole stream, and after the tests of a chunk pair the rows whose ring is full are drained
+// from a scalar mask -- one copy of the drain, which forms its lane masks on the scalar side and stores through a 32-bit offset.
 #ifndef CB_BATCH
 #define CB_BATCH 5
 #endif
@@ -463,21 +466,23 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLICE 
 #endif
         for (int tb = a_begin; tb < a_end; tb += CB_BATCH) {
             const int nt = min(CB_BATCH, a_end - tb);
-            // the batch's atoms: lane 3 t + a holds atom a of row molecule t; the loops over t below are REAL loops (t is a scalar
-            // register): coordinates come by v_readlane, the per-row counters live in lane t of three registers -- one copy of the
-            // test and of the drain code whatever the batch size
+            // the batch's atoms: lane 3 t + a holds atom a of row molecule t.  The sphere test is unrolled over the batch (below); the
+            // drains take t in a scalar register: coordinates come by v_readlane, a row's entry counts live in lane t of row_cnt --
+            // one copy of the drain code whatever the batch size
             if (tb > a_begin) {
                 my = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (lane < 3 * nt) my = pos4f[3 * tb + lane];
             }
             int row_cnt = 0;          // lane t: entries of row t so far (front | back << 16)
-            int q_head = 0, q_cnt = 0;    // lane t: ring of row t (head index, entries waiting)
+            v2f b_x = v2f{box.L[0], box.invL[0]}, b_y = v2f{box.L[1], box.invL[1]}, b_z = v2f{box.L[2], box.invL[2]};
             auto rl = [&](float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); };
-            // ---- pass 2: 128 queued survivors of row t (n of them valid), two per lane (lane, lane + 64) so that the arithmetic runs
-            // on packed fp32: nine distances each, the smallest decides; the two halves are filed one after the other (ring order) ----
+            // ---- pass 2: 128 queued survivors of row t (n of them valid; the ring's head at `head`), two per lane (lane, lane + 64) so
+            // that the arithmetic runs on packed fp32: nine distances each, the smallest decides; the two halves are filed one after the
+            // other (ring order) ----
             // NU = 1: the row's leftover at the end of the stream when it fits one half (n <= 64) -- one survivor per lane, the same fp32
             // operations on it unpacked, the same filing: no second half of gathers and arithmetic on lanes that hold nothing
-            auto drain = [&](int t, int n, auto nu_) {
+            // (t is a scalar REGISTER here: ONE copy of each form whatever the row; the ring's state is the caller's)
+            auto drain = [&](int t, int n, int head, auto nu_) {
                 constexpr int NU = decltype(nu_)::value;
                 using V = typename std::conditional<NU == 2, v2f, float>::type;
                 auto pk = [](const float (&x)[NU]) -> V { if constexpr (NU == 2) return v2f{x[0], x[1]}; else return x[0]; };
@@ -486,16 +491,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLICE 
                 const unsigned long long t_d0 = wall_clock64();
                 n_drain++;
 #endif
-                const int head = __builtin_amdgcn_readlane(q_head, t);
+                const int self = tb + t;
                 int slot[NU];
-                bool v[NU];
                 float4 A[NU][3];
 #pragma unroll
-                for (int u = 0; u < NU; ++u) {
-                    const bool v0 = lane + 64 * u < n;
-                    slot[u] = v0 ? s_q[w][t][cq_wrap(head + lane + 64 * u)] : tb + t;
-                    v[u] = v0 && slot[u] != tb + t;          // (a molecule is not its own partner)
-                }
+                for (int u = 0; u < NU; ++u)          // (a lane beyond n holds the row molecule itself, which is not its own partner)
+                    slot[u] = lane + 64 * u < n ? s_q[w][t][cq_wrap(head + lane + 64 * u)] : self;
 #pragma unroll
                 for (int u = 0; u < NU; ++u)
 #pragma unroll
@@ -524,10 +525,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLICE 
                     ay[b] = pk(hy);
                     az[b] = pk(hz);
                 }
+                // (box edge and its inverse share a register pair, hidden from the compiler like the rows' constants below)
+                asm volatile("" : "+s"(b_x), "+s"(b_y), "+s"(b_z));
+                auto edge = [](const v2f &b) -> V { if constexpr (NU == 2) return b.xx; else return b.x; };
+                auto inv = [](const v2f &b) -> V { if constexpr (NU == 2) return b.yy; else return b.y; };
                 if (!RINT) {          // one periodic image per molecule pair, from the first atoms
-                    const V sx = box.L[0] * __builtin_elementwise_rint((ax[0] - px[0]) * box.invL[0]);
-                    const V sy = box.L[1] * __builtin_elementwise_rint((ay[0] - py[0]) * box.invL[1]);
-                    const V sz = box.L[2] * __builtin_elementwise_rint((az[0] - pz[0]) * box.invL[2]);
+                    const V sx = edge(b_x) * __builtin_elementwise_rint((ax[0] - px[0]) * inv(b_x));
+                    const V sy = edge(b_y) * __builtin_elementwise_rint((ay[0] - py[0]) * inv(b_y));
+                    const V sz = edge(b_z) * __builtin_elementwise_rint((az[0] - pz[0]) * inv(b_z));
 #pragma unroll
                     for (int b = 0; b < 3; ++b) {
                         ax[b] -= sx;
@@ -544,40 +549,41 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLICE 
                     for (int b = 0; b < 3; ++b) {
                         V dx = px[a] - ax[b], dy = py[a] - ay[b], dz = pz[a] - az[b];
                         if (RINT) {
-                            dx -= box.L[0] * __builtin_elementwise_rint(dx * box.invL[0]);
-                            dy -= box.L[1] * __builtin_elementwise_rint(dy * box.invL[1]);
-                            dz -= box.L[2] * __builtin_elementwise_rint(dz * box.invL[2]);
+                            dx -= edge(b_x) * __builtin_elementwise_rint(dx * inv(b_x));
+                            dy -= edge(b_y) * __builtin_elementwise_rint(dy * inv(b_y));
+                            dz -= edge(b_z) * __builtin_elementwise_rint(dz * inv(b_z));
                         }
                         V r2 = dx * dx;
                         r2 = __builtin_elementwise_fma(dy, dy, r2);
                         r2 = __builtin_elementwise_fma(dz, dz, r2);
                         m2 = __builtin_elementwise_min(m2, r2);
                     }
+                // the row's counts ride in a scalar register over both halves; its rows' base is scalar too: a lane adds 32 bits
+                int c2 = __builtin_amdgcn_readlane(row_cnt, t);
+                char *row_out = reinterpret_cast<char *>(nl + (size_t)(self - c_begin) * cap);
 #pragma unroll
                 for (int u = 0; u < NU; ++u) {
                     const float m2u = half(m2, u);
-                    const bool pass = v[u] && m2u < rlist2;
-                    const unsigned long long m_pass = __builtin_amdgcn_ballot_w64(pass);
+                    // (lane masks of the comparisons, combined on the scalar side)
+                    const bool other = slot[u] != self, in_list = m2u < rlist2, in_near = m2u < rnear2;
+                    const unsigned long long m_pass = __builtin_amdgcn_ballot_w64(other) & __builtin_amdgcn_ballot_w64(in_list);
                     if (m_pass != 0ull) {
-                        const bool is_near = pass && m2u < rnear2;
-                        const unsigned long long m_near = __builtin_amdgcn_ballot_w64(is_near);
+                        const unsigned long long m_near = m_pass & __builtin_amdgcn_ballot_w64(in_near);
                         const int np_ = __popcll(m_pass), nn_ = __popcll(m_near);
-                        const int c2 = __builtin_amdgcn_readlane(row_cnt, t);
                         const int cnt = c2 & 0xffff, cntf = (int)((unsigned)c2 >> 16);
                         if (!COUNT_ONLY) {
                             const int mp = __builtin_amdgcn_mbcnt_hi((unsigned)(m_pass >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m_pass, 0u));
                             const int mn = __builtin_amdgcn_mbcnt_hi((unsigned)(m_near >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m_near, 0u));
                             const int pos_near = cnt + mn, pos_far = (cap - 1 - cntf) - (mp - mn);
                             if (cnt + cntf + np_ <= cap) {
-                                int *row_out = nl + (size_t)(tb + t - c_begin) * cap;
-                                if (pass) row_out[is_near ? pos_near : pos_far] = slot[u] | (sites[u] << 29);
+                                const unsigned at = (unsigned)(in_near ? pos_near : pos_far) << 2;          // (only listed lanes store)
+                                if (other && in_list) *reinterpret_cast<int *>(row_out + at) = slot[u] | (sites[u] << 29);
                             }
                         }
-                        row_cnt = lane == t ? c2 + nn_ + ((np_ - nn_) << 16) : row_cnt;
+                        c2 += nn_ + ((np_ - nn_) << 16);
                     }
                 }
-                q_head = lane == t ? cq_wrap(head + n) : q_head;
-                q_cnt = lane == t ? q_cnt - n : q_cnt;
+                row_cnt = lane == t ? c2 : row_cnt;
 #ifdef AMM_CBS_TIMING
                 t_drain += wall_clock64() - t_d0;
 #endif
@@ -611,25 +617,48 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLICE 
             fetch(0, cand, js);
             // (lane 3 t: the radius of row t's sphere without the candidate's own extent)
             const float plim_l = my.w + rlist;
+            // the rows of the batch are tested in UNROLLED code (rows >= nt: skipped by a scalar branch): a row's first atom, its radius,
+            // its ring's entry count and head stay in scalar registers over the whole stream -- read from the lanes once per batch --
+            // and its ring is a constant offset into the wavefront's LDS.  A ring's head is 0 or 128 until the final drain: one bit.
+            v2f r_xy[CB_BATCH], r_zl[CB_BATCH];          // (two constants to an aligned register pair: the packed operations pick a half)
+            int r_qn[CB_BATCH];
+#pragma unroll
+            for (int t = 0; t < CB_BATCH; ++t) {
+                r_xy[t] = v2f{rl(my.x, 3 * t), rl(my.y, 3 * t)};
+                r_zl[t] = v2f{rl(my.z, 3 * t), rl(plim_l, 3 * t)};
+                r_qn[t] = 0;
+            }
+            unsigned r_head = 0;          // bit t: the ring of row t starts at 128
             for (int cb = 0; cb < total; cb += 128) {
                 if (cb + 128 < total) fetch(cb + 128, cand_n, js_n);
                 // the two chunks side by side in packed registers (a chunk beyond the stream holds far-away / never-reached candidates)
                 const v2f cx = v2f{cand[0].x, cand[1].x}, cy = v2f{cand[0].y, cand[1].y}, cz = v2f{cand[0].z, cand[1].z};
                 const v2f cw = v2f{cand[0].w, cand[1].w};
-                for (int t = 0; t < nt; ++t) {
-                    const float p0x = rl(my.x, 3 * t), p0y = rl(my.y, 3 * t), p0z = rl(my.z, 3 * t), plim = rl(plim_l, 3 * t);
-                    int qn = __builtin_amdgcn_readlane(q_cnt, t);
-                    const int head = __builtin_amdgcn_readlane(q_head, t);
-                    v2f dx = p0x - cx, dy = p0y - cy, dz = p0z - cz;
+                unsigned pend = 0;            // bit t: the ring of row t holds 128 or more
+                int rows = nt;
+                asm volatile("" : "+s"(rows));          // (compared row by row below, not as five lane masks kept over the loop)
+#pragma unroll
+                for (int t = 0; t < CB_BATCH; ++t) {
+                    if (t >= rows) break;
+                    int qn = r_qn[t];
+                    const int head = (int)((r_head >> t) & 1u) << 7;
+                    // (an empty statement that hides where the pair came from: without it the compiler splats every constant
+                    // into a register pair of its own ahead of the loop -- 40 scalar registers, which it does not have)
+                    // (a slice's kernel has no scalar registers to spare: it reads the four constants from the lanes at every test, as
+                    // all did before, and keeps the ring state alone in scalar registers)
+                    if (!SLICE) asm volatile("" : "+s"(r_xy[t]), "+s"(r_zl[t]));
+                    const v2f xy = SLICE ? v2f{rl(my.x, 3 * t), rl(my.y, 3 * t)} : r_xy[t], zl = SLICE ? v2f{rl(my.z, 3 * t), rl(plim_l, 3 * t)} : r_zl[t];
+                    v2f dx = xy.xx - cx, dy = xy.yy - cy, dz = zl.xx - cz;
                     if (RINT) {
-                        dx -= box.L[0] * __builtin_elementwise_rint(dx * box.invL[0]);
-                        dy -= box.L[1] * __builtin_elementwise_rint(dy * box.invL[1]);
-                        dz -= box.L[2] * __builtin_elementwise_rint(dz * box.invL[2]);
+                        asm volatile("" : "+s"(b_x), "+s"(b_y), "+s"(b_z));
+                        dx -= b_x.xx * __builtin_elementwise_rint(dx * b_x.yy);
+                        dy -= b_y.xx * __builtin_elementwise_rint(dy * b_y.yy);
+                        dz -= b_z.xx * __builtin_elementwise_rint(dz * b_z.yy);
                     }
                     v2f r2 = dx * dx;
                     r2 = __builtin_elementwise_fma(dy, dy, r2);
                     r2 = __builtin_elementwise_fma(dz, dz, r2);
-                    const v2f lim = plim + cw;
+                    const v2f lim = zl.yy + cw;
                     const v2f lim2 = lim * lim;
 #pragma unroll
                     for (int u = 0; u < 2; ++u) {
@@ -637,17 +666,28 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLICE 
                         const bool pass = (u ? r2.y < lim2.y : r2.x < lim2.x) && (!RINT || (u ? lim.y : lim.x) > 0.f);
                         const unsigned long long m = __builtin_amdgcn_ballot_w64(pass);
                         if (m == 0ull) continue;
-                        const int at = qn + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                        if (pass) s_q[w][t][cq_wrap(head + at)] = js[u];
+                        const int at = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)) + (head + qn);
+                        if (pass) s_q[w][t][cq_wrap(at)] = js[u];
                         qn += __popcll(m);
                     }
-                    q_cnt = lane == t ? qn : q_cnt;
-                    if (qn >= 128) {
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                        __builtin_amdgcn_wave_barrier();
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                        drain(t, 128, std::integral_constant<int, 2>());
-                    }
+                    r_qn[t] = qn;
+                    pend |= qn >= 128 ? 1u << t : 0u;
+                }
+                // the rows whose ring is full, lowest first (rings and rows of different t are independent: the order of a row's own
+                // tests and drains is what it was); a ring grows only by its own test, so 127 + 128 <= CB_QCAP holds as before
+                if (pend) {
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    unsigned todo = pend;
+                    do {
+                        const int t = __builtin_ctz(todo);
+                        todo &= todo - 1;
+                        drain(t, 128, (int)((r_head >> t) & 1u) << 7, std::integral_constant<int, 2>());
+                    } while (todo);
+                    r_head ^= pend;
+#pragma unroll
+                    for (int t = 0; t < CB_BATCH; ++t) r_qn[t] &= 127;          // (a full ring held 128 .. 255: minus 128; the others < 128)
                 }
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
@@ -658,13 +698,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLICE 
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll 1          // (ONE copy of each drain form)
             for (int t = 0; t < nt; ++t) {
-                const int n = __builtin_amdgcn_readlane(q_cnt, t);
+                int n = 0;
+#pragma unroll
+                for (int k = 0; k < CB_BATCH; ++k) n = k == t ? r_qn[k] : n;
+                const int head = (int)((r_head >> t) & 1u) << 7;
 #if CB_HALF_DRAIN
-                if (n > 64) drain(t, n, std::integral_constant<int, 2>());
-                else if (n > 0) drain(t, n, std::integral_constant<int, 1>());
+                if (n > 64) drain(t, n, head, std::integral_constant<int, 2>());
+                else if (n > 0) drain(t, n, head, std::integral_constant<int, 1>());
 #else
-                if (n > 0) drain(t, n, std::integral_constant<int, 2>());
+                if (n > 0) drain(t, n, head, std::integral_constant<int, 2>());
 #endif
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // the ring reads are done before the next batch refills them

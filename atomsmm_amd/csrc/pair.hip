@@ -2228,9 +2228,9 @@ int amm_pair_count_within_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos,
 extern "C" __attribute__((weak)) const char *amm_variant_tag(void);
 const char *amm_kernel_revision_impl() {
 #ifdef AMM_CLUSTER_TUNE
-    return "r10-lookupoffset-tune";
+    return "r11-buildloops-tune";
 #else
-    return amm_variant_tag ? "r10-lookupoffset-tune" : "r10-lookupoffset";
+    return amm_variant_tag ? "r11-buildloops-tune" : "r11-buildloops";
 #endif
 }
 
