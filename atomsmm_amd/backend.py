@@ -65,6 +65,7 @@ EXPORTS = [
     'amm_hbond_create', 'amm_hbond_set_params', 'amm_hbond_set_globals', 'amm_hbond_stats', 'amm_hbond_release',
     'amm_many_create', 'amm_many_set_params', 'amm_many_set_globals', 'amm_many_stats', 'amm_many_release',
     'amm_rmsd_create', 'amm_rmsd_set_reference', 'amm_rmsd_stats', 'amm_rmsd_release',
+    'amm_gayberne_create', 'amm_gayberne_set_params', 'amm_gayberne_stats', 'amm_gayberne_release',
     'amm_vsite_define', 'amm_vsite_place', 'amm_vsite_spread', 'amm_vsite_stats',
 ]
 
@@ -227,6 +228,10 @@ def lib():
         L.amm_rmsd_set_reference.argtypes = [vp, C.c_int32, ip, C.c_int32, dp]
         L.amm_rmsd_stats.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
         L.amm_rmsd_release.argtypes = [vp, C.c_int32]
+        L.amm_gayberne_create.argtypes = [vp, ip, C.c_int32, ip, dp, ip, ip, dp, ip, ip, C.c_double, C.c_double, C.c_int32, ip]
+        L.amm_gayberne_set_params.argtypes = [vp, C.c_int32, dp, C.c_int32, dp, C.c_int32]
+        L.amm_gayberne_stats.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
+        L.amm_gayberne_release.argtypes = [vp, C.c_int32]
         L.amm_cv_create.argtypes = [vp, ip, C.c_int32, C.c_int32, ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip]
         L.amm_cv_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
         L.amm_cv_set_variables.argtypes = [vp, C.c_int32, dp, C.c_int32]
@@ -800,6 +805,43 @@ class HipContext:
     def rmsd_release(self, fid):
         """Free an RMSD force (its id is retired)."""
         _chk(lib().amm_rmsd_release(self.h, fid))
+
+    def gayberne_create(self, active, axes, par, ex_ptr, ex_col, ex_par, rev_ptr, rev_src, rc=0.0, rs=-1.0, periodic=False):
+        """A Gay-Berne force (csrc/gayberne.hip).  active: the interacting particles, ascending; axes[k]: the x- and y-particle of
+        active[k] (-1: none); par[k]: sigma, epsilon, sx, sy, sz, ex, ey, ez; ex_ptr / ex_col / ex_par: the exceptions as a CSR over
+        active rows -- columns (active indices) ascending, (sigma, epsilon) per entry, every pair on both rows; rev_ptr / rev_src: per
+        particle of the context the 2 * row + (0: x, 1: y) that name it, ascending.  rc = 0: NoCutoff; rs < 0: no switch."""
+        n_act = len(active)
+        a_, ap = _hi(np.asarray(active, dtype=np.int32).reshape(-1) if n_act else [0])
+        x_, xp = _hi(np.asarray(axes, dtype=np.int32).reshape(-1) if n_act else [0])
+        p_, pp = _hd(np.asarray(par, dtype=np.float64).reshape(-1) if n_act else [0.0])
+        ep_, epp = _hi(np.asarray(ex_ptr, dtype=np.int32).reshape(-1))
+        ec_, ecp = _hi(np.asarray(ex_col, dtype=np.int32).reshape(-1) if len(ex_col) else [0])
+        ev_, evp = _hd(np.asarray(ex_par, dtype=np.float64).reshape(-1) if len(ex_col) else [0.0])
+        rp_, rpp = _hi(np.asarray(rev_ptr, dtype=np.int32).reshape(-1))
+        rs_, rsp = _hi(np.asarray(rev_src, dtype=np.int32).reshape(-1) if len(rev_src) else [0])
+        fid = C.c_int32(-1)
+        _chk(lib().amm_gayberne_create(self.h, ap, n_act, xp, pp, epp, ecp, evp, rpp, rsp, float(rc), float(rs), int(bool(periodic)), C.byref(fid)))
+        return fid.value
+
+    def gayberne_set_params(self, fid, par, ex_par):
+        """New parameter rows and exception values, laid out as at creation; the counts must not change (waits for the stream)."""
+        par = np.asarray(par, dtype=np.float64).reshape(-1, 8)
+        ex_par = np.asarray(ex_par, dtype=np.float64).reshape(-1, 2)
+        p_, pp = _hd(par.reshape(-1) if len(par) else [0.0])
+        e_, ep = _hd(ex_par.reshape(-1) if len(ex_par) else [0.0])
+        _chk(lib().amm_gayberne_set_params(self.h, fid, pp, len(par), ep, len(ex_par)))
+
+    def gayberne_stats(self, fid):
+        """dict(active, scanned, survivors, launches, chunks): interacting particles, ordered pairs one evaluation tests, those that
+        passed the cutoff and the exceptions in the last evaluation (each pair counts from both sides), launches so far, chunks per row."""
+        out = (C.c_int64 * 5)()
+        _chk(lib().amm_gayberne_stats(self.h, fid, out))
+        return dict(active=int(out[0]), scanned=int(out[1]), survivors=int(out[2]), launches=int(out[3]), chunks=int(out[4]))
+
+    def gayberne_release(self, fid):
+        """Free a Gay-Berne force (its id is retired)."""
+        _chk(lib().amm_gayberne_release(self.h, fid))
 
     def cv_create(self, inner_ids, n_deriv, code, consts, globals_):
         """A CustomCVForce with any energy text (csrc/cv.hip): the ids of the inner forces in the order of the collective variables

@@ -261,13 +261,15 @@ struct CustomGbForce; // custom_gb.hip: a CustomGBForce -- computed per-particle
 struct HbondForce;    // hbond.hip: a CustomHbondForce -- donors against acceptors over all pairs, the energy written as text
 struct ManyForce;     // manyparticle.hip: a CustomManyParticleForce -- sets of three particles under a cutoff, the energy written as text
 struct RmsdForce;     // rmsd.hip: an RMSDForce -- the deviation of selected particles from a reference after the best rigid fit
+struct GayBerneForce; // gayberne.hip: a GayBerneForce -- ellipsoids whose frames other particles define, over all pairs of interacting particles
 // The force families.  A family is described ONCE: its tag here, the struct that goes with the tag in amm_force_type, and its row of
 // the table behind amm_family (families.hip).  The typed lookup and its refusals, amm_force_eval_dispatch, release, amm_destroy, amm_set_slice and
 // cv.hip's messages all read the row -- a new family adds these three lines, its own .hip file and its extern "C" entry points.
-// Twelve families today (and the tag of a released id).
+// Thirteen families today (and the tag of a released id).
 enum : int { AMM_FORCE_RELEASED = 0, AMM_FORCE_PAIR = 1, AMM_FORCE_BONDED = 2, AMM_FORCE_PME = 3, AMM_FORCE_TERM_EXPR = 4, AMM_FORCE_CV = 5,
              AMM_FORCE_COMPOUND = 6, AMM_FORCE_GB = 7, AMM_FORCE_CMAP = 8, AMM_FORCE_CUSTOM_GB = 9, AMM_FORCE_HBOND = 10,
-             AMM_FORCE_MANY_PARTICLE = 11, AMM_FORCE_RMSD = 12, AMM_FORCE_TYPES = 13 };   // ForceObj::type, the row amm_family returns
+             AMM_FORCE_MANY_PARTICLE = 11, AMM_FORCE_RMSD = 12, AMM_FORCE_GAYBERNE = 13,
+             AMM_FORCE_TYPES = 14 };   // ForceObj::type, the row amm_family returns
 template <class T> inline constexpr int amm_force_type = -1;
 template <> inline constexpr int amm_force_type<PairForce> = AMM_FORCE_PAIR;
 template <> inline constexpr int amm_force_type<BondedSet> = AMM_FORCE_BONDED;
@@ -281,6 +283,7 @@ template <> inline constexpr int amm_force_type<CustomGbForce> = AMM_FORCE_CUSTO
 template <> inline constexpr int amm_force_type<HbondForce> = AMM_FORCE_HBOND;
 template <> inline constexpr int amm_force_type<ManyForce> = AMM_FORCE_MANY_PARTICLE;
 template <> inline constexpr int amm_force_type<RmsdForce> = AMM_FORCE_RMSD;
+template <> inline constexpr int amm_force_type<GayBerneForce> = AMM_FORCE_GAYBERNE;
 struct ForceFamily {
     const char *noun, *tag, *prefix;   // "a CMAP force", "AMM_FORCE_CMAP", "amm_cmap_*"
     const char *bad_id;                // what the family's entry points say of an id that is not theirs (behind "<entry point>: " if they name themselves)
@@ -664,6 +667,14 @@ int amm_rmsd_set_reference_impl(amm_ctx *ctx, RmsdForce *rf, const int32_t *h_pa
 int amm_rmsd_eval_impl(amm_ctx *ctx, RmsdForce *rf, const double *d_pos, double *d_force, int accumulate, double *d_energy);
 int amm_rmsd_stats_impl(RmsdForce *rf, int64_t out[4]);
 void amm_rmsd_free(RmsdForce *rf);
+// gayberne.hip: a force of type AMM_FORCE_GAYBERNE (the tables are those of amm_gayberne_create, include/atomsmm_hip.h)
+int amm_gayberne_create_impl(amm_ctx *ctx, const int32_t *h_active, int n_act, const int32_t *h_axes, const double *h_par, const int32_t *h_ex_ptr,
+                             const int32_t *h_ex_col, const double *h_ex_par, const int32_t *h_rev_ptr, const int32_t *h_rev_src, double rc,
+                             double rs, int periodic, GayBerneForce **out);
+int amm_gayberne_set_params_impl(amm_ctx *ctx, GayBerneForce *gf, const double *h_par, int n_act, const double *h_ex_par, int n_ex);
+int amm_gayberne_eval_impl(amm_ctx *ctx, GayBerneForce *gf, const double *d_pos, double *d_force, int accumulate, double *d_energy);
+int amm_gayberne_stats_impl(amm_ctx *ctx, GayBerneForce *gf, int64_t out[5]);
+void amm_gayberne_free(GayBerneForce *gf);
 // implemented in pair.hip / cells.hip / bonded.hip / integrate.hip
 int amm_pair_build_consts(const amm_pair_desc &d, PairConsts &pc);
 int amm_pair_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double *d_force, int accumulate,

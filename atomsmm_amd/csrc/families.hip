@@ -1,7 +1,7 @@
 // atomsmm_amd/csrc/families.hip -- the table of force families (amm_ctx.h: ForceFamily) and everything derived from it: the typed lookup
 // with its refusals, registration, release and the dispatch of an evaluation; then the extern "C" entry points of the families whose
 // implementation is a .hip file of its own (term expressions, collective variables, compound bonds, generalized Born, CMAP, custom
-// generalized Born, hydrogen bonds, many-particle sets, RMSD).
+// generalized Born, hydrogen bonds, many-particle sets, RMSD, Gay-Berne ellipsoids).
 #include <algorithm>
 #include <cstring>
 
@@ -22,7 +22,7 @@ static int released_eval(amm_ctx *, void *, const double *, double *, int, doubl
 }
 static void released_free(void *) {}
 
-// One row per AMM_FORCE_* value (a released id and the twelve families), in the enum's order: noun phrase, tag, entry points, bad-id wording, single rank, eval, free.
+// One row per AMM_FORCE_* value (a released id and the thirteen families), in the enum's order: noun phrase, tag, entry points, bad-id wording, single rank, eval, free.
 const ForceFamily &amm_family(int type) {
     static const ForceFamily rows[AMM_FORCE_TYPES] = {
         {"a released id", "AMM_FORCE_RELEASED", "none", "released force id", false, released_eval, released_free},
@@ -51,6 +51,8 @@ const ForceFamily &amm_family(int type) {
          eval_as<ManyForce, amm_many_eval_impl>, free_as<ManyForce, amm_many_free>},
         {"an RMSD force", "AMM_FORCE_RMSD", "amm_rmsd_*", "not the id of an RMSD force (AMM_FORCE_RMSD)", true,
          eval_as<RmsdForce, amm_rmsd_eval_impl>, free_as<RmsdForce, amm_rmsd_free>},
+        {"a Gay-Berne force", "AMM_FORCE_GAYBERNE", "amm_gayberne_*", "not the id of a Gay-Berne force (AMM_FORCE_GAYBERNE)", true,
+         eval_as<GayBerneForce, amm_gayberne_eval_impl>, free_as<GayBerneForce, amm_gayberne_free>},
     };
     return rows[type];
 }
@@ -462,5 +464,48 @@ int amm_rmsd_stats(amm_ctx *ctx, int32_t force_id, int64_t *out) {
 }
 
 int amm_rmsd_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_RMSD, "amm_rmsd_release"); }
+
+// GayBerneForce (csrc/gayberne.hip): the interacting particles compacted by the caller, their exceptions as a CSR over the compacted
+// indices and the reverse table of the axis particles
+int amm_gayberne_create(amm_ctx *ctx, const int32_t *h_active, int32_t n_active, const int32_t *h_axes, const double *h_par, const int32_t *h_ex_ptr,
+                        const int32_t *h_ex_col, const double *h_ex_par, const int32_t *h_rev_ptr, const int32_t *h_rev_src, double cutoff,
+                        double switch_distance, int32_t periodic, int32_t *force_id) {
+    if (!ctx || !force_id || !h_rev_ptr || (n_active > 0 && (!h_active || !h_axes || !h_par || !h_ex_ptr))) {
+        amm_set_error("amm_gayberne_create: null argument");
+        return 1;
+    }
+    if (n_active > 0 && h_ex_ptr[n_active] > 0 && (!h_ex_col || !h_ex_par)) {
+        amm_set_error("amm_gayberne_create: null argument");
+        return 1;
+    }
+    if (h_rev_ptr[ctx->n] > 0 && !h_rev_src) {
+        amm_set_error("amm_gayberne_create: null argument");
+        return 1;
+    }
+    GayBerneForce *gf = nullptr;
+    if (amm_gayberne_create_impl(ctx, h_active, n_active, h_axes, h_par, h_ex_ptr, h_ex_col, h_ex_par, h_rev_ptr, h_rev_src, cutoff, switch_distance,
+                                 periodic, &gf))
+        return 1;
+    *force_id = amm_force_register(ctx, AMM_FORCE_GAYBERNE, gf);
+    return 0;
+}
+
+int amm_gayberne_set_params(amm_ctx *ctx, int32_t force_id, const double *h_par, int32_t n_active, const double *h_ex_par, int32_t n_entries) {
+    GayBerneForce *gf = amm_force_get<GayBerneForce>(ctx, force_id, "amm_gayberne_set_params");
+    if (!gf) return 1;
+    return amm_gayberne_set_params_impl(ctx, gf, h_par, n_active, h_ex_par, n_entries);
+}
+
+int amm_gayberne_stats(amm_ctx *ctx, int32_t force_id, int64_t *out) {
+    GayBerneForce *gf = amm_force_get<GayBerneForce>(ctx, force_id, "amm_gayberne_stats");
+    if (!gf) return 1;
+    if (!out) {
+        amm_set_error("amm_gayberne_stats: null argument");
+        return 1;
+    }
+    return amm_gayberne_stats_impl(ctx, gf, out);
+}
+
+int amm_gayberne_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_GAYBERNE, "amm_gayberne_release"); }
 
 }   // extern "C"

@@ -255,6 +255,7 @@ class _Entry:
         self.hbond = None           # a CustomHbondForce (csrc/hbond.hip): dict(id, variables); the id is also in term_ids, term_expr is
                                     # set, `program` is that of expr.compile_hbond
         self.rmsd = None            # an RMSDForce (csrc/rmsd.hip): its backend id, which is also in term_ids
+        self.gayberne = None        # a GayBerneForce (csrc/gayberne.hip): its backend id, which is also in term_ids
         self.many = None            # a CustomManyParticleForce (csrc/manyparticle.hip): dict(id, variables, types); carried as hbond is,
                                     # `program` is that of expr.compile_many_particle
 
@@ -281,6 +282,66 @@ def many_particle_table(filters, types, central):
                         table[a, b, c] = code
                         break
     return table
+
+
+def gayberne_tables(force, n):
+    """What a GayBerneForce hands to the Gay-Berne kernels (csrc/gayberne.hip), checked against a System of n particles:
+    active   int32 [A]: the interacting particles, ascending -- epsilon > 0, or a member of an exception with epsilon > 0;
+    axes     int32 [A][2]: x- and y-particle of the row, -1: none;
+    par      float64 [A][8]: sigma, epsilon, sx, sy, sz, ex, ey, ez;
+    ex_ptr / ex_col / ex_par   the exceptions between active particles as a CSR over rows: columns are ACTIVE indices, ascending,
+             (sigma, epsilon) per entry, every pair on both rows (an exception with an inactive member can only have epsilon 0 and a
+             partner that the scan never meets: it is dropped);
+    rev_ptr / rev_src   int32 [n + 1] / [.]: per particle the entries 2 * row + (0: x-particle, 1: y-particle) that name it, ascending.
+    Raises OpenMMException by name for what the definition forbids."""
+    cls = 'GayBerneForce'
+    if force.getNumParticles() != n:
+        raise mm.OpenMMException('%s: the force has %d particles, the System %d' % (cls, force.getNumParticles(), n))
+    rows = force._particles
+    for i, (sigma, eps, xp, yp, sx, sy, sz, ex, ey, ez) in enumerate(rows):
+        if not (-1 <= xp < n and -1 <= yp < n):
+            raise mm.OpenMMException('%s: an axis particle of particle %d is out of range' % (cls, i))
+        if xp == i or yp == i:
+            raise mm.OpenMMException('%s: particle %d is its own axis particle' % (cls, i))
+        if sigma < 0.0 or eps < 0.0 or min(sx, sy, sz) <= 0.0 or min(ex, ey, ez) <= 0.0:
+            raise mm.OpenMMException('%s: particle %d needs sigma, epsilon >= 0 and diameters and well-depth scales above zero' % (cls, i))
+        if xp == -1 and not (sx == sy == sz and ex == ey == ez):
+            raise mm.OpenMMException('%s: particle %d has no x-particle, which only a sphere (sx = sy = sz, ex = ey = ez) may omit' % (cls, i))
+        if xp == -1 and yp != -1:
+            raise mm.OpenMMException('%s: particle %d has a y-particle and no x-particle' % (cls, i))
+        if yp == -1 and not (sy == sz and ey == ez):
+            raise mm.OpenMMException('%s: particle %d has no y-particle, which only a uniaxial shape (sy = sz, ey = ez) may omit' % (cls, i))
+    pairs = {}
+    for k, (i, j, sigma, eps) in enumerate(force._exceptions):
+        if not (0 <= i < n and 0 <= j < n) or i == j:
+            raise mm.OpenMMException('%s: exception %d names a particle that does not exist, or one particle twice' % (cls, k))
+        if sigma < 0.0 or eps < 0.0:
+            raise mm.OpenMMException('%s: exception %d needs sigma, epsilon >= 0' % (cls, k))
+        key = (min(i, j), max(i, j))
+        if key in pairs:
+            raise mm.OpenMMException('%s: two exceptions for particles %d and %d' % ((cls,) + key))
+        pairs[key] = (sigma, eps)
+    interacting = {i for i, row in enumerate(rows) if row[1] > 0.0}
+    interacting |= {m for key, (_, eps) in pairs.items() if eps > 0.0 for m in key}
+    active = np.array(sorted(interacting), dtype=np.int32)
+    act_of = {int(p): k for k, p in enumerate(active)}
+    axes = np.array([[rows[p][2], rows[p][3]] for p in active], dtype=np.int32).reshape(-1, 2)
+    par = np.array([rows[p][:2] + rows[p][4:] for p in active], dtype=np.float64).reshape(-1, 8)
+    entries = sorted((act_of[a], act_of[b], v) for (i, j), v in pairs.items() if i in act_of and j in act_of
+                     for a, b in ((i, j), (j, i)))
+    ex_ptr = np.zeros(len(active) + 1, dtype=np.int32)
+    for r, _, _ in entries:
+        ex_ptr[r + 1] += 1
+    ex_ptr = np.cumsum(ex_ptr, dtype=np.int32)
+    ex_col = np.array([c for _, c, _ in entries], dtype=np.int32)
+    ex_par = np.array([v for _, _, v in entries], dtype=np.float64).reshape(-1, 2)
+    named = sorted((int(axes[k, r]), 2 * k + r) for k in range(len(active)) for r in range(2) if axes[k, r] >= 0)
+    rev_ptr = np.zeros(n + 1, dtype=np.int32)
+    for p, _ in named:
+        rev_ptr[p + 1] += 1
+    rev_ptr = np.cumsum(rev_ptr, dtype=np.int32)
+    rev_src = np.array([src for _, src in named], dtype=np.int32)
+    return dict(active=active, axes=axes, par=par, ex_ptr=ex_ptr, ex_col=ex_col, ex_par=ex_par, rev_ptr=rev_ptr, rev_src=rev_src)
 
 
 def slice_bounds(n_items, rank, world):
@@ -364,6 +425,8 @@ class Engine:
         self._check_custom_gb(system, integrator)
         self._check_hbond(system, integrator)
         self._check_many_particle(system, integrator)
+        if self.world > 1 and any(isinstance(f, mm.GayBerneForce) for f in system.getForces()):
+            raise InputError('a GayBerneForce runs on a single rank: its wavefronts walk all pairs of ellipsoids and are not sliced')
         self._check_massless(system, integrator)
         if self.free_space and self.world > 1:
             raise InputError('a System in free space (NoCutoff / CutoffNonPeriodic) runs on a single rank: its pair forces walk all pairs '
@@ -923,6 +986,58 @@ class Engine:
             raise mm.OpenMMException('many_stats: the force does not belong to this Context')
         return self.ctx.many_stats(hits[0].many['id'])
 
+    GAYBERNE_MAX = 32768      # csrc/gayberne.hip: AMM_GY_MAX_ROWS interacting particles
+
+    def _translate_gayberne(self, force, entry):
+        """A GayBerneForce: the interacting particles compacted, their exceptions as a CSR and the reverse table of the axis particles
+        (gayberne_tables) go to the Gay-Berne kernels (csrc/gayberne.hip).  One backend force carried in entry.term_ids, so every
+        loop over an entry's forces reaches it and the scheduler's fusion rules decline its group, as they do for a hydrogen-bond
+        force.  It reads no Context parameter: deriv(energy, p) sees no dependence through it."""
+        cls = 'GayBerneForce'
+        method = force.getNonbondedMethod()
+        periodic = method == force.CutoffPeriodic
+        if periodic and self.free_space:
+            raise InputError('%s uses CutoffPeriodic in a System in free space' % cls)
+        n = self.n
+        rc = 0.0 if method == force.NoCutoff else float(force._cutoff)
+        if method != force.NoCutoff and not rc > 0.0:
+            raise InputError('%s: the cutoff distance must be above zero' % cls)
+        rs = -1.0
+        if method != force.NoCutoff and force.getUseSwitchingFunction():
+            rs = float(force._switch)
+            if not 0.0 <= rs < rc:
+                raise InputError('%s: the switching distance %g lies outside [0, cutoff = %g)' % (cls, rs, rc))
+        if periodic and rc > 0.5 * float(self.box.min()):
+            raise InputError('%s: the cutoff %g exceeds half the shortest box edge (%g)' % (cls, rc, float(self.box.min())))
+        tab = gayberne_tables(force, n)
+        if len(tab['active']) > self.GAYBERNE_MAX:
+            raise InputError('%s: %d particles with epsilon > 0 (limit %d)' % (cls, len(tab['active']), self.GAYBERNE_MAX))
+        try:
+            fid = self.ctx.gayberne_create(tab['active'], tab['axes'], tab['par'], tab['ex_ptr'], tab['ex_col'], tab['ex_par'], tab['rev_ptr'],
+                                           tab['rev_src'], rc=rc, rs=rs, periodic=periodic)
+        except B.HipError as exc:
+            raise InputError('%s: %s' % (cls, exc))
+        entry.term_ids.append(fid)
+        entry.gayberne = fid
+
+        def reload():          # updateParametersInContext: the particle and exception parameters are read again
+            new = gayberne_tables(force, n)
+            for key, what in (('active', 'the set of interacting particles (epsilon > 0, or in an exception with epsilon > 0)'),
+                              ('axes', 'the x- or y-particle of an ellipsoid'), ('ex_ptr', 'the pairs that have an exception'),
+                              ('ex_col', 'the pairs that have an exception')):
+                if not np.array_equal(new[key], tab[key]):
+                    raise mm.OpenMMException('updateParametersInContext: %s has changed' % what)
+            self.ctx.gayberne_set_params(fid, new['par'], new['ex_par'])
+            return 'values'
+        entry.reload = reload
+
+    def gayberne_stats(self, force):
+        """dict(active, scanned, survivors, launches, chunks) of a GayBerneForce of this Context (backend.HipContext.gayberne_stats)."""
+        hits = [e for e in self.entries if e.force is force and getattr(e, 'gayberne', None) is not None]
+        if not hits:
+            raise mm.OpenMMException('gayberne_stats: the force does not belong to this Context')
+        return self.ctx.gayberne_stats(hits[0].gayberne)
+
     def _translate_gb(self, force, entry):
         """A GBSAOBCForce: one backend force (csrc/gb.hip) carried in entry.term_ids, so every loop over an entry's forces reaches it
         and the scheduler's fusion rules decline its group, as they do for a term-expression force."""
@@ -1125,6 +1240,8 @@ class Engine:
             self._translate_hbond(force, entry)
         elif isinstance(force, mm.CustomManyParticleForce):
             self._translate_many_particle(force, entry)
+        elif isinstance(force, mm.GayBerneForce):
+            self._translate_gayberne(force, entry)
         elif isinstance(force, mm.CMAPTorsionForce):
             self._translate_cmap(force, entry)
         elif isinstance(force, mm.RBTorsionForce):

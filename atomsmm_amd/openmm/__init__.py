@@ -1012,6 +1012,100 @@ class RMSDForce(Force):
         context._engine.update_force_parameters(self)
 
 
+class GayBerneForce(Force):
+    """Ellipsoids with the Gay-Berne pair energy (csrc/gayberne.hip).  A particle's frame: x along r_i - r_xparticle,
+    y the part of r_i - r_yparticle perpendicular to it, z = x cross y; the diameters sx, sy, sz and the well-depth scales ex, ey, ez
+    belong to those axes.  xparticle = -1 needs a sphere (sx = sy = sz, ex = ey = ez), yparticle = -1 a uniaxial shape (sy = sz,
+    ey = ez).  sigma = (sigma1 + sigma2) / 2, epsilon = sqrt(epsilon1 epsilon2) unless an exception gives both; shapes always come
+    from the particles.  The torque on an ellipsoid comes back as forces on its x- and y-particle."""
+    NoCutoff, CutoffNonPeriodic, CutoffPeriodic = range(3)
+
+    def __init__(self):
+        Force.__init__(self)
+        self._particles = []       # [sigma, epsilon, xparticle, yparticle, sx, sy, sz, ex, ey, ez]
+        self._exceptions = []      # [i, j, sigma, epsilon]
+        self._exc_index = {}
+        self._method = self.NoCutoff
+        self._cutoff = 1.0
+        self._use_switch = False
+        self._switch = -1.0
+
+    def usesPeriodicBoundaryConditions(self):
+        return self._method == self.CutoffPeriodic
+
+    def getNonbondedMethod(self):
+        return self._method
+
+    def setNonbondedMethod(self, method):
+        if int(method) not in (self.NoCutoff, self.CutoffNonPeriodic, self.CutoffPeriodic):
+            raise OpenMMException('GayBerneForce: Illegal value for nonbonded method')
+        self._method = int(method)
+
+    def getCutoffDistance(self):
+        return Quantity(self._cutoff, nm)
+
+    def setCutoffDistance(self, distance):
+        self._cutoff = float(md_value(distance))
+
+    def getUseSwitchingFunction(self):
+        return self._use_switch
+
+    def setUseSwitchingFunction(self, use):
+        self._use_switch = bool(use)
+
+    def getSwitchingDistance(self):
+        return Quantity(self._switch, nm)
+
+    def setSwitchingDistance(self, distance):
+        self._switch = float(md_value(distance))
+
+    @staticmethod
+    def _particle_record(sigma, epsilon, xparticle, yparticle, sx, sy, sz, ex, ey, ez):
+        return [float(md_value(sigma)), float(md_value(epsilon)), int(xparticle), int(yparticle), float(md_value(sx)), float(md_value(sy)),
+                float(md_value(sz)), float(ex), float(ey), float(ez)]
+
+    def getNumParticles(self):
+        return len(self._particles)
+
+    def addParticle(self, sigma, epsilon, xparticle, yparticle, sx, sy, sz, ex, ey, ez):
+        self._particles.append(self._particle_record(sigma, epsilon, xparticle, yparticle, sx, sy, sz, ex, ey, ez))
+        return len(self._particles) - 1
+
+    def getParticleParameters(self, index):
+        sigma, epsilon, xp, yp, sx, sy, sz, ex, ey, ez = self._particles[index]
+        return [Quantity(sigma, nm), Quantity(epsilon, kjmol), xp, yp, Quantity(sx, nm), Quantity(sy, nm), Quantity(sz, nm), ex, ey, ez]
+
+    def setParticleParameters(self, index, sigma, epsilon, xparticle, yparticle, sx, sy, sz, ex, ey, ez):
+        self._particles[index] = self._particle_record(sigma, epsilon, xparticle, yparticle, sx, sy, sz, ex, ey, ez)
+
+    def getNumExceptions(self):
+        return len(self._exceptions)
+
+    def addException(self, particle1, particle2, sigma, epsilon, replace=False):
+        key = (min(particle1, particle2), max(particle1, particle2))
+        rec = [int(particle1), int(particle2), float(md_value(sigma)), float(md_value(epsilon))]
+        if key in self._exc_index:
+            if not replace:
+                raise OpenMMException('GayBerneForce: There is already an exception for particles %d and %d' % key)
+            self._exceptions[self._exc_index[key]] = rec
+            return self._exc_index[key]
+        self._exceptions.append(rec)
+        self._exc_index[key] = len(self._exceptions) - 1
+        return len(self._exceptions) - 1
+
+    def getExceptionParameters(self, index):
+        i, j, sigma, epsilon = self._exceptions[index]
+        return [i, j, Quantity(sigma, nm), Quantity(epsilon, kjmol)]
+
+    def setExceptionParameters(self, index, particle1, particle2, sigma, epsilon):
+        self._exceptions[index] = [int(particle1), int(particle2), float(md_value(sigma)), float(md_value(epsilon))]
+
+    def updateParametersInContext(self, context):
+        """Upload the particle and exception parameters again.  The interacting particles, their axis particles and the pairs that
+        have an exception must not have changed."""
+        context._engine.update_force_parameters(self)
+
+
 class CustomCVForce(Force, _GlobalParams):
     """Energy = function of collective variables, each the energy of an inner Force object."""
 

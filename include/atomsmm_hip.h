@@ -567,6 +567,37 @@ int amm_rmsd_stats(amm_ctx *ctx, int32_t force_id, int64_t *out);
 /* Free such a force; the id is retired and leaves every group definition. */
 int amm_rmsd_release(amm_ctx *ctx, int32_t force_id);
 
+/* GayBerneForce (force type AMM_FORCE_GAYBERNE; csrc/gayberne.hip): ellipsoids with the anisotropic pair
+ * energy E = U eta chi S(r) of OpenMM's class, the frame of an ellipsoid defined by its x- and y-particle, the torque returned as
+ * forces on those particles (the exact gradient, the roll of the frame about its x axis included).
+ * The caller compacts the INTERACTING particles (epsilon > 0, or in an exception with epsilon > 0): marker atoms never enter the scan.
+ *   h_active[n_active]      their particle indices, ascending
+ *   h_axes[n_active][2]     x- and y-particle of the row (-1: none; no x-particle: a sphere; no y-particle: sy = sz and ey = ez)
+ *   h_par[n_active][8]      sigma, epsilon, sx, sy, sz, ex, ey, ez (nm, kJ/mol, nm x 3, pure numbers)
+ *   h_ex_ptr[n_active + 1], h_ex_col[], h_ex_par[][2]   the exceptions as a CSR over active rows: columns are active indices,
+ *                           ascending within a row; (sigma, epsilon) per entry, epsilon 0 removes the pair; every pair on both rows
+ *   h_rev_ptr[n + 1], h_rev_src[]   per particle of the context the entries 2 * row + (0: x-particle, 1: y-particle) that name it,
+ *                           ascending: the order in which the spread adds them
+ *   cutoff                  0: NoCutoff; above 0: pairs at r >= cutoff contribute nothing (no shift)
+ *   switch_distance         below 0: none; else S = 1 - 10 t^3 + 15 t^4 - 6 t^5, t = (r - switch_distance) / (cutoff - switch_distance)
+ *   periodic                minimum images for the pair AND for the frames; needs cutoff <= half the shortest box edge
+ * Refused, each with AMM_FORCE_GAYBERNE in the message: more than 32768 active particles, an index out of range, an axis particle
+ * that is the particle itself, a shape its axes cannot orient, tables that are not ordered or not consistent, a switching distance
+ * outside [0, cutoff), more than one rank (also amm_set_slice while such a force lives).  An ordinary member of a group; no inner
+ * force of amm_cv_create.  fp64, no atomics, fixed order of summation: the same positions give the same bits.  All pairs of active
+ * particles are scanned, each pair evaluated from both sides; four launches per evaluation. */
+int amm_gayberne_create(amm_ctx *ctx, const int32_t *h_active, int32_t n_active, const int32_t *h_axes, const double *h_par, const int32_t *h_ex_ptr,
+                        const int32_t *h_ex_col, const double *h_ex_par, const int32_t *h_rev_ptr, const int32_t *h_rev_src, double cutoff,
+                        double switch_distance, int32_t periodic, int32_t *force_id);
+/* setParticleParameters / setExceptionParameters + updateParametersInContext: new values in the layout of creation; the counts, the
+ * axes and the sparsity of the exceptions stay.  Waits for the stream.  A refused call leaves the force as it was. */
+int amm_gayberne_set_params(amm_ctx *ctx, int32_t force_id, const double *h_par, int32_t n_active, const double *h_ex_par, int32_t n_entries);
+/* out[0]: active rows; out[1]: ordered pairs an evaluation tests; out[2]: those that passed the cutoff and the exceptions in the last
+ * evaluation (each pair from both sides); out[3]: launches so far; out[4]: chunks a row's columns are split into. */
+int amm_gayberne_stats(amm_ctx *ctx, int32_t force_id, int64_t *out);
+/* Free such a force; the id is retired and leaves every group definition. */
+int amm_gayberne_release(amm_ctx *ctx, int32_t force_id);
+
 /* Reciprocal space of a NonbondedForce with nonbondedMethod PME / Ewald, as RESPASystem and FarNonbondedForce
  * keep it in group 2 with the source force's Ewald tolerance / PME parameters (systems.py:74-75,
  * forces.py:185-188; setReciprocalSpaceForceGroup: utils.py:147-152).  Smooth PME, B-spline order 5, grid
