@@ -23,6 +23,7 @@ OP_EVAL, OP_KICK, OP_MOVE, OP_COPY, OP_COMBINE, OP_EXPR, OP_BATH = 1, 2, 3, 4, 5
 OP_SAVE_REF, OP_CONSTRAIN_X, OP_CONSTRAIN_V = 8, 9, 10
 OP_ALLREDUCE = 11
 OP_STOCK = 12
+OP_DRUDE_STEP = 13
 STOCK_VERLET, STOCK_LANGEVIN_MIDDLE, STOCK_LANGEVIN, STOCK_BROWNIAN = range(4)   # amm_stock_define kinds
 VSITE_AVERAGE2, VSITE_AVERAGE3, VSITE_OUT_OF_PLANE = range(3)                     # amm_vsite_define kinds
 EXCHANGE_REDUCE, EXCHANGE_GATHER = 0, 1
@@ -66,6 +67,7 @@ EXPORTS = [
     'amm_many_create', 'amm_many_set_params', 'amm_many_set_globals', 'amm_many_stats', 'amm_many_release',
     'amm_rmsd_create', 'amm_rmsd_set_reference', 'amm_rmsd_stats', 'amm_rmsd_release',
     'amm_gayberne_create', 'amm_gayberne_set_params', 'amm_gayberne_stats', 'amm_gayberne_release',
+    'amm_drude_create', 'amm_drude_set_params', 'amm_drude_release', 'amm_drude_step_define',
     'amm_vsite_define', 'amm_vsite_place', 'amm_vsite_spread', 'amm_vsite_stats',
 ]
 
@@ -232,6 +234,10 @@ def lib():
         L.amm_gayberne_set_params.argtypes = [vp, C.c_int32, dp, C.c_int32, dp, C.c_int32]
         L.amm_gayberne_stats.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
         L.amm_gayberne_release.argtypes = [vp, C.c_int32]
+        L.amm_drude_create.argtypes = [vp, ip, dp, C.c_int32, ip, dp, C.c_int32, C.c_int32, ip]
+        L.amm_drude_set_params.argtypes = [vp, C.c_int32, ip, dp, C.c_int32, ip, dp, C.c_int32]
+        L.amm_drude_release.argtypes = [vp, C.c_int32]
+        L.amm_drude_step_define.argtypes = [vp, ip, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, ip]
         L.amm_cv_create.argtypes = [vp, ip, C.c_int32, C.c_int32, ip, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip]
         L.amm_cv_set_globals.argtypes = [vp, C.c_int32, dp, C.c_int32]
         L.amm_cv_set_variables.argtypes = [vp, C.c_int32, dp, C.c_int32]
@@ -842,6 +848,48 @@ class HipContext:
     def gayberne_release(self, fid):
         """Free a Gay-Berne force (its id is retired)."""
         _chk(lib().amm_gayberne_release(self.h, fid))
+
+    def drude_create(self, idx, par, pairs, thole, periodic=False):
+        """A Drude force (csrc/drude.hip).  idx[k]: particle, particle1 .. particle4 of Drude particle k (-1: none); par[k]: charge,
+        polarizability, aniso12, aniso34; pairs[p]: the two Drude entries of screened pair p; thole[p]: its Thole factor."""
+        idx = np.asarray(idx, dtype=np.int32).reshape(-1, 5)
+        par = np.asarray(par, dtype=np.float64).reshape(-1, 4)
+        pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+        thole = np.asarray(thole, dtype=np.float64).reshape(-1)
+        assert len(idx) == len(par) and len(pairs) == len(thole)
+        i_, ip_ = _hi(idx.reshape(-1) if len(idx) else [0])
+        p_, pp = _hd(par.reshape(-1) if len(par) else [0.0])
+        s_, sp = _hi(pairs.reshape(-1) if len(pairs) else [0])
+        t_, tp = _hd(thole if len(thole) else [0.0])
+        fid = C.c_int32(-1)
+        _chk(lib().amm_drude_create(self.h, ip_, pp, len(idx), sp, tp, len(pairs), int(bool(periodic)), C.byref(fid)))
+        return fid.value
+
+    def drude_set_params(self, fid, idx, par, pairs, thole):
+        """New charges, polarizabilities, anisotropies and Thole factors, laid out as at creation; no index may change (waits for the stream)."""
+        idx = np.asarray(idx, dtype=np.int32).reshape(-1, 5)
+        par = np.asarray(par, dtype=np.float64).reshape(-1, 4)
+        pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+        thole = np.asarray(thole, dtype=np.float64).reshape(-1)
+        i_, ip_ = _hi(idx.reshape(-1) if len(idx) else [0])
+        p_, pp = _hd(par.reshape(-1) if len(par) else [0.0])
+        s_, sp = _hi(pairs.reshape(-1) if len(pairs) else [0])
+        t_, tp = _hd(thole if len(thole) else [0.0])
+        _chk(lib().amm_drude_set_params(self.h, fid, ip_, pp, len(idx), sp, tp, len(pairs)))
+
+    def drude_release(self, fid):
+        """Free a Drude force (its id is retired)."""
+        _chk(lib().amm_drude_release(self.h, fid))
+
+    def drude_step_define(self, pairs, dt, friction, kT, drude_friction, drude_kT, max_distance=0.0):
+        """The step of a DrudeLangevinIntegrator for OP_DRUDE_STEP: pairs[k] = (Drude particle, parent); dt in ps, frictions in 1/ps,
+        kT in kJ/mol, the hard wall in nm (0: none)."""
+        pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+        s_, sp = _hi(pairs.reshape(-1) if len(pairs) else [0])
+        sid = C.c_int32(-1)
+        _chk(lib().amm_drude_step_define(self.h, sp, len(pairs), float(dt), float(friction), float(kT), float(drude_friction), float(drude_kT),
+                                         float(max_distance), C.byref(sid)))
+        return sid.value
 
     def cv_create(self, inner_ids, n_deriv, code, consts, globals_):
         """A CustomCVForce with any energy text (csrc/cv.hip): the ids of the inner forces in the order of the collective variables

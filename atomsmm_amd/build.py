@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(CSRC, '_obj')
-SOURCES = ['abi.hip', 'families.hip', 'run_ops.hip', 'pair.hip', 'pair_expr.hip', 'term_expr.hip', 'cv.hip', 'compound.hip', 'cmap.hip', 'cluster.hip', 'group.hip', 'bonded.hip', 'integrate.hip', 'pme.hip', 'expr.hip', 'constraints.hip', 'comm.hip', 'minimize.hip', 'barostat.hip', 'free.hip', 'gb.hip', 'custom_gb.hip', 'hbond.hip', 'manyparticle.hip', 'rmsd.hip', 'gayberne.hip', 'stock.hip', 'vsite.hip']
+SOURCES = ['abi.hip', 'families.hip', 'run_ops.hip', 'pair.hip', 'pair_expr.hip', 'term_expr.hip', 'cv.hip', 'compound.hip', 'cmap.hip', 'cluster.hip', 'group.hip', 'bonded.hip', 'integrate.hip', 'pme.hip', 'expr.hip', 'constraints.hip', 'comm.hip', 'minimize.hip', 'barostat.hip', 'free.hip', 'gb.hip', 'custom_gb.hip', 'hbond.hip', 'manyparticle.hip', 'rmsd.hip', 'gayberne.hip', 'drude.hip', 'stock.hip', 'vsite.hip']
 HEADERS = ['amm_ctx.h', 'pair_math.h', 'pair_tab.h', 'erfcx_table.h', 'device_utils.h', 'expr_vm.h', 'expr_force.h', 'pair_expr_vm.h', 'term_expr_vm.h', 'pair_args.h', 'cluster.h', 'bonded_terms.h', 'compound_geom.h', 'cons_sweeps.h', 'rmsd_fit.h',
            os.path.join('..', '..', 'include', 'atomsmm_hip.h')]
 LIB = os.path.join(HERE, 'libatomsmm_hip.so')

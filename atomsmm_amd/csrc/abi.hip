@@ -97,6 +97,7 @@ int amm_destroy(amm_ctx *ctx) {
     if (ctx->d_expr_part) (void)hipFree(ctx->d_expr_part);
     if (ctx->d_fscratch) (void)hipFree(ctx->d_fscratch);
     if (ctx->constraints) amm_constraints_free(ctx->constraints);
+    amm_drude_steps_free(ctx);
     for (MinObj *mo : ctx->minimizers) amm_min_free(mo);
     if (ctx->alt_x) (void)hipFree(ctx->alt_x);
     if (ctx->alt_v) (void)hipFree(ctx->alt_v);
@@ -146,6 +147,17 @@ int amm_check(amm_ctx *ctx) {
     if (ctx->constraints && amm_constraints_failed(ctx, ctx->constraints)) {
         amm_set_error("constraint solver did not converge (SHAKE / RATTLE, 500 iterations): time step too large or bad geometry");
         return 2;
+    }
+    if (!ctx->drude_steps.empty()) {
+        const int flagged = amm_drude_step_flagged(ctx);
+        if (flagged < 0) {
+            amm_set_error("amm_check: reading the hard wall flag of the Drude step failed");
+            return 1;
+        }
+        if (flagged) {
+            amm_set_error("Drude particle moved too far beyond hard wall constraint");
+            return 2;
+        }
     }
     for (size_t id = 0; id < ctx->forces.size(); ++id) {
         if (ManyForce *mf = ctx->forces[id].as<ManyForce>()) {
@@ -1111,6 +1123,18 @@ int amm_stock_define(amm_ctx *ctx, int32_t kind, double dt, double friction, dou
     sd.b = friction > 0.0 ? (1.0 - sd.a) / friction : dt;
     ctx->stocks.push_back(sd);
     *stock_id = (int32_t)ctx->stocks.size() - 1;
+    return 0;
+}
+
+int amm_drude_step_define(amm_ctx *ctx, const int32_t *h_pairs, int32_t n_pairs, double dt, double friction, double kT, double drude_friction,
+                          double drude_kT, double max_distance, int32_t *step_id) {
+    if (!ctx || !step_id || (n_pairs > 0 && !h_pairs)) {
+        amm_set_error("amm_drude_step_define: null argument");
+        return 1;
+    }
+    int id = -1;
+    if (amm_drude_step_define_impl(ctx, h_pairs, n_pairs, dt, friction, kT, drude_friction, drude_kT, max_distance, &id)) return 1;
+    *step_id = id;
     return 0;
 }
 

@@ -262,14 +262,15 @@ struct HbondForce;    // hbond.hip: a CustomHbondForce -- donors against accepto
 struct ManyForce;     // manyparticle.hip: a CustomManyParticleForce -- sets of three particles under a cutoff, the energy written as text
 struct RmsdForce;     // rmsd.hip: an RMSDForce -- the deviation of selected particles from a reference after the best rigid fit
 struct GayBerneForce; // gayberne.hip: a GayBerneForce -- ellipsoids whose frames other particles define, over all pairs of interacting particles
+struct DrudeForce;    // drude.hip: a DrudeForce -- anisotropic springs between Drude particles and their parents, Thole-screened dipole pairs
 // The force families.  A family is described ONCE: its tag here, the struct that goes with the tag in amm_force_type, and its row of
 // the table behind amm_family (families.hip).  The typed lookup and its refusals, amm_force_eval_dispatch, release, amm_destroy, amm_set_slice and
 // cv.hip's messages all read the row -- a new family adds these three lines, its own .hip file and its extern "C" entry points.
-// Thirteen families today (and the tag of a released id).
+// Fourteen families today (and the tag of a released id).
 enum : int { AMM_FORCE_RELEASED = 0, AMM_FORCE_PAIR = 1, AMM_FORCE_BONDED = 2, AMM_FORCE_PME = 3, AMM_FORCE_TERM_EXPR = 4, AMM_FORCE_CV = 5,
              AMM_FORCE_COMPOUND = 6, AMM_FORCE_GB = 7, AMM_FORCE_CMAP = 8, AMM_FORCE_CUSTOM_GB = 9, AMM_FORCE_HBOND = 10,
-             AMM_FORCE_MANY_PARTICLE = 11, AMM_FORCE_RMSD = 12, AMM_FORCE_GAYBERNE = 13,
-             AMM_FORCE_TYPES = 14 };   // ForceObj::type, the row amm_family returns
+             AMM_FORCE_MANY_PARTICLE = 11, AMM_FORCE_RMSD = 12, AMM_FORCE_GAYBERNE = 13, AMM_FORCE_DRUDE = 14,
+             AMM_FORCE_TYPES = 15 };   // ForceObj::type, the row amm_family returns
 template <class T> inline constexpr int amm_force_type = -1;
 template <> inline constexpr int amm_force_type<PairForce> = AMM_FORCE_PAIR;
 template <> inline constexpr int amm_force_type<BondedSet> = AMM_FORCE_BONDED;
@@ -284,6 +285,7 @@ template <> inline constexpr int amm_force_type<HbondForce> = AMM_FORCE_HBOND;
 template <> inline constexpr int amm_force_type<ManyForce> = AMM_FORCE_MANY_PARTICLE;
 template <> inline constexpr int amm_force_type<RmsdForce> = AMM_FORCE_RMSD;
 template <> inline constexpr int amm_force_type<GayBerneForce> = AMM_FORCE_GAYBERNE;
+template <> inline constexpr int amm_force_type<DrudeForce> = AMM_FORCE_DRUDE;
 struct ForceFamily {
     const char *noun, *tag, *prefix;   // "a CMAP force", "AMM_FORCE_CMAP", "amm_cmap_*"
     const char *bad_id;                // what the family's entry points say of an id that is not theirs (behind "<entry point>: " if they name themselves)
@@ -331,6 +333,16 @@ struct BathDef {
 struct StockDef {
     int kind = 0;                  // AMM_STOCK_*
     double dt = 0, friction = 0, kT = 0, a = 1, b = 0;
+};
+
+// The step of a DrudeLangevinIntegrator (amm_drude_step_define; drude.hip): a, b as in StockDef from the friction of the ordinary atoms
+// and of the centres of mass, aD, bD from the friction of the relative motion of a pair; wall: the hard wall distance, 0: none
+struct DrudeStepDef {
+    double dt = 0, kT = 0, kTD = 0, a = 1, b = 0, aD = 1, bD = 0, wall = 0;
+    int n_pairs = 0;
+    int *d_drude_of = nullptr;     // [n] the Drude particle an atom is the parent of, -1: none
+    int *d_parent_of = nullptr;    // [n] the parent of a Drude particle, -1: not a Drude particle
+    int *d_flag = nullptr;         // set when a pair is beyond twice the hard wall (amm_check reads and clears it)
 };
 
 // Regulated mode of a context (RegulatedTranslationPropagator, propagators.py:1537-1575): every AMM_OP_MOVE is
@@ -474,6 +486,7 @@ struct amm_ctx {
     std::vector<ExprDef> exprs;    // registered per-DOF expressions (AMM_OP_EXPR)
     std::vector<BathDef> baths;    // registered baths (AMM_OP_BATH)
     std::vector<StockDef> stocks;  // registered stock integrators (AMM_OP_STOCK)
+    std::vector<DrudeStepDef> drude_steps;   // registered Drude steps (AMM_OP_DRUDE_STEP)
     IsoDef iso;                    // isokinetic mode: what AMM_OP_KICK means (amm_iso_define)
     RegDef reg;                    // regulated mode: what AMM_OP_MOVE means (amm_regulated_define)
     unsigned long long expr_seed = 0, expr_counter = 0;
@@ -675,6 +688,19 @@ int amm_gayberne_set_params_impl(amm_ctx *ctx, GayBerneForce *gf, const double *
 int amm_gayberne_eval_impl(amm_ctx *ctx, GayBerneForce *gf, const double *d_pos, double *d_force, int accumulate, double *d_energy);
 int amm_gayberne_stats_impl(amm_ctx *ctx, GayBerneForce *gf, int64_t out[5]);
 void amm_gayberne_free(GayBerneForce *gf);
+// drude.hip: a force of type AMM_FORCE_DRUDE (the tables are those of amm_drude_create, include/atomsmm_hip.h) and the step of
+// AMM_OP_DRUDE_STEP
+int amm_drude_create_impl(amm_ctx *ctx, const int32_t *h_idx, const double *h_par, int n_spring, const int32_t *h_pent, const double *h_thole,
+                          int n_pair, int periodic, DrudeForce **out);
+int amm_drude_set_params_impl(amm_ctx *ctx, DrudeForce *df, const int32_t *h_idx, const double *h_par, int n_spring, const int32_t *h_pent,
+                              const double *h_thole, int n_pair);
+int amm_drude_eval_impl(amm_ctx *ctx, DrudeForce *df, const double *d_pos, double *d_force, int accumulate, double *d_energy);
+void amm_drude_free(DrudeForce *df);
+int amm_drude_step_define_impl(amm_ctx *ctx, const int32_t *h_pairs, int n_pairs, double dt, double friction, double kT, double drude_friction,
+                               double drude_kT, double max_distance, int *id);
+int amm_drude_step_impl(amm_ctx *ctx, const DrudeStepDef &D, const double *d_f, unsigned long long counter);
+int amm_drude_step_flagged(amm_ctx *ctx);
+void amm_drude_steps_free(amm_ctx *ctx);
 // implemented in pair.hip / cells.hip / bonded.hip / integrate.hip
 int amm_pair_build_consts(const amm_pair_desc &d, PairConsts &pc);
 int amm_pair_eval_impl(amm_ctx *ctx, PairForce *pf, const double *d_pos, double *d_force, int accumulate,

@@ -1,7 +1,7 @@
 // atomsmm_amd/csrc/families.hip -- the table of force families (amm_ctx.h: ForceFamily) and everything derived from it: the typed lookup
 // with its refusals, registration, release and the dispatch of an evaluation; then the extern "C" entry points of the families whose
 // implementation is a .hip file of its own (term expressions, collective variables, compound bonds, generalized Born, CMAP, custom
-// generalized Born, hydrogen bonds, many-particle sets, RMSD, Gay-Berne ellipsoids).
+// generalized Born, hydrogen bonds, many-particle sets, RMSD, Gay-Berne ellipsoids, Drude oscillators).
 #include <algorithm>
 #include <cstring>
 
@@ -22,7 +22,7 @@ static int released_eval(amm_ctx *, void *, const double *, double *, int, doubl
 }
 static void released_free(void *) {}
 
-// One row per AMM_FORCE_* value (a released id and the thirteen families), in the enum's order: noun phrase, tag, entry points, bad-id wording, single rank, eval, free.
+// One row per AMM_FORCE_* value (a released id and the fourteen families), in the enum's order: noun phrase, tag, entry points, bad-id wording, single rank, eval, free.
 const ForceFamily &amm_family(int type) {
     static const ForceFamily rows[AMM_FORCE_TYPES] = {
         {"a released id", "AMM_FORCE_RELEASED", "none", "released force id", false, released_eval, released_free},
@@ -53,6 +53,8 @@ const ForceFamily &amm_family(int type) {
          eval_as<RmsdForce, amm_rmsd_eval_impl>, free_as<RmsdForce, amm_rmsd_free>},
         {"a Gay-Berne force", "AMM_FORCE_GAYBERNE", "amm_gayberne_*", "not the id of a Gay-Berne force (AMM_FORCE_GAYBERNE)", true,
          eval_as<GayBerneForce, amm_gayberne_eval_impl>, free_as<GayBerneForce, amm_gayberne_free>},
+        {"a Drude force", "AMM_FORCE_DRUDE", "amm_drude_*", "not the id of a Drude force (AMM_FORCE_DRUDE)", true,
+         eval_as<DrudeForce, amm_drude_eval_impl>, free_as<DrudeForce, amm_drude_free>},
     };
     return rows[type];
 }
@@ -507,5 +509,27 @@ int amm_gayberne_stats(amm_ctx *ctx, int32_t force_id, int64_t *out) {
 }
 
 int amm_gayberne_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_GAYBERNE, "amm_gayberne_release"); }
+
+// DrudeForce (csrc/drude.hip): the rows of the object model; the library derives the spring constants and the pair parameters
+int amm_drude_create(amm_ctx *ctx, const int32_t *h_idx, const double *h_par, int32_t n_drude, const int32_t *h_pair, const double *h_thole,
+                     int32_t n_pairs, int32_t periodic, int32_t *force_id) {
+    if (!ctx || !force_id || (n_drude > 0 && (!h_idx || !h_par)) || (n_pairs > 0 && (!h_pair || !h_thole))) {
+        amm_set_error("amm_drude_create: null argument");
+        return 1;
+    }
+    DrudeForce *df = nullptr;
+    if (amm_drude_create_impl(ctx, h_idx, h_par, n_drude, h_pair, h_thole, n_pairs, periodic, &df)) return 1;
+    *force_id = amm_force_register(ctx, AMM_FORCE_DRUDE, df);
+    return 0;
+}
+
+int amm_drude_set_params(amm_ctx *ctx, int32_t force_id, const int32_t *h_idx, const double *h_par, int32_t n_drude, const int32_t *h_pair,
+                         const double *h_thole, int32_t n_pairs) {
+    DrudeForce *df = amm_force_get<DrudeForce>(ctx, force_id, "amm_drude_set_params");
+    if (!df) return 1;
+    return amm_drude_set_params_impl(ctx, df, h_idx, h_par, n_drude, h_pair, h_thole, n_pairs);
+}
+
+int amm_drude_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_DRUDE, "amm_drude_release"); }
 
 }   // extern "C"

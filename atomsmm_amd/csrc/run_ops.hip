@@ -691,6 +691,25 @@ struct OpRun {
             // (the launch evaluated the lists' displacement triggers -- for the atoms it moved, not for sites placed since)
             if (!ctx->vsites) amm_watch_moved(ctx);
         } break;
+        case AMM_OP_DRUDE_STEP: {
+            const double *f = slot(op.b);
+            if (op.a < 0 || op.a >= (int)ctx->drude_steps.size()) {
+                amm_set_error("amm_run_ops: DRUDE_STEP with an unknown step id");
+                return FAILED;
+            }
+            if (!f) {
+                amm_set_error("amm_run_ops: DRUDE_STEP force buffer not bound");
+                return FAILED;
+            }
+            if (ctx->iso.on || ctx->reg.on) {
+                amm_set_error("amm_run_ops: DRUDE_STEP does not run in the isokinetic or the regulated mode");
+                return FAILED;
+            }
+            if (complete(f)) return FAILED;
+            if (amm_drude_step_impl(ctx, ctx->drude_steps[op.a], f, (1ull << 63) | ++ctx->expr_counter)) return FAILED;
+            if (x_written()) return FAILED;
+            if (!ctx->vsites) amm_watch_moved(ctx);
+        } break;
         case AMM_OP_ALLREDUCE: {
             if (!slot(op.a)) {
                 amm_set_error("amm_run_ops: ALLREDUCE of an unbound buffer");

@@ -256,6 +256,7 @@ class _Entry:
                                     # set, `program` is that of expr.compile_hbond
         self.rmsd = None            # an RMSDForce (csrc/rmsd.hip): its backend id, which is also in term_ids
         self.gayberne = None        # a GayBerneForce (csrc/gayberne.hip): its backend id, which is also in term_ids
+        self.drude = None           # a DrudeForce (csrc/drude.hip): its backend id, which is also in term_ids
         self.many = None            # a CustomManyParticleForce (csrc/manyparticle.hip): dict(id, variables, types); carried as hbond is,
                                     # `program` is that of expr.compile_many_particle
 
@@ -344,6 +345,47 @@ def gayberne_tables(force, n):
     return dict(active=active, axes=axes, par=par, ex_ptr=ex_ptr, ex_col=ex_col, ex_par=ex_par, rev_ptr=rev_ptr, rev_src=rev_src)
 
 
+def drude_tables(force, n, constrained=()):
+    """What a DrudeForce hands to the Drude kernels (csrc/drude.hip), checked against a System of n particles whose
+    constrained particles are `constrained`:
+    idx      int32 [D][5]: particle, particle1 .. particle4 (-1: none);
+    par      float64 [D][4]: charge, polarizability, aniso12, aniso34;
+    pairs    int32 [P][2]: the two Drude entries of a screened pair;  thole  float64 [P].
+    Raises OpenMMException by name for what the definition forbids."""
+    cls = 'DrudeForce'
+    rows = force._particles
+    held = set(int(c) for c in constrained)
+    seen = {}
+    for k, (p, p1, p2, p3, p4, q, alpha, a12, a34) in enumerate(rows):
+        if not (0 <= p < n and 0 <= p1 < n):
+            raise mm.OpenMMException('%s: Drude particle %d names a particle or a parent that is out of range' % (cls, k))
+        if not all(-1 <= a < n for a in (p2, p3, p4)):
+            raise mm.OpenMMException('%s: Drude particle %d names an anisotropy particle that is out of range' % (cls, k))
+        for a in (p, p1):
+            if a in seen or p == p1:
+                raise mm.OpenMMException('%s: particle %d is listed twice as a Drude particle or a parent (Drude particles %d and %d)'
+                                         % (cls, a, seen.get(a, k), k))
+        seen[p] = seen[p1] = k
+        if p in held:
+            raise mm.OpenMMException('%s: Drude particle %d (particle %d) is constrained' % (cls, k, p))
+        if p2 == p1 or (p3 != -1 and p3 == p4):
+            raise mm.OpenMMException('%s: an anisotropy direction of Drude particle %d joins a particle to itself' % (cls, k))
+        a1 = a12 if p2 != -1 else 1.0
+        a2 = a34 if (p3 != -1 and p4 != -1) else 1.0
+        if not alpha > 0.0:
+            raise mm.OpenMMException('%s: Drude particle %d needs a polarizability above zero' % (cls, k))
+        if not (a1 > 0.0 and a2 > 0.0 and 3.0 - a1 - a2 > 0.0):
+            raise mm.OpenMMException('%s: Drude particle %d needs aniso12, aniso34 and 3 - aniso12 - aniso34 above zero' % (cls, k))
+    for k, (d1, d2, thole) in enumerate(force._pairs):
+        if not (0 <= d1 < len(rows) and 0 <= d2 < len(rows)) or d1 == d2:
+            raise mm.OpenMMException('%s: screened pair %d names a Drude particle that does not exist, or one twice' % (cls, k))
+    idx = np.array([r[:5] for r in rows], dtype=np.int32).reshape(-1, 5)
+    par = np.array([r[5:] for r in rows], dtype=np.float64).reshape(-1, 4)
+    pairs = np.array([r[:2] for r in force._pairs], dtype=np.int32).reshape(-1, 2)
+    thole = np.array([r[2] for r in force._pairs], dtype=np.float64)
+    return dict(idx=idx, par=par, pairs=pairs, thole=thole)
+
+
 def slice_bounds(n_items, rank, world):
     """[begin, end) of rank's contiguous slice of n_items cell-sorted slots: ceil(n / world) each, the same formula as the
     HIP library (csrc/pair.hip first_build).  Atom decomposition: every rank holds all positions and
@@ -427,6 +469,7 @@ class Engine:
         self._check_many_particle(system, integrator)
         if self.world > 1 and any(isinstance(f, mm.GayBerneForce) for f in system.getForces()):
             raise InputError('a GayBerneForce runs on a single rank: its wavefronts walk all pairs of ellipsoids and are not sliced')
+        self._check_drude(system, integrator)
         self._check_massless(system, integrator)
         if self.free_space and self.world > 1:
             raise InputError('a System in free space (NoCutoff / CutoffNonPeriodic) runs on a single rank: its pair forces walk all pairs '
@@ -543,6 +586,63 @@ class Engine:
             what = 'the native Nose-Hoover-Langevin bath'
         if what is not None:
             raise InputError('a System with massless particles or virtual sites does not run with %s' % what)
+
+    def _check_drude(self, system, integrator):
+        """A DrudeForce or a DrudeLangevinIntegrator: what they cannot run with is refused here, by name, when the Context is created."""
+        forces = [f for f in system.getForces() if isinstance(f, mm.DrudeForce)]
+        self._drude_force = None
+        drude_step = self._stock is not None and getattr(self._stock, '_drude', False)
+        if drude_step and len(forces) != 1:
+            raise InputError('a DrudeLangevinIntegrator needs a System with exactly one DrudeForce (this one has %d)' % len(forces))
+        if not forces:
+            return
+        if self.world > 1:
+            raise InputError('a DrudeForce runs on a single rank: its springs and screened pairs are not sliced')
+        texts = [e.replace(' ', '') for _, _, e in getattr(integrator, '_steps', []) if isinstance(e, str)]
+        if any('deriv(energy' in t for t in texts):
+            raise NotImplementedError('deriv(energy, ...) in a System with a DrudeForce is not supported: the Drude kernels have no '
+                                      'derivative mode')
+        if any('cosh(z)' in t and 'LkT' in t for t in texts):
+            raise NotImplementedError('a DrudeForce does not run with the SIN(R) / isokinetic path')
+        if any('tanh(' in t for t in texts):
+            raise NotImplementedError('a DrudeForce does not run with the regulated path')
+        constrained = {int(c[k]) for c in system._constraints for k in (0, 1)}
+        for force in forces:
+            drude_tables(force, system.getNumParticles(), constrained)
+        if drude_step:
+            self._drude_force = forces[0]
+
+    def drude_pairs(self):
+        """int32 [P][2]: (Drude particle, parent) of the DrudeForce a DrudeLangevinIntegrator steps."""
+        return np.array([r[:2] for r in self._drude_force._particles], dtype=np.int32).reshape(-1, 2)
+
+    def drude_temperatures(self):
+        """(system temperature, Drude temperature) in K of a DrudeLangevinIntegrator's System: one read of the stored velocities, summed
+        on the host.  System: sum of m v^2 over ordinary massive atoms plus M v_cm^2 over pairs, over dof k_B with dof = 3 per ordinary
+        massive atom + 3 per pair - constraints - 3 with a CMMotionRemover.  Drude: sum of m_red v_rel^2 over pairs, over 3 n_pairs k_B."""
+        if self._drude_force is None:
+            raise mm.OpenMMException('computeSystemTemperature / computeDrudeTemperature need a DrudeLangevinIntegrator')
+        v = self.v.cpu().numpy().astype(np.float64)
+        m = np.array(self.system._masses, dtype=np.float64)
+        pairs = self.drude_pairs()
+        both = np.array([m[p] > 0.0 and m[p1] > 0.0 for p, p1 in pairs], dtype=bool).reshape(-1)
+        pairs = pairs[both]
+        p, p1 = pairs[:, 0], pairs[:, 1]
+        ordinary = m > 0.0
+        ordinary[p] = False
+        ordinary[p1] = False
+        M = m[p] + m[p1]
+        mu = m[p] * m[p1] / M
+        vcm = (m[p, None] * v[p] + m[p1, None] * v[p1]) / M[:, None]
+        vrel = v[p] - v[p1]
+        ke2 = float((m[ordinary, None] * v[ordinary] ** 2).sum() + (M[:, None] * vcm ** 2).sum())
+        dof = 3 * int(ordinary.sum()) + 3 * len(pairs) - self.system.getNumConstraints()
+        if any(isinstance(f, mm.CMMotionRemover) for f in self.system.getForces()):
+            dof -= 3
+        kB = unit.BOLTZMANN_CONSTANT_kB._value
+        t_sys = ke2 / (dof * kB) if dof > 0 else 0.0
+        t_drude = float((mu[:, None] * vrel ** 2).sum()) / (3 * len(pairs) * kB) if len(pairs) else 0.0
+        return t_sys, t_drude
 
     def _define_vsites(self, system):
         sites = sorted(getattr(system, '_vsites', {}).items())
@@ -1038,6 +1138,33 @@ class Engine:
             raise mm.OpenMMException('gayberne_stats: the force does not belong to this Context')
         return self.ctx.gayberne_stats(hits[0].gayberne)
 
+    def _translate_drude(self, force, entry):
+        """A DrudeForce: its rows (drude_tables) go to the Drude kernels (csrc/drude.hip), which derive the spring constants and the
+        pair parameters.  One backend force carried in entry.term_ids, so every loop over an entry's forces reaches it and the
+        scheduler's fusion rules decline its group, as they do for a CMAP force.  It reads no Context parameter."""
+        cls = 'DrudeForce'
+        periodic = force.usesPeriodicBoundaryConditions()
+        if periodic and self.free_space:
+            raise InputError('%s uses periodic boundary conditions in a System in free space' % cls)
+        n = self.n
+        constrained = {int(c[k]) for c in self.system._constraints for k in (0, 1)}
+        tab = drude_tables(force, n, constrained)
+        try:
+            fid = self.ctx.drude_create(tab['idx'], tab['par'], tab['pairs'], tab['thole'], periodic=periodic)
+        except B.HipError as exc:
+            raise InputError('%s: %s' % (cls, exc))
+        entry.term_ids.append(fid)
+        entry.drude = fid
+
+        def reload():          # updateParametersInContext: charges, polarizabilities, anisotropies and Thole factors are read again
+            new = drude_tables(force, n, constrained)
+            for key, what in (('idx', 'a particle of a Drude particle'), ('pairs', 'a Drude particle of a screened pair')):
+                if not np.array_equal(new[key], tab[key]):
+                    raise mm.OpenMMException('updateParametersInContext: %s has changed' % what)
+            self.ctx.drude_set_params(fid, new['idx'], new['par'], new['pairs'], new['thole'])
+            return 'values'
+        entry.reload = reload
+
     def _translate_gb(self, force, entry):
         """A GBSAOBCForce: one backend force (csrc/gb.hip) carried in entry.term_ids, so every loop over an entry's forces reaches it
         and the scheduler's fusion rules decline its group, as they do for a term-expression force."""
@@ -1242,6 +1369,8 @@ class Engine:
             self._translate_many_particle(force, entry)
         elif isinstance(force, mm.GayBerneForce):
             self._translate_gayberne(force, entry)
+        elif isinstance(force, mm.DrudeForce):
+            self._translate_drude(force, entry)
         elif isinstance(force, mm.CMAPTorsionForce):
             self._translate_cmap(force, entry)
         elif isinstance(force, mm.RBTorsionForce):
@@ -2541,7 +2670,14 @@ class Engine:
         """amm_check on every rank TOGETHER: a neighbour-row overflow or a constraint failure is detected by the rank
         that owns the row, and a rank that raised alone would leave its peers inside the next collective."""
         if not self._coll:
-            return self.ctx.check()
+            if self._drude_force is None:
+                return self.ctx.check()
+            try:
+                return self.ctx.check()
+            except B.HipError as exc:      # (the hard wall of a DrudeLangevinIntegrator speaks as OpenMM does)
+                if 'Drude particle moved too far beyond hard wall constraint' in str(exc):
+                    raise mm.OpenMMException('Drude particle moved too far beyond hard wall constraint')
+                raise
         err = None
         try:
             self.ctx.check()
@@ -2915,6 +3051,8 @@ class Engine:
 
     def _compile(self):
         """Unroll one outer step of the CustomIntegrator program into backend ops (host-side control flow)."""
+        if self._stock is not None and getattr(self._stock, '_drude', False):
+            return self._compile_drude()
         if self._stock is not None and self.stock_native and hasattr(self.ctx, 'stock_define'):
             return self._compile_stock()
         integ = self.integrator
@@ -3009,6 +3147,28 @@ class Engine:
         if key not in self._expr_ids:
             self._expr_ids[key] = self.ctx.stock_define(stock._stock_kind, stock._dt, stock._friction, stock._kT())
         ops.append(B.Op(B.OP_STOCK, self._expr_ids[key], slot, 0, 0.0))
+        for g in valid:
+            valid[g] = False
+        self._deriv_cache.clear()
+        if hasattr(self.ctx, 'regulated_define'):
+            self.ctx.regulated_define(False)
+        if hasattr(self.ctx, 'iso_define'):
+            self.ctx.iso_define(False)
+        return ops, valid, dict(zip(integ._gnames, integ._gvalues)), dict(self._mirror_work)
+
+    def _compile_drude(self):
+        """The step of a DrudeLangevinIntegrator as ONE op behind the evaluation of all forces, as _compile_stock: the launch
+        thermalises pairs and atoms, moves, constrains and applies the hard wall (csrc/drude.hip).  There is no op-by-op form."""
+        stock, integ = self._stock, self.integrator
+        valid = dict(self._valid)
+        self._mirror_work = dict(self._mirror)
+        ops = []
+        slot = self._force_ref('f', ops, valid)
+        key = ('drude', stock._dt, stock._friction, stock._kT(), stock._drude_friction, stock._drude_kT(), stock._max_drude_distance)
+        if key not in self._expr_ids:
+            self._expr_ids[key] = self.ctx.drude_step_define(self.drude_pairs(), stock._dt, stock._friction, stock._kT(), stock._drude_friction,
+                                                             stock._drude_kT(), stock._max_drude_distance)
+        ops.append(B.Op(B.OP_DRUDE_STEP, self._expr_ids[key], slot, 0, 0.0))
         for g in valid:
             valid[g] = False
         self._deriv_cache.clear()

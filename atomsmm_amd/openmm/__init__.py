@@ -1106,6 +1106,63 @@ class GayBerneForce(Force):
         context._engine.update_force_parameters(self)
 
 
+class DrudeForce(Force):
+    """Drude oscillators (csrc/drude.hip): a Drude particle hangs on its parent (particle1) by a harmonic spring whose
+    stiffness K q^2 / alpha may differ along the directions particle1 - particle2 and particle3 - particle4 (aniso12, aniso34; -1: no
+    such particle, the direction is isotropic), and the dipoles of two Drude particles (the particle with its charge, the parent with
+    the opposite one) interact with the Thole-screened energy K q_i q_j (1 - (1 + u/2) exp(-u)) / r, u = thole r / (alpha_1 alpha_2)^(1/6)."""
+
+    def __init__(self):
+        Force.__init__(self)
+        self._particles = []       # [particle, particle1, particle2, particle3, particle4, charge, polarizability, aniso12, aniso34]
+        self._pairs = []           # [drude1, drude2, thole]
+        self._periodic = False
+
+    def usesPeriodicBoundaryConditions(self):
+        return self._periodic
+
+    def setUsesPeriodicBoundaryConditions(self, periodic):
+        self._periodic = bool(periodic)
+
+    @staticmethod
+    def _particle_record(particle, particle1, particle2, particle3, particle4, charge, polarizability, aniso12, aniso34):
+        return [int(particle), int(particle1), int(particle2), int(particle3), int(particle4), float(md_value(charge)),
+                float(md_value(polarizability)), float(aniso12), float(aniso34)]
+
+    def getNumParticles(self):
+        return len(self._particles)
+
+    def addParticle(self, particle, particle1, particle2, particle3, particle4, charge, polarizability, aniso12, aniso34):
+        self._particles.append(self._particle_record(particle, particle1, particle2, particle3, particle4, charge, polarizability,
+                                                     aniso12, aniso34))
+        return len(self._particles) - 1
+
+    def getParticleParameters(self, index):
+        p, p1, p2, p3, p4, charge, alpha, aniso12, aniso34 = self._particles[index]
+        return [p, p1, p2, p3, p4, Quantity(charge, _unit.elementary_charge), Quantity(alpha, nm ** 3), aniso12, aniso34]
+
+    def setParticleParameters(self, index, particle, particle1, particle2, particle3, particle4, charge, polarizability, aniso12, aniso34):
+        self._particles[index] = self._particle_record(particle, particle1, particle2, particle3, particle4, charge, polarizability,
+                                                       aniso12, aniso34)
+
+    def getNumScreenedPairs(self):
+        return len(self._pairs)
+
+    def addScreenedPair(self, drude1, drude2, thole):
+        self._pairs.append([int(drude1), int(drude2), float(thole)])
+        return len(self._pairs) - 1
+
+    def getScreenedPairParameters(self, index):
+        return list(self._pairs[index])
+
+    def setScreenedPairParameters(self, index, drude1, drude2, thole):
+        self._pairs[index] = [int(drude1), int(drude2), float(thole)]
+
+    def updateParametersInContext(self, context):
+        """Upload charges, polarizabilities, anisotropies and Thole factors again.  No particle index may have changed."""
+        context._engine.update_force_parameters(self)
+
+
 class CustomCVForce(Force, _GlobalParams):
     """Energy = function of collective variables, each the energy of an inner Force object."""
 
@@ -2082,6 +2139,63 @@ class BrownianIntegrator(_ThermostatedIntegrator):
         return prog
 
 
+class DrudeLangevinIntegrator(LangevinIntegrator):
+    """openmm.DrudeLangevinIntegrator(temperature, frictionCoeff, drudeTemperature, drudeFrictionCoeff, stepSize): the leapfrog
+    Langevin scheme with two thermostats -- every Drude pair of the System's one DrudeForce is thermalised at `temperature` in its
+    centre of mass and at `drudeTemperature` in its relative coordinate -- and an optional hard wall on the pair distance.  The engine
+    runs the step as `EVAL ; DRUDE_STEP`, one launch for the whole post-force update (csrc/drude.hip); there is no
+    op-by-op form of it (`_program` is the plain Langevin step, which the engine uses for its checks only)."""
+    _drude = True
+
+    def __init__(self, temperature, frictionCoeff, drudeTemperature, drudeFrictionCoeff, stepSize):
+        LangevinIntegrator.__init__(self, temperature, frictionCoeff, stepSize)
+        self._drude_temperature = float(md_value(drudeTemperature))
+        self._drude_friction = float(md_value(drudeFrictionCoeff))
+        self._max_drude_distance = 0.0
+        if self._drude_temperature < 0 or self._drude_friction < 0:
+            raise OpenMMException('DrudeLangevinIntegrator: the Drude temperature and friction coefficient must not be negative')
+
+    def getDrudeTemperature(self):
+        return Quantity(self._drude_temperature, _unit.kelvin)
+
+    def setDrudeTemperature(self, temperature):
+        self._drude_temperature = float(md_value(temperature))
+        self._changed()
+
+    def getDrudeFriction(self):
+        return Quantity(self._drude_friction, _unit.dimensionless / _unit.picosecond)
+
+    def setDrudeFriction(self, frictionCoeff):
+        self._drude_friction = float(md_value(frictionCoeff))
+        self._changed()
+
+    def getMaxDrudeDistance(self):
+        return Quantity(self._max_drude_distance, nm)
+
+    def setMaxDrudeDistance(self, distance):
+        distance = float(md_value(distance))
+        if distance < 0:
+            raise OpenMMException('DrudeLangevinIntegrator: the maximum Drude distance must not be negative')
+        self._max_drude_distance = distance
+        self._changed()
+
+    def _drude_kT(self):
+        return _unit.BOLTZMANN_CONSTANT_kB._value * self._drude_temperature
+
+    def _bound(self):
+        if self._context is None:
+            raise OpenMMException('This Integrator is not bound to a context!')
+        return self._context._engine
+
+    def computeSystemTemperature(self):
+        """The temperature of the ordinary atoms and of the pairs' centres of mass: one read of the stored velocities."""
+        return Quantity(self._bound().drude_temperatures()[0], _unit.kelvin)
+
+    def computeDrudeTemperature(self):
+        """The temperature of the pairs' relative motion: one read of the stored velocities."""
+        return Quantity(self._bound().drude_temperatures()[1], _unit.kelvin)
+
+
 
 class CustomIntegrator(Integrator):
     ComputeGlobal, ComputePerDof, ComputeSum, ConstrainPositions, ConstrainVelocities, UpdateContextState, \
@@ -2301,6 +2415,8 @@ def molecules_of(system):
             pairs += [(r[k], r[k + 1]) for r in force._torsions for k in (1, 2, 3, 5, 6, 7)]
         elif isinstance(force, CustomCompoundBondForce):       # consecutive particles, as an angle or torsion (a centroid bond joins nothing)
             pairs += [(a, b) for members, _ in force._bonds for a, b in zip(members[:-1], members[1:])]
+        elif isinstance(force, DrudeForce):                    # a Drude particle hangs on its parent: a box move must not tear them apart
+            pairs += [(r[0], r[1]) for r in force._particles if 0 <= r[0] < n and 0 <= r[1] < n]
     # (a virtual site belongs to the molecule of its parents, as in OpenMM's getMolecules)
     pairs += [(index, site.getParticle(k)) for index, site in sorted(getattr(system, '_vsites', {}).items())
               for k in range(site.getNumParticles()) if 0 <= site.getParticle(k) < n]

@@ -312,6 +312,9 @@ class ForceField:
                         break
                     terms.append((int(t.get('periodicity%d' % n)), float(t.get('phase%d' % n)), float(t.get('k%d' % n))))
                 table.append((types_of(t, 4), terms))
+        if root.find('DrudeForce') is not None:
+            raise NotImplementedError('<DrudeForce>: the Drude section of a force field file is not supported; build the DrudeForce '
+                                      'through the API (openmm.DrudeForce.addParticle / addScreenedPair)')
         for rb in root.findall('RBTorsionForce'):
             if rb.find('Improper') is not None:
                 raise NotImplementedError('<RBTorsionForce>: <Improper> entries are not supported')

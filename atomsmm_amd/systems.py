@@ -288,6 +288,9 @@ class ComputingSystem(_AtomsMM_System):
         if any(isinstance(force, openmm.GayBerneForce) for force in system.getForces()):
             raise NotImplementedError('ComputingSystem / PressureComputer: the virial of a GayBerneForce is not supported (the Gay-Berne '
                                       'kernels keep the force on the owning ellipsoid of a pair and on its axis particles, not the pair\'s virial)')
+        if any(isinstance(force, openmm.DrudeForce) for force in system.getForces()):
+            raise NotImplementedError('ComputingSystem / PressureComputer: the virial of a DrudeForce is not supported (the Drude kernels '
+                                      'park the forces of a spring and of a screened pair per atom, not their virial)')
         if any(isinstance(force, openmm.RMSDForce) for force in system.getForces()):
             raise NotImplementedError('ComputingSystem / PressureComputer: the virial of an RMSDForce is not supported (the RMSD kernels '
                                       'read raw coordinates and form no virial)')

@@ -239,6 +239,84 @@ def solvated_chain(nside=44, n_chain=3000, n_solute=30, seed=SEED, density=33.36
                 chain=ic.astype(np.int32), solute=isol.astype(np.int32), n_waters=nmol)
 
 
+def swm4_box(n_side=3, seed=SEED, density=33.368, drude_displacement=0.005):
+    """n_side^3 rigid five-site polarizable waters of the SWM4 shape on a lattice with random orientations: O (the parent, with the
+    Lennard-Jones site), D (its Drude particle), H1, H2 and the massless M on the bisector, a ThreeParticleAverageSite of O, H1, H2.
+    Atom order per molecule: O, D, H1, H2, M.  The parameters are those of the SWM4-NDP model as recalled -- r(OH) = 0.09572 nm,
+    HOH = 104.52 deg, r(OM) = 0.024034 nm, q_H = 0.55733, q_M = -1.11466, q_D = -1.71636 = -q_O, alpha = 0.97825e-3 nm^3, O: sigma =
+    0.318395 nm, epsilon = 0.88257 kJ/mol, m_D = 0.4 taken from the oxygen -- "SWM4-like": nothing depends on the literature values.
+    The Drude particles start drude_displacement (nm, rms per component) from their oxygens.  An exception for every pair within a
+    molecule.  Returns the case as arrays (positions, box, mass, charge, sigma, epsilon, exc_pairs, constraints (i, j, d), drude rows,
+    site rows, velocities at 300 K -- 1 K in the Drude pairs' relative motion); swm4_system makes the System."""
+    rng = np.random.default_rng(seed)
+    nmol = n_side ** 3
+    L = (nmol / density) ** (1.0 / 3.0)
+    a = L / n_side
+    g = (np.arange(n_side) + 0.5) * a
+    centers = np.stack(np.meshgrid(g, g, g, indexing='ij'), -1).reshape(-1, 3)
+    r0, th0, r_om = 0.09572, np.deg2rad(104.52), 0.024034
+    h1 = np.array([r0 * np.sin(th0 / 2), r0 * np.cos(th0 / 2), 0.0])
+    h2 = np.array([-r0 * np.sin(th0 / 2), r0 * np.cos(th0 / 2), 0.0])
+    w = 0.5 * r_om / (r0 * np.cos(th0 / 2))                # M = (1 - 2 w) O + w H1 + w H2
+    qn = rng.normal(size=(nmol, 4))
+    qn /= np.linalg.norm(qn, axis=1)[:, None]
+    qw, x, y, z = qn.T
+    R = np.stack([
+        np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * qw), 2 * (x * z + y * qw)], -1),
+        np.stack([2 * (x * y + z * qw), 1 - 2 * (x * x + z * z), 2 * (y * z - x * qw)], -1),
+        np.stack([2 * (x * z - y * qw), 2 * (y * z + x * qw), 1 - 2 * (x * x + y * y)], -1)], 1)
+    pos = np.empty((nmol, 5, 3))
+    pos[:, 0] = centers
+    pos[:, 1] = centers + rng.normal(scale=drude_displacement, size=(nmol, 3))
+    pos[:, 2] = centers + R @ h1
+    pos[:, 3] = centers + R @ h2
+    pos[:, 4] = (1 - 2 * w) * pos[:, 0] + w * pos[:, 2] + w * pos[:, 3]
+    pos = pos.reshape(-1, 3)
+    q_d, q_h, alpha, m_d = -1.71636, 0.55733, 0.97825e-3, 0.4
+    charge = np.tile([-q_d, q_d, q_h, q_h, -2 * q_h], nmol)
+    sigma = np.tile([0.318395, 1.0, 1.0, 1.0, 1.0], nmol)
+    epsilon = np.tile([0.88257, 0.0, 0.0, 0.0, 0.0], nmol)
+    mass = np.tile([15.9994 - m_d, m_d, 1.008, 1.008, 0.0], nmol)
+    o = 5 * np.arange(nmol, dtype=np.int32)
+    exc = np.concatenate([np.stack([o + i, o + j], 1) for i in range(5) for j in range(i + 1, 5)]).astype(np.int32)
+    r_hh = 2 * r0 * np.sin(th0 / 2)
+    constraints = [(int(b), int(b) + 2, r0) for b in o] + [(int(b), int(b) + 3, r0) for b in o] + [(int(b) + 2, int(b) + 3, r_hh) for b in o]
+    drude = [(int(b) + 1, int(b), -1, -1, -1, q_d, alpha, 1.0, 1.0) for b in o]
+    sites = [(int(b) + 4, int(b), int(b) + 2, int(b) + 3, 1 - 2 * w, w, w) for b in o]
+    kB = 0.0083144626181532
+    vel = np.zeros((5 * nmol, 3))
+    massive = mass > 0
+    vel[massive] = rng.normal(size=(int(massive.sum()), 3)) * np.sqrt(kB * 300.0 / mass[massive])[:, None]
+    mu = m_d * (15.9994 - m_d) / 15.9994
+    vel[o + 1] = vel[o] + rng.normal(size=(nmol, 3)) * np.sqrt(kB * 1.0 / mu)
+    return dict(positions=pos, box=np.full(3, L), charge=charge, sigma=sigma, epsilon=epsilon, mass=mass, exc_pairs=exc,
+                constraints=constraints, drude=drude, sites=sites, velocities=vel, n_waters=nmol)
+
+
+def swm4_system(case, nonbondedMethod='PME', cutoff=None, ewaldTolerance=5e-4, drude=True):
+    """The System of a swm4_box() case: the NonbondedForce (group 0) with its exceptions, the rigid-water constraints, M as a
+    ThreeParticleAverageSite and the DrudeForce (group 1; drude=False leaves it out).  cutoff None: 1 nm, or 0.48 of the box edge
+    in a box too small for that.  Returns (system, the DrudeForce or None)."""
+    from .. import openmm
+    L = float(case['box'][0])
+    if cutoff is None:
+        cutoff = min(1.0, 0.48 * L)
+    system = system_from_arrays(case, nonbondedMethod=nonbondedMethod, cutoff=cutoff, ewaldTolerance=ewaldTolerance, flexible=False)
+    for i, j, d in case['constraints']:
+        system.addConstraint(i, j, d)
+    for site, p1, p2, p3, w1, w2, w3 in case['sites']:
+        system.setVirtualSite(site, openmm.ThreeParticleAverageSite(p1, p2, p3, w1, w2, w3))
+    force = None
+    if drude:
+        force = openmm.DrudeForce()
+        for row in case['drude']:
+            force.addParticle(*row)
+        force.setUsesPeriodicBoundaryConditions(True)
+        force.setForceGroup(1)
+        system.addForce(force)
+    return system, force
+
+
 def build_c5_system(case, outer='damped'):
     """The System of config C5 from a solvated_chain() case, through the AtomsMM-shaped API only:
     SolvationSystem (softcore solute-solvent force with the global parameter lambda_vdw, systems.py:240-315) ->

@@ -128,9 +128,12 @@ enum {
     AMM_OP_CONSTRAIN_V = 10,/* addConstrainVelocities (propagators.py:272, 1131): RATTLE                              */
     AMM_OP_ALLREDUCE = 11,  /* buf[a] <- sum over ranks of buf[a] (RCCL, the context's own communicator: amm_comm_init):
                                the exchange of atom decomposition after the EVAL of a sliced group      */
-    AMM_OP_STOCK = 12       /* the whole post-force update of one step of stock integrator a (amm_stock_define) with the forces
+    AMM_OP_STOCK = 12,      /* the whole post-force update of one step of stock integrator a (amm_stock_define) with the forces
                                in buf[b], in ONE launch: kick, RATTLE, moves, bath, SHAKE and velocity correction per constraint
                                cluster (or per atom of no cluster); takes one random-stream counter                     */
+    AMM_OP_DRUDE_STEP = 13  /* the whole post-force update of one step of Drude step a (amm_drude_step_define) with the forces in
+                               buf[b], in ONE launch: the dual Langevin thermostat of every Drude pair and the Langevin step of
+                               every other atom, SHAKE, the hard wall; takes one random-stream counter                  */
 };
 typedef struct {
     int32_t op, a, b, c;
@@ -598,6 +601,30 @@ int amm_gayberne_stats(amm_ctx *ctx, int32_t force_id, int64_t *out);
 /* Free such a force; the id is retired and leaves every group definition. */
 int amm_gayberne_release(amm_ctx *ctx, int32_t force_id);
 
+/* DrudeForce (force type AMM_FORCE_DRUDE; csrc/drude.hip): anisotropic harmonic springs between Drude
+ * particles and their parents, and Thole-screened interactions between the dipoles of pairs of them, with K = 138.935456:
+ *   spring  a1 = aniso12 if p2 != -1 else 1, a2 = aniso34 if p3, p4 != -1 else 1, a3 = 3 - a1 - a2, k3 = K q^2/(alpha a3),
+ *           k1 = K q^2/(alpha a1) - k3, k2 = K q^2/(alpha a2) - k3, d = x_p - x_p1,
+ *           E = 1/2 k3 |d|^2 + 1/2 k1 (d.unit(x_p1 - x_p2))^2 + 1/2 k2 (d.unit(x_p3 - x_p4))^2
+ *   pair    s = thole/(alpha_A alpha_B)^(1/6); over the four site pairs of {p_A: q_A, p1_A: -q_A} x {p_B: q_B, p1_B: -q_B}, u = s r:
+ *           E += K q_i q_j (1 - (1 + u/2) exp(-u))/r
+ *   h_idx[n_drude][5]     p, p1, p2, p3, p4 (-1: none)
+ *   h_par[n_drude][4]     charge (e), polarizability (nm^3), aniso12, aniso34
+ *   h_pair[n_pairs][2]    the two entries of h_idx a screened pair joins;  h_thole[n_pairs]
+ *   periodic              every displacement takes its own minimum image in the orthorhombic box
+ * Refused, each with AMM_FORCE_DRUDE in the message: an index out of range, p = p1, a polarizability or an a1, a2, a3 that is not
+ * above zero, a pair that names an entry twice or one that does not exist, more than one rank (also amm_set_slice while such a
+ * force lives).  An ordinary member of a group; no inner force of amm_cv_create.  fp64, no atomics, fixed order of summation: the
+ * same positions give the same bits.  Two launches per evaluation. */
+int amm_drude_create(amm_ctx *ctx, const int32_t *h_idx, const double *h_par, int32_t n_drude, const int32_t *h_pair, const double *h_thole,
+                     int32_t n_pairs, int32_t periodic, int32_t *force_id);
+/* setParticleParameters / setScreenedPairParameters + updateParametersInContext: new values in the layout of creation; the counts and
+ * every index stay.  Waits for the stream.  A refused call leaves the force as it was. */
+int amm_drude_set_params(amm_ctx *ctx, int32_t force_id, const int32_t *h_idx, const double *h_par, int32_t n_drude, const int32_t *h_pair,
+                         const double *h_thole, int32_t n_pairs);
+/* Free such a force; the id is retired and leaves every group definition. */
+int amm_drude_release(amm_ctx *ctx, int32_t force_id);
+
 /* Reciprocal space of a NonbondedForce with nonbondedMethod PME / Ewald, as RESPASystem and FarNonbondedForce
  * keep it in group 2 with the source force's Ewald tolerance / PME parameters (systems.py:74-75,
  * forces.py:185-188; setReciprocalSpaceForceGroup: utils.py:147-152).  Smooth PME, B-spline order 5, grid
@@ -663,6 +690,15 @@ int amm_bath_define(amm_ctx *ctx, double z, double kT, int32_t *bath_id);
  * negative friction or kT, a step size of 0 (three kinds divide by it).  The op itself is refused while the isokinetic or the regulated mode is on. */
 enum { AMM_STOCK_VERLET = 0, AMM_STOCK_LANGEVIN_MIDDLE = 1, AMM_STOCK_LANGEVIN = 2, AMM_STOCK_BROWNIAN = 3 };
 int amm_stock_define(amm_ctx *ctx, int32_t kind, double dt, double friction, double kT, int32_t *stock_id);
+/* The step of a DrudeLangevinIntegrator for AMM_OP_DRUDE_STEP (csrc/drude.hip has the formulas):
+ *   h_pairs[n_pairs][2]   (Drude particle, parent) of every pair; no particle in two pairs
+ *   dt in ps; friction, kT of the ordinary atoms and of the pairs' centres of mass; drude_friction, drude_kT of the pairs' relative
+ *   motion (1/ps, kJ/mol); max_distance: the hard wall in nm, 0: none.
+ * A pair found beyond twice the hard wall after a step sets a flag: the next amm_check returns 2 with the message "Drude particle
+ * moved too far beyond hard wall constraint" and clears it.  Refused: an index out of range or named twice, a negative friction,
+ * kT or distance, a step size of 0, more than one rank.  The op itself is refused while the isokinetic or the regulated mode is on. */
+int amm_drude_step_define(amm_ctx *ctx, const int32_t *h_pairs, int32_t n_pairs, double dt, double friction, double kT, double drude_friction,
+                          double drude_kT, double max_distance, int32_t *step_id);
 /* The Nose-Hoover-Langevin bath block of NHL_R_Integrator (integrators.py:272-330; MassiveNoseHooverLangevinPropagator,
  * propagators.py:1362-1449) as ONE AMM_OP_BATH: v <- v exp(-h w) ; w <- z w + sqrt(kT (1 - z^2)/Q) gaussian +
  * (m v^2 - kT)(1 - z)/(Q friction) ; v <- v exp(-h w), with the per-DOF thermostat velocities w in buffer slot `slot`
