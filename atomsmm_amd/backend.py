@@ -43,7 +43,7 @@ RULE_NAMES = ('plain', 'defer_trailing_kicks', 'inner_components', 'fused_inner'
 EXPORTS = [
     'amm_abi_version', 'amm_last_error', 'amm_create', 'amm_destroy', 'amm_set_stream', 'amm_set_slice',
     'amm_synchronize', 'amm_check', 'amm_pair_create', 'amm_pair_set_params', 'amm_pair_share_list', 'amm_bonded_create',
-    'amm_bonded_add_terms', 'amm_bonded_finalize', 'amm_bonded_set_sliced', 'amm_bonded_release', 'amm_force_eval', 'amm_kick',
+    'amm_bonded_add_terms', 'amm_bonded_finalize', 'amm_bonded_set_sliced', 'amm_bonded_release', 'amm_bonded_stats', 'amm_force_eval', 'amm_kick',
     'amm_move', 'amm_copy', 'amm_mvv', 'amm_bind_state', 'amm_bind_buffer', 'amm_group_define', 'amm_run_ops',
     'amm_set_fuse_inner', 'amm_set_outer_skin',
     'amm_pair_get_stats', 'amm_profile_enable', 'amm_profile_read', 'amm_pair_count_within', 'amm_pair_row_padding', 'amm_pair_guest_factor', 'amm_kernel_revision', 'amm_pair_table_check',
@@ -250,6 +250,7 @@ def lib():
         L.amm_bonded_finalize.argtypes = [vp, C.c_int32]
         L.amm_bonded_set_sliced.argtypes = [vp, C.c_int32, C.c_int32]
         L.amm_bonded_release.argtypes = [vp, C.c_int32]
+        L.amm_bonded_stats.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
         L.amm_force_eval.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp]
         L.amm_kick.argtypes = [vp, vp, vp, vp, C.c_int32, vp, C.c_double]
         L.amm_move.argtypes = [vp, vp, vp, C.c_double]
@@ -551,6 +552,12 @@ class HipContext:
         _chk(lib().amm_bonded_finalize(self.h, fid))
         if sliced:
             _chk(lib().amm_bonded_set_sliced(self.h, fid, 1))
+
+    def bonded_stats(self, fid):
+        """dict(ncomp, max_comp, terms_ok, G, mol3_ok, mixed_ok, n_gterms, n_sc): the layouts amm_bonded_finalize built for the set."""
+        out = (C.c_int64 * 8)()
+        _chk(lib().amm_bonded_stats(self.h, fid, out))
+        return dict(zip(('ncomp', 'max_comp', 'terms_ok', 'G', 'mol3_ok', 'mixed_ok', 'n_gterms', 'n_sc'), (int(v) for v in out)))
 
     def bonded_release(self, fid):
         """Free a bond-list set that has been replaced (its id is retired)."""

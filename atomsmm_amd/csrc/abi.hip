@@ -908,6 +908,29 @@ int amm_bonded_set_sliced(amm_ctx *ctx, int32_t force_id, int32_t on) {
 
 int amm_bonded_release(amm_ctx *ctx, int32_t force_id) { return amm_force_release(ctx, force_id, AMM_FORCE_BONDED, nullptr); }
 
+// which layouts amm_bonded_finalize built and which launches they admit (read-only; see include/atomsmm_hip.h)
+int amm_bonded_stats(amm_ctx *ctx, int32_t force_id, int64_t *out) {
+    BondedSet *bs = amm_force_get<BondedSet>(ctx, force_id);
+    if (!bs) return 1;
+    if (!out) {
+        amm_set_error("amm_bonded_stats: null argument");
+        return 1;
+    }
+    if (!bs->finalized) {
+        amm_set_error("amm_bonded_stats before amm_bonded_finalize");
+        return 1;
+    }
+    out[0] = bs->ncomp;
+    out[1] = bs->max_comp;
+    out[2] = bs->terms_ok ? 1 : 0;
+    out[3] = bs->G;                              // lanes per component: the term tables' stride and the inner-components launch's
+    out[4] = bs->mol3_ok ? 1 : 0;
+    out[5] = bs->mixed_ok ? 1 : 0;
+    out[6] = bs->n_gterms;
+    out[7] = bs->mixed_ok ? bs->n_sc : 0;
+    return 0;
+}
+
 int amm_pme_create(amm_ctx *ctx, double alpha, int32_t nx, int32_t ny, int32_t nz, double Kc, const double *h_q,
                    int32_t *force_id) {
     if (!ctx || !h_q || !force_id) {

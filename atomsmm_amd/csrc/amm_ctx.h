@@ -216,6 +216,7 @@ struct BondedSet {
     int4 *d_rec_l = nullptr;       // atoms of the term as slots within their connected component
     int *d_comp_ptr = nullptr, *d_comp_atoms = nullptr;   // connected components of the term graph (CSR)
     int ncomp = 0, max_comp = 0;
+    int G = 4;                     // lanes per component: what the term tables are sized by and the inner-components launch runs with
     // term-parallel inner loop: every component has at most G terms (G lanes per component) -> lane l evaluates term l
     bool terms_ok = false;
     // ... and, further, every component is one three-site molecule {3 c, 3 c + 1, 3 c + 2} (slot = atom order) with at most four terms,

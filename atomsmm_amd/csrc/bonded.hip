@@ -740,9 +740,10 @@ int amm_bonded_finalize_impl(amm_ctx *ctx, BondedSet *bs) {
     bs->max_comp = maxc;
     // term tables of the term-parallel inner loop: terms numbered within their component in the order the records were
     // laid down above (kind, term), so that an atom's packed (term slot, role) list repeats its record order
+    bs->G = maxc <= 4 ? 4 : 8;
     bs->terms_ok = maxc <= 8 && nref > 0;
     if (bs->terms_ok) {
-        const int G = maxc <= 4 ? 4 : 8;
+        const int G = bs->G;
         std::vector<int> nterm(ncomp, 0);
         std::vector<int4> term_l((size_t)ncomp * G, make_int4(-1, -1, -1, -1));
         std::vector<double4> term_q((size_t)ncomp * G, make_double4(0.0, 0.0, 0.0, 0.0));
@@ -1118,7 +1119,7 @@ int amm_inner_components_impl(amm_ctx *ctx, BondedSet *bs, double *x, double *v,
         C.pre[p].plus = p < npre ? pre_plus[p] : 0;
     }
     dim3 block(256);
-    const int G = bs->max_comp <= 4 ? 4 : 8;
+    const int G = bs->G;
     dim3 grid((unsigned)(((long)bs->ncomp * G + 255) / 256));
     C.d2 = d2;
     C.bath_z = bath ? bath->z : 1.0;

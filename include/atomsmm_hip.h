@@ -266,6 +266,11 @@ int amm_pair_energy_derivative(amm_ctx *ctx, int32_t force_id, const double *d_p
 int amm_pair_energy_states(amm_ctx *ctx, int32_t force_id, const double *d_pos, const double *d_lambdas, int32_t n_states, double *d_out);
 
 int amm_bonded_create(amm_ctx *ctx, int32_t *force_id);
+/* Accuracy of AMM_ANGLE_HARMONIC: the angle is acos(cos theta) and the force divides by sqrt(1 - cos^2 theta), so the relative error of
+ * the force grows like eps / sin^2 theta.  With sin theta >= 1e-2 (an angle at least 1e-2 rad = 0.6 degrees from 0 and from pi) the force
+ * is as accurate as the rounding of the input coordinates allows; closer to linearity it is finite but loses digits (1e-3 rad: about
+ * 1e-10 relative; an angle within 6e-8 rad of 0 or pi is taken as exactly 0 or pi), while the energy stays good to
+ * k |theta - theta0| min(8 eps / sin theta, 6e-8).  theta0 = pi itself is harmless (the force vanishes with the distance from pi). */
 int amm_bonded_add_terms(amm_ctx *ctx, int32_t force_id, int32_t kind, const int32_t *h_idx,
                          const double *h_params, int32_t n_terms, int32_t periodic,
                          const amm_pair_desc *desc_or_null);
@@ -276,6 +281,14 @@ int amm_bonded_set_sliced(amm_ctx *ctx, int32_t force_id, int32_t on);
  * NonbondedForce (forces.py:292-309, systems.py:303-311), which OpenMM does in place.  The id is retired (never reused) and
  * leaves every group definition. */
 int amm_bonded_release(amm_ctx *ctx, int32_t force_id);
+/* Which device layouts amm_bonded_finalize built for the set, and so which launches it admits (read-only, no device work):
+ * out[0] connected components of the term graph (an atom in no term is a component of its own), out[1] atoms of the largest,
+ * out[2] 1 when every component has at most G terms and the inner-components launch runs with term lanes, out[3] G (4 or 8: lanes
+ * per component of that launch; rule 2 of amm_run_ops takes it when out[1] <= 8), out[4] 1 when the set is a box of three-site
+ * molecules that a molecule-row pair launch can integrate as its epilogue, out[5] 1 when the fused EVAL + kicks launch runs the
+ * small components four lanes each (mixed sets), out[6] terms of the term-parallel tables (0: below option terms_from, the
+ * record walk is the only evaluation), out[7] small components of a mixed set.  Refused before amm_bonded_finalize. */
+int amm_bonded_stats(amm_ctx *ctx, int32_t force_id, int64_t *out);
 
 /* CustomBondForce / CustomAngleForce / CustomTorsionForce / CustomExternalForce with ANY energy text (what OpenMM compiles with
  * Lepton; the texts the reference ships are the kinds of amm_bonded_add_terms).  A force object of its own, an ordinary member of a
