@@ -4,7 +4,7 @@ HIP library (include/atomsmm_hip.h) and takes over what OpenMM's C++ does for th
 the CustomIntegrator step program (`integrator.step(n)`).
 
 Design (MI355X-first, not OpenMM's):
-  * every Force object becomes backend objects once, at Context creation -- a pair force (cell list ->
+  * every Force object becomes backend objects once, at Context creation (atomsmm_amd/translate) -- a pair force (cell list ->
     Verlet list -> lanes-per-atom traversal) or bond-list terms (owner-computes CSR);
   * the step program is *unrolled on the host* into a flat op list (EVAL group / KICK / MOVE / COPY)
     with one force cache per group: a group is re-evaluated only if positions changed since its last
@@ -27,13 +27,12 @@ import numpy as np
 from . import backend as B
 from . import expr as X
 from . import openmm as mm
-from . import tables as T
+from . import translate as TR
 from . import unit
-from .forces import describe_energy
+# (named here by backend.py, scripts/ and the tests of the forces they belong to)
+from .translate import MANY_PERMUTATIONS, _Entry, dispersion_correction, gayberne_tables, many_particle_table  # noqa: F401
 from .utils import InputError
 
-_FAMILY = {'near-none': B.NEAR_NONE, 'near-shift': B.NEAR_SHIFT, 'near-force-switch': B.NEAR_FSWITCH,
-           'damped': B.DAMPED}
 _SAFE_FUNCS = {name: getattr(math, name) for name in ('sqrt', 'exp', 'log', 'sin', 'cos', 'tan', 'erf', 'erfc', 'floor', 'ceil')}
 _SAFE_FUNCS.update(step=lambda x: 1.0 if x >= 0 else 0.0, delta=lambda x: 1.0 if x == 0 else 0.0,
                    select=lambda c, a, b: a if c != 0 else b, min=min, max=max, abs=abs)
@@ -46,114 +45,6 @@ _SCALARS = 2048        # device scalars of a host-walked program: deriv(energy, 
 _COMPARE = {'<': lambda a, b: a < b, '>': lambda a, b: a > b, '<=': lambda a, b: a <= b, '>=': lambda a, b: a >= b,
             '=': lambda a, b: a == b, '!=': lambda a, b: a != b}
 _context_factory = B.HipContext   # the only backend; tests of the host logic substitute a call recorder
-
-
-def custom_long_range_correction(u, sigma, eps, box, rc, rswitch, codes=None, pairs=None):
-    """Long-range correction of a CustomNonbondedForce as OpenMM defines it [recalled; pinned by tests/test_systems.py:39
-    (interaction group, met to 2e-8) and tests/test_computers.py:31 (no groups)]: with I(s, e) = int_rc^inf u r^2 dr +
-    int_rs^rc (1 - S) u r^2 dr for a pair of mixed parameters (s, e),
-        E = 2 pi N^2 / V * [sum over class pairs of count * I] / (N (N + 1)/2),
-    classes = atoms of equal (sigma, epsilon); count = n_i n_j for two classes, n_i (n_i + 1)/2 within a class; with an
-    interaction group (`codes` 1 / 2) the count is the number of (set 1, set 2) pairs.  N = number of particles."""
-    n = len(sigma)
-
-    def refine(f):
-        """OpenMM's quadrature (CustomNonbondedForceImpl::integrateInteraction [recalled]): midpoint rule on (0, 1),
-        the number of points tripled (the old midpoints stay) until two sums agree to 1e-5 -- reproduced as is, because
-        the reference literals carry ITS truncation error (tests/test_systems.py:39 is met to 1e-9 this way, to 2e-8
-        with an exact quadrature; tests/test_computers.py:33 needs the former)."""
-        total, points = 0.0, 1
-        for iteration in range(9):
-            idx = np.arange(points)
-            xs = (idx[idx % 3 != 1] + 0.5) / points
-            old = total
-            total = float(np.sum(f(xs))) / points + old / 3.0
-            if iteration > 2 and (total == 0.0 or abs((total - old) / total) < 1e-5):
-                return total
-            points *= 3
-        raise RuntimeError('long-range correction did not converge')
-
-    def integral(s, e):
-        def tail(x):                                   # int_rc^inf u r^2 dr = (1/rc) int_0^1 u(rc/x) r^4 dx, r = rc/x
-            r = rc / x
-            return u(r, s, e) * r ** 4
-        out = refine(tail) / rc
-        if rswitch is not None:
-            def shell(x):                              # int_rs^rc (1 - S) u r^2 dr
-                r = rswitch + x * (rc - rswitch)
-                return x ** 3 * (10.0 + x * (-15.0 + x * 6.0)) * u(r, s, e) * r * r
-            out += refine(shell) * (rc - rswitch)
-        return out
-
-    if pairs is None:
-        pairs = lrc_class_pairs(sigma, eps, codes)
-    total = sum(weight * integral(s, e) for s, e, weight in pairs)
-    return 2.0 * math.pi * n * n / float(np.prod(box)) * total / (n * (n + 1) / 2.0)
-
-
-def lrc_class_pairs(sigma, eps, codes=None):
-    """[(sigma_ij, eps_ij, number of pairs)] over the classes of equal (sigma, epsilon) -- the part of a long-range
-    correction that depends on the per-particle parameters only (a 250 000-atom system has a handful of classes): the
-    softcore force's correction is re-evaluated at every change of lambda, and twice per deriv(energy, lambda)."""
-    table = np.stack([np.asarray(sigma, dtype=np.float64), np.asarray(eps, dtype=np.float64)], axis=1)
-
-    def classes(members):
-        values, counts = np.unique(table[members], axis=0, return_counts=True)
-        return [(float(s_), float(e_), int(c_)) for (s_, e_), c_ in zip(values, counts)]
-    out = []
-    if codes is not None:
-        for s1, e1, n1 in classes(np.where(np.asarray(codes) == 1.0)[0]):
-            for s2, e2, n2 in classes(np.where(np.asarray(codes) == 2.0)[0]):
-                s, e = 0.5 * (s1 + s2), math.sqrt(e1 * e2)
-                if e != 0.0 and s > 0.0:
-                    out.append((s, e, n1 * n2))
-    else:
-        every = classes(np.arange(len(table)))
-        for a, (s1, e1, n1) in enumerate(every):
-            for s2, e2, n2 in every[a:]:
-                s, e = 0.5 * (s1 + s2), math.sqrt(e1 * e2)
-                if e != 0.0 and s > 0.0:
-                    out.append((s, e, n1 * (n1 + 1) / 2 if (s1, e1) == (s2, e2) else n1 * n2))
-    return out
-
-
-def softcore_long_range_correction(sigma, eps, codes, box, rc, rswitch, lam, pairs=None):
-    """SolvationSystem's softcore force (systems.py:266-272): u = 4 lambda eps (1-x)/x^2, x = (r/sigma)^6 + (1-lambda)/2."""
-    def u(r, s, e):
-        x = (r / s) ** 6 + 0.5 * (1.0 - lam)
-        return 4.0 * lam * e * (1.0 - x) / (x * x)
-    return custom_long_range_correction(u, sigma, eps, box, rc, rswitch, codes, pairs)
-
-
-def dispersion_correction(sigma, eps, box, rc, rswitch=None):
-    """Long-range LJ correction of OpenMM's NonbondedForce, with the switching-function term
-    (SURVEY.md Appendix B.6): (2 pi N^2/V) <int_rc^inf V r^2 dr + int_rs^rc (1-S) V r^2 dr> over type pairs."""
-    classes = {}
-    for s, e in zip(sigma, eps):
-        classes[(s, e)] = classes.get((s, e), 0) + 1
-    keys = list(classes)
-    n = float(len(sigma))
-    total = 0.0
-    for a in range(len(keys)):
-        for b in range(a, len(keys)):
-            e = math.sqrt(keys[a][1] * keys[b][1])
-            if e == 0.0:
-                continue
-            s = 0.5 * (keys[a][0] + keys[b][0])
-            s6 = s ** 6
-            s12 = s6 * s6
-            w = 0.5 * classes[keys[a]] * (classes[keys[a]] + 1) if a == b else float(classes[keys[a]]) * classes[keys[b]]
-            term = 4 * e * (s12 / (9 * rc ** 9) - s6 / (3 * rc ** 3))
-            if rswitch is not None:
-                r = np.linspace(rswitch, rc, 2001)
-                t = (r - rswitch) / (rc - rswitch)
-                S = 1 + t ** 3 * (15 * t - 6 * t * t - 10)
-                g = (1 - S) * 4 * e * (s12 / r ** 12 - s6 / r ** 6) * r * r
-                h = r[1] - r[0]
-                term += h / 3 * (g[0] + g[-1] + 4 * g[1:-1:2].sum() + 2 * g[2:-1:2].sum())
-            total += w * term
-    total /= 0.5 * n * (n + 1)
-    return 2 * math.pi * n * n * total / (box[0] * box[1] * box[2])
 
 
 class LocalWorld:
@@ -223,167 +114,6 @@ class LocalWorld:
         out = self._slots[0]
         self._barrier.wait()
         return out
-
-
-class _Entry:
-    """One System force translated to backend objects."""
-
-    def __init__(self, force, group):
-        self.force = force
-        self.group = group
-        self.pair_ids = []          # backend pair forces (sliced across ranks)
-        self.bonded_id = None       # backend bonded set holding this force's bond-list terms
-        self.terms = []             # (kind, idx, params, periodic, desc) for group-level merging
-        self.constant = 0.0         # energy-only constant (dispersion correction)
-        self.recip_group = None
-        self.recip = None
-        self.update = None          # callable(parameters) refreshing lambda-dependent parameters
-        self.softcore = None        # softcore pair force: dict(pid, lambda_name, constant, depends)
-        self.depends = set()        # global parameters this entry's backend data depend on
-        self.pair_expr = False      # a CustomNonbondedForce on the pair-expression kernel (generic energy text) ...
-        self.program = None         # ... and its compiled program (expr.compile_pair)
-        self.term_ids = []          # backend term-expression forces (csrc/term_expr.hip): a bond / angle / torsion / external force with
-        self.term_expr = False      # a generic energy text; `program` is then that of expr.compile_term
-        self.cv = None              # a CustomCVForce on the collective-variable kernel (csrc/cv.hip): dict(id, names, derivs, inner, inner_ids);
-                                    # the id is also in term_ids, `program` is that of expr.compile_cv
-        self.compound = None        # a CustomCompoundBondForce / CustomCentroidBondForce (csrc/compound.hip): dict(id, variables, centroid);
-                                    # the id is also in term_ids, term_expr is set, `program` is that of expr.compile_compound
-        self.gb = None              # a GBSAOBCForce (csrc/gb.hip): its backend id, which is also in term_ids
-        self.cmap = None            # a CMAPTorsionForce (csrc/cmap.hip): its backend id, which is also in term_ids
-        self.custom_gb = None       # a CustomGBForce (csrc/custom_gb.hip): dict(id, n_values); the id is also in term_ids, `program`
-                                    # is what expr.compile_custom_gb returned
-        self.hbond = None           # a CustomHbondForce (csrc/hbond.hip): dict(id, variables); the id is also in term_ids, term_expr is
-                                    # set, `program` is that of expr.compile_hbond
-        self.rmsd = None            # an RMSDForce (csrc/rmsd.hip): its backend id, which is also in term_ids
-        self.gayberne = None        # a GayBerneForce (csrc/gayberne.hip): its backend id, which is also in term_ids
-        self.drude = None           # a DrudeForce (csrc/drude.hip): its backend id, which is also in term_ids
-        self.many = None            # a CustomManyParticleForce (csrc/manyparticle.hip): dict(id, variables, types); carried as hbond is,
-                                    # `program` is that of expr.compile_many_particle
-
-
-MANY_PERMUTATIONS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))     # of a tuple's positions, in lexicographic order
-
-
-def many_particle_table(filters, types, central):
-    """The permutation table of a CustomManyParticleForce over sets of three (csrc/manyparticle.hip).  filters[r]: the
-    set of types role r takes (empty: any); types: the sorted distinct types of the particles, whose positions are the dense type
-    indices.  Entry [a][b][c] speaks for a set whose tuple -- its particles in ascending order or, in central mode, the centre first
-    and the satellites ascending -- has the dense types (a, b, c): the code k of the first permutation MANY_PERMUTATIONS[k] = perm,
-    in lexicographic order, for which every role r takes the type of the tuple's element perm[r], or -1 when there is none (the set
-    is skipped).  Central mode keeps the centre at p1: codes 0 and 1 only.  Returns an int32 array [T][T][T]."""
-    T = len(types)
-    table = np.full((T, T, T), -1, dtype=np.int32)
-    candidates = MANY_PERMUTATIONS[:2] if central else MANY_PERMUTATIONS
-    for a in range(T):
-        for b in range(T):
-            for c in range(T):
-                tuple_types = (types[a], types[b], types[c])
-                for code, perm in enumerate(candidates):
-                    if all(not filters[r] or tuple_types[perm[r]] in filters[r] for r in range(3)):
-                        table[a, b, c] = code
-                        break
-    return table
-
-
-def gayberne_tables(force, n):
-    """What a GayBerneForce hands to the Gay-Berne kernels (csrc/gayberne.hip), checked against a System of n particles:
-    active   int32 [A]: the interacting particles, ascending -- epsilon > 0, or a member of an exception with epsilon > 0;
-    axes     int32 [A][2]: x- and y-particle of the row, -1: none;
-    par      float64 [A][8]: sigma, epsilon, sx, sy, sz, ex, ey, ez;
-    ex_ptr / ex_col / ex_par   the exceptions between active particles as a CSR over rows: columns are ACTIVE indices, ascending,
-             (sigma, epsilon) per entry, every pair on both rows (an exception with an inactive member can only have epsilon 0 and a
-             partner that the scan never meets: it is dropped);
-    rev_ptr / rev_src   int32 [n + 1] / [.]: per particle the entries 2 * row + (0: x-particle, 1: y-particle) that name it, ascending.
-    Raises OpenMMException by name for what the definition forbids."""
-    cls = 'GayBerneForce'
-    if force.getNumParticles() != n:
-        raise mm.OpenMMException('%s: the force has %d particles, the System %d' % (cls, force.getNumParticles(), n))
-    rows = force._particles
-    for i, (sigma, eps, xp, yp, sx, sy, sz, ex, ey, ez) in enumerate(rows):
-        if not (-1 <= xp < n and -1 <= yp < n):
-            raise mm.OpenMMException('%s: an axis particle of particle %d is out of range' % (cls, i))
-        if xp == i or yp == i:
-            raise mm.OpenMMException('%s: particle %d is its own axis particle' % (cls, i))
-        if sigma < 0.0 or eps < 0.0 or min(sx, sy, sz) <= 0.0 or min(ex, ey, ez) <= 0.0:
-            raise mm.OpenMMException('%s: particle %d needs sigma, epsilon >= 0 and diameters and well-depth scales above zero' % (cls, i))
-        if xp == -1 and not (sx == sy == sz and ex == ey == ez):
-            raise mm.OpenMMException('%s: particle %d has no x-particle, which only a sphere (sx = sy = sz, ex = ey = ez) may omit' % (cls, i))
-        if xp == -1 and yp != -1:
-            raise mm.OpenMMException('%s: particle %d has a y-particle and no x-particle' % (cls, i))
-        if yp == -1 and not (sy == sz and ey == ez):
-            raise mm.OpenMMException('%s: particle %d has no y-particle, which only a uniaxial shape (sy = sz, ey = ez) may omit' % (cls, i))
-    pairs = {}
-    for k, (i, j, sigma, eps) in enumerate(force._exceptions):
-        if not (0 <= i < n and 0 <= j < n) or i == j:
-            raise mm.OpenMMException('%s: exception %d names a particle that does not exist, or one particle twice' % (cls, k))
-        if sigma < 0.0 or eps < 0.0:
-            raise mm.OpenMMException('%s: exception %d needs sigma, epsilon >= 0' % (cls, k))
-        key = (min(i, j), max(i, j))
-        if key in pairs:
-            raise mm.OpenMMException('%s: two exceptions for particles %d and %d' % ((cls,) + key))
-        pairs[key] = (sigma, eps)
-    interacting = {i for i, row in enumerate(rows) if row[1] > 0.0}
-    interacting |= {m for key, (_, eps) in pairs.items() if eps > 0.0 for m in key}
-    active = np.array(sorted(interacting), dtype=np.int32)
-    act_of = {int(p): k for k, p in enumerate(active)}
-    axes = np.array([[rows[p][2], rows[p][3]] for p in active], dtype=np.int32).reshape(-1, 2)
-    par = np.array([rows[p][:2] + rows[p][4:] for p in active], dtype=np.float64).reshape(-1, 8)
-    entries = sorted((act_of[a], act_of[b], v) for (i, j), v in pairs.items() if i in act_of and j in act_of
-                     for a, b in ((i, j), (j, i)))
-    ex_ptr = np.zeros(len(active) + 1, dtype=np.int32)
-    for r, _, _ in entries:
-        ex_ptr[r + 1] += 1
-    ex_ptr = np.cumsum(ex_ptr, dtype=np.int32)
-    ex_col = np.array([c for _, c, _ in entries], dtype=np.int32)
-    ex_par = np.array([v for _, _, v in entries], dtype=np.float64).reshape(-1, 2)
-    named = sorted((int(axes[k, r]), 2 * k + r) for k in range(len(active)) for r in range(2) if axes[k, r] >= 0)
-    rev_ptr = np.zeros(n + 1, dtype=np.int32)
-    for p, _ in named:
-        rev_ptr[p + 1] += 1
-    rev_ptr = np.cumsum(rev_ptr, dtype=np.int32)
-    rev_src = np.array([src for _, src in named], dtype=np.int32)
-    return dict(active=active, axes=axes, par=par, ex_ptr=ex_ptr, ex_col=ex_col, ex_par=ex_par, rev_ptr=rev_ptr, rev_src=rev_src)
-
-
-def drude_tables(force, n, constrained=()):
-    """What a DrudeForce hands to the Drude kernels (csrc/drude.hip), checked against a System of n particles whose
-    constrained particles are `constrained`:
-    idx      int32 [D][5]: particle, particle1 .. particle4 (-1: none);
-    par      float64 [D][4]: charge, polarizability, aniso12, aniso34;
-    pairs    int32 [P][2]: the two Drude entries of a screened pair;  thole  float64 [P].
-    Raises OpenMMException by name for what the definition forbids."""
-    cls = 'DrudeForce'
-    rows = force._particles
-    held = set(int(c) for c in constrained)
-    seen = {}
-    for k, (p, p1, p2, p3, p4, q, alpha, a12, a34) in enumerate(rows):
-        if not (0 <= p < n and 0 <= p1 < n):
-            raise mm.OpenMMException('%s: Drude particle %d names a particle or a parent that is out of range' % (cls, k))
-        if not all(-1 <= a < n for a in (p2, p3, p4)):
-            raise mm.OpenMMException('%s: Drude particle %d names an anisotropy particle that is out of range' % (cls, k))
-        for a in (p, p1):
-            if a in seen or p == p1:
-                raise mm.OpenMMException('%s: particle %d is listed twice as a Drude particle or a parent (Drude particles %d and %d)'
-                                         % (cls, a, seen.get(a, k), k))
-        seen[p] = seen[p1] = k
-        if p in held:
-            raise mm.OpenMMException('%s: Drude particle %d (particle %d) is constrained' % (cls, k, p))
-        if p2 == p1 or (p3 != -1 and p3 == p4):
-            raise mm.OpenMMException('%s: an anisotropy direction of Drude particle %d joins a particle to itself' % (cls, k))
-        a1 = a12 if p2 != -1 else 1.0
-        a2 = a34 if (p3 != -1 and p4 != -1) else 1.0
-        if not alpha > 0.0:
-            raise mm.OpenMMException('%s: Drude particle %d needs a polarizability above zero' % (cls, k))
-        if not (a1 > 0.0 and a2 > 0.0 and 3.0 - a1 - a2 > 0.0):
-            raise mm.OpenMMException('%s: Drude particle %d needs aniso12, aniso34 and 3 - aniso12 - aniso34 above zero' % (cls, k))
-    for k, (d1, d2, thole) in enumerate(force._pairs):
-        if not (0 <= d1 < len(rows) and 0 <= d2 < len(rows)) or d1 == d2:
-            raise mm.OpenMMException('%s: screened pair %d names a Drude particle that does not exist, or one twice' % (cls, k))
-    idx = np.array([r[:5] for r in rows], dtype=np.int32).reshape(-1, 5)
-    par = np.array([r[5:] for r in rows], dtype=np.float64).reshape(-1, 4)
-    pairs = np.array([r[:2] for r in force._pairs], dtype=np.int32).reshape(-1, 2)
-    thole = np.array([r[2] for r in force._pairs], dtype=np.float64)
-    return dict(idx=idx, par=par, pairs=pairs, thole=thole)
 
 
 def slice_bounds(n_items, rank, world):
@@ -463,13 +193,9 @@ class Engine:
         # measure its host-side cost on a single GPU
         self._coll = self.world > 1 or (os.environ.get('AMM_FORCE_COLLECTIVES') == '1' and dist.is_available()
                                         and dist.is_initialized())
-        self._check_gb(system, integrator)
-        self._check_custom_gb(system, integrator)
-        self._check_hbond(system, integrator)
-        self._check_many_particle(system, integrator)
-        if self.world > 1 and any(isinstance(f, mm.GayBerneForce) for f in system.getForces()):
-            raise InputError('a GayBerneForce runs on a single rank: its wavefronts walk all pairs of ellipsoids and are not sliced')
-        self._check_drude(system, integrator)
+        TR.check_system(self, system, integrator)
+        # the DrudeForce a DrudeLangevinIntegrator steps (check_system: there is exactly one)
+        self._drude_force = [f for f in system.getForces() if isinstance(f, mm.DrudeForce)][0] if TR.drude_step_of(self) else None
         self._check_massless(system, integrator)
         if self.free_space and self.world > 1:
             raise InputError('a System in free space (NoCutoff / CutoffNonPeriodic) runs on a single rank: its pair forces walk all pairs '
@@ -519,8 +245,8 @@ class Engine:
             self.ctx.set_outer_skin(float(properties['OuterSkin']))
         self._pair_info = {}
         for force in system.getForces():
-            self._translate(force)
-        self._share_lists()
+            TR.translate(self, force)
+        TR.share_lists(self)
         self._slots = {}
         self._buffers = {}
         self._arena_free = []
@@ -587,31 +313,6 @@ class Engine:
         if what is not None:
             raise InputError('a System with massless particles or virtual sites does not run with %s' % what)
 
-    def _check_drude(self, system, integrator):
-        """A DrudeForce or a DrudeLangevinIntegrator: what they cannot run with is refused here, by name, when the Context is created."""
-        forces = [f for f in system.getForces() if isinstance(f, mm.DrudeForce)]
-        self._drude_force = None
-        drude_step = self._stock is not None and getattr(self._stock, '_drude', False)
-        if drude_step and len(forces) != 1:
-            raise InputError('a DrudeLangevinIntegrator needs a System with exactly one DrudeForce (this one has %d)' % len(forces))
-        if not forces:
-            return
-        if self.world > 1:
-            raise InputError('a DrudeForce runs on a single rank: its springs and screened pairs are not sliced')
-        texts = [e.replace(' ', '') for _, _, e in getattr(integrator, '_steps', []) if isinstance(e, str)]
-        if any('deriv(energy' in t for t in texts):
-            raise NotImplementedError('deriv(energy, ...) in a System with a DrudeForce is not supported: the Drude kernels have no '
-                                      'derivative mode')
-        if any('cosh(z)' in t and 'LkT' in t for t in texts):
-            raise NotImplementedError('a DrudeForce does not run with the SIN(R) / isokinetic path')
-        if any('tanh(' in t for t in texts):
-            raise NotImplementedError('a DrudeForce does not run with the regulated path')
-        constrained = {int(c[k]) for c in system._constraints for k in (0, 1)}
-        for force in forces:
-            drude_tables(force, system.getNumParticles(), constrained)
-        if drude_step:
-            self._drude_force = forces[0]
-
     def drude_pairs(self):
         """int32 [P][2]: (Drude particle, parent) of the DrudeForce a DrudeLangevinIntegrator steps."""
         return np.array([r[:2] for r in self._drude_force._particles], dtype=np.int32).reshape(-1, 2)
@@ -663,536 +364,31 @@ class Engine:
             self.ctx.vsite_place(self.x)
             self._invalidate_forces()
 
-    @staticmethod
-    def _free_space_mode(system, has_box):
-        """True: a free-space Context -- every NonbondedForce / CustomNonbondedForce is NoCutoff or CutoffNonPeriodic, no bonded
-        force uses periodic boundary conditions and the System holds a force (box vectors may be absent; present ones are ignored).
-        False: all nonbonded forces periodic, as ever.  A mixture is an InputError."""
-        def pair_forces(force):
-            if isinstance(force, (mm.NonbondedForce, mm.CustomNonbondedForce, mm.GBSAOBCForce, mm.CustomGBForce)):
-                return [force]
-            if isinstance(force, mm.CustomCVForce):
-                return [f for k in range(force.getNumCollectiveVariables()) for f in pair_forces(force.getCollectiveVariable(k))]
-            return []
-        forces = list(system.getForces())
-        pairs = [f for force in forces for f in pair_forces(force)]
-        # a generalized-Born force runs in free space only (csrc/gb.hip): refused by name, not as a mixture
-        for cls in (mm.GBSAOBCForce, mm.CustomGBForce):
-            if not any(isinstance(f, cls) for f in pairs):
-                continue
-            for f in pairs:
-                if isinstance(f, cls) and f.usesPeriodicBoundaryConditions():
-                    raise InputError('%s: CutoffPeriodic is not supported: generalized-Born solvent runs in free space only '
-                                     '(NoCutoff / CutoffNonPeriodic)' % cls.__name__)
-                if f.usesPeriodicBoundaryConditions():
-                    raise InputError('a %s in a System with a box-periodic %s: generalized-Born solvent runs in free space '
-                                     'only (every nonbonded method NoCutoff or CutoffNonPeriodic)' % (cls.__name__, f.__class__.__name__))
-        free = [f for f in pairs if not f.usesPeriodicBoundaryConditions()]
-        if free and len(free) != len(pairs):
-            raise InputError('the System mixes periodic and non-periodic nonbonded methods: every NonbondedForce / CustomNonbondedForce '
-                             'must be NoCutoff or CutoffNonPeriodic (free space), or every one periodic')
-        if (pairs and not free) or (not pairs and (has_box or not forces)):
-            return False              # periodic, or nothing to decide by (no box and no forces: the error of old)
-        periodic = [f for f in forces if not pair_forces(f) and not isinstance(f, mm.MonteCarloBarostat) and f.usesPeriodicBoundaryConditions()]
-        if periodic:
-            raise InputError('the System mixes non-periodic nonbonded methods (or no box) with a %s that uses periodic boundary '
-                             'conditions' % periodic[0].__class__.__name__)
-        return True
-
-    GB_MAX_ATOMS = 32768      # csrc/amm_ctx.h: AMM_FREE_MAX_ATOMS
-
-    def _check_gb(self, system, integrator):
-        """What a GBSAOBCForce cannot run with, refused by name when the Context is created (CutoffPeriodic and box-periodic
-        companions: _free_space_mode)."""
-        gbs = [f for f in system.getForces() if isinstance(f, mm.GBSAOBCForce)]
-        if not gbs:
-            return
-        n = system.getNumParticles()
-        for gb in gbs:
-            if gb.getNumParticles() != n:
-                raise mm.OpenMMException('GBSAOBCForce must have exactly as many particles as the System it belongs to (%d, the System '
-                                         'has %d)' % (gb.getNumParticles(), n))
-        if self.world > 1:
-            raise InputError('a GBSAOBCForce runs on a single rank: its passes walk all pairs and are not sliced')
-        if n > self.GB_MAX_ATOMS:
-            raise InputError('a GBSAOBCForce walks all n^2 pairs three times per evaluation and takes at most %d atoms (the System has %d)'
-                             % (self.GB_MAX_ATOMS, n))
-        for _kind, _target, expr in getattr(integrator, '_steps', []):
-            if expr and 'deriv(' in expr:
-                raise NotImplementedError('deriv(energy, ...) through a GBSAOBCForce is not supported: the generalized-Born kernels have '
-                                          'no parameter-derivative evaluation (step: %s)' % expr)
-
-    def _check_custom_gb(self, system, integrator):
-        """What a CustomGBForce cannot run with, refused by name when the Context is created (CutoffPeriodic and box-periodic
-        companions: _free_space_mode; its texts and limits: _translate_custom_gb)."""
-        cgs = [f for f in system.getForces() if isinstance(f, mm.CustomGBForce)]
-        if not cgs:
-            return
-        n = system.getNumParticles()
-        for cg in cgs:
-            if cg.getNumParticles() != n:
-                raise mm.OpenMMException('CustomGBForce must have exactly as many particles as the System it belongs to (%d, the System '
-                                         'has %d)' % (cg.getNumParticles(), n))
-            if cg.getNumEnergyParameterDerivatives():
-                raise NotImplementedError('CustomGBForce.addEnergyParameterDerivative(%r) is not supported: the custom generalized-Born '
-                                          'kernels differentiate in positions only' % cg.getEnergyParameterDerivativeName(0))
-        if self.world > 1:
-            raise InputError('a CustomGBForce runs on a single rank: its passes walk all pairs and are not sliced')
-        if n > self.GB_MAX_ATOMS:
-            raise InputError('a CustomGBForce walks all n^2 pairs up to three times per evaluation and takes at most %d atoms (the System '
-                             'has %d)' % (self.GB_MAX_ATOMS, n))
-        for _kind, _target, expr in getattr(integrator, '_steps', []):
-            if expr and 'deriv(' in expr:
-                raise NotImplementedError('deriv(energy, ...) through a CustomGBForce is not supported: the custom generalized-Born '
-                                          'kernels have no parameter-derivative evaluation (step: %s)' % expr)
-
-    @staticmethod
-    def check_custom_gb_symmetry(text, per_particle_names, value_names, global_values, rows, functions=None, samples=6, seed=20240607):
-        """A pair energy term is evaluated from both rows and counted half (csrc/custom_gb.hip), so it must not change when the
-        particles swap -- parameters AND computed values: check_pair_symmetry with the values among the swapped names.  The sample
-        parameters are rows the force has (`rows`: [n][parameters]; a type index is no uniform draw), the values seeded draws."""
-        rng = np.random.default_rng(seed)
-        rows = np.unique(np.asarray(rows, dtype=np.float64).reshape(-1, len(per_particle_names)), axis=0) if per_particle_names else np.zeros((1, 0))
-        for _ in range(samples):
-            a, b = rows[rng.integers(0, len(rows))], rows[rng.integers(0, len(rows))]
-            one = dict(zip(per_particle_names, map(float, a)), **{nm: float(rng.uniform(0.2, 1.5)) for nm in value_names})
-            two = dict(zip(per_particle_names, map(float, b)), **{nm: float(rng.uniform(0.2, 1.5)) for nm in value_names})
-            env = dict(global_values, r=float(rng.uniform(0.3, 1.2)))
-            fwd = dict(env, **{nm + '1': v for nm, v in one.items()}, **{nm + '2': v for nm, v in two.items()})
-            swp = dict(env, **{nm + '1': v for nm, v in two.items()}, **{nm + '2': v for nm, v in one.items()})
-            try:
-                x, y = X.eval_global(text, fwd, functions=functions), X.eval_global(text, swp, functions=functions)
-            except (ArithmeticError, ValueError) as exc:
-                if isinstance(exc, X.ExpressionError):
-                    raise
-                continue               # (outside the text's domain at this draw: says nothing about symmetry)
-            if x != x and y != y:
-                continue
-            if not abs(x - y) <= 1e-12 * max(abs(x), abs(y), 1e-300):
-                raise InputError('CustomGBForce: the pair energy term %r is not symmetric in particles 1 and 2' % text.split(';')[0])
-
-    def _translate_custom_gb(self, force, entry):
-        """A CustomGBForce: its texts compiled here (expr.compile_custom_gb), one backend force (csrc/custom_gb.hip) carried in
-        entry.term_ids, so every loop over an entry's forces reaches it and the scheduler's fusion rules decline its group."""
-        cls = 'CustomGBForce'
-        if force.usesPeriodicBoundaryConditions():
-            raise InputError('%s: CutoffPeriodic is not supported: generalized-Born solvent runs in free space only' % cls)
-        if force.getNumEnergyParameterDerivatives():
-            raise NotImplementedError('%s.addEnergyParameterDerivative is not supported' % cls)
-        names = [force.getPerParticleParameterName(k) for k in range(force.getNumPerParticleParameters())]
-        gnames = [force.getGlobalParameterName(k) for k in range(force.getNumGlobalParameters())]
-        values = [tuple(force.getComputedValueParameters(k)) for k in range(force.getNumComputedValues())]
-        terms = [tuple(force.getEnergyTermParameters(k)) for k in range(force.getNumEnergyTerms())]
-        functions = list(force._functions)
-        try:
-            progs = X.compile_custom_gb(names, gnames, values, terms, T.declared(functions) if functions else None)
-        except X.ExpressionError as exc:
-            raise InputError('%s: not a model the custom generalized-Born kernels can run: %s' % (cls, exc))
-        uses_tables = any(X.table_words(p.code) for p in progs.programs)
-        n = self.n
-
-        def params():
-            if force.getNumParticles() != n:
-                raise mm.OpenMMException('%s must have exactly as many particles as the System it belongs to' % cls)
-            allp = np.array(force._particles, dtype=np.float64).reshape(n, -1) if names else np.zeros((n, 0))
-            if allp.shape[1] != len(names):
-                raise mm.OpenMMException('%s: every particle needs %d parameters' % (cls, len(names)))
-            return allp
-
-        def checked():
-            """The particles' rows after the checks the host can make: every pair energy term is symmetric over them."""
-            rows = params()
-            callables = {name: T.host_callable(fn) for name, fn in functions} or None
-            for text, kind in terms:
-                if kind != force.SingleParticle:
-                    self.check_custom_gb_symmetry(text, names, [v[0] for v in values], {g: self.parameters[g] for g in gnames}, rows,
-                                                  functions=callables)
-            return rows
-
-        rows = checked()
-        rc = force._cutoff if force.getNonbondedMethod() == force.CutoffNonPeriodic else 0.0
-        excl = np.array(force._exclusions, dtype=np.int32).reshape(-1, 2)
-        frozen = (len(values), len(terms), [list(v) for v in values], [list(t) for t in terms], excl.copy(), len(functions))
-        try:
-            gid = self.ctx.custom_gb_create(len(values), progs.types, [(p.code, p.consts) for p in progs.programs],
-                                            [self.parameters[g] for g in gnames], np.ascontiguousarray(rows.T), excl, rc)
-            if uses_tables or functions:
-                self.ctx.custom_gb_set_tables(gid, [T.device_table(fn) for _, fn in functions])
-        except B.HipError as exc:
-            raise InputError('%s: %s' % (cls, exc))
-        entry.term_ids.append(gid)
-        entry.custom_gb = dict(id=gid, n_values=len(values))
-        entry.program = progs
-
-        def reload():          # updateParametersInContext: the per-particle parameters and the tables' values are read again
-            now = (force.getNumComputedValues(), force.getNumEnergyTerms(), [list(v) for v in force._values], [list(t) for t in force._terms],
-                   np.array(force._exclusions, dtype=np.int32).reshape(-1, 2), len(force._functions))
-            if now[:4] != frozen[:4] or now[5] != frozen[5] or not np.array_equal(now[4], frozen[4]):
-                raise mm.OpenMMException('%s.updateParametersInContext: the computed values, energy terms, exclusions and the number of '
-                                         'tabulated functions cannot change in a live Context' % cls)
-            fresh = checked()
-            try:
-                if functions:
-                    self.ctx.custom_gb_set_tables(gid, [T.device_table(fn) for _, fn in functions])
-                self.ctx.custom_gb_set_params(gid, np.ascontiguousarray(fresh.T))
-            except B.HipError as exc:
-                raise InputError('%s: %s' % (cls, exc))
-            return 'values'
-        entry.reload = reload
-        if gnames:
-            depends = set(gnames)
-
-            def update(parameters, changed):
-                if not (depends & changed):
-                    return False
-                self.ctx.custom_gb_set_globals(gid, [parameters[g] for g in gnames])
-                return 'values'
-            entry.update = update
-            entry.depends = depends
+    # what translation owns and callers name on the class (atomsmm_amd/translate)
+    _free_space_mode = staticmethod(TR.free_space_mode)
+    _translate_cv = TR.translate_cv
+    check_pair_symmetry = staticmethod(TR.check_pair_symmetry)
+    check_custom_gb_symmetry = staticmethod(TR.check_custom_gb_symmetry)
+    GAYBERNE_MAX, RB_TEXT, _CV_INNER_CLASSES = TR.GAYBERNE_MAX, TR.RB_TEXT, TR.CV_INNER_CLASSES
 
     def custom_gb_values(self, force):
         """CustomGBForce.getComputedValues(context): the computed values at the current positions, [value][particle]."""
-        hits = [e for e in self.entries if e.force is force and getattr(e, 'custom_gb', None) is not None]
-        if not hits:
-            raise mm.OpenMMException('getComputedValues: the force does not belong to this Context')
-        cg = hits[0].custom_gb
+        cg = TR.entry_of(self, force, 'custom_gb', 'getComputedValues').custom_gb
         out = self.ctx.custom_gb_values(cg['id'], self.x, cg['n_values'])
         self._check()
         return out
 
-    HBOND_MAX = 32768         # csrc/hbond.hip: AMM_HB_MAX_ROWS donors, and as many acceptors
-
-    def _check_hbond(self, system, integrator):
-        """What a CustomHbondForce cannot run with, refused by name when the Context is created (its text and limits:
-        _translate_hbond; as a collective variable: _translate_cv_general names the classes it takes)."""
-        if not any(isinstance(f, mm.CustomHbondForce) for f in system.getForces()):
-            return
-        if self.world > 1:
-            raise InputError('a CustomHbondForce runs on a single rank: its passes walk all donor-acceptor pairs and are not sliced')
-        for _kind, _target, expr in getattr(integrator, '_steps', []):
-            if expr and 'deriv(' in expr:
-                raise NotImplementedError('deriv(energy, ...) through a CustomHbondForce is not supported: the hydrogen-bond kernel '
-                                          'differentiates in the geometric variables only (step: %s)' % expr)
-
-    def _translate_hbond(self, force, entry):
-        """A CustomHbondForce: the text compiled with its variable table (expr.compile_hbond) and evaluated over all donor-acceptor
-        pairs by the hydrogen-bond kernels (csrc/hbond.hip).  One backend force, carried in entry.term_ids as a term-expression
-        force is, so every loop over an entry's forces reaches it and the scheduler's fusion rules decline its group."""
-        cls = 'CustomHbondForce'
-        if getattr(force, '_functions', None):
-            raise NotImplementedError('%s: tabulated functions in the energy expression are not supported' % cls)
-        if self.world > 1:
-            raise InputError('a %s runs on a single rank' % cls)
-        method = force.getNonbondedMethod()
-        periodic = method == force.CutoffPeriodic
-        if periodic and self.free_space:
-            raise InputError('%s uses CutoffPeriodic in a System in free space' % cls)
-        dnames = [force.getPerDonorParameterName(k) for k in range(force.getNumPerDonorParameters())]
-        anames = [force.getPerAcceptorParameterName(k) for k in range(force.getNumPerAcceptorParameters())]
-        gnames = [force.getGlobalParameterName(k) for k in range(force.getNumGlobalParameters())]
-        try:
-            prog, variables = X.compile_hbond(force.getEnergyFunction(), dnames, anames, gnames)
-        except X.ExpressionError as exc:
-            raise InputError('%s: not an energy expression the hydrogen-bond kernel can run: %s' % (cls, exc))
-        kinds = [self._COMPOUND_KINDS[kind] for kind, _ in variables]
-        slots = [list(s) for _, s in variables]
-        named = sorted({s for _, ss in variables for s in ss})
-        slot_names = ('d1', 'd2', 'd3', 'a1', 'a2', 'a3')
-        n = self.n
-
-        def tables():
-            out = []
-            for side, rows, names, limit in (('donor', force._donors, dnames, 0), ('acceptor', force._acceptors, anames, 3)):
-                if len(rows) > self.HBOND_MAX:
-                    raise InputError('%s: %d %ss (limit %d)' % (cls, len(rows), side, self.HBOND_MAX))
-                idx = np.zeros((len(rows), 3), dtype=np.int32)
-                par = np.zeros((len(names), len(rows)), dtype=np.float64)
-                for t, (members, p) in enumerate(rows):
-                    if len(p) != len(names):
-                        raise mm.OpenMMException('%s: every %s needs %d parameters' % (cls, side, len(names)))
-                    if not 0 <= members[0] < n or any(not -1 <= m < n for m in members[1:]):
-                        raise mm.OpenMMException('%s: a particle index of %s %d is out of range' % (cls, side, t))
-                    for r in range(3):
-                        if members[r] == -1 and limit + r in named:
-                            raise InputError('%s: the energy expression names %s, which %s %d leaves at -1' % (cls, slot_names[limit + r], side, t))
-                    idx[t] = members
-                    par[:, t] = p
-                out += [idx, par]
-            return out
-
-        def exclusions():
-            ex = np.array(force._exclusions, dtype=np.int32).reshape(-1, 2)
-            if len(ex) and (ex.min() < 0 or ex[:, 0].max() >= force.getNumDonors() or ex[:, 1].max() >= force.getNumAcceptors()):
-                raise mm.OpenMMException('%s: an exclusion names a donor or an acceptor that does not exist (the indices are those of '
-                                         'donors and acceptors, not of atoms)' % cls)
-            return ex
-
-        didx, dpar, aidx, apar = tables()
-        excl = exclusions()
-        rc = 0.0 if method == force.NoCutoff else float(force._cutoff)
-        if method != force.NoCutoff and not rc > 0.0:
-            raise InputError('%s: the cutoff distance must be above zero' % cls)
-        try:
-            fid = self.ctx.hbond_create(prog.code, prog.consts, [self.parameters[g] for g in prog.globals_], kinds, slots, didx, aidx, dpar, apar,
-                                        excl, rc=rc, periodic=periodic)
-        except B.HipError as exc:
-            raise InputError('%s: %s' % (cls, exc))
-        entry.term_ids.append(fid)
-        entry.term_expr = True
-        entry.program = prog
-        entry.hbond = dict(id=fid, variables=variables)
-
-        def reload():          # updateParametersInContext: the per-donor and per-acceptor parameters are read again
-            f_didx, f_dpar, f_aidx, f_apar = tables()
-            if len(f_didx) != len(didx) or len(f_aidx) != len(aidx):
-                raise mm.OpenMMException('updateParametersInContext: the number of donors or acceptors has changed')
-            if not (np.array_equal(f_didx, didx) and np.array_equal(f_aidx, aidx)):
-                raise mm.OpenMMException('updateParametersInContext: the particles of a donor or an acceptor have changed')
-            if not np.array_equal(exclusions(), excl):
-                raise mm.OpenMMException('updateParametersInContext: the exclusions have changed')
-            self.ctx.hbond_set_params(fid, f_dpar, len(didx), f_apar, len(aidx))
-            return 'values'
-        entry.reload = reload
-        if prog.globals_:
-            depends = set(prog.globals_)
-
-            def update(parameters, changed):
-                if not (depends & changed):
-                    return False
-                self.ctx.hbond_set_globals(fid, [parameters[g] for g in prog.globals_])
-                return 'values'
-            entry.update = update
-            entry.depends = depends
-
     def hbond_stats(self, force):
         """dict(scanned, survivors, launches, chunks) of a CustomHbondForce of this Context (backend.HipContext.hbond_stats)."""
-        hits = [e for e in self.entries if e.force is force and getattr(e, 'hbond', None) is not None]
-        if not hits:
-            raise mm.OpenMMException('hbond_stats: the force does not belong to this Context')
-        return self.ctx.hbond_stats(hits[0].hbond['id'])
-
-    MANY_MAX = 32768          # csrc/manyparticle.hip: AMM_MP_MAX_PARTICLES
-    MANY_MAX_NOCUTOFF = 2048  # ... AMM_MP_MAX_NOCUTOFF: the neighbour table is n x (n - 1) without a cutoff
-    MANY_MAX_TYPES = 16       # ... AMM_MP_MAX_TYPES
-
-    def _check_many_particle(self, system, integrator):
-        """What a CustomManyParticleForce cannot run with, refused by name when the Context is created (its text and limits:
-        _translate_many_particle; as a collective variable: _translate_cv_general names the classes it takes)."""
-        if not any(isinstance(f, mm.CustomManyParticleForce) for f in system.getForces()):
-            return
-        if self.world > 1:
-            raise InputError('a CustomManyParticleForce runs on a single rank: its wavefronts walk the neighbours of every particle and are not sliced')
-        for _kind, _target, expr in getattr(integrator, '_steps', []):
-            if expr and 'deriv(' in expr:
-                raise NotImplementedError('deriv(energy, ...) through a CustomManyParticleForce is not supported: the many-particle kernel '
-                                          'differentiates in the geometric variables only (step: %s)' % expr)
-
-    def _translate_many_particle(self, force, entry):
-        """A CustomManyParticleForce over sets of three: the text compiled with its variable table (expr.compile_many_particle), the
-        type filters turned into the permutation table (many_particle_table) and the sets enumerated on the device by the
-        many-particle kernels (csrc/manyparticle.hip).  One backend force, carried in entry.term_ids as a hydrogen-bond force is, so
-        every loop over an entry's forces reaches it and the scheduler's fusion rules decline its group."""
-        cls = 'CustomManyParticleForce'
-        per_set = force.getNumParticlesPerSet()
-        if per_set != 3:
-            raise NotImplementedError('%s: sets of %d particles are not supported (the many-particle kernel enumerates sets of three)' % (cls, per_set))
-        if getattr(force, '_functions', None):
-            raise NotImplementedError('%s: tabulated functions in the energy expression are not supported' % cls)
-        if self.world > 1:
-            raise InputError('a %s runs on a single rank' % cls)
-        method = force.getNonbondedMethod()
-        periodic = method == force.CutoffPeriodic
-        if periodic and self.free_space:
-            raise InputError('%s uses CutoffPeriodic in a System in free space' % cls)
-        central = force.getPermutationMode() == force.UniqueCentralParticle
-        pnames = [force.getPerParticleParameterName(k) for k in range(force.getNumPerParticleParameters())]
-        gnames = [force.getGlobalParameterName(k) for k in range(force.getNumGlobalParameters())]
-        try:
-            prog, variables = X.compile_many_particle(force.getEnergyFunction(), 3, pnames, gnames)
-        except X.ExpressionError as exc:
-            raise InputError('%s: not an energy expression the many-particle kernel can run: %s' % (cls, exc))
-        kinds = [self._COMPOUND_KINDS[kind] for kind, _ in variables]
-        slots = [list(s) for _, s in variables]
-        n = self.n
-        if force.getNumParticles() != n:
-            raise mm.OpenMMException('%s: the force has %d particles, the System %d' % (cls, force.getNumParticles(), n))
-        if n > self.MANY_MAX:
-            raise InputError('%s: %d particles (limit %d)' % (cls, n, self.MANY_MAX))
-        if method == force.NoCutoff and n > self.MANY_MAX_NOCUTOFF:
-            raise InputError('%s: %d particles under NoCutoff (limit %d: the neighbour table is n x (n - 1); use a cutoff)' % (cls, n, self.MANY_MAX_NOCUTOFF))
-
-        def tables():
-            par = np.zeros((len(pnames), n), dtype=np.float64)
-            raw = np.zeros(n, dtype=np.int64)
-            for t, (p, kind) in enumerate(force._particles):
-                if len(p) != len(pnames):
-                    raise mm.OpenMMException('%s: every particle needs %d parameters' % (cls, len(pnames)))
-                par[:, t] = p
-                raw[t] = kind
-            known = sorted(set(raw.tolist()))
-            if len(known) > self.MANY_MAX_TYPES:
-                raise InputError('%s: %d distinct particle types (limit %d)' % (cls, len(known), self.MANY_MAX_TYPES))
-            known = known or [0]
-            dense = np.array([known.index(t) for t in raw.tolist()], dtype=np.int32)
-            filters = [force.getTypeFilter(r) for r in range(3)]
-            return par, dense, len(known), many_particle_table(filters, known, central)
-
-        def exclusions():
-            ex = np.array(force._exclusions, dtype=np.int32).reshape(-1, 2)
-            if len(ex) and (ex.min() < 0 or ex.max() >= n):
-                raise mm.OpenMMException('%s: an exclusion names a particle that does not exist' % cls)
-            return ex
-
-        par, dense, n_types, table = tables()
-        excl = exclusions()
-        rc = 0.0 if method == force.NoCutoff else float(force._cutoff)
-        if method != force.NoCutoff and not rc > 0.0:
-            raise InputError('%s: the cutoff distance must be above zero' % cls)
-        try:
-            fid = self.ctx.many_create(prog.code, prog.consts, [self.parameters[g] for g in prog.globals_], kinds, slots, par, dense, n_types, table,
-                                       excl, rc=rc, periodic=periodic, central=central)
-        except B.HipError as exc:
-            raise InputError('%s: %s' % (cls, exc))
-        entry.term_ids.append(fid)
-        entry.term_expr = True
-        entry.program = prog
-        entry.many = dict(id=fid, variables=variables, types=n_types)
-
-        def reload():          # updateParametersInContext: the per-particle parameters, the types and the filters are read again
-            if force.getNumParticles() != n:
-                raise mm.OpenMMException('updateParametersInContext: the number of particles has changed')
-            if not np.array_equal(exclusions(), excl):
-                raise mm.OpenMMException('updateParametersInContext: the exclusions have changed')
-            f_par, f_dense, f_types, f_table = tables()
-            self.ctx.many_set_params(fid, f_par, f_dense, f_types, f_table)
-            entry.many['types'] = f_types
-            return 'values'
-        entry.reload = reload
-        if prog.globals_:
-            depends = set(prog.globals_)
-
-            def update(parameters, changed):
-                if not (depends & changed):
-                    return False
-                self.ctx.many_set_globals(fid, [parameters[g] for g in prog.globals_])
-                return 'values'
-            entry.update = update
-            entry.depends = depends
+        return self.ctx.hbond_stats(TR.entry_of(self, force, 'hbond', 'hbond_stats').hbond['id'])
 
     def many_stats(self, force):
         """dict(particles, sets, launches, fullest, capacity) of a CustomManyParticleForce of this Context (backend.HipContext.many_stats)."""
-        hits = [e for e in self.entries if e.force is force and getattr(e, 'many', None) is not None]
-        if not hits:
-            raise mm.OpenMMException('many_stats: the force does not belong to this Context')
-        return self.ctx.many_stats(hits[0].many['id'])
-
-    GAYBERNE_MAX = 32768      # csrc/gayberne.hip: AMM_GY_MAX_ROWS interacting particles
-
-    def _translate_gayberne(self, force, entry):
-        """A GayBerneForce: the interacting particles compacted, their exceptions as a CSR and the reverse table of the axis particles
-        (gayberne_tables) go to the Gay-Berne kernels (csrc/gayberne.hip).  One backend force carried in entry.term_ids, so every
-        loop over an entry's forces reaches it and the scheduler's fusion rules decline its group, as they do for a hydrogen-bond
-        force.  It reads no Context parameter: deriv(energy, p) sees no dependence through it."""
-        cls = 'GayBerneForce'
-        method = force.getNonbondedMethod()
-        periodic = method == force.CutoffPeriodic
-        if periodic and self.free_space:
-            raise InputError('%s uses CutoffPeriodic in a System in free space' % cls)
-        n = self.n
-        rc = 0.0 if method == force.NoCutoff else float(force._cutoff)
-        if method != force.NoCutoff and not rc > 0.0:
-            raise InputError('%s: the cutoff distance must be above zero' % cls)
-        rs = -1.0
-        if method != force.NoCutoff and force.getUseSwitchingFunction():
-            rs = float(force._switch)
-            if not 0.0 <= rs < rc:
-                raise InputError('%s: the switching distance %g lies outside [0, cutoff = %g)' % (cls, rs, rc))
-        if periodic and rc > 0.5 * float(self.box.min()):
-            raise InputError('%s: the cutoff %g exceeds half the shortest box edge (%g)' % (cls, rc, float(self.box.min())))
-        tab = gayberne_tables(force, n)
-        if len(tab['active']) > self.GAYBERNE_MAX:
-            raise InputError('%s: %d particles with epsilon > 0 (limit %d)' % (cls, len(tab['active']), self.GAYBERNE_MAX))
-        try:
-            fid = self.ctx.gayberne_create(tab['active'], tab['axes'], tab['par'], tab['ex_ptr'], tab['ex_col'], tab['ex_par'], tab['rev_ptr'],
-                                           tab['rev_src'], rc=rc, rs=rs, periodic=periodic)
-        except B.HipError as exc:
-            raise InputError('%s: %s' % (cls, exc))
-        entry.term_ids.append(fid)
-        entry.gayberne = fid
-
-        def reload():          # updateParametersInContext: the particle and exception parameters are read again
-            new = gayberne_tables(force, n)
-            for key, what in (('active', 'the set of interacting particles (epsilon > 0, or in an exception with epsilon > 0)'),
-                              ('axes', 'the x- or y-particle of an ellipsoid'), ('ex_ptr', 'the pairs that have an exception'),
-                              ('ex_col', 'the pairs that have an exception')):
-                if not np.array_equal(new[key], tab[key]):
-                    raise mm.OpenMMException('updateParametersInContext: %s has changed' % what)
-            self.ctx.gayberne_set_params(fid, new['par'], new['ex_par'])
-            return 'values'
-        entry.reload = reload
+        return self.ctx.many_stats(TR.entry_of(self, force, 'many', 'many_stats').many['id'])
 
     def gayberne_stats(self, force):
         """dict(active, scanned, survivors, launches, chunks) of a GayBerneForce of this Context (backend.HipContext.gayberne_stats)."""
-        hits = [e for e in self.entries if e.force is force and getattr(e, 'gayberne', None) is not None]
-        if not hits:
-            raise mm.OpenMMException('gayberne_stats: the force does not belong to this Context')
-        return self.ctx.gayberne_stats(hits[0].gayberne)
-
-    def _translate_drude(self, force, entry):
-        """A DrudeForce: its rows (drude_tables) go to the Drude kernels (csrc/drude.hip), which derive the spring constants and the
-        pair parameters.  One backend force carried in entry.term_ids, so every loop over an entry's forces reaches it and the
-        scheduler's fusion rules decline its group, as they do for a CMAP force.  It reads no Context parameter."""
-        cls = 'DrudeForce'
-        periodic = force.usesPeriodicBoundaryConditions()
-        if periodic and self.free_space:
-            raise InputError('%s uses periodic boundary conditions in a System in free space' % cls)
-        n = self.n
-        constrained = {int(c[k]) for c in self.system._constraints for k in (0, 1)}
-        tab = drude_tables(force, n, constrained)
-        try:
-            fid = self.ctx.drude_create(tab['idx'], tab['par'], tab['pairs'], tab['thole'], periodic=periodic)
-        except B.HipError as exc:
-            raise InputError('%s: %s' % (cls, exc))
-        entry.term_ids.append(fid)
-        entry.drude = fid
-
-        def reload():          # updateParametersInContext: charges, polarizabilities, anisotropies and Thole factors are read again
-            new = drude_tables(force, n, constrained)
-            for key, what in (('idx', 'a particle of a Drude particle'), ('pairs', 'a Drude particle of a screened pair')):
-                if not np.array_equal(new[key], tab[key]):
-                    raise mm.OpenMMException('updateParametersInContext: %s has changed' % what)
-            self.ctx.drude_set_params(fid, new['idx'], new['par'], new['pairs'], new['thole'])
-            return 'values'
-        entry.reload = reload
-
-    def _translate_gb(self, force, entry):
-        """A GBSAOBCForce: one backend force (csrc/gb.hip) carried in entry.term_ids, so every loop over an entry's forces reaches it
-        and the scheduler's fusion rules decline its group, as they do for a term-expression force."""
-        def arrays():
-            if force.getNumParticles() != self.n:
-                raise mm.OpenMMException('GBSAOBCForce must have exactly as many particles as the System it belongs to')
-            par = np.array(force._particles, dtype=np.float64).reshape(-1, 3)
-            if force.usesPeriodicBoundaryConditions():
-                raise InputError('GBSAOBCForce: CutoffPeriodic is not supported: generalized-Born solvent runs in free space only')
-            rc = force._cutoff if force.getNonbondedMethod() == force.CutoffNonPeriodic else 0.0
-            return (par[:, 0], par[:, 1], par[:, 2]), dict(eps_in=force.getSoluteDielectric(), eps_out=force.getSolventDielectric(),
-                                                            sa_energy=force._sa_energy, rc=rc)
-        try:
-            per_atom, scalars = arrays()
-            gid = self.ctx.gb_create(*per_atom, **scalars)
-        except B.HipError as exc:
-            raise InputError('GBSAOBCForce: %s' % exc)
-        entry.term_ids.append(gid)
-        entry.gb = gid
-
-        def reload():          # updateParametersInContext: everything is read again
-            per_atom, scalars = arrays()
-            try:
-                self.ctx.gb_set_params(gid, *per_atom, **scalars)
-            except B.HipError as exc:
-                raise InputError('GBSAOBCForce: %s' % exc)
-            return 'values'
-        entry.reload = reload
+        return self.ctx.gayberne_stats(TR.entry_of(self, force, 'gayberne', 'gayberne_stats').gayberne)
 
     # ------------------------------------------------------------------------------- constant pressure
     def _init_barostat(self):
@@ -1332,1198 +528,15 @@ class Engine:
                 self._baro_scale = min(self._baro_scale * 1.1, 0.3 * float(np.prod(self.box)))
                 self._baro_window = [0, 0]
 
-    # ------------------------------------------------------------------------------- translation
-    def _register_globals(self, force):
-        if hasattr(force, 'getNumGlobalParameters'):
-            for i in range(force.getNumGlobalParameters()):
-                self.parameters.setdefault(force.getGlobalParameterName(i), force.getGlobalParameterDefaultValue(i))
-
-    def _translate(self, force):
-        self._register_globals(force)
-        if isinstance(force, mm.CMMotionRemover):
-            return
-        if isinstance(force, mm.MonteCarloBarostat):
-            if self.free_space:
-                raise InputError('a MonteCarloBarostat needs a periodic box: a System in free space (NoCutoff / CutoffNonPeriodic) has '
-                                 'no volume to change')
-            if self.barostat is not None:
-                raise InputError('a System holds one MonteCarloBarostat at most')
-            self.barostat = force       # no energy of its own: it drives Engine.step (_barostat_attempt)
-            self.parameters[force.Pressure()] = force.getDefaultPressure()._value
-            self.parameters[force.Temperature()] = force.getDefaultTemperature()._value
-            return
-        entry = _Entry(force, force.getForceGroup())
-        if isinstance(force, mm.NonbondedForce):
-            self._translate_nonbonded(force, entry)
-        elif isinstance(force, mm.CustomNonbondedForce):
-            self._translate_custom_nonbonded(force, entry)
-        elif isinstance(force, mm.CustomCVForce):
-            self._translate_cv(force, entry)
-        elif isinstance(force, mm.GBSAOBCForce):
-            self._translate_gb(force, entry)
-        elif isinstance(force, mm.CustomGBForce):
-            self._translate_custom_gb(force, entry)
-        elif isinstance(force, mm.CustomHbondForce):
-            self._translate_hbond(force, entry)
-        elif isinstance(force, mm.CustomManyParticleForce):
-            self._translate_many_particle(force, entry)
-        elif isinstance(force, mm.GayBerneForce):
-            self._translate_gayberne(force, entry)
-        elif isinstance(force, mm.DrudeForce):
-            self._translate_drude(force, entry)
-        elif isinstance(force, mm.CMAPTorsionForce):
-            self._translate_cmap(force, entry)
-        elif isinstance(force, mm.RBTorsionForce):
-            self._translate_rb(force, entry)
-        elif self._translate_bond_list_force(force, entry):
-            pass
-        else:
-            raise InputError('force type {} is not supported by the HIP path'.format(force.__class__.__name__))
-        self._finish_entry(entry)
-        self.entries.append(entry)
-
-    def _translate_bond_list_force(self, force, entry):
-        """The classes whose terms are lists of atoms -- bonds, angles, torsions, external terms: bond-list terms of the hand-written
-        kinds, or a term-expression force for any other text.  False: `force` is none of them.  (Also the inner forces of a
-        CustomCVForce: _translate_cv_general.)"""
-        if isinstance(force, mm.CustomBondForce):
-            self._translate_custom_bond(force, entry)
-        elif isinstance(force, mm.HarmonicBondForce):
-            b = np.array([[r[0], r[1]] for r in force._bonds], dtype=np.int32).reshape(-1, 2)
-            p = np.array([[r[2], r[3]] for r in force._bonds], dtype=np.float64).reshape(-1, 2)
-            entry.terms.append((B.BOND_HARMONIC, b, p, force.usesPeriodicBoundaryConditions(), None))
-        elif isinstance(force, mm.HarmonicAngleForce):
-            a = np.array([r[:3] for r in force._angles], dtype=np.int32).reshape(-1, 3)
-            p = np.array([r[3:] for r in force._angles], dtype=np.float64).reshape(-1, 2)
-            entry.terms.append((B.ANGLE_HARMONIC, a, p, force.usesPeriodicBoundaryConditions(), None))
-        elif isinstance(force, mm.CustomAngleForce):
-            if force.getEnergyFunction().replace(' ', '') != '0.5*(K0*(theta-t0)^2-Kn*(theta-tn)^2)':
-                self._translate_term_expression(force, entry)
-            else:
-                # difference of two harmonic angles (RESPASystem.redefine_angle, systems.py:226)
-                a = np.array([r[:3] for r in force._angles], dtype=np.int32).reshape(-1, 3)
-                p = np.array([r[3] for r in force._angles], dtype=np.float64).reshape(-1, 4)
-                periodic = force.usesPeriodicBoundaryConditions()
-                entry.terms.append((B.ANGLE_HARMONIC, a, p[:, [0, 1]], periodic, None))
-                entry.terms.append((B.ANGLE_HARMONIC, a, np.stack([p[:, 2], -p[:, 3]], axis=1), periodic, None))
-        elif isinstance(force, (mm.CustomTorsionForce, mm.CustomExternalForce)):
-            self._translate_term_expression(force, entry)
-        elif isinstance(force, mm.PeriodicTorsionForce):
-            t = np.array([r[:4] for r in force._torsions], dtype=np.int32).reshape(-1, 4)
-            p = np.array([[r[4], r[5], r[6]] for r in force._torsions], dtype=np.float64).reshape(-1, 3)
-            entry.terms.append((B.TORSION_PERIODIC, t, p, force.usesPeriodicBoundaryConditions(), None))
-        elif isinstance(force, (mm.CustomCompoundBondForce, mm.CustomCentroidBondForce)):
-            self._translate_compound(force, entry)
-        elif isinstance(force, mm.RMSDForce):
-            self._translate_rmsd(force, entry)
-        else:
-            return False
-        return True
-
-    def _translate_rmsd(self, force, entry):
-        """An RMSDForce: the selected particles and the reference rows of those particles go to the RMSD kernels (csrc/rmsd.hip), which
-        centre the reference, fit and differentiate.  One backend force carried in entry.term_ids, so every loop over an entry's forces
-        reaches it and the scheduler's fusion rules decline its group, as they do for a term-expression force.  (Also an inner force
-        of a CustomCVForce: _translate_cv_general.)  It reads no parameter: deriv(energy, p) sees no dependence through it."""
-        cls = 'RMSDForce'
-        if self.world > 1:
-            raise NotImplementedError('%s runs on a single rank' % cls)
-        n = self.n
-
-        def tables():
-            reference = np.array(force._reference, dtype=np.float64).reshape(-1, 3)
-            if len(reference) != n:
-                raise mm.OpenMMException('%s: %d reference positions, the System has %d particles' % (cls, len(reference), n))
-            particles = force.getParticles() or list(range(n))
-            if min(particles) < 0 or max(particles) >= n:
-                raise mm.OpenMMException('%s: a particle index is out of range' % cls)
-            if len(set(particles)) != len(particles):
-                raise mm.OpenMMException('%s: a particle is listed twice' % cls)
-            if not np.isfinite(reference).all():
-                raise mm.OpenMMException('%s: a reference position is not finite' % cls)
-            particles = np.array(particles, dtype=np.int32)
-            return particles, np.ascontiguousarray(reference[particles])
-
-        fid = self.ctx.rmsd_create(*tables())
-        entry.term_ids.append(fid)
-        entry.rmsd = fid
-
-        def reload():          # updateParametersInContext: the reference and the particle list are read again
-            self.ctx.rmsd_set_reference(fid, *tables())
-            return 'values'
-        entry.reload = reload
-
-    def _pair_create(self, desc, q, sigma, eps, excl):
-        if self.free_space:
-            # all pairs at the distance the positions give (csrc/free.hip): no list to build, to share or to count
-            desc.flags |= B.FREE_SPACE
-            return self.ctx.pair_create(desc, q, sigma, eps, excl, skin=self.skin)
-        pid = self.ctx.pair_create(desc, q, sigma, eps, excl, skin=self.skin)
-        key = np.sort(np.sort(np.asarray(excl, dtype=np.int64).reshape(-1, 2), axis=1), axis=0).tobytes()
-        # interaction-group forces keep a list of their own: it holds the (set 1, set 2) pairs only
-        if desc.family == B.SOFTCORE or desc.flags & (B.GROUP_LJ | B.GROUP_Q):
-            key = ('group', pid)
-        # a force guarded by step(rc0 - r) reaches rc0 only (the discount of FarNonbondedForce): it can then walk the front part
-        # of the total force's rows, and be evaluated on the total's pass
-        reach = min(float(desc.rc), float(desc.rc0)) if (desc.flags & B.GUARD_RC0 and desc.rc0 > 0) else float(desc.rc)
-        self._pair_info[pid] = (reach, key)
-        return pid
-
-    def _share_lists(self):
-        """RESPASystem leaves a short-ranged copy (group 1, and its negative in group 31) and the full force over the
-        same particles and exclusions: the shorter-ranged ones traverse the front part of the longest-ranged force's
-        neighbour rows instead of building lists of their own (amm_pair_share_list)."""
-        by_key = {}
-        for pid, (rc, key) in self._pair_info.items():
-            by_key.setdefault(key, []).append((rc, pid))
-        self.shared = {}
-        for members in by_key.values():
-            members.sort(reverse=True)
-            host_rc, host = members[0]
-            for rc, pid in members[1:]:
-                if rc < host_rc:
-                    try:
-                        self.ctx.pair_share_list(pid, host)
-                        self.shared[pid] = host
-                    except B.HipError:
-                        pass          # incompatible radius with an earlier guest: keeps its own list
-
-    def _finish_entry(self, entry):
-        if entry.terms:
-            entry.bonded_id = self._make_bonded(entry.terms, sliced=False)
-
-    def _replace_bonded(self, entry, terms):
-        """New bond-list set of a force whose terms changed; the set it replaces is freed (amm_bonded_release)."""
-        old = entry.bonded_id
-        entry.bonded_id = self._make_bonded(terms, sliced=False) if terms else None
-        if old is not None:
-            self.ctx.bonded_release(old)
-
-    def _forget_groups(self):
-        """Group definitions are stale (bond-list terms were rebuilt): drop them and free the merged sets they owned."""
-        for bid in self._group_bonded:
-            self.ctx.bonded_release(bid)
-        del self._group_bonded[:]
-        self._group_defs.clear()
-
-    def _make_bonded(self, terms, sliced):
-        bid = self.ctx.bonded_create()
-        for kind, idx, par, periodic, desc in terms:
-            if len(idx):
-                self.ctx.bonded_add_terms(bid, kind, idx, par, periodic=periodic, desc=desc)
-        self.ctx.bonded_finalize(bid, sliced=sliced)
-        return bid
-
-    @staticmethod
-    def _effective(base, scales, names, parameters):
-        """base (n,3) + sum_p lambda_p * scales[p] (n,3): parameter offsets (forces.py:247-258)."""
-        out = base.copy()
-        for k, name in enumerate(names):
-            out += parameters[name] * scales[k]
-        return out
-
-    def _translate_nonbonded(self, nb, entry):
-        method = nb.getNonbondedMethod()
-        if method not in (nb.NoCutoff, nb.CutoffNonPeriodic, nb.CutoffPeriodic, nb.Ewald, nb.PME):
-            raise InputError('the HIP path evaluates NonbondedForces with NoCutoff, CutoffNonPeriodic, CutoffPeriodic, Ewald or PME')
-        periodic = not self.free_space
-        # NoCutoff: all non-excepted pairs, 4 eps ((sigma/r)^12 - (sigma/r)^6) + Kc qq / r -- no switch, no reaction field (rc = 0)
-        no_cutoff = method == nb.NoCutoff
-        rc = 0.0 if no_cutoff else nb._cutoff
-        n = self.n
-        base = np.array(nb._particles, dtype=np.float64).reshape(n, 3)
-        names = []
-        for rec in nb._particle_offsets:
-            if rec[0] not in names:
-                names.append(rec[0])
-        scales = np.zeros((len(names), n, 3))
-        for name, idx, qs, ss, es in nb._particle_offsets:
-            scales[names.index(name), idx] = [qs, ss, es]
-        exc = np.array([[r[0], r[1]] for r in nb._exceptions], dtype=np.int32).reshape(-1, 2)
-        exc_base = np.array([r[2:] for r in nb._exceptions], dtype=np.float64).reshape(-1, 3)
-        enames = []
-        for rec in nb._exception_offsets:
-            if rec[0] not in enames:
-                enames.append(rec[0])
-        escales = np.zeros((len(enames), len(exc), 3))
-        for name, idx, qs, ss, es in nb._exception_offsets:
-            escales[enames.index(name), idx] = [qs, ss, es]
-        use_switch = nb._use_switch and not no_cutoff
-        flags = B.SWITCH if use_switch else 0
-        alpha = krf = crf = 0.0
-        ewald = method in (nb.Ewald, nb.PME)
-        if no_cutoff:
-            pass
-        elif ewald:
-            alpha = nb._pme[0] if nb._pme[0] > 0 else math.sqrt(-math.log(2 * nb._ewald_tol)) / rc
-            flags |= B.COULOMB_EWALD
-        else:
-            eps_rf = nb._rf_dielectric
-            krf = (eps_rf - 1) / ((2 * eps_rf + 1) * rc ** 3)
-            crf = 3 * eps_rf / ((2 * eps_rf + 1) * rc)
-            flags |= B.COULOMB_RF
-        desc = B.pair_desc(B.NONBONDED, rc, rswitch=nb._switch if use_switch else 0.0, alpha=alpha, flags=flags,
-                           krf=krf, crf=crf)
-        eff = self._effective(base, scales, names, self.parameters)
-        pid = self._pair_create(desc, eff[:, 0], eff[:, 1], eff[:, 2], exc)
-        entry.pair_ids.append(pid)
-        entry.alpha = alpha
-        entry.ewald = ewald
-        if ewald:
-            entry.recip_group = nb._recip_group if nb._recip_group >= 0 else nb.getForceGroup()
-            # PME mesh: explicit setPMEParameters, else OpenMM's rule ceil(2 alpha L / (3 tol^(1/5))) [recalled];
-            # nonbondedMethod Ewald is evaluated on the same mesh (smooth PME stands in for the explicit k-sum)
-            if nb._pme[0] > 0 and min(nb._pme[1:]) > 0:
-                grid = [int(k) for k in nb._pme[1:]]
-            else:
-                grid = [max(6, int(math.ceil(2 * alpha * L / (3 * nb._ewald_tol ** 0.2)))) for L in self.box]
-            entry.recip = self.ctx.pme_create(alpha, grid, eff[:, 0])
-            entry.recip_grid = grid
-
-        def bonded_terms(parameters):
-            q = self._effective(base, scales, names, parameters)[:, 0]
-            terms = []
-            ep = self._effective(exc_base, escales, enames, parameters) if len(exc) else exc_base
-            keep = (ep[:, 0] != 0.0) | (ep[:, 2] != 0.0) if len(exc) else np.zeros(0, bool)
-            if keep.any():
-                terms.append((B.BOND_LJC, exc[keep], ep[keep], periodic, B.pair_desc(B.NONBONDED, rc)))
-            if ewald and len(exc):
-                terms.append((B.BOND_EWALD_EXCL, exc, (q[exc[:, 0]] * q[exc[:, 1]]).reshape(-1, 1), periodic,
-                              B.pair_desc(B.NONBONDED, rc, alpha=alpha)))
-            return terms
-
-        defaults = {nb.getGlobalParameterName(i): nb.getGlobalParameterDefaultValue(i)
-                    for i in range(nb.getNumGlobalParameters())}
-
-        def constant(parameters):
-            # OpenMM evaluates the dispersion coefficient with the global parameters at their DEFAULT values and keeps
-            # it when Context.setParameter changes them -- pinned by tests/test_systems.py:54 and :121 (sigma/epsilon
-            # offsets at lambda_vdw = 0.5: the literals are met to 2e-7 kJ/mol only this way)
-            if not nb._dispersion or self.free_space:       # (no volume: no dispersion correction in free space)
-                return 0.0
-            p = self._effective(base, scales, names, defaults)
-            return self._vscale * dispersion_correction(p[:, 1], p[:, 2], self._box_ref, rc, nb._switch if nb._use_switch else None)
-
-        entry.terms = bonded_terms(self.parameters)
-        entry.constant = constant(self.parameters)
-        entry.rescale = lambda: setattr(entry, 'constant', constant(self.parameters))
-        lam = set(names) | set(enames)
-
-        def update(parameters, changed, force=False):
-            if not (lam & changed) and not force:
-                return False
-            p = self._effective(base, scales, names, parameters)
-            self.ctx.pair_set_params(pid, p[:, 0], p[:, 1], p[:, 2])
-            if entry.recip is not None:
-                self.ctx.pme_set_charges(entry.recip, p[:, 0])
-            entry.terms = bonded_terms(parameters)
-            self._replace_bonded(entry, entry.terms)
-            entry.constant = constant(parameters)
-            return True
-
-        def reload():
-            # NonbondedForce.updateParametersInContext: particle and exception parameters are read again (their number
-            # and the exception pairs must not have changed, as in OpenMM)
-            fresh = np.array(nb._particles, dtype=np.float64).reshape(n, 3)
-            fresh_exc = np.array([r[2:] for r in nb._exceptions], dtype=np.float64).reshape(-1, 3)
-            if fresh_exc.shape != exc_base.shape:
-                raise mm.OpenMMException('updateParametersInContext: the number of exceptions has changed')
-            base[:] = fresh
-            exc_base[:] = fresh_exc
-            return update(self.parameters, set(), force=True)
-
-        entry.reload = reload
-        if lam:
-            entry.update = update
-            entry.depends = set(lam)
-            # parameters whose offsets touch the charges only: the energy is a quadratic form of them
-            entry.quadratic_in = {nm for nm in lam
-                                  if not (nm in names and np.any(scales[names.index(nm)][:, 1:]))
-                                  and not (nm in enames and np.any(escales[enames.index(nm)][:, 1:]))}
-
-    def _descriptor_of(self, force):
-        desc = getattr(force, '_amm', None)
-        if desc is None:
-            globs = {force.getGlobalParameterName(i): force.getGlobalParameterDefaultValue(i)
-                     for i in range(force.getNumGlobalParameters())}
-            desc = describe_energy(force.getEnergyFunction(), globs)
-        if desc is None:
-            raise InputError('energy expression not recognised by the HIP path (supported: the AtomsMM near / '
-                             'damped-smoothed / exception families): ' + force.getEnergyFunction().split(';')[0])
-        return desc
-
-    def _pair_desc_from(self, d, rc, builtin_switch=None):
-        family = d['family']
-        flags = B.GUARD_RC0 if d.get('guard') else 0
-        if family == 'damped':
-            degree = int(d.get('degree', 1))
-            rswitch = builtin_switch if (degree == 1 and builtin_switch is not None) else d['rswitch']
-            return B.pair_desc(B.DAMPED, rc, rswitch=rswitch, alpha=d['alpha'], degree=degree, sign=d.get('sign', 1.0),
-                               Kc=d.get('Kc', B.KC))
-        rc0, rs0 = d.get('rc0'), d.get('rs0')
-        if rc0 is None or rs0 is None:
-            raise InputError('near force without rc0/rs0')
-        if d.get('noshift'):
-            flags |= B.NO_SHIFT
-        return B.pair_desc(_FAMILY[family], rc, rc0=rc0, rs0=rs0, flags=flags, sign=d.get('sign', 1.0), Kc=d.get('Kc', B.KC))
-
-    @staticmethod
-    def check_pair_symmetry(text, per_particle_names, global_values, samples=6, seed=20240607, tabulated=None):
-        """A pair is evaluated from both atoms' rows and counted once (csrc/pair_expr.hip), so the text must not change when the
-        particles swap: evaluate it on the host at a handful of seeded random (r, parameters of 1, parameters of 2) and at the
-        swapped parameters.  OpenMM leaves an asymmetric text undefined (which atom is 1 depends on its neighbour list).
-        tabulated: (name -> callable, the force's particle rows [n][parameters]) of a force with tabulated functions -- the sample
-        parameters are then rows the force HAS (a uniform draw is no type index): every pair of distinct rows when they are few
-        (an asymmetric A(type1, type2) shows at the one pair of types it concerns), seeded draws of pairs otherwise."""
-        rng = np.random.default_rng(seed)
-        if tabulated is None:
-            functions, draws = None, [None] * samples
-        else:
-            functions, rows = tabulated
-            if not per_particle_names:
-                return                 # (nothing to swap)
-            rows = np.unique(np.asarray(rows, dtype=np.float64).reshape(-1, len(per_particle_names)), axis=0)
-            if len(rows) <= 24:
-                draws = [(rows[i], rows[j]) for i in range(len(rows)) for j in range(i + 1, len(rows))]
-            else:
-                draws = [(rows[i], rows[j]) for i, j in rng.integers(0, len(rows), size=(16 * samples, 2)) if i != j]
-        for draw in draws:
-            r = float(rng.uniform(0.3, 1.2))
-            if draw is None:
-                one = {nm: float(rng.uniform(0.2, 1.5)) for nm in per_particle_names}
-                two = {nm: float(rng.uniform(0.2, 1.5)) for nm in per_particle_names}
-            else:
-                one, two = (dict(zip(per_particle_names, map(float, row))) for row in draw)
-            env = dict(global_values, r=r)
-            fwd = dict(env, **{nm + '1': one[nm] for nm in per_particle_names}, **{nm + '2': two[nm] for nm in per_particle_names})
-            swp = dict(env, **{nm + '1': two[nm] for nm in per_particle_names}, **{nm + '2': one[nm] for nm in per_particle_names})
-            try:
-                if functions is None:
-                    a, b = X.eval_global(text, fwd), X.eval_global(text, swp)
-                else:
-                    a, b = X.eval_global(text, fwd, functions=functions), X.eval_global(text, swp, functions=functions)
-                    if a != a and b != b:
-                        continue       # (an index outside its table both ways: NaN on the device too, nothing about symmetry)
-            except (ArithmeticError, ValueError) as exc:
-                if isinstance(exc, X.ExpressionError):
-                    raise
-                continue               # (outside the text's domain at this draw: says nothing about symmetry)
-            if not abs(a - b) <= 1e-12 * max(abs(a), abs(b), 1e-300):      # (a few roundings of operations taken in another order)
-                raise InputError('energy expression is not symmetric in particles 1 and 2')
-
-    def _translate_pair_expression(self, force, entry):
-        """A CustomNonbondedForce whose energy text is none of the AtomsMM families: compiled here (expr.compile_pair) and interpreted
-        per pair, with its derivative in r, by the pair-expression kernel (csrc/pair_expr.hip) on per-atom neighbour rows."""
-        text = force.getEnergyFunction()
-        # (what the generic kernel leaves out is said together with why the force came here)
-        generic = 'energy expression not recognised as one of the AtomsMM families (%s); the generic pair-expression kernel ' % text.split(';')[0]
-        if getattr(force, '_derivs', None):
-            raise NotImplementedError(generic + 'differentiates in r only: no addEnergyParameterDerivative')
-        if self.free_space or force.getNonbondedMethod() != force.CutoffPeriodic:
-            raise NotImplementedError(generic + 'evaluates with CutoffPeriodic only (not NoCutoff / CutoffNonPeriodic)')
-        if self.world > 1:
-            raise NotImplementedError(generic + 'runs on a single rank')
-        if force.getNumInteractionGroups() > 0:
-            raise NotImplementedError(generic + 'takes no interaction groups')
-        if force.getUseLongRangeCorrection():
-            raise NotImplementedError(generic + 'computes no long-range correction')
-        names = [force.getPerParticleParameterName(k) for k in range(force.getNumPerParticleParameters())]
-        if len(names) > X.PAIR_MAX_PARAMS:
-            raise InputError(generic + 'takes at most %d per-particle parameters (%d given): a neighbour row carries three doubles '
-                             'per atom' % (X.PAIR_MAX_PARAMS, len(names)))
-        gnames = [force.getGlobalParameterName(k) for k in range(force.getNumGlobalParameters())]
-        # addTabulatedFunction: (name, function) in the force's order -- the order of the table indices in the program
-        functions = list(getattr(force, '_functions', []))
-        try:
-            prog = X.compile_pair(text, names, gnames, T.declared(functions)) if functions else X.compile_pair(text, names, gnames)
-        except X.ExpressionError as exc:
-            raise InputError('energy expression not recognised by the HIP path as one of the AtomsMM families, and not a pair '
-                             'expression the generic kernel can run: %s' % exc)
-        uses_tables = bool(X.table_words(prog.code))
-        if not uses_tables:
-            self.check_pair_symmetry(text, names, {g: self.parameters[g] for g in prog.globals_})
-        n = self.n
-        if force.getNumParticles() != n:
-            raise mm.OpenMMException('CustomNonbondedForce must have exactly as many particles as the System')
-        direct = T.direct_index_uses(text, functions) if uses_tables else []
-
-        def slots():
-            allp = np.array(force._particles, dtype=np.float64).reshape(n, -1)
-            if allp.shape[1] != len(names):
-                raise mm.OpenMMException('CustomNonbondedForce: every particle needs %d parameters' % len(names))
-            # a per-particle value passed straight into a discrete function is an index: a whole number inside the table
-            for symbol, fname, size in direct:
-                if symbol[:-1] in names and symbol[-1] in '12':
-                    column = allp[:, names.index(symbol[:-1])]
-                    bad = np.nonzero(~((column == np.rint(column)) & (column >= 0) & (column < size)))[0]
-                    if len(bad):
-                        raise mm.OpenMMException('CustomNonbondedForce: particle %d has %s = %r, passed to the tabulated function %s as an '
-                                                 'index: it must be a whole number in 0 .. %d' %
-                                                 (bad[0], symbol[:-1], float(column[bad[0]]), fname, size - 1))
-            return [np.ascontiguousarray(allp[:, k]) if k < len(names) else np.zeros(n) for k in range(3)]
-
-        def tables_checked():
-            """What amm_pair_expr_set_tables takes, after the checks the host can make: the particles' indices lie in their tables,
-            and the text is symmetric over the rows the force has."""
-            rows = np.stack(slots()[:len(names)], axis=1) if names else np.zeros((n, 0))
-            self.check_pair_symmetry(text, names, {g: self.parameters[g] for g in prog.globals_},
-                                     tabulated=({name: T.host_callable(fn) for name, fn in functions}, rows))
-            return [T.device_table(fn) for _, fn in functions]
-
-        tables = tables_checked() if uses_tables else None
-        rc = force._cutoff
-        use_switch = force.getUseSwitchingFunction()
-        if use_switch and not (0.0 <= force._switch < rc):
-            raise mm.OpenMMException('CustomNonbondedForce: the switching distance must lie between 0 and the cutoff')
-        desc = B.pair_desc(B.PAIR_EXPR, rc, rswitch=force._switch if use_switch else 0.0, flags=B.SWITCH if use_switch else 0)
-        excl = np.array(force._exclusions, dtype=np.int32).reshape(-1, 2)
-        pid = self.ctx.pair_expr_create(desc, prog.code, prog.consts, [self.parameters[g] for g in prog.globals_], *slots(), excl,
-                                        skin=self.skin)
-        self._pair_info[pid] = (float(rc), ('expr', pid))       # (a list of its own: never host or guest of a shared one)
-        entry.pair_ids.append(pid)
-        entry.pair_expr = True
-        entry.program = prog
-        if uses_tables:
-            self.ctx.pair_expr_set_tables(pid, tables)
-
-        def reload():          # updateParametersInContext: the per-particle parameters (and the tabulated functions) are read again
-            fresh = slots()
-            if uses_tables:
-                self.ctx.pair_expr_set_tables(pid, tables_checked())
-            self.ctx.pair_set_params(pid, *fresh)
-            return 'values'
-        entry.reload = reload
-        if prog.globals_:
-            depends = set(prog.globals_)
-
-            def update(parameters, changed):
-                if not (depends & changed):
-                    return False
-                self.ctx.pair_expr_set_globals(pid, [parameters[g] for g in prog.globals_])
-                return 'values'
-            entry.update = update
-            entry.depends = depends
-
-    def _translate_custom_nonbonded(self, force, entry):
-        if getattr(force, '_amm', None) is None:
-            globs = {force.getGlobalParameterName(i): force.getGlobalParameterDefaultValue(i)
-                     for i in range(force.getNumGlobalParameters())}
-            if describe_energy(force.getEnergyFunction(), globs) is None:
-                return self._translate_pair_expression(force, entry)
-        d = dict(self._descriptor_of(force))
-        if d['family'] == 'ljc':
-            raise InputError('the LJC exception expression belongs in a CustomBondForce')
-        if self.free_space:
-            if force.getNonbondedMethod() == force.NoCutoff:
-                raise InputError('only a NonbondedForce runs without a cutoff (NoCutoff): the near and damped-smoothed energy texts of '
-                                 'a CustomNonbondedForce are not defined beyond their cutoff -- use CutoffNonPeriodic')
-            if d['family'] in ('softcore', 'lj-virial') or force.getNumInteractionGroups() > 0 or d['family'] == 'lj' \
-                    or d.get('noshift') or d.get('scale_name') or d.get('scale_text'):
-                raise NotImplementedError('softcore forces, interaction groups, lj-virial and the alchemical pair forces are not '
-                                          'evaluated under a non-periodic nonbonded method (free space)')
-        elif force.getNonbondedMethod() != force.CutoffPeriodic:
-            raise InputError('the HIP path evaluates CutoffPeriodic CustomNonbondedForces only')
-        if d['family'] == 'softcore':
-            return self._translate_softcore(force, entry, d)
-        if d['family'] == 'lj-virial':
-            return self._translate_lj_virial(force, entry)
-        if d['family'] == 'lj' or d.get('noshift') or d.get('scale_name') or d.get('scale_text') or force.getNumInteractionGroups() > 0:
-            return self._translate_alchemical_pair(force, entry, d)
-        if force.getNumInteractionGroups() > 0:
-            raise NotImplementedError('interaction groups are supported for the softcore solute-solvent force only')
-        if force.getUseLongRangeCorrection():
-            raise NotImplementedError('long-range correction is supported for the softcore solute-solvent force only')
-        rc = force._cutoff
-        for key in ('rc0', 'rs0', 'alpha', 'rswitch', 'Kc'):
-            if d.get(key) is None and key in self.parameters:
-                d[key] = self.parameters[key]
-        builtin = force._switch if force.getUseSwitchingFunction() else None
-        if builtin is not None and d['family'] != 'damped':
-            raise NotImplementedError('built-in switching function on a near force')
-        desc = self._pair_desc_from(d, rc, builtin)
-        n = self.n
-        if force.getNumParticles() != n:
-            raise mm.OpenMMException('CustomNonbondedForce must have exactly as many particles as the System')
-        allp = np.array(force._particles, dtype=np.float64).reshape(n, -1)
-        names = list(getattr(force, '_offset_parameters', []))
-        base = allp[:, :3]
-        scales = np.stack([allp[:, 3 * (k + 1):3 * (k + 2)] for k in range(len(names))]) if names else np.zeros((0, n, 3))
-        eff = self._effective(base, scales, names, self.parameters)
-        excl = np.array(force._exclusions, dtype=np.int32).reshape(-1, 2)
-        pid = self._pair_create(desc, eff[:, 0], eff[:, 1], eff[:, 2], excl)
-        entry.pair_ids.append(pid)
-        if names:
-            lam = set(names)
-
-            def update(parameters, changed):
-                if not (lam & changed):
-                    return False
-                p = self._effective(base, scales, names, parameters)
-                self.ctx.pair_set_params(pid, p[:, 0], p[:, 1], p[:, 2])
-                return True
-            entry.update = update
-            entry.depends = set(lam)
-            # offsets that touch the charges only: the energy is a quadratic in them (energies_at_states interpolates; energy_derivative
-            # keeps its small central step for this force)
-            entry.charge_offsets_in = {nm for k, nm in enumerate(names) if not np.any(scales[k][:, 1:])}
-
-    def _translate_alchemical_pair(self, force, entry, d, outer=None, outer_depends=()):
-        """Pair forces of AlchemicalRespaSystem (systems.py:628-772): force-switched potentials without the constant
-        shift, plain Lennard-Jones, optionally restricted to the (solute, solvent) interaction group, optionally
-        multiplied by a global parameter (`respa_switch`) and -- as the collective variable of a CustomCVForce -- by
-        `outer(parameters)`, the coupling function."""
-        n = self.n
-        if getattr(force, '_offset_parameters', []):
-            raise NotImplementedError('alchemical pair force with parameter offsets')
-        if self.free_space:
-            raise NotImplementedError('alchemical pair forces (interaction groups, coupling factors) are not evaluated under a '
-                                      'non-periodic nonbonded method (free space)')
-        if force.getNonbondedMethod() != force.CutoffPeriodic:
-            raise InputError('the HIP path evaluates CutoffPeriodic CustomNonbondedForces only')
-        p = np.array(force._particles, dtype=np.float64).reshape(n, -1)
-        if p.shape[1] == 2:                            # per-particle (sigma, epsilon) only: AlchemicalSystem (systems.py:378-379)
-            p = np.concatenate([np.zeros((n, 1)), p], axis=1)
-        p = p[:, :3]
-        q = p[:, 0].copy()
-        ngroups = force.getNumInteractionGroups()
-        flags, Kc = 0, d.get('Kc', B.KC)
-        codes = None
-        if ngroups > 1:
-            raise NotImplementedError('more than one interaction group')
-        sigma, eps = p[:, 1], p[:, 2]
-        if ngroups == 1:
-            if not (d['family'] == 'lj' or d.get('lj_only') or d.get('coulomb_only')):
-                raise NotImplementedError('interaction groups on a force with both electrostatics and Lennard-Jones')
-            set1, set2 = force._groups[0]
-            if set1 & set2:
-                raise NotImplementedError('overlapping interaction-group sets')
-            codes = np.zeros(n)
-            codes[sorted(set1)] = 1.0
-            codes[sorted(set2)] = 2.0
-            if d.get('coulomb_only'):      # the expression has no sigma / epsilon: the sigma slot selects the pairs
-                sigma, eps = 2.0 * codes, np.zeros(n)
-                flags |= B.GROUP_Q
-            else:
-                q, Kc = codes, 1.0
-                flags |= B.GROUP_LJ
-        elif d['family'] == 'lj' or d.get('lj_only'):
-            q = np.zeros(n)
-        rc = force._cutoff
-        rswitch = force._switch if force.getUseSwitchingFunction() else None
-        scale_name = d.get('scale_name')
-        scale_text = d.get('scale_text')
-        scale_symbols = X.symbols(scale_text) if scale_text else set()
-        for name in scale_symbols:
-            if name not in self.parameters:          # e.g. the reference's `linear` coupling leaves two_pi undefined
-                raise mm.OpenMMException('Unknown variable in expression: ' + name)
-
-        def scale(parameters):
-            value = d.get('sign', 1.0)
-            if scale_name:
-                value *= parameters[scale_name]
-            if scale_text:
-                value *= X.eval_global(scale_text, {k: parameters[k] for k in scale_symbols})
-            if outer is not None:
-                value *= outer(parameters)
-            return value
-
-        if d['family'] == 'lj':
-            if rswitch is not None:
-                flags |= B.SWITCH
-            desc = B.pair_desc(B.NONBONDED, rc, rswitch=rswitch or 0.0, flags=flags, sign=scale(self.parameters), Kc=Kc)
-        elif d['family'] == 'near-force-switch':
-            if rswitch is not None:
-                raise NotImplementedError('built-in switching function on a force-switched potential')
-            if d.get('noshift'):
-                flags |= B.NO_SHIFT
-            if d.get('guard'):
-                flags |= B.GUARD_RC0
-            desc = B.pair_desc(B.NEAR_FSWITCH, rc, rc0=d.get('rc0') or rc, rs0=d['rs0'], flags=flags,
-                               sign=scale(self.parameters), Kc=Kc)
-        else:
-            raise NotImplementedError('alchemical pair family ' + d['family'])
-        excl = np.array(force._exclusions, dtype=np.int32).reshape(-1, 2)
-        pid = self._pair_create(desc, q, sigma, eps, excl)
-        entry.pair_ids.append(pid)
-        if d.get('coulomb_only'):
-            def reload():          # updateParametersInContext: the charges may have changed (reset_coulomb_scaling_factor)
-                fresh = np.array(force._particles, dtype=np.float64).reshape(n, -1)[:, 0]
-                self.ctx.pair_set_params(pid, fresh, sigma, eps)
-                return 'values'
-            entry.reload = reload
-        lrc = 0.0
-        if force.getUseLongRangeCorrection():
-            if d['family'] != 'lj':
-                raise NotImplementedError('long-range correction of this CustomNonbondedForce')
-            lrc = custom_long_range_correction(lambda r, s_, e_: 4.0 * e_ * ((s_ / r) ** 12 - (s_ / r) ** 6), p[:, 1], p[:, 2],
-                                               self._box_ref, rc, rswitch, codes)
-        entry.constant = lrc * scale(self.parameters)
-        if lrc:
-            entry.rescale = lambda: setattr(entry, 'constant', self._vscale * lrc * scale(self.parameters))
-        depends = set(outer_depends) | ({scale_name} if scale_name else set()) | scale_symbols
-        if depends:
-            def update(parameters, changed):
-                if not (depends & changed):
-                    return False
-                self.ctx.pair_set_scale(pid, scale(parameters))
-                entry.constant = self._vscale * lrc * scale(parameters)
-                return 'values'
-            entry.update = update
-            entry.depends = set(depends)
-
-    def _translate_cv(self, force, entry):
-        """CustomCVForce of AlchemicalRespaSystem (systems.py:738-772): ((gt0-gt1)*S(lambda) + gt1) times ONE collective
-        variable, the energy of a CustomNonbondedForce -- i.e. that pair force with a lambda-dependent overall factor.  Any other
-        CustomCVForce takes the general path (_translate_cv_general)."""
-        if force.getNumCollectiveVariables() != 1 or not isinstance(force.getCollectiveVariable(0), mm.CustomNonbondedForce) or \
-                getattr(force, '_functions', None):
-            return self._translate_cv_general(force, entry)
-        name, inner = force.getCollectiveVariableName(0), force.getCollectiveVariable(0)
-        text = force.getEnergyFunction()
-        used = X.symbols(text) - {name}
-        self._register_globals(inner)
-
-        def outer(parameters):
-            env = {k: parameters[k] for k in used}
-            e1 = X.eval_global(text, dict(env, **{name: 1.0}))
-            e0 = X.eval_global(text, dict(env, **{name: 0.0}))
-            e2 = X.eval_global(text, dict(env, **{name: 2.0}))
-            if e0 != 0.0 or abs(e2 - 2.0 * e1) > 1e-12 * max(1.0, abs(e1)):
-                raise NotImplementedError('CustomCVForce energy is not proportional to its collective variable')
-            return e1
-        d = dict(self._descriptor_of(inner))
-        self._translate_alchemical_pair(inner, entry, d, outer=outer, outer_depends=used)
-
-    _CV_INNER_CLASSES = ('HarmonicBondForce', 'HarmonicAngleForce', 'PeriodicTorsionForce', 'CustomBondForce', 'CustomAngleForce',
-                         'CustomTorsionForce', 'CustomExternalForce', 'CustomCompoundBondForce', 'CustomCentroidBondForce', 'RMSDForce')
-
-    def _translate_cv_general(self, force, entry):
-        """CustomCVForce with any energy text over several collective variables, each the energy of a bond / angle / torsion / external
-        force: one backend object (csrc/cv.hip, AMM_FORCE_CV) that owns the compiled outer text (expr.compile_cv) and the ids of the
-        inner forces -- bond-list sets for the hand-written kinds, term-expression forces for any other text, members of no group.
-        Its id goes into entry.term_ids, so every loop over an entry's forces reaches it; entry.cv names it, its collective
-        variables and the parameters it differentiates in."""
-        cls = 'CustomCVForce'
-        n_cv = force.getNumCollectiveVariables()
-        if self.world > 1:
-            raise NotImplementedError('%s with a general energy expression (%d collective variables) runs on a single rank' % (cls, n_cv))
-        if getattr(force, '_functions', None):
-            raise NotImplementedError('%s: tabulated functions in the energy expression of collective variables are not supported' % cls)
-        if n_cv < 1:
-            raise InputError('%s without a collective variable' % cls)
-        text = force.getEnergyFunction()
-        names = [force.getCollectiveVariableName(k) for k in range(n_cv)]
-        gnames = [force.getGlobalParameterName(k) for k in range(force.getNumGlobalParameters())]
-        derivs = list(dict.fromkeys(getattr(force, '_derivs', ())))
-        for p in derivs:
-            if p not in gnames:
-                raise InputError('%s: addEnergyParameterDerivative(%r) names no global parameter of the force' % (cls, p))
-        inners = [force.getCollectiveVariable(k) for k in range(n_cv)]
-        for name, inner in zip(names, inners):
-            if not isinstance(inner, tuple(getattr(mm, c) for c in self._CV_INNER_CLASSES)):
-                raise NotImplementedError('%s over a %s (collective variable %s): outside the pattern of AlchemicalRespaSystem, a collective '
-                                          'variable is the energy of one of %s' % (cls, inner.__class__.__name__, name, ', '.join(self._CV_INNER_CLASSES)))
-            if hasattr(inner, 'getEnergyFunction'):
-                inner_globals = {inner.getGlobalParameterName(k) for k in range(inner.getNumGlobalParameters())}
-                shared = sorted(set(derivs) & inner_globals & X.symbols(inner.getEnergyFunction()))
-                if shared:
-                    raise NotImplementedError('%s: the derivative parameter %s is also read by the energy expression of collective variable %s; '
-                                              'parameter derivatives through inner forces are not supported' % (cls, shared[0], name))
-        try:
-            prog = X.compile_cv(text, names, derivs, gnames)
-        except X.ExpressionError as exc:
-            raise InputError('%s: not an energy expression the collective-variable kernel can run: %s' % (cls, exc))
-        subs, inner_ids = [], []
-        for name, inner in zip(names, inners):
-            self._register_globals(inner)
-            sub = _Entry(inner, entry.group)
-            self._translate_bond_list_force(inner, sub)
-            self._finish_entry(sub)
-            ids = ([sub.bonded_id] if sub.bonded_id is not None else []) + sub.term_ids
-            if not ids:          # (a force without terms: an empty bond-list set, energy 0)
-                sub.bonded_id = self._make_bonded([], sliced=False)
-                ids = [sub.bonded_id]
-            if sub.update is not None and not sub.term_expr:
-                raise NotImplementedError('%s: collective variable %s is a %s whose bond-list terms are rebuilt when a global parameter '
-                                          'changes' % (cls, name, inner.__class__.__name__))
-            subs.append(sub)
-            inner_ids.append(ids[0])
-        cid = self.ctx.cv_create(inner_ids, len(derivs), prog.code, prog.consts, [self.parameters[g] for g in prog.globals_])
-        if derivs:
-            self.ctx.cv_set_variables(cid, [self.parameters[p] for p in derivs])
-        entry.term_ids.append(cid)
-        entry.program = prog
-        entry.cv = dict(id=cid, names=names, derivs=derivs, inner=subs, inner_ids=inner_ids)
-        outer, seeded = set(prog.globals_), set(derivs)
-
-        def update(parameters, changed):
-            hit = False
-            if outer & changed:
-                self.ctx.cv_set_globals(cid, [parameters[g] for g in prog.globals_])
-                hit = True
-            if seeded & changed:
-                self.ctx.cv_set_variables(cid, [parameters[p] for p in derivs])
-                hit = True
-            for sub in subs:
-                if sub.update is not None and sub.update(parameters, changed):
-                    hit = True
-            return 'values' if hit else False
-        entry.update = update
-        entry.depends = outer | seeded | set().union(*[sub.depends for sub in subs])
-        reloads = [sub.reload for sub in subs if getattr(sub, 'reload', None) is not None]
-        if reloads:
-            def reload():          # updateParametersInContext: the inner forces that can read their per-term parameters again
-                for one in reloads:
-                    one()
-                return 'values'
-            entry.reload = reload
-
     def collective_variable_values(self, force):
         """CustomCVForce.getCollectiveVariableValues(context): the energies of the inner forces at the current positions."""
-        hits = [e for e in self.entries if e.force is force]
-        if not hits:
-            raise mm.OpenMMException('getCollectiveVariableValues: the force does not belong to this Context')
-        cv = getattr(hits[0], 'cv', None)
+        cv = TR.entry_of(self, force, None, 'getCollectiveVariableValues').cv
         if cv is None:
             raise NotImplementedError('getCollectiveVariableValues of a CustomCVForce over a CustomNonbondedForce (the pattern of '
                                       'AlchemicalRespaSystem runs as a scaled pair force: its collective variable is never formed)')
         values = self.ctx.cv_values(cv['id'], self.x, len(cv['names']))
         self._check()
         return tuple(float(v) for v in values)
-
-    def _translate_lj_virial(self, force, entry):
-        """ComputingSystem's dispersion virial (systems.py:893-897): a CustomNonbondedForce with the cutoff, switch and
-        long-range-correction settings imported from the NonbondedForce."""
-        n = self.n
-        if force.getNumInteractionGroups() > 0 or getattr(force, '_offset_parameters', []):
-            raise NotImplementedError('virial force with interaction groups or parameter offsets')
-        p = np.array(force._particles, dtype=np.float64).reshape(n, -1)[:, :3]
-        rc = force._cutoff
-        rswitch = force._switch if force.getUseSwitchingFunction() else None
-        excl = np.array(force._exclusions, dtype=np.int32).reshape(-1, 2)
-        desc = B.pair_desc(B.LJ_VIRIAL, rc, rswitch=rswitch or 0.0, flags=B.SWITCH if rswitch is not None else 0)
-        entry.pair_ids.append(self._pair_create(desc, p[:, 0], p[:, 1], p[:, 2], excl))
-        if force.getUseLongRangeCorrection():
-            virial = custom_long_range_correction(
-                lambda r, s, e: 24.0 * e * (2.0 * (s / r) ** 12 - (s / r) ** 6), p[:, 1], p[:, 2], self._box_ref, rc, rswitch)
-            entry.constant = virial
-            entry.rescale = lambda: setattr(entry, 'constant', self._vscale * virial)
-
-    def _translate_softcore(self, force, entry, d):
-        """SolvationSystem's softcore CustomNonbondedForce (systems.py:266-272): one interaction group solute x
-        solvent, cutoff / built-in switch / long-range correction imported from the NonbondedForce
-        (forces.py:284-291), lambda_vdw a global parameter."""
-        n = self.n
-        if force.getNumInteractionGroups() != 1:
-            raise NotImplementedError('softcore force: exactly one interaction group is supported')
-        set1, set2 = force._groups[0]
-        if set1 & set2:
-            raise NotImplementedError('softcore force: overlapping interaction-group sets')
-        names = list(getattr(force, '_offset_parameters', []))
-        allp = np.array(force._particles, dtype=np.float64).reshape(n, -1)
-        if allp.shape[1] == 2:                         # per-particle (sigma, epsilon) only: AlchemicalSoftcoreCVForce
-            allp = np.concatenate([np.zeros((n, 1)), allp], axis=1)
-        base = allp[:, :3]
-        scales = np.stack([allp[:, 3 * (k + 1):3 * (k + 2)] for k in range(len(names))]) if names else np.zeros((0, n, 3))
-        codes = np.zeros(n)
-        codes[sorted(set1)] = 1.0
-        codes[sorted(set2)] = 2.0
-        lam_name = d['lambda_name']
-        if 'lambda_value' in d:                        # a constant written into the expression, not a Context parameter
-            lam_name = '__softcore_lambda_%d' % len(self.entries)
-            self.parameters[lam_name] = float(d['lambda_value'])
-        rc = force._cutoff
-        rswitch = force._switch if force.getUseSwitchingFunction() else None
-        excl = np.array(force._exclusions, dtype=np.int32).reshape(-1, 2)
-        eff = self._effective(base, scales, names, self.parameters)
-        scale_name = d.get('scale_name')
-        desc = B.pair_desc(B.SOFTCORE, rc, rswitch=rswitch or 0.0, alpha=self.parameters[lam_name],
-                           flags=B.SWITCH if rswitch is not None else 0, Kc=1.0,
-                           sign=self.parameters[scale_name] if scale_name else 1.0)
-        pid = self._pair_create(desc, codes, eff[:, 1], eff[:, 2], excl)
-        entry.pair_ids.append(pid)
-        use_lrc = force.getUseLongRangeCorrection()
-
-        class_pairs = {}        # the (sigma, eps) classes depend on the offset parameters only, not on lambda
-
-        def classes_of(parameters):
-            key = tuple(parameters[name] for name in names)
-            if key not in class_pairs:
-                p = self._effective(base, scales, names, parameters)
-                class_pairs.clear()
-                class_pairs[key] = [lrc_class_pairs(p[:, 1], p[:, 2], codes), p[:, 1], p[:, 2], None]
-            return class_pairs[key]
-
-        def quadrature(parameters, lam_value):
-            record = classes_of(parameters)
-            return record, softcore_long_range_correction(record[1], record[2], codes, self._box_ref, rc, rswitch, lam_value, record[0])
-
-        def on_unit_interval(parameters):
-            """The correction as a function of lambda on [0, 1] (it is analytic there): a Chebyshev interpolant through 24 of
-            the quadrature's values, made once per set of offset parameters -- an AFED step asks for the correction and
-            its lambda-derivative some twenty times, at 0.4 ms of host quadrature each otherwise."""
-            record = classes_of(parameters)
-            if record[3] is None:
-                series = np.polynomial.Chebyshev.interpolate(
-                    lambda nodes: np.array([quadrature(parameters, float(x))[1] for x in nodes]), 23, domain=[0.0, 1.0])
-                record[3] = (series, series.deriv())
-            return record[3]
-
-        def constant(parameters):
-            if not use_lrc:
-                return 0.0
-            lam_value = parameters[lam_name]
-            if 0.0 <= lam_value <= 1.0:
-                value = float(on_unit_interval(parameters)[0](lam_value))
-            else:
-                value = quadrature(parameters, lam_value)[1]
-            return self._vscale * value * (parameters[scale_name] if scale_name else 1.0)
-
-        def constant_derivative(parameters):
-            """d(correction)/d(lambda)"""
-            if not use_lrc:
-                return 0.0
-            lam_value = parameters[lam_name]
-            if 0.0 <= lam_value <= 1.0:
-                value = float(on_unit_interval(parameters)[1](lam_value))
-            else:
-                h = 1e-6
-                value = (quadrature(parameters, lam_value + h)[1] - quadrature(parameters, lam_value - h)[1]) / (2 * h)
-            return self._vscale * value * (parameters[scale_name] if scale_name else 1.0)
-
-        def derivative_polynomial(parameters):
-            """d(correction)/d(lambda) on [0, 1] as monomial coefficients in u = 2 lambda - 1 (lowest first), for the evaluation on
-            the device while lambda lives there (amm_expr_eval_scalar: Horner) -- the interpolant's derivative, as constant_derivative."""
-            if not use_lrc:
-                return []
-            record = classes_of(parameters)
-            if len(record) < 5:          # (made once per set of offset parameters, like the interpolant)
-                cheb = np.array(on_unit_interval(parameters)[1].coef, dtype=np.float64)
-                # (the trailing Chebyshev terms of an analytic function are below rounding: |T_k| <= 1 bounds what is dropped)
-                keep = len(cheb)
-                while keep > 1 and np.abs(cheb[keep - 1:]).sum() < 1e-15 * np.abs(cheb).max():
-                    keep -= 1
-                record.append([float(c) for c in np.polynomial.chebyshev.cheb2poly(cheb[:keep])])
-            scale = self._vscale * (parameters[scale_name] if scale_name else 1.0)
-            return record[4] if scale == 1.0 else [c * scale for c in record[4]]
-
-        entry.constant = constant(self.parameters)
-        entry.rescale = lambda: setattr(entry, 'constant', constant(self.parameters))
-        lam = set(names) | {lam_name} | ({scale_name} if scale_name else set())
-        entry.softcore = dict(pid=pid, lambda_name=lam_name, constant=constant, constant_derivative=constant_derivative, depends=lam,
-                              use_lrc=bool(use_lrc), derivative_polynomial=derivative_polynomial)
-
-        def update(parameters, changed):
-            if not (lam & changed):
-                return False
-            if set(names) & changed:
-                p = self._effective(base, scales, names, parameters)
-                self.ctx.pair_set_params(pid, codes, p[:, 1], p[:, 2])
-            self.ctx.pair_set_lambda(pid, parameters[lam_name])
-            if scale_name:
-                self.ctx.pair_set_scale(pid, parameters[scale_name])
-            entry.constant = constant(parameters)
-            return 'values'            # no bond-list terms changed: group definitions stay
-        entry.update = update
-        entry.depends = set(lam)
-
-    # (class, kind, variables, per-term names: count / name getters, rows attribute, atoms per term, what OpenMM calls a term)
-    _TERM_CLASSES = (('CustomBondForce', B.TERM_BOND, ('r',), 'PerBond', '_bonds', 2, 'bonds'),
-                     ('CustomAngleForce', B.TERM_ANGLE, ('theta',), 'PerAngle', '_angles', 3, 'angles'),
-                     ('CustomTorsionForce', B.TERM_TORSION, ('theta',), 'PerTorsion', '_torsions', 4, 'torsions'),
-                     ('CustomExternalForce', B.TERM_EXTERNAL, ('x', 'y', 'z'), 'PerParticle', '_particles', 1, 'particles'))
-
-    def _translate_term_expression(self, force, entry):
-        """A CustomBondForce / CustomAngleForce / CustomTorsionForce / CustomExternalForce whose energy text is none of the hand-written
-        kinds: compiled here (expr.compile_term) and interpreted per term, with its derivative in the term's variable, by the
-        term-expression kernels (csrc/term_expr.hip).  A force object of its own: no bond-list terms to merge into the group's set."""
-        cls, kind, variables, per, attr, arity, what = [c for c in self._TERM_CLASSES if isinstance(force, getattr(mm, c[0]))][0]
-        text = force.getEnergyFunction()
-        generic = '%s: energy expression not recognised as one of the hand-written kinds (%s); the generic term-expression kernel ' % (
-            cls, text.split(';')[0])
-        if getattr(force, '_derivs', None):
-            raise NotImplementedError(generic + 'differentiates in %s only: no addEnergyParameterDerivative' % ', '.join(variables))
-        if self.world > 1:
-            raise NotImplementedError(generic + 'runs on a single rank')
-        periodic = bool(kind != B.TERM_EXTERNAL and force.usesPeriodicBoundaryConditions())
-        if periodic and self.free_space:
-            raise InputError('%s uses periodic boundary conditions in a System in free space' % cls)
-        names = [getattr(force, 'get%sParameterName' % per)(k) for k in range(getattr(force, 'getNum%sParameters' % per)())]
-        gnames = [force.getGlobalParameterName(k) for k in range(force.getNumGlobalParameters())]
-        try:
-            prog = X.compile_term(text, variables, names, gnames)
-        except X.ExpressionError as exc:
-            raise InputError('%s: energy expression not recognised by the HIP path as one of the hand-written kinds, and not a term '
-                             'expression the generic kernel can run: %s' % (cls, exc))
-
-        def tables():
-            rows = getattr(force, attr)
-            idx = np.full((len(rows), 4), -1, dtype=np.int32)
-            par = np.zeros((len(names), len(rows)), dtype=np.float64)
-            for t, row in enumerate(rows):
-                if len(row[arity]) != len(names):
-                    raise mm.OpenMMException('%s: every one of the %s needs %d parameters' % (cls, what, len(names)))
-                idx[t, :arity] = row[:arity]
-                par[:, t] = row[arity]
-            if len(rows) and (idx[:, :arity].min() < 0 or idx[:, :arity].max() >= self.n):
-                raise mm.OpenMMException('%s: a particle index is out of range' % cls)
-            return idx, par
-
-        idx, par = tables()
-        tid = self.ctx.term_expr_create(kind, prog.code, prog.consts, [self.parameters[g] for g in prog.globals_], idx, par,
-                                        periodic=periodic)
-        entry.term_ids.append(tid)
-        entry.term_expr = True
-        entry.program = prog
-
-        def reload():          # updateParametersInContext: the per-term parameters are read again
-            fresh_idx, fresh = tables()
-            if len(fresh_idx) != len(idx):
-                raise mm.OpenMMException('updateParametersInContext: the number of %s has changed' % what)
-            if not np.array_equal(fresh_idx, idx):
-                raise mm.OpenMMException('updateParametersInContext: the particles of the %s have changed' % what)
-            self.ctx.term_expr_set_params(tid, fresh, len(idx))
-            return 'values'
-        entry.reload = reload
-        if prog.globals_:
-            depends = set(prog.globals_)
-
-            def update(parameters, changed):
-                if not (depends & changed):
-                    return False
-                self.ctx.term_expr_set_globals(tid, [parameters[g] for g in prog.globals_])
-                return 'values'
-            entry.update = update
-            entry.depends = depends
-
-    RB_TEXT = 'c0 + cp*(c1 + cp*(c2 + cp*(c3 + cp*(c4 + cp*c5)))); cp = -cos(theta)'
-
-    def _translate_rb(self, force, entry):
-        """An RBTorsionForce: sum_n c_n cos(psi)^n with cos(psi) = -cos(phi), lowered to the torsion text RB_TEXT with the six
-        per-torsion parameters c0 .. c5 on the term-expression kernel (_translate_term_expression): no kernel of its own."""
-        if self.world > 1:
-            raise NotImplementedError('RBTorsionForce runs on a single rank')
-        if force.usesPeriodicBoundaryConditions() and self.free_space:
-            raise InputError('RBTorsionForce uses periodic boundary conditions in a System in free space')
-        text = mm.CustomTorsionForce(self.RB_TEXT)
-        for k in range(6):
-            text.addPerTorsionParameter('c%d' % k)
-
-        def restate():
-            rows = [[r[0], r[1], r[2], r[3], list(r[4:])] for r in force._torsions]
-            if any(not 0 <= a < self.n for r in rows for a in r[:4]):
-                raise mm.OpenMMException('RBTorsionForce: a particle index is out of range')
-            text._torsions = rows
-            text.setUsesPeriodicBoundaryConditions(force.usesPeriodicBoundaryConditions())
-        restate()
-        self._translate_term_expression(text, entry)
-        upload = entry.reload
-
-        def reload():          # updateParametersInContext: the coefficients are read again
-            restate()
-            return upload()
-        entry.reload = reload
-
-    def _translate_cmap(self, force, entry):
-        """A CMAPTorsionForce: every map as the 16 coefficients per cell of tables.cmap_coefficients, every torsion as a map index and
-        eight atoms, evaluated with one lane per torsion by the CMAP kernels (csrc/cmap.hip).  One backend force carried in
-        entry.term_ids, so every loop over an entry's forces reaches it and the scheduler's fusion rules decline its group, as they
-        do for a term-expression force."""
-        cls = 'CMAPTorsionForce'
-        if self.world > 1:
-            raise NotImplementedError('%s runs on a single rank' % cls)
-        periodic = bool(force.usesPeriodicBoundaryConditions())
-        if periodic and self.free_space:
-            raise InputError('%s uses periodic boundary conditions in a System in free space' % cls)
-
-        def tables():
-            sizes = np.array([size for size, _ in force._maps], dtype=np.int32)
-            coeffs = [T.cmap_coefficients(size, energy).reshape(-1) for size, energy in force._maps]
-            coeffs = np.concatenate(coeffs) if coeffs else np.zeros(0)
-            rows = np.array(force._torsions, dtype=np.int32).reshape(-1, 9)
-            if len(rows) and (rows[:, 0].min() < 0 or rows[:, 0].max() >= len(sizes)):
-                raise mm.OpenMMException('%s: a map index is out of range' % cls)
-            if len(rows) and (rows[:, 1:].min() < 0 or rows[:, 1:].max() >= self.n):
-                raise mm.OpenMMException('%s: a particle index is out of range' % cls)
-            return sizes, coeffs, np.ascontiguousarray(rows[:, 0]), np.ascontiguousarray(rows[:, 1:])
-
-        sizes, coeffs, maps, idx = tables()
-        fid = self.ctx.cmap_create(sizes, coeffs, maps, idx, periodic=periodic)
-        entry.term_ids.append(fid)
-        entry.cmap = fid
-
-        def reload():          # updateParametersInContext: the maps' values and the torsions' map indices are read again
-            fresh_sizes, fresh_coeffs, fresh_maps, fresh_idx = tables()
-            if len(fresh_sizes) != len(sizes):
-                raise mm.OpenMMException('updateParametersInContext: the number of maps has changed')
-            if not np.array_equal(fresh_sizes, sizes):
-                raise mm.OpenMMException('updateParametersInContext: the size of a map has changed')
-            if len(fresh_idx) != len(idx):
-                raise mm.OpenMMException('updateParametersInContext: the number of torsions has changed')
-            if not np.array_equal(fresh_idx, idx):
-                raise mm.OpenMMException('updateParametersInContext: the particles of a torsion have changed')
-            self.ctx.cmap_set_params(fid, fresh_coeffs, fresh_maps, len(sizes))
-            return 'values'
-        entry.reload = reload
-
-    _COMPOUND_KINDS = dict(x=B.CVAR_X, y=B.CVAR_Y, z=B.CVAR_Z, distance=B.CVAR_DISTANCE, angle=B.CVAR_ANGLE, dihedral=B.CVAR_DIHEDRAL)
-
-    def _translate_compound(self, force, entry):
-        """A CustomCompoundBondForce or CustomCentroidBondForce: the text compiled with its variable table (expr.compile_compound) and
-        evaluated with one lane per (bond, variable) by the compound-bond kernels (csrc/compound.hip).  One backend force per
-        OpenMM force, carried in entry.term_ids as a term-expression force is, so every loop over an entry's forces reaches it."""
-        cls = force.__class__.__name__
-        centroid = isinstance(force, mm.CustomCentroidBondForce)
-        n_slots = force.getNumGroupsPerBond() if centroid else force.getNumParticlesPerBond()
-        if getattr(force, '_functions', None):
-            raise NotImplementedError('%s: tabulated functions in the energy expression are not supported' % cls)
-        if getattr(force, '_derivs', None):
-            raise NotImplementedError('%s: addEnergyParameterDerivative is not supported (the compound-bond kernel differentiates in '
-                                      'the geometric variables only)' % cls)
-        if self.world > 1:
-            raise NotImplementedError('%s runs on a single rank' % cls)
-        periodic = bool(force.usesPeriodicBoundaryConditions())
-        if periodic and self.free_space:
-            raise InputError('%s uses periodic boundary conditions in a System in free space' % cls)
-        names = [force.getPerBondParameterName(k) for k in range(force.getNumPerBondParameters())]
-        gnames = [force.getGlobalParameterName(k) for k in range(force.getNumGlobalParameters())]
-        try:
-            prog, variables = X.compile_compound(force.getEnergyFunction(), n_slots, 'g' if centroid else 'p', names, gnames)
-        except X.ExpressionError as exc:
-            raise InputError('%s: not an energy expression the compound-bond kernel can run: %s' % (cls, exc))
-        kinds = [self._COMPOUND_KINDS[kind] for kind, _ in variables]
-        slots = [list(s) for _, s in variables]
-
-        def groups():
-            masses = self.system._masses
-            ptr, atoms, weights = [0], [], []
-            for g, (particles, w) in enumerate(force._groups):
-                if not particles:
-                    raise mm.OpenMMException('%s: group %d is empty' % (cls, g))
-                if min(particles) < 0 or max(particles) >= self.n:
-                    raise mm.OpenMMException('%s: a particle index of group %d is out of range' % (cls, g))
-                w = list(w) if len(w) else [float(masses[i]) for i in particles]
-                if not (math.fsum(w) != 0.0 and math.isfinite(math.fsum(w))):
-                    raise mm.OpenMMException('%s: the weights of group %d sum to zero' % (cls, g))
-                atoms += list(particles)
-                weights += w
-                ptr.append(len(atoms))
-            return np.array(ptr, dtype=np.int32), np.array(atoms, dtype=np.int32), np.array(weights, dtype=np.float64)
-
-        def tables(limit):
-            rows = force._bonds
-            idx = np.zeros((len(rows), n_slots), dtype=np.int32)
-            par = np.zeros((len(names), len(rows)), dtype=np.float64)
-            for t, (members, p) in enumerate(rows):
-                if len(p) != len(names):
-                    raise mm.OpenMMException('%s: every bond needs %d parameters' % (cls, len(names)))
-                idx[t] = members
-                par[:, t] = p
-            if len(rows) and (idx.min() < 0 or idx.max() >= limit):
-                raise mm.OpenMMException('%s: a %s index is out of range' % (cls, 'group' if centroid else 'particle'))
-            return idx, par
-
-        grp = groups() if centroid else None
-        idx, par = tables(len(grp[0]) - 1 if centroid else self.n)
-        if centroid and len(grp[0]) == 1:
-            grp = None if not len(idx) else grp          # (no groups and no bonds: a force without terms)
-        fid = self.ctx.compound_create(n_slots, prog.code, prog.consts, [self.parameters[g] for g in prog.globals_], kinds, slots, idx, par,
-                                       periodic=periodic, groups=grp)
-        entry.term_ids.append(fid)
-        entry.term_expr = True
-        entry.program = prog
-        entry.compound = dict(id=fid, variables=variables, centroid=centroid)
-
-        def reload():          # updateParametersInContext: per-bond parameters and (centroid bonds) group weights are read again
-            fresh_grp = groups() if centroid else None
-            if centroid and grp is not None:
-                if len(fresh_grp[0]) != len(grp[0]):
-                    raise mm.OpenMMException('updateParametersInContext: the number of groups has changed')
-                if not (np.array_equal(fresh_grp[0], grp[0]) and np.array_equal(fresh_grp[1], grp[1])):
-                    raise mm.OpenMMException('updateParametersInContext: the particles of a group have changed')
-            fresh_idx, fresh = tables(len(fresh_grp[0]) - 1 if centroid else self.n)
-            if len(fresh_idx) != len(idx):
-                raise mm.OpenMMException('updateParametersInContext: the number of bonds has changed')
-            if not np.array_equal(fresh_idx, idx):
-                raise mm.OpenMMException('updateParametersInContext: the %s of a bond have changed' % ('groups' if centroid else 'particles'))
-            self.ctx.compound_set_params(fid, fresh, len(idx))
-            if centroid and grp is not None:
-                self.ctx.compound_set_weights(fid, fresh_grp[2])
-            return 'values'
-        entry.reload = reload
-        if prog.globals_:
-            depends = set(prog.globals_)
-
-            def update(parameters, changed):
-                if not (depends & changed):
-                    return False
-                self.ctx.compound_set_globals(fid, [parameters[g] for g in prog.globals_])
-                return 'values'
-            entry.update = update
-            entry.depends = depends
-
-    def _translate_custom_bond(self, force, entry):
-        if force.getEnergyFunction().replace(' ', '') == '0.5*(K0*(r-r0)^2-Kn*(r-rn)^2)':
-            # difference of two harmonic bonds (RESPASystem.redefine_bond, systems.py:162): +K0 at r0, -Kn at rn
-            idx = np.array([[b[0], b[1]] for b in force._bonds], dtype=np.int32).reshape(-1, 2)
-            par = np.array([b[2] for b in force._bonds], dtype=np.float64).reshape(-1, 4)
-            periodic = force.usesPeriodicBoundaryConditions()
-            entry.terms.append((B.BOND_HARMONIC, idx, par[:, [0, 1]], periodic, None))
-            entry.terms.append((B.BOND_HARMONIC, idx, np.stack([par[:, 2], -par[:, 3]], axis=1), periodic, None))
-            return
-        if force.getEnergyFunction().replace(' ', '') == '-K*r*(r-r0)':
-            # bond-stretching virial of ComputingSystem (systems.py:914): per-bond (r0, K)
-            idx = np.array([[b[0], b[1]] for b in force._bonds], dtype=np.int32).reshape(-1, 2)
-            par = np.array([b[2] for b in force._bonds], dtype=np.float64).reshape(-1, 2)
-            entry.terms.append((B.BOND_VIRIAL_HARMONIC, idx, par, force.usesPeriodicBoundaryConditions(), None))
-            return
-        if getattr(force, '_amm', None) is None:
-            globs = {force.getGlobalParameterName(i): force.getGlobalParameterDefaultValue(i)
-                     for i in range(force.getNumGlobalParameters())}
-            if describe_energy(force.getEnergyFunction(), globs) is None:
-                return self._translate_term_expression(force, entry)
-        d = dict(self._descriptor_of(force))
-        nb_ = force.getNumBonds()
-        idx = np.array([[b[0], b[1]] for b in force._bonds], dtype=np.int32).reshape(-1, 2)
-        allp = np.array([b[2] for b in force._bonds], dtype=np.float64).reshape(nb_, -1)
-        names = list(getattr(force, '_offset_parameters', []))
-        base = allp[:, :3]
-        scales = np.stack([allp[:, 3 * (k + 1):3 * (k + 2)] for k in range(len(names))]) if names else np.zeros((0, nb_, 3))
-        periodic = force.usesPeriodicBoundaryConditions()
-        if d['family'] == 'ljc':
-            kind, desc = B.BOND_LJC, B.pair_desc(B.NONBONDED, 1.0, Kc=d.get('Kc', B.KC))
-        elif d['family'] == 'lj-virial':
-            kind, desc = B.BOND_VIRIAL_LJ, None
-        else:
-            for key in ('rc0', 'rs0', 'Kc'):
-                if d.get(key) is None and key in self.parameters:
-                    d[key] = self.parameters[key]
-            kind, desc = B.BOND_NEAR, self._pair_desc_from(d, d['rc0'])
-
-        scale_name = d.get('scale_name')
-        if scale_name and kind != B.BOND_NEAR:
-            raise NotImplementedError('global scale factor on a bond force of this kind')
-
-        def terms(parameters):
-            dsc = desc
-            if scale_name:      # respa_switch (systems.py:643, 674): the whole energy times a global parameter
-                dsc = self._pair_desc_from(dict(d, sign=d.get('sign', 1.0) * parameters[scale_name]), d['rc0'])
-            return [(kind, idx, self._effective(base, scales, names, parameters), periodic, dsc)]
-
-        entry.terms = terms(self.parameters)
-        if names or scale_name:
-            lam = set(names) | ({scale_name} if scale_name else set())
-
-            def update(parameters, changed):
-                if not (lam & changed):
-                    return False
-                entry.terms = terms(parameters)
-                self._replace_bonded(entry, entry.terms)
-                return True
-            entry.update = update
-            entry.depends = set(lam)
-            # offsets on the charge product only: the energy is linear in them (energies_at_states, as for the pair forces above)
-            entry.charge_offsets_in = {nm for k, nm in enumerate(names) if not np.any(scales[k][:, 1:])}
 
     # ------------------------------------------------------------------------------- state
     def _invalidate_forces(self):
@@ -2539,6 +552,14 @@ class Engine:
 
     def set_velocities(self, arr):
         self.v.copy_(self.torch.as_tensor(arr, device=self.v.device))
+
+    def _forget_groups(self):
+        """Group definitions are stale (an entry's update or reload rebuilt its bond-list terms): drop them and free the merged sets
+        they owned."""
+        for bid in self._group_bonded:
+            self.ctx.bonded_release(bid)
+        del self._group_bonded[:]
+        self._group_defs.clear()
 
     def set_parameter(self, name, value):
         if name not in self.parameters:
@@ -2580,21 +601,17 @@ class Engine:
     def update_force_parameters(self, force):
         """`force.updateParametersInContext(context)`: per-particle (and exception) parameters of an existing force are
         uploaded again -- what AlchemicalRespaSystem.reset_coulomb_scaling_factor relies on (systems.py:806-815)."""
-        hits = [e for e in self.entries if e.force is force]
-        if not hits:
-            raise mm.OpenMMException('updateParametersInContext: the force does not belong to this Context')
-        for entry in hits:
-            reload = getattr(entry, 'reload', None)
-            if reload is None:
-                raise NotImplementedError('updateParametersInContext for ' + type(force).__name__ + ' with this energy expression')
-            result = reload()
-            if result:
-                if result != 'values':
-                    self._forget_groups()
-                self._programs.clear()
-                self._emit_memo.clear()
-                self._segment_memo.clear()
-                self._invalidate_forces()
+        reload = getattr(TR.entry_of(self, force, None, 'updateParametersInContext'), 'reload', None)
+        if reload is None:
+            raise NotImplementedError('updateParametersInContext for ' + type(force).__name__ + ' with this energy expression')
+        result = reload()
+        if result:
+            if result != 'values':
+                self._forget_groups()
+            self._programs.clear()
+            self._emit_memo.clear()
+            self._segment_memo.clear()
+            self._invalidate_forces()
 
     def invalidate_program(self):
         self._programs.clear()
@@ -2828,7 +845,7 @@ class Engine:
             gather = False
         ids = list(pair_ids)
         if terms:
-            merged = self._make_bonded(terms, sliced=reduced)
+            merged = TR.make_bonded(self, terms, sliced=reduced)
             self._group_bonded.append(merged)
             # the first member of a group writes the buffer, the others add to it: an interaction-group force touches a few rows
             # only (it would have to clear the rest first), so the bond lists go first in its group
@@ -2915,7 +932,7 @@ class Engine:
             self.apply_constraints()
             k = 100.0 / max(1e-4, ctol)          # (OpenMM's first strength)
             for _ in range(9):                   # k grows by 10^8 at most: beyond that the restraints swamp fp64 sums of the energy
-                rid = self._make_bonded([(B.BOND_HARMONIC, pairs, np.stack([dist, np.full(len(dist), k)], axis=1), True, None)], sliced=False)
+                rid = TR.make_bonded(self, [(B.BOND_HARMONIC, pairs, np.stack([dist, np.full(len(dist), k)], axis=1), True, None)], sliced=False)
                 try:
                     done = self._minimize_pass(tolerance, max_iterations, reporter, memory, max_step, rid, k,
                                                lambda: self._constraint_errors(d_pairs, d_dist), result)
@@ -3923,18 +1940,7 @@ class Engine:
         * parameter offsets of a NonbondedForce (SolvationSystem's `lambda_coul`, systems.py:289-308): the energy is a
           quadratic form of the charges, so the central difference over a whole unit of lambda is exact; offsets that act
           on sigma / epsilon (`use_softcore=False`, systems.py:309-312) take a small central step instead (O(h^2))."""
-        if any(getattr(entry, 'gb', None) is not None for entry in self.entries):
-            raise NotImplementedError('deriv(energy, %s) through a GBSAOBCForce is not supported: the generalized-Born kernels have no '
-                                      'parameter-derivative evaluation' % name)
-        if any(getattr(entry, 'custom_gb', None) is not None for entry in self.entries):
-            raise NotImplementedError('deriv(energy, %s) through a CustomGBForce is not supported: the custom generalized-Born kernels '
-                                      'have no parameter-derivative evaluation' % name)
-        if any(getattr(entry, 'hbond', None) is not None for entry in self.entries):
-            raise NotImplementedError('deriv(energy, %s) through a CustomHbondForce is not supported: the hydrogen-bond kernel '
-                                      'differentiates in the geometric variables only' % name)
-        if any(getattr(entry, 'many', None) is not None for entry in self.entries):
-            raise NotImplementedError('deriv(energy, %s) through a CustomManyParticleForce is not supported: the many-particle kernel '
-                                      'differentiates in the geometric variables only' % name)
+        TR.refuse_derivative(self, name)
         self._refuse_in_free_space('deriv(energy, %s)' % name)
         if name not in self.parameters:
             raise mm.OpenMMException('deriv(energy, %s): no such Context parameter' % name)

@@ -1408,7 +1408,7 @@ class PeriodicTorsionForce(Force):
 
 class RBTorsionForce(Force):
     """Ryckaert-Bellemans torsions: E = sum_n c_n cos(psi)^n, n = 0 .. 5, with psi = phi - pi and phi the dihedral of
-    PeriodicTorsionForce (so cos(psi) = -cos(phi)).  Lowered to the term-expression kernel (engine.py: _translate_rb)."""
+    PeriodicTorsionForce (so cos(psi) = -cos(phi)).  Lowered to the term-expression kernel (translate/terms.py: translate_rb)."""
 
     def __init__(self):
         Force.__init__(self)

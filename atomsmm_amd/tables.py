@@ -1,6 +1,6 @@
 """Host side of the tabulated functions of a CustomNonbondedForce (openmm.Continuous1DFunction, Discrete1DFunction,
 Discrete2DFunction) on the pair-expression kernel (csrc/pair_expr.hip): the spline solve, the data the device reads,
-the same functions as host callables (the symmetry check of engine.py evaluates the text with them), and the check of the
+the same functions as host callables (the symmetry checks of translate/ evaluate the text with them), and the check of the
 per-particle values that a text passes straight into a discrete function.
 
 A Continuous1DFunction is the natural cubic spline (second derivative 0 at both ends) through its values at equally spaced knots
